@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: GPU-resident rollout + PPO / GRPO update on QuadPole ("quadrotor_env.py").
 
-    python bench.py --gpus N --steps K --warmup W [--config c3|c4|c5] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--config c3|c4|c5] [--scaling weak|strong] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: a rollout of every env of this rank's shard (one persistent kernel:
 actor MLP on the matrix cores + sampling + dynamics + recording) followed by `learn` on that buffer.
@@ -34,6 +34,7 @@ Besides the contract fields the JSON line carries
   roofline.other_configs   (plain `--config c3` runs) BASELINE.json configs[1], [3], [4] -- C2, and C4's / C5's per-GPU shards -- run in the
                     same process after the headline's timed region: value, ms_per_step, steps, env_steps_per_step, dtype, and the
                     dominant kernel's roofline fraction of each (launches untimed in their timed regions; extra steps carry the events).
+  dump_outputs      with --dump-outputs DIR: the directory, number of arrays and bytes written there (see dump_outputs()).
   cpu_baseline      the CPU port of the reference path (oracle/) timed on this box's host cores over bounded samples:
                     all cores (<= 16), exactly 8 cores (sched_setaffinity, comparable with BASELINE.md section 2), and C1 exactly.
 """
@@ -415,6 +416,50 @@ def sustained_mfma_peak(tg, torch, dev, dtype_code, sampler=None):
                     "back to back: the matrix rate the package sustains under its power limit"}
 
 
+DUMP_ENVS = 512                      # envs of the trajectory sample --dump-outputs writes
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, buf, algo, nets):
+    """What the last timed step handed its caller, as DIR/<name>.npy: the rollout (obs / act / rew / mask / len of a fixed, seeded
+    sample of DUMP_ENVS envs in the reference's (env, t, .) layout, env = group * E + episode, plus the rollout's reward / row
+    statistics), the policy's weights after learn() and learn()'s loss statistics.  Rank 0's shard only; the weights are the same
+    on every rank."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    tr = buf.device_traj
+    k = min(tr.n, DUMP_ENVS)
+    idx = np.sort(np.random.default_rng(20240617).choice(tr.n, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(tr.obs.device)
+    T = tr.T
+    arrays = {
+        "traj_env_index": idx.astype(np.float64),
+        "traj_obs": tr.obs[:, :T, :].index_select(2, sel).permute(2, 1, 0).float(),
+        "traj_act": tr.act.index_select(2, sel).permute(2, 1, 0).float(),
+        "traj_rew": tr.rew.index_select(1, sel).t().float(),
+        "traj_mask": tr.mask.index_select(1, sel).t().float(),
+        "traj_len": tr.len.index_select(0, sel).float(),
+        "traj_stats": tr.stats.double(),                    # sum of rewards, episodes, valid env-steps of the whole rollout
+    }
+    for net_name, net in zip(("actor", "critic"), nets):
+        for name, p in net.named_parameters():
+            arrays[f"param_{net_name}.{name}"] = p.detach().float()
+    for key, v in (algo.last_stats or {}).items():
+        try:
+            arrays[f"stats_{key}"] = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            continue
+    total = 0
+    for name, a in arrays.items():
+        a = a.contiguous().cpu().numpy() if torch.is_tensor(a) else a
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_LIMIT_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+    return {"dir": dirname, "files": len(arrays), "bytes": total}
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -448,6 +493,9 @@ def main():
     ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"],
                     help="with --config c3: also run C2 and the C4 / C5 per-GPU shards after the headline's timed region and nest their "
                          "results under roofline.other_configs (auto: when no flag reshapes the workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (a fixed sample of the trajectory, the "
+                         "post-update weights, the loss statistics) as DIR/<name>.npy, float32 / float64, < 64 MB in all")
     ap.add_argument("--check", action="store_true",
                     help="with --gpus N > 1: before the timed run every rank runs the small rank-count cases of tests/dist_product_worker.py "
                          "twice -- as a rank of the N-rank group and alone (a one-rank subgroup) -- and asserts that its trajectory "
@@ -771,6 +819,10 @@ def run_config(args, ctx, secondary=False):
         torch.cuda.synchronize()
         detach_probes()
     gc.enable()
+    dumped = None
+    if args.dump_outputs and not secondary and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, buf, algo, nets)
+        progress(f"outputs of the last timed step: {dumped['files']} arrays, {dumped['bytes'] / 1e6:.1f} MB in {args.dump_outputs}")
     # collectives of the timed region on this rank: count, bytes and stream time per tag
     coll = {}
     for tag, nbytes, a, b in coll_log:
@@ -886,6 +938,7 @@ def run_config(args, ctx, secondary=False):
                        "parallelism": f"env-shard x{world} (whole groups per rank), 1 grad all-reduce per optimizer step"},
             "rollout_only_env_steps_per_s": total_steps / t_roll if t_roll > 0 else None,
             "rollout_ms": 1e3 * t_roll / args.steps,
+            "dump_outputs": dumped,
             "launch_events": None if args.no_launch_events else
                              ({"after_the_timed_region": True, "timed_steps": timed_steps} if secondary else
                               {"every_nth_step": event_every, "timed_steps": timed_steps}),

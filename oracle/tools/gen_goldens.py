@@ -9,6 +9,13 @@ reference's outputs.  No reference source text is stored.
     PYTHONPATH=oracle/tools/gymnasium_standin:/root/reference \
     python oracle/tools/gen_goldens.py
 
+gen_chain_shape_steps ({ppo,grpo}_step_h{128,256}.npz) writes under pinned CPU numerics and
+refuses to run without them: a test compares the oracle with these fixtures at fp32 rounding
+level, in a child process under the same pin (tests/chain_step_worker.py).  Add
+MKL_CBWR=AVX2 ATEN_CPU_CAPABILITY=avx2 ONEDNN_MAX_CPU_ISA=AVX2 to the environment above; those
+four fixtures alone: python -c "import gen_goldens; gen_goldens.gen_chain_shape_steps()" from
+oracle/tools with the same environment.
+
 `gymnasium` is absent from this image; `oracle/tools/gymnasium_standin` supplies
 the tiny surface the reference touches.  Locals of `GRPO.learn` /
 `PPO.learn` (reward-to-go, advantages, loss scalars) are not returned by the
@@ -518,6 +525,11 @@ def _pin(out, prefix, named):
 
 
 def gen_chain_shape_steps():
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from chain_step_worker import PINNED_CPU_ENV
+    missing = {k: v for k, v in PINNED_CPU_ENV.items() if os.environ.get(k) != v}
+    if missing:
+        raise SystemExit(f"gen_chain_shape_steps needs {missing} in the environment (see the module docstring)")
     cfgs = [("ppo", "h256", 20, 4, (256,) * 5, 0.3, 0.999, 3e-4, 400), ("grpo", "h256", 20, 4, (256,) * 5, 0.3, 0.5, 3e-4, 401),
             ("ppo", "h128", 5, 1, (128,) * 4, 0.5, 0.99, 2e-4, 402), ("grpo", "h128", 5, 1, (128,) * 4, 0.5, 0.5, 3e-4, 403)]
     for kind, tag, S, A, hidden, cov, gamma, lr, seed in cfgs:

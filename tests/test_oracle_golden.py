@@ -1,14 +1,20 @@
 """CPU: the oracle restatement against the golden vectors generated from the real
 reference (oracle/tools/gen_goldens.py) and against the reference tests' known answers."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
 
-from conftest import check_pinned, keep_first_step_gradients, load_golden
+from chain_step_worker import PINNED_CPU_ENV
+from conftest import check_pinned, load_golden
 from oracle import envs as E
 from oracle import learner as L
 
 ENVS = ["CartPole", "QuadPole2D", "QuadPole"]
+CHAIN_WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "chain_step_worker.py")
 
 
 @pytest.mark.parametrize("name", ENVS)
@@ -191,38 +197,27 @@ def test_ppo_step_with_gae_and_per_dimension_covariance():
 
 
 @pytest.mark.parametrize("kind,tag,S,A", [("ppo", "h128", 5, 1), ("grpo", "h128", 5, 1), ("ppo", "h256", 20, 4), ("grpo", "h256", 20, 4)])
-def test_learn_at_chain_kernel_shapes(kind, tag, S, A):
+def test_learn_at_chain_kernel_shapes(kind, tag, S, A, tmp_path):
     """learn() at the net shapes the hot learner kernels run (128 x 4, 256 x 5; ~4,000 rows, 2 updates).  The initial
     weights are rebuilt from the fixture's seed (the constructors draw them from torch's CPU generator, as the
-    reference's do) and checked against the fixture's samples before anything else."""
+    reference's do) and checked against the fixture's samples before anything else.  The oracle runs in a fresh child
+    process under the CPU numerics the fixtures were written with (tests/chain_step_worker.py says why)."""
     g = load_golden(f"{kind}_step_{tag}.npz")
-    hidden = tuple(int(h) for h in g["hidden"])
-    torch.manual_seed(int(g["seed"]))
-    pol = L.OraclePolicy(S, A, hidden, cov=float(g["cov"]), critic=kind == "ppo")
-    nets = ("actor", "critic") if kind == "ppo" else ("actor",)
-    named = lambda: [(f"{n}.{k}", p) for n in nets for k, p in getattr(pol, n).named_parameters()]
-    check_pinned(g, "init", named(), atol=0.0, sum_rtol=1e-9)
-    opt = torch.optim.Adam(pol.parameters(), lr=float(g["lr"]))
-    first = keep_first_step_gradients(opt, named)
-    t = lambda k: torch.from_numpy(g[k])
+    path = tmp_path / "step.pt"
+    proc = subprocess.run([sys.executable, CHAIN_WORKER, kind, tag, str(S), str(A), str(path)], capture_output=True, timeout=600,
+                          env=dict(os.environ, **PINNED_CPU_ENV))
+    assert proc.returncode == 0, proc.stderr.decode("utf-8", "replace")[-3000:]
+    r = torch.load(path, weights_only=False)
+    check_pinned(g, "init", list(r["init"].items()), atol=0.0, sum_rtol=1e-9)
     if kind == "ppo":
-        logs = L.ppo_learn(pol, opt, t("obs"), t("act"), t("rew"), t("mask"), epsilon=0.2, gamma=float(g["gamma"]), c1=0.5, kl_coeff=0.5,
-                           entropy_coeff=0.01, updates_per_iter=2)
-        np.testing.assert_allclose([l["total"] for l in logs], g["total_loss"], rtol=1e-5, atol=1e-6)
-        np.testing.assert_allclose([l["critic"] for l in logs], g["critic_loss"], rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose([l["total"] for l in r["logs"]], g["total_loss"], rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose([l["critic"] for l in r["logs"]], g["critic_loss"], rtol=1e-5, atol=1e-6)
     else:
-        old = L.OraclePolicy(S, A, hidden, cov=float(g["cov"]), critic=False)
-        old.load_state_dict(pol.state_dict())
-        gen = torch.Generator().manual_seed(int(g["seed"]))
-        with torch.no_grad():
-            for p_ in old.parameters():
-                p_.add_(float(g["old_policy_perturbation"]) * torch.randn(p_.shape, generator=gen))
-        Js = L.grpo_learn(pol, old, opt, t("obs"), t("act"), t("rew"), t("mask"), epsilon=0.15, gamma=float(g["gamma"]), updates_per_iter=2)
-        np.testing.assert_allclose(Js, g["J"], rtol=2e-4, atol=1e-5)
+        np.testing.assert_allclose(r["J"], g["J"], rtol=2e-4, atol=1e-5)
     # <= 1e-5 (north_star: fp32 within 1e-5); <= 0.5 % of the entries may be Adam-amplified rounding noise (up to 2 lr steps)
-    check_pinned(g, "final", named(), atol=1e-5, outlier_frac=0.005, outlier_atol=4 * float(g["lr"]), sum_rtol=1e-3)
-    check_pinned(g, "firstgrad", list(first.items()), norm_rel=1e-4, atol=1e-8)
-    check_pinned(g, "lastgrad", [(k, p.grad) for k, p in named()], norm_rel=1e-3, atol=1e-7)
+    check_pinned(g, "final", list(r["final"].items()), atol=1e-5, outlier_frac=0.005, outlier_atol=4 * float(g["lr"]), sum_rtol=1e-3)
+    check_pinned(g, "firstgrad", list(r["first"].items()), norm_rel=1e-4, atol=1e-8)
+    check_pinned(g, "lastgrad", list(r["last"].items()), norm_rel=1e-3, atol=1e-7)
 
 
 def test_ppo_minibatch_step():
