@@ -27,6 +27,20 @@ CASES = {
     "grpo_f32": ("grpo", "CartPole", dict(max_steps=32), 5, 1, (128, 128), None, 4, 16, False, 2, None),
 }
 
+# Cases that straddle a kernel-variant threshold, kept out of CASES (bench.py --check walks CASES): E = None means 16 x CUs, so that
+# one rank's 2 x 16 x CUs envs take the fp32 fused rollout's 32-env workgroups while each of two ranks alone would take the 16-env
+# ones -- the shards must still run the one-rank rollout's kernel (DeviceRollout(global_groups=...)) and reproduce it bit for bit
+SHARD_CASES = {
+    "grpo_f32_block_threshold": ("grpo", "CartPole", dict(max_steps=8), 5, 1, (128, 128), None, 2, None, False, 2, None),
+}
+
+
+def case_spec(name):
+    spec = CASES[name] if name in CASES else SHARD_CASES[name]
+    if spec[8] is None:
+        spec = spec[:8] + (16 * torch.cuda.get_device_properties(0).multi_processor_count,) + spec[9:]
+    return spec
+
 
 def local_permutation(m_local, rank, world, device):
     """This rank's minibatch permutation: a function of (rank, world, row count) only, so that a one-rank run can rebuild the
@@ -59,7 +73,7 @@ def run_cases(names, rank, world, group=None, device=None, emulate_world=2, grou
     dev = device if device is not None else torch.device("cuda", 0)
     out = {}
     for name in names:
-        algo_name, env_name, env_kw, S, A, hidden, cdt, G, E, restart, updates, bs = CASES[name]
+        algo_name, env_name, env_kw, S, A, hidden, cdt, G, E, restart, updates, bs = case_spec(name)
         G = G if groups is None else int(groups)
         torch.manual_seed(1234)                                   # identical initial weights on every rank
         cls = tg.GaussianActorCritic_NeuralNetwork if algo_name == "ppo" else tg.GaussianActor_NeuralNetwork
@@ -173,7 +187,7 @@ def check_case(one, two, case):
 
 def main():
     rank, world, port, path = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
-    names = sys.argv[5].split(",") if len(sys.argv) > 5 else list(CASES)
+    names = sys.argv[5].split(",") if len(sys.argv) > 5 else list(CASES) + list(SHARD_CASES)
     group = None
     if world > 1:
         import torch.distributed as dist

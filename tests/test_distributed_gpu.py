@@ -44,7 +44,8 @@ def runs(tmp_path_factory):
     return {w: [torch.load(f, weights_only=False) for f in files] for w, files in outs.items()}
 
 
-@pytest.mark.parametrize("case", ["ppo_bf16_full", "ppo_f32_minibatch_equal", "ppo_f32_minibatch_ragged", "grpo_bf16", "grpo_f32"])
+@pytest.mark.parametrize("case", ["ppo_bf16_full", "ppo_f32_minibatch_equal", "ppo_f32_minibatch_ragged", "grpo_bf16", "grpo_f32",
+                                  "grpo_f32_block_threshold"])
 def test_two_ranks_equal_one_rank_on_the_product_path(runs, case):
     """Trajectory shards bit-for-bit, PPO's global moments, optimizer-step counts, both ranks bit-identical to each other, post-step
     weights within 1e-6 (fp32) / the stated bf16 bound of the one-rank run: dist_product_worker.check_case."""

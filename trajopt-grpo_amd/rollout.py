@@ -97,13 +97,16 @@ class DeviceRollout:
     def __init__(self, env, policy, num_groups: int, episodes_per_group: int, restart: bool = False,
                  dtype=torch.float32, device=None, seed: int = 0, group_offset: int = 0,
                  compute_dtype: Optional[torch.dtype] = None, use_graph: Optional[bool] = False,
-                 fused: Optional[bool] = None):
+                 fused: Optional[bool] = None, global_groups: Optional[int] = None):
         self.lib = N.load()
         self.env, self.policy = env, policy
         # a swarm env contributes n_agents bodies per episode, laid out as consecutive env slots of the group
         self.agents = int(getattr(env, "n_agents", 1))
         self.G, self.E = int(num_groups), int(episodes_per_group) * self.agents
         self.n = self.G * self.E
+        # groups of the whole rollout across ranks (this engine holds [group_offset, group_offset + G) of them): kernel variants
+        # are chosen from the global env count, so that a rank's shard runs the same arithmetic as a one-rank rollout
+        self.global_groups = self.G if global_groups is None else int(global_groups)
         self.restart = bool(restart)
         self.device = torch.device(device) if device is not None else policy.device
         if self.device.type != "cuda":
@@ -158,7 +161,8 @@ class DeviceRollout:
         # launch (the parity tests replay both ways and compare bits)
         self.forced_per_step = False
         # 16 / 32: envs per workgroup of the fp32 fused rollout, fixed before the first run() (tests hold both kernels to the same
-        # bar); None: tg_fused_rollout_f32_block_envs decides
+        # bar); None: tg_fused_rollout_f32_block_envs decides from the GLOBAL env count (global_groups x E), so every shard of a
+        # multi-rank rollout uses the kernel -- and the summation order -- of the one-rank rollout
         self.f32_block_envs = None
         self._f32_block_envs = 32
 
@@ -248,8 +252,10 @@ class DeviceRollout:
         lib, tr, st = self.lib, self.traj.native(), N.stream_ptr(self.device)
         if self._frag is None:
             if self._fused_f32:
-                # 16 envs per workgroup while every workgroup still gets a CU of its own (C2's 4,096 envs), else 32
-                self._f32_block_envs = self.f32_block_envs or lib.tg_fused_rollout_f32_block_envs(self.n, int(self.params.agents))
+                # 16 envs per workgroup while every workgroup of the one-rank rollout still gets a CU of its own (C2's 4,096 envs),
+                # else 32: keyed on the global env count, so that the shards of a multi-rank rollout sum the mean in the same order
+                self._f32_block_envs = self.f32_block_envs or lib.tg_fused_rollout_f32_block_envs(self.global_groups * self.E,
+                                                                                                    int(self.params.agents))
                 self._frag = M.RegisterStreamF32(self.policy.actor, self._fused_H, self._f32_block_envs)
             else:
                 self._frag = M.FragmentStream(self.policy.actor, self._fused_H)
@@ -422,7 +428,8 @@ class RolloutManager:
     def engine(self) -> DeviceRollout:
         if self._engine is None:
             self._engine = DeviceRollout(self.env, self.policy, self.local_groups, self.num_episodes_per_worker,
-                                         self.restart, group_offset=self.group_lo, **self._engine_kw)
+                                         self.restart, group_offset=self.group_lo, global_groups=self.num_workers,
+                                         **self._engine_kw)
         return self._engine
 
     def rollout_device(self, initial_states=None, forced_actions=None) -> DeviceTrajectory:
