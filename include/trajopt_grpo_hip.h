@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TG_ABI_VERSION 12
+#define TG_ABI_VERSION 13
 
 enum { TG_OK = 0, TG_ERR_ARG = -1, TG_ERR_HIP = -2, TG_ERR_UNSUPPORTED = -3 };
 
@@ -360,6 +360,26 @@ int  tg_mlp_forward_chain_blocks(void);
 int  tg_mlp_forward_chain_loss(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
                                int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss, void* stream);
 
+/* ---- GRPO's KL penalty to a frozen reference policy (DeepSeekMath GRPO; grpo.py:127-134) ----
+ * The `_ref` variants of the five training heads (tg_surrogate_loss, tg_mlp_forward_chain_loss, tg_mlp_f32_forward_backward,
+ * tg_mlp_f32w_forward_backward, tg_mlp_f32r_forward_backward) take the same arguments plus `ref`.  Per valid actor row, with
+ * lp = the row's log-probability under the current policy and x = d_logp_ref[row] - lp:
+ *   D = exp(x) - x - 1             added to the KL sum (slot 2 of the f64 [4] sums / d_work)
+ *   d loss / d lp += coef (exp(x) - 1)
+ * i.e. loss = surr_coef * sum min(rho A, clip(rho) A) - coef * sum D, and GRPO passes coef = surr_coef * beta.
+ * ref == NULL or coef == 0: the plain entry point's kernel, bit for bit.  Refused: a penalty on a critic (tg_chain_loss.kind != 0,
+ * tg_loss_args.d_value != NULL), a NULL d_logp_ref with a nonzero coef, and a nonzero host kl_coef beside it (slot 2 is the
+ * penalty's; a device d_norm8 / d_coef kl_coef must be 0 too). */
+typedef struct tg_ref_penalty {
+    const float* d_logp_ref;  /* [rows] f32: log pi_ref(a | s) of the same rows the head reads (row-indexed as d_logp_old) */
+    float        coef;        /* d loss / d (sum D) = -coef */
+    int32_t      reserved;    /* 0 */
+} tg_ref_penalty;
+int  tg_surrogate_loss_ref(const tg_loss_args* a, const tg_ref_penalty* ref, void* stream);
+int  tg_mlp_forward_chain_loss_ref(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                                   int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
+                                   const tg_ref_penalty* ref, void* stream);
+
 /* ---- MLP backward-data pass, all hidden layers in one persistent launch ----
  * For Linear(in, H) ReLU [Linear(H, H) ReLU]^(n_hidden_layers-1) Linear(H, out <= 8), H in {128, 256}, 3..6 hidden
  * layers, bf16:
@@ -469,6 +489,9 @@ int  tg_mlp_f32_forward(const float* d_x, int32_t in_pad, const float* d_stream,
 int  tg_mlp_f32_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
                                  int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
                                  const tg_chain_loss* loss, void* stream);
+int  tg_mlp_f32_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
+                                     int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
+                                     const tg_chain_loss* loss, const tg_ref_penalty* ref, void* stream);   /* (tg_ref_penalty above) */
 /* The same passes at H = 256 (the reference's QuadPole factory at its own precision: pipelines/quadpole_pipeline_ppo.py:54-58,
  * 20-256x5-{4,1} fp32), csrc/mlp_f32_wide.hip: a wave owns 16 rows on v_mfma_f32_16x16x4_f32, two 4-wave workgroups per CU.
  *   d_stream  f32, tg_mlp_f32w_stream_floats(n_hidden_layers) floats, in 16-KiB blocks of 16 pieces x 64 lanes x 16 B, lane = (i = lane & 15,
@@ -485,6 +508,9 @@ int  tg_mlp_f32w_forward(const float* d_x, int32_t in_pad, const float* d_stream
                          float* d_out, void* stream);
 int  tg_mlp_f32w_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
                                   int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss, void* stream);
+int  tg_mlp_f32w_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
+                                      int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss,
+                                      const tg_ref_penalty* ref, void* stream);
 /* The H = 128 net with at most ONE H x H layer (BASELINE configs[1], C2: 5-128-128-1, pipelines/cartpole_pipeline_grpo.py:54-76) on the
  * same 16-row machine with its whole weight stream resident in LDS (csrc/mlp_f32_wide.hip, mlp_f32_res_kernel): 12 waves per CU (16 without gradients), no
  * barrier in the row loop, rows dealt 16 at a time wave-major across the CUs (C2's ~176,000 rows are 10.78 wave-rounds per SIMD: 11
@@ -504,6 +530,9 @@ int  tg_mlp_f32r_forward(const float* d_x, int32_t in_pad, const float* d_stream
 int  tg_mlp_f32r_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table, int32_t hidden,
                                   int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
                                   const tg_chain_loss* loss, void* stream);
+int  tg_mlp_f32r_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table,
+                                      int32_t hidden, int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_dz,
+                                      void* d_top_maskbits, const tg_chain_loss* loss, const tg_ref_penalty* ref, void* stream);
 enum { TG_F32DW_MM = 0, TG_F32DW_HEAD = 1 };
 typedef struct tg_f32_dw_job {
     const float* d_p;

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TG_NATIVE_LIB: another build of the same library (probe builds with different compile-time flags, tools/mall_probe.py)
 LIB_PATH = os.environ.get("TG_NATIVE_LIB") or os.path.join(_HERE, "libtrajopt_grpo_hip.so")
-ABI_VERSION = 12                     # TG_ABI_VERSION of include/trajopt_grpo_hip.h this binding was written for
+ABI_VERSION = 13                     # TG_ABI_VERSION of include/trajopt_grpo_hip.h this binding was written for
 
 TG_ENV_CARTPOLE, TG_ENV_QUADPOLE2D, TG_ENV_QUADPOLE, TG_ENV_QUADROTOR12, TG_ENV_PENDULUM = 0, 1, 2, 3, 4
 TG_F32, TG_F64 = 0, 1
@@ -97,6 +97,11 @@ class ChainLoss(C.Structure):
                 ("critic_coef", C.c_float), ("kl_coef", C.c_float), ("d_dout8", C.c_void_p), ("d_head_slabs", C.c_void_p),
                 ("d_work", C.c_void_p), ("d_bias_partial", C.c_void_p), ("d_logp_old_out", C.c_void_p), ("d_norm8", C.c_void_p)]
 
+class RefPenalty(C.Structure):
+    """tg_ref_penalty (include/trajopt_grpo_hip.h): GRPO's KL penalty to a frozen reference policy, for the `_ref` entry points."""
+    _fields_ = [("d_logp_ref", C.c_void_p), ("coef", C.c_float), ("reserved", C.c_int32)]
+
+
 class CompactArgs(C.Structure):
     """tg_compact_args (include/trajopt_grpo_hip.h)."""
     _fields_ = [("d_mask", C.c_void_p), ("d_offsets", C.c_void_p), ("n", C.c_int64), ("T", C.c_int32), ("S", C.c_int32), ("A", C.c_int32),
@@ -140,6 +145,7 @@ SIGNATURES = {
     "tg_gaussian_logp": (C.c_int, [_VP, _I64, _VP, _I64, _I64, _P(_F), C.c_int, _VP, _I64, _VP]),
     "tg_loss_work_blocks": (C.c_int, []),
     "tg_surrogate_loss": (C.c_int, [_P(LossArgs), _VP]),
+    "tg_surrogate_loss_ref": (C.c_int, [_P(LossArgs), _P(RefPenalty), _VP]),
     "tg_relu_bwd_bias_blocks": (C.c_int, []),
     "tg_relu_bwd_bias": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "tg_head_bwd_relu_bias": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
@@ -159,17 +165,23 @@ SIGNATURES = {
     "tg_mlp_forward_chain_blocks": (C.c_int, []),
     "tg_mlp_forward_chain_loss": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                             C.POINTER(ChainLoss), _VP]),
+    "tg_mlp_forward_chain_loss_ref": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                C.POINTER(ChainLoss), _P(RefPenalty), _VP]),
     "tg_mlp_f32_stream_floats": (C.c_int64, [_I32, _I32, _I32]),
     "tg_mlp_f32_blocks": (C.c_int, []),
     "tg_mlp_f32_forward": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, _VP, _VP]),
     "tg_mlp_f32_forward_backward": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP,
                                               C.POINTER(ChainLoss), _VP]),
+    "tg_mlp_f32_forward_backward_ref": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP,
+                                                  C.POINTER(ChainLoss), _P(RefPenalty), _VP]),
     "tg_mlp_f32w_stream_floats": (C.c_int64, [_I32]),
     "tg_mlp_f32w_table_floats": (C.c_int64, []),
     "tg_mlp_f32w_blocks": (C.c_int, []),
     "tg_mlp_f32w_forward": (C.c_int, [_VP, _I32, _VP, _VP, _I32, _I64, _VP, _VP]),
     "tg_mlp_f32w_forward_backward": (C.c_int, [_VP, _I32, _VP, _VP, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                C.POINTER(ChainLoss), _VP]),
+    "tg_mlp_f32w_forward_backward_ref": (C.c_int, [_VP, _I32, _VP, _VP, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                   C.POINTER(ChainLoss), _P(RefPenalty), _VP]),
     "tg_mlp_f32r_supported": (C.c_int, [_I32, _I32, _I32]),
     "tg_mlp_f32r_stream_floats": (C.c_int64, [_I32, _I32]),
     "tg_mlp_f32r_w0_floats": (C.c_int64, [_I32, _I32]),
@@ -178,6 +190,8 @@ SIGNATURES = {
     "tg_mlp_f32r_forward": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _I32, _I32, _I32, _I64, _VP, _VP]),
     "tg_mlp_f32r_forward_backward": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP,
                                                C.POINTER(ChainLoss), _VP]),
+    "tg_mlp_f32r_forward_backward_ref": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                   _VP, C.POINTER(ChainLoss), _P(RefPenalty), _VP]),
     "tg_mlp_f32_weight_grad_workspace": (C.c_int64, [_I32]),
     "tg_mlp_f32_weight_grad": (C.c_int, [_I32, C.POINTER(F32DwJob), _I32, _I64, _VP, _I64, _VP, _I32, _VP, _VP]),
     "tg_mlp_f32_weight_grad_adam": (C.c_int, [_I32, C.POINTER(F32DwJob), _I32, _I64, _VP, _I64, _VP, _I32, _VP, C.POINTER(AdamRider), _VP]),

@@ -28,6 +28,7 @@ from . import distributed as D
 from . import hip_ops as K
 from . import mlp as M
 from . import optim as O
+from . import policies as P
 from .rollout import DeviceTrajectory
 
 
@@ -454,8 +455,9 @@ class _GpuLearner(Algorithm):
             cache[name] = t = torch.empty(numel, dtype=dtype, device=device)
         return t
 
-    def _logp_nograd(self, actor, xin, act, var):
-        out = torch.empty(xin.shape[0], dtype=torch.float32, device=xin.device)
+    def _logp_nograd(self, actor, xin, act, var, out=None):
+        if out is None:
+            out = torch.empty(xin.shape[0], dtype=torch.float32, device=xin.device)
         for lo in range(0, xin.shape[0], self.chunk_rows):
             hi = min(lo + self.chunk_rows, xin.shape[0])
             mean = self._forward(actor, xin[lo:hi], view=True)
@@ -463,24 +465,60 @@ class _GpuLearner(Algorithm):
         return out
 
 
+def _check_ref_model(ref_model, policy):
+    """GRPO's reference policy: one of the project's Gaussian policies, on the policy's device, with the policy's input and output
+    widths (its hidden shape is its own)."""
+    if ref_model is None:
+        return None
+    if not isinstance(ref_model, (P.GaussianActor_NeuralNetwork, P.GaussianActorCritic_NeuralNetwork)):
+        raise ValueError(f"ref_model must be a GaussianActor_NeuralNetwork or GaussianActorCritic_NeuralNetwork, got {type(ref_model).__name__}")
+    def widths(net):
+        lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
+        return lin[0].in_features, lin[-1].out_features
+    if widths(ref_model.actor) != widths(policy.actor):
+        raise ValueError(f"ref_model's actor maps {widths(ref_model.actor)[0]} -> {widths(ref_model.actor)[1]}, the policy's "
+                         f"{widths(policy.actor)[0]} -> {widths(policy.actor)[1]}: the widths must agree")
+    d_ref, d_pol = next(ref_model.actor.parameters()).device, next(policy.actor.parameters()).device
+    if d_ref != d_pol:
+        raise ValueError(f"ref_model is on {d_ref}, the policy on {d_pol}: the reference pass runs on the policy's device")
+    return ref_model
+
+
 class GRPO(_GpuLearner):
-    """Group Relative Policy Optimization.  algorithms/grpo.py:12-169."""
+    """Group Relative Policy Optimization.  algorithms/grpo.py:12-169.
+
+    ref_model (with beta != 0): the KL penalty to a frozen reference policy of DeepSeekMath's GRPO, as grpo.py:127-134 means it
+    ("GRPO ref_model").  Per valid row, x = log pi_ref(a|s) - log pi(a|s) with each policy's own variance and
+    D = exp(x) - x - 1; J = (sum min(rho A, clip(rho) A) - beta sum D) / G.  log pi_ref is computed once per learn() (no grad) on the
+    same compacted rows the updates read; last_stats gains "kl_ref" (the mean D of each update).  Only valid rows count (the
+    reference evaluates the reference policy on all rows: that form cannot be combined with the masked surrogate).  The sign is the
+    reference's: with the default maximize=False (descent on J as grpo.py writes it) the beta term pushes the policy AWAY from the
+    reference policy -- pass maximize=True for a penalty that keeps it close.  ref_model=None or beta == 0: no reference pass, the
+    plain kernels, bit-identical to a GRPO without ref_model."""
 
     def __init__(self, epsilon: float, beta: float, gamma: float, policy, optimizer, ref_model=None,
                  updates_per_iter: int = 10, *, maximize: bool = False, chunk_rows=None, autocast_dtype=None,
                  process_group=None, fused_mlp: bool = True):
         self.epsilon, self.beta, self.gamma = epsilon, beta, gamma
-        self.ref_model = ref_model
+        self.ref_model = _check_ref_model(ref_model, policy)
         self.updates_per_iter = updates_per_iter
         self.maximize = maximize
         self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp)
         self.old_policy = copy.deepcopy(self.policy)                        # grpo.py:48
         self._old_synced = self._actor_keys()
 
+    def _ref_input(self, ref_actor, xin, in_dim, cap):
+        """The reference actor's input rows: the policy's prepared `xin` itself when the reference net takes the same padded layout,
+        else re-prepared from its first `in_dim` columns (a reference net of another shape / path)."""
+        m = self._mlp(ref_actor)
+        if m is not None and m.in_pad == xin.shape[1] and m.cd == xin.dtype:
+            return xin                                  # (a ones column at 31 meets zero weights in the forward pass)
+        X = xin[:, :in_dim].float()
+        if m is None:
+            return X
+        return m.prepare_input(X, out=self._ws.get("xin_ref", X.shape[0], m.in_pad, m.cd, X.device, cap))
+
     def _learn(self, buffer) -> None:
-        if self.ref_model is not None:
-            raise NotImplementedError("the reference's ref_model branch mis-unpacks a 3-tuple (grpo.py:129-132) "
-                                      "and never runs in shipped code; it is not reproduced")
         traj = device_trajectory(buffer, self.policy.device)
         var = self.policy.var
         rew = traj.rew if traj.rew.dtype == torch.float32 else traj.rew.float()
@@ -498,7 +536,12 @@ class GRPO(_GpuLearner):
         _, world = D.rank_world(self.process_group)
         G_global = traj.G * world
         coef = (-1.0 if self.maximize else 1.0) / G_global                  # J /= group_size, descent on J
+        # the KL penalty to the reference policy (grpo.py:127-134): d loss / d (sum D) = -coef * beta
+        ref_actor = self.ref_model.actor if (self.ref_model is not None and self.beta != 0 and self.updates_per_iter > 0) else None
+        ref_coef = coef * float(self.beta) if ref_actor is not None else 0.0
         self._entry_refresh(actor)
+        if ref_actor is not None:
+            self._entry_refresh(ref_actor)                                  # (the caller may have refreshed the reference policy)
         self._refresh(self.old_policy.actor)
         _ = self.bucket                                                     # (the gradient windows exist before can_fuse_head() asks)
         # grpo.py:118-119.  When old_policy still IS the policy (the usual case: grpo.py:148 copied it at the end of the last learn()
@@ -522,6 +565,11 @@ class GRPO(_GpuLearner):
         X = xin                                                             # (the loops below only ask for its row count and device)
         old_logp = (self._ws.get("old_logp", X.shape[0], 1, torch.float32, X.device, traj.T * traj.n).view(-1) if fold_old else
                     self._logp_nograd(self.old_policy.actor, xin, act, var))
+        ref_logp = None
+        if ref_actor is not None:                                           # once per learn(): the reference policy is frozen
+            in_dim = next(m for m in ref_actor.network if isinstance(m, torch.nn.Linear)).in_features
+            ref_logp = self._logp_nograd(ref_actor, self._ref_input(ref_actor, xin, in_dim, traj.T * traj.n), act, self.ref_model.var,
+                                         out=self._ws.get("ref_logp", X.shape[0], 1, torch.float32, X.device, traj.T * traj.n).view(-1))
         for u in range(self.updates_per_iter):
             if u > 0:
                 self._zero_grads()
@@ -534,7 +582,8 @@ class GRPO(_GpuLearner):
                 if fuse:        # loss head + head gradient inside the forward chain (tg_mlp_forward_chain_loss)
                     m_actor.forward_loss(xin[lo:hi], 0, act=act[lo:hi], logp_old=old_logp[lo:hi], adv=adv[lo:hi], var=var,
                                          epsilon=self.epsilon, surr_coef=coef, sums_out=sums,
-                                         logp_old_out=old_logp[lo:hi] if (fold_old and u == 0) else None)
+                                         logp_old_out=old_logp[lo:hi] if (fold_old and u == 0) else None,
+                                         logp_ref=ref_logp[lo:hi] if ref_logp is not None else None, ref_coef=ref_coef)
                     # (asked for right before the launch it rides on: it marks the weight layouts as current)
                     rider = self._adam_rider(actor, last, whole_update=lo == 0 and hi == X.shape[0])
                     m_actor.backward_fused(adam=rider)
@@ -542,7 +591,8 @@ class GRPO(_GpuLearner):
                 else:
                     mean = self._forward(actor, xin[lo:hi], train=True, view=True)     # the loss kernel takes a row stride
                     _, s, g_mean, _ = K.surrogate_loss(mean.detach(), None, act[lo:hi], old_logp[lo:hi], adv[lo:hi], None,
-                                                       None, None, var, self.epsilon, coef, 0.0, 0.0, want_total=False)
+                                                       None, None, var, self.epsilon, coef, 0.0, 0.0, want_total=False,
+                                                       logp_ref=ref_logp[lo:hi] if ref_logp is not None else None, ref_coef=ref_coef)
                     self._backward(actor, mean, g_mean)
                 sums += s
             if rider is not None:                                            # (one rank: no all-reduce; the step rode on the reduction)
@@ -555,7 +605,12 @@ class GRPO(_GpuLearner):
         if self.updates_per_iter > 0:
             allJ = all_sums
             D.allreduce_sum_(allJ, self.process_group, "loss_stats")
-            self._stats_pending = lambda: {"J": (allJ[:, 0] / G_global).tolist(), "n_valid": allJ[0, 3].item()}
+            if ref_actor is None:
+                self._stats_pending = lambda: {"J": (allJ[:, 0] / G_global).tolist(), "n_valid": allJ[0, 3].item()}
+            else:                                                           # slot 2: sum D (GRPO's heads have kl_coef = 0)
+                beta = float(self.beta)
+                self._stats_pending = lambda: {"J": ((allJ[:, 0] - beta * allJ[:, 2]) / G_global).tolist(), "n_valid": allJ[0, 3].item(),
+                                               "kl_ref": (allJ[:, 2] / allJ[:, 3].clamp_min(1.0)).tolist()}
 
     def save(self, path: str) -> None:
         torch.save(self.optimizer.state_dict(), os.path.join(path, "optimizer.pth"))   # grpo.py:154

@@ -15,10 +15,12 @@ struct F32Loss {            // (as ChainLoss of mlp_fwd_chain.hip)
     const float* norm8;     // non-null: n_m / n_i and the three coefficients come from this device f32 [8] (tg_ppo_norm's output)
     float* dout4;           // out: d loss / d head output, f32 [rows][4] (columns >= A zero)
     double* work;           // out: f64 [grid][4] partial loss sums (surrogate, squared error, KL, count)
+    // kRef instantiations only (tg_ref_penalty): log pi_ref of the row [rows] and coef * beta; read, never written, by the device
+    const float* logp_ref; float ref_coef;
 };
 
-// host: tg_chain_loss -> F32Loss
-static inline void fill_f32_loss(F32Loss& L, const tg_chain_loss* loss) {
+// host: tg_chain_loss (+ the reference policy's penalty, or null) -> F32Loss
+static inline void fill_f32_loss(F32Loss& L, const tg_chain_loss* loss, const tg_ref_penalty* ref = nullptr) {
     L.kind = loss->kind; L.A = loss->act_dim;
     L.act = loss->kind == 0 ? loss->d_act : loss->d_ret;
     L.logp_old = loss->d_logp_old; L.adv = loss->d_adv; L.logp_old_out = loss->kind == 0 ? loss->d_logp_old_out : nullptr;
@@ -31,6 +33,7 @@ static inline void fill_f32_loss(F32Loss& L, const tg_chain_loss* loss) {
     L.logp_const = -0.5f * (float)loss->act_dim * 1.8378770664093453f - 0.5f * logdet;
     L.epsilon = loss->epsilon; L.surr_coef = loss->surr_coef; L.critic_coef = loss->critic_coef; L.kl_coef = loss->kl_coef;
     L.dout4 = (float*)loss->d_dout8; L.work = loss->d_work;
+    L.logp_ref = ref != nullptr ? ref->d_logp_ref : nullptr; L.ref_coef = ref != nullptr ? ref->coef : 0.f;
 }
 
 // device, at kernel entry: the normalisation pair and the coefficients from the device when PPO keeps them there
@@ -43,32 +46,37 @@ __device__ static inline void f32_loss_from_device(F32Loss& L) {
 }
 
 // The per-row inputs of the loss head, loadable ahead of the row's products (f32_loss_load) ...
-struct F32LossIn { float act[4]; float lpo, adv; };
+struct F32LossIn { float act[4]; float lpo, adv, lref; };
 
 // (every load unconditional within its uniform branch: columns >= A re-read the last action column)
 // row = base + r: `base` wave-uniform (it goes into the scalar part of the address), `r` the lane's part
-template <typename R>
+// kRef: also the row's reference log-probability (GRPO's KL penalty to a frozen reference policy)
+template <bool kRef = false, typename R>
 __device__ static inline F32LossIn f32_loss_load(const F32Loss& L, int64_t base, R r) {
     F32LossIn in;
-    in.act[1] = in.act[2] = in.act[3] = 0.f; in.lpo = 0.f; in.adv = 0.f;
+    in.act[1] = in.act[2] = in.act[3] = 0.f; in.lpo = 0.f; in.adv = 0.f; in.lref = 0.f;
     if (L.kind == 0) {
         const float* act = L.act + base * L.A;
 #pragma unroll
         for (int k = 0; k < 4; ++k) in.act[k] = act[r * L.A + (k < L.A ? k : L.A - 1)];
         if (L.logp_old_out == nullptr) in.lpo = (L.logp_old + base)[r];
         in.adv = (L.adv + base)[r];
+        if constexpr (kRef) in.lref = (L.logp_ref + base)[r];
     } else {
         in.act[0] = (L.act + base)[r];
     }
     return in;
 }
-__device__ static inline F32LossIn f32_loss_load(const F32Loss& L, int64_t rowc) { return f32_loss_load(L, (int64_t)0, rowc); }
+template <bool kRef = false>
+__device__ static inline F32LossIn f32_loss_load(const F32Loss& L, int64_t rowc) { return f32_loss_load<kRef>(L, (int64_t)0, rowc); }
 
 // ... and the arithmetic: head outputs o[4] -> d loss / d output g[4] and the row's contributions to the loss sums.  `row` / `valid` /
 // `writer` decide what is written (one lane per row writes).  kZeroInvalid: a lane past the last row gets g = 0 (mlp_f32_chain.hip);
 // false: it keeps the clamped row's own g -- the 16-row kernels let such lanes recompute and re-store the last row's values
 // (identical bytes), so that every store instruction is issued whatever the row count.
-template <bool kZeroInvalid = true>
+// kRef: GRPO's penalty to the reference policy, x = lp_ref - lp, D = exp(x) - x - 1 (grpo.py:133): D joins the KL sum and
+// d loss / d lp gains ref_coef (exp(x) - 1), ref_coef = coef * beta (the term enters J as - beta D).
+template <bool kZeroInvalid = true, bool kRef = false>
 __device__ static inline void f32_loss_compute(const F32Loss& L, const F32LossIn& in, const float (&o)[4], int64_t row, bool valid, bool writer,
                                                float (&g)[4], float& c_surr, float& c_crit, float& c_kl) {
     g[0] = g[1] = g[2] = g[3] = 0.f;
@@ -102,6 +110,12 @@ __device__ static inline void f32_loss_compute(const F32Loss& L, const F32LossIn
             c_kl = eo * (lpo - lp);
             dlp -= L.kl_coef * eo;
         }
+        if constexpr (kRef) {
+            const float x = in.lref - lp;
+            const float em1 = expf(x) - 1.0f;
+            c_kl += em1 - x;
+            dlp += L.ref_coef * em1;
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) g[k] = dlp * dmu[k] * L.inv_var[k];
     } else {
@@ -115,11 +129,11 @@ __device__ static inline void f32_loss_compute(const F32Loss& L, const F32LossIn
 }
 
 // One row, inputs loaded on the spot (`rowc` = the row clamped into range).
-template <bool kZeroInvalid = true>
+template <bool kZeroInvalid = true, bool kRef = false>
 __device__ static inline void f32_loss_row(const F32Loss& L, const float (&o)[4], int64_t row, int64_t rowc, bool valid, bool writer,
                                            float (&g)[4], float& c_surr, float& c_crit, float& c_kl) {
-    const F32LossIn in = f32_loss_load(L, rowc);
-    f32_loss_compute<kZeroInvalid>(L, in, o, row, valid, writer, g, c_surr, c_crit, c_kl);
+    const F32LossIn in = f32_loss_load<kRef>(L, rowc);
+    f32_loss_compute<kZeroInvalid, kRef>(L, in, o, row, valid, writer, g, c_surr, c_crit, c_kl);
 }
 
 }  // namespace tg

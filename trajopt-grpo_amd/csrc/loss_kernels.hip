@@ -46,9 +46,12 @@ struct LossK {
     Var8 v;
     float epsilon, surr_coef, critic_coef, kl_coef;
     float* grad_mean; float* grad_value; double* work; int64_t M;
+    const float* logp_ref; float ref_coef;      // kRef only (tg_ref_penalty)
 };
 
-template <int A>
+// kRef: GRPO's KL penalty to a frozen reference policy (tg_surrogate_loss_ref): x = lp_ref - lp, D = exp(x) - x - 1 into the KL sum,
+// d total / d logp += ref_coef (exp(x) - 1)
+template <int A, bool kRef = false>
 __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
     __shared__ double sh[4][4];
     double s_surr = 0, s_crit = 0, s_kl = 0, s_cnt = 0;
@@ -57,6 +60,7 @@ __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
     // (locals: writing into the by-value argument struct would send it to scratch)
     float surr_coef = p.surr_coef, critic_coef = p.critic_coef, kl_coef = p.kl_coef;
     if (p.coef != nullptr) { surr_coef = p.coef[0]; critic_coef = p.coef[1]; kl_coef = p.coef[2]; }
+    [[maybe_unused]] const float ref_coef = kRef ? p.ref_coef : 0.0f;
     const float lo = 1.0f - p.epsilon, hi = 1.0f + p.epsilon;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.M; i += (int64_t)gridDim.x * blockDim.x) {
         const bool valid = p.mask == nullptr || p.mask[i] != 0;
@@ -85,6 +89,12 @@ __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
                 const float eo = expf(lpo);
                 s_kl += (double)(eo * (lpo - lp));
                 dlp -= kl_coef * eo;
+            }
+            if constexpr (kRef) {
+                const float x = p.logp_ref[i] - lp;
+                const float em1 = expf(x) - 1.0f;
+                s_kl += (double)(em1 - x);
+                dlp += ref_coef * em1;
             }
 #pragma unroll
             for (int k = 0; k < A; ++k) g[k] = dlp * (a[k] - mu[k]) * p.v.inv_var[k];   // d logp / d mu_k
@@ -183,8 +193,10 @@ int tg_gaussian_logp(const float* d_mean, int64_t mean_row_stride, const float* 
     return TG_OK;
 }
 
-int tg_surrogate_loss(const tg_loss_args* a, void* stream) {
+static int surrogate_loss(const tg_loss_args* a, const tg_ref_penalty* ref, void* stream) {
     TG_REQUIRE(a != nullptr, "tg_surrogate_loss: null args");
+    const int use_ref = ref_penalty_check(ref, a->d_value != nullptr, a->kl_coef, "tg_surrogate_loss_ref");
+    if (use_ref < 0) return use_ref;
     TG_REQUIRE(a->d_mean && a->d_act && a->d_logp_old && a->d_adv && a->d_grad_mean && a->d_sums && a->d_work,
                "tg_surrogate_loss: null pointer");
     TG_REQUIRE((a->d_value == nullptr) == (a->d_ret == nullptr), "tg_surrogate_loss: value and ret go together");
@@ -199,12 +211,14 @@ int tg_surrogate_loss(const tg_loss_args* a, void* stream) {
     k.mask = a->d_mask; k.norm = a->d_norm; k.coef = a->d_coef;
     k.epsilon = a->epsilon; k.surr_coef = a->surr_coef; k.critic_coef = a->critic_coef; k.kl_coef = a->kl_coef;
     k.grad_mean = a->d_grad_mean; k.grad_value = a->d_grad_value; k.work = a->d_work; k.M = a->M;
+    k.logp_ref = use_ref ? ref->d_logp_ref : nullptr; k.ref_coef = use_ref ? ref->coef : 0.0f;
     hipStream_t st = (hipStream_t)stream;
     int64_t nb = ceil_div(a->M > 0 ? a->M : 1, kLossThreads);
     const unsigned grid = (unsigned)(nb < kLossBlocks ? nb : kLossBlocks);
 #define L(AA)                                                                                            \
     case AA:                                                                                             \
-        hipLaunchKernelGGL(surrogate_loss_kernel<AA>, dim3(grid), dim3(kLossThreads), 0, st, k);         \
+        if (use_ref) hipLaunchKernelGGL((surrogate_loss_kernel<AA, true>), dim3(grid), dim3(kLossThreads), 0, st, k); \
+        else hipLaunchKernelGGL(surrogate_loss_kernel<AA>, dim3(grid), dim3(kLossThreads), 0, st, k);   \
         break;
     switch (a->act_dim) { L(1) L(2) L(3) L(4) L(5) L(6) L(7) L(8) }
 #undef L
@@ -213,5 +227,9 @@ int tg_surrogate_loss(const tg_loss_args* a, void* stream) {
     TG_LAUNCH_CHECK("tg_surrogate_loss(final)");
     return TG_OK;
 }
+
+int tg_surrogate_loss(const tg_loss_args* a, void* stream) { return surrogate_loss(a, nullptr, stream); }
+
+int tg_surrogate_loss_ref(const tg_loss_args* a, const tg_ref_penalty* ref, void* stream) { return surrogate_loss(a, ref, stream); }
 
 }  // extern "C"

@@ -86,8 +86,10 @@ TG_CLOCK_PROBE_VAR(g_probe_f32_chain, attach_probe_f32_chain)          // the tr
 TG_CLOCK_PROBE_VAR(g_probe_f32_dw, attach_probe_f32_dw)
 int attach_probe_f32(int which, void* d_probe) { return which == 0 ? attach_probe_f32_chain(d_probe) : attach_probe_f32_dw(d_probe); }
 
-template <int H, bool kTrain>
+// kRef (training only): GRPO's KL penalty to a frozen reference policy in the loss head (f32_loss.hpp)
+template <int H, bool kTrain, bool kRef = false>
 __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
+    static_assert(!kRef || kTrain, "the reference penalty is a term of the training pass");
     constexpr int MT = H / 32;                  // 32-feature tiles per layer
     constexpr int G4 = H / 8;                   // groups of 4 MFMA steps per H x H block
     constexpr int BLK = G4 * 64;                // uint4 per block
@@ -301,7 +303,7 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
         } else {
             // ---- loss head (loss_kernels.hip::surrogate_loss_kernel, same arithmetic), evaluated by both lane halves ----
             float g[4], c_surr, c_crit, c_kl;
-            f32_loss_row(L, o, row, rowc, valid, h == 0, g, c_surr, c_crit, c_kl);
+            f32_loss_row<true, kRef>(L, o, row, rowc, valid, h == 0, g, c_surr, c_crit, c_kl);
             if (valid && h == 0) {
                 s_surr += (double)c_surr; s_crit += (double)c_crit; s_kl += (double)c_kl; s_cnt += 1.0;
                 *reinterpret_cast<float4*>(L.dout4 + row * 4) = float4{g[0], g[1], g[2], g[3]};
@@ -388,9 +390,9 @@ static int f32_chain_grid(int64_t rows) {
     return (int)(n_rounds < cus ? n_rounds : cus);
 }
 
-template <int H, bool kTrain>
+template <int H, bool kTrain, bool kRef = false>
 static int launch_f32_chain(const F32ChainArgs& args_in, hipStream_t st) {
-    auto kern = mlp_f32_chain_kernel<H, kTrain>;
+    auto kern = mlp_f32_chain_kernel<H, kTrain, kRef>;
     F32ChainArgs args = args_in;
     const int n_stream = args.net.n_hh * (H / 32) * (kTrain ? 2 : 1);
     args.resident = n_stream > 0 && f32_chain_lds<H>(args.net.n_hh, args.net.k2, n_stream) <= 160 * 1024;
@@ -1683,10 +1685,13 @@ int tg_mlp_f32_forward(const float* d_x, int32_t in_pad, const float* d_stream, 
     return hidden == 128 ? launch_f32_chain<128, false>(a, st) : launch_f32_chain<64, false>(a, st);
 }
 
-int tg_mlp_f32_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
+static int f32_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
                                 int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits, const tg_chain_loss* loss,
-                                void* stream) {
-    TG_REQUIRE(d_x && d_stream && d_acts && d_dz && loss, "tg_mlp_f32_forward_backward: null pointer");
+                                const tg_ref_penalty* ref, void* stream) {
+    TG_REQUIRE(loss, "tg_mlp_f32_forward_backward: null pointer");
+    const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_f32_forward_backward_ref");
+    if (use_ref < 0) return use_ref;
+    TG_REQUIRE(d_x && d_stream && d_acts && d_dz, "tg_mlp_f32_forward_backward: null pointer");
     TG_REQUIRE(rows > 0, "tg_mlp_f32_forward_backward: no rows");
     TG_REQUIRE(loss->kind == 0 || loss->kind == 1, "tg_mlp_f32_forward_backward: kind %d", loss->kind);
     TG_REQUIRE(loss->act_dim >= 1 && loss->act_dim <= 4, "tg_mlp_f32_forward_backward: %d outputs unsupported (1..4)", loss->act_dim);
@@ -1707,9 +1712,22 @@ int tg_mlp_f32_forward_backward(const float* d_x, int32_t in_pad, const float* d
     }
     a.top_mask = (uint32_t*)d_top_maskbits;
     a.x = d_x; a.rows = rows;
-    fill_f32_loss(a.loss, loss);
+    fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr);
     hipStream_t st = (hipStream_t)stream;
+    if (use_ref) return hidden == 128 ? launch_f32_chain<128, true, true>(a, st) : launch_f32_chain<64, true, true>(a, st);
     return hidden == 128 ? launch_f32_chain<128, true>(a, st) : launch_f32_chain<64, true>(a, st);
+}
+
+int tg_mlp_f32_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
+                                int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits, const tg_chain_loss* loss,
+                                void* stream) {
+    return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, nullptr, stream);
+}
+
+int tg_mlp_f32_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
+                                    int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits, const tg_chain_loss* loss,
+                                    const tg_ref_penalty* ref, void* stream) {
+    return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref, stream);
 }
 
 #if TG_F32DW_STAMPS

@@ -81,8 +81,9 @@ static size_t f32_wide_lds() {
 
 TG_CLOCK_PROBE_VAR(g_probe_f32_wide, attach_probe_f32_wide)
 
-template <bool kTrain>
+template <bool kTrain, bool kRef = false>                                // kRef: GRPO's reference-policy penalty (f32_loss.hpp)
 __global__ __launch_bounds__(256, 2) void mlp_f32_wide_kernel(F32WideArgs a) {
+    static_assert(!kRef || kTrain, "the reference penalty is a term of the training pass");
     constexpr int H = kWideH, NT = H / 16, D = kWideD, P = kWideP, WPW = kWideWaves, KS = kWidePieces;
     extern __shared__ uint4 lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_wide_kernel(F32WideArgs a) {
             if (valid && g == 0) *reinterpret_cast<float4*>(a.out + row * 4) = float4{o[0], o[1], o[2], o[3]};
         } else {
             float gr[4], c_surr, c_crit, c_kl;
-            f32_loss_row<false>(L, o, row, rowc, valid, g == 0, gr, c_surr, c_crit, c_kl);
+            f32_loss_row<false, kRef>(L, o, row, rowc, valid, g == 0, gr, c_surr, c_crit, c_kl);
             if (valid && g == 0) {
                 s_surr += (double)c_surr; s_crit += (double)c_crit; s_kl += (double)c_kl; s_cnt += 1.0;
                 *reinterpret_cast<float4*>(L.dout4 + row * 4) = float4{gr[0], gr[1], gr[2], gr[3]};
@@ -371,9 +372,9 @@ static int f32_wide_grid(int64_t rows) {
     return (int)(n_rounds < slots ? n_rounds : slots);
 }
 
-template <bool kTrain>
+template <bool kTrain, bool kRef = false>
 static int launch_f32_wide(const F32WideArgs& args, hipStream_t st) {
-    auto kern = mlp_f32_wide_kernel<kTrain>;
+    auto kern = mlp_f32_wide_kernel<kTrain, kRef>;
     const size_t shmem = f32_wide_lds();
     static LdsOptIn opt_in;
     if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_f32w_forward")) return rc;
@@ -437,8 +438,9 @@ static size_t f32_res_lds(int n_hh, int in_pad, bool train) {
 
 TG_CLOCK_PROBE_VAR(g_probe_f32_res, attach_probe_f32_res)
 
-template <int H, int K4, bool kTrain>                                    // K4 = padded input width / 4: the first layer's products per tile
-__global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32ResArgs a) {
+template <int H, int K4, bool kTrain, bool kRef = false>                // K4 = padded input width / 4: the first layer's products per tile
+__global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32ResArgs a) {     // kRef: as mlp_f32_wide_kernel's
+    static_assert(!kRef || kTrain, "the reference penalty is a term of the training pass");
     constexpr int NT = H / 16, WPW = res_waves(kTrain), BLK = NT * 64;           // uint4 per block
     extern __shared__ uint4 lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -558,7 +560,7 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
         const bool valid = row < rows;
         const int jr = lane_row(q);
         F32LossIn lin;
-        if constexpr (kTrain) lin = f32_loss_load(L, q * 16, jr);        // (used after both layers: in flight behind them)
+        if constexpr (kTrain) lin = f32_loss_load<kRef>(L, q * 16, jr);  // (used after both layers: in flight behind them)
         f32x4 xin[NT];
         uint32_t mb0 = 0, mb1 = 0;                       // ReLU mask bits of layer 0 / layer 1: tile t -> bits 4 t .. 4 t + 3
         // ---- layer 0 ----
@@ -647,7 +649,7 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
 #if TG_F32R_ABLATE & 8
             gr[0] = o[0] + lin.adv; gr[1] = gr[2] = gr[3] = 0.f; c_surr = c_crit = c_kl = o[0];
 #else
-            f32_loss_compute<false>(L, lin, o, row, valid, g == 0, gr, c_surr, c_crit, c_kl);
+            f32_loss_compute<false, kRef>(L, lin, o, row, valid, g == 0, gr, c_surr, c_crit, c_kl);
 #endif
             if (valid && g == 0) {
                 s_surr += (double)c_surr; s_crit += (double)c_crit; s_kl += (double)c_kl; s_cnt += 1.0;
@@ -731,9 +733,9 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
     }
 }
 
-template <int K4, bool kTrain>
+template <int K4, bool kTrain, bool kRef = false>
 static int launch_f32_res_k(const F32ResArgs& args, hipStream_t st) {
-    auto kern = mlp_f32_res_kernel<128, K4, kTrain>;
+    auto kern = mlp_f32_res_kernel<128, K4, kTrain, kRef>;
     const size_t shmem = f32_res_lds<128>(args.n_hh, args.in_pad, kTrain);
     static LdsOptIn opt_in;
     if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_f32r_forward")) return rc;
@@ -743,13 +745,13 @@ static int launch_f32_res_k(const F32ResArgs& args, hipStream_t st) {
     TG_LAUNCH_CHECK("tg_mlp_f32r_forward");
     return TG_OK;
 }
-template <bool kTrain>
+template <bool kTrain, bool kRef = false>
 static int launch_f32_res(const F32ResArgs& args, hipStream_t st) {
     switch (args.in_pad) {
-        case 8: return launch_f32_res_k<2, kTrain>(args, st);
-        case 16: return launch_f32_res_k<4, kTrain>(args, st);
-        case 24: return launch_f32_res_k<6, kTrain>(args, st);
-        default: return launch_f32_res_k<8, kTrain>(args, st);
+        case 8: return launch_f32_res_k<2, kTrain, kRef>(args, st);
+        case 16: return launch_f32_res_k<4, kTrain, kRef>(args, st);
+        case 24: return launch_f32_res_k<6, kTrain, kRef>(args, st);
+        default: return launch_f32_res_k<8, kTrain, kRef>(args, st);
     }
 }
 
@@ -1067,9 +1069,12 @@ int tg_mlp_f32r_forward(const float* d_x, int32_t in_pad, const float* d_stream,
     return launch_f32_res<false>(a, (hipStream_t)stream);
 }
 
-int tg_mlp_f32r_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table, int32_t hidden,
+static int f32r_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table, int32_t hidden,
                                  int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
-                                 const tg_chain_loss* loss, void* stream) {
+                                 const tg_chain_loss* loss, const tg_ref_penalty* ref, void* stream) {
+    TG_REQUIRE(loss, "tg_mlp_f32r_forward_backward: null pointer");
+    const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_f32r_forward_backward_ref");
+    if (use_ref < 0) return use_ref;
     F32ResArgs a{};
     if (int rc = fill_f32_res(a, d_x, in_pad, d_stream, d_w0, d_table, hidden, n_hidden_layers, rows, "tg_mlp_f32r_forward_backward")) return rc;
     TG_REQUIRE(loss && d_acts && d_dz, "tg_mlp_f32r_forward_backward: null pointer");
@@ -1088,8 +1093,22 @@ int tg_mlp_f32r_forward_backward(const float* d_x, int32_t in_pad, const float* 
         a.dz[l] = (float*)d_dz[l];
     }
     a.top_mask = (uint32_t*)d_top_maskbits;
-    fill_f32_loss(a.loss, loss);
-    return launch_f32_res<true>(a, (hipStream_t)stream);
+    fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr);
+    return use_ref ? launch_f32_res<true, true>(a, (hipStream_t)stream) : launch_f32_res<true>(a, (hipStream_t)stream);
+}
+
+int tg_mlp_f32r_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table, int32_t hidden,
+                                 int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
+                                 const tg_chain_loss* loss, void* stream) {
+    return f32r_forward_backward(d_x, in_pad, d_stream, d_w0, d_table, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, nullptr,
+                                 stream);
+}
+
+int tg_mlp_f32r_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table,
+                                     int32_t hidden, int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_dz,
+                                     void* d_top_maskbits, const tg_chain_loss* loss, const tg_ref_penalty* ref, void* stream) {
+    return f32r_forward_backward(d_x, in_pad, d_stream, d_w0, d_table, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref,
+                                 stream);
 }
 
 int tg_mlp_f32w_blocks(void) { return 2 * device_cus(); }
@@ -1108,8 +1127,12 @@ int tg_mlp_f32w_forward(const float* d_x, int32_t in_pad, const float* d_stream,
     return launch_f32_wide<false>(a, (hipStream_t)stream);
 }
 
-int tg_mlp_f32w_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
-                                 int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss, void* stream) {
+static int f32w_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
+                                 int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss, const tg_ref_penalty* ref,
+                                 void* stream) {
+    TG_REQUIRE(loss, "tg_mlp_f32w_forward_backward: null pointer");
+    const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_f32w_forward_backward_ref");
+    if (use_ref < 0) return use_ref;
     F32WideArgs a{};
     if (int rc = fill_f32_wide(a, d_x, in_pad, d_stream, d_table, n_hidden_layers, rows, "tg_mlp_f32w_forward_backward")) return rc;
     TG_REQUIRE(loss && d_acts && d_dz, "tg_mlp_f32w_forward_backward: null pointer");
@@ -1125,8 +1148,19 @@ int tg_mlp_f32w_forward_backward(const float* d_x, int32_t in_pad, const float* 
         a.acts[l] = (float*)d_acts[l];
         a.dz[l] = (float*)d_dz[l];
     }
-    fill_f32_loss(a.loss, loss);
-    return launch_f32_wide<true>(a, (hipStream_t)stream);
+    fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr);
+    return use_ref ? launch_f32_wide<true, true>(a, (hipStream_t)stream) : launch_f32_wide<true>(a, (hipStream_t)stream);
+}
+
+int tg_mlp_f32w_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
+                                 int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss, void* stream) {
+    return f32w_forward_backward(d_x, in_pad, d_stream, d_table, n_hidden_layers, rows, d_acts, d_dz, loss, nullptr, stream);
+}
+
+int tg_mlp_f32w_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
+                                     int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss, const tg_ref_penalty* ref,
+                                     void* stream) {
+    return f32w_forward_backward(d_x, in_pad, d_stream, d_table, n_hidden_layers, rows, d_acts, d_dz, loss, ref, stream);
 }
 
 }  // extern "C"

@@ -55,6 +55,8 @@ struct ChainLoss {                          // (kept small: every field is a sca
     float* head_slabs;                      // out: f32 [grid][4][16][H] partial head weight gradients
     double* work;                           // out: f64 [grid][4] partial loss sums (surrogate, squared error, KL, count)
     float* bias_partial;                    // out: f32 [grid][4] partial head bias gradients
+    const float* logp_ref; float ref_coef;  // kRef only (tg_ref_penalty): log pi_ref per row [rows] (staged beside the other loss
+                                            // inputs, slot 6 of the wave's tile) and coef * beta
 };
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
@@ -218,12 +220,15 @@ __device__ static inline int wave_of(unsigned tid) { return (int)(tid >> 6); }
 // 16 c + col and 32-feature block, the 8 consecutive features 8 g .. 8 g + 7 -- as accumulators (4 of half f = 0, 4 of f = 1:
 // mlp.FragmentStream arranges the weight rows so), then packed: 16 B that are both the next layer's B operand for k-step =
 // block (natural k order) and a contiguous piece of the activation row.
-template <int H, int WPW, bool kStore, int D, bool kA0, bool kHead = false>
+// kRef (with kHead): GRPO's KL penalty to a frozen reference policy in the loss head (tg_mlp_forward_chain_loss_ref): one more
+// per-row input, one expf per row.
+template <int H, int WPW, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false>
 __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16_t* __restrict__ x, const uint4* __restrict__ wfrag,
                                                                     const float* __restrict__ bias, int32_t n_hh, int64_t rows,
                                                                     ChainActs acts, float* __restrict__ out, int32_t out_cols,
                                                                     ChainLoss L) {
     static_assert(!kHead || (kStore && !kA0), "the fused head belongs to the learner's training pass");
+    static_assert(!kRef || kHead, "the reference penalty is a term of the fused head");
     if constexpr (kHead) {
         if (L.norm8 != nullptr) {                                       // (uniform scalar loads, before anything is in flight)
             const int q = L.kind == 1 ? 2 : 0;
@@ -305,6 +310,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                 // (kind 2 loads the slot it is about to write: never used, but every round issues the same number of DMAs)
                 __builtin_amdgcn_global_load_lds(L.logp_old + r, (lds_void*)(lin + 32 * 4), 4, 0, 0);
                 __builtin_amdgcn_global_load_lds(L.adv + r, (lds_void*)(lin + 32 * 5), 4, 0, 0);
+                if constexpr (kRef) __builtin_amdgcn_global_load_lds(L.logp_ref + r, (lds_void*)(lin + 32 * 6), 4, 0, 0);
             } else {
                 __builtin_amdgcn_global_load_lds(L.act + r, (lds_void*)(lin + 32 * 0), 4, 0, 0);
             }
@@ -482,6 +488,12 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                                     c_kl = eo * (lpo - lp);
                                     dlp -= L.kl_coef * eo;
                                 }
+                                if constexpr (kRef) {          // x = lp_ref - lp, D = exp(x) - x - 1 (f32_loss.hpp: the same arithmetic)
+                                    const float x = lds_loadf(lin + 32 * 6 + rl) - lp;
+                                    const float em1 = expf(x) - 1.0f;
+                                    c_kl += em1 - x;
+                                    dlp += L.ref_coef * em1;
+                                }
 #pragma unroll
                                 for (int k = 0; k < 4; ++k) g[k] = dlp * dmu[k] * L.inv_var[k];
                             } else {
@@ -595,13 +607,13 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     if constexpr (kHead) { TG_CLOCK_PROBE_END(g_probe_fwd_chain) } else { TG_CLOCK_PROBE_END(g_probe_fwd_chain_plain) }
 }
 
-template <int H, bool kStore, int D, bool kA0, bool kHead = false>
+template <int H, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false>
 static int chain_launch(const void* x, const void* wfrag, const float* bias, int n_hh, int64_t rows, const ChainActs& acts, float* out,
                         int out_cols, hipStream_t st, const ChainLoss& loss = ChainLoss{}) {
     constexpr int WPW = 8, KS = H / 16;
     const size_t shmem = (size_t)D * KS * 1024 + (size_t)(n_hh + 2) * H * sizeof(float) + (size_t)WPW * 2048 +
                          (size_t)WPW * 32 * 128 + (kHead ? (size_t)2 * WPW * 1024 + (size_t)WPW * 16 * 48 + (size_t)WPW * (H / 32) * 16 * 16 : 0);
-    auto kern = mlp_fwd_chain_kernel<H, WPW, kStore, D, kA0, kHead>;
+    auto kern = mlp_fwd_chain_kernel<H, WPW, kStore, D, kA0, kHead, kRef>;
     static LdsOptIn opt_in;
     if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_forward_chain")) return rc;
     const int cus = device_cus();
@@ -651,9 +663,13 @@ int tg_mlp_forward_chain(const void* d_x, const void* d_wfrag, const float* d_bi
 
 int tg_mlp_forward_chain_blocks(void) { return device_cus(); }
 
-int tg_mlp_forward_chain_loss(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
-                              int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss, void* stream) {
-    TG_REQUIRE(d_x && d_wfrag && d_bias && d_acts && d_masks && loss, "tg_mlp_forward_chain_loss: null pointer");
+static int forward_chain_loss(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                              int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss, const tg_ref_penalty* ref,
+                              void* stream) {
+    TG_REQUIRE(loss, "tg_mlp_forward_chain_loss: null pointer");
+    const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_forward_chain_loss_ref");
+    if (use_ref < 0) return use_ref;
+    TG_REQUIRE(d_x && d_wfrag && d_bias && d_acts && d_masks, "tg_mlp_forward_chain_loss: null pointer");
     TG_REQUIRE(hidden == 128 || hidden == 256, "tg_mlp_forward_chain_loss: hidden width %d unsupported (128, 256)", hidden);
     TG_REQUIRE(n_hidden_layers >= 3 && n_hidden_layers <= kChainMaxHidden, "tg_mlp_forward_chain_loss: %d hidden layers outside 3..%d",
                n_hidden_layers, kChainMaxHidden);
@@ -690,10 +706,25 @@ int tg_mlp_forward_chain_loss(const void* d_x, const void* d_wfrag, const float*
     L.logp_const = -0.5f * (float)loss->act_dim * 1.8378770664093453f - 0.5f * logdet;
     L.epsilon = loss->epsilon; L.surr_coef = loss->surr_coef; L.critic_coef = loss->critic_coef; L.kl_coef = loss->kl_coef;
     L.dout8 = (uint16_t*)loss->d_dout8; L.head_slabs = loss->d_head_slabs; L.work = loss->d_work; L.bias_partial = loss->d_bias_partial;
+    L.logp_ref = use_ref ? ref->d_logp_ref : nullptr; L.ref_coef = use_ref ? ref->coef : 0.0f;
     hipStream_t st = (hipStream_t)stream;
     const int n_hh = n_hidden_layers - 1;
+    if (use_ref)
+        return hidden == 256 ? chain_launch<256, true, 4, false, true, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L)
+                             : chain_launch<128, true, 4, false, true, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L);
     return hidden == 256 ? chain_launch<256, true, 4, false, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L)
                          : chain_launch<128, true, 4, false, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L);
+}
+
+int tg_mlp_forward_chain_loss(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                              int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss, void* stream) {
+    return forward_chain_loss(d_x, d_wfrag, d_bias, hidden, n_hidden_layers, rows, d_acts, d_masks, loss, nullptr, stream);
+}
+
+int tg_mlp_forward_chain_loss_ref(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                                  int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
+                                  const tg_ref_penalty* ref, void* stream) {
+    return forward_chain_loss(d_x, d_wfrag, d_bias, hidden, n_hidden_layers, rows, d_acts, d_masks, loss, ref, stream);
 }
 
 }  // extern "C"

@@ -113,6 +113,15 @@ static inline int device_cus() {
     }
     return n[d];
 }
+// The reference-policy penalty of a `_ref` entry point (tg_ref_penalty): 1 = active, 0 = none (the plain kernel), < 0 = refused.
+// Checked before anything else the entry point looks at: nothing is launched for a refused penalty.
+static inline int ref_penalty_check(const tg_ref_penalty* ref, bool critic, float kl_coef, const char* who) {
+    if (ref == nullptr || ref->coef == 0.0f) return 0;
+    if (critic) return set_error(TG_ERR_ARG, "%s: the reference-policy penalty is an actor term (a critic / value head got one)", who);
+    if (ref->d_logp_ref == nullptr) return set_error(TG_ERR_ARG, "%s: d_logp_ref is null with a nonzero coef", who);
+    if (kl_coef != 0.0f) return set_error(TG_ERR_ARG, "%s: kl_coef must be 0 beside the reference-policy penalty (both use the KL sum)", who);
+    return 1;
+}
 struct LdsOptIn { size_t bytes[kMaxDevices] = {}; };
 static inline int reserve_dynamic_lds(const void* kernel, size_t bytes, LdsOptIn& cache, const char* what) {
     if (bytes > 160 * 1024) return set_error(TG_ERR_ARG, "%s: %zu B of LDS needed (> 160 KiB)", what, bytes);

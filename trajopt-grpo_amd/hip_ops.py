@@ -192,10 +192,12 @@ def gaussian_logp(mean: torch.Tensor, act: torch.Tensor, var, out: torch.Tensor 
 
 
 def surrogate_loss(mean, value, act, logp_old, adv, ret, mask, norm, var, epsilon, surr_coef, critic_coef, kl_coef,
-                   want_total: bool = True, coef: torch.Tensor = None):
+                   want_total: bool = True, coef: torch.Tensor = None, logp_ref: torch.Tensor = None, ref_coef: float = 0.0):
     """One launch of tg_surrogate_loss: returns (total f32 scalar, sums f64[4], d total/d mean, d total/d value|None).
     want_total=False skips the handful of scalar launches that combine the sums (the learners only use the sums).
-    coef: device f32 [3] {surr_coef, critic_coef, kl_coef} used instead of the three host numbers (PPO: tg_ppo_norm's output [4:7])."""
+    coef: device f32 [3] {surr_coef, critic_coef, kl_coef} used instead of the three host numbers (PPO: tg_ppo_norm's output [4:7]).
+    logp_ref f32 [M] with ref_coef != 0 (tg_surrogate_loss_ref): GRPO's KL penalty to a frozen reference policy, x = logp_ref - logp,
+    D = exp(x) - x - 1 in sums[2] (kl_coef must be 0; no value head), total -= ref_coef * sum D."""
     N.require_cuda(mean, act, logp_old, adv, coef)
     assert mean.dtype == torch.float32 and mean.dim() == 2 and mean.stride(1) == 1
     M, A = mean.shape
@@ -223,6 +225,14 @@ def surrogate_loss(mean, value, act, logp_old, adv, ret, mask, norm, var, epsilo
     sums = torch.empty(4, dtype=torch.float64, device=mean.device)
     work = torch.empty(4 * N.load().tg_loss_work_blocks(), dtype=torch.float64, device=mean.device)
     a.d_grad_mean, a.d_sums, a.d_work, a.M = grad_mean.data_ptr(), sums.data_ptr(), work.data_ptr(), M
+    if logp_ref is not None and float(ref_coef) != 0.0:
+        N.require_cuda(logp_ref)
+        assert logp_ref.dtype == torch.float32 and logp_ref.is_contiguous() and logp_ref.numel() == M
+        r = N.RefPenalty()
+        r.d_logp_ref, r.coef = logp_ref.data_ptr(), float(ref_coef)
+        N.check(N.load().tg_surrogate_loss_ref(C.byref(a), C.byref(r), _st(mean)), "tg_surrogate_loss_ref")
+        total = (surr_coef * sums[0] + critic_coef * sums[1] - float(ref_coef) * sums[2]).float() if want_total else None
+        return total, sums, grad_mean, grad_value
     N.check(N.load().tg_surrogate_loss(C.byref(a), _st(mean)), "tg_surrogate_loss")
     total = (surr_coef * sums[0] + critic_coef * sums[1] + kl_coef * sums[2]).float() if want_total else None
     return total, sums, grad_mean, grad_value

@@ -70,6 +70,21 @@ def inherit_ones_column(dst: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
     return dst
 
 
+def _ref_penalty(kind, rows, logp_ref, ref_coef, kl_coef):
+    """N.RefPenalty for forward_loss(logp_ref=..., ref_coef=...), or None: no penalty (the plain entry points)."""
+    if logp_ref is None or float(ref_coef) == 0.0:
+        return None
+    N.require_cuda(logp_ref)
+    if kind != 0:
+        raise ValueError("the reference-policy penalty is a term of the actor's loss (kind 0)")
+    if float(kl_coef) != 0.0:
+        raise ValueError("kl_coef must be 0 beside the reference-policy penalty: both use the KL sum")
+    assert logp_ref.dtype == torch.float32 and logp_ref.is_contiguous() and logp_ref.numel() == rows
+    r = N.RefPenalty()
+    r.d_logp_ref, r.coef = logp_ref.data_ptr(), float(ref_coef)
+    return r
+
+
 def lin_ok(l) -> bool:
     return l.weight.grad is not None and l.weight.grad.dtype == torch.float32 and l.bias.grad is not None
 _SPLIT_BATCHES = 128
@@ -413,18 +428,23 @@ class GemmMLP:
 
     @torch.no_grad()
     def forward_loss(self, xp: torch.Tensor, kind: int, *, act=None, logp_old=None, adv=None, ret=None, norm=None, var=None,
-                     epsilon=0.0, surr_coef=0.0, critic_coef=0.0, kl_coef=0.0, sums_out=None, logp_old_out=None, norm8=None) -> torch.Tensor:
+                     epsilon=0.0, surr_coef=0.0, critic_coef=0.0, kl_coef=0.0, sums_out=None, logp_old_out=None, norm8=None,
+                     logp_ref=None, ref_coef=0.0) -> torch.Tensor:
         """Training forward pass with the loss head inside it (kind 0: actor, clipped surrogate; kind 1: critic, squared error).
         Stores what backward_fused() needs, adds the head's weight / bias gradient into their windows and returns the f64 sums
         [surrogate, squared error, KL, count] of these rows -- or, given `sums_out` (f64 [4] on the device), ADDS them there and
         returns None; on the fp32 chain learner that addition rides on backward_fused()'s reduction launch (no launches of its own),
         so `sums_out` is complete once backward_fused() has been enqueued.
         norm8: device f32 [8] (hip_ops.ppo_norm): the normalisation pair and the three coefficients are read from it on the device;
-        `norm` and the `*_coef` arguments are then ignored."""
+        `norm` and the `*_coef` arguments are then ignored.
+        logp_ref (f32 [rows], kind 0) with ref_coef != 0: GRPO's KL penalty to a frozen reference policy in the head (the `_ref` entry
+        points): D = exp(x) - x - 1, x = logp_ref - logp, joins the KL sum (slot 2; kl_coef must be 0) and d loss / d logp gains
+        ref_coef (exp(x) - 1).  Otherwise the plain entry points run."""
         lib = N.load()
+        ref = _ref_penalty(kind, xp.shape[0], logp_ref, ref_coef, kl_coef)
         if self._f32 is not None:
             return self._forward_loss_f32(xp, kind, act, logp_old, adv, ret, norm, var, epsilon, surr_coef, critic_coef, kl_coef, sums_out,
-                                          logp_old_out, norm8)
+                                          logp_old_out, norm8, ref)
         self._flush_riders()                 # (a forward_loss() that was never followed by backward_fused(): its head gradient is due)
         self._fresh("chain")
         L = len(self.linears)
@@ -448,13 +468,19 @@ class GemmMLP:
         if self.fwd_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        N.check(lib.tg_mlp_forward_chain_loss(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1,
-                                              rows, ptrs, mptrs, N.C.byref(a), N.stream_ptr(dev)), "tg_mlp_forward_chain_loss")
+        if ref is None:
+            N.check(lib.tg_mlp_forward_chain_loss(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1,
+                                                  rows, ptrs, mptrs, N.C.byref(a), N.stream_ptr(dev)), "tg_mlp_forward_chain_loss")
+        else:
+            N.check(lib.tg_mlp_forward_chain_loss_ref(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1,
+                                                      rows, ptrs, mptrs, N.C.byref(a), N.C.byref(ref), N.stream_ptr(dev)),
+                    "tg_mlp_forward_chain_loss_ref")
         if ev is not None:
             ev[1].record()
             stored = sum(1 for t in hid if t is not None)
-            per_row = 2 * self.in_pad + stored * 2 * H + (L - 1) * (H // 8) + 16 + (4 * self.out_dim + 8 if kind == 0 else 4)
-            self.fwd_events.append((ev[0], ev[1], rows, per_row, f"tg::mlp_fwd_chain_kernel<{H},8,true,4,false,true>"))
+            per_row = 2 * self.in_pad + stored * 2 * H + (L - 1) * (H // 8) + 16 + (4 * self.out_dim + 8 if kind == 0 else 4) + (4 if ref else 0)
+            self.fwd_events.append((ev[0], ev[1], rows, per_row,
+                                    f"tg::mlp_fwd_chain_kernel<{H},8,true,4,false,true{',true' if ref else ''}>"))
         grid = min(nblk, -(-rows // 256))
         lin = self.linears[-1]
         # the head's partial weight / bias gradients (rows >= 4 of a slab are never written) and -- with sums_out -- the loss sums are
@@ -519,7 +545,7 @@ class GemmMLP:
         return self.can_fuse_head()
 
     def _forward_loss_f32(self, xp, kind, act, logp_old, adv, ret, norm, var, epsilon, surr_coef, critic_coef, kl_coef, sums_out=None,
-                          logp_old_out=None, norm8=None):
+                          logp_old_out=None, norm8=None, ref=None):
         """forward_loss() of an fp32 net: forward + loss head + backward-data pass in ONE launch (tg_mlp_f32_forward_backward);
         every hidden layer's activation and dZ is written for backward_fused() (tg_mlp_f32_weight_grad)."""
         lib = N.load()
@@ -546,7 +572,18 @@ class GemmMLP:
         if self.fwd_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        if f.res:
+        if ref is not None:                 # (the same launches with GRPO's reference-policy penalty in the head)
+            if f.res:
+                N.check(lib.tg_mlp_f32r_forward_backward_ref(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.w0.data_ptr(), f.table.data_ptr(), H,
+                                                             nh, rows, ptrs, zptrs, N.ptr(tmask), N.C.byref(a), N.C.byref(ref), N.stream_ptr(dev)),
+                        "tg_mlp_f32r_forward_backward_ref")
+            elif f.wide:
+                N.check(lib.tg_mlp_f32w_forward_backward_ref(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.table.data_ptr(), nh, rows, ptrs,
+                                                             zptrs, N.C.byref(a), N.C.byref(ref), N.stream_ptr(dev)), "tg_mlp_f32w_forward_backward_ref")
+            else:
+                N.check(lib.tg_mlp_f32_forward_backward_ref(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), H, nh, rows, ptrs, zptrs, N.ptr(tmask),
+                                                            N.C.byref(a), N.C.byref(ref), N.stream_ptr(dev)), "tg_mlp_f32_forward_backward_ref")
+        elif f.res:
             N.check(lib.tg_mlp_f32r_forward_backward(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.w0.data_ptr(), f.table.data_ptr(), H, nh, rows,
                                                      ptrs, zptrs, N.ptr(tmask), N.C.byref(a), N.stream_ptr(dev)), "tg_mlp_f32r_forward_backward")
         elif f.wide:
@@ -560,8 +597,9 @@ class GemmMLP:
             # matrix-core flops per row: first layer + forward and backward products of the H x H layers (head: vector unit)
             # algorithmic flops per row (un-padded): forward first layer + H x H layers + head, backward head + H x H layers
             self.fwd_events.append((ev[0], ev[1], rows, 2 * H * self.in_dim + 4 * (nh - 1) * H * H + 4 * H * self.out_dim,
-                                    "tg::mlp_f32_wide_kernel<true>" if f.wide else
-                                    (f"tg::mlp_f32_res_kernel<{H},{f.in_pad // 4},true>" if f.res else f"tg::mlp_f32_chain_kernel<{H},true>")))
+                                    ("tg::mlp_f32_wide_kernel<true" if f.wide else
+                                     (f"tg::mlp_f32_res_kernel<{H},{f.in_pad // 4},true" if f.res else f"tg::mlp_f32_chain_kernel<{H},true"))
+                                    + (",true>" if ref is not None else ">")))
         grid = lib.tg_mlp_f32r_grid(rows) if f.res else min(nblk, -(-rows // (64 if f.wide else 256)))      # (the launchers' own grids)
         self._acts, self._bits, self._dz_head, self._tmask = [xp] + acts, dzs, dout, tmask
         assert getattr(self, "_loss_rider", None) is None, "forward_loss(sums_out=...) must be followed by backward_fused()"
