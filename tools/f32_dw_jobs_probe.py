@@ -28,25 +28,3 @@ def run(names):
 sel = os.environ.get("JOBS")
 for names in ([sel.split(",")] if sel else (["mm"], ["x"], ["head"], ["mm", "mm"], ["x", "head"], ["mm", "x", "head"], ["mm"] * 4, ["mm"] * 4 + ["x", "head"])):
     print(names, "%.0f us" % run(names), flush=True)
-
-if os.environ.get("STAMPS"):
-    import ctypes, numpy as np
-    raw = ctypes.CDLL(os.environ["TG_NATIVE_LIB"])
-    buf = (ctypes.c_ulonglong * (4096 * 4))()
-    torch.cuda.synchronize()
-    assert raw.tg_debug_f32_stamps(buf) == 0
-    a = np.frombuffer(buf, dtype=np.uint64).reshape(-1, 4).astype(np.float64)
-    a = a[a[:, 3] > 0]
-    per = a[:, :3] / a[:, 3:4]
-    print("waves", len(a), "stages/wave", a[:, 3].mean(), "cycles per stage: wait+bias %.0f  arrive %.0f  products+reads %.0f" % tuple(per.mean(0)))
-    for w in range(4):
-        print(" wave", w, per[w::4].mean(0))
-
-    buf2 = (ctypes.c_ulonglong * (4096 * 6))()
-    assert raw.tg_debug_f32_stamps2(buf2) == 0
-    b = np.frombuffer(buf2, dtype=np.uint64).reshape(-1, 6).astype(np.float64)
-    b = b[b[:, 3] > 0]
-    t0 = b[:, 0].min(); r0 = b[:, 4].min()
-    print("waves", len(b), "memtime: entry spread %.0f, loop start-entry %.0f, loop %.0f, exit-loop end %.0f, last exit - first entry %.0f cycles" % (
-        b[:, 0].max() - t0, (b[:, 1] - b[:, 0]).mean(), (b[:, 2] - b[:, 1]).mean(), (b[:, 3] - b[:, 2]).mean(), b[:, 3].max() - t0))
-    print("realtime (100 MHz): last exit - first entry %.1f us; clock = %.3f GHz" % ((b[:, 5].max() - r0) / 100.0, (b[:, 3].max() - t0) / ((b[:, 5].max() - r0) * 10.0)))

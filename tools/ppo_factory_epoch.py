@@ -6,8 +6,8 @@ its host round trips ARE the step.
 
     python tools/ppo_factory_epoch.py [--tree DIR] [--epochs 60] [--gae]
 
---tree: the directory that holds the `trajopt-grpo_amd` package to time (default: this repository); tools/final_r05.sh points it
-at an unpacked round-4 tree for the before / after pair."""
+--tree: the directory that holds the `trajopt-grpo_amd` package to time (default: this repository); point it
+at an unpacked older tree for a before / after pair."""
 import argparse
 import importlib.util
 import json

@@ -13,7 +13,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# TG_NATIVE_LIB: another build of the same library (probe builds with different compile-time flags, tools/mall_probe.py)
+# TG_NATIVE_LIB: another build of the same library, loaded instead of the in-tree one
 LIB_PATH = os.environ.get("TG_NATIVE_LIB") or os.path.join(_HERE, "libtrajopt_grpo_hip.so")
 ABI_VERSION = 13                     # TG_ABI_VERSION of include/trajopt_grpo_hip.h this binding was written for
 

@@ -26,59 +26,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 
-// Cache policy of the chain kernels' activation / dZ stores.  Default: non-temporal (written once, read by a later kernel from
-// beyond the caches anyway at the learner's 4 M-row chunks).  -DTG_ACT_STORE_NT=0 builds the default-policy form for the
-// cache-residency probe (tools/mall_probe.py).
-#ifndef TG_ACT_STORE_NT
-#define TG_ACT_STORE_NT 1
-#endif
-// Probe builds only (tools/mall_probe.py --window): -DTG_PROBE_ROW_WINDOW=W (a power of two) folds every row-indexed global
-// address of the chain / weight-gradient kernels into the first W rows of its buffer.  The results are meaningless; the
-// instruction stream and the bytes moved are those of the real launch, but the streams stay cache-resident: what the update
-// would cost if its activation / dZ round trips were served on-die.  -DTG_DW_LOAD_AUX=0: default cache policy for the
-// weight-gradient kernel's panel loads (the product build reads them non-temporal).
-#ifndef TG_PROBE_ROW_WINDOW
-#define TG_PROBE_ROW_WINDOW 0
-#endif
-#ifndef TG_DW_LOAD_AUX
-#define TG_DW_LOAD_AUX 2
-#endif
-// Probe builds only (tools/build_probe_libs.sh `fusedbound`): -DTG_ABLATE_FUSED_CHAIN=1 takes out of the bf16 chain kernels exactly
-// the memory traffic a single forward + loss + backward kernel would not have -- the forward chain's mask-bit and d loss / d output
-// stores, the backward chain's loads of them and its second read of the input row.  Results are meaningless; the timing is an
-// upper bound on what that fusion could gain, before its own costs.
-#ifndef TG_TILED_STORE
-#define TG_TILED_STORE 0
-#endif
-#ifndef TG_ABLATE_FUSED_CHAIN
-#define TG_ABLATE_FUSED_CHAIN 0
-#endif
-// Probe builds only (tools/build_probe_libs.sh `headrelay1` / `headrelay2`): what the forward chain's head hand-off -- the top
-// activation relayed block by block through shared LDS tiles behind eight workgroup barriers, so that the head's weight gradient
-// is contracted on chip -- costs: 1 = the relay removed, 2 = the relay without its barriers.  Results meaningless.
-#ifndef TG_ABLATE_HEAD_RELAY
-#define TG_ABLATE_HEAD_RELAY 0
-#endif
-// Probe builds only (`chainvalu1..3`): how much of the bf16 chain kernels' time their vector instructions are -- bit 0: the forward
-// chain's ReLU mask bits not formed (7 instructions per 8 activations), bit 1: ReLU's clamp of the packed pair left out (1 per pair).
-// Results meaningless.  (profiles/r05_chain_valu_sensitivity.md)
-#ifndef TG_ABLATE_CHAIN_VALU
-#define TG_ABLATE_CHAIN_VALU 0
-#endif
-__device__ static inline int64_t mem_row(int64_t r) {
-#if TG_PROBE_ROW_WINDOW
-    return r & (int64_t)(TG_PROBE_ROW_WINDOW - 1);
-#else
-    return r;
-#endif
-}
+// Cache policy of the chain kernels' activation / dZ stores: non-temporal (written once, read by a later kernel from beyond
+// the caches anyway at the learner's 4 M-row chunks).
 typedef unsigned int act_u32x4 __attribute__((ext_vector_type(4)));
 __device__ static inline void act_store16(act_u32x4 v, act_u32x4* p) {
-#if TG_ACT_STORE_NT
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 // ReLU + bf16 pack of 8 accumulators: round first (v_cvt_pk_bf16_f32, 2 per instruction), then clamp the PACKED halves
@@ -89,9 +41,6 @@ __device__ static inline uint32_t relu_pack_bf16x2(float a, float b) {
     typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const bf16x2 p = __builtin_convertvector(f32x2{a, b}, bf16x2);          // ONE v_cvt_pk_bf16_f32
-#if TG_ABLATE_CHAIN_VALU & 2
-    return __builtin_bit_cast(uint32_t, p);                                 // (probe build: no clamp)
-#endif
     const i16x2 zero = {0, 0};
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(i16x2, p), zero));
 }

@@ -58,28 +58,6 @@ __device__ static inline void lds_store16(char* __restrict__ p, uint4 v) { *rein
 // (written once, read by the weight-gradient kernel).  `__restrict__`: alias scope (mfma_ring.hpp).
 __device__ static inline void store_pair(uint4* __restrict__ st, uint16_t* __restrict__ g, int64_t row0, int64_t rows, int ld,
                                          int lane, const bf16x8 (&a)[2], const bf16x8 (&b)[2]) {
-#if TG_TILED_STORE
-    // Probe build (-DTG_TILED_STORE=1): the registers go out as they stand into a TILED layout [32-row tile][16-B feature chunk]
-    // [row][16 B] -- every instruction writes four 256-B runs (whole 128-B lines), no LDS transpose.  Consumers do not read this
-    // layout: timing only (what the epilogue's transpose costs).
-    {
-        const int col = lane & 15, grp = lane >> 4;
-        const int64_t tile = row0 >> 5;
-        // (g = buffer + first column of the block pair; buffers are 512-B aligned, ld a power of two: recover both)
-        const int colofs = (int)(((uintptr_t)g >> 1) & (uintptr_t)(ld - 1));
-        uint16_t* base = g - colofs;
-        const int chunk0 = colofs / 8;                                                     // 16-B chunk of the pair's first block
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int row = 16 * c + col;
-            uint16_t* ta = base + ((tile * (ld / 8) + chunk0 + grp) * 32 + row) * 8;
-            uint16_t* tb = base + ((tile * (ld / 8) + chunk0 + 4 + grp) * 32 + row) * 8;
-            act_store16(__builtin_bit_cast(act_u32x4, a[c]), reinterpret_cast<act_u32x4*>(ta));
-            act_store16(__builtin_bit_cast(act_u32x4, b[c]), reinterpret_cast<act_u32x4*>(tb));
-        }
-        return;
-    }
-#endif
     const int col = lane & 15, grp = lane >> 4;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -92,7 +70,7 @@ __device__ static inline void store_pair(uint4* __restrict__ st, uint16_t* __res
         const int r = 8 * j + (lane >> 3), ch = lane & 7;
         const uint4 v = st[r * 8 + (ch ^ (r & 7))];
         int64_t row = row0 + r;
-        row = row < rows ? row : rows - 1; row = mem_row(row);
+        row = row < rows ? row : rows - 1;
         act_store16(act_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<act_u32x4*>(g + row * ld + 8 * ch));
     }
 }
@@ -137,24 +115,18 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
     // kFuse0: this wave's 32 input rows of `round` (64 B each) into X[round parity][wave], in the tile image [row / 4][row % 4][64 B]
     // with the 16-B chunk c of a row in slot c ^ (row / 4 & 3) (bank-conflict-free for the transposing reads AND plain: mlp_dw.hip)
     [[maybe_unused]] auto dma_x0 = [&](int64_t round, int par) {
-#if TG_ABLATE_FUSED_CHAIN
-        return;
-#endif
 #pragma unroll
         for (int pc = 0; pc < 2; ++pc) {
             int64_t r = round * (32 * WPW) + wave * 32 + 16 * pc + (lane >> 2);
-            r = r < rows ? r : rows - 1; r = mem_row(r);
+            r = r < rows ? r : rows - 1;
             const int chunk = (lane & 3) ^ ((lane >> 4) & 3);
             __builtin_amdgcn_global_load_lds(ptrs.x + r * 4 + chunk, (lds_void*)(xtiles + (par * WPW + wave) * 2048 + pc * 1024), 16, 0, 0);
         }
     };
     auto dma_dzh = [&](int64_t round) {
-#if TG_ABLATE_FUSED_CHAIN
-        return;
-#endif
         if (lane < 32) {
             int64_t r = round * (32 * WPW) + wave * 32 + lane;
-            r = r < rows ? r : rows - 1; r = mem_row(r);
+            r = r < rows ? r : rows - 1;
             __builtin_amdgcn_global_load_lds(dzh + r, (lds_void*)my_dzs, 16, 0, 0);
         }
     };
@@ -162,31 +134,19 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
     // L&1); H = 128: a row's two halves are 16 B together and lanes 0..31 fetch one row each.
     static_assert(MT == 8 || MT == 4, "the mask staging moves 16 B per lane (H = 256 or 128)");
     auto dma_mask = [&](int64_t round, int j, int buf) {
-#if TG_ABLATE_FUSED_CHAIN
-        return;
-#endif
         if constexpr (MT == 8) {
             int64_t r = round * (32 * WPW) + wave * 32 + (lane >> 1);
-            r = r < rows ? r : rows - 1; r = mem_row(r);
+            r = r < rows ? r : rows - 1;
             __builtin_amdgcn_global_load_lds(ptrs.mask[j] + r * MT + (lane & 1) * WPL, (lds_void*)(my_mks + buf * 64), 16, 0, 0);
         } else if (lane < 32) {
             int64_t r = round * (32 * WPW) + wave * 32 + lane;
-            r = r < rows ? r : rows - 1; r = mem_row(r);
+            r = r < rows ? r : rows - 1;
             __builtin_amdgcn_global_load_lds(ptrs.mask[j] + r * MT, (lds_void*)(my_mks + buf * 64), 16, 0, 0);
         }
     };
 
     int pre_pos = 0, pre_slot = 0, cur_slot = 0;
     int mseq = 0;                                   // running layer number of this workgroup; its masks sit in buffer mseq % 3
-#if TG_ABLATE_FUSED_CHAIN
-    // (the probe build loads none of them: give the staging areas operands that look like data -- half the mask bits set, small
-    // gradients, unit inputs -- zeros would multiply for free and let the package clock up)
-    for (int q = threadIdx.x; q < WPW * 64; q += 64 * WPW) dzs[q] = uint4{0x3C003C00u, 0xBC003C00u, 0u, 0u};
-    for (int q = threadIdx.x; q < WPW * 3 * 64; q += 64 * WPW) mks[q] = uint4{0xA5A5C3C3u, 0x5A5A3C3Cu, 0x0FF0F00Fu, 0x33CC55AAu};
-    if constexpr (kFuse0)
-        for (int q = threadIdx.x; q < 2 * WPW * 128; q += 64 * WPW) reinterpret_cast<uint4*>(xtiles)[q] = uint4{0x3F803F80u, 0x3F80BF80u, 0x3F003F00u, 0x3F803F80u};
-    __syncthreads();
-#endif
     TG_CLOCK_PROBE_BEGIN(g_probe_bwd_chain)
     dma_dzh(blockIdx.x);
     if constexpr (kFuse0) dma_x0(blockIdx.x, 0);

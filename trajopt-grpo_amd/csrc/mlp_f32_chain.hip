@@ -27,14 +27,6 @@
 #include "f32_loss.hpp"
 #include "f32_dw.hpp"
 
-#ifndef TG_F32DW_STAMPS
-#define TG_F32DW_STAMPS 0          /* diagnostic build: s_memtime stamps around the phases of the wide job's stage loop (never in the product) */
-#endif
-#ifndef TG_F32DW_ABLATE
-#define TG_F32DW_ABLATE 0          /* timing-only probe builds of the wide weight-gradient job: 1 = no products, 2 = no stream;
-                                      of the one-barrier 8-wave job: 3 = no rebuild inside the loop, 4 = no products, 5 = no DMA inside the loop */
-#endif
-
 namespace tg {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -421,7 +413,7 @@ static int launch_f32_chain(const F32ChainArgs& args_in, hipStream_t st) {
 //   wide job (H x H layer): stage = SRW rows of P and of Q (16 KiB), 4 slots;
 //   light job (first layer: P = dZ_0, narrow Q = the input rows; head: wide Q = the top activation, narrow P = d loss / d
 //   output): stage = SRL rows of the wide operand (16 KiB) + the narrow operand as a zero-padded [SRL][32] image (4-8 KiB), 3 slots.
-__device__ uint4 g_f32_zero16;
+__device__ uint4 g_f32_zero16;                             // 16 zero bytes: the source of an image's padding lanes
 // Its address, held in a register pair by the kernel that uses it (`const uint4* zero16 = f32_zero16_addr();` at the top): written
 // as `&g_f32_zero16` at the use, hipcc re-loads the symbol's address through the GOT in front of every LDS-DMA -- a scalar memory
 // round trip per piece inside the stage loops (found in round 5 on the H = 256 jobs: ~15 % of a stage).
@@ -430,11 +422,6 @@ __device__ static inline const uint4* f32_zero16_addr() {
     asm volatile("" : "+s"(z));
     return z;
 }
-#if TG_F32DW_STAMPS
-__device__ unsigned long long g_f32_stamps[4096 * 4];      // per wave: cycles in [wait + bias][arrive][products + reads], stages
-__device__ unsigned long long g_f32_stamps3[4096 * 12];     // fused job, per wave: cycles in [wait + barrier][issue][phase 1][barrier][operand reads][products], stages
-__device__ unsigned long long g_f32_stamps2[4096 * 6];     // per wave: s_memtime at entry / loop start / loop end / exit, s_memrealtime at entry / exit
-#endif                             // 16 zero bytes: the source of an image's padding lanes
 
 typedef __attribute__((address_space(3))) void f32_lds_void;
 __device__ static inline float lds_f(const float* __restrict__ p) { return *p; }
@@ -508,10 +495,6 @@ __device__ static void f32_dw_fused(const F32DwJob& job, int64_t rows, char* lds
     using F = F32FusedGeom<H, kRecP, kRecQ>;
     constexpr int MT = H / 32, TW = MT >= 4 ? 2 : 1;
     constexpr int SR = F::SR, NG = F::NG;
-#if TG_F32DW_STAMPS
-    const unsigned long long fs_entry = __builtin_amdgcn_s_memtime(), fs_rt0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long fs_loop0 = 0, fs_loop1 = 0;
-#endif
     constexpr int KS = 4 / MT;                                          // the first layer's tile: k-steps split over KS waves (H = 64: 2)
     static_assert(SR / (256 / H) == 8, "a thread rebuilds 8 rows of one feature per stage");
     const int D = job.ring_slots;                                       // 2 or 3 (host: what fits 79 KiB)
@@ -587,24 +570,12 @@ __device__ static void f32_dw_fused(const F32DwJob& job, int64_t rows, char* lds
         slot_issue = slot_issue + 1 == D ? 0 : slot_issue + 1;
     }
     const int tile0 = wave % MT, ks0 = wave / MT;                       // first-layer rider: this wave's tile and k-step phase
-#if TG_F32DW_STAMPS
-    unsigned long long st[7] = {0, 0, 0, 0, 0, 0, 0};
-    fs_loop0 = __builtin_amdgcn_s_memtime();
-#define TG_FSTAMP(k) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st[k] += now_ - st_t; st_t = now_; }
-#else
-#define TG_FSTAMP(k)
-#endif
 #pragma unroll 1
     for (int64_t sg = my; sg < n_st; sg += nb) {
-#if TG_F32DW_STAMPS
-        unsigned long long st_t = __builtin_amdgcn_s_memtime();
-        st[6] += 1;
-#endif
         if (D == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NG) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();       // the stage has landed for every wave; every wave is done with the previous stage's slot and panels
         asm volatile("" ::: "memory");
-        TG_FSTAMP(0)
         issue(sg_issue, slot_issue);
         sg_issue += nb;
         slot_issue = slot_issue + 1 == D ? 0 : slot_issue + 1;
@@ -615,7 +586,6 @@ __device__ static void f32_dw_fused(const F32DwJob& job, int64_t rows, char* lds
         const uint32_t* Mm = reinterpret_cast<const uint32_t*>(sb + F::OFF_G + 512);
         const float* AT = reinterpret_cast<const float*>(sb + F::OFF_AT);
         const float* Z0 = reinterpret_cast<const float*>(sb + F::OFF_Z0);
-        TG_FSTAMP(1)
         // ---- phase 1: rebuild, and the riders' vector work ----
         if constexpr (kRecQ) {
             // a0[row][f] = relu(b0[f] + sum_k W0[f][k] x[row][k]), k ascending
@@ -671,10 +641,8 @@ __device__ static void f32_dw_fused(const F32DwJob& job, int64_t rows, char* lds
             for (int r = 0; r < 8; ++r) bsum += pz[r];
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // this thread's panel writes have landed ...
-        TG_FSTAMP(2)
         __builtin_amdgcn_s_barrier();                               // ... and everyone's
         asm volatile("" ::: "memory");
-        TG_FSTAMP(3)
         // ---- phase 2: products (every operand in registers first: one exposed LDS latency per stage) ----
         const float* Pa = kRecP ? Pp : reinterpret_cast<const float*>(sb + F::OFF_P);
         const float* Qa = kRecQ ? Qp : reinterpret_cast<const float*>(sb + F::OFF_Q);
@@ -700,7 +668,6 @@ __device__ static void f32_dw_fused(const F32DwJob& job, int64_t rows, char* lds
         for (int s = 0; s < SR / 2; ++s)
 #pragma unroll
             for (int x = 0; x < TW; ++x) asm volatile("" : "+v"(av[s][x]), "+v"(bv[s][x]));     // (the products stay behind the wait)
-        TG_FSTAMP(4)
 #pragma unroll
         for (int s = 0; s < SR / 2; ++s) {
 #pragma unroll
@@ -711,12 +678,7 @@ __device__ static void f32_dw_fused(const F32DwJob& job, int64_t rows, char* lds
                 if (s % KS == 0) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(za[s / KS], xb[s / KS], acc0, 0, 0, 0);
             }
         }
-        TG_FSTAMP(5)
     }
-#if TG_F32DW_STAMPS
-    fs_loop1 = __builtin_amdgcn_s_memtime();
-#endif
-#undef TG_FSTAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // no LDS-DMA may outlive the workgroup's LDS allocation
     __syncthreads();
     // ---- the row groups' partial sums (and, H = 64, the k-step phases' partial tiles) meet in LDS, added in a fixed order ----
@@ -781,14 +743,6 @@ __device__ static void f32_dw_fused(const F32DwJob& job, int64_t rows, char* lds
             }
         }
     }
-#if TG_F32DW_STAMPS
-    if (lane == 0 && blockIdx.x < 1024) {
-        unsigned long long* o = g_f32_stamps3 + ((size_t)blockIdx.x * 4 + wave) * 12;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) o[k] = st[k];
-        o[7] = fs_entry; o[8] = fs_loop0; o[9] = fs_loop1; o[10] = __builtin_amdgcn_s_memtime(); o[11] = __builtin_amdgcn_s_memrealtime() - fs_rt0;
-    }
-#endif
 }
 
 template <int H>
@@ -800,10 +754,6 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_dw_kernel(F32DwArgs args, int6
     extern __shared__ uint4 lds[];
     char* lds_c = reinterpret_cast<char*>(lds);
     TG_CLOCK_PROBE_BEGIN(g_probe_f32_dw)
-#if TG_F32DW_STAMPS
-    const unsigned long long st_entry = __builtin_amdgcn_s_memtime(), st_rt0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long st_loop0 = 0, st_loop1 = 0;
-#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, kk = lane >> 5;
     int jb = 0;
@@ -858,9 +808,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_dw_kernel(F32DwArgs args, int6
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"((P_ - 1) * NG) : "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-#if TG_F32DW_ABLATE != 2                                    /* probe build 2: no stream (the ring keeps its prologue's data) */
             issue(sg_issue, slot_issue);
-#endif
             sg_issue += nb;
             slot_issue = slot_issue + 1 == D ? 0 : slot_issue + 1;
         };
@@ -880,16 +828,9 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_dw_kernel(F32DwArgs args, int6
             for (int r = 0; r < RPG; ++r) bt[r] = lds_f(P + (rg * RPG + r) * H + cb);
             slot = slot + 1 == D ? 0 : slot + 1;
         }
-#if TG_F32DW_STAMPS
-        unsigned long long st_a = 0, st_b = 0, st_c = 0, st_n = 0;
-        st_loop0 = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll 1
         for (; sg < n_st; sg += nb) {
             const int64_t r0 = sg * SR;
-#if TG_F32DW_STAMPS
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#endif
             // (every read of the previous stage's slot has landed in registers before this wave passes the barrier in arrive())
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             {
@@ -907,13 +848,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_dw_kernel(F32DwArgs args, int6
                 }
             }
             const bool more = sg + nb < n_st;
-#if TG_F32DW_STAMPS
-            const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-#endif
             if (more) arrive();
-#if TG_F32DW_STAMPS
-            const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-#endif
             const float* P = reinterpret_cast<const float*>(lds_c + slot * G::WIDE_SLOT);
             const float* Q = P + SR * H;
 #pragma unroll
@@ -922,11 +857,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_dw_kernel(F32DwArgs args, int6
                 for (int x = 0; x < TW; ++x)
 #pragma unroll
                     for (int y = 0; y < TW; ++y) {
-#if TG_F32DW_ABLATE == 1                                    /* probe build: no products (operands kept live) */
-                        asm volatile("" :: "v"(av[s][x]), "v"(bv[s][y]));
-#else
                         acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][x], bv[s][y], acc[x][y], 0, 0, 0);
-#endif
                     }
                 if (more) {                                         // the next stage's step-s operands, in the shadow of these products
 #pragma unroll
@@ -939,18 +870,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_dw_kernel(F32DwArgs args, int6
             }
             static_assert(RPG <= SR / 2, "the bias reads ride on the steps");
             if (more) slot = slot + 1 == D ? 0 : slot + 1;
-#if TG_F32DW_STAMPS
-            const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-            st_a += t1 - t0; st_b += t2 - t1; st_c += t3 - t2; st_n += 1;
-#endif
         }
-#if TG_F32DW_STAMPS
-        st_loop1 = __builtin_amdgcn_s_memtime();
-        if (lane == 0 && blockIdx.x < 1024) {
-            unsigned long long* o = g_f32_stamps + ((size_t)blockIdx.x * 4 + wave) * 4;
-            o[0] = st_a; o[1] = st_b; o[2] = st_c; o[3] = st_n;
-        }
-#endif
     } else {
         // ================= light job: one wide operand, SRL rows per stage =================
         constexpr int SR = G::SRL, D = G::LIGHT_SLOTS, P_ = D - 1, NG = G::NG_LIGHT;
@@ -1070,12 +990,6 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_dw_kernel(F32DwArgs args, int6
         if (tid < H) slab[H * H + tid] = bsum;
     }
     TG_CLOCK_PROBE_END(g_probe_f32_dw)
-#if TG_F32DW_STAMPS
-    if (lane == 0 && blockIdx.x < 1024) {
-        unsigned long long* o = g_f32_stamps2 + ((size_t)blockIdx.x * 4 + wave) * 6;
-        o[0] = st_entry; o[1] = st_loop0; o[2] = st_loop1; o[3] = __builtin_amdgcn_s_memtime(); o[4] = st_rt0; o[5] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 }
 
 // The fused job (both operands rebuilt, both riders) as ONE 8-wave workgroup per slot, for nets whose only H x H layer is this job
@@ -1092,7 +1006,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_dw_kernel(F32DwArgs args, int6
 // rebuilds a stage past the end: its P-side operands arrive as zeros, so every sum it touches gets zeros.
 //   kLean (with kPipe, padded width 8): the net has at most 5 inputs and ONE output (CartPole, Pendulum: C2) -- the terms that are
 // identically zero (input columns 5..7, head rows 1..3) are not computed: a third of the rebuild's vector instructions, which is
-// what the stage's time follows (tools/f32_dw_pipe_ablation.sh).  Same bits: fma(0, x, o) == o.
+// what the stage's time follows (profiles/r04_f32_dw_8wave.md).  Same bits: fma(0, x, o) == o.
 template <int H, int IN_PAD, bool kPipe, bool kLean = false>
 __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job, int64_t rows, float* __restrict__ ws) {
     const uint4* zero16 = f32_zero16_addr();
@@ -1111,13 +1025,6 @@ __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job,
     extern __shared__ uint4 lds[];
     char* lds_c = reinterpret_cast<char*>(lds);
     TG_CLOCK_PROBE_BEGIN(g_probe_f32_dw)
-#if TG_F32DW_STAMPS
-    const unsigned long long fs_entry = __builtin_amdgcn_s_memtime(), fs_rt0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long fs_loop0 = 0, fs_loop1 = 0, st[7] = {0, 0, 0, 0, 0, 0, 0};
-#define TG_FSTAMP(k) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st[k] += now_ - st_t; st_t = now_; }
-#else
-#define TG_FSTAMP(k)
-#endif
     const int D = kPipe ? 2 : job.ring_slots;                           // 2 or 3 (host: what fits 79 KiB)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, kk = lane >> 5;
@@ -1227,7 +1134,7 @@ __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job,
             for (int r = 0; r < RPT; ++r) {
                 o[r] = fmaf(w.x, xv[r].x, o[r]); o[r] = fmaf(w.y, xv[r].y, o[r]); o[r] = fmaf(w.z, xv[r].z, o[r]); o[r] = fmaf(w.w, xv[r].w, o[r]);
             }
-            if constexpr (kVecRider && TG_F32DW_ABLATE != 6) {
+            if constexpr (kVecRider) {
 #pragma unroll
                 for (int r = 0; r < RPT; ++r) {                     // rows ascending
                     w0acc[4 * k4 + 0] = fmaf(z[r], xv[r].x, w0acc[4 * k4 + 0]); w0acc[4 * k4 + 1] = fmaf(z[r], xv[r].y, w0acc[4 * k4 + 1]);
@@ -1280,12 +1187,10 @@ __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job,
             const float pv = ((mw[r] >> m_shift) & 1u) != 0u ? v : 0.f;
             lds_st(Pw + (rb + r) * H + f, pv);
             bsum += pv;
-#if TG_F32DW_ABLATE != 6                                    /* probe build 6: 56 of the rebuild's ~165 vector instructions gone */
             hacc[0] = fmaf(g4[r].x, at[r], hacc[0]); hacc[1] = fmaf(g4[r].y, at[r], hacc[1]);
             hacc[2] = fmaf(g4[r].z, at[r], hacc[2]); hacc[3] = fmaf(g4[r].w, at[r], hacc[3]);
             const float g_lo = gc1 ? g4[r].y : g4[r].x, g_hi = gc1 ? g4[r].w : g4[r].z;
             gsum += gc2 ? g_hi : g_lo;
-#endif
         }
     };
     // ---- the first layer's rider of a stage: this wave's tile, its k-steps KS s + ks0, operands straight from the ring slot ----
@@ -1324,9 +1229,7 @@ __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job,
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();   // stage k + 1 has landed; stage k's panels are complete; slot and panel set of stage k - 1 are free
             asm volatile("" ::: "memory");
-#if TG_F32DW_ABLATE != 5
             issue(sg_issue, cur);                                       // stage k + 2 into the slot stage k was rebuilt from
-#endif
             sg_issue += nb;
             const char* sn = lds_c + (cur ^ 1) * F::SLOT;               // stage k + 1's slot
             float* Pn = pan + (cur ^ 1) * 2 * SR * H;
@@ -1341,21 +1244,14 @@ __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job,
                     bv[s][0] = lds_f(Qa + 2 * (4 * h + s) * H);
                     bv[s][1] = lds_f(Qa + 2 * (4 * h + s) * H + 32);
                 }
-#if TG_F32DW_ABLATE != 3
                 if (h == 0) rebuild_q(sn, Pn + SR * H);
                 else rebuild_p(sn, Pn);
-#endif
-#if TG_F32DW_ABLATE == 4
-#pragma unroll
-                for (int s = 0; s < 4; ++s) asm volatile("" :: "v"(av[s]), "v"(bv[s][0]), "v"(bv[s][1]));
-#else
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s][0], acc[0], 0, 0, 0);
                     acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s][1], acc[1], 0, 0, 0);
                 }
                 rider_half(sn, h);
-#endif
             }
         }
     } else {
@@ -1367,20 +1263,12 @@ __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job,
         sg_issue += nb;
         slot_issue = slot_issue + 1 == D ? 0 : slot_issue + 1;
     }
-#if TG_F32DW_STAMPS
-    fs_loop0 = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll 1
     for (int64_t sg = my; sg < n_st; sg += nb) {
-#if TG_F32DW_STAMPS
-        unsigned long long st_t = __builtin_amdgcn_s_memtime();
-        st[6] += 1;
-#endif
         if (D == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NG) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();       // the stage has landed for every wave; every wave is done with the previous stage's slot and panels
         asm volatile("" ::: "memory");
-        TG_FSTAMP(0)
         issue(sg_issue, slot_issue);
         sg_issue += nb;
         slot_issue = slot_issue + 1 == D ? 0 : slot_issue + 1;
@@ -1388,14 +1276,11 @@ __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job,
         slot = slot + 1 == D ? 0 : slot + 1;
         const float* X = reinterpret_cast<const float*>(sb + F::OFF_X);
         const float* Z0 = reinterpret_cast<const float*>(sb + F::OFF_Z0);
-        TG_FSTAMP(1)
         rebuild_q(sb, Qp);
         rebuild_p(sb, Pp);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // this thread's panel writes have landed ...
-        TG_FSTAMP(2)
         __builtin_amdgcn_s_barrier();                               // ... and everyone's
         asm volatile("" ::: "memory");
-        TG_FSTAMP(3)
         // ---- phase 2: products, in two halves of 4 k-steps (a half's operands in registers first: 16 registers, and the
         // second half's reads go out while the first half's products run) ----
         const float* Pa = Pp + kk * H + 32 * wm + i;
@@ -1426,13 +1311,8 @@ __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job,
                 if (s % KS == 0) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(za[s / KS], xb[s / KS], acc0, 0, 0, 0);
             }
         }
-        TG_FSTAMP(5)
     }
-#if TG_F32DW_STAMPS
-    fs_loop1 = __builtin_amdgcn_s_memtime();
-#endif
     }
-#undef TG_FSTAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // no LDS-DMA may outlive the workgroup's LDS allocation
     __syncthreads();
     // ---- the row groups' partial sums and the k-step phases' partial tiles meet in LDS, added in a fixed order ----
@@ -1498,14 +1378,6 @@ __global__ __launch_bounds__(512, 4) void mlp_f32_dw_fused8_kernel(F32DwJob job,
         }
     }
     TG_CLOCK_PROBE_END(g_probe_f32_dw)
-#if TG_F32DW_STAMPS
-    if (lane == 0 && blockIdx.x < 512) {
-        unsigned long long* o = g_f32_stamps3 + ((size_t)blockIdx.x * 8 + wave) * 12;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) o[k] = st[k];
-        o[7] = fs_entry; o[8] = fs_loop0; o[9] = fs_loop1; o[10] = __builtin_amdgcn_s_memtime(); o[11] = __builtin_amdgcn_s_memrealtime() - fs_rt0;
-    }
-#endif
 }
 
 // grad[m][n] += sum over the job's slabs, in a fixed order.
@@ -1729,18 +1601,6 @@ int tg_mlp_f32_forward_backward_ref(const float* d_x, int32_t in_pad, const floa
                                     const tg_ref_penalty* ref, void* stream) {
     return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref, stream);
 }
-
-#if TG_F32DW_STAMPS
-int tg_debug_f32_stamps(unsigned long long* host_out) {    /* diagnostic builds only: not part of the ABI */
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_f32_stamps), sizeof(unsigned long long) * 4096 * 4) == hipSuccess ? 0 : -1;
-}
-int tg_debug_f32_stamps3(unsigned long long* host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_f32_stamps3), sizeof(unsigned long long) * 4096 * 12) == hipSuccess ? 0 : -1;
-}
-int tg_debug_f32_stamps2(unsigned long long* host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_f32_stamps2), sizeof(unsigned long long) * 4096 * 6) == hipSuccess ? 0 : -1;
-}
-#endif
 
 int64_t tg_mlp_f32_weight_grad_workspace(int32_t hidden) {
     if (hidden != 64 && hidden != 128 && hidden != 256) return 0;

@@ -25,25 +25,6 @@
 #include "f32_loss.hpp"
 #include "f32_dw.hpp"
 
-#ifndef TG_F32W_ABLATE
-#define TG_F32W_ABLATE 0           /* timing-only probe builds of the chain kernel (results meaningless): bit 0 = no block barrier, bit 1 = no
-                                      weight DMA inside the rounds, bit 2 = no activation / dZ stores (tools/f32_wide_ablation.sh); of the wide
-                                      weight-gradient job: bit 3 = no stage barrier, bit 4 = no DMA inside the stage loop */
-#endif
-#ifndef TG_F32R_TRAIN_WAVES
-#define TG_F32R_TRAIN_WAVES 12     /* waves per CU of the resident kernel's training launches (probe builds: 16) */
-#endif
-#ifndef TG_F32W_NT_STORE
-#define TG_F32W_NT_STORE 0         /* 1: the same for the H = 256 chain kernel */
-#endif
-#ifndef TG_F32R_NT_STORE
-#define TG_F32R_NT_STORE 1         /* the resident kernel's activation / dZ tiles leave as non-temporal stores (A/B: profiles/r05_f32_res_kernel.md; 0 = plain) */
-#endif
-#ifndef TG_F32R_ABLATE
-#define TG_F32R_ABLATE 0           /* ... of the resident H = 128 kernel: bit 0 = no activation / dZ / mask stores, bit 1 = no matrix products in
-                                      the H x H tiles, bit 2 = no LDS reads of their weights, bit 3 = no head / loss arithmetic (tools/f32_res_ablation.sh) */
-#endif
-
 namespace tg {
 
 constexpr int kWideH = 256;
@@ -136,12 +117,12 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_wide_kernel(F32WideArgs a) {
     // instead of following it (the shared TG_RING_NEXT issues the DMA first).
 #define TG_WIDE_HEAD(WAITN)                                                                                \
     TG_RING_WAIT(WAITN)                                                                                    \
-    if (!(TG_F32W_ABLATE & 1)) __builtin_amdgcn_s_barrier();                                               \
+    __builtin_amdgcn_s_barrier();                                                                          \
     asm volatile("" ::: "memory");                                                                         \
     const uint4* cur = ring + cur_slot * KS * 64;                                                          \
     cur_slot = (cur_slot + 1 == D) ? 0 : cur_slot + 1;
     auto dma_next = [&]() {
-        if (!(TG_F32W_ABLATE & 2)) ring_dma_block<KS, WPW>(wfrag + (int64_t)pre_pos * KS * 64, ring + pre_slot * KS * 64, wave, lane);
+        ring_dma_block<KS, WPW>(wfrag + (int64_t)pre_pos * KS * 64, ring + pre_slot * KS * 64, wave, lane);
         pre_pos = (pre_pos + 1 == n_blocks) ? 0 : pre_pos + 1;
         pre_slot = (pre_slot + 1 == D) ? 0 : pre_slot + 1;
     };
@@ -191,15 +172,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_wide_kernel(F32WideArgs a) {
     };
     auto bits_slot = [&](int layer) { return bits_s + ((layer * WPW + wave) * 64 + lane) * 2; };
     auto store_tile = [&](float* gptr, int64_t row, int mo, const f32x4& v) {
-#if TG_F32W_ABLATE & 4
-        asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
-#else
-#if TG_F32W_NT_STORE
-        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(gptr + row * H + 16 * mo + 4 * g));
-#else
         *reinterpret_cast<float4*>(gptr + row * H + 16 * mo + 4 * g) = float4{v[0], v[1], v[2], v[3]};
-#endif
-#endif
     };
 
     double s_surr = 0.0, s_crit = 0.0, s_kl = 0.0, s_cnt = 0.0;
@@ -416,7 +389,7 @@ static int fill_f32_wide(F32WideArgs& a, const float* d_x, int32_t in_pad, const
 // round's input row and this round's loss inputs loaded ahead, a round's addresses as scalar base + small lane offset.
 // ------------------------------------------------------------------------------------------------------------------------
 constexpr int kResWaves = 16;                  // no-grad launches: 4 waves per SIMD (~95 registers)
-constexpr int kResWavesTrain = TG_F32R_TRAIN_WAVES;            // training launches: 3 per SIMD (143 registers; 16 waves = 128 registers, 22 spilled: measured, no faster)
+constexpr int kResWavesTrain = 12;             // training launches: 3 per SIMD (143 registers; 16 waves = 128 registers, 22 spilled: measured, no faster)
 constexpr int res_waves(bool train) { return train ? kResWavesTrain : kResWaves; }
 constexpr int kResMaxHidden = 2;
 
@@ -491,23 +464,11 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
     auto tile_pair = [&](const uint4* __restrict__ blk_a, const uint4* __restrict__ blk_b, const f32x4 (&xin)[NT], f32x4& acc_a, f32x4& acc_b) {
         const uint4* __restrict__ pa = blk_a + lane;
         const uint4* __restrict__ pb = blk_b + lane;
-#if TG_F32R_ABLATE & 4
-        uint4 wa = uint4{(unsigned)lane, 1u, 2u, 3u}, wb = wa;
-        asm volatile("" : "+v"(wa.x), "+v"(wa.y), "+v"(wa.z), "+v"(wa.w));
-        asm volatile("" : "+v"(wb.x), "+v"(wb.y), "+v"(wb.z), "+v"(wb.w));
-#else
         uint4 wa = wide_lds_u4(pa), wb = wide_lds_u4(pb);
-#endif
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             uint4 na = wa, nb = wb;
-#if !(TG_F32R_ABLATE & 4)
             if (t + 1 < NT) { na = wide_lds_u4(pa + (t + 1) * 64); nb = wide_lds_u4(pb + (t + 1) * 64); }
-#endif
-#if TG_F32R_ABLATE & 2
-            asm volatile("" ::"v"(wa.x), "v"(wa.y), "v"(wa.z), "v"(wa.w), "v"(wb.x), "v"(wb.y), "v"(wb.z), "v"(wb.w));
-            acc_a[t & 3] += xin[t][0]; acc_b[t & 3] += xin[t][1];
-#else
             acc_a = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.x), xin[t][0], acc_a, 0, 0, 0);
             acc_b = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.x), xin[t][0], acc_b, 0, 0, 0);
             acc_a = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.y), xin[t][1], acc_a, 0, 0, 0);
@@ -516,10 +477,8 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
             acc_b = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.z), xin[t][2], acc_b, 0, 0, 0);
             acc_a = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.w), xin[t][3], acc_a, 0, 0, 0);
             acc_b = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.w), xin[t][3], acc_b, 0, 0, 0);
-#endif
             wa = na; wb = nb;
         }
-#if !(TG_F32R_ABLATE & 6)
         // (pin the order -- and with it the number of pieces in registers at a time: hipcc otherwise hoists a whole block's reads)
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
@@ -527,20 +486,12 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
             __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
             if (i + 2 < NT) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         }
-#endif
     };
     // Addresses: a round's 16 rows start at a wave-uniform base (scalar registers), the lane adds a small offset -- `jr` = the lane's
     // row within the round, clamped into range (a lane past the last row re-does the last row: identical bytes).
     auto store_tile = [&](float* round_base, int jr, int mo, const f32x4& v) {
-#if TG_F32R_ABLATE & 1
-        asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
-#else
-#if TG_F32R_NT_STORE
+        // non-temporal (A/B: profiles/r05_f32_res_kernel.md)
         __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(round_base + (jr * H + 4 * g) + 16 * mo));
-#else
-        *reinterpret_cast<float4*>(round_base + (jr * H + 4 * g) + 16 * mo) = float4{v[0], v[1], v[2], v[3]};
-#endif
-#endif
     };
     auto lane_row = [&](int64_t q) { const int64_t last = rows - 1 - q * 16; return last < j ? (int)last : j; };
 
@@ -590,13 +541,11 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
         float sacc[4] = {0.f, 0.f, 0.f, 0.f};
         const int A = kTrain ? L.A : a.out_dim;
         auto head_tile = [&](int k, const f32x4& v, int t) {
-#if !(TG_F32R_ABLATE & 8)
             const float4 w = wide_lds_f4(wh_s + k * H + 16 * t + 4 * g);
             sacc[k] = fmaf(v[0], w.x, sacc[k]);
             sacc[k] = fmaf(v[1], w.y, sacc[k]);
             sacc[k] = fmaf(v[2], w.z, sacc[k]);
             sacc[k] = fmaf(v[3], w.w, sacc[k]);
-#endif
         };
         if (n_hh == 1) {
             // (one copy of the layer per output count: a run-time `k < A` inside would cut the schedule of every tile pair)
@@ -646,11 +595,7 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
             if (valid && g == 0) *reinterpret_cast<float4*>(a.out + q * 64 + jr * 4) = float4{o[0], o[1], o[2], o[3]};
         } else {
             float gr[4], c_surr, c_crit, c_kl;
-#if TG_F32R_ABLATE & 8
-            gr[0] = o[0] + lin.adv; gr[1] = gr[2] = gr[3] = 0.f; c_surr = c_crit = c_kl = o[0];
-#else
             f32_loss_compute<false, kRef>(L, lin, o, row, valid, g == 0, gr, c_surr, c_crit, c_kl);
-#endif
             if (valid && g == 0) {
                 s_surr += (double)c_surr; s_crit += (double)c_crit; s_kl += (double)c_kl; s_cnt += 1.0;
                 *reinterpret_cast<float4*>(L.dout4 + q * 64 + jr * 4) = float4{gr[0], gr[1], gr[2], gr[3]};
@@ -671,14 +616,10 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
                     v <<= 4 * (g >> 1);
                     wds[w] = v | (uint32_t)__shfl_xor((int)v, 32, 64);
                 }
-#if TG_F32R_ABLATE & 1
-                asm volatile("" ::"v"(wds[0]), "v"(wds[1]));
-#else
                 if (g < 2) {
 #pragma unroll
                     for (int w = 0; w < NW; ++w) (a.top_mask + q * (16 * 2 * NW))[jr * (2 * NW) + g * NW + w] = wds[w];
                 }
-#endif
             }
             __builtin_amdgcn_sched_barrier(0);                   // (phase boundary: nothing hoisted across, registers stay bounded)
             // ---- backward: dZ_top = (g . W_head) * (a_top > 0), then dZ_0 = (W_1^T . dZ_1) * mask ----
@@ -870,13 +811,9 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_wide_dw_kernel(F32DwArgs args,
 #pragma unroll 1
         for (int64_t sg = my; sg < n_st; sg += nb) {
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"((P - 1) * NG) : "memory");
-#if !(TG_F32W_ABLATE & 8)                              /* probe builds (timing only): bit 3 = no stage barrier, bit 4 = no DMA inside the stage loop */
             __builtin_amdgcn_s_barrier();
-#endif
             asm volatile("" ::: "memory");
-#if !(TG_F32W_ABLATE & 16)
             issue(sg_issue, slot_issue);
-#endif
             sg_issue += nb;
             slot_issue = slot_issue + 1 == D ? 0 : slot_issue + 1;
             const float* Pp = reinterpret_cast<const float*>(lds_c + slot * kWdSlotW);

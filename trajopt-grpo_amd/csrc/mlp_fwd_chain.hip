@@ -89,28 +89,6 @@ __device__ static inline float4 lds_float4(const float* __restrict__ p) { return
 // with identical bytes.
 __device__ static inline void store_pair(uint4* __restrict__ st, uint16_t* __restrict__ g, int64_t row0, int64_t rows, int ld,
                                          int lane, const bf16x8 (&a)[2], const bf16x8 (&b)[2]) {
-#if TG_TILED_STORE
-    // Probe build (-DTG_TILED_STORE=1): the registers go out as they stand into a TILED layout [32-row tile][16-B feature chunk]
-    // [row][16 B] -- every instruction writes four 256-B runs (whole 128-B lines), no LDS transpose.  Consumers do not read this
-    // layout: timing only (what the epilogue's transpose costs).
-    {
-        const int col = lane & 15, grp = lane >> 4;
-        const int64_t tile = row0 >> 5;
-        // (g = buffer + first column of the block pair; buffers are 512-B aligned, ld a power of two: recover both)
-        const int colofs = (int)(((uintptr_t)g >> 1) & (uintptr_t)(ld - 1));
-        uint16_t* base = g - colofs;
-        const int chunk0 = colofs / 8;                                                     // 16-B chunk of the pair's first block
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int row = 16 * c + col;
-            uint16_t* ta = base + ((tile * (ld / 8) + chunk0 + grp) * 32 + row) * 8;
-            uint16_t* tb = base + ((tile * (ld / 8) + chunk0 + 4 + grp) * 32 + row) * 8;
-            act_store16(__builtin_bit_cast(act_u32x4, a[c]), reinterpret_cast<act_u32x4*>(ta));
-            act_store16(__builtin_bit_cast(act_u32x4, b[c]), reinterpret_cast<act_u32x4*>(tb));
-        }
-        return;
-    }
-#endif
     const int col = lane & 15, grp = lane >> 4;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -123,7 +101,7 @@ __device__ static inline void store_pair(uint4* __restrict__ st, uint16_t* __res
         const int r = 8 * j + (lane >> 3), ch = lane & 7;
         const uint4 v = st[r * 8 + (ch ^ (r & 7))];
         int64_t row = row0 + r;
-        row = row < rows ? row : rows - 1; row = mem_row(row);
+        row = row < rows ? row : rows - 1;
         // non-temporal: written once, read by a later kernel (A/B: 2.96 -> 2.91 ms per 2^22 rows)
         act_store16(act_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<act_u32x4*>(g + row * ld + 8 * ch));
     }
@@ -139,9 +117,6 @@ __device__ static inline void store_pair(uint4* __restrict__ st, uint16_t* __res
 // + selects per dword.  Plain VALU -> VALU dependences need no wait states.
 __device__ static inline uint32_t block_bits(bf16x8 x) {
     const uint4 a = __builtin_bit_cast(uint4, x);
-#if TG_ABLATE_CHAIN_VALU & 1
-    return a.x;                                              // (probe build: the words are garbage, no instruction spent)
-#endif
     uint32_t m, t0;
     asm("v_pk_min_u16 %0, %2, %6\n\t"
         "v_pk_min_u16 %1, %3, %6\n\t"
@@ -162,10 +137,6 @@ __device__ static inline uint32_t pair_mask_word(const bf16x8* x, int w, int nib
 // and the even lane stores the half-row's MT / 2 words.
 template <int MT>
 __device__ static inline void store_mask_words(uint32_t* __restrict__ g, int64_t row, int grp, const uint32_t (&w)[MT / 2]) {
-#if TG_ABLATE_FUSED_CHAIN
-    asm volatile("" ::"v"(w[0]), "v"(w[MT / 2 - 1]));          // (the words are still formed: a fused kernel needs them too)
-    return;
-#endif
     uint32_t full[MT / 2];
 #pragma unroll
     for (int i = 0; i < MT / 2; ++i) full[i] = w[i] | (uint32_t)__builtin_amdgcn_ds_swizzle((int)w[i], 0x401F);   // xor 0x10
@@ -291,7 +262,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             int64_t r = base + 16 * p + (lane >> 2);
-            r = r < rows ? r : rows - 1; r = mem_row(r);
+            r = r < rows ? r : rows - 1;
             __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(x) + r * 4 + (lane & 3), (lds_void*)(my_xs + 64 * p), 16, 0,
                                              0);
         }
@@ -302,7 +273,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
         TG_HEAD_LDS
         if (lane < 32) {
             int64_t r = round * (32 * WPW) + wave * 32 + lane;
-            r = r < rows ? r : rows - 1; r = mem_row(r);
+            r = r < rows ? r : rows - 1;
             if (L.kind != 1) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
@@ -337,7 +308,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             rowc[c] = row0 + 16 * c + col;
-            rowc[c] = rowc[c] < rows ? rowc[c] : rows - 1; rowc[c] = mem_row(rowc[c]);
+            rowc[c] = rowc[c] < rows ? rowc[c] : rows - 1;
         }
         bf16x8 xin[2][K8], xout[2][K8];
 
@@ -518,9 +489,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                         typedef float f32x2 __attribute__((ext_vector_type(2)));
                         const uint4 o = {__builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{g[0], g[1]}, bf16x2)),
                                          __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{g[2], g[3]}, bf16x2)), 0u, 0u};
-#if !TG_ABLATE_FUSED_CHAIN
                         if (valid) *reinterpret_cast<uint4*>(L.dout8 + rowc[c] * 8) = o;     // (a clamped duplicate must not zero the last row)
-#endif
                         lds_store16(dt + rl * 32, o);
                         lds_store16(dt + rl * 32 + 16, uint4{0u, 0u, 0u, 0u});
                     }
@@ -542,14 +511,11 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                         lds_store16(tw + (rl >> 2) * 256 + (rl & 3) * 64 + ((grp ^ ((rl >> 2) & 3)) * 16), __builtin_bit_cast(uint4, xin[c][b]));
                     }
                 };
-#if TG_ABLATE_HEAD_RELAY != 1                                  /* probe build 1: no relay at all (timing only: the head's weight gradient is not formed) */
                 write_tile(0);
 #pragma unroll
                 for (int b = 0; b < MT; ++b) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if TG_ABLATE_HEAD_RELAY != 2                                  /* probe build 2: the relay without its eight workgroup barriers (racy: timing only) */
                     __builtin_amdgcn_s_barrier();
-#endif
                     asm volatile("" ::: "memory");
                     if (b + 1 < MT) write_tile(b + 1);
                     f32x4 t = {};
@@ -567,7 +533,6 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                                     __builtin_bit_cast(uint4, float4{h.x + t[0], h.y + t[1], h.z + t[2], h.w + t[3]}));
                     }
                 }
-#endif
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the next round's loss inputs overwrite what was read above)
                 dma_loss_inputs(round + gridDim.x);
             }
