@@ -34,6 +34,11 @@ extern "C" {
 
 enum { TG_OK = 0, TG_ERR_ARG = -1, TG_ERR_HIP = -2, TG_ERR_UNSUPPORTED = -3 };
 
+/* hidden activation of the fp32 policy kernels' `_act` entry points (tg_fused_rollout_f32_act, tg_mlp_f32_forward_act,
+ * tg_mlp_f32_forward_backward_act); every hidden layer of a net uses the same one */
+#define TG_ACT_RELU 0
+#define TG_ACT_TANH 1
+
 /* environments (environments/cartpole_env.py, environments/quadrotor_env.py) */
 enum { TG_ENV_CARTPOLE = 0, TG_ENV_QUADPOLE2D = 1, TG_ENV_QUADPOLE = 2, TG_ENV_QUADROTOR12 = 3, TG_ENV_PENDULUM = 4 };
 /* arithmetic type of the environment state / trajectory */
@@ -184,6 +189,12 @@ int  tg_fused_rollout_f32_block_envs(int64_t n, int32_t agents);
 int  tg_fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab,
                           int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
                           int64_t env_offset, int32_t t_begin, int32_t t_end, void* stream);
+/* The same rollout with the hidden activation as an argument: TG_ACT_RELU launches exactly what tg_fused_rollout_f32 launches,
+ * TG_ACT_TANH the same kernels with a = tanhf(z) (the device library's, |error| <= 4 * 2^-24) in place of max(z, 0).
+ * An unknown activation is refused. */
+int  tg_fused_rollout_f32_act(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                              int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                              int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, void* stream);
 
 /* d_rng[1] += 1 (enqueued; one thread) */
 int  tg_rng_advance(uint64_t* d_rng, void* stream);
@@ -492,6 +503,18 @@ int  tg_mlp_f32_forward_backward(const float* d_x, int32_t in_pad, const float* 
 int  tg_mlp_f32_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
                                      int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
                                      const tg_chain_loss* loss, const tg_ref_penalty* ref, void* stream);   /* (tg_ref_penalty above) */
+/* The two passes with the hidden activation as an argument (and, for the training pass, a nullable `ref`: NULL = the plain head,
+ * else GRPO's reference penalty as in the `_ref` entry).  TG_ACT_RELU launches exactly what tg_mlp_f32_forward /
+ * tg_mlp_f32_forward_backward[_ref] launch.  TG_ACT_TANH: a = tanhf(z) (the device library's, |error| <= 4 * 2^-24) and
+ * dZ = dA * (1 - a^2) from the stored fp32 a (torch's tanh_backward); a mask bit cannot stand for 1 - a^2, so nothing is rebuilt:
+ * every d_acts[i] and d_dz[i] must be given and d_top_maskbits must be NULL (the weight-gradient jobs are plain MM / HEAD jobs).
+ * Refused before any launch: an unknown activation, Tanh with a mask buffer or a NULL d_acts[i] / d_dz[i], and everything the
+ * plain entries refuse. */
+int  tg_mlp_f32_forward_act(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
+                            int64_t rows, float* d_out, int32_t activation, void* stream);
+int  tg_mlp_f32_forward_backward_act(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
+                                     int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
+                                     const tg_chain_loss* loss, const tg_ref_penalty* ref, int32_t activation, void* stream);
 /* The same passes at H = 256 (the reference's QuadPole factory at its own precision: pipelines/quadpole_pipeline_ppo.py:54-58,
  * 20-256x5-{4,1} fp32), csrc/mlp_f32_wide.hip: a wave owns 16 rows on v_mfma_f32_16x16x4_f32, two 4-wave workgroups per CU.
  *   d_stream  f32, tg_mlp_f32w_stream_floats(n_hidden_layers) floats, in 16-KiB blocks of 16 pieces x 64 lanes x 16 B, lane = (i = lane & 15,

@@ -19,6 +19,7 @@ ABI_VERSION = 13                     # TG_ABI_VERSION of include/trajopt_grpo_hi
 
 TG_ENV_CARTPOLE, TG_ENV_QUADPOLE2D, TG_ENV_QUADPOLE, TG_ENV_QUADROTOR12, TG_ENV_PENDULUM = 0, 1, 2, 3, 4
 TG_F32, TG_F64 = 0, 1
+TG_ACT_RELU, TG_ACT_TANH = 0, 1         # hidden activation of the fp32 kernels' `_act` entry points
 ENV_IDS = {"CartPole": TG_ENV_CARTPOLE, "QuadPole2D": TG_ENV_QUADPOLE2D, "QuadPole": TG_ENV_QUADPOLE,
            "Quadrotor": TG_ENV_QUADROTOR12, "Pendulum": TG_ENV_PENDULUM}
 
@@ -133,6 +134,7 @@ SIGNATURES = {
     "tg_fused_rollout_f32_supported": (C.c_int, [_I32, _I32]),
     "tg_fused_rollout_f32_block_envs": (C.c_int, [_I64, _I32]),
     "tg_fused_rollout_f32": (C.c_int, [_P(EnvParams), _P(Traj), _VP, _VP, _I32, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _VP]),
+    "tg_fused_rollout_f32_act": (C.c_int, [_P(EnvParams), _P(Traj), _VP, _VP, _I32, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _I32, _VP]),
     "tg_rng_advance": (C.c_int, [_VP, _VP]),
     "tg_colsum_finish": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP]),
     "tg_head_prep_blocks": (C.c_int, []),
@@ -174,6 +176,9 @@ SIGNATURES = {
                                               C.POINTER(ChainLoss), _VP]),
     "tg_mlp_f32_forward_backward_ref": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP,
                                                   C.POINTER(ChainLoss), _P(RefPenalty), _VP]),
+    "tg_mlp_f32_forward_act": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, _VP, _I32, _VP]),
+    "tg_mlp_f32_forward_backward_act": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP,
+                                                  C.POINTER(ChainLoss), _P(RefPenalty), _I32, _VP]),
     "tg_mlp_f32w_stream_floats": (C.c_int64, [_I32]),
     "tg_mlp_f32w_table_floats": (C.c_int64, []),
     "tg_mlp_f32w_blocks": (C.c_int, []),

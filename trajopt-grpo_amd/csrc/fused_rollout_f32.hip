@@ -20,6 +20,7 @@
 //     and t), dynamics, recording and termination are the code of rollout_step_kernel.
 // HBM traffic per env-step is the trajectory record only.
 #include "env_dynamics.hpp"
+#include "act_f32.hpp"
 
 #include <string.h>
 
@@ -48,10 +49,10 @@ __device__ static inline void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-// H = hidden width (64 / 128), NHH = number of H x H layers (hidden layers - 1).
+// H = hidden width (64 / 128), NHH = number of H x H layers (hidden layers - 1), kAct = hidden activation (act_f32.hpp).
 // Tables: `wstream` f32 [H/32 waves][K1/2 + NHH*H/2 registers][64 lanes]; `tab` f32 [(NHH+1)*H biases][4*H head
 // weights, rows >= A zero][4 head biases].
-template <typename Env, int H, int NHH>
+template <typename Env, int H, int NHH, int kAct>
 __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
     typename Env::C c, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew, uint8_t* __restrict__ mask,
     int32_t* __restrict__ len, int64_t n, int32_t T, int32_t t0, int32_t t1, const float* __restrict__ wstream,
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[4 * q + j], h ? hi : lo, acc, 0, 0, 0);
             }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+        for (int r = 0; r < 16; ++r) acc[r] = act_f32<kAct>(acc[r]);
         // ---- H x H layers: exchange the activation vector through LDS, multiply with the register-resident rows ----
 #pragma unroll
         for (int l = 0; l < NHH; ++l) {
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wh[l][4 * q + 3], x.w, acc, 0, 0, 0);
             }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+            for (int r = 0; r < 16; ++r) acc[r] = act_f32<kAct>(acc[r]);
             par ^= 1;
         }
         // ---- head: per-lane partial dot products over this lane's 16 features, summed through LDS in a fixed order ----
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
 // recording, termination) is the code above; lanes 16..63 shadow lanes 0..15.
 typedef float f32x4r __attribute__((ext_vector_type(4)));
 
-template <typename Env, int H, int NHH>
+template <typename Env, int H, int NHH, int kAct>
 __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
     typename Env::C c, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew, uint8_t* __restrict__ mask,
     int32_t* __restrict__ len, int64_t n, int32_t T, int32_t t0, int32_t t1, const float* __restrict__ wstream,
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[tt][r] = fmaxf(acc[tt][r], 0.0f);
+            for (int r = 0; r < 4; ++r) acc[tt][r] = act_f32<kAct>(acc[tt][r]);
         // ---- H x H layers: exchange the activation vector through LDS, multiply with the register-resident rows ----
 #pragma unroll
         for (int l = 0; l < NHH; ++l) {
@@ -321,7 +322,7 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc[tt][r] = fmaxf(acc[tt][r], 0.0f);
+                for (int r = 0; r < 4; ++r) acc[tt][r] = act_f32<kAct>(acc[tt][r]);
             par ^= 1;
         }
         // ---- head: per-lane partial dot products over this lane's 8 features, summed through LDS in a fixed order ----
@@ -381,7 +382,7 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
     if (Env::kBalanceTerminates && in_range && alive) len[i] = -balanced_steps;   // a later segment [t1, ..) picks the count up
 }
 
-template <template <typename> class EnvT, int H, int NHH>
+template <template <typename> class EnvT, int H, int NHH, int kAct>
 static int fused_f32_launch(const tg_env_params* p, const tg_traj* tr, const float* wstream, const float* tab, const float* sigma,
                             const uint64_t* rng, int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
     using Env = EnvT<float>;
@@ -394,13 +395,13 @@ static int fused_f32_launch(const tg_env_params* p, const tg_traj* tr, const flo
     if (block_envs == 16) {
         const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * 16 + 2 * A * 4 * WPW * 16);
         const dim3 grid((unsigned)ceil_div(tr->n, 16));
-        hipLaunchKernelGGL((fused_rollout_f32x16_kernel<Env, H, NHH>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
+        hipLaunchKernelGGL((fused_rollout_f32x16_kernel<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
                            (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset,
                            p->agents);
     } else {
         const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * 32 + 2 * A * 2 * WPW * 32);
         const dim3 grid((unsigned)ceil_div(tr->n, 32));
-        hipLaunchKernelGGL((fused_rollout_f32_kernel<Env, H, NHH>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
+        hipLaunchKernelGGL((fused_rollout_f32_kernel<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
                            (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset,
                            p->agents);
     }
@@ -408,11 +409,11 @@ static int fused_f32_launch(const tg_env_params* p, const tg_traj* tr, const flo
     return TG_OK;
 }
 
-template <template <typename> class EnvT>
+template <template <typename> class EnvT, int kAct>
 static int fused_f32_dispatch(int hidden, int n_hh, const tg_env_params* p, const tg_traj* tr, const float* wstream, const float* tab,
                               const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
 #define TG_F32_CASE(HH, NN) \
-    case HH * 10 + NN: return fused_f32_launch<EnvT, HH, NN>(p, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
+    case HH * 10 + NN: return fused_f32_launch<EnvT, HH, NN, kAct>(p, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
     switch (hidden * 10 + n_hh) {
         TG_F32_CASE(64, 0) TG_F32_CASE(64, 1) TG_F32_CASE(64, 2) TG_F32_CASE(64, 3)
         TG_F32_CASE(128, 0) TG_F32_CASE(128, 1) TG_F32_CASE(128, 2) TG_F32_CASE(128, 3)
@@ -438,9 +439,10 @@ int tg_fused_rollout_f32_block_envs(int64_t n, int32_t agents) {
     return (n <= (int64_t)16 * device_cus() && agents <= 16) ? 16 : 32;
 }
 
-int tg_fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
-                         int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
-                         int32_t t_begin, int32_t t_end, void* stream) {
+static int fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
+                             int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                             int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
+    TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "tg_fused_rollout_f32_act: unknown activation %d", activation);
     TG_REQUIRE(p && tr && d_wstream && d_tab && sigma && d_rng, "tg_fused_rollout_f32: null pointer");
     TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_fused_rollout_f32: null trajectory pointer");
     TG_REQUIRE(tr->dtype == TG_F32, "tg_fused_rollout_f32: float32 trajectories only");
@@ -454,13 +456,31 @@ int tg_fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const float*
     if (t_begin == t_end) return TG_OK;
     const int n_hh = n_hidden_layers - 1;
     hipStream_t st = (hipStream_t)stream;
-    switch (p->env_id) {
-        case TG_ENV_CARTPOLE: return fused_f32_dispatch<CartPoleEnv>(hidden, n_hh, p, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
-        case TG_ENV_QUADPOLE2D: return fused_f32_dispatch<QuadPole2DEnv>(hidden, n_hh, p, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
-        case TG_ENV_QUADPOLE: return fused_f32_dispatch<QuadPoleEnv>(hidden, n_hh, p, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
-        case TG_ENV_PENDULUM: return fused_f32_dispatch<PendulumEnv>(hidden, n_hh, p, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
+    switch (activation * 16 + p->env_id) {
+#define TG_F32_ENV(ACT, ID, ENV)                                                                                                      \
+    case ACT * 16 + ID:                                                                                                               \
+        return fused_f32_dispatch<ENV, ACT>(hidden, n_hh, p, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
+        TG_F32_ENV(TG_ACT_RELU, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
+        TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE, QuadPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_PENDULUM, PendulumEnv)
+        TG_F32_ENV(TG_ACT_TANH, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
+        TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE, QuadPoleEnv) TG_F32_ENV(TG_ACT_TANH, TG_ENV_PENDULUM, PendulumEnv)
+#undef TG_F32_ENV
         default: return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_f32: env %d is not instantiated", p->env_id);
     }
+}
+
+int tg_fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
+                         int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                         int32_t t_begin, int32_t t_end, void* stream) {
+    return fused_rollout_f32(p, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+                             TG_ACT_RELU, stream);
+}
+
+int tg_fused_rollout_f32_act(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
+                             int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                             int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
+    return fused_rollout_f32(p, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+                             activation, stream);
 }
 
 }  // extern "C"

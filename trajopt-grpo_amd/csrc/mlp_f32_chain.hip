@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include "tg_common.hpp"
+#include "act_f32.hpp"
 #include "adam_update.hpp"
 #include "f32_loss.hpp"
 #include "f32_dw.hpp"
@@ -47,7 +48,7 @@ struct F32ChainArgs {
     const float* x;         // [rows][2 k2] f32, zero padded
     int64_t rows;
     F32Net net;
-    float* acts[kF32MaxHidden];   // kTrain: post-ReLU outputs of the hidden layers, f32 [rows][H]
+    float* acts[kF32MaxHidden];   // kTrain: post-activation outputs of the hidden layers, f32 [rows][H]
     float* dz[kF32MaxHidden];     // kTrain: d loss / d pre-activation of the hidden layers, f32 [rows][H]
     float* out;             // !kTrain: head output f32 [rows][4]
     uint32_t* top_mask;     // kTrain, optional: the top hidden layer's ReLU mask bits, u32 [rows][4] (per row: [lane half h][MT / 2 words];
@@ -79,9 +80,15 @@ TG_CLOCK_PROBE_VAR(g_probe_f32_dw, attach_probe_f32_dw)
 int attach_probe_f32(int which, void* d_probe) { return which == 0 ? attach_probe_f32_chain(d_probe) : attach_probe_f32_dw(d_probe); }
 
 // kRef (training only): GRPO's KL penalty to a frozen reference policy in the loss head (f32_loss.hpp)
-template <int H, bool kTrain, bool kRef = false>
+// kAct: the hidden activation (act_f32.hpp).  ReLU keeps its mask bits on chip (and may rebuild operands: top_mask, null acts[0] /
+// dz[top]); Tanh takes dZ = dA (1 - a^2) from the fp32 activations themselves: the top layer's are still in registers when the head's
+// gradient is formed, each layer below re-reads the tile of acts[l - 1] this lane stored itself in the forward pass (same lane, same
+// addresses: its own earlier stores), so every acts[i] and dz[i] is written and nothing is rebuilt.
+template <int H, bool kTrain, bool kRef = false, int kAct = TG_ACT_RELU>
 __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
     static_assert(!kRef || kTrain, "the reference penalty is a term of the training pass");
+    static_assert(act_supported<kAct>(), "unknown hidden activation");
+    constexpr bool kRelu = kAct == TG_ACT_RELU;
     constexpr int MT = H / 32;                  // 32-feature tiles per layer
     constexpr int G4 = H / 8;                   // groups of 4 MFMA steps per H x H block
     constexpr int BLK = G4 * 64;                // uint4 per block
@@ -244,10 +251,15 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
                         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w4.z), xr[4 * q + 2], acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w4.w), xr[4 * q + 3], acc, 0, 0, 0);
                     }
-                const uint32_t m = relu_bits(acc);
+                if constexpr (kRelu) {
+                    const uint32_t m = relu_bits(acc);
+                    if constexpr (kTrain) { if (mo & 1) *bits_slot(0, mo >> 1) |= m << 16; else *bits_slot(0, mo >> 1) = m; }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = act_f32<kAct>(acc[r]);
+                }
                 xin[mo] = acc;
                 if constexpr (kTrain) {
-                    if (mo & 1) *bits_slot(0, mo >> 1) |= m << 16; else *bits_slot(0, mo >> 1) = m;
                     if (valid && a.acts[0] != nullptr) store_tile<H>(a.acts[0], row, mo, h, acc);      // (null: the weight-gradient job recomputes it)
                 }
             }
@@ -258,12 +270,15 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
             for (int mo = 0; mo < MT; ++mo) {
                 TG_F32_BLOCK_BEGIN
                 f32x16 acc = tile_products(cur, xin, bias_rows(bias_s + l * H + 32 * mo + 4 * h));
-                const uint32_t m = relu_bits(acc);
-                xout[mo] = acc;
-                if constexpr (kTrain) {
-                    if (mo & 1) *bits_slot(l, mo >> 1) |= m << 16; else *bits_slot(l, mo >> 1) = m;
-                    defer_store(a.acts[l], mo, acc);
+                if constexpr (kRelu) {
+                    const uint32_t m = relu_bits(acc);
+                    if constexpr (kTrain) { if (mo & 1) *bits_slot(l, mo >> 1) |= m << 16; else *bits_slot(l, mo >> 1) = m; }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = act_f32<kAct>(acc[r]);
                 }
+                xout[mo] = acc;
+                if constexpr (kTrain) defer_store(a.acts[l], mo, acc);
                 TG_F32_BLOCK_END
             }
 #pragma unroll
@@ -301,9 +316,10 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
                 *reinterpret_cast<float4*>(L.dout4 + row * 4) = float4{g[0], g[1], g[2], g[3]};
             }
             // ---- backward: dZ_top = (g . W_head) * (a_top > 0), then dZ_below = (W^T . dZ) * mask per layer, top down ----
+            // (Tanh: * (1 - a^2) instead of * mask, a = the fp32 activation: xin for the top layer, re-read from acts[l - 1] below)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                const uint32_t mw = *bits_slot(n_hh, mt >> 1) >> (16 * (mt & 1));
+                const uint32_t mw = kRelu ? *bits_slot(n_hh, mt >> 1) >> (16 * (mt & 1)) : 0u;
                 f32x16 d;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -314,26 +330,52 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
                             const float4 w = *reinterpret_cast<const float4*>(wh_s + k * H + 32 * mt + 8 * q + 4 * h);
                             s.x = fmaf(g[k], w.x, s.x); s.y = fmaf(g[k], w.y, s.y); s.z = fmaf(g[k], w.z, s.z); s.w = fmaf(g[k], w.w, s.w);
                         }
-                    d[4 * q + 0] = (mw >> (4 * q + 0)) & 1u ? s.x : 0.f;
-                    d[4 * q + 1] = (mw >> (4 * q + 1)) & 1u ? s.y : 0.f;
-                    d[4 * q + 2] = (mw >> (4 * q + 2)) & 1u ? s.z : 0.f;
-                    d[4 * q + 3] = (mw >> (4 * q + 3)) & 1u ? s.w : 0.f;
+                    if constexpr (kRelu) {
+                        d[4 * q + 0] = (mw >> (4 * q + 0)) & 1u ? s.x : 0.f;
+                        d[4 * q + 1] = (mw >> (4 * q + 1)) & 1u ? s.y : 0.f;
+                        d[4 * q + 2] = (mw >> (4 * q + 2)) & 1u ? s.z : 0.f;
+                        d[4 * q + 3] = (mw >> (4 * q + 3)) & 1u ? s.w : 0.f;
+                    } else {
+                        d[4 * q + 0] = s.x * fmaf(-xin[mt][4 * q + 0], xin[mt][4 * q + 0], 1.0f);
+                        d[4 * q + 1] = s.y * fmaf(-xin[mt][4 * q + 1], xin[mt][4 * q + 1], 1.0f);
+                        d[4 * q + 2] = s.z * fmaf(-xin[mt][4 * q + 2], xin[mt][4 * q + 2], 1.0f);
+                        d[4 * q + 3] = s.w * fmaf(-xin[mt][4 * q + 3], xin[mt][4 * q + 3], 1.0f);
+                    }
                 }
                 xin[mt] = d;
                 if (valid && a.dz[n_hh] != nullptr) store_tile<H>(a.dz[n_hh], row, mt, h, d);         // (null: recomputed from g and the mask bits)
             }
-            if (valid && a.top_mask != nullptr) {
+            if (kRelu && valid && a.top_mask != nullptr) {
 #pragma unroll
                 for (int w = 0; w < MT / 2; ++w) a.top_mask[row * 4 + h * (MT / 2) + w] = *bits_slot(n_hh, w);
             }
             for (int l = n_hh; l >= 1; --l) {
 #pragma unroll
                 for (int ko = 0; ko < MT; ++ko) {
+                    // (Tanh: this lane's own 16 values of tile ko of acts[l - 1], requested ahead of the block's products; the
+                    // forward pass's deferred store of that tile was flushed blocks ago, and rowc keeps an invalid row's read in
+                    // bounds -- its column of the products is never stored)
+                    float4 av[4];
+                    if constexpr (!kRelu) {
+                        const float* p = a.acts[l - 1] + rowc * H + 32 * ko + 4 * h;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) av[q] = *reinterpret_cast<const float4*>(p + 8 * q);
+                    }
                     TG_F32_BLOCK_BEGIN
                     f32x16 acc = tile_products(cur, xin, f32x16{});
-                    const uint32_t mw = *bits_slot(l - 1, ko >> 1) >> (16 * (ko & 1));
+                    if constexpr (kRelu) {
+                        const uint32_t mw = *bits_slot(l - 1, ko >> 1) >> (16 * (ko & 1));
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] = (mw >> r) & 1u ? acc[r] : 0.f;
+                        for (int r = 0; r < 16; ++r) acc[r] = (mw >> r) & 1u ? acc[r] : 0.f;
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            acc[4 * q + 0] *= fmaf(-av[q].x, av[q].x, 1.0f);
+                            acc[4 * q + 1] *= fmaf(-av[q].y, av[q].y, 1.0f);
+                            acc[4 * q + 2] *= fmaf(-av[q].z, av[q].z, 1.0f);
+                            acc[4 * q + 3] *= fmaf(-av[q].w, av[q].w, 1.0f);
+                        }
+                    }
                     xout[ko] = acc;
                     defer_store(a.dz[l - 1], ko, acc);
                     TG_F32_BLOCK_END
@@ -382,9 +424,9 @@ static int f32_chain_grid(int64_t rows) {
     return (int)(n_rounds < cus ? n_rounds : cus);
 }
 
-template <int H, bool kTrain, bool kRef = false>
+template <int H, bool kTrain, bool kRef = false, int kAct = TG_ACT_RELU>
 static int launch_f32_chain(const F32ChainArgs& args_in, hipStream_t st) {
-    auto kern = mlp_f32_chain_kernel<H, kTrain, kRef>;
+    auto kern = mlp_f32_chain_kernel<H, kTrain, kRef, kAct>;
     F32ChainArgs args = args_in;
     const int n_stream = args.net.n_hh * (H / 32) * (kTrain ? 2 : 1);
     args.resident = n_stream > 0 && f32_chain_lds<H>(args.net.n_hh, args.net.k2, n_stream) <= 160 * 1024;
@@ -1545,8 +1587,9 @@ int64_t tg_mlp_f32_stream_floats(int32_t hidden, int32_t n_hidden_layers, int32_
 
 int tg_mlp_f32_blocks(void) { return device_cus(); }
 
-int tg_mlp_f32_forward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers, int64_t rows,
-                       float* d_out, void* stream) {
+static int f32_forward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers, int64_t rows,
+                       float* d_out, int32_t activation, void* stream) {
+    TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "tg_mlp_f32_forward_act: unknown activation %d", activation);
     TG_REQUIRE(d_x && d_stream && d_out, "tg_mlp_f32_forward: null pointer");
     TG_REQUIRE(rows >= 0, "tg_mlp_f32_forward: negative row count");
     F32ChainArgs a{};
@@ -1554,12 +1597,28 @@ int tg_mlp_f32_forward(const float* d_x, int32_t in_pad, const float* d_stream, 
     if (rows == 0) return TG_OK;
     a.x = d_x; a.rows = rows; a.out = d_out;
     hipStream_t st = (hipStream_t)stream;
+    if (activation == TG_ACT_TANH)
+        return hidden == 128 ? launch_f32_chain<128, false, false, TG_ACT_TANH>(a, st) : launch_f32_chain<64, false, false, TG_ACT_TANH>(a, st);
     return hidden == 128 ? launch_f32_chain<128, false>(a, st) : launch_f32_chain<64, false>(a, st);
+}
+
+int tg_mlp_f32_forward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers, int64_t rows,
+                       float* d_out, void* stream) {
+    return f32_forward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_out, TG_ACT_RELU, stream);
+}
+
+int tg_mlp_f32_forward_act(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers, int64_t rows,
+                           float* d_out, int32_t activation, void* stream) {
+    return f32_forward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_out, activation, stream);
 }
 
 static int f32_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
                                 int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits, const tg_chain_loss* loss,
-                                const tg_ref_penalty* ref, void* stream) {
+                                const tg_ref_penalty* ref, int32_t activation, void* stream) {
+    TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "tg_mlp_f32_forward_backward_act: unknown activation %d", activation);
+    // (Tanh: a mask bit cannot stand for 1 - a^2 -- nothing is rebuilt, every activation and dZ is written)
+    TG_REQUIRE(activation == TG_ACT_RELU || d_top_maskbits == nullptr,
+               "tg_mlp_f32_forward_backward_act: Tanh nets have no mask bits (d_top_maskbits must be NULL)");
     TG_REQUIRE(loss, "tg_mlp_f32_forward_backward: null pointer");
     const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_f32_forward_backward_ref");
     if (use_ref < 0) return use_ref;
@@ -1577,7 +1636,8 @@ static int f32_forward_backward(const float* d_x, int32_t in_pad, const float* d
     for (int l = 0; l < n_hidden_layers; ++l) {
         // with >= 2 hidden layers the first activation and the top layer's dZ may be left out: the weight-gradient job of the layer
         // that would read them rebuilds them (tg_f32_dw_job.recompute) -- the latter needs the top layer's mask bits
-        const bool a_opt = l == 0 && n_hidden_layers >= 2, z_opt = l == n_hidden_layers - 1 && n_hidden_layers >= 2 && d_top_maskbits;
+        const bool relu = activation == TG_ACT_RELU;
+        const bool a_opt = relu && l == 0 && n_hidden_layers >= 2, z_opt = relu && l == n_hidden_layers - 1 && n_hidden_layers >= 2 && d_top_maskbits;
         TG_REQUIRE((d_acts[l] || a_opt) && (d_dz[l] || z_opt), "tg_mlp_f32_forward_backward: buffer %d is null", l);
         a.acts[l] = (float*)d_acts[l];
         a.dz[l] = (float*)d_dz[l];
@@ -1586,6 +1646,10 @@ static int f32_forward_backward(const float* d_x, int32_t in_pad, const float* d
     a.x = d_x; a.rows = rows;
     fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr);
     hipStream_t st = (hipStream_t)stream;
+    if (activation == TG_ACT_TANH) {
+        if (use_ref) return hidden == 128 ? launch_f32_chain<128, true, true, TG_ACT_TANH>(a, st) : launch_f32_chain<64, true, true, TG_ACT_TANH>(a, st);
+        return hidden == 128 ? launch_f32_chain<128, true, false, TG_ACT_TANH>(a, st) : launch_f32_chain<64, true, false, TG_ACT_TANH>(a, st);
+    }
     if (use_ref) return hidden == 128 ? launch_f32_chain<128, true, true>(a, st) : launch_f32_chain<64, true, true>(a, st);
     return hidden == 128 ? launch_f32_chain<128, true>(a, st) : launch_f32_chain<64, true>(a, st);
 }
@@ -1593,13 +1657,22 @@ static int f32_forward_backward(const float* d_x, int32_t in_pad, const float* d
 int tg_mlp_f32_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
                                 int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits, const tg_chain_loss* loss,
                                 void* stream) {
-    return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, nullptr, stream);
+    return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, nullptr,
+                                TG_ACT_RELU, stream);
 }
 
 int tg_mlp_f32_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
                                     int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits, const tg_chain_loss* loss,
                                     const tg_ref_penalty* ref, void* stream) {
-    return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref, stream);
+    return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref,
+                                TG_ACT_RELU, stream);
+}
+
+int tg_mlp_f32_forward_backward_act(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
+                                    int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits, const tg_chain_loss* loss,
+                                    const tg_ref_penalty* ref, int32_t activation, void* stream) {
+    return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref,
+                                activation, stream);
 }
 
 int64_t tg_mlp_f32_weight_grad_workspace(int32_t hidden) {

@@ -19,7 +19,10 @@ minimises bytes per row:
     output tiles on 256 CUs: 1.6-1.9 ms per 2^20 rows).
 Gradients are accumulated in fp32 straight into `param.grad` (the learner's flat all-reduce bucket).
 
-Only ReLU hidden activations take this path; anything else stays on torch autograd.
+Only ReLU hidden activations take the bf16 and per-layer paths.  fp32 nets of the fp32 chain shapes (H in {64, 128}, 1-4 hidden
+layers, <= 32 inputs, <= 4 outputs) may use Tanh instead: the fp32 chain learner (tg_mlp_f32_forward_act / _forward_backward_act /
+_weight_grad) and the fp32 fused rollout take the activation as a compile-time kernel argument (`hidden_activation()`).  Any other
+activation, a mix of activations, or a Tanh net outside those shapes stays on torch autograd.
 """
 from __future__ import annotations
 
@@ -141,6 +144,26 @@ def supports(net) -> bool:
     return all(l.out_features % 8 == 0 for l in mods[0:-1:2])
 
 
+# hidden activations of the fp32 kernels' `_act` entry points (include/trajopt_grpo_hip.h TG_ACT_*)
+ACTIVATIONS = {"ReLU": N.TG_ACT_RELU, "Tanh": N.TG_ACT_TANH}
+
+
+def hidden_activation(net):
+    """"ReLU" or "Tanh" if `net` is Linear [act Linear]+ with the SAME hidden activation after every hidden layer (exactly torch.nn.ReLU
+    or torch.nn.Tanh modules), else None (mixed lists, Sigmoid, anything else).  Says nothing about the shape."""
+    mods = list(getattr(net, "network", []))
+    if len(mods) < 3 or len(mods) % 2 == 0:
+        return None
+    if any(not isinstance(m, torch.nn.Linear) for m in mods[0::2]):
+        return None
+    kinds = {type(m) for m in mods[1::2]}
+    if kinds == {torch.nn.ReLU}:
+        return "ReLU"
+    if kinds == {torch.nn.Tanh}:
+        return "Tanh"
+    return None
+
+
 def _round_up(x, m):
     return (x + m - 1) // m * m
 
@@ -170,7 +193,16 @@ class _Workspace:
 
 class GemmMLP:
     def __init__(self, net, compute_dtype=torch.bfloat16):
-        assert supports(net)
+        # ReLU nets: every path below.  Tanh nets: the fp32 chain learner only (its kernels take the activation as an argument; the
+        # per-layer GEMMs, the ReLU-backward kernels and the bf16 chains are ReLU by construction): forward(keep=True) and backward()
+        # refuse them instead of applying ReLU
+        self.act = hidden_activation(net)
+        if self.act == "Tanh":
+            if compute_dtype != torch.float32 or not f32_chain_supported(net):
+                raise ValueError("GemmMLP runs a Tanh net only in float32 on the fp32 chain learner (Linear(S<=32, H) Tanh "
+                                 "[Linear(H, H) Tanh]{0..3} Linear(H, A<=4), H in {64, 128})")
+        else:
+            assert supports(net)
         self.net = net
         self.cd = compute_dtype
         self.linears = [m for m in net.network if isinstance(m, torch.nn.Linear)]
@@ -181,7 +213,12 @@ class GemmMLP:
         # (parity tests: every hidden activation and dZ of the fp32 chain learner written to HBM, so that each can be compared with
         # fp64; the product rebuilds the first activation and the top dZ on chip instead)
         self.f32_store_all = False
-        if compute_dtype == torch.float32 and f32_res_supported(net):
+        if self.act == "Tanh":
+            # (the resident 16-row kernel and the H = 256 kernel are ReLU-only: a Tanh net of the resident shape runs the chain kernel;
+            # nothing is rebuilt from mask bits, so every activation and dZ is stored)
+            self._f32 = F32ChainStream(net, f32_chain_supported(net), activation="Tanh")
+            self.f32_store_all = True
+        elif compute_dtype == torch.float32 and f32_res_supported(net):
             self._f32 = F32ResStream(net)                       # H = 128, <= 2 hidden layers: the resident 16-row kernel (C2's shape)
         elif compute_dtype == torch.float32 and f32_chain_supported(net):
             self._f32 = F32ChainStream(net, f32_chain_supported(net))
@@ -235,17 +272,21 @@ class GemmMLP:
         self._built = {}            # derived operand -> the key (_key()) of the weights it was last built from
         self.refresh()
 
-    def disable_f32_chain(self):
+    def disable_f32_chain(self) -> bool:
         """Back to the per-layer path with the 32-wide padded input (a learner whose actor and critic would otherwise expect
-        differently padded inputs: e.g. > 4 actions beside a 1-output critic)."""
+        differently padded inputs: e.g. > 4 actions beside a 1-output critic).  False for a Tanh net, which has no per-layer path
+        (nothing changes: the caller runs it on torch autograd instead)."""
+        if self.act != "ReLU":
+            return False
         if self._f32 is None:
-            return
+            return True
         self._f32 = None
         self.in_pad = _round_up(self.in_dim, 32)
         w0 = self.w[0]
         self.w[0] = torch.zeros(w0.shape[0], self.in_pad, dtype=w0.dtype, device=w0.device)
         self._built.clear()                                         # (a re-allocated operand: nothing built counts any more)
         self.refresh()
+        return True
 
     def _log_path(self, net):
         """One INFO line per net shape (logger `trajopt_grpo_amd`) saying which kernels run it, and a WARNING when a net falls off the
@@ -257,6 +298,8 @@ class GemmMLP:
         _LOGGED_SHAPES.add(shape)
         if self._f32 is not None and self._f32.wide:
             _LOG.info("%s: fp32 chain learner at H = 256 (tg_mlp_f32w_forward / _forward_backward / tg_mlp_f32_weight_grad)", shape)
+        elif self._f32 is not None and self.act == "Tanh":
+            _LOG.info("%s Tanh: fp32 chain learner (tg_mlp_f32_forward_act / _forward_backward_act / _weight_grad)", shape)
         elif self._f32 is not None:
             _LOG.info("%s: fp32 chain learner (tg_mlp_f32_forward / _forward_backward / _weight_grad)", shape)
         elif self._chain is not None and self._bchain is not None:
@@ -367,6 +410,9 @@ class GemmMLP:
             elif f.wide:
                 N.check(N.load().tg_mlp_f32w_forward(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.table.data_ptr(), f.n_hidden, xp.shape[0],
                                                      out.data_ptr(), N.stream_ptr(xp.device)), "tg_mlp_f32w_forward")
+            elif f.act != 0:
+                N.check(N.load().tg_mlp_f32_forward_act(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.H, f.n_hidden, xp.shape[0],
+                                                        out.data_ptr(), f.act, N.stream_ptr(xp.device)), "tg_mlp_f32_forward_act")
             else:
                 N.check(N.load().tg_mlp_f32_forward(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.H, f.n_hidden, xp.shape[0],
                                                     out.data_ptr(), N.stream_ptr(xp.device)), "tg_mlp_f32_forward")
@@ -402,6 +448,9 @@ class GemmMLP:
             self._acts = [xp] + hid if keep else None
             self._bits = [None] + bits if keep else None
             return out if padded else out[:, :self.out_dim].contiguous()
+        if self.act != "ReLU":
+            raise NotImplementedError(f"GemmMLP.forward(keep={keep}) of a {self.act} net: the per-layer GEMM path applies ReLU; a {self.act} net "
+                                      "trains through forward_loss() / backward_fused() (fp32 chain learner) only")
         self._fresh("w")
         acts = [xp]
         h = xp
@@ -445,6 +494,7 @@ class GemmMLP:
         if self._f32 is not None:
             return self._forward_loss_f32(xp, kind, act, logp_old, adv, ret, norm, var, epsilon, surr_coef, critic_coef, kl_coef, sums_out,
                                           logp_old_out, norm8, ref)
+        assert self.act == "ReLU"
         self._flush_riders()                 # (a forward_loss() that was never followed by backward_fused(): its head gradient is due)
         self._fresh("chain")
         L = len(self.linears)
@@ -572,7 +622,12 @@ class GemmMLP:
         if self.fwd_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        if ref is not None:                 # (the same launches with GRPO's reference-policy penalty in the head)
+        if f.act != 0:                      # Tanh: the `_act` entry (plain head or reference penalty); everything stored, no mask bits
+            assert tmask is None and all(t is not None for t in acts + dzs)
+            N.check(lib.tg_mlp_f32_forward_backward_act(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), H, nh, rows, ptrs, zptrs, None,
+                                                        N.C.byref(a), N.C.byref(ref) if ref is not None else None, f.act,
+                                                        N.stream_ptr(dev)), "tg_mlp_f32_forward_backward_act")
+        elif ref is not None:               # (the same launches with GRPO's reference-policy penalty in the head)
             if f.res:
                 N.check(lib.tg_mlp_f32r_forward_backward_ref(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.w0.data_ptr(), f.table.data_ptr(), H,
                                                              nh, rows, ptrs, zptrs, N.ptr(tmask), N.C.byref(a), N.C.byref(ref), N.stream_ptr(dev)),
@@ -599,7 +654,8 @@ class GemmMLP:
             self.fwd_events.append((ev[0], ev[1], rows, 2 * H * self.in_dim + 4 * (nh - 1) * H * H + 4 * H * self.out_dim,
                                     ("tg::mlp_f32_wide_kernel<true" if f.wide else
                                      (f"tg::mlp_f32_res_kernel<{H},{f.in_pad // 4},true" if f.res else f"tg::mlp_f32_chain_kernel<{H},true"))
-                                    + (",true>" if ref is not None else ">")))
+                                    + (",true" if ref is not None else (",false" if f.act else ""))
+                                    + (f",{f.act}>" if f.act else ">")))
         grid = lib.tg_mlp_f32r_grid(rows) if f.res else min(nblk, -(-rows // (64 if f.wide else 256)))      # (the launchers' own grids)
         self._acts, self._bits, self._dz_head, self._tmask = [xp] + acts, dzs, dout, tmask
         assert getattr(self, "_loss_rider", None) is None, "forward_loss(sums_out=...) must be followed by backward_fused()"
@@ -808,6 +864,12 @@ class GemmMLP:
 
     @torch.no_grad()
     def backward(self, dout: torch.Tensor):
+        if self.act != "ReLU":
+            raise NotImplementedError(f"GemmMLP.backward() of a {self.act} net: the per-layer backward kernels apply the ReLU mask; a "
+                                      f"{self.act} net trains through forward_loss() / backward_fused() (fp32 chain learner) only")
+        return self._backward_relu(dout)
+
+    def _backward_relu(self, dout: torch.Tensor):
         """dout fp32 [rows][out_dim] = d loss / d output.  Accumulates into weight.grad / bias.grad (fp32)."""
         acts = self._acts
         assert acts is not None, "backward() needs forward(keep=True)"
@@ -1000,10 +1062,12 @@ def fragment_stream(net, H: int):
 # ---------------------------------------------------------------------------------------------
 # register-resident fp32 weights of the fp32 fused rollout kernel (csrc/fused_rollout_f32.hip)
 # ---------------------------------------------------------------------------------------------
-def fused_rollout_f32_supported(net, obs_dim: int, act_dim: int) -> int:
-    """Hidden width H if `net` is Linear(S,H) ReLU [Linear(H,H) ReLU]* Linear(H,A) with H in {64,128} and 1..4 hidden
-    layers (what tg_fused_rollout_f32 has kernels for), else 0."""
-    if not supports(net) or obs_dim > 32 or act_dim > 4:
+def fused_rollout_f32_supported(net, obs_dim: int, act_dim: int, activations=("ReLU",)) -> int:
+    """Hidden width H if `net` is Linear(S,H) act [Linear(H,H) act]* Linear(H,A) with act in `activations` (hidden_activation();
+    the kernels have "ReLU" and "Tanh": DeviceRollout asks for both, the default keeps the ReLU-only meaning of tg_fused_rollout_f32),
+    H in {64,128} and 1..4 hidden layers (what tg_fused_rollout_f32[_act] has kernels for), else 0."""
+    act = hidden_activation(net)
+    if act is None or act not in activations or act not in ACTIVATIONS or obs_dim > 32 or act_dim > 4:
         return 0
     lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
     H = lin[0].out_features
@@ -1115,9 +1179,10 @@ class RegisterStreamF32:
 # fp32 chain learner (csrc/mlp_f32_chain.hip): weight stream of tg_mlp_f32_forward / _forward_backward
 # ---------------------------------------------------------------------------------------------
 def f32_chain_supported(net) -> int:
-    """Hidden width H if `net` is Linear(S<=32, H) ReLU [Linear(H, H) ReLU]{0..3} Linear(H, A<=4) with H in {64, 128} -- the
-    reference's own policy shapes (pipelines/cartpole_pipeline_grpo.py:54-76, cartpole_pipeline_ppo.py:54-79) -- else 0."""
-    if not supports(net):
+    """Hidden width H if `net` is Linear(S<=32, H) act [Linear(H, H) act]{0..3} Linear(H, A<=4), act = ReLU or Tanh
+    (hidden_activation()), with H in {64, 128} -- the reference's own policy shapes (pipelines/cartpole_pipeline_grpo.py:54-76,
+    cartpole_pipeline_ppo.py:54-79) -- else 0."""
+    if hidden_activation(net) is None:
         return 0
     lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
     H = lin[0].out_features
@@ -1149,7 +1214,7 @@ class F32ResStream:
               W_1[16 t + 4 g + e][16 ko + i]            (nothing with one hidden layer)
       w0:     [8 mo][in_pad / 4 steps s][64 lanes]: W0[16 mo + i][4 s + g]              (zero beyond the inputs)
       table:  [2][128] hidden biases | [4][128] head weights (rows >= A zero) | [4] head bias | 12 zeros"""
-    wide, res = False, True
+    wide, res, act = False, True, 0                 # (act: TG_ACT_RELU -- the resident kernel is ReLU-only)
 
     def __init__(self, net):
         lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
@@ -1233,7 +1298,7 @@ class F32WideStream:
       forward, layer l = 1 .. nh - 1, block mo, piece t:  W_l[16 mo + i][16 t + 4 g + e]
       backward, layer l = nh - 1 .. 1, block ko, piece t: W_l[16 t + 4 g + e][16 ko + i]
     then the tables: [5][256] hidden biases | [4][256] head weights (rows >= A zero) | [4] head bias | 12 zeros."""
-    wide, res = True, False
+    wide, res, act = True, False, 0                 # (act: TG_ACT_RELU -- the H = 256 kernel is ReLU-only)
 
     def __init__(self, net):
         lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
@@ -1304,9 +1369,10 @@ class F32ChainStream:
       [backward blocks]  layer l = n_hh..1 (top first), output tile ko over the layer's INPUT features:
                          W_l[32 mt + F(t, kk)][32 ko + i]"""
 
-    def __init__(self, net, H: int):
+    def __init__(self, net, H: int, activation: str = "ReLU"):
         lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
         self.lin, self.H = lin, H
+        self.act = ACTIVATIONS[activation]          # the kernels' hidden activation (TG_ACT_*): the stream itself does not depend on it
         dev = lin[0].weight.device
         nh = len(lin) - 1
         self.n_hidden, self.in_dim, self.out_dim = nh, lin[0].in_features, lin[-1].out_features

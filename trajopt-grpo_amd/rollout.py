@@ -137,15 +137,16 @@ class DeviceRollout:
         H = M.fused_rollout_supported(policy.actor, self.S, self.A)
         can_fuse = bool(H) and dtype == torch.float32 and compute_dtype == torch.bfloat16
         # ... and its float32 sibling (csrc/fused_rollout_f32.hip) for fp32 policies of the reference's sizes (64 / 128
-        # wide, up to 4 hidden layers): fp32 products, weights register-resident, one workgroup per 32 envs.
-        H32 = M.fused_rollout_f32_supported(policy.actor, self.S, self.A)
+        # wide, up to 4 hidden layers, ReLU or Tanh): fp32 products, weights register-resident, one workgroup per 32 envs.
+        H32 = M.fused_rollout_f32_supported(policy.actor, self.S, self.A, activations=("ReLU", "Tanh"))
+        self._f32_act = M.ACTIVATIONS.get(M.hidden_activation(policy.actor), N.TG_ACT_RELU)
         self._fused_f32 = (not can_fuse) and bool(H32) and dtype == torch.float32 and compute_dtype in (None, torch.float32)
         if self._fused_f32:
             can_fuse, H = True, H32
         if fused and not can_fuse:
-            raise ValueError("fused rollout needs a float32 trajectory and an actor Linear(S,H) ReLU [Linear(H,H) ReLU]* "
-                             "Linear(H,A), S<=32, A<=4: H in {128,256} with compute_dtype=bfloat16, or H in {64,128} and "
-                             "1..4 hidden layers in float32")
+            raise ValueError("fused rollout needs a float32 trajectory and an actor Linear(S,H) act [Linear(H,H) act]* "
+                             "Linear(H,A), S<=32, A<=4: act = ReLU with H in {128,256} and compute_dtype=bfloat16, or act = ReLU "
+                             "or Tanh (the same for every hidden layer) with H in {64,128} and 1..4 hidden layers in float32")
         self.fused = can_fuse if fused is None else bool(fused)
         self._fused_H = H
         self._frag = None
@@ -272,7 +273,12 @@ class DeviceRollout:
         if self.step_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        if self._fused_f32:
+        if self._fused_f32 and self._f32_act != N.TG_ACT_RELU:
+            N.check(lib.tg_fused_rollout_f32_act(C.byref(self.params), C.byref(tr), self._frag.stream.data_ptr(),
+                                                 self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs, self._sigma,
+                                                 self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end, self._f32_act, st),
+                    "tg_fused_rollout_f32_act")
+        elif self._fused_f32:
             N.check(lib.tg_fused_rollout_f32(C.byref(self.params), C.byref(tr), self._frag.stream.data_ptr(),
                                              self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs, self._sigma,
                                              self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end, st),
