@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: GPU-resident rollout + PPO / GRPO update on QuadPole ("quadrotor_env.py").
 
-    python bench.py --gpus N --steps K --warmup W [--config c3|c4|c5] [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config c3|c4|c5] [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: a rollout of every env of this rank's shard (one persistent kernel:
 actor MLP on the matrix cores + sampling + dynamics + recording) followed by `learn` on that buffer.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the outputs of --dump-outputs and the
+JSON line (with the figures the timed steps record on the way: launch events, kernel clocks, socket power, collectives).  Whatever
+takes work of its own -- the CPU baseline, the fixed-work step, the stand-alone kernel probes, the sustained matrix rate and the
+other configs -- runs only with --full; the fields marked [full] below are absent (or null) without it.
 
   --config c3 (default)  BASELINE.json configs[2]: QuadPole PPO, 65,536 envs x 256 steps, the reference factory's
                          hyper-parameters (pipelines/quadpole_pipeline_ppo.py: 20-256x5-{4,1} actor-critic, cov 0.3,
@@ -27,16 +32,20 @@ Besides the contract fields the JSON line carries
   roofline          the hand-written kernel FAMILY with the most GPU time in the step (weight gradients, backward-data chain
                     or forward chain), algorithmic bytes of every launch of the timed steps / its duration by HIP events on
                     the launch stream; `kernels` has the same figures for all three families.
-  rollout_kernel    the fused rollout kernel against the MFMA roofline (2 x actor parameters flop per valid env-step).
-  dynamics_kernel   the stand-alone dynamics kernel (tg_rollout_step) at this env count, HBM roofline, timed after the run.
+  rollout_kernel    the fused rollout kernel against the MFMA roofline (2 x actor parameters flop per valid env-step);
+                    [full] `all_alive`: one more rollout with the bounds opened, its matrix-core rate without idle lanes.
+  dynamics_kernel   [full] the stand-alone dynamics kernel (tg_rollout_step) at this env count, HBM roofline, timed after the run.
   fixed work        `update_ns_per_valid_row` (learn time per valid row: does not depend on how long the policy survives) and
-                    `fixed_work_ms_per_step` (one step with the bounds opened: every env runs the full horizon, 16.8 M rows).
-  roofline.other_configs   (plain `--config c3` runs) BASELINE.json configs[1], [3], [4] -- C2, and C4's / C5's per-GPU shards -- run in the
-                    same process after the headline's timed region: value, ms_per_step, steps, env_steps_per_step, dtype, and the
-                    dominant kernel's roofline fraction of each (launches untimed in their timed regions; extra steps carry the events).
+                    [full] `fixed_work_ms_per_step` (one step with the bounds opened: every env runs the full horizon, 16.8 M rows).
+  sustained_matrix_rate   [full] the chain kernels' bare MFMA loop run for ~0.6 s after the timed region; `kernels.*.frac_of_sustained`.
+  roofline.other_configs   [full] (`--config c3` runs that no flag reshapes) BASELINE.json configs[1], [3], [4] -- C2, and C4's / C5's
+                    per-GPU shards -- run in the same process after the headline's timed region: value, ms_per_step, steps,
+                    env_steps_per_step, dtype, and the dominant kernel's roofline fraction of each (launches untimed in their timed
+                    regions; extra steps carry the events).
   dump_outputs      with --dump-outputs DIR: the directory, number of arrays and bytes written there (see dump_outputs()).
-  cpu_baseline      the CPU port of the reference path (oracle/) timed on this box's host cores over bounded samples:
+  cpu_baseline      [full] the CPU port of the reference path (oracle/) timed on this box's host cores over bounded samples:
                     all cores (<= 16), exactly 8 cores (sched_setaffinity, comparable with BASELINE.md section 2), and C1 exactly.
+  full              whether this was a --full run.
 """
 import argparse
 import json
@@ -479,8 +488,11 @@ def main():
     ap.add_argument("--updates", type=int, default=None,
                     help="updates_per_iter (c3: the PPO factory's 32; c4 / c5: GRPO's constructor default 10, grpo.py:26-35)")
     ap.add_argument("--policy-dtype", default=None, choices=["bf16", "fp32"], help="default bf16 (c2: fp32, as BASELINE says)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fixed-work", action="store_true", help="skip the all-alive (bounds opened) step after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes work of its own: the CPU baseline, the fixed-work step, the "
+                         "stand-alone kernel probes, the sustained matrix rate and the other configs (a plain run does none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fixed-work", action="store_true", help="with --full: skip the all-alive (bounds opened) step after the timed region")
     ap.add_argument("--graph", action="store_true", help="replay the T-step rollout loop as one hipGraph")
     ap.add_argument("--no-fused", action="store_true",
                     help="per-step launches (actor GEMMs + tg_rollout_step) instead of the fused persistent rollout kernel")
@@ -491,8 +503,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo only for rehearsing the multi-rank path on a single GPU (ranks share the device)")
     ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"],
-                    help="with --config c3: also run C2 and the C4 / C5 per-GPU shards after the headline's timed region and nest their "
-                         "results under roofline.other_configs (auto: when no flag reshapes the workload)")
+                    help="with --full and --config c3: also run C2 and the C4 / C5 per-GPU shards after the headline's timed region and "
+                         "nest their results under roofline.other_configs (auto: when no flag reshapes the workload)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (a fixed sample of the trajectory, the "
                          "post-update weights, the loss statistics) as DIR/<name>.npy, float32 / float64, < 64 MB in all")
@@ -501,6 +513,8 @@ def main():
                          "twice -- as a rank of the N-rank group and alone (a one-rank subgroup) -- and asserts that its trajectory "
                          "shard, PPO's global moments and the post-step weights agree (SURVEY 8e); the result rides in the JSON line")
     args = ap.parse_args()
+    if args.other_configs == "on" and not args.full:
+        ap.error("--other-configs on needs --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # bare invocation: one child process per GPU through torchrun.  This parent has made no GPU call (torch is not
@@ -529,7 +543,7 @@ def main():
             print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.config == "c3":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.config == "c3":
         progress("cpu baseline (3 legs, ~40 s) ...")
         cpu = cpu_baseline(args.horizon if args.horizon is not None else 256, 32)
         progress(f"cpu baseline: {cpu['value']:.0f} env-steps/s on {cpu['cores']} cores")
@@ -582,11 +596,11 @@ def main():
 
     # ---- the other GPU configs of BASELINE.json (C2, C4's and C5's per-GPU shards) on the same box, in the same process, after the
     # headline's timed region: their launches untimed, then a few steps with the hot kernels' launches bracketed for the roofline.
-    # Nested under `roofline` (where the driver's parser keeps objects whole).  Only for the plain headline command: any flag that
-    # reshapes the workload (--envs, --horizon, ...) is a probe run of ONE config.
+    # Nested under `roofline`.  Only with --full, and there only for the headline's own workload: any flag that reshapes it
+    # (--envs, --horizon, ...) makes a probe run of ONE config.
     plain = (args.envs is None and args.horizon is None and args.updates is None and args.policy_dtype is None and not args.graph
              and not args.no_fused and not args.no_launch_events)
-    if args.config == "c3" and (args.other_configs == "on" or (args.other_configs == "auto" and plain)):
+    if args.full and args.config == "c3" and (args.other_configs == "on" or (args.other_configs == "auto" and plain)):
         others = {}
         for name, steps, warm, ev_steps in (("c2", 200, 5, 8), ("c4", 20, 3, 2), ("c5", 20, 3, 2)):
             a2 = argparse.Namespace(**vars(args))
@@ -844,7 +858,7 @@ def run_config(args, ctx, secondary=False):
     # ---- fixed work: one step with nobody terminating (every env runs the whole horizon) ----
     progress(f"timed region done: {1e3 * dt / args.steps:.0f} ms/step")
     fixed = None
-    if not args.no_fixed_work and hasattr(make_env(), "spatial_bounds"):
+    if args.full and not args.no_fixed_work and hasattr(make_env(), "spatial_bounds"):
         mgr_open = tg.RolloutManager(lambda: make_env(True), policy, restart=restart, num_workers=G_global,
                                      num_episodes_per_worker=E, dtype=torch.float32, seed=4321, compute_dtype=cdt,
                                      fused=False if args.no_fused else None)
@@ -857,7 +871,8 @@ def run_config(args, ctx, secondary=False):
         fixed = (time.perf_counter() - f0, buf_open.device_traj.env_steps())
         del mgr_open, buf_open
 
-    dyn = dynamics_kernel_probe(tg, dev, envs_local * agents) if rank == 0 and agents == 1 and not cartpole and not secondary else None
+    probes = args.full and rank == 0 and not secondary          # the stand-alone probes below: --full runs of the headline config
+    dyn = dynamics_kernel_probe(tg, dev, envs_local * agents) if probes and agents == 1 and not cartpole else None
     if dyn is not None and args.config == "c3":
         # north_star's ">= 60 % of the HBM roofline on the dynamics kernel": reachable where the stream is HBM-resident.  At 65,536
         # envs one launch moves 12.4 MB in ~5 us: the launch is a kernel boundary (~1.5 us) plus ONE wave of work per SIMD lane
@@ -871,7 +886,7 @@ def run_config(args, ctx, secondary=False):
                        "one_launch_form = the same dynamics with the time loop INSIDE the launch (tg_rollout_forced, the teacher-forced "
                        "replay path): at 65,536 envs a plain write stream of the trajectory")
     fused_all_alive = None
-    if rank == 0 and mgr.engine.fused and agents == 1 and not cartpole and not secondary:
+    if probes and mgr.engine.fused and agents == 1 and not cartpole:
         # the fused kernel with nobody terminating (bounds opened): its matrix-core rate without idle lanes
         eng = tg.DeviceRollout(make_env(True), policy, G_local, E, restart=restart, seed=7, compute_dtype=cdt, fused=True)
         eng.run()
@@ -902,7 +917,7 @@ def run_config(args, ctx, secondary=False):
     else:
         total_steps = float(env_steps)
     sustained = None
-    if rank == 0 and probe_fams and not args.no_launch_events:
+    if args.full and rank == 0 and probe_fams and not args.no_launch_events:
         code = 1 if f32_learner else 0
         if code not in ctx.setdefault("sustained", {}):        # (once per process and dtype: the other configs' legs reuse it)
             progress("sustained matrix-rate probe (~1 s) ...")
@@ -939,6 +954,7 @@ def run_config(args, ctx, secondary=False):
             "rollout_only_env_steps_per_s": total_steps / t_roll if t_roll > 0 else None,
             "rollout_ms": 1e3 * t_roll / args.steps,
             "dump_outputs": dumped,
+            "full": args.full,
             "launch_events": None if args.no_launch_events else
                              ({"after_the_timed_region": True, "timed_steps": timed_steps} if secondary else
                               {"every_nth_step": event_every, "timed_steps": timed_steps}),
