@@ -3,6 +3,7 @@ import os
 import types
 
 import numpy as np
+import pytest
 import torch
 
 import trajopt_grpo_amd as tg
@@ -253,3 +254,24 @@ def test_ones_column_mark_follows_the_prepared_bytes_not_their_address():
     assert not M.has_ones_column(mb)
     assert M.has_ones_column(M.inherit_ones_column(mb, part))
     assert not M.has_ones_column(M.inherit_ones_column(own.index_select(0, torch.tensor([0, 1])), own))
+
+
+def test_policy_refuses_a_covariance_the_kernels_cannot_honour():
+    """policy.var feeds the sampling kernels, log_prob and the loss heads as diag(cov): off-diagonal terms (which the reference's
+    MultivariateNormal(mean, cov) would honour, actor_critic.py:131) must raise instead of being dropped silently."""
+    for cls in (tg.GaussianActor_NeuralNetwork, tg.GaussianActorCritic_NeuralNetwork):
+        pol = cls(3, 2, (8,), cov=[0.3, 0.2], device="cpu")
+        assert torch.equal(pol.var, torch.tensor([0.3, 0.2]))                      # per-dimension lists: as before
+        assert torch.equal(cls(3, 2, (8,), cov=0.5, device="cpu").var, torch.tensor([0.5, 0.5]))
+        pol.cov = torch.diag(torch.tensor([0.1, 0.4]))                            # any diagonal matrix is fine
+        assert torch.equal(pol.var, torch.tensor([0.1, 0.4]))
+        lp, _ = pol.log_prob(torch.zeros(4, 3), torch.zeros(4, 2))
+        assert lp.shape == (4,)
+        for bad in (torch.tensor([[0.3, 0.1], [0.1, 0.2]]), torch.tensor([[0.3, 0.0], [1e-6, 0.2]]), torch.ones(2, 3)):
+            pol.cov = bad
+            with pytest.raises(ValueError, match="diagonal"):
+                pol.var
+            with pytest.raises(ValueError, match="diagonal"):
+                pol.log_prob(torch.zeros(4, 3), torch.zeros(4, 2))
+            with pytest.raises(ValueError, match="diagonal"):
+                pol(np.zeros((4, 3), dtype=np.float32))

@@ -77,8 +77,13 @@ class _GaussianBase(ActorCritic):
     # ---- helpers ----------------------------------------------------------
     @property
     def var(self) -> torch.Tensor:
-        """diag(cov) as a CPU float32 vector."""
-        return torch.diagonal(self.cov).clone()
+        """diag(cov) as a CPU float32 vector.  The sampling kernels, log_prob and the loss heads all take the covariance as this
+        vector, so a covariance with off-diagonal terms (which the reference's MultivariateNormal would honour) is refused."""
+        cov = torch.as_tensor(self.cov)
+        if cov.dim() != 2 or cov.shape[0] != cov.shape[1] or bool((cov - torch.diag(torch.diagonal(cov))).any()):
+            raise ValueError(f"policy covariance must be a diagonal square matrix (the rollout and learner kernels sample and "
+                             f"score each action dimension on its own); got shape {tuple(cov.shape)}:\n{cov}")
+        return torch.diagonal(cov).clone()
 
     def to(self, device):
         self.device = torch.device(device)
