@@ -618,6 +618,21 @@ int  tg_params_differ(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t 
 int  tg_adam_step_push(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2, double eps,
                        int64_t step, int32_t zero_grads, const tg_gather_segment* d_segments, int32_t n_segments,
                        const int32_t* d_inv_start, const int32_t* d_inv_dst, void* stream);
+/* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_(params, max_norm), norm_type 2) with no host round trip.
+ * tg_grad_clip_coef: d_out2 = {norm, coef} in float32, norm = ||d_flat[0..n)||_2 and coef = min(1, max_norm / (norm + 1e-6)) formed in
+ *   float32 as torch forms it (coef == 1 exactly when nothing is clipped).  The squares are summed in float64 -- no overflow for any
+ *   finite float32 input -- as one partial per block in d_work (tg_grad_clip_workspace(n) bytes, 8-byte aligned) and the partials in
+ *   a fixed order by a second, one-block launch: no floating-point atomics, the same bytes give the same bits.  n == 0: {0, 1}
+ *   (d_flat and d_work may be NULL).  d_out2 may be a row of a larger table that the host reads later.
+ * tg_adam_step_clip / tg_adam_step_push_clip: tg_adam_step / tg_adam_step_push on g' = g * *d_coef (one float32 product, rounded
+ *   once, as g.mul_(coef) rounds it).  zero_grads == 0: g' is written back, the caller reads clipped gradients; else zeroed as before. */
+int64_t tg_grad_clip_workspace(int64_t n);
+int  tg_grad_clip_coef(const float* d_flat, int64_t n, double max_norm, float* d_out2, double* d_work, void* stream);
+int  tg_adam_step_clip(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2, double eps,
+                       int64_t step, int32_t zero_grads, const float* d_coef, void* stream);
+int  tg_adam_step_push_clip(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2,
+                            double eps, int64_t step, int32_t zero_grads, const tg_gather_segment* d_segments, int32_t n_segments,
+                            const int32_t* d_inv_start, const int32_t* d_inv_dst, const float* d_coef, void* stream);
 /* tg_mlp_f32_weight_grad with the optimizer step RIDING on its reduction launch: the thread that completes a gradient element applies
  * tg_adam_step's update to its parameter and (push tables given) tg_adam_step_push's layout writes, then leaves the gradient zeroed
  * (zero_grads) or holding the accumulated value -- what `loss.backward(); optimizer.step()` (algorithms/grpo.py:144-145) leaves, bit

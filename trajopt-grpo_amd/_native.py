@@ -204,6 +204,11 @@ SIGNATURES = {
     "tg_gather_streams": (C.c_int, [_VP, _I32, _I64, _VP, _VP]),
     "tg_params_differ": (C.c_int, [_VP, _I32, _I64, _VP, _VP]),
     "tg_adam_step_push": (C.c_int, [_VP, _I32, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I32, _VP, _I32, _VP, _VP, _VP]),
+    "tg_grad_clip_workspace": (C.c_int64, [_I64]),
+    "tg_grad_clip_coef": (C.c_int, [_VP, _I64, C.c_double, _VP, _VP, _VP]),
+    "tg_adam_step_clip": (C.c_int, [_VP, _I32, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I32, _VP, _VP]),
+    "tg_adam_step_push_clip": (C.c_int, [_VP, _I32, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I32, _VP, _I32, _VP, _VP, _VP,
+                                         _VP]),
     "tg_returns_moments_max_horizon": (C.c_int, []),
     "tg_returns_moments": (C.c_int, [_VP, _VP, _F, _VP, _I64, _I32, _I64, _VP, _VP, _VP]),
     "tg_learn_count_workspace": (C.c_int64, [_I64]),

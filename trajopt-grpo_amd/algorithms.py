@@ -86,8 +86,14 @@ class _GpuLearner(Algorithm):
     # slower (GB-sized blocks outgrow the caching allocator every time); a fixed first chunk keeps the big blocks reusable.
     chunk_rows = 1 << 22
 
-    def _setup(self, policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp=True):
+    def _setup(self, policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp=True, max_grad_norm=None):
         self.policy, self.optimizer = policy, optimizer
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
+                raise ValueError(f"max_grad_norm must be None or a finite number > 0, got {max_grad_norm!r}")
+            max_grad_norm = float(max_grad_norm)
+        self.max_grad_norm = max_grad_norm
+        self._clip_blocks, self._clip_steps = [], 0
         if chunk_rows is not None:
             self.chunk_rows = int(chunk_rows)
         elif os.environ.get("TG_CHUNK_ROWS"):
@@ -123,7 +129,11 @@ class _GpuLearner(Algorithm):
                         m._ws.default_cap = max(m._ws.default_cap, cap)
             self._rollout_engine = getattr(getattr(buffer, "rollout_manager", None), "engine", None) if ok else None
             self._check_deferred()
+            self._clip_blocks, self._clip_steps = [], 0
             self._learn(buffer)
+            if self._clip_steps and self._stats_pending is not None:
+                inner, blocks, steps = self._stats_pending, self._clip_blocks, self._clip_steps
+                self._stats_pending = lambda: {**inner(), "grad_norm": torch.cat(blocks)[:steps, 0].tolist()}
 
     def _entry_refresh(self, *nets):
         """The derived weight layouts of `nets` at the entry of learn(): rebuilt whatever the version keys say -- a weight written
@@ -295,6 +305,9 @@ class _GpuLearner(Algorithm):
             if m is not None:
                 m.refresh()
 
+    def _clip_metadata(self) -> dict:
+        return {} if self.max_grad_norm is None else {"max_grad_norm": self.max_grad_norm}
+
     def _zero_grads(self):
         """`optimizer.zero_grad()` (grpo.py:143, ppo.py:181) on the flat bucket -- skipped when the previous update's Adam launch
         already left every gradient zero (FusedAdam.step(zero_grads=True))."""
@@ -311,12 +324,40 @@ class _GpuLearner(Algorithm):
         last=False: another update of this learn() follows -- the Adam launch also zeroes the gradients it consumed (the final
         update's gradients stay in .grad, as after the reference's learn())."""
         refresher = self._optimizer_setup(*nets)
-        stepped = bool(self._fused_adam) and self._fused_adam.step(zero_grads=not last and self._adam_covers_bucket, refresher=refresher)
+        # max_grad_norm: the fused step multiplies by the device-side coefficient itself; an optimizer it does not take (and a bucket
+        # it does not cover) gets clip_grad_norm_'s own in-place scaling of the whole bucket -- by the device scalar, no host read
+        coef = self._clip_coef() if self.max_grad_norm is not None else None
+        in_step = coef is not None and bool(self._fused_adam) and self._adam_covers_bucket
+        if coef is not None and not in_step:
+            self.bucket.flat.mul_(coef)
+        stepped = bool(self._fused_adam) and self._fused_adam.step(zero_grads=not last and self._adam_covers_bucket, refresher=refresher,
+                                                                   clip_coef=coef if in_step else None)
         if not stepped:
+            if in_step:                     # (refused before any launch: nothing has been scaled yet)
+                self.bucket.flat.mul_(coef)
             self.optimizer.step()
         self._refresh(*nets)
         if stepped and not self._fused_adam.pushed:
             refresher.run()
+
+    def _clip_coef(self):
+        """tg_grad_clip_coef on the flat gradient bucket, after the all-reduce (every rank: the same bytes, the same bits): the
+        device float32 [1] holding min(1, max_grad_norm / (norm + 1e-6)).  The norm itself stays in the row next to it until
+        last_stats asks (rows of [64][2] blocks, one row per optimizer step of this learn(): nothing here visits the host)."""
+        flat = self.bucket.flat
+        if flat.dtype != torch.float32:
+            raise RuntimeError(f"max_grad_norm needs float32 gradients, the bucket holds {flat.dtype}")
+        row = self._clip_steps % 64
+        if row == 0:
+            self._clip_blocks.append(torch.empty(64, 2, dtype=torch.float32, device=flat.device))
+        out2 = self._clip_blocks[-1][row]
+        self._clip_steps += 1
+        lib = K.N.load()
+        work = self._small("clip_work", max(int(lib.tg_grad_clip_workspace(flat.numel())) // 8, 1), torch.float64, flat.device)
+        with torch.cuda.device(flat.device):
+            K.N.check(lib.tg_grad_clip_coef(flat.data_ptr(), flat.numel(), self.max_grad_norm, out2.data_ptr(), work.data_ptr(),
+                                            K.N.stream_ptr(flat.device)), "tg_grad_clip_coef")
+        return out2[1:2]
 
     def _optimizer_setup(self, *nets):
         """The fused optimizer step and the refresher of `nets`' derived layouts (None without a fused step), created on first use."""
@@ -343,6 +384,8 @@ class _GpuLearner(Algorithm):
         m = self._mlp(net)
         if not (whole_update and m is not None and m._f32 is not None) or D.rank_world(self.process_group)[1] != 1 or D._ALWAYS:
             return None                     # (TG_COLLECTIVES_AT_WORLD_1=1: the gradient all-reduce is wanted even at one rank)
+        if self.max_grad_norm is not None:
+            return None                     # (the norm needs every gradient element finished before any parameter moves)
         refresher = self._optimizer_setup(net)
         if refresher is None or not self._adam_covers_bucket:
             return None
@@ -512,16 +555,21 @@ class GRPO(_GpuLearner):
     reference evaluates the reference policy on all rows: that form cannot be combined with the masked surrogate).  The sign is the
     reference's: with the default maximize=False (descent on J as grpo.py writes it) the beta term pushes the policy AWAY from the
     reference policy -- pass maximize=True for a penalty that keeps it close.  ref_model=None or beta == 0: no reference pass, the
-    plain kernels, bit-identical to a GRPO without ref_model."""
+    plain kernels, bit-identical to a GRPO without ref_model.
+
+    max_grad_norm (a finite number > 0): `torch.nn.utils.clip_grad_norm_(policy.parameters(), max_grad_norm)` between backward() and
+    optimizer.step() of every update, on the device ("Gradient clipping"): the norm of the all-reduced gradient
+    bucket, the step on g * min(1, max_grad_norm / (norm + 1e-6)); last_stats gains "grad_norm" (the pre-clip norm of each update).
+    None: no clipping, the launches of a learner without the keyword."""
 
     def __init__(self, epsilon: float, beta: float, gamma: float, policy, optimizer, ref_model=None,
                  updates_per_iter: int = 10, *, maximize: bool = False, chunk_rows=None, autocast_dtype=None,
-                 process_group=None, fused_mlp: bool = True):
+                 process_group=None, fused_mlp: bool = True, max_grad_norm=None):
         self.epsilon, self.beta, self.gamma = epsilon, beta, gamma
         self.ref_model = _check_ref_model(ref_model, policy)
         self.updates_per_iter = updates_per_iter
         self.maximize = maximize
-        self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp)
+        self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm)
         self.old_policy = copy.deepcopy(self.policy)                        # grpo.py:48
         self._old_synced = self._actor_keys()
 
@@ -638,21 +686,24 @@ class GRPO(_GpuLearner):
 
     def metadata(self):
         return {"algorithm": "GRPO", "epsilon": self.epsilon, "beta": self.beta,
-                "updates_per_iter": self.updates_per_iter}
+                "updates_per_iter": self.updates_per_iter, **self._clip_metadata()}
 
 
 class PPO(_GpuLearner):
-    """Proximal Policy Optimization.  algorithms/ppo.py:8-225."""
+    """Proximal Policy Optimization.  algorithms/ppo.py:8-225.
+
+    max_grad_norm: as GRPO's -- one norm over the actor's and the critic's gradients together (one optimizer), before every optimizer
+    step (every minibatch's in minibatch mode); last_stats gains "grad_norm", one entry per step."""
 
     def __init__(self, epsilon: float, policy, optimizer, ref_model, updates_per_iter: int, c1: float = 0.5,
                  kl_coeff: float = 0.5, gamma: float = 0.99, lam: float = 0.95, entropy: float = 0.01,
                  batch_size: int = 64, monte_carlo: bool = True, *, chunk_rows=None, autocast_dtype=None,
-                 process_group=None, seed: int = 0, fused_mlp: bool = True):
+                 process_group=None, seed: int = 0, fused_mlp: bool = True, max_grad_norm=None):
         self.epsilon, self.c1, self.ref_model = epsilon, c1, ref_model
         self.updates_per_iter = updates_per_iter
         self.gamma, self.lam, self.entropy = gamma, lam, entropy
         self.batch_size, self.kl_coeff, self.monte_carlo = batch_size, kl_coeff, monte_carlo
-        self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp)
+        self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm)
         self.old_policy = copy.deepcopy(self.policy)                        # ppo.py:62 (never read in learn)
         self._seed = seed
         self._gen = None
@@ -811,7 +862,7 @@ class PPO(_GpuLearner):
     def metadata(self) -> dict:
         return {"algorithm": "PPO", "epsilon": self.epsilon, "c1": self.c1, "kl_coeff": self.kl_coeff,
                 "gamma": self.gamma, "lam": self.lam, "entropy": self.entropy, "batch_size": self.batch_size,
-                "updates_per_iter": self.updates_per_iter}
+                "updates_per_iter": self.updates_per_iter, **self._clip_metadata()}
 
     def save(self, path: str) -> None:
         torch.save(self.optimizer.state_dict(), os.path.join(path, "optimizer.pt"))    # ppo.py:214

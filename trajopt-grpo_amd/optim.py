@@ -137,13 +137,16 @@ class FusedAdam:
         return r
 
     @torch.no_grad()
-    def step(self, zero_grads: bool = False, refresher: "StreamRefresher" = None) -> bool:
+    def step(self, zero_grads: bool = False, refresher: "StreamRefresher" = None, clip_coef: torch.Tensor = None) -> bool:
         """One optimizer step; False (nothing done) when the fused form does not apply -- the caller then runs optimizer.step().
         zero_grads: the launch also zeroes every .grad it has consumed (the next update's optimizer.zero_grad() -- grpo.py:143,
         ppo.py:181 -- folded in); `grads_zeroed` then tells the caller that its own zeroing launch can be skipped.
         refresher: the derived weight layouts of this optimizer's nets.  Once they have been built by a gather (StreamRefresher.run),
         the step's own launch keeps them current (tg_adam_step_push: the thread that updates a weight writes it into every layout
-        position derived from it) and marks them fresh -- `self.pushed` says so; otherwise the caller runs refresher.run()."""
+        position derived from it) and marks them fresh -- `self.pushed` says so; otherwise the caller runs refresher.run().
+        clip_coef: one device float32 (tg_grad_clip_coef's coefficient) -- the step is taken on g * clip_coef (tg_adam_step[_push]_clip)
+        and a gradient that is not zeroed is left clipped.  There is no rider() form of this: the norm needs every gradient element
+        finished before any parameter moves."""
         self.grads_zeroed = False
         self.pushed = False
         if not self.usable():
@@ -154,6 +157,10 @@ class FusedAdam:
         self._build()
         lib = N.load()
         push = refresher.push_tables() if refresher is not None else None
+        if clip_coef is not None:
+            assert clip_coef.dtype == torch.float32 and clip_coef.is_cuda and clip_coef.numel() == 1
+        clip = () if clip_coef is None else (clip_coef.data_ptr(),)
+        sfx = "" if clip_coef is None else "_clip"
         for gi, ((tab, n, total), g) in enumerate(zip(self._tables, self.opt.param_groups)):
             for p in g["params"]:
                 self.opt.state[p]["step"] += 1
@@ -162,12 +169,14 @@ class FusedAdam:
             with torch.cuda.device(dev):
                 if push is not None and gi == 0:
                     seg, n_seg, inv_start, inv_dst = push
-                    N.check(lib.tg_adam_step_push(tab.data_ptr(), n, total, g["lr"], g["betas"][0], g["betas"][1], g["eps"], step,
-                                                  1 if zero_grads else 0, seg.data_ptr(), n_seg, inv_start.data_ptr(), inv_dst.data_ptr(),
-                                                  N.stream_ptr(dev)), "tg_adam_step_push")
+                    fn = getattr(lib, "tg_adam_step_push" + sfx)
+                    N.check(fn(tab.data_ptr(), n, total, g["lr"], g["betas"][0], g["betas"][1], g["eps"], step,
+                               1 if zero_grads else 0, seg.data_ptr(), n_seg, inv_start.data_ptr(), inv_dst.data_ptr(), *clip,
+                               N.stream_ptr(dev)), "tg_adam_step_push" + sfx)
                 else:
-                    N.check(lib.tg_adam_step(tab.data_ptr(), n, total, g["lr"], g["betas"][0], g["betas"][1], g["eps"], step,
-                                             1 if zero_grads else 0, N.stream_ptr(dev)), "tg_adam_step")
+                    fn = getattr(lib, "tg_adam_step" + sfx)
+                    N.check(fn(tab.data_ptr(), n, total, g["lr"], g["betas"][0], g["betas"][1], g["eps"], step,
+                               1 if zero_grads else 0, *clip, N.stream_ptr(dev)), "tg_adam_step" + sfx)
         N.RAW_PARAM_WRITES[0] += 1
         self.grads_zeroed = bool(zero_grads)
         if push is not None:
