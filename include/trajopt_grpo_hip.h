@@ -147,6 +147,18 @@ int  tg_rollout_step(const tg_env_params* p, const tg_traj* tr, int32_t t, const
  * observation, reward and mask byte are written, nothing else.  Bit-identical to the per-step launches. */
 int  tg_rollout_forced(const tg_env_params* p, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream);
 
+/* Time-limit bootstrapping, first half: the state each episode's LAST step produced (the rollout drops it: slot len of obs holds
+ * the padding's zeros) and whether the clock, not a failure, ended the episode.  For env slot i with L = len[i] in [1, T]:
+ *   d_s_final f32 [n][S], row i = Env.step(obs[:, L-1, i], act[:, L-1, i]) with step count L -- the step function of tg_env_step,
+ *                                 bit for bit (an f64 trajectory's state is rounded to f32 once, on the store);
+ *   d_timeout u8  [n],    [i]   = !failed(s_final) && (time_rule(L) || L == T): `failed` is the env's own failure test (CartPole
+ *                                 |x| > 1; QuadPole2D / QuadPole out of bounds; Pendulum: never), `time_rule` its own clock test
+ *                                 (step count >= time_trunc_step resp. max_steps).  A Pendulum episode ended by the balance rule
+ *                                 is neither: a terminal.
+ * A slot whose len is outside [1, T] gets zeros and 0.  Reads d_obs, d_act, d_len of the trajectory only; writes nothing into it.
+ * Swarm envs (p->agents > 1) are refused with TG_ERR_UNSUPPORTED. */
+int  tg_rollout_final_state(const tg_env_params* p, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout, void* stream);
+
 /* counters[0] = sum of episode lengths (= env-steps executed = sum of mask),
  * counters[1] = episodes ended.  rollout/rollout_worker.py:67-68 */
 int  tg_rollout_finish(const tg_traj* tr, void* stream);
@@ -704,6 +716,13 @@ int  tg_learn_compact(const tg_compact_args* args, void* stream);
 int  tg_scatter_rows(const float* d_src, int64_t src_stride, const int64_t* d_idx, int64_t rows, float* d_dst, void* stream);
 int  tg_ppo_returns(const float* d_rew, const float* d_values, const uint8_t* d_mask, float gamma, float lam, int monte_carlo,
                     float* d_adv, float* d_ret, int64_t n, int32_t T, double* d_moments, double* d_work, void* stream);
+/* Time-limit bootstrapping, second half: tg_ppo_returns on the rewards with gamma * d_boot[i] added to the reward of env i's last
+ * step, t == d_len[i] - 1 -- fp32, r + (gamma * boot), each operation rounded on its own -- without writing d_rew or copying it:
+ * bit-identical to tg_ppo_returns on a reward tensor augmented that way.  d_len i32 [n], d_boot f32 [n] (0 = no bootstrap; a
+ * d_len[i] outside [1, T] adds nothing).  Same two launches, same d_work / d_moments layout. */
+int  tg_ppo_returns_boot(const float* d_rew, const float* d_values, const uint8_t* d_mask, const int32_t* d_len, const float* d_boot,
+                         float gamma, float lam, int monte_carlo, float* d_adv, float* d_ret, int64_t n, int32_t T, double* d_moments,
+                         double* d_work, void* stream);
 int  tg_ppo_norm(const double* d_moments, double c1, double kl_coeff, float* d_norm8, void* stream);
 int  tg_gather_rows2(const int64_t* d_idx, int64_t rows, const float* d_src0, float* d_dst0, const float* d_src1, float* d_dst1,
                      void* stream);

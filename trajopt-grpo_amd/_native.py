@@ -19,6 +19,7 @@ ABI_VERSION = 13                     # TG_ABI_VERSION of include/trajopt_grpo_hi
 
 TG_ENV_CARTPOLE, TG_ENV_QUADPOLE2D, TG_ENV_QUADPOLE, TG_ENV_QUADROTOR12, TG_ENV_PENDULUM = 0, 1, 2, 3, 4
 TG_F32, TG_F64 = 0, 1
+TG_OK, TG_ERR_ARG, TG_ERR_HIP, TG_ERR_UNSUPPORTED = 0, -1, -2, -3
 TG_ACT_RELU, TG_ACT_TANH = 0, 1         # hidden activation of the fp32 kernels' `_act` entry points
 ENV_IDS = {"CartPole": TG_ENV_CARTPOLE, "QuadPole2D": TG_ENV_QUADPOLE2D, "QuadPole": TG_ENV_QUADPOLE,
            "Quadrotor": TG_ENV_QUADROTOR12, "Pendulum": TG_ENV_PENDULUM}
@@ -127,6 +128,7 @@ SIGNATURES = {
     "tg_rollout_begin": (C.c_int, [_P(Traj), C.c_int, C.c_int, _VP]),
     "tg_rollout_step": (C.c_int, [_P(EnvParams), _P(Traj), _I32, _VP, _I64, _P(_F), _VP, _I64, _VP]),
     "tg_rollout_forced": (C.c_int, [_P(EnvParams), _P(Traj), _I32, _I32, _VP]),
+    "tg_rollout_final_state": (C.c_int, [_P(EnvParams), _P(Traj), _VP, _VP, _VP]),
     "tg_rollout_finish": (C.c_int, [_P(Traj), _VP]),
     "tg_rollout_finish_stats_workspace": (C.c_int, []),
     "tg_rollout_finish_stats": (C.c_int, [_P(Traj), _VP, _VP, _VP, _VP]),
@@ -216,6 +218,7 @@ SIGNATURES = {
     "tg_learn_compact": (C.c_int, [C.POINTER(CompactArgs), _VP]),
     "tg_scatter_rows": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP]),
     "tg_ppo_returns": (C.c_int, [_VP, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _I64, _I32, _VP, _VP, _VP]),
+    "tg_ppo_returns_boot": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _I64, _I32, _VP, _VP, _VP]),
     "tg_ppo_norm": (C.c_int, [_VP, C.c_double, C.c_double, _VP, _VP]),
     "tg_gather_rows2": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),

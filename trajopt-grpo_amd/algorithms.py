@@ -693,12 +693,22 @@ class PPO(_GpuLearner):
     """Proximal Policy Optimization.  algorithms/ppo.py:8-225.
 
     max_grad_norm: as GRPO's -- one norm over the actor's and the critic's gradients together (one optimizer), before every optimizer
-    step (every minibatch's in minibatch mode); last_stats gains "grad_norm", one entry per step."""
+    step (every minibatch's in minibatch mode); last_stats gains "grad_norm", one entry per step.
+
+    bootstrap_truncated=True: an episode the CLOCK ended (not a failure, not Pendulum's balance terminal) has its cut return
+    completed with the critic's value of the state its last step produced ("Time-limit bootstrapping"): returns and
+    advantages are those of the rewards with gamma * V(s_final) added to the episode's last step, Monte Carlo and GAE alike, computed
+    on the device in the prologue; the trajectory's rewards are not modified.  last_stats gains "n_bootstrapped" (episodes
+    bootstrapped, over all ranks).  Needs the buffer's rollout engine (the env parameters); swarm envs are refused.  False: the
+    launches of a learner without the keyword."""
 
     def __init__(self, epsilon: float, policy, optimizer, ref_model, updates_per_iter: int, c1: float = 0.5,
                  kl_coeff: float = 0.5, gamma: float = 0.99, lam: float = 0.95, entropy: float = 0.01,
                  batch_size: int = 64, monte_carlo: bool = True, *, chunk_rows=None, autocast_dtype=None,
-                 process_group=None, seed: int = 0, fused_mlp: bool = True, max_grad_norm=None):
+                 process_group=None, seed: int = 0, fused_mlp: bool = True, max_grad_norm=None, bootstrap_truncated: bool = False):
+        if not isinstance(bootstrap_truncated, bool):
+            raise ValueError(f"bootstrap_truncated must be True or False, got {bootstrap_truncated!r}")
+        self.bootstrap_truncated = bootstrap_truncated
         self.epsilon, self.c1, self.ref_model = epsilon, c1, ref_model
         self.updates_per_iter = updates_per_iter
         self.gamma, self.lam, self.entropy = gamma, lam, entropy
@@ -753,7 +763,33 @@ class PPO(_GpuLearner):
         self._optimizer_step(actor, critic, last=last)
         sums_out.append(both)
 
+    def _bootstrap_params(self, buffer):
+        """The env parameters tg_rollout_final_state steps with: those of the engine that rolled the buffer's trajectory out."""
+        engine = getattr(getattr(buffer, "rollout_manager", None), "engine", None)
+        params = getattr(engine, "params", None)
+        if params is None:
+            raise ValueError("PPO(bootstrap_truncated=True) re-steps each episode's last transition with the env parameters of "
+                             "buffer.rollout_manager.engine: this buffer has no rollout engine (hand-built tensors?)")
+        if int(params.agents) > 1:
+            raise ValueError(f"PPO(bootstrap_truncated=True) does not support swarm envs (agents={int(params.agents)}): a swarm episode "
+                             "ends when any of its bodies does, which a body's own final state does not tell")
+        return params
+
+    def _bootstrap_values(self, params, traj, critic, m_c):
+        """(b f32 [n], timeout u8 [n]): b[i] = V(s_final[i]) where the clock ended episode i, else 0 -- the re-step launch, the
+        critic's input rows prepared as the valid rows are, one no-grad pass over n rows, one multiply.  Enqueued; no host read."""
+        n, dev = traj.n, traj.mask.device
+        s_final, timeout = K.rollout_final_state(params, traj, self._small("boot_state", n * traj.S, torch.float32, dev).view(n, traj.S),
+                                                 self._small("boot_timeout", n, torch.uint8, dev))
+        if m_c is not None:
+            xin = m_c.prepare_input(s_final, out=self._small("boot_xin", n * m_c.in_pad, m_c.cd, dev).view(n, m_c.in_pad))
+            v = m_c.forward(xin, keep=False, padded=True)[:, 0]
+        else:
+            v = self._forward(critic, s_final).reshape(-1)
+        return torch.mul(v, timeout, out=self._small("boot_value", n, torch.float32, dev)), timeout
+
     def _learn(self, buffer) -> None:
+        boot_params = self._bootstrap_params(buffer) if self.bootstrap_truncated else None
         traj = device_trajectory(buffer, self.policy.device)
         var = self.policy.var
         T, n = traj.T, traj.n
@@ -796,7 +832,15 @@ class PPO(_GpuLearner):
             K.scatter_rows(out, idx[lo:hi], V)
         # ppo.py:100-124 + the masked moments of :138-139 in two launches; the ranks' sums in one all-reduce; the normalisation
         # constants and 1 / n on the device (tg_ppo_norm): nothing of this visits the host
-        moments = K.ppo_returns(rew, V, traj.mask, self.gamma, self.lam, self.monte_carlo, adv_full, ret_full, work)
+        n_boot = None
+        if boot_params is None:
+            moments = K.ppo_returns(rew, V, traj.mask, self.gamma, self.lam, self.monte_carlo, adv_full, ret_full, work)
+        else:
+            # time-limit bootstrapping: the same two launches on r + gamma * V(s_final) at each clock-ended episode's last step
+            boot, timeout = self._bootstrap_values(boot_params, traj, critic, m_c)
+            moments = K.ppo_returns_boot(rew, V, traj.mask, traj.len, boot, self.gamma, self.lam, self.monte_carlo, adv_full, ret_full, work)
+            n_boot = timeout.sum(dtype=torch.int64).reshape(1)              # (a new tensor: read when last_stats is)
+            D.allreduce_sum_(n_boot, self.process_group, "n_bootstrapped")
         D.allreduce_sum_(moments, self.process_group, "ppo_moments")
         norm8 = K.ppo_norm(moments, self.c1, self.kl_coeff, out=self._small("norm8", 8, torch.float32, dev))
         self.norm8 = norm8                                                  # (diagnostics: this learn()'s constants, on the device)
@@ -855,14 +899,18 @@ class PPO(_GpuLearner):
                 nn = S[:, 3]
                 a_loss, c_loss, kl = -S[:, 0] / nn, S[:, 1] / nn, S[:, 2] / nn
                 total = a_loss + c1 * c_loss - ent_c * ent + kl_c * kl
-                return {"actor_loss": a_loss.tolist(), "critic_loss": c_loss.tolist(), "kl_div": kl.tolist(),
-                        "total_loss": total.tolist(), "entropy": ent, "n_valid": float(n_dev)}
+                out = {"actor_loss": a_loss.tolist(), "critic_loss": c_loss.tolist(), "kl_div": kl.tolist(),
+                       "total_loss": total.tolist(), "entropy": ent, "n_valid": float(n_dev)}
+                if n_boot is not None:
+                    out["n_bootstrapped"] = int(n_boot.item())
+                return out
             self._stats_pending = stats
 
     def metadata(self) -> dict:
         return {"algorithm": "PPO", "epsilon": self.epsilon, "c1": self.c1, "kl_coeff": self.kl_coeff,
                 "gamma": self.gamma, "lam": self.lam, "entropy": self.entropy, "batch_size": self.batch_size,
-                "updates_per_iter": self.updates_per_iter, **self._clip_metadata()}
+                "updates_per_iter": self.updates_per_iter, **self._clip_metadata(),
+                **({"bootstrap_truncated": True} if self.bootstrap_truncated else {})}
 
     def save(self, path: str) -> None:
         torch.save(self.optimizer.state_dict(), os.path.join(path, "optimizer.pt"))    # ppo.py:214

@@ -48,6 +48,10 @@ struct StepOut {
 // of CONSECUTIVE balanced steps after which the fp64-accumulated `_time_balanced` first exceeds the limit.  The
 // rollout kernels keep the running count (as -len[env] while the episode runs).
 
+// Time-limit bootstrapping (tg_rollout_final_state) needs to know WHY an episode ended: every env states the two clauses of its
+// `truncated` separately as well -- failed(o, c): the failure test on the new state; time_rule(steps_after, c): the clock test.
+// The same comparisons as in step(), which does not call them (its code is what it was).
+
 // ---------------------------------------------------------------------------
 // CartPole swing-up.  cartpole_env.py:48-49, 51-92, 138-182.
 // ---------------------------------------------------------------------------
@@ -103,6 +107,9 @@ template <typename R> struct CartPoleEnv {
         reward = r;
         return out;
     }
+
+    __device__ static inline bool failed(const R (&o)[S], const C&) { return Math<R>::abs_(o[0]) > (R)1; }          // :168
+    __device__ static inline bool time_rule(int steps_after, const C& c) { return steps_after >= c.time_trunc_step; }
 
     // reset: theta0 ~ U(-pi, pi); state [0, 0, sin, cos, 0].  :102-119
     __device__ static inline void reset(const uint32_t (&rnd)[4], R (&o)[S]) {
@@ -184,6 +191,11 @@ template <typename R> struct QuadPole2DEnv {
         reward = r;
         return out;
     }
+
+    __device__ static inline bool failed(const R (&o)[S], const C& c) {                                              // :1020-1022
+        return (o[0] < -c.bound) || (o[0] > c.bound) || (o[1] < -c.bound) || (o[1] > c.bound);
+    }
+    __device__ static inline bool time_rule(int steps_after, const C& c) { return steps_after >= c.max_steps; }
 
     // reset: phi0 ~ U(-pi, pi); quad [0,0,0,0,0,1,0], pend [sin, cos, 0].  :930-961
     __device__ static inline void reset(const uint32_t (&rnd)[4], R (&o)[S]) {
@@ -354,6 +366,14 @@ template <typename R> struct QuadPoleEnv {
         return out;
     }
 
+    __device__ static inline bool failed(const R (&o)[S], const C& c) {                                              // :614-622
+        bool oob = false;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) oob = oob || (o[i] < -c.bound) || (o[i] > c.bound);
+        return oob;
+    }
+    __device__ static inline bool time_rule(int steps_after, const C& c) { return steps_after >= c.max_steps; }
+
     // reset: alpha, beta ~ U(-1,1); q_p = normalise(q_y (x) q_x); everything else 0 / identity.  :530-576
     __device__ static inline void reset(const uint32_t (&rnd)[4], R (&o)[S]) {
         const double al = -1.0 + 2.0 * Philox::u01d(rnd[0], rnd[1]);
@@ -421,6 +441,10 @@ template <typename R> struct PendulumEnv {
         reward = r;
         return out;
     }
+
+    // never fails; the balance rule (a real terminal) is neither clause
+    __device__ static inline bool failed(const R (&)[S], const C&) { return false; }
+    __device__ static inline bool time_rule(int steps_after, const C& c) { return steps_after >= c.time_trunc_step; }
 
     // reset: theta0 ~ U(pi - 0.05, pi + 0.05), or U(-pi, pi) with swingup; state [sin, cos, 0].  :86-106
     __device__ static inline void reset(const uint32_t (&rnd)[4], R (&o)[S]) { reset(rnd, o, 0); }

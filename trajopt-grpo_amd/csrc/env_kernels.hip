@@ -225,6 +225,38 @@ __global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c, R
     if (in_range) len[i] = my_len;
 }
 
+// ---------------------------------------------------------------------------
+// the state after an episode's last step, and whether the clock ended it (tg_rollout_final_state)
+// ---------------------------------------------------------------------------
+// The rollout kernels drop the state an episode's last step produced (slot L of obs holds the padding's zeros).  One lane per env
+// re-steps the last recorded transition -- Env::step on (obs[:, L-1, i], act[:, L-1, i]) with steps_after = L: the same body, so
+// the same bits as step_kernel gives for that input -- and writes it as an f32 row, with the time-limit flag
+// !failed(s_final) && (time_rule(L) || L == T).  A slot without a finished episode (len outside [1, T]) reads step 0 (a valid
+// address) and writes zeros / 0.
+template <typename Env, typename R>
+__global__ __launch_bounds__(256) void final_state_kernel(typename Env::C c, const R* __restrict__ obs, const float* __restrict__ act,
+                                                          const int32_t* __restrict__ len, int64_t n, int32_t T,
+                                                          float* __restrict__ s_final, uint8_t* __restrict__ timeout) {
+    constexpr int S = Env::S, A = Env::A;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t T1 = (int64_t)T + 1;
+    const int32_t L = len[i];
+    const bool ended = L >= 1 && L <= T;
+    const int32_t t = ended ? L - 1 : 0;
+    R s[S], o[S];
+    float a[A];
+#pragma unroll
+    for (int k = 0; k < S; ++k) s[k] = obs[(k * T1 + t) * n + i];
+#pragma unroll
+    for (int k = 0; k < A; ++k) a[k] = act[((int64_t)k * T + t) * n + i];
+    R r;
+    (void)Env::step(s, a, c, t + 1, o, r);
+#pragma unroll
+    for (int k = 0; k < S; ++k) s_final[i * S + k] = ended ? (float)o[k] : 0.0f;
+    timeout[i] = (ended && !Env::failed(o, c) && (Env::time_rule(L, c) || L == T)) ? 1 : 0;
+}
+
 // sum of episode lengths (= env-steps executed = sum of mask) and #episodes ended
 __global__ __launch_bounds__(256) void rollout_finish_kernel(const int32_t* __restrict__ len, int64_t n,
                                                              uint64_t* __restrict__ counters) {
@@ -419,6 +451,17 @@ static int forced_dispatch(const tg_env_params* p, const tg_traj* tr, int32_t t_
     hipLaunchKernelGGL((rollout_forced_kernel<EnvT<R>, R>), dim3((unsigned)ceil_div(tr->n, 64)), dim3(64), 0, st, c, (R*)tr->d_obs,
                        (const float*)tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t_begin, t_end, p->agents);
     TG_LAUNCH_CHECK("tg_rollout_forced");
+    return TG_OK;
+}
+
+template <template <typename> class EnvT, typename R>
+static int final_state_dispatch(const tg_env_params* p, const tg_traj* tr, float* s_final, uint8_t* timeout, hipStream_t st) {
+    int block;
+    dim3 grid = env_grid(tr->n, block);
+    auto c = EnvT<R>::C::make(*p);
+    hipLaunchKernelGGL((final_state_kernel<EnvT<R>, R>), grid, dim3(block), 0, st, c, (const R*)tr->d_obs, (const float*)tr->d_act,
+                       (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
+    TG_LAUNCH_CHECK("tg_rollout_final_state");
     return TG_OK;
 }
 
@@ -623,6 +666,19 @@ int tg_rollout_forced(const tg_env_params* p, const tg_traj* tr, int32_t t_begin
                "tg_rollout_forced: agents=%d must be a power of two <= 64 dividing n", p->agents);
     if (t_begin == t_end) return TG_OK;
 #define CALL(E, R) forced_dispatch<E, R>(p, tr, t_begin, t_end, (hipStream_t)stream)
+    TG_ENV_SWITCH(p->env_id, tr->dtype, CALL)
+#undef CALL
+}
+
+int tg_rollout_final_state(const tg_env_params* p, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout, void* stream) {
+    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_len && d_s_final && d_timeout, "tg_rollout_final_state: null pointer");
+    TG_REQUIRE(tr->n > 0 && tr->horizon > 0, "tg_rollout_final_state: bad sizes n=%lld T=%d", (long long)tr->n, tr->horizon);
+    TG_REQUIRE(tr->horizon == p->max_steps, "tg_rollout_final_state: trajectory horizon %d != env.max_steps %d", tr->horizon,
+               p->max_steps);
+    if (p->agents > 1)
+        return set_error(TG_ERR_UNSUPPORTED, "tg_rollout_final_state: swarm envs (agents=%d) are not supported: a swarm episode ends "
+                         "when any of its bodies does, which a body's own final state does not tell", p->agents);
+#define CALL(E, R) final_state_dispatch<E, R>(p, tr, d_s_final, d_timeout, (hipStream_t)stream)
     TG_ENV_SWITCH(p->env_id, tr->dtype, CALL)
 #undef CALL
 }

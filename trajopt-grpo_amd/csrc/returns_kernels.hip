@@ -135,12 +135,22 @@ __global__ __launch_bounds__(256) void env_moments_kernel(const float* __restric
 // [T][n], then the lane reads its own column back in ascending time for the fp64 sums (same-thread store -> load: program order).
 // work: f64 [3][2 n]: plane j = {count, sum, sum of squares}, advantages in columns [0, n), returns in [n, 2 n) -- the layout
 // group_moments_kernel reduces as two groups of n.
-template <bool kGae>
+// kBoot (tg_ppo_returns_boot): time-limit bootstrapping -- the reward of the env's last step, t == len[i] - 1, is read as
+// r + gamma * boot[i] (two separately rounded fp32 operations) before the recurrence sees it; rew itself is not written.
+template <bool kGae, bool kBoot = false>
 __global__ __launch_bounds__(256) void ppo_returns_kernel(const float* __restrict__ rew, const float* __restrict__ val,
                                                           const uint8_t* __restrict__ mask, float gamma, float lam, float* adv,
-                                                          float* ret, int64_t n, int32_t T, double* __restrict__ work) {
+                                                          float* ret, int64_t n, int32_t T, double* __restrict__ work,
+                                                          const int32_t* __restrict__ len = nullptr,
+                                                          const float* __restrict__ boot = nullptr) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    int32_t t_boot = -1;     // (a slot without a finished episode: no step gets the bonus)
+    float bonus = 0.0f;
+    if constexpr (kBoot) {
+        t_boot = len[i] - 1;
+        bonus = rn_mul(gamma, boot[i]);
+    }
     float carry = 0.0f;      // Monte Carlo: (gamma * R[t+1]) * m[t+1]
     float next_v_m = 0.0f;   // GAE: V[t+1] * m[t+1]
     float next_a_m = 0.0f;   // GAE: (gamma*lam*A[t+1]) * m[t+1]
@@ -164,6 +174,9 @@ __global__ __launch_bounds__(256) void ppo_returns_kernel(const float* __restric
                 const int32_t t = t_hi - 1 - k;
                 const int64_t idx = (int64_t)t * n + i;
                 const float mf = (float)m[k];
+                if constexpr (kBoot) {
+                    if (t == t_boot) r[k] = rn_add(r[k], bonus);
+                }
                 if constexpr (kGae) {                            // gae_scan_kernel's step
                     float a;
                     if (t == T - 1) {
@@ -329,6 +342,26 @@ int tg_ppo_returns(const float* d_rew, const float* d_values, const uint8_t* d_m
     // the per-env partials as two groups of n (advantages | returns): tg_masked_moments' group stage, once
     hipLaunchKernelGGL(group_moments_kernel, dim3(2), dim3(256), 0, st, d_work, 2 * n, n, d_moments);
     TG_LAUNCH_CHECK("tg_ppo_returns(group)");
+    return TG_OK;
+}
+
+int tg_ppo_returns_boot(const float* d_rew, const float* d_values, const uint8_t* d_mask, const int32_t* d_len, const float* d_boot,
+                        float gamma, float lam, int monte_carlo, float* d_adv, float* d_ret, int64_t n, int32_t T, double* d_moments,
+                        double* d_work, void* stream) {
+    TG_REQUIRE(d_rew && d_values && d_mask && d_len && d_boot && d_adv && d_ret && d_moments && d_work, "tg_ppo_returns_boot: null pointer");
+    TG_REQUIRE(n > 0 && T > 0, "tg_ppo_returns_boot: bad sizes n=%lld T=%d", (long long)n, T);
+    TG_REQUIRE(d_adv != d_ret, "tg_ppo_returns_boot: adv and ret must be distinct buffers");
+    hipStream_t st = (hipStream_t)stream;
+    const int block = n <= ((int64_t)1 << 18) ? 64 : 256;
+    if (monte_carlo)
+        hipLaunchKernelGGL((ppo_returns_kernel<false, true>), dim3((unsigned)ceil_div(n, block)), dim3(block), 0, st, d_rew, d_values, d_mask,
+                           gamma, lam, d_adv, d_ret, n, T, d_work, d_len, d_boot);
+    else
+        hipLaunchKernelGGL((ppo_returns_kernel<true, true>), dim3((unsigned)ceil_div(n, block)), dim3(block), 0, st, d_rew, d_values, d_mask,
+                           gamma, lam, d_adv, d_ret, n, T, d_work, d_len, d_boot);
+    TG_LAUNCH_CHECK("tg_ppo_returns_boot");
+    hipLaunchKernelGGL(group_moments_kernel, dim3(2), dim3(256), 0, st, d_work, 2 * n, n, d_moments);
+    TG_LAUNCH_CHECK("tg_ppo_returns_boot(group)");
     return TG_OK;
 }
 

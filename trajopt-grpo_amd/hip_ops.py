@@ -145,6 +145,48 @@ def ppo_returns(rew, values, mask, gamma: float, lam: float, monte_carlo: bool, 
     return moments
 
 
+def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: torch.Tensor = None):
+    """tg_rollout_final_state on a DeviceTrajectory: (s_final f32 [n][S], timeout u8 [n]) -- the state each episode's last step
+    produced (Env.step on obs[:, len-1], act[:, len-1]: tg_env_step's bits) and whether the clock, not a failure, ended the episode.
+    params: the env's tg_env_params (DeviceRollout.params / Env.native_params()).  A swarm env is refused: ValueError."""
+    N.require_cuda(traj.obs, traj.act, traj.len, s_final, timeout)
+    assert traj.obs.is_contiguous() and traj.act.is_contiguous() and traj.len.is_contiguous() and traj.len.dtype == torch.int32
+    dev = traj.obs.device
+    if s_final is None:
+        s_final = torch.empty(traj.n, traj.S, dtype=torch.float32, device=dev)
+    if timeout is None:
+        timeout = torch.empty(traj.n, dtype=torch.uint8, device=dev)
+    assert s_final.dtype == torch.float32 and s_final.is_contiguous() and s_final.numel() == traj.n * traj.S
+    assert timeout.dtype == torch.uint8 and timeout.is_contiguous() and timeout.numel() == traj.n
+    tr = traj.native()
+    rc = N.load().tg_rollout_final_state(C.byref(params), C.byref(tr), s_final.data_ptr(), timeout.data_ptr(), _st(traj.obs))
+    if rc == N.TG_ERR_UNSUPPORTED:
+        raise ValueError(N.load().tg_last_error().decode("utf-8", "replace"))
+    N.check(rc, "tg_rollout_final_state")
+    return s_final, timeout
+
+
+def ppo_returns_boot(rew, values, mask, length, boot, gamma: float, lam: float, monte_carlo: bool, adv: torch.Tensor, ret: torch.Tensor,
+                     work: torch.Tensor = None) -> torch.Tensor:
+    """tg_ppo_returns_boot: ppo_returns() on the rewards with gamma * boot[i] added to the reward of env i's last step
+    (t == length[i] - 1; fp32, each operation rounded on its own) -- `rew` is read, not written.  length i32 [n], boot f32 [n]."""
+    N.require_cuda(rew, values, mask, length, boot, adv, ret, work)
+    T, n = rew.shape
+    for t in (rew, values, adv, ret):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == T * n
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == T * n
+    assert length.dtype == torch.int32 and length.is_contiguous() and length.numel() == n
+    assert boot.dtype == torch.float32 and boot.is_contiguous() and boot.numel() == n
+    if work is None:
+        work = torch.empty(6 * n, dtype=torch.float64, device=rew.device)
+    assert work.dtype == torch.float64 and work.numel() >= 6 * n
+    moments = torch.empty(2, 3, dtype=torch.float64, device=rew.device)
+    N.check(N.load().tg_ppo_returns_boot(rew.data_ptr(), values.data_ptr(), mask.data_ptr(), length.data_ptr(), boot.data_ptr(), float(gamma),
+                                         float(lam), 1 if monte_carlo else 0, adv.data_ptr(), ret.data_ptr(), n, T, moments.data_ptr(),
+                                         work.data_ptr(), _st(rew)), "tg_ppo_returns_boot")
+    return moments
+
+
 def ppo_norm(moments: torch.Tensor, c1: float, kl_coeff: float, out: torch.Tensor = None) -> torch.Tensor:
     """tg_ppo_norm: f32 [8] = {adv mean, 1 / (adv std + 1e-8), ret mean, 1 / (ret std + 1e-8), -1 / n, c1 / n, kl_coeff / n, n} on the
     device (what the loss heads read through `norm8=`)."""

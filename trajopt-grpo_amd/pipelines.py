@@ -165,10 +165,11 @@ def create_cartpole_pipeline_grpo(test_name, checkpoint_name, env_fn=None, polic
 
 
 def _ppo_pipeline(env_fn, policy, lr, updates, gamma, num_workers, episodes, test_name, checkpoint_name, algorithm,
-                  rollout_manager, buffer, visualizer, publisher, logger, load_path):
+                  rollout_manager, buffer, visualizer, publisher, logger, load_path, bootstrap_truncated=False):
     algorithm = algorithm or PPO(epsilon=0.2, c1=0.5, kl_coeff=0.5, policy=policy,
                                  optimizer=torch.optim.Adam(policy.parameters(), lr=lr), ref_model=None,
-                                 updates_per_iter=updates, gamma=gamma, lam=0.95, entropy=0.01, batch_size=None)
+                                 updates_per_iter=updates, gamma=gamma, lam=0.95, entropy=0.01, batch_size=None,
+                                 bootstrap_truncated=bootstrap_truncated)
     rollout_manager = rollout_manager or RolloutManager(env_fn=env_fn, worker_class=RolloutWorker, policy=policy,
                                                         num_workers=num_workers, num_episodes_per_worker=episodes)
     return _assemble(test_name, checkpoint_name, env_fn, policy, algorithm, rollout_manager, buffer, visualizer,
@@ -177,30 +178,30 @@ def _ppo_pipeline(env_fn, policy, lr, updates, gamma, num_workers, episodes, tes
 
 def create_cartpole_pipeline_ppo(test_name, checkpoint_name, env_fn=None, policy=None, algorithm=None,
                                  rollout_manager=None, buffer=None, visualizer=None, publisher=None, logger=None,
-                                 load_path=None) -> Pipeline:
+                                 load_path=None, *, bootstrap_truncated=False) -> Pipeline:
     """pipelines/cartpole_pipeline_ppo.py:21-108 defaults."""
     env_fn = env_fn or (lambda: CartPole())
     policy = policy or GaussianActorCritic_NeuralNetwork(input_dim=5, output_dim=1, hidden_dims=(128, 128, 128), cov=0.5)
     return _ppo_pipeline(env_fn, policy, 2e-4, 24, 0.99, 10, 8, test_name, checkpoint_name, algorithm, rollout_manager,
-                         buffer, visualizer, publisher, logger, load_path)
+                         buffer, visualizer, publisher, logger, load_path, bootstrap_truncated=bootstrap_truncated)
 
 
 def create_quadpole2d_pipeline_ppo(test_name, checkpoint_name, env_fn=None, policy=None, algorithm=None,
                                    rollout_manager=None, buffer=None, visualizer=None, publisher=None, logger=None,
-                                   load_path=None) -> Pipeline:
+                                   load_path=None, *, bootstrap_truncated=False) -> Pipeline:
     """pipelines/quadpole2d_pipeline_ppo.py defaults."""
     env_fn = env_fn or (lambda: QuadPole2D())
     policy = policy or GaussianActorCritic_NeuralNetwork(input_dim=10, output_dim=2, hidden_dims=(128, 128, 128), cov=0.5)
     return _ppo_pipeline(env_fn, policy, 2e-4, 24, 0.99, 10, 8, test_name, checkpoint_name, algorithm, rollout_manager,
-                         buffer, visualizer, publisher, logger, load_path)
+                         buffer, visualizer, publisher, logger, load_path, bootstrap_truncated=bootstrap_truncated)
 
 
 def create_quadpole_pipeline_ppo(test_name, checkpoint_name, env_fn=None, policy=None, algorithm=None,
                                  rollout_manager=None, buffer=None, visualizer=None, publisher=None, logger=None,
-                                 load_path=None) -> Pipeline:
+                                 load_path=None, *, bootstrap_truncated=False) -> Pipeline:
     """pipelines/quadpole_pipeline_ppo.py:21-109 defaults."""
     env_fn = env_fn or (lambda: QuadPole())
     policy = policy or GaussianActorCritic_NeuralNetwork(input_dim=20, output_dim=4,
                                                          hidden_dims=(256, 256, 256, 256, 256), cov=0.3)
     return _ppo_pipeline(env_fn, policy, 3e-4, 32, 0.999, 10, 5, test_name, checkpoint_name, algorithm, rollout_manager,
-                         buffer, visualizer, publisher, logger, load_path)
+                         buffer, visualizer, publisher, logger, load_path, bootstrap_truncated=bootstrap_truncated)
