@@ -211,6 +211,51 @@ int  tg_fused_rollout_f32_act(const tg_env_params* p, const tg_traj* tr, const f
 /* d_rng[1] += 1 (enqueued; one thread) */
 int  tg_rng_advance(uint64_t* d_rng, void* stream);
 
+/* ---- Per-env domain randomisation of the physical parameters ----
+ * Env slot i of a rollout steps its OWN vehicle: the reference env constructed with slot i's parameters, every derived constant
+ * (hover thrust, Lq / I, mp / (m0 + mp), ...) following them.  The parameters live in a device table
+ *   d_ptab f64 [12][n]   (env fastest): column i = the p[] of tg_env_params for slot i
+ * which tg_env_randomize fills and the `_dr` entry points read next to `p` (`p` still supplies env_id, max_steps,
+ * time_trunc_step, agents and timestep, and the nominal p[] the table scales).
+ *
+ * tg_env_randomize, one launch: row r of the table = p->p[r], times -- when r == index[k] for some k < count -- the factor
+ *   f_k(i) = lo[k] + (hi[k] - lo[k]) * u01d(w[2 (k & 1)], w[2 (k & 1) + 1])                      (IEEE double, no contraction)
+ *   w      = Philox4x32-10(key = seed ^ (spec->seed * 0x9E3779B97F4A7C15), counter = ((key_offset + i) / key_div, 0xFFFFFFFE - k / 2, stream_id))
+ *   u01d(a, b) = ((a << 32 | b) >> 11) * 2^-53
+ * with the seed, stream_id, key_offset and key_div of the rollout's tg_env_reset: parameters are re-drawn with every rollout, do not
+ * depend on how envs are sharded over ranks, and the episodes of a `restart` group (key_div = E) share one vehicle as they share one
+ * initial state.  The counter's third word ("sub") counts down from 0xFFFFFFFE, two parameters per draw: the reset uses 0xFFFFFFFF
+ * and time step t uses t, so no draw is shared.  Refused (TG_ERR_ARG, nothing launched): a null table, count outside [0, 12], an
+ * index outside [0, 12) or listed twice, a factor range that is not finite with 0 < lo <= hi. */
+typedef struct tg_randomize_spec {
+    int32_t  count;        /* randomised parameters, <= 12 */
+    int32_t  index[12];    /* which p[] each of them scales */
+    double   lo[12];       /* factor range of each: finite, 0 < lo <= hi */
+    double   hi[12];
+    uint64_t seed;         /* combined with the rollout seed (above) */
+} tg_randomize_spec;
+int  tg_env_randomize(const tg_env_params* p, const tg_randomize_spec* spec, double* d_ptab, int64_t n, uint64_t seed,
+                      uint64_t stream_id, int64_t key_offset, int64_t key_div, void* stream);
+
+/* The rollout entry points with the table: the same arguments plus d_ptab (f64 [12][tr->n], not NULL), the same kernels except that
+ * the lane that owns env slot i builds its constants from column i at kernel entry (the fused and teacher-forced kernels keep them
+ * for all their steps) instead of taking one set by value.  A table whose every column is p->p gives the plain entry point's
+ * trajectory bit for bit. */
+int  tg_rollout_step_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean,
+                        int64_t mean_row_stride, const float* sigma, const uint64_t* d_rng, int64_t env_offset, void* stream);
+int  tg_rollout_forced_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream);
+int  tg_rollout_final_state_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
+                               void* stream);
+int  tg_fused_rollout_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+                         int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                         int32_t t_begin, int32_t t_end, void* stream);
+int  tg_fused_rollout_f32_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                             int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                             int64_t env_offset, int32_t t_begin, int32_t t_end, void* stream);
+int  tg_fused_rollout_f32_act_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                                 int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                                 int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, void* stream);
+
 /* ---- returns / advantages (algorithms/grpo.py:66-74,110-115; algorithms/ppo.py:93-139) ---- */
 
 /* reward-to-go reverse scan, fp32, bit-for-bit the reference recurrence:

@@ -2,7 +2,10 @@
 """End-to-end learning check: PPO with the reference factories' hyper-parameters but 4,096 parallel episodes per
 epoch instead of 50-80.
 
-    python3 tools/train_ppo.py [epochs] [CartPole|QuadPole2D|QuadPole] [bf16|fp32]
+    python3 tools/train_ppo.py [epochs] [CartPole|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
+
+--randomize (repeatable): per-env domain randomisation, e.g. `--randomize mass=0.8:1.25 --randomize tether_length=0.5:2` -- every
+env slot draws its own factor on that physical parameter in every rollout (Env.randomize).
 
 CartPole / QuadPole2D (pipelines/cartpole_pipeline_ppo.py, quadpole2d_pipeline_ppo.py): 128x3 actor-critic, cov 0.5,
 eps 0.2, gamma 0.99, 24 full-batch updates, Adam 2e-4 (published curves: -37 -> ~800 and -70 -> ~1047).
@@ -17,7 +20,27 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import trajopt_grpo_amd as tg  # noqa: E402
 
 
+def pop_randomize(argv):
+    """Removes every `--randomize name=lo:hi` from argv; -> {name: (lo, hi)}."""
+    ranges, rest, k = {}, [], 0
+    while k < len(argv):
+        if argv[k] == "--randomize" or argv[k].startswith("--randomize="):
+            item = argv[k].split("=", 1)[1] if argv[k].startswith("--randomize=") else (argv[k + 1] if k + 1 < len(argv) else "")
+            k += 1 if argv[k].startswith("--randomize=") else 2
+            try:
+                name, rng = item.split("=", 1)
+                lo, hi = rng.split(":", 1)
+                ranges[name] = (float(lo), float(hi))
+            except ValueError:
+                raise SystemExit(f"--randomize expects name=lo:hi, got {item!r}")
+        else:
+            rest.append(argv[k])
+            k += 1
+    return ranges, rest
+
+
 def main():
+    ranges, sys.argv[1:] = pop_randomize(sys.argv[1:])
     epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 120
     name = sys.argv[2] if len(sys.argv) > 2 else "CartPole"
     dev = torch.device("cuda", 0)
@@ -32,7 +55,8 @@ def main():
         if len(sys.argv) > 3 and sys.argv[3] == "bf16":          # bf16 policy compute: fused bf16 rollout + chain kernels at H = 128
             cdt = torch.bfloat16
     pol = tg.GaussianActorCritic_NeuralNetwork(S, A, hidden, cov=cov, device=dev)
-    mgr = tg.RolloutManager(lambda: tg.environments.ENV_CLASSES[name](), pol, num_workers=64, num_episodes_per_worker=64,
+    tg.environments.ENV_CLASSES[name]().randomize(ranges)         # (refuses a bad name or range before anything is allocated)
+    mgr = tg.RolloutManager(lambda: tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, num_workers=64, num_episodes_per_worker=64,
                             seed=0, compute_dtype=cdt)
     buf = tg.Rollout_Buffer(mgr)
     algo = tg.PPO(epsilon=0.2, policy=pol, optimizer=torch.optim.Adam(pol.parameters(), lr=lr), ref_model=None,

@@ -104,6 +104,11 @@ class RefPenalty(C.Structure):
     _fields_ = [("d_logp_ref", C.c_void_p), ("coef", C.c_float), ("reserved", C.c_int32)]
 
 
+class RandomizeSpec(C.Structure):
+    """tg_randomize_spec (include/trajopt_grpo_hip.h): which p[] entries tg_env_randomize scales per env slot, and by what range."""
+    _fields_ = [("count", C.c_int32), ("index", C.c_int32 * 12), ("lo", C.c_double * 12), ("hi", C.c_double * 12), ("seed", C.c_uint64)]
+
+
 class CompactArgs(C.Structure):
     """tg_compact_args (include/trajopt_grpo_hip.h)."""
     _fields_ = [("d_mask", C.c_void_p), ("d_offsets", C.c_void_p), ("n", C.c_int64), ("T", C.c_int32), ("S", C.c_int32), ("A", C.c_int32),
@@ -138,6 +143,14 @@ SIGNATURES = {
     "tg_fused_rollout_f32": (C.c_int, [_P(EnvParams), _P(Traj), _VP, _VP, _I32, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _VP]),
     "tg_fused_rollout_f32_act": (C.c_int, [_P(EnvParams), _P(Traj), _VP, _VP, _I32, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _I32, _VP]),
     "tg_rng_advance": (C.c_int, [_VP, _VP]),
+    "tg_env_randomize": (C.c_int, [_P(EnvParams), _P(RandomizeSpec), _VP, _I64, _U64, _U64, _I64, _I64, _VP]),
+    "tg_rollout_step_dr": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _I32, _VP, _I64, _P(_F), _VP, _I64, _VP]),
+    "tg_rollout_forced_dr": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _I32, _I32, _VP]),
+    "tg_rollout_final_state_dr": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _VP]),
+    "tg_fused_rollout_dr": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _VP]),
+    "tg_fused_rollout_f32_dr": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _VP]),
+    "tg_fused_rollout_f32_act_dr": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _I32,
+                                              _VP]),
     "tg_colsum_finish": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP]),
     "tg_head_prep_blocks": (C.c_int, []),
     "tg_head_prep": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _VP, _VP, _VP]),

@@ -775,12 +775,19 @@ class PPO(_GpuLearner):
                              "ends when any of its bodies does, which a body's own final state does not tell")
         return params
 
-    def _bootstrap_values(self, params, traj, critic, m_c):
+    @staticmethod
+    def _bootstrap_table(buffer):
+        """The per-env parameter table of the engine's last rollout (None unless it was randomised): the re-step must use the vehicle
+        each slot was rolled out with."""
+        return getattr(buffer.rollout_manager.engine, "env_params", None)
+
+    def _bootstrap_values(self, params, traj, critic, m_c, env_params=None):
         """(b f32 [n], timeout u8 [n]): b[i] = V(s_final[i]) where the clock ended episode i, else 0 -- the re-step launch, the
         critic's input rows prepared as the valid rows are, one no-grad pass over n rows, one multiply.  Enqueued; no host read."""
         n, dev = traj.n, traj.mask.device
         s_final, timeout = K.rollout_final_state(params, traj, self._small("boot_state", n * traj.S, torch.float32, dev).view(n, traj.S),
-                                                 self._small("boot_timeout", n, torch.uint8, dev))
+                                                 self._small("boot_timeout", n, torch.uint8, dev),
+                                                 env_params=env_params)
         if m_c is not None:
             xin = m_c.prepare_input(s_final, out=self._small("boot_xin", n * m_c.in_pad, m_c.cd, dev).view(n, m_c.in_pad))
             v = m_c.forward(xin, keep=False, padded=True)[:, 0]
@@ -790,6 +797,7 @@ class PPO(_GpuLearner):
 
     def _learn(self, buffer) -> None:
         boot_params = self._bootstrap_params(buffer) if self.bootstrap_truncated else None
+        boot_table = self._bootstrap_table(buffer) if self.bootstrap_truncated else None
         traj = device_trajectory(buffer, self.policy.device)
         var = self.policy.var
         T, n = traj.T, traj.n
@@ -837,7 +845,7 @@ class PPO(_GpuLearner):
             moments = K.ppo_returns(rew, V, traj.mask, self.gamma, self.lam, self.monte_carlo, adv_full, ret_full, work)
         else:
             # time-limit bootstrapping: the same two launches on r + gamma * V(s_final) at each clock-ended episode's last step
-            boot, timeout = self._bootstrap_values(boot_params, traj, critic, m_c)
+            boot, timeout = self._bootstrap_values(boot_params, traj, critic, m_c, env_params=boot_table)
             moments = K.ppo_returns_boot(rew, V, traj.mask, traj.len, boot, self.gamma, self.lam, self.monte_carlo, adv_full, ret_full, work)
             n_boot = timeout.sum(dtype=torch.int64).reshape(1)              # (a new tensor: read when last_stats is)
             D.allreduce_sum_(n_boot, self.process_group, "n_bootstrapped")

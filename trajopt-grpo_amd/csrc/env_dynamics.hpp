@@ -10,6 +10,8 @@
 #pragma once
 #include "tg_common.hpp"
 
+#include <type_traits>
+
 namespace tg {
 
 // div_/inv_sqrt_/norm2_: the double build keeps the reference's exact operation order (division, sqrt then
@@ -52,6 +54,47 @@ struct StepOut {
 // `truncated` separately as well -- failed(o, c): the failure test on the new state; time_rule(steps_after, c): the clock test.
 // The same comparisons as in step(), which does not call them (its code is what it was).
 
+// Per-env domain randomisation (tg_env_randomize and the `_dr` entry points).  Every env's constants C are a function of the twelve
+// p[] values of tg_env_params plus timestep / max_steps / time_trunc_step: `C::build`, __host__ __device__, plain IEEE double
+// operations with contraction off, so the host (`C::make`, one vehicle for the whole launch, passed by value in the kernel
+// arguments) and a lane that builds the C of its own env slot from its column of the parameter table produce the same bits.
+// PerEnvTable is what a `_dr` kernel takes in place of the by-value C: the table f64 [12][n] (env fastest) and the fields that
+// are not randomised.
+struct PerEnvTable {
+    const double* ptab;
+    double timestep;
+    int32_t max_steps, time_trunc_step;
+};
+// PerEnv<Env> is Env with the table in place of the by-value constants: a kernel template instantiated with it IS the kPerEnv = true
+// kernel, while its instantiation with the plain Env stays the very kernel it was (the flag rides on the Env type because a
+// further template parameter would change the mangled name of every existing instantiation).  step / failed / time_rule / reset
+// are inherited untouched and keep taking the env's own C.
+template <typename Env> struct PerEnv : Env {
+    using C = PerEnvTable;
+};
+template <typename Env> struct EnvTraits {
+    static constexpr bool kPerEnv = false;
+    using Consts = typename Env::C;
+};
+template <typename Env> struct EnvTraits<PerEnv<Env>> {
+    static constexpr bool kPerEnv = true;
+    using Consts = typename Env::C;
+};
+// the constants of env slot i, built by the lane that owns it from column i of the table
+template <typename Env>
+__device__ static inline typename EnvTraits<Env>::Consts env_constants(const PerEnvTable& pe, int64_t n, int64_t i) {
+    double q[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) q[k] = pe.ptab[k * n + i];     // (rows an env does not read cost nothing: dead loads)
+    return EnvTraits<Env>::Consts::build(q, pe.timestep, pe.max_steps, pe.time_trunc_step);
+}
+// The constants a kernel steps with: its by-value argument (kPerEnv = false), or the lane's own (kPerEnv = true).
+template <typename C> __device__ static inline const C& pick_constants(const C& uniform, const C&) { return uniform; }
+template <typename C> __device__ static inline const C& pick_constants(const PerEnvTable&, const C& own) { return own; }
+static inline PerEnvTable per_env_table(const tg_env_params* p, const double* d_ptab) {
+    return PerEnvTable{d_ptab, p->timestep, p->max_steps, p->time_trunc_step};
+}
+
 // ---------------------------------------------------------------------------
 // CartPole swing-up.  cartpole_env.py:48-49, 51-92, 138-182.
 // ---------------------------------------------------------------------------
@@ -61,12 +104,13 @@ template <typename R> struct CartPoleEnv {
     struct C {
         R mc, mp, l, g, dt;
         int max_steps, time_trunc_step;
-        __host__ static C make(const tg_env_params& p) {
+        __host__ __device__ static inline C build(const double (&q)[12], double timestep, int max_steps, int time_trunc_step) {
             C c;
-            c.mc = (R)p.p[0]; c.mp = (R)p.p[1]; c.l = (R)p.p[2]; c.g = (R)p.p[3]; c.dt = (R)p.timestep;
-            c.max_steps = p.max_steps; c.time_trunc_step = p.time_trunc_step;
+            c.mc = (R)q[0]; c.mp = (R)q[1]; c.l = (R)q[2]; c.g = (R)q[3]; c.dt = (R)timestep;
+            c.max_steps = max_steps; c.time_trunc_step = time_trunc_step;
             return c;
         }
+        __host__ static C make(const tg_env_params& p) { return build(p.p, p.timestep, p.max_steps, p.time_trunc_step); }
     };
 
     __device__ static inline StepOut step(const R (&s)[S], const float (&a)[A], const C& c, int steps_after,
@@ -130,17 +174,19 @@ template <typename R> struct QuadPole2DEnv {
         R mq_Lp, mpLp, M, g, dt, bound, balance_radius;
         float hover32, Lq_over_I32, dt32;
         int max_steps;
-        __host__ static C make(const tg_env_params& p) {
+        __host__ __device__ static inline C build(const double (&q)[12], double timestep, int max_steps, int) {
+#pragma clang fp contract(off)
             C c;
-            const double mq = p.p[0], mp = p.p[1], I = p.p[2], Lq = p.p[3], Lp = p.p[4], g = p.p[5];
+            const double mq = q[0], mp = q[1], I = q[2], Lq = q[3], Lp = q[4], g = q[5];
             c.mq_Lp = (R)(mq * Lp); c.mpLp = (R)(mp * Lp); c.M = (R)(mq + mp); c.g = (R)g;
-            c.dt = (R)p.timestep; c.bound = (R)p.p[6]; c.balance_radius = (R)p.p[7];
+            c.dt = (R)timestep; c.bound = (R)q[6]; c.balance_radius = (R)q[7];
             c.hover32 = (float)((mq + mp) * g / 2);                           // :895
             c.Lq_over_I32 = (float)(Lq / I);
-            c.dt32 = (float)p.timestep;
-            c.max_steps = p.max_steps;
+            c.dt32 = (float)timestep;
+            c.max_steps = max_steps;
             return c;
         }
+        __host__ static C make(const tg_env_params& p) { return build(p.p, p.timestep, p.max_steps, p.time_trunc_step); }
     };
 
     __device__ static inline StepOut step(const R (&s)[S], const float (&a)[A], const C& c, int steps_after,
@@ -225,20 +271,22 @@ template <typename R> struct QuadPoleEnv {
         R m0, m_p, g, L, Ixx, Iyy, Izz, arm, dt, bound, tension_k, m0L, inv_m0, s22, mpL2;
         float hover32, tc32;
         int max_steps;
-        __host__ static C make(const tg_env_params& p) {
+        __host__ __device__ static inline C build(const double (&q)[12], double timestep, int max_steps, int) {
+#pragma clang fp contract(off)
             C c;
-            const double m0 = p.p[0], mp = p.p[1], g = p.p[2], L = p.p[3];
+            const double m0 = q[0], mp = q[1], g = q[2], L = q[3];
             c.m0 = (R)m0; c.m_p = (R)mp; c.g = (R)g; c.L = (R)L;
-            c.Ixx = (R)p.p[4]; c.Iyy = (R)p.p[5]; c.Izz = (R)p.p[6];
-            c.tc32 = (float)p.p[7]; c.arm = (R)p.p[8]; c.bound = (R)p.p[9];
-            c.dt = (R)p.timestep;
+            c.Ixx = (R)q[4]; c.Iyy = (R)q[5]; c.Izz = (R)q[6];
+            c.tc32 = (float)q[7]; c.arm = (R)q[8]; c.bound = (R)q[9];
+            c.dt = (R)timestep;
             c.tension_k = (R)(mp / (m0 + mp)); c.m0L = (R)(m0 * L); c.inv_m0 = (R)(1.0 / m0);
             c.s22 = (R)(1.4142135623730951 / 2.0);
             c.mpL2 = (R)(mp * (L * L));   // divisor of :511 (kept as a divisor below)
             c.hover32 = (float)((m0 + mp) * g / 4);                           // :382
-            c.max_steps = p.max_steps;
+            c.max_steps = max_steps;
             return c;
         }
+        __host__ static C make(const tg_env_params& p) { return build(p.p, p.timestep, p.max_steps, p.time_trunc_step); }
     };
 
     __device__ static inline StepOut step(const R (&s)[S], const float (&a)[A], const C& c, int steps_after,
@@ -402,16 +450,18 @@ template <typename R> struct PendulumEnv {
     struct C {
         R mgl, inv_ml2, dt;
         int max_steps, time_trunc_step, term_steps, swingup;
-        __host__ static C make(const tg_env_params& p) {
+        __host__ __device__ static inline C build(const double (&q)[12], double timestep, int max_steps, int time_trunc_step) {
+#pragma clang fp contract(off)
             C c;
-            const double mass = p.p[0], length = p.p[1], gravity = p.p[2];
+            const double mass = q[0], length = q[1], gravity = q[2];
             c.mgl = (R)(mass * gravity * length);                             // python-float product, :61
             c.inv_ml2 = (R)(1.0 / (mass * (length * length)));
-            c.dt = (R)p.timestep;
-            c.max_steps = p.max_steps; c.time_trunc_step = p.time_trunc_step;
-            c.swingup = p.p[3] != 0.0; c.term_steps = (int)p.p[4];
+            c.dt = (R)timestep;
+            c.max_steps = max_steps; c.time_trunc_step = time_trunc_step;
+            c.swingup = q[3] != 0.0; c.term_steps = (int)q[4];
             return c;
         }
+        __host__ static C make(const tg_env_params& p) { return build(p.p, p.timestep, p.max_steps, p.time_trunc_step); }
     };
 
     __device__ static inline StepOut step(const R (&s)[S], const float (&a)[A], const C& c, int steps_after,

@@ -28,6 +28,47 @@ __global__ __launch_bounds__(256) void reset_kernel(R* __restrict__ state, int64
 }
 
 // ---------------------------------------------------------------------------
+// per-env physical parameters (tg_env_randomize)
+// ---------------------------------------------------------------------------
+// Column i of the table f64 [12][n] = the p[] of env slot i: the nominal value, times -- for the spec's k-th parameter -- the factor
+//   lo_k + (hi_k - lo_k) * u01d(w[2 (k & 1)], w[2 (k & 1) + 1]),   w = Philox::draw(seed', (key_offset + i) / key_div, 0xFFFFFFFE - k / 2, stream_id)
+// with the key of tg_env_reset (a `restart` group shares one vehicle as it shares one initial state; independent of sharding) and
+// sub values counted down from 0xFFFFFFFE, which neither the reset (0xFFFFFFFF) nor a time step (t) uses.  Plain IEEE double
+// operations, contraction off: tests/domain_rand_fp64.py restates them bit for bit.
+struct PTabNominal { double p[12]; };
+__global__ __launch_bounds__(256) void env_randomize_kernel(PTabNominal nom, tg_randomize_spec spec, double* __restrict__ ptab, int64_t n,
+                                                            uint64_t seed, uint32_t stream_id, int64_t key_offset, int64_t key_div) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t key = (uint64_t)((key_offset + i) / key_div);
+    double factor[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) factor[k] = 1.0;
+#pragma unroll
+    for (int d = 0; d < 6; ++d) {
+        if (2 * d < spec.count) {                                           // (uniform)
+            uint32_t w[4];
+            Philox::draw(seed, key, 0xFFFFFFFEu - (uint32_t)d, stream_id, w);
+            factor[2 * d] = spec.lo[2 * d] + (spec.hi[2 * d] - spec.lo[2 * d]) * Philox::u01d(w[0], w[1]);
+            if (2 * d + 1 < spec.count)
+                factor[2 * d + 1] = spec.lo[2 * d + 1] + (spec.hi[2 * d + 1] - spec.lo[2 * d + 1]) * Philox::u01d(w[2], w[3]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 12; ++r) {
+        double v = nom.p[r];
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            if (k < spec.count && spec.index[k] == r) v = nom.p[r] * factor[k];
+        ptab[r * n + i] = v;
+    }
+}
+
+// seed' of the parameter draw: the rollout seed combined with the seed given to randomize()
+static inline uint64_t randomize_seed(uint64_t seed, uint64_t spec_seed) { return seed ^ (spec_seed * 0x9E3779B97F4A7C15ull); }
+
+// ---------------------------------------------------------------------------
 // standalone Env.step on SoA state
 // ---------------------------------------------------------------------------
 template <typename Env, typename R>
@@ -64,7 +105,7 @@ struct Sigma { float v[8]; };
 // two on the critical path).  Used for small launches, which are latency-bound; large launches are
 // bandwidth-bound and skip the loads of ended envs instead.
 template <typename Env, typename R, bool kSample, bool kSpec>
-__global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c, R* __restrict__ obs,
+__global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c_arg, R* __restrict__ obs,
                                                            float* __restrict__ act, R* __restrict__ rew,
                                                            uint8_t* __restrict__ mask, int32_t* __restrict__ len,
                                                            int64_t n, int32_t T, int32_t t,
@@ -79,6 +120,9 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c, R*
     R s[S], o[S];
     float mu[A], a[A];
     const int32_t my_len = len[ic];
+    constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;        // (domain randomisation: Env = PerEnv<...>, c_arg = the parameter table)
+    typename EnvTraits<Env>::Consts own;
+    if constexpr (kPerEnv && kSpec) own = env_constants<Env>(c_arg, n, ic);
     if constexpr (kSpec) {
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = obs[(k * T1 + t) * n + ic];
@@ -95,6 +139,8 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c, R*
     // wavefront-wide termination: if all 64 envs of this wave have ended, leave before touching the
     // trajectory again (wave-uniform branch, no divergence)
     if (__ballot(alive) == 0ull) return;
+    if constexpr (kPerEnv && !kSpec) own = env_constants<Env>(c_arg, n, ic);
+    const auto& c = pick_constants(c_arg, own);
     if constexpr (!kSpec) {
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = alive ? obs[(k * T1 + t) * n + ic] : (R)0;
@@ -166,7 +212,7 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c, R*
 // bound by its ~500 vector instructions, not by their latency.)
 constexpr int kForcedAhead = 8;
 template <typename Env, typename R>
-__global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c, R* __restrict__ obs, const float* __restrict__ act,
+__global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c_arg, R* __restrict__ obs, const float* __restrict__ act,
                                                             R* __restrict__ rew, uint8_t* __restrict__ mask, int32_t* __restrict__ len,
                                                             int64_t n, int32_t T, int32_t t_begin, int32_t t_end, int32_t agents) {
     constexpr int S = Env::S, A = Env::A;
@@ -174,6 +220,10 @@ __global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c, R
     const bool in_range = i < n;
     const int64_t ic = in_range ? i : n - 1;
     const int64_t T1 = (int64_t)T + 1;
+    constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;        // (domain randomisation: Env = PerEnv<...>, c_arg = the parameter table)
+    typename EnvTraits<Env>::Consts own;
+    if constexpr (kPerEnv) own = env_constants<Env>(c_arg, n, ic);   // this lane's vehicle, for all the steps of the range
+    const auto& c = pick_constants(c_arg, own);
     int32_t my_len = len[ic];
     bool alive = in_range && (Env::kBalanceTerminates ? my_len <= 0 : my_len == 0);
     R s[S];
@@ -234,12 +284,16 @@ __global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c, R
 // !failed(s_final) && (time_rule(L) || L == T).  A slot without a finished episode (len outside [1, T]) reads step 0 (a valid
 // address) and writes zeros / 0.
 template <typename Env, typename R>
-__global__ __launch_bounds__(256) void final_state_kernel(typename Env::C c, const R* __restrict__ obs, const float* __restrict__ act,
+__global__ __launch_bounds__(256) void final_state_kernel(typename Env::C c_arg, const R* __restrict__ obs, const float* __restrict__ act,
                                                           const int32_t* __restrict__ len, int64_t n, int32_t T,
                                                           float* __restrict__ s_final, uint8_t* __restrict__ timeout) {
     constexpr int S = Env::S, A = Env::A;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;        // (domain randomisation: Env = PerEnv<...>, c_arg = the parameter table)
+    typename EnvTraits<Env>::Consts own;
+    if constexpr (kPerEnv) own = env_constants<Env>(c_arg, n, i);
+    const auto& c = pick_constants(c_arg, own);
     const int64_t T1 = (int64_t)T + 1;
     const int32_t L = len[i];
     const bool ended = L >= 1 && L <= T;
@@ -421,24 +475,31 @@ static int step_dispatch(const tg_env_params* p, const void* state, int64_t ld, 
     return TG_OK;
 }
 
+// d_ptab != NULL in the three dispatchers below: the `_dr` entry point -- the kernel's PerEnv instantiation with the table.
 template <template <typename> class EnvT, typename R>
-static int rollout_dispatch(const tg_env_params* p, const tg_traj* tr, int32_t t, const float* mean, int64_t mean_rs,
+static int rollout_dispatch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* mean, int64_t mean_rs,
                             const float* sigma, const uint64_t* rng, int64_t env_offset, hipStream_t st) {
     int block;
     dim3 grid = env_grid(tr->n, block);
     auto c = EnvT<R>::C::make(*p);
+    const PerEnvTable pe = per_env_table(p, d_ptab);
     Sigma sg;
     memset(&sg, 0, sizeof(sg));
     const bool spec = tr->n <= ((int64_t)1 << 18);
 #define TG_RS(SAMPLE, SPEC)                                                                                            \
-    hipLaunchKernelGGL((rollout_step_kernel<EnvT<R>, R, SAMPLE, SPEC>), grid, dim3(block), 0, st, c, (R*)tr->d_obs,      \
-                       tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs, sg, rng, \
-                       env_offset, p->agents)
+    if (d_ptab != nullptr)                                                                                             \
+        hipLaunchKernelGGL((rollout_step_kernel<PerEnv<EnvT<R>>, R, SAMPLE, SPEC>), grid, dim3(block), 0, st, pe, (R*)tr->d_obs, \
+                           tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs, sg, rng, \
+                           env_offset, p->agents);                                                                     \
+    else                                                                                                               \
+        hipLaunchKernelGGL((rollout_step_kernel<EnvT<R>, R, SAMPLE, SPEC>), grid, dim3(block), 0, st, c, (R*)tr->d_obs,  \
+                           tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs, sg, rng, \
+                           env_offset, p->agents)
     if (mean != nullptr) {
         for (int k = 0; k < EnvT<R>::A; ++k) sg.v[k] = sigma[k];
-        if (spec) TG_RS(true, true); else TG_RS(true, false);
+        if (spec) { TG_RS(true, true); } else { TG_RS(true, false); }
     } else {
-        if (spec) TG_RS(false, true); else TG_RS(false, false);
+        if (spec) { TG_RS(false, true); } else { TG_RS(false, false); }
     }
 #undef TG_RS
     TG_LAUNCH_CHECK("tg_rollout_step");
@@ -446,21 +507,31 @@ static int rollout_dispatch(const tg_env_params* p, const tg_traj* tr, int32_t t
 }
 
 template <template <typename> class EnvT, typename R>
-static int forced_dispatch(const tg_env_params* p, const tg_traj* tr, int32_t t_begin, int32_t t_end, hipStream_t st) {
+static int forced_dispatch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, hipStream_t st) {
     auto c = EnvT<R>::C::make(*p);
-    hipLaunchKernelGGL((rollout_forced_kernel<EnvT<R>, R>), dim3((unsigned)ceil_div(tr->n, 64)), dim3(64), 0, st, c, (R*)tr->d_obs,
-                       (const float*)tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t_begin, t_end, p->agents);
+    if (d_ptab != nullptr)
+        hipLaunchKernelGGL((rollout_forced_kernel<PerEnv<EnvT<R>>, R>), dim3((unsigned)ceil_div(tr->n, 64)), dim3(64), 0, st,
+                           per_env_table(p, d_ptab), (R*)tr->d_obs, (const float*)tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n,
+                           tr->horizon, t_begin, t_end, p->agents);
+    else
+        hipLaunchKernelGGL((rollout_forced_kernel<EnvT<R>, R>), dim3((unsigned)ceil_div(tr->n, 64)), dim3(64), 0, st, c, (R*)tr->d_obs,
+                           (const float*)tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t_begin, t_end, p->agents);
     TG_LAUNCH_CHECK("tg_rollout_forced");
     return TG_OK;
 }
 
 template <template <typename> class EnvT, typename R>
-static int final_state_dispatch(const tg_env_params* p, const tg_traj* tr, float* s_final, uint8_t* timeout, hipStream_t st) {
+static int final_state_dispatch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* s_final, uint8_t* timeout,
+                                hipStream_t st) {
     int block;
     dim3 grid = env_grid(tr->n, block);
     auto c = EnvT<R>::C::make(*p);
-    hipLaunchKernelGGL((final_state_kernel<EnvT<R>, R>), grid, dim3(block), 0, st, c, (const R*)tr->d_obs, (const float*)tr->d_act,
-                       (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
+    if (d_ptab != nullptr)
+        hipLaunchKernelGGL((final_state_kernel<PerEnv<EnvT<R>>, R>), grid, dim3(block), 0, st, per_env_table(p, d_ptab), (const R*)tr->d_obs,
+                           (const float*)tr->d_act, (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
+    else
+        hipLaunchKernelGGL((final_state_kernel<EnvT<R>, R>), grid, dim3(block), 0, st, c, (const R*)tr->d_obs, (const float*)tr->d_act,
+                           (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
     TG_LAUNCH_CHECK("tg_rollout_final_state");
     return TG_OK;
 }
@@ -573,6 +644,27 @@ int tg_env_reset(const tg_env_params* p, int dtype, void* d_state, int64_t ld, i
 #undef CALL
 }
 
+int tg_env_randomize(const tg_env_params* p, const tg_randomize_spec* spec, double* d_ptab, int64_t n, uint64_t seed,
+                     uint64_t stream_id, int64_t key_offset, int64_t key_div, void* stream) {
+    TG_REQUIRE(p && spec, "tg_env_randomize: null pointer");
+    TG_REQUIRE(d_ptab != nullptr, "tg_env_randomize: null parameter table");
+    TG_REQUIRE(n >= 0 && key_div >= 1 && key_offset >= 0, "tg_env_randomize: bad sizes n=%lld key_div=%lld", (long long)n, (long long)key_div);
+    TG_REQUIRE(spec->count >= 0 && spec->count <= 12, "tg_env_randomize: count=%d outside [0, 12]", spec->count);
+    for (int k = 0; k < spec->count; ++k) {
+        TG_REQUIRE(spec->index[k] >= 0 && spec->index[k] < 12, "tg_env_randomize: index[%d]=%d outside p[0..11]", k, spec->index[k]);
+        for (int j = 0; j < k; ++j) TG_REQUIRE(spec->index[j] != spec->index[k], "tg_env_randomize: p[%d] listed twice", spec->index[k]);
+        TG_REQUIRE(isfinite(spec->lo[k]) && isfinite(spec->hi[k]) && spec->lo[k] > 0.0 && spec->lo[k] <= spec->hi[k],
+                   "tg_env_randomize: factor range [%g, %g] of p[%d] must be finite with 0 < lo <= hi", spec->lo[k], spec->hi[k], spec->index[k]);
+    }
+    if (n == 0) return TG_OK;
+    PTabNominal nom;
+    memcpy(nom.p, p->p, sizeof(nom.p));
+    hipLaunchKernelGGL(env_randomize_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, nom, *spec, d_ptab, n,
+                       randomize_seed(seed, spec->seed), (uint32_t)stream_id, key_offset, key_div);
+    TG_LAUNCH_CHECK("tg_env_randomize");
+    return TG_OK;
+}
+
 int tg_env_step(const tg_env_params* p, int dtype, const void* d_state, int64_t ld, const float* d_action, int64_t ld_a,
                 void* d_next, int64_t ld_next, int32_t* d_steps, void* d_time_balanced, void* d_reward,
                 uint8_t* d_truncated, int64_t n, void* stream) {
@@ -637,8 +729,8 @@ int tg_rollout_begin(const tg_traj* tr, int obs_dim, int act_dim, void* stream) 
     return TG_OK;
 }
 
-int tg_rollout_step(const tg_env_params* p, const tg_traj* tr, int32_t t, const float* d_mean, int64_t mean_row_stride,
-                    const float* sigma, const uint64_t* d_rng, int64_t env_offset, void* stream) {
+static int rollout_step_impl(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean,
+                             int64_t mean_row_stride, const float* sigma, const uint64_t* d_rng, int64_t env_offset, void* stream) {
     TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_rollout_step: null pointer");
     TG_REQUIRE(tr->n > 0 && tr->horizon > 0 && t >= 0 && t < tr->horizon, "tg_rollout_step: t=%d outside horizon %d", t,
                tr->horizon);
@@ -652,12 +744,23 @@ int tg_rollout_step(const tg_env_params* p, const tg_traj* tr, int32_t t, const 
         TG_REQUIRE(sigma != nullptr && d_rng != nullptr, "tg_rollout_step: sampling needs sigma and d_rng");
         TG_REQUIRE(mean_row_stride >= A, "tg_rollout_step: mean_row_stride %lld < act_dim %d", (long long)mean_row_stride, A);
     }
-#define CALL(E, R) rollout_dispatch<E, R>(p, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, (hipStream_t)stream)
+#define CALL(E, R) rollout_dispatch<E, R>(p, d_ptab, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, (hipStream_t)stream)
     TG_ENV_SWITCH(p->env_id, tr->dtype, CALL)
 #undef CALL
 }
 
-int tg_rollout_forced(const tg_env_params* p, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream) {
+int tg_rollout_step(const tg_env_params* p, const tg_traj* tr, int32_t t, const float* d_mean, int64_t mean_row_stride,
+                    const float* sigma, const uint64_t* d_rng, int64_t env_offset, void* stream) {
+    return rollout_step_impl(p, nullptr, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, stream);
+}
+
+int tg_rollout_step_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean,
+                       int64_t mean_row_stride, const float* sigma, const uint64_t* d_rng, int64_t env_offset, void* stream) {
+    TG_REQUIRE(d_ptab != nullptr, "tg_rollout_step_dr: null parameter table");
+    return rollout_step_impl(p, d_ptab, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, stream);
+}
+
+static int rollout_forced_impl(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream) {
     TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_rollout_forced: null pointer");
     TG_REQUIRE(tr->n > 0 && tr->horizon > 0 && t_begin >= 0 && t_begin <= t_end && t_end <= tr->horizon,
                "tg_rollout_forced: steps [%d, %d) outside horizon %d", t_begin, t_end, tr->horizon);
@@ -665,12 +768,22 @@ int tg_rollout_forced(const tg_env_params* p, const tg_traj* tr, int32_t t_begin
     TG_REQUIRE(p->agents <= 1 || (p->agents <= 64 && (p->agents & (p->agents - 1)) == 0 && tr->n % p->agents == 0),
                "tg_rollout_forced: agents=%d must be a power of two <= 64 dividing n", p->agents);
     if (t_begin == t_end) return TG_OK;
-#define CALL(E, R) forced_dispatch<E, R>(p, tr, t_begin, t_end, (hipStream_t)stream)
+#define CALL(E, R) forced_dispatch<E, R>(p, d_ptab, tr, t_begin, t_end, (hipStream_t)stream)
     TG_ENV_SWITCH(p->env_id, tr->dtype, CALL)
 #undef CALL
 }
 
-int tg_rollout_final_state(const tg_env_params* p, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout, void* stream) {
+int tg_rollout_forced(const tg_env_params* p, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream) {
+    return rollout_forced_impl(p, nullptr, tr, t_begin, t_end, stream);
+}
+
+int tg_rollout_forced_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream) {
+    TG_REQUIRE(d_ptab != nullptr, "tg_rollout_forced_dr: null parameter table");
+    return rollout_forced_impl(p, d_ptab, tr, t_begin, t_end, stream);
+}
+
+static int final_state_impl(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
+                            void* stream) {
     TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_len && d_s_final && d_timeout, "tg_rollout_final_state: null pointer");
     TG_REQUIRE(tr->n > 0 && tr->horizon > 0, "tg_rollout_final_state: bad sizes n=%lld T=%d", (long long)tr->n, tr->horizon);
     TG_REQUIRE(tr->horizon == p->max_steps, "tg_rollout_final_state: trajectory horizon %d != env.max_steps %d", tr->horizon,
@@ -678,9 +791,19 @@ int tg_rollout_final_state(const tg_env_params* p, const tg_traj* tr, float* d_s
     if (p->agents > 1)
         return set_error(TG_ERR_UNSUPPORTED, "tg_rollout_final_state: swarm envs (agents=%d) are not supported: a swarm episode ends "
                          "when any of its bodies does, which a body's own final state does not tell", p->agents);
-#define CALL(E, R) final_state_dispatch<E, R>(p, tr, d_s_final, d_timeout, (hipStream_t)stream)
+#define CALL(E, R) final_state_dispatch<E, R>(p, d_ptab, tr, d_s_final, d_timeout, (hipStream_t)stream)
     TG_ENV_SWITCH(p->env_id, tr->dtype, CALL)
 #undef CALL
+}
+
+int tg_rollout_final_state(const tg_env_params* p, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout, void* stream) {
+    return final_state_impl(p, nullptr, tr, d_s_final, d_timeout, stream);
+}
+
+int tg_rollout_final_state_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
+                              void* stream) {
+    TG_REQUIRE(d_ptab != nullptr, "tg_rollout_final_state_dr: null parameter table");
+    return final_state_impl(p, d_ptab, tr, d_s_final, d_timeout, stream);
 }
 
 int tg_rollout_finish(const tg_traj* tr, void* stream) {

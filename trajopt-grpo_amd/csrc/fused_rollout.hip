@@ -61,9 +61,12 @@ __device__ static inline bf16x8 x_fragment(const unsigned short* __restrict__ p)
 //                    ONE weight ring feeds all 8 waves (256 envs per workgroup).  Measured fastest.
 //   NT = 1, WPW = 4: 128 envs per workgroup, two workgroups per CU (twice the weight stream per CU); more
 //                    workgroups for small env counts.
+// Env = PerEnv<...> (tg_fused_rollout_dr; c_arg is then the parameter table): the lane builds the constants of its own env at entry
+// and keeps them in registers while it holds that env -- a compaction moves envs between lanes, so the lane rebuilds them for the
+// env it received (12 loads that hit L2 and a handful of double operations, once per kCompactEvery steps at most).
 template <typename Env, int H, int NT, int WPW>
 __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_kernel(
-    typename Env::C c, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew,
+    typename Env::C c_arg, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew,
     uint8_t* __restrict__ mask, int32_t* __restrict__ len, int64_t n, int32_t T, int32_t t0, int32_t t1,
     const uint4* __restrict__ wfrag, const float* __restrict__ bias, int32_t n_hh, SigmaF sigma,
     const uint64_t* __restrict__ rng, int64_t env_offset, int32_t agents) {
@@ -88,6 +91,10 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
     bool in_range = (i < n) && (NT == 2 || h == 0);
     int64_t ic = (i < n) ? i : n - 1;
     const int64_t T1 = (int64_t)T + 1;
+    constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
+    typename EnvTraits<Env>::Consts own_c;
+    if constexpr (kPerEnv) own_c = env_constants<Env>(c_arg, n, ic);
+    const auto& c = pick_constants(c_arg, own_c);
 
     for (int q = threadIdx.x; q < (n_hh + 2) * H; q += 64 * WPW) bias_s[q] = bias[q];
 
@@ -152,6 +159,7 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
                 alive = true;
                 in_range = (h == 0);
                 ic = i;
+                if constexpr (kPerEnv) own_c = env_constants<Env>(c_arg, n, ic);   // the vehicle follows the env, like the Philox key
             } else {
                 alive = false;
                 in_range = false;                             // an empty slot records nothing
@@ -329,7 +337,7 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
 }
 
 template <template <typename> class EnvT, int H, int NT, int WPW>
-static int fused_launch(const tg_env_params* p, const tg_traj* tr, const void* wfrag, const float* bias, int n_hh,
+static int fused_launch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* wfrag, const float* bias, int n_hh,
                         const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, hipStream_t st) {
     using Env = EnvT<float>;
     constexpr int KS = H / 16;
@@ -339,10 +347,19 @@ static int fused_launch(const tg_env_params* p, const tg_traj* tr, const void* w
     for (int k = 0; k < Env::A; ++k) sg.v[k] = sigma[k];
     const size_t shmem = (size_t)((NT == 1 && WPW == 4) ? 3 : 4) * KS * 1024 + (size_t)(n_hh + 2) * H * sizeof(float) +
                          (size_t)WPW * 64 * 32 * 2 + 4 * WPW;
+    const dim3 grid((unsigned)ceil_div(tr->n, 32 * NT * WPW));
+    if (d_ptab != nullptr) {           // tg_fused_rollout_dr: the PerEnv instantiation with the parameter table
+        auto kern_dr = fused_rollout_kernel<PerEnv<Env>, H, NT, WPW>;
+        static LdsOptIn opt_in_dr;
+        if (int rc = reserve_dynamic_lds((const void*)kern_dr, shmem, opt_in_dr, "tg_fused_rollout_dr")) return rc;
+        hipLaunchKernelGGL(kern_dr, grid, dim3(64 * WPW), shmem, st, per_env_table(p, d_ptab), (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew,
+                           tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg, rng, env_offset, p->agents);
+        TG_LAUNCH_CHECK("tg_fused_rollout_dr");
+        return TG_OK;
+    }
     auto kern = fused_rollout_kernel<Env, H, NT, WPW>;
     static LdsOptIn opt_in;
     if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_fused_rollout")) return rc;
-    const dim3 grid((unsigned)ceil_div(tr->n, 32 * NT * WPW));
     hipLaunchKernelGGL(kern, grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask,
                        tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg, rng, env_offset, p->agents);
     TG_LAUNCH_CHECK("tg_fused_rollout");
@@ -355,9 +372,9 @@ using namespace tg;
 
 extern "C" {
 
-int tg_fused_rollout(const tg_env_params* p, const tg_traj* tr, const void* d_wfrag, const float* d_bias, int32_t hidden,
-                     int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t t_begin,
-                     int32_t t_end, void* stream) {
+static int fused_rollout_impl(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+                              int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                              int32_t t_begin, int32_t t_end, void* stream) {
     TG_REQUIRE(p && tr && d_wfrag && d_bias && sigma && d_rng, "tg_fused_rollout: null pointer");
     TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_fused_rollout: null trajectory pointer");
     TG_REQUIRE(tr->dtype == TG_F32, "tg_fused_rollout: float32 trajectories only");
@@ -375,8 +392,8 @@ int tg_fused_rollout(const tg_env_params* p, const tg_traj* tr, const void* d_wf
     // it gives twice as many workgroups).  (NT 2 x 4 waves was measured slower at every size, DESIGN_HISTORY: not instantiated.)
     const int variant = tr->n < 32768 ? 1 : 0;
 #define CALL(E, HH)                                                                                                       \
-    (variant == 0 ? fused_launch<E, HH, 1, 8>(p, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st) \
-                  : fused_launch<E, HH, 1, 4>(p, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st))
+    (variant == 0 ? fused_launch<E, HH, 1, 8>(p, d_ptab, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st) \
+                  : fused_launch<E, HH, 1, 4>(p, d_ptab, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st))
     switch (p->env_id * 1000 + hidden) {
         case TG_ENV_CARTPOLE * 1000 + 128: return CALL(CartPoleEnv, 128);
         case TG_ENV_CARTPOLE * 1000 + 256: return CALL(CartPoleEnv, 256);
@@ -391,6 +408,19 @@ int tg_fused_rollout(const tg_env_params* p, const tg_traj* tr, const void* d_wf
                              "(widths 128 and 256)", p->env_id, hidden);
     }
 #undef CALL
+}
+
+int tg_fused_rollout(const tg_env_params* p, const tg_traj* tr, const void* d_wfrag, const float* d_bias, int32_t hidden,
+                     int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t t_begin,
+                     int32_t t_end, void* stream) {
+    return fused_rollout_impl(p, nullptr, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
+}
+
+int tg_fused_rollout_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+                        int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                        int32_t t_begin, int32_t t_end, void* stream) {
+    TG_REQUIRE(d_ptab != nullptr, "tg_fused_rollout_dr: null parameter table");
+    return fused_rollout_impl(p, d_ptab, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
 }
 
 }  // extern "C"

@@ -50,11 +50,13 @@ __device__ static inline void lds_barrier() {
 }
 
 // H = hidden width (64 / 128), NHH = number of H x H layers (hidden layers - 1), kAct = hidden activation (act_f32.hpp).
+// Env = PerEnv<...> (the `_dr` entry points; c_arg is then the parameter table): every lane builds the constants of its own env at
+// entry and keeps them in registers for the whole rollout (the waves step the workgroup's envs redundantly: the same bits in each).
 // Tables: `wstream` f32 [H/32 waves][K1/2 + NHH*H/2 registers][64 lanes]; `tab` f32 [(NHH+1)*H biases][4*H head
 // weights, rows >= A zero][4 head biases].
 template <typename Env, int H, int NHH, int kAct>
 __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
-    typename Env::C c, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew, uint8_t* __restrict__ mask,
+    typename Env::C c_arg, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew, uint8_t* __restrict__ mask,
     int32_t* __restrict__ len, int64_t n, int32_t T, int32_t t0, int32_t t1, const float* __restrict__ wstream,
     const float* __restrict__ tab, SigmaF32 sigma, const uint64_t* __restrict__ rng, int64_t env_offset, int32_t agents) {
     constexpr int S = Env::S, A = Env::A, WPW = H / 32;
@@ -72,6 +74,10 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
     const bool in_range = (i < n) && (h == 0) && (wave == 0);
     const int64_t ic = (i < n) ? i : n - 1;
     const int64_t T1 = (int64_t)T + 1;
+    constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
+    typename EnvTraits<Env>::Consts own;                    // kPerEnv: this lane's vehicle, for the whole rollout
+    if constexpr (kPerEnv) own = env_constants<Env>(c_arg, n, ic);
+    const auto& c = pick_constants(c_arg, own);
 
     for (int q = threadIdx.x; q < NTAB; q += 64 * WPW) tab_s[q] = tab[q];
     float w1[R1], wh[NHH > 0 ? NHH : 1][RH];
@@ -214,7 +220,7 @@ typedef float f32x4r __attribute__((ext_vector_type(4)));
 
 template <typename Env, int H, int NHH, int kAct>
 __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
-    typename Env::C c, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew, uint8_t* __restrict__ mask,
+    typename Env::C c_arg, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew, uint8_t* __restrict__ mask,
     int32_t* __restrict__ len, int64_t n, int32_t T, int32_t t0, int32_t t1, const float* __restrict__ wstream,
     const float* __restrict__ tab, SigmaF32 sigma, const uint64_t* __restrict__ rng, int64_t env_offset, int32_t agents) {
     constexpr int S = Env::S, A = Env::A, WPW = H / 32, E = 16;
@@ -232,6 +238,10 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
     const bool in_range = (i < n) && (g == 0) && (wave == 0);
     const int64_t ic = (i < n) ? i : n - 1;
     const int64_t T1 = (int64_t)T + 1;
+    constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
+    typename EnvTraits<Env>::Consts own;                    // kPerEnv: this lane's vehicle, for the whole rollout
+    if constexpr (kPerEnv) own = env_constants<Env>(c_arg, n, ic);
+    const auto& c = pick_constants(c_arg, own);
 
     for (int q = threadIdx.x; q < NTAB; q += 64 * WPW) tab_s[q] = tab[q];
     float w1[2][S1], wh[NHH > 0 ? NHH : 1][2][SH];
@@ -383,7 +393,7 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
 }
 
 template <template <typename> class EnvT, int H, int NHH, int kAct>
-static int fused_f32_launch(const tg_env_params* p, const tg_traj* tr, const float* wstream, const float* tab, const float* sigma,
+static int fused_f32_launch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* wstream, const float* tab, const float* sigma,
                             const uint64_t* rng, int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
     using Env = EnvT<float>;
     constexpr int WPW = H / 32, A = Env::A;
@@ -395,25 +405,35 @@ static int fused_f32_launch(const tg_env_params* p, const tg_traj* tr, const flo
     if (block_envs == 16) {
         const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * 16 + 2 * A * 4 * WPW * 16);
         const dim3 grid((unsigned)ceil_div(tr->n, 16));
-        hipLaunchKernelGGL((fused_rollout_f32x16_kernel<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
-                           (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset,
-                           p->agents);
+        if (d_ptab != nullptr)
+            hipLaunchKernelGGL((fused_rollout_f32x16_kernel<PerEnv<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, per_env_table(p, d_ptab),
+                               (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg,
+                               rng, env_offset, p->agents);
+        else
+            hipLaunchKernelGGL((fused_rollout_f32x16_kernel<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
+                               (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset,
+                               p->agents);
     } else {
         const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * 32 + 2 * A * 2 * WPW * 32);
         const dim3 grid((unsigned)ceil_div(tr->n, 32));
-        hipLaunchKernelGGL((fused_rollout_f32_kernel<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
-                           (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset,
-                           p->agents);
+        if (d_ptab != nullptr)
+            hipLaunchKernelGGL((fused_rollout_f32_kernel<PerEnv<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, per_env_table(p, d_ptab),
+                               (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg,
+                               rng, env_offset, p->agents);
+        else
+            hipLaunchKernelGGL((fused_rollout_f32_kernel<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
+                               (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset,
+                               p->agents);
     }
     TG_LAUNCH_CHECK("tg_fused_rollout_f32");
     return TG_OK;
 }
 
 template <template <typename> class EnvT, int kAct>
-static int fused_f32_dispatch(int hidden, int n_hh, const tg_env_params* p, const tg_traj* tr, const float* wstream, const float* tab,
+static int fused_f32_dispatch(int hidden, int n_hh, const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* wstream, const float* tab,
                               const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
 #define TG_F32_CASE(HH, NN) \
-    case HH * 10 + NN: return fused_f32_launch<EnvT, HH, NN, kAct>(p, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
+    case HH * 10 + NN: return fused_f32_launch<EnvT, HH, NN, kAct>(p, d_ptab, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
     switch (hidden * 10 + n_hh) {
         TG_F32_CASE(64, 0) TG_F32_CASE(64, 1) TG_F32_CASE(64, 2) TG_F32_CASE(64, 3)
         TG_F32_CASE(128, 0) TG_F32_CASE(128, 1) TG_F32_CASE(128, 2) TG_F32_CASE(128, 3)
@@ -439,7 +459,7 @@ int tg_fused_rollout_f32_block_envs(int64_t n, int32_t agents) {
     return (n <= (int64_t)16 * device_cus() && agents <= 16) ? 16 : 32;
 }
 
-static int fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
+static int fused_rollout_f32(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
                              int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                              int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
     TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "tg_fused_rollout_f32_act: unknown activation %d", activation);
@@ -459,7 +479,7 @@ static int fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const fl
     switch (activation * 16 + p->env_id) {
 #define TG_F32_ENV(ACT, ID, ENV)                                                                                                      \
     case ACT * 16 + ID:                                                                                                               \
-        return fused_f32_dispatch<ENV, ACT>(hidden, n_hh, p, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
+        return fused_f32_dispatch<ENV, ACT>(hidden, n_hh, p, d_ptab, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
         TG_F32_ENV(TG_ACT_RELU, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
         TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE, QuadPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_PENDULUM, PendulumEnv)
         TG_F32_ENV(TG_ACT_TANH, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
@@ -472,14 +492,30 @@ static int fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const fl
 int tg_fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
                          int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                          int32_t t_begin, int32_t t_end, void* stream) {
-    return fused_rollout_f32(p, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+    return fused_rollout_f32(p, nullptr, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
                              TG_ACT_RELU, stream);
 }
 
 int tg_fused_rollout_f32_act(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
                              int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                              int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
-    return fused_rollout_f32(p, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+    return fused_rollout_f32(p, nullptr, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+                             activation, stream);
+}
+
+int tg_fused_rollout_f32_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                            int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                            int64_t env_offset, int32_t t_begin, int32_t t_end, void* stream) {
+    TG_REQUIRE(d_ptab != nullptr, "tg_fused_rollout_f32_dr: null parameter table");
+    return fused_rollout_f32(p, d_ptab, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+                             TG_ACT_RELU, stream);
+}
+
+int tg_fused_rollout_f32_act_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                                int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                                int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
+    TG_REQUIRE(d_ptab != nullptr, "tg_fused_rollout_f32_act_dr: null parameter table");
+    return fused_rollout_f32(p, d_ptab, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
                              activation, stream);
 }
 

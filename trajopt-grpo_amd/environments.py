@@ -6,7 +6,8 @@ arguments, attributes (`max_steps`, `observation_space`, `action_space`, `env_na
 `timestep`, `_is_3d`, `state_dict`, `_initial_state`) and `reset/restart/step` return
 shapes.  A single instance is a drop-in for the reference's scalar env (every call is one
 kernel launch on one env: correct, not fast); the throughput path is
-`rollout.DeviceRollout`, which steps `num_envs x horizon` from the same parameters.
+`rollout.DeviceRollout`, which steps `num_envs x horizon` from the same parameters -- or, after
+`Env.randomize(...)`, with per-env physical parameters drawn around them (the scalar API keeps stepping the nominal env).
 `render` is out of scope (matplotlib) and raises.
 """
 from __future__ import annotations
@@ -46,6 +47,9 @@ class Env:
 
     ENV_ID = None
     _state_split = None    # ((key, size), ...) of state_dict, as the reference stores it
+    RANDOMIZABLE = {}      # attribute name -> index into tg_env_params.p[]: the physical parameters randomize() may scale
+    _randomize = None      # {name: (lo, hi)} while domain randomisation is on
+    _randomize_seed = 0
 
     def __init__(self, env_name: str, device=None, dtype=torch.float64):
         self.env_name = env_name
@@ -73,6 +77,60 @@ class Env:
 
     def _fill_params(self, p):
         raise NotImplementedError
+
+    # -- per-env domain randomisation (device rollouts) --------------------
+    def randomize(self, ranges=None, *, seed: int = 0):
+        """Each env slot of a device rollout steps its own vehicle: `ranges` maps a physical parameter (a name of
+        `RANDOMIZABLE`) to `(lo, hi)`, the range of a multiplicative factor on this env's nominal value (finite, 0 < lo <= hi).
+        Slot i is the reference env constructed with the scaled values -- hover thrust and every other derived constant follow.
+        The factors are re-drawn with every rollout from the rollout's own Philox stream ("Domain randomisation")
+        and can be read back from `DeviceRollout.env_params`.  `randomize({})` / `randomize(None)` switches it off.
+        Validated here, not at the first rollout: ValueError names the offending key.  The scalar reset() / step() API of this
+        object has no slot index and keeps stepping the NOMINAL env."""
+        if not ranges:
+            self._randomize, self._randomize_seed = None, 0
+            return self
+        if not hasattr(ranges, "items"):
+            raise ValueError("randomize(): ranges must map parameter names to (lo, hi)")
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"randomize(): seed {seed} is not an unsigned 64-bit integer")
+        checked = {}
+        for name, rng in ranges.items():
+            if name not in self.RANDOMIZABLE:
+                raise ValueError(f"randomize(): {name!r} is not a randomisable parameter of {type(self).__name__} "
+                                 f"(randomisable: {', '.join(self.RANDOMIZABLE)})")
+            try:
+                lo, hi = (float(v) for v in rng)
+            except (TypeError, ValueError):
+                raise ValueError(f"randomize(): the range of {name!r} must be a (lo, hi) pair of numbers, got {rng!r}") from None
+            if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= hi):
+                raise ValueError(f"randomize(): the factor range of {name!r} must be finite with 0 < lo <= hi, got ({lo}, {hi})")
+            checked[name] = (lo, hi)
+        self._randomize, self._randomize_seed = checked, seed
+        return self
+
+    @property
+    def randomization(self):
+        """{name: (lo, hi)} while domain randomisation is on, else None."""
+        return dict(self._randomize) if self._randomize else None
+
+    def randomize_metadata(self):
+        """What a saved metadata dictionary keeps under "randomize" (None when off): `env.randomize(**entry)` restores it."""
+        if not self._randomize:
+            return None
+        return {"ranges": {k: [lo, hi] for k, (lo, hi) in self._randomize.items()}, "seed": self._randomize_seed}
+
+    def randomize_spec(self):
+        """tg_randomize_spec of the current ranges, parameters in p[] order (the order of the dictionary does not matter); None when off."""
+        if not self._randomize:
+            return None
+        spec = N.RandomizeSpec()
+        items = sorted(self._randomize.items(), key=lambda kv: self.RANDOMIZABLE[kv[0]])
+        spec.count, spec.seed = len(items), self._randomize_seed
+        for k, (name, (lo, hi)) in enumerate(items):
+            spec.index[k], spec.lo[k], spec.hi[k] = self.RANDOMIZABLE[name], lo, hi
+        return spec
 
     @property
     def obs_dim(self):
@@ -242,6 +300,7 @@ class CartPole(Env):
     """Swing-up cart-pole.  environments/cartpole_env.py:6-182."""
     ENV_ID = N.TG_ENV_CARTPOLE
     _state_split = (("cartpole", 5),)
+    RANDOMIZABLE = {"masscart": 0, "masspole": 1, "length": 2, "gravity": 3}
 
     def __init__(self, env_name: str = "CartPole", masscart: float = 1.0, masspole: float = 1.0, length: float = 0.5,
                  gravity: float = 9.80665, timestep: float = 0.02, max_steps: int = 500, device=None,
@@ -272,6 +331,7 @@ class Pendulum(Env):
     does (:158); its rollout worker unpacks them the other way round and only uses their disjunction."""
     ENV_ID = N.TG_ENV_PENDULUM
     _state_split = (("pendulum", 3),)
+    RANDOMIZABLE = {"mass": 0, "length": 1, "gravity": 2}
     BALANCE_TIME = 5.0                                                        # :151
 
     def __init__(self, env_name: str = "Pendulum", swingup: bool = False, mass: float = 1.0, length: float = 0.5,
@@ -302,6 +362,7 @@ class QuadPole2D(Env):
     """Planar quadrotor + pendulum payload.  environments/quadrotor_env.py:867-1223."""
     ENV_ID = N.TG_ENV_QUADPOLE2D
     _state_split = (("quadrotor", 8), ("pendulum", 2))     # as _propogate leaves it (:1041-1042)
+    RANDOMIZABLE = {"mq": 0, "mp": 1, "I": 2, "Lq": 3, "Lp": 4, "gravity": 5}
 
     def __init__(self, env_name="QuadPole2D", max_steps=500, timestep=0.02, device=None, dtype=torch.float64):
         super().__init__(env_name, device, dtype)
@@ -338,6 +399,8 @@ class QuadPole(Env):
     """3-D quadrotor (quaternion attitude) + tethered payload.  environments/quadrotor_env.py:353-713."""
     ENV_ID = N.TG_ENV_QUADPOLE
     _state_split = (("quadrotor", 13), ("pendulum", 7))
+    RANDOMIZABLE = {"mass": 0, "load_mass": 1, "gravity": 2, "tether_length": 3, "Ixx": 4, "Iyy": 5, "Izz": 6, "torque_constant": 7,
+                    "arm_length": 8}
 
     def __init__(self, env_name="QuadPole", max_steps=500, device=None, dtype=torch.float64):
         super().__init__(env_name, device, dtype)

@@ -145,10 +145,12 @@ def ppo_returns(rew, values, mask, gamma: float, lam: float, monte_carlo: bool, 
     return moments
 
 
-def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: torch.Tensor = None):
+def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: torch.Tensor = None, env_params: torch.Tensor = None):
     """tg_rollout_final_state on a DeviceTrajectory: (s_final f32 [n][S], timeout u8 [n]) -- the state each episode's last step
     produced (Env.step on obs[:, len-1], act[:, len-1]: tg_env_step's bits) and whether the clock, not a failure, ended the episode.
-    params: the env's tg_env_params (DeviceRollout.params / Env.native_params()).  A swarm env is refused: ValueError."""
+    params: the env's tg_env_params (DeviceRollout.params / Env.native_params()).  A swarm env is refused: ValueError.
+    env_params: the per-env parameter table of a randomised rollout (DeviceRollout.env_params, f64 [12][n]): every slot is re-stepped
+    with its own vehicle (tg_rollout_final_state_dr)."""
     N.require_cuda(traj.obs, traj.act, traj.len, s_final, timeout)
     assert traj.obs.is_contiguous() and traj.act.is_contiguous() and traj.len.is_contiguous() and traj.len.dtype == torch.int32
     dev = traj.obs.device
@@ -159,7 +161,13 @@ def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: tor
     assert s_final.dtype == torch.float32 and s_final.is_contiguous() and s_final.numel() == traj.n * traj.S
     assert timeout.dtype == torch.uint8 and timeout.is_contiguous() and timeout.numel() == traj.n
     tr = traj.native()
-    rc = N.load().tg_rollout_final_state(C.byref(params), C.byref(tr), s_final.data_ptr(), timeout.data_ptr(), _st(traj.obs))
+    if env_params is not None:
+        N.require_cuda(env_params)
+        assert env_params.dtype == torch.float64 and env_params.is_contiguous() and tuple(env_params.shape) == (12, traj.n)
+        rc = N.load().tg_rollout_final_state_dr(C.byref(params), env_params.data_ptr(), C.byref(tr), s_final.data_ptr(), timeout.data_ptr(),
+                                                _st(traj.obs))
+    else:
+        rc = N.load().tg_rollout_final_state(C.byref(params), C.byref(tr), s_final.data_ptr(), timeout.data_ptr(), _st(traj.obs))
     if rc == N.TG_ERR_UNSUPPORTED:
         raise ValueError(N.load().tg_last_error().decode("utf-8", "replace"))
     N.check(rc, "tg_rollout_final_state")

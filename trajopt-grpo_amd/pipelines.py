@@ -78,7 +78,7 @@ class Pipeline:
             torch.distributed.barrier()
 
     def get_metadata(self) -> Dict[str, Any]:
-        return {
+        meta = {
             "test_name": self.test_name,
             "checkpoint_name": self.checkpoint_name,
             "creation_date": self.today,
@@ -90,6 +90,10 @@ class Pipeline:
             "publisher": self.publisher.metadata() if self.publisher is not None else {},
             "logger": self.logger.metadata() if self.logger is not None else {},
         }
+        rand = self.env.randomize_metadata()
+        if rand is not None:                       # only when domain randomisation is on: Env.randomize(**meta["randomize"]) restores it
+            meta["randomize"] = rand
+        return meta
 
     def load_metadata(self, path: str) -> Dict[str, Any]:
         with open(path, "r") as f:

@@ -166,6 +166,10 @@ class DeviceRollout:
         # multi-rank rollout uses the kernel -- and the summation order -- of the one-rank rollout
         self.f32_block_envs = None
         self._f32_block_envs = 32
+        # domain randomisation (Env.randomize): the p[] of every env slot of the last rollout, device f64 [12][n] (env fastest) -- drawn
+        # by tg_env_randomize right after the reset, read by the `_dr` entry points on every path; None while randomisation is off
+        self.env_params = None
+        self._rand_spec = None
 
     # ---- policy mean for time step t -------------------------------------------------
     def _refresh_weights(self, entry: bool = False):
@@ -207,11 +211,25 @@ class DeviceRollout:
                                       seed, stream_id, self.group_offset * self.E, self.E if self.restart else 1, st),
                 "tg_env_reset")
 
+    def _randomize(self, st):
+        """One tg_env_randomize launch: this rollout's per-env parameters, keyed like the reset (same seed, stream id, global env or
+        group index), so they do not depend on the sharding and a `restart` group shares one vehicle."""
+        if self._rand_spec is None:
+            return
+        if self.env_params is None:
+            self.env_params = torch.empty(12, self.n, dtype=torch.float64, device=self.device)
+        N.check(self.lib.tg_env_randomize(C.byref(self.params), C.byref(self._rand_spec), self.env_params.data_ptr(), self.n,
+                                          int(self._seed_host), int(self._stream_host), self.group_offset * self.E,
+                                          self.E if self.restart else 1, st), "tg_env_randomize")
+
     @torch.no_grad()
     def run(self, initial_states=None, forced_actions=None) -> DeviceTrajectory:
         """One rollout.  `initial_states` (N,S) and `forced_actions` (N,T,A) or (G,E,T,A)
         replace the RNG draws (teacher-forced parity runs)."""
         self.params = self.env.native_params()
+        self._rand_spec = self.env.randomize_spec()
+        if self._rand_spec is None:
+            self.env_params = None                        # off (again): no table on any path below, the graph replay included
         self.traj.host_valid_rows = None                 # (set again by Rollout_Buffer.sample for THIS rollout)
         self.traj.stats_fresh = False
         # the policy's covariance is read fresh every rollout (the reference reads self.cov in every forward,
@@ -224,7 +242,9 @@ class DeviceRollout:
             with torch.cuda.device(self.device):
                 self._enqueue_prepare(initial_states)
                 self._enqueue_fused(0, self.T)
-        elif self.use_graph and sample and initial_states is None:
+        elif self.use_graph and sample and initial_states is None and self._rand_spec is None:
+            # (a randomised rollout does not take the graph: its parameter draw depends on the host stream id, like the reset, and
+            #  the captured launches would be the plain entry points)
             self._run_graph()
         else:
             with torch.cuda.device(self.device):
@@ -247,6 +267,7 @@ class DeviceRollout:
         else:
             init = torch.as_tensor(np.asarray(initial_states), dtype=self.dtype).reshape(self.n, self.S)
             self.traj.obs[:, 0, :].copy_(init.t().to(self.device))
+        self._randomize(st)
 
     def _enqueue_fused(self, t_begin: int, t_end: int):
         """All steps [t_begin, t_end) in one persistent launch (tg_fused_rollout)."""
@@ -273,7 +294,17 @@ class DeviceRollout:
         if self.step_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        if self._fused_f32 and self._f32_act != N.TG_ACT_RELU:
+        pt = None if self.env_params is None else self.env_params.data_ptr()
+        if pt is not None and self._fused_f32:
+            N.check(lib.tg_fused_rollout_f32_act_dr(C.byref(self.params), pt, C.byref(tr), self._frag.stream.data_ptr(),
+                                                    self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs, self._sigma,
+                                                    self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end, self._f32_act, st),
+                    "tg_fused_rollout_f32_act_dr")
+        elif pt is not None:
+            N.check(lib.tg_fused_rollout_dr(C.byref(self.params), pt, C.byref(tr), self._frag.stream.data_ptr(),
+                                            self._frag.bias.data_ptr(), self._fused_H, n_hidden, self._sigma, self.rng.data_ptr(),
+                                            self.group_offset * self.E, t_begin, t_end, st), "tg_fused_rollout_dr")
+        elif self._fused_f32 and self._f32_act != N.TG_ACT_RELU:
             N.check(lib.tg_fused_rollout_f32_act(C.byref(self.params), C.byref(tr), self._frag.stream.data_ptr(),
                                                  self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs, self._sigma,
                                                  self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end, self._f32_act, st),
@@ -301,6 +332,7 @@ class DeviceRollout:
     def _enqueue_steps(self, sample: bool, entry: bool = False):
         lib, tr, st = self.lib, self.traj.native(), N.stream_ptr(self.device)
         p = C.byref(self.params)
+        pt = None if self.env_params is None else self.env_params.data_ptr()      # randomised: the `_dr` entry points
         if sample:
             self._refresh_weights(entry)
         elif not self.forced_per_step:
@@ -310,7 +342,10 @@ class DeviceRollout:
             if self.step_events is not None:
                 ev = N.event_pair()
                 ev[0].record()
-            N.check(lib.tg_rollout_forced(p, C.byref(tr), 0, self.T, st), "tg_rollout_forced")
+            if pt is not None:
+                N.check(lib.tg_rollout_forced_dr(p, pt, C.byref(tr), 0, self.T, st), "tg_rollout_forced_dr")
+            else:
+                N.check(lib.tg_rollout_forced(p, C.byref(tr), 0, self.T, st), "tg_rollout_forced")
             if ev is not None:
                 ev[1].record()
                 self.step_events.append((None, ev[0], ev[1]))
@@ -324,13 +359,20 @@ class DeviceRollout:
                 if self.step_events is not None:
                     ev = N.event_pair()
                     ev[0].record()
-                N.check(lib.tg_rollout_step(p, C.byref(tr), t, mean.data_ptr(), mean.stride(0), self._sigma,
-                                            self.rng.data_ptr(), env_offset, st), "tg_rollout_step")
+                if pt is not None:
+                    N.check(lib.tg_rollout_step_dr(p, pt, C.byref(tr), t, mean.data_ptr(), mean.stride(0), self._sigma,
+                                                   self.rng.data_ptr(), env_offset, st), "tg_rollout_step_dr")
+                else:
+                    N.check(lib.tg_rollout_step(p, C.byref(tr), t, mean.data_ptr(), mean.stride(0), self._sigma,
+                                                self.rng.data_ptr(), env_offset, st), "tg_rollout_step")
             else:
                 if self.step_events is not None:
                     ev = N.event_pair()
                     ev[0].record()
-                N.check(lib.tg_rollout_step(p, C.byref(tr), t, None, 0, None, None, env_offset, st), "tg_rollout_step")
+                if pt is not None:
+                    N.check(lib.tg_rollout_step_dr(p, pt, C.byref(tr), t, None, 0, None, None, env_offset, st), "tg_rollout_step_dr")
+                else:
+                    N.check(lib.tg_rollout_step(p, C.byref(tr), t, None, 0, None, None, env_offset, st), "tg_rollout_step")
             if ev is not None:
                 ev[1].record()
                 self.step_events.append((t, ev[0], ev[1]))
