@@ -448,6 +448,29 @@ int  tg_mlp_forward_chain_loss_ref(const void* d_x, const void* d_wfrag, const f
                                    int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
                                    const tg_ref_penalty* ref, void* stream);
 
+/* ---- A learned, state-independent log-std of the Gaussian policy (one parameter per action dimension) ----
+ * The `_std` variants of the training heads take the same arguments plus a nullable `ref` (GRPO's penalty above) and `std`.  The
+ * head then reads log_std[k], k < act_dim, from DEVICE memory at kernel entry -- inv_var[k] = exp(-2 log_std[k]), logp_const =
+ * -act_dim / 2 log(2 pi) - sum log_std; tg_loss_args.var / tg_chain_loss.var are not read -- and writes, per valid actor row,
+ *   d_out[row][k] = (d loss / d logp) * ((act_k - mean_k)^2 inv_var[k] - 1)      k < act_dim; columns >= act_dim zero
+ * the row's contribution to d loss / d log_std[k] (d loss / d logp as the head forms it: surrogate, kl_coef term, reference
+ * penalty).  Rows the head skips (tg_loss_args.d_mask) get zeros.  tg_log_std_grad sums the rows of d_out in f64 in a fixed order
+ * (no float atomics) and ADDS the sums, plus `add` to every component, into d_grad f32 [act_dim]: the log_std window of the
+ * gradient bucket, once per chunk (`add` = -entropy coefficient on one chunk of one rank, 0 elsewhere).  d_work: f64
+ * [tg_log_std_grad_blocks()][4] scratch.
+ * std == NULL: what the `_ref` entry point launches.  Refused: act_dim > 4, a critic head, a NULL field of `std`. */
+typedef struct tg_learned_std {
+    const float* d_log_std;   /* [act_dim] f32, read on the device at kernel entry */
+    float*       d_out;       /* [rows][4] f32 */
+} tg_learned_std;
+int  tg_surrogate_loss_std(const tg_loss_args* a, const tg_ref_penalty* ref, const tg_learned_std* std, void* stream);
+int  tg_mlp_forward_chain_loss_std(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                                   int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
+                                   const tg_ref_penalty* ref, const tg_learned_std* std, void* stream);
+int  tg_log_std_grad_blocks(void);
+int  tg_log_std_grad(const float* d_rows4, int64_t rows, int32_t act_dim, float add, float* d_grad, double* d_work, void* stream);
+/* (the fp32 chain learners' `_std` entry points are declared beside their plain ones below) */
+
 /* ---- MLP backward-data pass, all hidden layers in one persistent launch ----
  * For Linear(in, H) ReLU [Linear(H, H) ReLU]^(n_hidden_layers-1) Linear(H, out <= 8), H in {128, 256}, 3..6 hidden
  * layers, bf16:
@@ -572,6 +595,10 @@ int  tg_mlp_f32_forward_act(const float* d_x, int32_t in_pad, const float* d_str
 int  tg_mlp_f32_forward_backward_act(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
                                      int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
                                      const tg_chain_loss* loss, const tg_ref_penalty* ref, int32_t activation, void* stream);
+int  tg_mlp_f32_forward_backward_act_std(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
+                                         int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
+                                         const tg_chain_loss* loss, const tg_ref_penalty* ref, const tg_learned_std* std,
+                                         int32_t activation, void* stream);   /* (tg_learned_std above) */
 /* The same passes at H = 256 (the reference's QuadPole factory at its own precision: pipelines/quadpole_pipeline_ppo.py:54-58,
  * 20-256x5-{4,1} fp32), csrc/mlp_f32_wide.hip: a wave owns 16 rows on v_mfma_f32_16x16x4_f32, two 4-wave workgroups per CU.
  *   d_stream  f32, tg_mlp_f32w_stream_floats(n_hidden_layers) floats, in 16-KiB blocks of 16 pieces x 64 lanes x 16 B, lane = (i = lane & 15,
@@ -591,6 +618,9 @@ int  tg_mlp_f32w_forward_backward(const float* d_x, int32_t in_pad, const float*
 int  tg_mlp_f32w_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
                                       int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss,
                                       const tg_ref_penalty* ref, void* stream);
+int  tg_mlp_f32w_forward_backward_std(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
+                                      int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss,
+                                      const tg_ref_penalty* ref, const tg_learned_std* std, void* stream);
 /* The H = 128 net with at most ONE H x H layer (BASELINE configs[1], C2: 5-128-128-1, pipelines/cartpole_pipeline_grpo.py:54-76) on the
  * same 16-row machine with its whole weight stream resident in LDS (csrc/mlp_f32_wide.hip, mlp_f32_res_kernel): 12 waves per CU (16 without gradients), no
  * barrier in the row loop, rows dealt 16 at a time wave-major across the CUs (C2's ~176,000 rows are 10.78 wave-rounds per SIMD: 11
@@ -613,6 +643,10 @@ int  tg_mlp_f32r_forward_backward(const float* d_x, int32_t in_pad, const float*
 int  tg_mlp_f32r_forward_backward_ref(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table,
                                       int32_t hidden, int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_dz,
                                       void* d_top_maskbits, const tg_chain_loss* loss, const tg_ref_penalty* ref, void* stream);
+int  tg_mlp_f32r_forward_backward_std(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table,
+                                      int32_t hidden, int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_dz,
+                                      void* d_top_maskbits, const tg_chain_loss* loss, const tg_ref_penalty* ref, const tg_learned_std* std,
+                                      void* stream);
 enum { TG_F32DW_MM = 0, TG_F32DW_HEAD = 1 };
 typedef struct tg_f32_dw_job {
     const float* d_p;

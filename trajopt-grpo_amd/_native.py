@@ -104,6 +104,12 @@ class RefPenalty(C.Structure):
     _fields_ = [("d_logp_ref", C.c_void_p), ("coef", C.c_float), ("reserved", C.c_int32)]
 
 
+class LearnedStd(C.Structure):
+    """tg_learned_std (include/trajopt_grpo_hip.h): the policy's log_std on the device and the heads' per-row side output, for the
+    `_std` entry points."""
+    _fields_ = [("d_log_std", C.c_void_p), ("d_out", C.c_void_p)]
+
+
 class RandomizeSpec(C.Structure):
     """tg_randomize_spec (include/trajopt_grpo_hip.h): which p[] entries tg_env_randomize scales per env slot, and by what range."""
     _fields_ = [("count", C.c_int32), ("index", C.c_int32 * 12), ("lo", C.c_double * 12), ("hi", C.c_double * 12), ("seed", C.c_uint64)]
@@ -163,6 +169,9 @@ SIGNATURES = {
     "tg_loss_work_blocks": (C.c_int, []),
     "tg_surrogate_loss": (C.c_int, [_P(LossArgs), _VP]),
     "tg_surrogate_loss_ref": (C.c_int, [_P(LossArgs), _P(RefPenalty), _VP]),
+    "tg_surrogate_loss_std": (C.c_int, [_P(LossArgs), _P(RefPenalty), _P(LearnedStd), _VP]),
+    "tg_log_std_grad_blocks": (C.c_int, []),
+    "tg_log_std_grad": (C.c_int, [_VP, _I64, _I32, _F, _VP, _VP, _VP]),
     "tg_relu_bwd_bias_blocks": (C.c_int, []),
     "tg_relu_bwd_bias": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "tg_head_bwd_relu_bias": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
@@ -184,6 +193,8 @@ SIGNATURES = {
                                             C.POINTER(ChainLoss), _VP]),
     "tg_mlp_forward_chain_loss_ref": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                 C.POINTER(ChainLoss), _P(RefPenalty), _VP]),
+    "tg_mlp_forward_chain_loss_std": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                C.POINTER(ChainLoss), _P(RefPenalty), _P(LearnedStd), _VP]),
     "tg_mlp_f32_stream_floats": (C.c_int64, [_I32, _I32, _I32]),
     "tg_mlp_f32_blocks": (C.c_int, []),
     "tg_mlp_f32_forward": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, _VP, _VP]),
@@ -194,6 +205,12 @@ SIGNATURES = {
     "tg_mlp_f32_forward_act": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, _VP, _I32, _VP]),
     "tg_mlp_f32_forward_backward_act": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP,
                                                   C.POINTER(ChainLoss), _P(RefPenalty), _I32, _VP]),
+    "tg_mlp_f32_forward_backward_act_std": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP,
+                                                      C.POINTER(ChainLoss), _P(RefPenalty), _P(LearnedStd), _I32, _VP]),
+    "tg_mlp_f32w_forward_backward_std": (C.c_int, [_VP, _I32, _VP, _VP, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                   C.POINTER(ChainLoss), _P(RefPenalty), _P(LearnedStd), _VP]),
+    "tg_mlp_f32r_forward_backward_std": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                   _VP, C.POINTER(ChainLoss), _P(RefPenalty), _P(LearnedStd), _VP]),
     "tg_mlp_f32w_stream_floats": (C.c_int64, [_I32]),
     "tg_mlp_f32w_table_floats": (C.c_int64, []),
     "tg_mlp_f32w_blocks": (C.c_int, []),

@@ -10,6 +10,10 @@ Mirrors algorithms/algorithm.py:3-35, algorithms/grpo.py:12-169 and algorithms/p
   * PPO `old_log_probs` come from the CURRENT policy (ppo.py:142-143); the critic regresses on
     batch-normalised returns while A = R_raw - V (ppo.py:111,139,169); the entropy of the
     fixed-covariance Gaussian is a constant (zero gradient).
+  A policy built with learn_std=True (policies.py) has a learned per-dimension `log_std`: both learners then route every update through
+  the `_std` entry points -- the heads read log_std on the device and emit its gradient, tg_log_std_grad adds it (and PPO's entropy
+  bonus, -entropy per component and optimizer step) into log_std's window of the gradient bucket; no update reads it on the host.
+  GRPO's one-rank Adam rider declines for such a policy (the optimizer owns more than the net's parameters).
 What changes is where it runs: RTG / moments / normalisation / log-prob / the loss head are HIP
 kernels over the device trajectory; the MLP forward/backward run through mlp.GemmMLP (forward chain
 kernel, backward-data chain kernel, weight-gradient kernel); gradients of all ranks are summed
@@ -130,6 +134,7 @@ class _GpuLearner(Algorithm):
             self._rollout_engine = getattr(getattr(buffer, "rollout_manager", None), "engine", None) if ok else None
             self._check_deferred()
             self._clip_blocks, self._clip_steps = [], 0
+            self._std_blocks, self._std_steps = [], 0
             self._learn(buffer)
             if self._clip_steps and self._stats_pending is not None:
                 inner, blocks, steps = self._stats_pending, self._clip_blocks, self._clip_steps
@@ -249,9 +254,10 @@ class _GpuLearner(Algorithm):
 
     def _actor_keys(self):
         """(key of policy.actor's parameters, key of old_policy.actor's): storage, torch version counters, raw-write count."""
-        def key(net):
-            return (tuple((p.data_ptr(), p._version) for p in net.parameters()), M.N.RAW_PARAM_WRITES[0])
-        return key(self.policy.actor), key(self.old_policy.actor)
+        def key(pol):
+            ps = list(pol.actor.parameters()) + ([pol.log_std] if getattr(pol, "log_std", None) is not None else [])
+            return (tuple((p.data_ptr(), p._version) for p in ps), M.N.RAW_PARAM_WRITES[0])
+        return key(self.policy), key(self.old_policy)
 
     def _old_actor_is_current(self) -> bool:
         """Nothing has written either actor since old_policy <- policy (grpo.py:148): their weights are the same bits, and so are
@@ -516,6 +522,35 @@ class _GpuLearner(Algorithm):
             cache[name] = t = torch.empty(numel, dtype=dtype, device=device)
         return t
 
+    # ---- a learned log-std (policies: learn_std=True): the heads read it on the device and leave each row's d loss / d log_std in a
+    # [rows][4] side output; tg_log_std_grad sums a chunk's rows into log_std's window of the gradient bucket ----
+    def _learned_std(self):
+        """policy.log_std (a device f32 Parameter whose .grad is its window of the flat bucket), or None: a fixed covariance, and
+        none of the `_std` entry points is touched."""
+        ls = getattr(self.policy, "log_std", None)
+        if ls is None:
+            return None
+        if ls.dtype != torch.float32 or not ls.is_cuda or ls.numel() > 4:
+            raise ValueError(f"a learned log_std must be a float32 device parameter of at most 4 action dimensions, got {ls.dtype} "
+                             f"{tuple(ls.shape)} on {ls.device}")
+        return ls
+
+    def _std_rows(self, rows, dev, cap):
+        return self._ws.get("std_rows", rows, 4, torch.float32, dev, cap)
+
+    def _std_reduce(self, ls, std_rows, add=0.0):
+        K.log_std_grad(std_rows, ls.numel(), ls.grad, add=add,
+                       work=self._small("std_work", 4 * K.N.load().tg_log_std_grad_blocks(), torch.float64, ls.device))
+
+    def _std_record(self, ls):
+        """sum(log_std) BEFORE the coming optimizer step into the next row of this learn()'s [64] blocks (read by last_stats)."""
+        blocks = self._std_blocks
+        row = self._std_steps % 64
+        if row == 0:
+            blocks.append(torch.empty(64, dtype=torch.float32, device=ls.device))
+        torch.sum(ls.detach(), dim=0, keepdim=True, out=blocks[-1][row:row + 1])
+        self._std_steps += 1
+
     def _logp_nograd(self, actor, xin, act, var, out=None):
         if out is None:
             out = torch.empty(xin.shape[0], dtype=torch.float32, device=xin.device)
@@ -610,6 +645,7 @@ class GRPO(_GpuLearner):
             self._entry_refresh(ref_actor)                                  # (the caller may have refreshed the reference policy)
         self._refresh(self.old_policy.actor)
         _ = self.bucket                                                     # (the gradient windows exist before can_fuse_head() asks)
+        ls = self._learned_std()                                            # (the old / reference passes keep their host `var`)
         # grpo.py:118-119.  When old_policy still IS the policy (the usual case: grpo.py:148 copied it at the end of the last learn()
         # and nothing has touched either since), its log-probabilities are the ones the first update's forward pass computes
         # anyway: that pass writes them (ratio exactly 1 there, as in the reference) and the no-grad pass is not run.
@@ -630,7 +666,7 @@ class GRPO(_GpuLearner):
             xin = self._prep(actor, X, traj.T * traj.n)
         X = xin                                                             # (the loops below only ask for its row count and device)
         old_logp = (self._ws.get("old_logp", X.shape[0], 1, torch.float32, X.device, traj.T * traj.n).view(-1) if fold_old else
-                    self._logp_nograd(self.old_policy.actor, xin, act, var))
+                    self._logp_nograd(self.old_policy.actor, xin, act, self.old_policy.var if ls is not None else var))
         ref_logp = None
         if ref_actor is not None:                                           # once per learn(): the reference policy is frozen
             in_dim = next(m for m in ref_actor.network if isinstance(m, torch.nn.Linear)).in_features
@@ -645,12 +681,18 @@ class GRPO(_GpuLearner):
             rider = None
             for lo in range(0, X.shape[0], self.chunk_rows):
                 hi = min(lo + self.chunk_rows, X.shape[0])
+                std_rows = self._std_rows(hi - lo, X.device, traj.T * traj.n) if ls is not None else None
                 if fuse:        # loss head + head gradient inside the forward chain (tg_mlp_forward_chain_loss)
-                    m_actor.forward_loss(xin[lo:hi], 0, act=act[lo:hi], logp_old=old_logp[lo:hi], adv=adv[lo:hi], var=var,
+                    m_actor.forward_loss(xin[lo:hi], 0, act=act[lo:hi], logp_old=old_logp[lo:hi], adv=adv[lo:hi],
+                                         var=None if ls is not None else var,
                                          epsilon=self.epsilon, surr_coef=coef, sums_out=sums,
                                          logp_old_out=old_logp[lo:hi] if (fold_old and u == 0) else None,
-                                         logp_ref=ref_logp[lo:hi] if ref_logp is not None else None, ref_coef=ref_coef)
-                    # (asked for right before the launch it rides on: it marks the weight layouts as current)
+                                         logp_ref=ref_logp[lo:hi] if ref_logp is not None else None, ref_coef=ref_coef,
+                                         log_std=ls, std_out=std_rows)
+                    if ls is not None:
+                        self._std_reduce(ls, std_rows)
+                    # (asked for right before the launch it rides on: it marks the weight layouts as current; with a learned log_std
+                    # the optimizer owns more than the net's parameters and the rider declines)
                     rider = self._adam_rider(actor, last, whole_update=lo == 0 and hi == X.shape[0])
                     m_actor.backward_fused(adam=rider)
                     continue
@@ -658,7 +700,10 @@ class GRPO(_GpuLearner):
                     mean = self._forward(actor, xin[lo:hi], train=True, view=True)     # the loss kernel takes a row stride
                     _, s, g_mean, _ = K.surrogate_loss(mean.detach(), None, act[lo:hi], old_logp[lo:hi], adv[lo:hi], None,
                                                        None, None, var, self.epsilon, coef, 0.0, 0.0, want_total=False,
-                                                       logp_ref=ref_logp[lo:hi] if ref_logp is not None else None, ref_coef=ref_coef)
+                                                       logp_ref=ref_logp[lo:hi] if ref_logp is not None else None, ref_coef=ref_coef,
+                                                       log_std=ls, std_out=std_rows)
+                    if ls is not None:
+                        self._std_reduce(ls, std_rows)
                     self._backward(actor, mean, g_mean)
                 sums += s
             if rider is not None:                                            # (one rank: no all-reduce; the step rode on the reduction)
@@ -671,12 +716,14 @@ class GRPO(_GpuLearner):
         if self.updates_per_iter > 0:
             allJ = all_sums
             D.allreduce_sum_(allJ, self.process_group, "loss_stats")
+            ls_end = ls.detach().clone() if ls is not None else None        # (after the last step; read when last_stats is)
+            extra = (lambda: {"log_std": ls_end.tolist()}) if ls_end is not None else dict
             if ref_actor is None:
-                self._stats_pending = lambda: {"J": (allJ[:, 0] / G_global).tolist(), "n_valid": allJ[0, 3].item()}
+                self._stats_pending = lambda: {"J": (allJ[:, 0] / G_global).tolist(), "n_valid": allJ[0, 3].item(), **extra()}
             else:                                                           # slot 2: sum D (GRPO's heads have kl_coef = 0)
                 beta = float(self.beta)
                 self._stats_pending = lambda: {"J": ((allJ[:, 0] - beta * allJ[:, 2]) / G_global).tolist(), "n_valid": allJ[0, 3].item(),
-                                               "kl_ref": (allJ[:, 2] / allJ[:, 3].clamp_min(1.0)).tolist()}
+                                               "kl_ref": (allJ[:, 2] / allJ[:, 3].clamp_min(1.0)).tolist(), **extra()}
 
     def save(self, path: str) -> None:
         torch.save(self.optimizer.state_dict(), os.path.join(path, "optimizer.pth"))   # grpo.py:154
@@ -729,6 +776,13 @@ class PPO(_GpuLearner):
         takes the old log-probabilities from the current policy: the same numbers) instead of reading it."""
         actor, critic = self.policy.actor, self.policy.critic
         self._zero_grads()
+        ls = self._learned_std()
+        # the entropy bonus (ppo.py:172,179): H = A/2 (1 + log 2 pi) + sum log_std, so -entropy * mean(H) adds exactly -entropy to every
+        # component of d loss / d log_std -- once per optimizer step whatever the row count and the world size (rank 0 adds it
+        # before the all-reduce), with the first chunk's reduction launch
+        ent_add = -float(self.entropy) if (ls is not None and D.rank_world(self.process_group)[0] == 0) else 0.0
+        if ls is not None:
+            self._std_record(ls)
         # [actor | critic] loss sums: a row of the learn()'s pre-zeroed table when there is one (full batch: one fill per learn(), not per update)
         both = self._sum_rows.pop() if getattr(self, "_sum_rows", None) else torch.zeros(2, 4, dtype=torch.float64, device=xin.device)
         sums = both[0]
@@ -741,10 +795,15 @@ class PPO(_GpuLearner):
             coefs = (-1.0 / n_global, self.c1 / n_global, self.kl_coeff / n_global)
         for lo in range(0, xin.shape[0], self.chunk_rows):
             hi = min(lo + self.chunk_rows, xin.shape[0])
+            std_rows = self._std_rows(hi - lo, xin.device, max(xin.shape[0], 1)) if ls is not None else None
             if fuse:            # both loss heads + head gradients inside the forward chains (tg_mlp_forward_chain_loss)
                 m_a.forward_loss(xin[lo:hi], 0, act=act[lo:hi], logp_old=old_logp[lo:hi], adv=adv[lo:hi], norm=nh[0:2] if host else None,
-                                 var=var, epsilon=self.epsilon, surr_coef=coefs[0], kl_coef=coefs[2], sums_out=both[0],
-                                 logp_old_out=old_logp[lo:hi] if write_old else None, norm8=dev8)
+                                 var=None if ls is not None else var, epsilon=self.epsilon, surr_coef=coefs[0], kl_coef=coefs[2],
+                                 sums_out=both[0], logp_old_out=old_logp[lo:hi] if write_old else None, norm8=dev8,
+                                 log_std=ls, std_out=std_rows)
+                if ls is not None:
+                    self._std_reduce(ls, std_rows, ent_add)
+                    ent_add = 0.0
                 m_a.backward_fused()
                 m_c.forward_loss(xin[lo:hi], 1, ret=ret[lo:hi], norm=nh[2:4] if host else None, critic_coef=coefs[1], sums_out=both[1],
                                  norm8=dev8)
@@ -755,10 +814,16 @@ class PPO(_GpuLearner):
             value = vout.reshape(-1).contiguous()
             _, s, g_mean, g_val = K.surrogate_loss(mean.detach(), value.detach(), act[lo:hi], old_logp[lo:hi], adv[lo:hi],
                                                    ret[lo:hi], None, norm8[:4], var, self.epsilon, coefs[0], coefs[1], coefs[2],
-                                                   want_total=False, coef=norm8[4:7] if host is None else None)
+                                                   want_total=False, coef=norm8[4:7] if host is None else None,
+                                                   log_std=ls, std_out=std_rows)
+            if ls is not None:
+                self._std_reduce(ls, std_rows, ent_add)
+                ent_add = 0.0
             self._backward(actor, mean, g_mean)
             self._backward(critic, vout, g_val.view_as(vout))
             sums += s
+        if ent_add != 0.0:                                                   # (a rank-0 step without rows: an empty minibatch slice)
+            ls.grad.add_(ent_add)
         self.bucket.allreduce(self.process_group)                            # one RCCL all-reduce / step
         self._optimizer_step(actor, critic, last=last)
         sums_out.append(both)
@@ -897,7 +962,10 @@ class PPO(_GpuLearner):
         if all_sums:
             S2 = table if table is not None else torch.stack(all_sums)      # [steps][actor | critic][4]
             D.allreduce_sum_(S2, self.process_group, "loss_stats")
-            ent = 0.5 * act.shape[1] * (1.0 + math.log(2 * math.pi)) + 0.5 * float(torch.log(var).sum())
+            ls = self._learned_std()
+            ent = 0.5 * act.shape[1] * (1.0 + math.log(2 * math.pi)) + (0.0 if ls is not None else 0.5 * float(torch.log(var).sum()))
+            std_blocks, std_steps = self._std_blocks, self._std_steps       # (sum log_std before each step, on the device)
+            ls_end = ls.detach().clone() if ls is not None else None
             c1, ent_c, kl_c = self.c1, self.entropy, self.kl_coeff
             n_dev = moments[0, 0].clone()                                   # (the buffers above are re-used by the next learn())
 
@@ -906,9 +974,16 @@ class PPO(_GpuLearner):
                 S[:, 1] += S2[:, 1, 1]                                      # the critic's squared error
                 nn = S[:, 3]
                 a_loss, c_loss, kl = -S[:, 0] / nn, S[:, 1] / nn, S[:, 2] / nn
-                total = a_loss + c1 * c_loss - ent_c * ent + kl_c * kl
+                if ls_end is None:
+                    ent_out = ent_steps = ent
+                else:                                                       # one entropy per optimizer step, taken before the step
+                    ent_steps = ent + torch.cat(std_blocks)[:std_steps].double()
+                    ent_out = ent_steps.tolist()
+                total = a_loss + c1 * c_loss - ent_c * ent_steps + kl_c * kl
                 out = {"actor_loss": a_loss.tolist(), "critic_loss": c_loss.tolist(), "kl_div": kl.tolist(),
-                       "total_loss": total.tolist(), "entropy": ent, "n_valid": float(n_dev)}
+                       "total_loss": total.tolist(), "entropy": ent_out, "n_valid": float(n_dev)}
+                if ls_end is not None:
+                    out["log_std"] = ls_end.tolist()
                 if n_boot is not None:
                     out["n_bootstrapped"] = int(n_boot.item())
                 return out

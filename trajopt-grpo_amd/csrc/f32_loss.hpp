@@ -17,19 +17,23 @@ struct F32Loss {            // (as ChainLoss of mlp_fwd_chain.hip)
     double* work;           // out: f64 [grid][4] partial loss sums (surrogate, squared error, KL, count)
     // kRef instantiations only (tg_ref_penalty): log pi_ref of the row [rows] and coef * beta; read, never written, by the device
     const float* logp_ref; float ref_coef;
+    // kStd instantiations only (tg_learned_std): the policy's log_std [A] on the device (inv_var / logp_const are formed from it at
+    // kernel entry) and the per-row d loss / d log_std side output f32 [rows][4]
+    const float* log_std; float* std_out;
 };
 
 // host: tg_chain_loss (+ the reference policy's penalty, or null) -> F32Loss
-static inline void fill_f32_loss(F32Loss& L, const tg_chain_loss* loss, const tg_ref_penalty* ref = nullptr) {
+static inline void fill_f32_loss(F32Loss& L, const tg_chain_loss* loss, const tg_ref_penalty* ref = nullptr, const tg_learned_std* std = nullptr) {
     L.kind = loss->kind; L.A = loss->act_dim;
     L.act = loss->kind == 0 ? loss->d_act : loss->d_ret;
     L.logp_old = loss->d_logp_old; L.adv = loss->d_adv; L.logp_old_out = loss->kind == 0 ? loss->d_logp_old_out : nullptr;
     L.n_m = loss->norm_mean; L.n_i = loss->norm_inv; L.norm8 = loss->d_norm8;
     float logdet = 0.f;
     for (int k = 0; k < 4; ++k) {
-        L.inv_var[k] = k < loss->act_dim ? 1.0f / loss->var[k] : 0.f;
-        if (k < loss->act_dim) logdet += logf(loss->var[k]);
+        L.inv_var[k] = (k < loss->act_dim && std == nullptr) ? 1.0f / loss->var[k] : 0.f;
+        if (k < loss->act_dim && std == nullptr) logdet += logf(loss->var[k]);
     }
+    L.log_std = std != nullptr ? std->d_log_std : nullptr; L.std_out = std != nullptr ? std->d_out : nullptr;
     L.logp_const = -0.5f * (float)loss->act_dim * 1.8378770664093453f - 0.5f * logdet;
     L.epsilon = loss->epsilon; L.surr_coef = loss->surr_coef; L.critic_coef = loss->critic_coef; L.kl_coef = loss->kl_coef;
     L.dout4 = (float*)loss->d_dout8; L.work = loss->d_work;
@@ -37,11 +41,24 @@ static inline void fill_f32_loss(F32Loss& L, const tg_chain_loss* loss, const tg
 }
 
 // device, at kernel entry: the normalisation pair and the coefficients from the device when PPO keeps them there
+// kStd: also the Gaussian's constants from the policy's log_std (uniform loads; columns >= A keep inv_var = 0)
+template <bool kStd = false>
 __device__ static inline void f32_loss_from_device(F32Loss& L) {
     if (L.norm8 != nullptr) {
         const int q = L.kind == 1 ? 2 : 0;
         L.n_m = L.norm8[q]; L.n_i = L.norm8[q + 1];
         L.surr_coef = L.norm8[4]; L.critic_coef = L.norm8[5]; L.kl_coef = L.norm8[6];
+    }
+    if constexpr (kStd) {
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < L.A) {
+                const float ls = L.log_std[k];
+                L.inv_var[k] = expf(-2.0f * ls);
+                sum += ls;
+            }
+        L.logp_const = -0.5f * (float)L.A * 1.8378770664093453f - sum;
     }
 }
 
@@ -76,7 +93,8 @@ __device__ static inline F32LossIn f32_loss_load(const F32Loss& L, int64_t rowc)
 // (identical bytes), so that every store instruction is issued whatever the row count.
 // kRef: GRPO's penalty to the reference policy, x = lp_ref - lp, D = exp(x) - x - 1 (grpo.py:133): D joins the KL sum and
 // d loss / d lp gains ref_coef (exp(x) - 1), ref_coef = coef * beta (the term enters J as - beta D).
-template <bool kZeroInvalid = true, bool kRef = false>
+// kStd: the row's contribution to d loss / d log_std, dlp (dmu_k^2 inv_var_k - 1), to std_out[row][4] (valid rows, the writer lane)
+template <bool kZeroInvalid = true, bool kRef = false, bool kStd = false>
 __device__ static inline void f32_loss_compute(const F32Loss& L, const F32LossIn& in, const float (&o)[4], int64_t row, bool valid, bool writer,
                                                float (&g)[4], float& c_surr, float& c_crit, float& c_kl) {
     g[0] = g[1] = g[2] = g[3] = 0.f;
@@ -118,6 +136,14 @@ __device__ static inline void f32_loss_compute(const F32Loss& L, const F32LossIn
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) g[k] = dlp * dmu[k] * L.inv_var[k];
+        if constexpr (kStd) {
+            if (valid && writer) {
+                float gs[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) gs[k] = k < L.A ? dlp * (dmu[k] * dmu[k] * L.inv_var[k] - 1.0f) : 0.f;
+                *reinterpret_cast<float4*>(L.std_out + row * 4) = float4{gs[0], gs[1], gs[2], gs[3]};
+            }
+        }
     } else {
         const float d = o[0] - (in.act[0] - L.n_m) * L.n_i;
         c_crit = d * d;
@@ -129,11 +155,11 @@ __device__ static inline void f32_loss_compute(const F32Loss& L, const F32LossIn
 }
 
 // One row, inputs loaded on the spot (`rowc` = the row clamped into range).
-template <bool kZeroInvalid = true, bool kRef = false>
+template <bool kZeroInvalid = true, bool kRef = false, bool kStd = false>
 __device__ static inline void f32_loss_row(const F32Loss& L, const float (&o)[4], int64_t row, int64_t rowc, bool valid, bool writer,
                                            float (&g)[4], float& c_surr, float& c_crit, float& c_kl) {
     const F32LossIn in = f32_loss_load<kRef>(L, rowc);
-    f32_loss_compute<kZeroInvalid, kRef>(L, in, o, row, valid, writer, g, c_surr, c_crit, c_kl);
+    f32_loss_compute<kZeroInvalid, kRef, kStd>(L, in, o, row, valid, writer, g, c_surr, c_crit, c_kl);
 }
 
 }  // namespace tg

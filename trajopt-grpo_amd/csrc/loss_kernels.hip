@@ -47,13 +47,23 @@ struct LossK {
     float epsilon, surr_coef, critic_coef, kl_coef;
     float* grad_mean; float* grad_value; double* work; int64_t M;
     const float* logp_ref; float ref_coef;      // kRef only (tg_ref_penalty)
+    const float* log_std; float* std_out;       // kStd only (tg_learned_std): device log_std [A]; out f32 [M][4]
 };
 
 // kRef: GRPO's KL penalty to a frozen reference policy (tg_surrogate_loss_ref): x = lp_ref - lp, D = exp(x) - x - 1 into the KL sum,
 // d total / d logp += ref_coef (exp(x) - 1)
-template <int A, bool kRef = false>
+// kStd: the policy's learned log-std (tg_surrogate_loss_std): inv_var / logp_const are formed here from the device's log_std, and
+// the row's contribution to d total / d log_std, dlp (dmu_k^2 inv_var_k - 1), goes to std_out[row][4] (zeros for a masked row)
+template <int A, bool kRef = false, bool kStd = false>
 __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
     __shared__ double sh[4][4];
+    Var8 v = p.v;
+    if constexpr (kStd) {
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < A; ++k) { const float ls = p.log_std[k]; v.inv_var[k] = expf(-2.0f * ls); sum += ls; }
+        v.logp_const = -0.5f * (float)A * 1.8378770664093453f - sum;
+    }
     double s_surr = 0, s_crit = 0, s_kl = 0, s_cnt = 0;
     float n_am = 0.f, n_ai = 1.f, n_rm = 0.f, n_ri = 1.f;
     if (p.norm != nullptr) { n_am = p.norm[0]; n_ai = p.norm[1]; n_rm = p.norm[2]; n_ri = p.norm[3]; }
@@ -68,11 +78,12 @@ __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
 #pragma unroll
         for (int k = 0; k < A; ++k) g[k] = 0.0f;
         float gv = 0.0f;
+        [[maybe_unused]] float gs[4] = {0.f, 0.f, 0.f, 0.f};
         if (valid) {
             float mu[A], a[A];
 #pragma unroll
             for (int k = 0; k < A; ++k) { mu[k] = p.mean[i * p.mean_rs + k]; a[k] = p.act[i * p.act_rs + k * p.act_cs]; }
-            const float lp = gaussian_logp(mu, a, p.v, A);
+            const float lp = gaussian_logp(mu, a, v, A);
             const float lpo = p.logp_old[i];
             const float adv = (p.adv[i] - n_am) * n_ai;
             const float rho = expf(lp - lpo);
@@ -97,7 +108,11 @@ __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
                 dlp += ref_coef * em1;
             }
 #pragma unroll
-            for (int k = 0; k < A; ++k) g[k] = dlp * (a[k] - mu[k]) * p.v.inv_var[k];   // d logp / d mu_k
+            for (int k = 0; k < A; ++k) g[k] = dlp * (a[k] - mu[k]) * v.inv_var[k];   // d logp / d mu_k
+            if constexpr (kStd) {
+#pragma unroll
+                for (int k = 0; k < (A < 4 ? A : 4); ++k) gs[k] = dlp * ((a[k] - mu[k]) * (a[k] - mu[k]) * v.inv_var[k] - 1.0f);
+            }
             if (p.value != nullptr) {
                 const float d = p.value[i] - (p.ret[i] - n_rm) * n_ri;
                 s_crit += (double)(d * d);
@@ -108,6 +123,7 @@ __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
 #pragma unroll
         for (int k = 0; k < A; ++k) p.grad_mean[i * A + k] = g[k];
         if (p.grad_value != nullptr) p.grad_value[i] = gv;
+        if constexpr (kStd) *reinterpret_cast<float4*>(p.std_out + i * 4) = float4{gs[0], gs[1], gs[2], gs[3]};
     }
     double acc[4] = {s_surr, s_crit, s_kl, s_cnt};
 #pragma unroll
@@ -149,6 +165,42 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const double* __restric
         const int j = threadIdx.x;
         sums[j] = ((sh[j][0] + sh[j][1]) + sh[j][2]) + sh[j][3];
     }
+}
+
+// d loss / d log_std: column sums of the heads' [rows][4] side output in f64, fixed order: a grid-stride pass into per-block
+// partials, then one block adds the partials in index order and ADDS the result (+ `add`) into the gradient window.
+constexpr int kStdBlocks = 256;
+
+__global__ __launch_bounds__(256) void log_std_partial_kernel(const float4* __restrict__ rows4, int64_t rows, double* __restrict__ work) {
+    __shared__ double sh[4][4];
+    double acc[4] = {0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {
+        const float4 r = rows4[i];
+        acc[0] += (double)r.x; acc[1] += (double)r.y; acc[2] += (double)r.z; acc[3] += (double)r.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sh[j][w] = acc[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int j = threadIdx.x;
+        work[(int64_t)blockIdx.x * 4 + j] = ((sh[j][0] + sh[j][1]) + sh[j][2]) + sh[j][3];
+    }
+}
+
+__global__ __launch_bounds__(64) void log_std_final_kernel(const double* __restrict__ work, int nblocks, int A, float add, float* __restrict__ grad) {
+    const int j = threadIdx.x;
+    if (j >= A) return;
+    double t = 0.0;
+    for (int b = 0; b < nblocks; ++b) t += work[(int64_t)b * 4 + j];
+    grad[j] = (float)((double)grad[j] + t + (double)add);
 }
 
 static int make_var(const float* var, int A, Var8& v, const char* who) {
@@ -193,18 +245,26 @@ int tg_gaussian_logp(const float* d_mean, int64_t mean_row_stride, const float* 
     return TG_OK;
 }
 
-static int surrogate_loss(const tg_loss_args* a, const tg_ref_penalty* ref, void* stream) {
+static int surrogate_loss(const tg_loss_args* a, const tg_ref_penalty* ref, void* stream, const tg_learned_std* std = nullptr) {
     TG_REQUIRE(a != nullptr, "tg_surrogate_loss: null args");
     const int use_ref = ref_penalty_check(ref, a->d_value != nullptr, a->kl_coef, "tg_surrogate_loss_ref");
     if (use_ref < 0) return use_ref;
+    // (PPO's per-layer path scores actor and critic in one launch: a learned log-std is refused only for a head without actions)
+    const int use_std = learned_std_check(std, a->d_act == nullptr, a->act_dim, "tg_surrogate_loss_std");
+    if (use_std < 0) return use_std;
     TG_REQUIRE(a->d_mean && a->d_act && a->d_logp_old && a->d_adv && a->d_grad_mean && a->d_sums && a->d_work,
                "tg_surrogate_loss: null pointer");
     TG_REQUIRE((a->d_value == nullptr) == (a->d_ret == nullptr), "tg_surrogate_loss: value and ret go together");
     TG_REQUIRE(a->d_value == nullptr || a->d_grad_value != nullptr, "tg_surrogate_loss: grad_value missing");
     TG_REQUIRE(a->M >= 0 && a->mean_row_stride >= a->act_dim, "tg_surrogate_loss: bad sizes");
     LossK k;
-    int rc = make_var(a->var, a->act_dim, k.v, "tg_surrogate_loss");
-    if (rc != TG_OK) return rc;
+    if (use_std) {
+        k.v = Var8{};                               // (formed on the device from log_std)
+    } else {
+        int rc = make_var(a->var, a->act_dim, k.v, "tg_surrogate_loss");
+        if (rc != TG_OK) return rc;
+    }
+    k.log_std = use_std ? std->d_log_std : nullptr; k.std_out = use_std ? std->d_out : nullptr;
     k.mean = a->d_mean; k.mean_rs = a->mean_row_stride;
     k.act = a->d_act; k.act_rs = a->act_row_stride; k.act_cs = a->act_col_stride;
     k.logp_old = a->d_logp_old; k.adv = a->d_adv; k.value = a->d_value; k.ret = a->d_ret;
@@ -220,8 +280,18 @@ static int surrogate_loss(const tg_loss_args* a, const tg_ref_penalty* ref, void
         if (use_ref) hipLaunchKernelGGL((surrogate_loss_kernel<AA, true>), dim3(grid), dim3(kLossThreads), 0, st, k); \
         else hipLaunchKernelGGL(surrogate_loss_kernel<AA>, dim3(grid), dim3(kLossThreads), 0, st, k);   \
         break;
-    switch (a->act_dim) { L(1) L(2) L(3) L(4) L(5) L(6) L(7) L(8) }
+#define LS(AA)                                                                                           \
+    case AA:                                                                                             \
+        if (use_ref) hipLaunchKernelGGL((surrogate_loss_kernel<AA, true, true>), dim3(grid), dim3(kLossThreads), 0, st, k); \
+        else hipLaunchKernelGGL((surrogate_loss_kernel<AA, false, true>), dim3(grid), dim3(kLossThreads), 0, st, k);   \
+        break;
+    if (use_std) {
+        switch (a->act_dim) { LS(1) LS(2) LS(3) LS(4) }
+    } else {
+        switch (a->act_dim) { L(1) L(2) L(3) L(4) L(5) L(6) L(7) L(8) }
+    }
 #undef L
+#undef LS
     TG_LAUNCH_CHECK("tg_surrogate_loss");
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, a->d_work, (int)grid, a->d_sums);
     TG_LAUNCH_CHECK("tg_surrogate_loss(final)");
@@ -231,5 +301,25 @@ static int surrogate_loss(const tg_loss_args* a, const tg_ref_penalty* ref, void
 int tg_surrogate_loss(const tg_loss_args* a, void* stream) { return surrogate_loss(a, nullptr, stream); }
 
 int tg_surrogate_loss_ref(const tg_loss_args* a, const tg_ref_penalty* ref, void* stream) { return surrogate_loss(a, ref, stream); }
+
+int tg_surrogate_loss_std(const tg_loss_args* a, const tg_ref_penalty* ref, const tg_learned_std* std, void* stream) {
+    return surrogate_loss(a, ref, stream, std);
+}
+
+int tg_log_std_grad_blocks(void) { return kStdBlocks; }
+
+int tg_log_std_grad(const float* d_rows4, int64_t rows, int32_t act_dim, float add, float* d_grad, double* d_work, void* stream) {
+    TG_REQUIRE(d_rows4 && d_grad && d_work, "tg_log_std_grad: null pointer");
+    TG_REQUIRE(rows >= 0 && act_dim >= 1 && act_dim <= 4, "tg_log_std_grad: bad sizes (rows %lld, act_dim %d)", (long long)rows, act_dim);
+    TG_REQUIRE(((uintptr_t)d_rows4 & 15) == 0, "tg_log_std_grad: the rows are not 16-B aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nb = ceil_div(rows > 0 ? rows : 1, (int64_t)256 * 8);
+    const unsigned grid = (unsigned)(nb < kStdBlocks ? nb : kStdBlocks);
+    hipLaunchKernelGGL(log_std_partial_kernel, dim3(grid), dim3(256), 0, st, (const float4*)d_rows4, rows, d_work);
+    TG_LAUNCH_CHECK("tg_log_std_grad");
+    hipLaunchKernelGGL(log_std_final_kernel, dim3(1), dim3(64), 0, st, d_work, (int)grid, act_dim, add, d_grad);
+    TG_LAUNCH_CHECK("tg_log_std_grad(final)");
+    return TG_OK;
+}
 
 }  // extern "C"

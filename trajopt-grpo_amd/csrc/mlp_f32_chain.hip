@@ -84,9 +84,11 @@ int attach_probe_f32(int which, void* d_probe) { return which == 0 ? attach_prob
 // dz[top]); Tanh takes dZ = dA (1 - a^2) from the fp32 activations themselves: the top layer's are still in registers when the head's
 // gradient is formed, each layer below re-reads the tile of acts[l - 1] this lane stored itself in the forward pass (same lane, same
 // addresses: its own earlier stores), so every acts[i] and dz[i] is written and nothing is rebuilt.
-template <int H, bool kTrain, bool kRef = false, int kAct = TG_ACT_RELU>
+// kStd (training only): the policy's learned log-std, read from the device at entry; per-row d loss / d log_std (f32_loss.hpp)
+template <int H, bool kTrain, bool kRef = false, int kAct = TG_ACT_RELU, bool kStd = false>
 __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
     static_assert(!kRef || kTrain, "the reference penalty is a term of the training pass");
+    static_assert(!kStd || kTrain, "the learned log-std is a term of the training pass");
     static_assert(act_supported<kAct>(), "unknown hidden activation");
     constexpr bool kRelu = kAct == TG_ACT_RELU;
     constexpr int MT = H / 32;                  // 32-feature tiles per layer
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
     // (a LOCAL copy: writing into the by-value argument struct itself sends all of it to scratch -- 272 B per lane and 23 more
     // registers in this kernel, 9 % of a small PPO epoch, measured in round 5)
     F32Loss L = a.loss;
-    if constexpr (kTrain) f32_loss_from_device(L);
+    if constexpr (kTrain) f32_loss_from_device<kStd>(L);
     const bool resident = a.resident != 0;
     // LDS (f32_chain_lds() on the host computes the same sizes): the block ring (2 blocks) or the whole resident stream, the
     // first layer's fragments, bias / head tables, the ReLU mask bits of the (n_hh + 1) hidden layers, the loss-sum scratch
@@ -310,7 +312,7 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
         } else {
             // ---- loss head (loss_kernels.hip::surrogate_loss_kernel, same arithmetic), evaluated by both lane halves ----
             float g[4], c_surr, c_crit, c_kl;
-            f32_loss_row<true, kRef>(L, o, row, rowc, valid, h == 0, g, c_surr, c_crit, c_kl);
+            f32_loss_row<true, kRef, kStd>(L, o, row, rowc, valid, h == 0, g, c_surr, c_crit, c_kl);
             if (valid && h == 0) {
                 s_surr += (double)c_surr; s_crit += (double)c_crit; s_kl += (double)c_kl; s_cnt += 1.0;
                 *reinterpret_cast<float4*>(L.dout4 + row * 4) = float4{g[0], g[1], g[2], g[3]};
@@ -424,9 +426,9 @@ static int f32_chain_grid(int64_t rows) {
     return (int)(n_rounds < cus ? n_rounds : cus);
 }
 
-template <int H, bool kTrain, bool kRef = false, int kAct = TG_ACT_RELU>
+template <int H, bool kTrain, bool kRef = false, int kAct = TG_ACT_RELU, bool kStd = false>
 static int launch_f32_chain(const F32ChainArgs& args_in, hipStream_t st) {
-    auto kern = mlp_f32_chain_kernel<H, kTrain, kRef, kAct>;
+    auto kern = mlp_f32_chain_kernel<H, kTrain, kRef, kAct, kStd>;
     F32ChainArgs args = args_in;
     const int n_stream = args.net.n_hh * (H / 32) * (kTrain ? 2 : 1);
     args.resident = n_stream > 0 && f32_chain_lds<H>(args.net.n_hh, args.net.k2, n_stream) <= 160 * 1024;
@@ -1614,7 +1616,7 @@ int tg_mlp_f32_forward_act(const float* d_x, int32_t in_pad, const float* d_stre
 
 static int f32_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
                                 int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits, const tg_chain_loss* loss,
-                                const tg_ref_penalty* ref, int32_t activation, void* stream) {
+                                const tg_ref_penalty* ref, int32_t activation, void* stream, const tg_learned_std* std = nullptr) {
     TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "tg_mlp_f32_forward_backward_act: unknown activation %d", activation);
     // (Tanh: a mask bit cannot stand for 1 - a^2 -- nothing is rebuilt, every activation and dZ is written)
     TG_REQUIRE(activation == TG_ACT_RELU || d_top_maskbits == nullptr,
@@ -1622,6 +1624,8 @@ static int f32_forward_backward(const float* d_x, int32_t in_pad, const float* d
     TG_REQUIRE(loss, "tg_mlp_f32_forward_backward: null pointer");
     const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_f32_forward_backward_ref");
     if (use_ref < 0) return use_ref;
+    const int use_std = learned_std_check(std, loss->kind != 0, loss->act_dim, "tg_mlp_f32_forward_backward_act_std");
+    if (use_std < 0) return use_std;
     TG_REQUIRE(d_x && d_stream && d_acts && d_dz, "tg_mlp_f32_forward_backward: null pointer");
     TG_REQUIRE(rows > 0, "tg_mlp_f32_forward_backward: no rows");
     TG_REQUIRE(loss->kind == 0 || loss->kind == 1, "tg_mlp_f32_forward_backward: kind %d", loss->kind);
@@ -1644,8 +1648,14 @@ static int f32_forward_backward(const float* d_x, int32_t in_pad, const float* d
     }
     a.top_mask = (uint32_t*)d_top_maskbits;
     a.x = d_x; a.rows = rows;
-    fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr);
+    fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr, use_std ? std : nullptr);
     hipStream_t st = (hipStream_t)stream;
+    if (use_std) {                                      // (separate instantiations: the plain heads below are untouched)
+#define TG_STD_LAUNCH(REF, ACT) (hidden == 128 ? launch_f32_chain<128, true, REF, ACT, true>(a, st) : launch_f32_chain<64, true, REF, ACT, true>(a, st))
+        if (activation == TG_ACT_TANH) return use_ref ? TG_STD_LAUNCH(true, TG_ACT_TANH) : TG_STD_LAUNCH(false, TG_ACT_TANH);
+        return use_ref ? TG_STD_LAUNCH(true, TG_ACT_RELU) : TG_STD_LAUNCH(false, TG_ACT_RELU);
+#undef TG_STD_LAUNCH
+    }
     if (activation == TG_ACT_TANH) {
         if (use_ref) return hidden == 128 ? launch_f32_chain<128, true, true, TG_ACT_TANH>(a, st) : launch_f32_chain<64, true, true, TG_ACT_TANH>(a, st);
         return hidden == 128 ? launch_f32_chain<128, true, false, TG_ACT_TANH>(a, st) : launch_f32_chain<64, true, false, TG_ACT_TANH>(a, st);
@@ -1673,6 +1683,13 @@ int tg_mlp_f32_forward_backward_act(const float* d_x, int32_t in_pad, const floa
                                     const tg_ref_penalty* ref, int32_t activation, void* stream) {
     return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref,
                                 activation, stream);
+}
+
+int tg_mlp_f32_forward_backward_act_std(const float* d_x, int32_t in_pad, const float* d_stream, int32_t hidden, int32_t n_hidden_layers,
+                                        int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits, const tg_chain_loss* loss,
+                                        const tg_ref_penalty* ref, const tg_learned_std* std, int32_t activation, void* stream) {
+    return f32_forward_backward(d_x, in_pad, d_stream, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref,
+                                activation, stream, std);
 }
 
 int64_t tg_mlp_f32_weight_grad_workspace(int32_t hidden) {

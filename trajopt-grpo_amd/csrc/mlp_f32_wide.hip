@@ -62,8 +62,9 @@ static size_t f32_wide_lds() {
 
 TG_CLOCK_PROBE_VAR(g_probe_f32_wide, attach_probe_f32_wide)
 
-template <bool kTrain, bool kRef = false>                                // kRef: GRPO's reference-policy penalty (f32_loss.hpp)
+template <bool kTrain, bool kRef = false, bool kStd = false>             // kRef: GRPO's reference-policy penalty, kStd: the learned log-std (f32_loss.hpp)
 __global__ __launch_bounds__(256, 2) void mlp_f32_wide_kernel(F32WideArgs a) {
+    static_assert(!kStd || kTrain, "the learned log-std is a term of the training pass");
     static_assert(!kRef || kTrain, "the reference penalty is a term of the training pass");
     constexpr int H = kWideH, NT = H / 16, D = kWideD, P = kWideP, WPW = kWideWaves, KS = kWidePieces;
     extern __shared__ uint4 lds[];
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_wide_kernel(F32WideArgs a) {
     const int64_t n_rounds = (rows + 63) / 64;
     F32Loss L = a.loss;                                                       // (a local copy: scalars in registers, not a re-read kernarg)
     if constexpr (kTrain) {
-        f32_loss_from_device(L);
+        f32_loss_from_device<kStd>(L);
         TG_CLOCK_PROBE_BEGIN(g_probe_f32_wide)
     }
     // a.acts[l] / a.dz[l] with a run-time l would put the whole argument struct into scratch: uniform selects instead
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_wide_kernel(F32WideArgs a) {
             if (valid && g == 0) *reinterpret_cast<float4*>(a.out + row * 4) = float4{o[0], o[1], o[2], o[3]};
         } else {
             float gr[4], c_surr, c_crit, c_kl;
-            f32_loss_row<false, kRef>(L, o, row, rowc, valid, g == 0, gr, c_surr, c_crit, c_kl);
+            f32_loss_row<false, kRef, kStd>(L, o, row, rowc, valid, g == 0, gr, c_surr, c_crit, c_kl);
             if (valid && g == 0) {
                 s_surr += (double)c_surr; s_crit += (double)c_crit; s_kl += (double)c_kl; s_cnt += 1.0;
                 *reinterpret_cast<float4*>(L.dout4 + row * 4) = float4{gr[0], gr[1], gr[2], gr[3]};
@@ -345,9 +346,9 @@ static int f32_wide_grid(int64_t rows) {
     return (int)(n_rounds < slots ? n_rounds : slots);
 }
 
-template <bool kTrain, bool kRef = false>
+template <bool kTrain, bool kRef = false, bool kStd = false>
 static int launch_f32_wide(const F32WideArgs& args, hipStream_t st) {
-    auto kern = mlp_f32_wide_kernel<kTrain, kRef>;
+    auto kern = mlp_f32_wide_kernel<kTrain, kRef, kStd>;
     const size_t shmem = f32_wide_lds();
     static LdsOptIn opt_in;
     if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_f32w_forward")) return rc;
@@ -411,8 +412,9 @@ static size_t f32_res_lds(int n_hh, int in_pad, bool train) {
 
 TG_CLOCK_PROBE_VAR(g_probe_f32_res, attach_probe_f32_res)
 
-template <int H, int K4, bool kTrain, bool kRef = false>                // K4 = padded input width / 4: the first layer's products per tile
-__global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32ResArgs a) {     // kRef: as mlp_f32_wide_kernel's
+template <int H, int K4, bool kTrain, bool kRef = false, bool kStd = false>   // K4 = padded input width / 4: the first layer's products per tile
+__global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32ResArgs a) {     // kRef, kStd: as mlp_f32_wide_kernel's
+    static_assert(!kStd || kTrain, "the learned log-std is a term of the training pass");
     static_assert(!kRef || kTrain, "the reference penalty is a term of the training pass");
     constexpr int NT = H / 16, WPW = res_waves(kTrain), BLK = NT * 64;           // uint4 per block
     extern __shared__ uint4 lds[];
@@ -430,7 +432,7 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
     const int64_t n_wr = (rows + 15) / 16;                               // wave-rounds of 16 rows
     F32Loss L = a.loss;
     if constexpr (kTrain) {
-        f32_loss_from_device(L);
+        f32_loss_from_device<kStd>(L);
         TG_CLOCK_PROBE_BEGIN(g_probe_f32_res)
     }
     for (int q = tid; q < n_stream * BLK; q += 64 * WPW) strm[q] = a.stream[q];
@@ -595,7 +597,7 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
             if (valid && g == 0) *reinterpret_cast<float4*>(a.out + q * 64 + jr * 4) = float4{o[0], o[1], o[2], o[3]};
         } else {
             float gr[4], c_surr, c_crit, c_kl;
-            f32_loss_compute<false, kRef>(L, lin, o, row, valid, g == 0, gr, c_surr, c_crit, c_kl);
+            f32_loss_compute<false, kRef, kStd>(L, lin, o, row, valid, g == 0, gr, c_surr, c_crit, c_kl);
             if (valid && g == 0) {
                 s_surr += (double)c_surr; s_crit += (double)c_crit; s_kl += (double)c_kl; s_cnt += 1.0;
                 *reinterpret_cast<float4*>(L.dout4 + q * 64 + jr * 4) = float4{gr[0], gr[1], gr[2], gr[3]};
@@ -674,9 +676,9 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
     }
 }
 
-template <int K4, bool kTrain, bool kRef = false>
+template <int K4, bool kTrain, bool kRef = false, bool kStd = false>
 static int launch_f32_res_k(const F32ResArgs& args, hipStream_t st) {
-    auto kern = mlp_f32_res_kernel<128, K4, kTrain, kRef>;
+    auto kern = mlp_f32_res_kernel<128, K4, kTrain, kRef, kStd>;
     const size_t shmem = f32_res_lds<128>(args.n_hh, args.in_pad, kTrain);
     static LdsOptIn opt_in;
     if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_f32r_forward")) return rc;
@@ -686,13 +688,13 @@ static int launch_f32_res_k(const F32ResArgs& args, hipStream_t st) {
     TG_LAUNCH_CHECK("tg_mlp_f32r_forward");
     return TG_OK;
 }
-template <bool kTrain, bool kRef = false>
+template <bool kTrain, bool kRef = false, bool kStd = false>
 static int launch_f32_res(const F32ResArgs& args, hipStream_t st) {
     switch (args.in_pad) {
-        case 8: return launch_f32_res_k<2, kTrain, kRef>(args, st);
-        case 16: return launch_f32_res_k<4, kTrain, kRef>(args, st);
-        case 24: return launch_f32_res_k<6, kTrain, kRef>(args, st);
-        default: return launch_f32_res_k<8, kTrain, kRef>(args, st);
+        case 8: return launch_f32_res_k<2, kTrain, kRef, kStd>(args, st);
+        case 16: return launch_f32_res_k<4, kTrain, kRef, kStd>(args, st);
+        case 24: return launch_f32_res_k<6, kTrain, kRef, kStd>(args, st);
+        default: return launch_f32_res_k<8, kTrain, kRef, kStd>(args, st);
     }
 }
 
@@ -1008,10 +1010,12 @@ int tg_mlp_f32r_forward(const float* d_x, int32_t in_pad, const float* d_stream,
 
 static int f32r_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table, int32_t hidden,
                                  int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_dz, void* d_top_maskbits,
-                                 const tg_chain_loss* loss, const tg_ref_penalty* ref, void* stream) {
+                                 const tg_chain_loss* loss, const tg_ref_penalty* ref, void* stream, const tg_learned_std* std = nullptr) {
     TG_REQUIRE(loss, "tg_mlp_f32r_forward_backward: null pointer");
     const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_f32r_forward_backward_ref");
     if (use_ref < 0) return use_ref;
+    const int use_std = learned_std_check(std, loss->kind != 0, loss->act_dim, "tg_mlp_f32r_forward_backward_std");
+    if (use_std < 0) return use_std;
     F32ResArgs a{};
     if (int rc = fill_f32_res(a, d_x, in_pad, d_stream, d_w0, d_table, hidden, n_hidden_layers, rows, "tg_mlp_f32r_forward_backward")) return rc;
     TG_REQUIRE(loss && d_acts && d_dz, "tg_mlp_f32r_forward_backward: null pointer");
@@ -1030,7 +1034,8 @@ static int f32r_forward_backward(const float* d_x, int32_t in_pad, const float* 
         a.dz[l] = (float*)d_dz[l];
     }
     a.top_mask = (uint32_t*)d_top_maskbits;
-    fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr);
+    fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr, use_std ? std : nullptr);
+    if (use_std) return use_ref ? launch_f32_res<true, true, true>(a, (hipStream_t)stream) : launch_f32_res<true, false, true>(a, (hipStream_t)stream);
     return use_ref ? launch_f32_res<true, true>(a, (hipStream_t)stream) : launch_f32_res<true>(a, (hipStream_t)stream);
 }
 
@@ -1046,6 +1051,14 @@ int tg_mlp_f32r_forward_backward_ref(const float* d_x, int32_t in_pad, const flo
                                      void* d_top_maskbits, const tg_chain_loss* loss, const tg_ref_penalty* ref, void* stream) {
     return f32r_forward_backward(d_x, in_pad, d_stream, d_w0, d_table, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref,
                                  stream);
+}
+
+int tg_mlp_f32r_forward_backward_std(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_w0, const float* d_table,
+                                     int32_t hidden, int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_dz,
+                                     void* d_top_maskbits, const tg_chain_loss* loss, const tg_ref_penalty* ref, const tg_learned_std* std,
+                                     void* stream) {
+    return f32r_forward_backward(d_x, in_pad, d_stream, d_w0, d_table, hidden, n_hidden_layers, rows, d_acts, d_dz, d_top_maskbits, loss, ref,
+                                 stream, std);
 }
 
 int tg_mlp_f32w_blocks(void) { return 2 * device_cus(); }
@@ -1066,10 +1079,12 @@ int tg_mlp_f32w_forward(const float* d_x, int32_t in_pad, const float* d_stream,
 
 static int f32w_forward_backward(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
                                  int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss, const tg_ref_penalty* ref,
-                                 void* stream) {
+                                 void* stream, const tg_learned_std* std = nullptr) {
     TG_REQUIRE(loss, "tg_mlp_f32w_forward_backward: null pointer");
     const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_f32w_forward_backward_ref");
     if (use_ref < 0) return use_ref;
+    const int use_std = learned_std_check(std, loss->kind != 0, loss->act_dim, "tg_mlp_f32w_forward_backward_std");
+    if (use_std < 0) return use_std;
     F32WideArgs a{};
     if (int rc = fill_f32_wide(a, d_x, in_pad, d_stream, d_table, n_hidden_layers, rows, "tg_mlp_f32w_forward_backward")) return rc;
     TG_REQUIRE(loss && d_acts && d_dz, "tg_mlp_f32w_forward_backward: null pointer");
@@ -1085,7 +1100,8 @@ static int f32w_forward_backward(const float* d_x, int32_t in_pad, const float* 
         a.acts[l] = (float*)d_acts[l];
         a.dz[l] = (float*)d_dz[l];
     }
-    fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr);
+    fill_f32_loss(a.loss, loss, use_ref ? ref : nullptr, use_std ? std : nullptr);
+    if (use_std) return use_ref ? launch_f32_wide<true, true, true>(a, (hipStream_t)stream) : launch_f32_wide<true, false, true>(a, (hipStream_t)stream);
     return use_ref ? launch_f32_wide<true, true>(a, (hipStream_t)stream) : launch_f32_wide<true>(a, (hipStream_t)stream);
 }
 
@@ -1098,6 +1114,12 @@ int tg_mlp_f32w_forward_backward_ref(const float* d_x, int32_t in_pad, const flo
                                      int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss, const tg_ref_penalty* ref,
                                      void* stream) {
     return f32w_forward_backward(d_x, in_pad, d_stream, d_table, n_hidden_layers, rows, d_acts, d_dz, loss, ref, stream);
+}
+
+int tg_mlp_f32w_forward_backward_std(const float* d_x, int32_t in_pad, const float* d_stream, const float* d_table, int32_t n_hidden_layers,
+                                     int64_t rows, void* const* d_acts, void* const* d_dz, const tg_chain_loss* loss, const tg_ref_penalty* ref,
+                                     const tg_learned_std* std, void* stream) {
+    return f32w_forward_backward(d_x, in_pad, d_stream, d_table, n_hidden_layers, rows, d_acts, d_dz, loss, ref, stream, std);
 }
 
 }  // extern "C"

@@ -57,6 +57,8 @@ struct ChainLoss {                          // (kept small: every field is a sca
     float* bias_partial;                    // out: f32 [grid][4] partial head bias gradients
     const float* logp_ref; float ref_coef;  // kRef only (tg_ref_penalty): log pi_ref per row [rows] (staged beside the other loss
                                             // inputs, slot 6 of the wave's tile) and coef * beta
+    const float* log_std; float* std_out;   // kStd only (tg_learned_std): the policy's log_std [A] on the device (inv_var / logp_const
+                                            // are formed from it at entry); out f32 [rows][4]: the row's d loss / d log_std
 };
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
@@ -193,13 +195,29 @@ __device__ static inline int wave_of(unsigned tid) { return (int)(tid >> 6); }
 // block (natural k order) and a contiguous piece of the activation row.
 // kRef (with kHead): GRPO's KL penalty to a frozen reference policy in the loss head (tg_mlp_forward_chain_loss_ref): one more
 // per-row input, one expf per row.
-template <int H, int WPW, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false>
+// kStd (with kHead): the policy's learned log-std (tg_mlp_forward_chain_loss_std): the Gaussian's constants come from the device, and
+// each valid actor row stores dlp (dmu_k^2 inv_var_k - 1), its contribution to d loss / d log_std (one more 16-B store per row).
+template <int H, int WPW, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false>
 __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16_t* __restrict__ x, const uint4* __restrict__ wfrag,
                                                                     const float* __restrict__ bias, int32_t n_hh, int64_t rows,
                                                                     ChainActs acts, float* __restrict__ out, int32_t out_cols,
                                                                     ChainLoss L) {
     static_assert(!kHead || (kStore && !kA0), "the fused head belongs to the learner's training pass");
     static_assert(!kRef || kHead, "the reference penalty is a term of the fused head");
+    static_assert(!kStd || kHead, "the learned log-std is a term of the fused head");
+    // (written into the by-value argument as norm8's values are below: the compiler's resource report shows 0 B of scratch and no
+    // vector-register spill for every instantiation of this kernel, the kStd ones included -- the fields stay scalar registers)
+    if constexpr (kStd) {                                               // (uniform scalar loads, as norm8's below)
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < L.A) {
+                const float ls = L.log_std[k];
+                L.inv_var[k] = expf(-2.0f * ls);
+                sum += ls;
+            }
+        L.logp_const = -0.5f * (float)L.A * 1.8378770664093453f - sum;
+    }
     if constexpr (kHead) {
         if (L.norm8 != nullptr) {                                       // (uniform scalar loads, before anything is in flight)
             const int q = L.kind == 1 ? 2 : 0;
@@ -467,6 +485,12 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                                 }
 #pragma unroll
                                 for (int k = 0; k < 4; ++k) g[k] = dlp * dmu[k] * L.inv_var[k];
+                                if constexpr (kStd) {          // (one more store behind the head's: the counted waits only get stricter)
+                                    *reinterpret_cast<float4*>(L.std_out + rowc[c] * 4) =
+                                        float4{dlp * (dmu[0] * dmu[0] * L.inv_var[0] - 1.0f), L.A > 1 ? dlp * (dmu[1] * dmu[1] * L.inv_var[1] - 1.0f) : 0.f,
+                                               L.A > 2 ? dlp * (dmu[2] * dmu[2] * L.inv_var[2] - 1.0f) : 0.f,
+                                               L.A > 3 ? dlp * (dmu[3] * dmu[3] * L.inv_var[3] - 1.0f) : 0.f};
+                                }
                             } else {
                                 const float d = acc[c][0] - (lds_loadf(lin + rl) - L.n_m) * L.n_i;
                                 c_crit = d * d;
@@ -572,13 +596,13 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     if constexpr (kHead) { TG_CLOCK_PROBE_END(g_probe_fwd_chain) } else { TG_CLOCK_PROBE_END(g_probe_fwd_chain_plain) }
 }
 
-template <int H, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false>
+template <int H, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false>
 static int chain_launch(const void* x, const void* wfrag, const float* bias, int n_hh, int64_t rows, const ChainActs& acts, float* out,
                         int out_cols, hipStream_t st, const ChainLoss& loss = ChainLoss{}) {
     constexpr int WPW = 8, KS = H / 16;
     const size_t shmem = (size_t)D * KS * 1024 + (size_t)(n_hh + 2) * H * sizeof(float) + (size_t)WPW * 2048 +
                          (size_t)WPW * 32 * 128 + (kHead ? (size_t)2 * WPW * 1024 + (size_t)WPW * 16 * 48 + (size_t)WPW * (H / 32) * 16 * 16 : 0);
-    auto kern = mlp_fwd_chain_kernel<H, WPW, kStore, D, kA0, kHead, kRef>;
+    auto kern = mlp_fwd_chain_kernel<H, WPW, kStore, D, kA0, kHead, kRef, kStd>;
     static LdsOptIn opt_in;
     if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_forward_chain")) return rc;
     const int cus = device_cus();
@@ -630,10 +654,12 @@ int tg_mlp_forward_chain_blocks(void) { return device_cus(); }
 
 static int forward_chain_loss(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
                               int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss, const tg_ref_penalty* ref,
-                              void* stream) {
+                              void* stream, const tg_learned_std* std = nullptr) {
     TG_REQUIRE(loss, "tg_mlp_forward_chain_loss: null pointer");
     const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_forward_chain_loss_ref");
     if (use_ref < 0) return use_ref;
+    const int use_std = learned_std_check(std, loss->kind != 0, loss->act_dim, "tg_mlp_forward_chain_loss_std");
+    if (use_std < 0) return use_std;
     TG_REQUIRE(d_x && d_wfrag && d_bias && d_acts && d_masks, "tg_mlp_forward_chain_loss: null pointer");
     TG_REQUIRE(hidden == 128 || hidden == 256, "tg_mlp_forward_chain_loss: hidden width %d unsupported (128, 256)", hidden);
     TG_REQUIRE(n_hidden_layers >= 3 && n_hidden_layers <= kChainMaxHidden, "tg_mlp_forward_chain_loss: %d hidden layers outside 3..%d",
@@ -665,15 +691,23 @@ static int forward_chain_loss(const void* d_x, const void* d_wfrag, const float*
     L.n_m = loss->norm_mean; L.n_i = loss->norm_inv; L.norm8 = loss->d_norm8;
     float logdet = 0.f;
     for (int k = 0; k < 4; ++k) {
-        L.inv_var[k] = k < loss->act_dim ? 1.0f / loss->var[k] : 0.f;
-        if (k < loss->act_dim) logdet += logf(loss->var[k]);
+        L.inv_var[k] = (k < loss->act_dim && !use_std) ? 1.0f / loss->var[k] : 0.f;
+        if (k < loss->act_dim && !use_std) logdet += logf(loss->var[k]);
     }
     L.logp_const = -0.5f * (float)loss->act_dim * 1.8378770664093453f - 0.5f * logdet;
+    L.log_std = use_std ? std->d_log_std : nullptr; L.std_out = use_std ? std->d_out : nullptr;
     L.epsilon = loss->epsilon; L.surr_coef = loss->surr_coef; L.critic_coef = loss->critic_coef; L.kl_coef = loss->kl_coef;
     L.dout8 = (uint16_t*)loss->d_dout8; L.head_slabs = loss->d_head_slabs; L.work = loss->d_work; L.bias_partial = loss->d_bias_partial;
     L.logp_ref = use_ref ? ref->d_logp_ref : nullptr; L.ref_coef = use_ref ? ref->coef : 0.0f;
     hipStream_t st = (hipStream_t)stream;
     const int n_hh = n_hidden_layers - 1;
+    if (use_std) {                                      // (separate instantiations: the plain heads below are untouched)
+        if (use_ref)
+            return hidden == 256 ? chain_launch<256, true, 4, false, true, true, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L)
+                                 : chain_launch<128, true, 4, false, true, true, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L);
+        return hidden == 256 ? chain_launch<256, true, 4, false, true, false, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L)
+                             : chain_launch<128, true, 4, false, true, false, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L);
+    }
     if (use_ref)
         return hidden == 256 ? chain_launch<256, true, 4, false, true, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L)
                              : chain_launch<128, true, 4, false, true, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L);
@@ -690,6 +724,12 @@ int tg_mlp_forward_chain_loss_ref(const void* d_x, const void* d_wfrag, const fl
                                   int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
                                   const tg_ref_penalty* ref, void* stream) {
     return forward_chain_loss(d_x, d_wfrag, d_bias, hidden, n_hidden_layers, rows, d_acts, d_masks, loss, ref, stream);
+}
+
+int tg_mlp_forward_chain_loss_std(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                                  int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
+                                  const tg_ref_penalty* ref, const tg_learned_std* std, void* stream) {
+    return forward_chain_loss(d_x, d_wfrag, d_bias, hidden, n_hidden_layers, rows, d_acts, d_masks, loss, ref, stream, std);
 }
 
 }  // extern "C"

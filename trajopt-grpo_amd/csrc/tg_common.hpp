@@ -122,6 +122,14 @@ static inline int ref_penalty_check(const tg_ref_penalty* ref, bool critic, floa
     if (kl_coef != 0.0f) return set_error(TG_ERR_ARG, "%s: kl_coef must be 0 beside the reference-policy penalty (both use the KL sum)", who);
     return 1;
 }
+// The learned log-std of a `_std` entry point (tg_learned_std): 1 = active, 0 = none (the `_ref` entry's kernel), < 0 = refused.
+static inline int learned_std_check(const tg_learned_std* std, bool critic, int act_dim, const char* who) {
+    if (std == nullptr) return 0;
+    if (critic) return set_error(TG_ERR_ARG, "%s: the learned log-std is an actor term (a critic / value head got one)", who);
+    if (std->d_log_std == nullptr || std->d_out == nullptr) return set_error(TG_ERR_ARG, "%s: d_log_std / d_out is null", who);
+    if (act_dim < 1 || act_dim > 4) return set_error(TG_ERR_ARG, "%s: a learned log-std needs 1..4 action dimensions, got %d", who, act_dim);
+    return 1;
+}
 struct LdsOptIn { size_t bytes[kMaxDevices] = {}; };
 static inline int reserve_dynamic_lds(const void* kernel, size_t bytes, LdsOptIn& cache, const char* what) {
     if (bytes > 160 * 1024) return set_error(TG_ERR_ARG, "%s: %zu B of LDS needed (> 160 KiB)", what, bytes);

@@ -242,12 +242,15 @@ def gaussian_logp(mean: torch.Tensor, act: torch.Tensor, var, out: torch.Tensor 
 
 
 def surrogate_loss(mean, value, act, logp_old, adv, ret, mask, norm, var, epsilon, surr_coef, critic_coef, kl_coef,
-                   want_total: bool = True, coef: torch.Tensor = None, logp_ref: torch.Tensor = None, ref_coef: float = 0.0):
+                   want_total: bool = True, coef: torch.Tensor = None, logp_ref: torch.Tensor = None, ref_coef: float = 0.0,
+                   log_std: torch.Tensor = None, std_out: torch.Tensor = None):
     """One launch of tg_surrogate_loss: returns (total f32 scalar, sums f64[4], d total/d mean, d total/d value|None).
     want_total=False skips the handful of scalar launches that combine the sums (the learners only use the sums).
     coef: device f32 [3] {surr_coef, critic_coef, kl_coef} used instead of the three host numbers (PPO: tg_ppo_norm's output [4:7]).
     logp_ref f32 [M] with ref_coef != 0 (tg_surrogate_loss_ref): GRPO's KL penalty to a frozen reference policy, x = logp_ref - logp,
-    D = exp(x) - x - 1 in sums[2] (kl_coef must be 0; no value head), total -= ref_coef * sum D."""
+    D = exp(x) - x - 1 in sums[2] (kl_coef must be 0; no value head), total -= ref_coef * sum D.
+    log_std (device f32 [A], A <= 4) with std_out (f32 [M][4]) (tg_surrogate_loss_std): the head reads the policy's learned log-std on
+    the device (`var` is ignored) and writes each row's contribution to d total / d log_std into std_out (log_std_grad() sums it)."""
     N.require_cuda(mean, act, logp_old, adv, coef)
     assert mean.dtype == torch.float32 and mean.dim() == 2 and mean.stride(1) == 1
     M, A = mean.shape
@@ -265,17 +268,32 @@ def surrogate_loss(mean, value, act, logp_old, adv, ret, mask, norm, var, epsilo
     if coef is not None:
         assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() >= 3 and not want_total
         a.d_coef = coef.data_ptr()
-    va, k = _var_array(var)
-    assert k == A
-    for i in range(A):
-        a.var[i] = va[i]
+    if log_std is None:
+        va, k = _var_array(var)
+        assert k == A
+        for i in range(A):
+            a.var[i] = va[i]
     a.act_dim, a.epsilon = A, float(epsilon)
     a.surr_coef, a.critic_coef, a.kl_coef = float(surr_coef), float(critic_coef), float(kl_coef)
     grad_mean = torch.empty(M, A, dtype=torch.float32, device=mean.device)
     sums = torch.empty(4, dtype=torch.float64, device=mean.device)
     work = torch.empty(4 * N.load().tg_loss_work_blocks(), dtype=torch.float64, device=mean.device)
     a.d_grad_mean, a.d_sums, a.d_work, a.M = grad_mean.data_ptr(), sums.data_ptr(), work.data_ptr(), M
-    if logp_ref is not None and float(ref_coef) != 0.0:
+    use_ref = logp_ref is not None and float(ref_coef) != 0.0
+    if log_std is not None:
+        sd = learned_std(log_std, std_out, M, A)
+        r = None
+        if use_ref:
+            N.require_cuda(logp_ref)
+            assert logp_ref.dtype == torch.float32 and logp_ref.is_contiguous() and logp_ref.numel() == M
+            r = N.RefPenalty()
+            r.d_logp_ref, r.coef = logp_ref.data_ptr(), float(ref_coef)
+        N.check(N.load().tg_surrogate_loss_std(C.byref(a), C.byref(r) if r is not None else None, C.byref(sd), _st(mean)),
+                "tg_surrogate_loss_std")
+        total = ((surr_coef * sums[0] + critic_coef * sums[1] + (-float(ref_coef) if use_ref else kl_coef) * sums[2]).float()
+                 if want_total else None)
+        return total, sums, grad_mean, grad_value
+    if use_ref:
         N.require_cuda(logp_ref)
         assert logp_ref.dtype == torch.float32 and logp_ref.is_contiguous() and logp_ref.numel() == M
         r = N.RefPenalty()
@@ -286,6 +304,31 @@ def surrogate_loss(mean, value, act, logp_old, adv, ret, mask, norm, var, epsilo
     N.check(N.load().tg_surrogate_loss(C.byref(a), _st(mean)), "tg_surrogate_loss")
     total = (surr_coef * sums[0] + critic_coef * sums[1] + kl_coef * sums[2]).float() if want_total else None
     return total, sums, grad_mean, grad_value
+
+
+def learned_std(log_std: torch.Tensor, out: torch.Tensor, rows: int, act_dim: int) -> "N.LearnedStd":
+    """N.LearnedStd for the `_std` entry points: log_std device f32 [act_dim <= 4], out device f32 [rows][4]."""
+    N.require_cuda(log_std, out)
+    assert log_std.dtype == torch.float32 and log_std.is_contiguous() and log_std.numel() == act_dim <= 4
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (rows, 4) and out.data_ptr() % 16 == 0
+    sd = N.LearnedStd()
+    sd.d_log_std, sd.d_out = log_std.data_ptr(), out.data_ptr()
+    return sd
+
+
+def log_std_grad(rows4: torch.Tensor, act_dim: int, grad: torch.Tensor, add: float = 0.0, work: torch.Tensor = None) -> torch.Tensor:
+    """tg_log_std_grad: grad[k] += sum over rows of rows4[:, k] (f64, fixed order) + add, k < act_dim.  rows4 f32 [rows][4] (the
+    heads' side output), grad f32 [act_dim] (log_std's window of the gradient bucket)."""
+    N.require_cuda(rows4, grad)
+    assert rows4.dtype == torch.float32 and rows4.is_contiguous() and rows4.dim() == 2 and rows4.shape[1] == 4
+    assert grad.dtype == torch.float32 and grad.is_contiguous() and grad.numel() == act_dim
+    lib = N.load()
+    if work is None:
+        work = torch.empty(4 * lib.tg_log_std_grad_blocks(), dtype=torch.float64, device=rows4.device)
+    assert work.dtype == torch.float64 and work.numel() >= 4 * lib.tg_log_std_grad_blocks()
+    N.check(lib.tg_log_std_grad(rows4.data_ptr(), rows4.shape[0], act_dim, float(add), grad.data_ptr(), work.data_ptr(), _st(rows4)),
+            "tg_log_std_grad")
+    return grad
 
 
 class SurrogateLoss(torch.autograd.Function):

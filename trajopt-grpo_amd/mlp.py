@@ -478,7 +478,7 @@ class GemmMLP:
     @torch.no_grad()
     def forward_loss(self, xp: torch.Tensor, kind: int, *, act=None, logp_old=None, adv=None, ret=None, norm=None, var=None,
                      epsilon=0.0, surr_coef=0.0, critic_coef=0.0, kl_coef=0.0, sums_out=None, logp_old_out=None, norm8=None,
-                     logp_ref=None, ref_coef=0.0) -> torch.Tensor:
+                     logp_ref=None, ref_coef=0.0, log_std=None, std_out=None) -> torch.Tensor:
         """Training forward pass with the loss head inside it (kind 0: actor, clipped surrogate; kind 1: critic, squared error).
         Stores what backward_fused() needs, adds the head's weight / bias gradient into their windows and returns the f64 sums
         [surrogate, squared error, KL, count] of these rows -- or, given `sums_out` (f64 [4] on the device), ADDS them there and
@@ -488,12 +488,21 @@ class GemmMLP:
         `norm` and the `*_coef` arguments are then ignored.
         logp_ref (f32 [rows], kind 0) with ref_coef != 0: GRPO's KL penalty to a frozen reference policy in the head (the `_ref` entry
         points): D = exp(x) - x - 1, x = logp_ref - logp, joins the KL sum (slot 2; kl_coef must be 0) and d loss / d logp gains
-        ref_coef (exp(x) - 1).  Otherwise the plain entry points run."""
+        ref_coef (exp(x) - 1).  Otherwise the plain entry points run.
+        log_std (device f32 [A], kind 0) with std_out (f32 [rows][4]): the policy's learned log-std (the `_std` entry points): the head
+        reads it on the device (`var` is ignored) and writes each row's contribution to d loss / d log_std into std_out
+        (hip_ops.log_std_grad sums it into the gradient window)."""
         lib = N.load()
         ref = _ref_penalty(kind, xp.shape[0], logp_ref, ref_coef, kl_coef)
+        std = None
+        if log_std is not None:
+            if kind != 0:
+                raise ValueError("the learned log-std is a term of the actor's loss (kind 0)")
+            from .hip_ops import learned_std
+            std = learned_std(log_std, std_out, xp.shape[0], self.out_dim)
         if self._f32 is not None:
             return self._forward_loss_f32(xp, kind, act, logp_old, adv, ret, norm, var, epsilon, surr_coef, critic_coef, kl_coef, sums_out,
-                                          logp_old_out, norm8, ref)
+                                          logp_old_out, norm8, ref, std)
         assert self.act == "ReLU"
         self._flush_riders()                 # (a forward_loss() that was never followed by backward_fused(): its head gradient is due)
         self._fresh("chain")
@@ -518,7 +527,11 @@ class GemmMLP:
         if self.fwd_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        if ref is None:
+        if std is not None:
+            N.check(lib.tg_mlp_forward_chain_loss_std(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1,
+                                                      rows, ptrs, mptrs, N.C.byref(a), N.C.byref(ref) if ref is not None else None,
+                                                      N.C.byref(std), N.stream_ptr(dev)), "tg_mlp_forward_chain_loss_std")
+        elif ref is None:
             N.check(lib.tg_mlp_forward_chain_loss(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1,
                                                   rows, ptrs, mptrs, N.C.byref(a), N.stream_ptr(dev)), "tg_mlp_forward_chain_loss")
         else:
@@ -528,9 +541,10 @@ class GemmMLP:
         if ev is not None:
             ev[1].record()
             stored = sum(1 for t in hid if t is not None)
-            per_row = 2 * self.in_pad + stored * 2 * H + (L - 1) * (H // 8) + 16 + (4 * self.out_dim + 8 if kind == 0 else 4) + (4 if ref else 0)
-            self.fwd_events.append((ev[0], ev[1], rows, per_row,
-                                    f"tg::mlp_fwd_chain_kernel<{H},8,true,4,false,true{',true' if ref else ''}>"))
+            per_row = (2 * self.in_pad + stored * 2 * H + (L - 1) * (H // 8) + 16 + (4 * self.out_dim + 8 if kind == 0 else 4) + (4 if ref else 0)
+                       + (16 if std else 0))
+            tail = (",true,true" if ref else ",false,true") if std else (",true" if ref else "")
+            self.fwd_events.append((ev[0], ev[1], rows, per_row, f"tg::mlp_fwd_chain_kernel<{H},8,true,4,false,true{tail}>"))
         grid = min(nblk, -(-rows // 256))
         lin = self.linears[-1]
         # the head's partial weight / bias gradients (rows >= 4 of a slab are never written) and -- with sums_out -- the loss sums are
@@ -578,9 +592,10 @@ class GemmMLP:
                 assert logp_old.dtype == torch.float32 and logp_old.is_contiguous()
                 a.d_logp_old = logp_old.data_ptr()
             a.d_adv = adv.data_ptr()
-            va = [float(v) for v in (var.tolist() if isinstance(var, torch.Tensor) else var)]
-            for i in range(self.out_dim):
-                a.var[i] = va[i]
+            if var is not None:                          # (None: a learned log-std, read by the head on the device)
+                va = [float(v) for v in (var.tolist() if isinstance(var, torch.Tensor) else var)]
+                for i in range(self.out_dim):
+                    a.var[i] = va[i]
         else:
             N.require_cuda(ret)
             assert ret.dtype == torch.float32 and ret.is_contiguous() and self.out_dim == 1
@@ -595,7 +610,7 @@ class GemmMLP:
         return self.can_fuse_head()
 
     def _forward_loss_f32(self, xp, kind, act, logp_old, adv, ret, norm, var, epsilon, surr_coef, critic_coef, kl_coef, sums_out=None,
-                          logp_old_out=None, norm8=None, ref=None):
+                          logp_old_out=None, norm8=None, ref=None, std=None):
         """forward_loss() of an fp32 net: forward + loss head + backward-data pass in ONE launch (tg_mlp_f32_forward_backward);
         every hidden layer's activation and dZ is written for backward_fused() (tg_mlp_f32_weight_grad)."""
         lib = N.load()
@@ -622,7 +637,23 @@ class GemmMLP:
         if self.fwd_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        if f.act != 0:                      # Tanh: the `_act` entry (plain head or reference penalty); everything stored, no mask bits
+        if std is not None:                 # the policy's learned log-std: the `_std` entries (a nullable reference penalty beside it)
+            rp = N.C.byref(ref) if ref is not None else None
+            if f.act != 0:
+                assert tmask is None and all(t is not None for t in acts + dzs)
+            if f.res:
+                N.check(lib.tg_mlp_f32r_forward_backward_std(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.w0.data_ptr(), f.table.data_ptr(), H,
+                                                             nh, rows, ptrs, zptrs, N.ptr(tmask), N.C.byref(a), rp, N.C.byref(std),
+                                                             N.stream_ptr(dev)), "tg_mlp_f32r_forward_backward_std")
+            elif f.wide:
+                N.check(lib.tg_mlp_f32w_forward_backward_std(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.table.data_ptr(), nh, rows, ptrs,
+                                                             zptrs, N.C.byref(a), rp, N.C.byref(std), N.stream_ptr(dev)),
+                        "tg_mlp_f32w_forward_backward_std")
+            else:
+                N.check(lib.tg_mlp_f32_forward_backward_act_std(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), H, nh, rows, ptrs, zptrs,
+                                                                N.ptr(tmask), N.C.byref(a), rp, N.C.byref(std), f.act, N.stream_ptr(dev)),
+                        "tg_mlp_f32_forward_backward_act_std")
+        elif f.act != 0:                    # Tanh: the `_act` entry (plain head or reference penalty); everything stored, no mask bits
             assert tmask is None and all(t is not None for t in acts + dzs)
             N.check(lib.tg_mlp_f32_forward_backward_act(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), H, nh, rows, ptrs, zptrs, None,
                                                         N.C.byref(a), N.C.byref(ref) if ref is not None else None, f.act,

@@ -242,9 +242,12 @@ class DeviceRollout:
             with torch.cuda.device(self.device):
                 self._enqueue_prepare(initial_states)
                 self._enqueue_fused(0, self.T)
-        elif self.use_graph and sample and initial_states is None and self._rand_spec is None:
+        elif (self.use_graph and sample and initial_states is None and self._rand_spec is None
+              and getattr(self.policy, "log_std", None) is None):
             # (a randomised rollout does not take the graph: its parameter draw depends on the host stream id, like the reset, and
-            #  the captured launches would be the plain entry points)
+            #  the captured launches would be the plain entry points.  Nor does a learned-std policy: sigma is baked into the
+            #  captured kernel arguments and moves with every learn(), so every rollout would pay a new capture -- it takes the
+            #  plain per-step launches below instead)
             self._run_graph()
         else:
             with torch.cuda.device(self.device):
