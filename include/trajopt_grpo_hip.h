@@ -780,6 +780,41 @@ int  tg_learn_count(const uint8_t* d_mask, int64_t entries, int64_t expected_row
                     void* stream);
 int  tg_learn_compact(const tg_compact_args* args, void* stream);
 
+/* ---- Running observation normalisation (policies: normalize_obs=True) ----
+ * The policy owns {count f64 [1], mean f64 [S], m2 f64 [S] = sum of squared deviations} and a derived f32 table [2][S] =
+ * {(float)mean, (float)(1 / sqrt(m2 / count + eps))} (count == 0: {0, 1}).  The normalised observation, wherever a policy reads a
+ * state, is ONE fp32 expression: xn[k] = clamp((x[k] - table[0][k]) * table[1][k], -clip, +clip) -- subtract, multiply and clamp
+ * each rounded on its own, an f64 observation rounded to f32 first, bf16 paths round xn once.  clip = +inf: no clamp.
+ * tg_obs_moments: over the valid (t, e) of a trajectory (f32 or f64 planes), per feature s, d_out f64 [S][3] = {count,
+ *   sum (x - c[s]), sum (x - c[s])^2} in f64, c = d_center f64 [S] (the running mean: identical on every rank, so the ranks' outputs
+ *   add).  Two launches, a fixed summation order: deterministic for a given trajectory shape.  d_work: the workspace-size query's
+ *   bytes for (T * n, S).
+ * tg_obs_norm_merge: Chan's merge of d_batch f64 [S][3] (tg_obs_moments' output, all-reduced) into d_count / d_mean / d_m2 and the
+ *   table rewritten IN PLACE (same allocation: captured graphs and cached arguments stay valid), one small launch, IEEE f64 sqrt
+ *   and divide.  d_batch == NULL: only the table is rewritten from the statistics as they stand.
+ * tg_obs_normalize_rows: rows x[r][k] at d_x + r * row_stride + k * feat_stride elements (TG_F32 / TG_F64; an SoA slot has
+ *   row_stride 1, row-major rows feat_stride 1) -> d_xin[r][0..in_pad): xn in bf16 (xin_bf16) or f32, zero padding, 1 in column
+ *   `ones_col` (or -1): tg_learn_compact's row contract.
+ * tg_learn_compact_on: tg_learn_compact whose input rows hold xn instead of x; everything else is tg_learn_compact's.
+ * tg_fused_rollout_on / tg_fused_rollout_f32_on: the fused rollouts with the three operations applied where the register-resident
+ *   state becomes the first layer's operand (separate kernel instantiations; the trajectory records the RAW observation).  d_ptab:
+ *   the per-env parameter table of the `_dr` entry points, or NULL; `activation` as in the `_act` entry points. */
+int64_t tg_obs_moments_workspace(int64_t entries, int32_t S);
+int  tg_obs_moments(const tg_traj* tr, int32_t S, const double* d_center, void* d_work, int64_t work_bytes, double* d_out, void* stream);
+int  tg_obs_norm_merge(const double* d_batch, int32_t S, double eps, double* d_count, double* d_mean, double* d_m2, float* d_table,
+                       void* stream);
+int  tg_obs_normalize_rows(const void* d_x, int32_t x_dtype, int64_t row_stride, int64_t feat_stride, int64_t rows, int32_t S,
+                           const float* d_obs_norm, float clip, void* d_xin, int32_t in_pad, int32_t xin_bf16, int32_t ones_col,
+                           void* stream);
+int  tg_learn_compact_on(const tg_compact_args* args, const float* d_obs_norm, float clip, void* stream);
+int  tg_fused_rollout_on(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+                         int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                         int32_t t_begin, int32_t t_end, const float* d_obs_norm, float clip, void* stream);
+int  tg_fused_rollout_f32_on(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                             int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                             int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, const float* d_obs_norm, float clip,
+                             void* stream);
+
 /* ---- PPO's prologue (algorithms/ppo.py:93-139) without a host round trip ----
  * tg_scatter_rows: d_dst[d_idx[r]] = d_src[r * src_stride] for r < rows -- the critic's values of the valid rows (the no-grad
  *   forward's padded output, column 0) back onto the zeroed [T][n] grid (ppo.py:93 evaluated on the valid rows only).

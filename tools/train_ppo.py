@@ -43,6 +43,8 @@ def main():
     ranges, sys.argv[1:] = pop_randomize(sys.argv[1:])
     learn_std = "--learn-std" in sys.argv                         # a learned per-dimension log-std instead of the fixed covariance
     sys.argv = [a for a in sys.argv if a != "--learn-std"]
+    normalize_obs = "--normalize-obs" in sys.argv                 # running observation normalisation (policy.obs_norm)
+    sys.argv = [a for a in sys.argv if a != "--normalize-obs"]
     epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 120
     name = sys.argv[2] if len(sys.argv) > 2 else "CartPole"
     dev = torch.device("cuda", 0)
@@ -56,7 +58,8 @@ def main():
         hidden, cov, lr, upd, gamma, cdt = (128, 128, 128), 0.5, 2e-4, 24, 0.99, None
         if len(sys.argv) > 3 and sys.argv[3] == "bf16":          # bf16 policy compute: fused bf16 rollout + chain kernels at H = 128
             cdt = torch.bfloat16
-    pol = tg.GaussianActorCritic_NeuralNetwork(S, A, hidden, cov=cov, device=dev, **({"learn_std": True} if learn_std else {}))
+    pol = tg.GaussianActorCritic_NeuralNetwork(S, A, hidden, cov=cov, device=dev, **({"learn_std": True} if learn_std else {}),
+                                               **({"normalize_obs": True} if normalize_obs else {}))
     tg.environments.ENV_CLASSES[name]().randomize(ranges)         # (refuses a bad name or range before anything is allocated)
     mgr = tg.RolloutManager(lambda: tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, num_workers=64, num_episodes_per_worker=64,
                             seed=0, compute_dtype=cdt)
@@ -71,7 +74,8 @@ def main():
         if ep % 10 == 0 or ep == epochs - 1:
             print(f"epoch {ep:4d}  avg return {float(buf.avg_reward[-1]):9.2f}  mean len {float(buf.device_traj.len.float().mean()):6.1f}  "
                   f"elapsed {time.time() - t0:6.1f}s"
-                  + (f"  log_std {[round(v, 4) for v in algo.last_stats['log_std']]}" if learn_std else ""), flush=True)
+                  + (f"  log_std {[round(v, 4) for v in algo.last_stats['log_std']]}" if learn_std else "")
+                  + (f"  obs_count {algo.last_stats['obs_count']:.0f}" if normalize_obs else ""), flush=True)
     print("first -> last:", float(buf.avg_reward[0]), "->", float(buf.avg_reward[-1]), " max", float(max(buf.avg_reward)))
 
 

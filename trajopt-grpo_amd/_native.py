@@ -246,6 +246,14 @@ SIGNATURES = {
     "tg_learn_count_workspace": (C.c_int64, [_I64]),
     "tg_learn_count": (C.c_int, [_VP, _I64, _I64, _VP, _I64, _VP, _VP]),
     "tg_learn_compact": (C.c_int, [C.POINTER(CompactArgs), _VP]),
+    "tg_obs_moments_workspace": (C.c_int64, [_I64, _I32]),
+    "tg_obs_moments": (C.c_int, [_P(Traj), _I32, _VP, _VP, _I64, _VP, _VP]),
+    "tg_obs_norm_merge": (C.c_int, [_VP, _I32, C.c_double, _VP, _VP, _VP, _VP, _VP]),
+    "tg_obs_normalize_rows": (C.c_int, [_VP, _I32, _I64, _I64, _I64, _I32, _VP, _F, _VP, _I32, _I32, _I32, _VP]),
+    "tg_learn_compact_on": (C.c_int, [C.POINTER(CompactArgs), _VP, _F, _VP]),
+    "tg_fused_rollout_on": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _VP, _F, _VP]),
+    "tg_fused_rollout_f32_on": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _I32, _VP,
+                                          _F, _VP]),
     "tg_scatter_rows": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP]),
     "tg_ppo_returns": (C.c_int, [_VP, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _I64, _I32, _VP, _VP, _VP]),
     "tg_ppo_returns_boot": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _I64, _I32, _VP, _VP, _VP]),

@@ -135,10 +135,26 @@ class _GpuLearner(Algorithm):
             self._check_deferred()
             self._clip_blocks, self._clip_steps = [], 0
             self._std_blocks, self._std_steps = [], 0
+            obs_count = self._obs_norm_update(buffer)
             self._learn(buffer)
+            if obs_count is not None and self._stats_pending is not None:
+                inner0 = self._stats_pending
+                self._stats_pending = lambda: {**inner0(), "obs_count": float(obs_count.item())}
             if self._clip_steps and self._stats_pending is not None:
                 inner, blocks, steps = self._stats_pending, self._clip_blocks, self._clip_steps
                 self._stats_pending = lambda: {**inner(), "grad_norm": torch.cat(blocks)[:steps, 0].tolist()}
+
+    def _obs_norm_update(self, buffer):
+        """normalize_obs: the policy's running statistics take in this rollout's valid observations (one all-reduce across the ranks)
+        and the table is rewritten -- BEFORE any row of this learn() is prepared, so that old log-probabilities, the old-policy pass,
+        every update and the bootstrap rows read the one table.  A frozen normaliser keeps its bits.  Returns a device copy of the
+        count (for last_stats), or None when the policy reads raw observations."""
+        on = getattr(self.policy, "obs_norm", None)
+        if on is None:
+            return None
+        if not on.frozen:
+            on.update(device_trajectory(buffer, self.policy.device), self.process_group)
+        return on.count.clone()
 
     def _entry_refresh(self, *nets):
         """The derived weight layouts of `nets` at the entry of learn(): rebuilt whatever the version keys say -- a weight written
@@ -224,7 +240,7 @@ class _GpuLearner(Algorithm):
                 out += leaves(v) if isinstance(v, dict) else [v]
             return out
 
-        src, dst = leaves(self.policy.state_dict()), leaves(self.old_policy.state_dict())
+        src, dst = leaves(self._weights_state(self.policy)), leaves(self._weights_state(self.old_policy))
         if len(src) == len(dst) and all(torch.is_tensor(a) and torch.is_tensor(b) and a.shape == b.shape and a.dtype == b.dtype
                                         and a.device == b.device for a, b in zip(src, dst)):
             # ... and with them the weight streams already built from these weights (the launch after the last optimizer step):
@@ -249,8 +265,27 @@ class _GpuLearner(Algorithm):
             for mo, what in marks:
                 mo.mark_built(what)                                         # (keyed on the old net's weights AFTER the copy)
         else:
-            self.old_policy.load_state_dict(self.policy.state_dict())
+            self._load_old(self._weights_state(self.policy))
         self._old_synced = self._actor_keys()                               # old_policy.actor == policy.actor as long as both keys stand
+
+    @staticmethod
+    def _weights_state(pol) -> dict:
+        """pol.state_dict() without the observation statistics: old_policy SHARES the policy's obs_norm object, there is nothing to copy."""
+        return {k: v for k, v in pol.state_dict().items() if k not in P.OBS_NORM_KEYS}
+
+    def _load_old(self, weights) -> None:
+        """old_policy.load_state_dict(weights) past its check that statistics come with a normalised policy (they are shared)."""
+        on, self.old_policy.obs_norm = self.old_policy.obs_norm, None
+        try:
+            self.old_policy.load_state_dict(weights)
+        finally:
+            self.old_policy.obs_norm = on
+
+    def _make_old_policy(self):
+        """A deep copy of the policy (grpo.py:48, ppo.py:62) that reads states through the policy's own obs_norm object."""
+        old = copy.deepcopy(self.policy)
+        old.obs_norm = getattr(self.policy, "obs_norm", None)
+        return old
 
     def _actor_keys(self):
         """(key of policy.actor's parameters, key of old_policy.actor's): storage, torch version counters, raw-write count."""
@@ -268,7 +303,7 @@ class _GpuLearner(Algorithm):
         """old_policy <- policy.  The constructors deep-copy the policy BEFORE a checkpoint is loaded into it
         (pipelines/pipeline.py:93-100 loads after construction), so a resume must re-synchronise the copy -- GRPO's
         first learn() would otherwise form its ratios against the random-init weights."""
-        self.old_policy.load_state_dict(self.policy.state_dict())
+        self._load_old(self._weights_state(self.policy))
         self._old_synced = self._actor_keys()
 
     @property
@@ -402,9 +437,10 @@ class _GpuLearner(Algorithm):
 
     def _prep(self, net, X, cap_rows=0):
         m = self._mlp(net)
+        on = getattr(self.policy, "obs_norm", None)
         if m is None:
-            return X
-        return m.prepare_input(X, out=self._ws.get("xin", X.shape[0], m.in_pad, m.cd, X.device, cap_rows))
+            return X if on is None else on.normalize(X)
+        return m.prepare_input(X, out=self._ws.get("xin", X.shape[0], m.in_pad, m.cd, X.device, cap_rows), obs_norm=on)
 
     def _forward(self, net, x, train=False, view=False):
         """fp32 output [rows][out].  train=True keeps what backward needs (activations or the autograd graph).
@@ -487,7 +523,8 @@ class _GpuLearner(Algorithm):
         d0_c = self._ws.get("row0", cap, 1, torch.float32, dev, cap).view(-1) if src0 is not None else None
         d1_c = self._ws.get("row1", cap, 1, torch.float32, dev, cap).view(-1) if src1 is not None else None
         ones = 31 if (m.in_pad == 32 and m.in_dim < 32 and m._f32 is None) else -1
-        K.learn_compact(traj, work, cap, xin_c, ones, act_c, idx_c, src0, d0_c, src1, d1_c, moments, norm_mode, group_size)
+        K.learn_compact(traj, work, cap, xin_c, ones, act_c, idx_c, src0, d0_c, src1, d1_c, moments, norm_mode, group_size,
+                        obs_norm=getattr(self.policy, "obs_norm", None))
         return traj, total, idx_c, xin_c, act_c, d0_c, d1_c, ones
 
     def _prepare_finish(self, handle):
@@ -577,6 +614,12 @@ def _check_ref_model(ref_model, policy):
     d_ref, d_pol = next(ref_model.actor.parameters()).device, next(policy.actor.parameters()).device
     if d_ref != d_pol:
         raise ValueError(f"ref_model is on {d_ref}, the policy on {d_pol}: the reference pass runs on the policy's device")
+    if (getattr(ref_model, "obs_norm", None) is None) != (getattr(policy, "obs_norm", None) is None):
+        raise ValueError("ref_model and the policy must agree on normalize_obs: one of them reads normalised observations, the other raw "
+                         "ones (the reference policy reads states through its OWN statistics, frozen)")
+    if getattr(policy, "obs_norm", None) is not None and ref_model.obs_norm is policy.obs_norm:
+        raise ValueError("ref_model shares the policy's obs_norm object: every learn() would update the reference policy's statistics.  "
+                         "Give it its own (copy.deepcopy(policy) does)")
     return ref_model
 
 
@@ -605,13 +648,21 @@ class GRPO(_GpuLearner):
         self.updates_per_iter = updates_per_iter
         self.maximize = maximize
         self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm)
-        self.old_policy = copy.deepcopy(self.policy)                        # grpo.py:48
+        self.old_policy = self._make_old_policy()                           # grpo.py:48
         self._old_synced = self._actor_keys()
 
-    def _ref_input(self, ref_actor, xin, in_dim, cap):
+    def _ref_input(self, ref_actor, xin, in_dim, cap, traj=None, idx=None):
         """The reference actor's input rows: the policy's prepared `xin` itself when the reference net takes the same padded layout,
-        else re-prepared from its first `in_dim` columns (a reference net of another shape / path)."""
+        else re-prepared from its first `in_dim` columns (a reference net of another shape / path).  A reference policy with a
+        normaliser never shares `xin` (those rows went through the POLICY's table): its rows are the valid rows' raw observations
+        through its own statistics."""
         m = self._mlp(ref_actor)
+        ref_on = getattr(self.ref_model, "obs_norm", None)
+        if ref_on is not None:
+            X = traj.obs_rows().index_select(0, idx)
+            if m is None:
+                return ref_on.normalize(X)
+            return m.prepare_input(X, out=self._ws.get("xin_ref", X.shape[0], m.in_pad, m.cd, X.device, cap), obs_norm=ref_on)
         if m is not None and m.in_pad == xin.shape[1] and m.cd == xin.dtype:
             return xin                                  # (a ones column at 31 meets zero weights in the forward pass)
         X = xin[:, :in_dim].float()
@@ -670,7 +721,7 @@ class GRPO(_GpuLearner):
         ref_logp = None
         if ref_actor is not None:                                           # once per learn(): the reference policy is frozen
             in_dim = next(m for m in ref_actor.network if isinstance(m, torch.nn.Linear)).in_features
-            ref_logp = self._logp_nograd(ref_actor, self._ref_input(ref_actor, xin, in_dim, traj.T * traj.n), act, self.ref_model.var,
+            ref_logp = self._logp_nograd(ref_actor, self._ref_input(ref_actor, xin, in_dim, traj.T * traj.n, traj, idx), act, self.ref_model.var,
                                          out=self._ws.get("ref_logp", X.shape[0], 1, torch.float32, X.device, traj.T * traj.n).view(-1))
         for u in range(self.updates_per_iter):
             if u > 0:
@@ -761,7 +812,7 @@ class PPO(_GpuLearner):
         self.gamma, self.lam, self.entropy = gamma, lam, entropy
         self.batch_size, self.kl_coeff, self.monte_carlo = batch_size, kl_coeff, monte_carlo
         self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm)
-        self.old_policy = copy.deepcopy(self.policy)                        # ppo.py:62 (never read in learn)
+        self.old_policy = self._make_old_policy()                           # ppo.py:62 (never read in learn)
         self._seed = seed
         self._gen = None
         # minibatch mode: callable (n_rows, device) -> int64 permutation of this rank's valid rows (time-major order);
@@ -853,11 +904,12 @@ class PPO(_GpuLearner):
         s_final, timeout = K.rollout_final_state(params, traj, self._small("boot_state", n * traj.S, torch.float32, dev).view(n, traj.S),
                                                  self._small("boot_timeout", n, torch.uint8, dev),
                                                  env_params=env_params)
+        on = getattr(self.policy, "obs_norm", None)        # (this learn()'s table: the update ran at the entry)
         if m_c is not None:
-            xin = m_c.prepare_input(s_final, out=self._small("boot_xin", n * m_c.in_pad, m_c.cd, dev).view(n, m_c.in_pad))
+            xin = m_c.prepare_input(s_final, out=self._small("boot_xin", n * m_c.in_pad, m_c.cd, dev).view(n, m_c.in_pad), obs_norm=on)
             v = m_c.forward(xin, keep=False, padded=True)[:, 0]
         else:
-            v = self._forward(critic, s_final).reshape(-1)
+            v = self._forward(critic, s_final if on is None else on.normalize(s_final)).reshape(-1)
         return torch.mul(v, timeout, out=self._small("boot_value", n, torch.float32, dev)), timeout
 
     def _learn(self, buffer) -> None:

@@ -74,11 +74,47 @@ template <typename Env> struct PerEnv : Env {
 };
 template <typename Env> struct EnvTraits {
     static constexpr bool kPerEnv = false;
+    static constexpr bool kObsNorm = false;
     using Consts = typename Env::C;
 };
 template <typename Env> struct EnvTraits<PerEnv<Env>> {
     static constexpr bool kPerEnv = true;
+    static constexpr bool kObsNorm = false;
     using Consts = typename Env::C;
+};
+// Running observation normalisation (the `_on` entry points of the fused rollouts).  ObsNormed<Env> -- Env a plain env or PerEnv<...>
+// -- rides on the Env type for PerEnv's reason: the kernel's argument becomes {Env's own argument, the f32 table [2][S] = {mean,
+// rstd}, the clamp}, its instantiation IS the kObsNorm = true kernel, and every existing instantiation keeps name and code.
+struct ObsNormTable {
+    const float* tab;
+    float clip;                                  // +inf: no clamp
+};
+template <typename BaseC> struct ObsNormArg {
+    BaseC base;
+    ObsNormTable on;
+};
+template <typename Env> struct ObsNormed : Env {
+    using C = ObsNormArg<typename Env::C>;
+};
+template <typename Env> struct EnvTraits<ObsNormed<Env>> {
+    static constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
+    static constexpr bool kObsNorm = true;
+    using Consts = typename EnvTraits<Env>::Consts;
+};
+// the env's own kernel argument (by-value constants or the parameter table) inside whatever the kernel was handed
+template <typename C> __device__ static inline const C& env_arg(const C& c) { return c; }
+template <typename B> __device__ static inline const B& env_arg(const ObsNormArg<B>& c) { return c.base; }
+// The policy's view of a state: the table's 2 S floats, read once per launch (uniform addresses: scalar loads), and the one
+// definition of the normalised observation (obs_normalize, tg_common.hpp) applied to the register-resident state where it becomes
+// the first layer's operand.  The table is per FEATURE, not per env: a compaction that moves envs between lanes moves nothing here.
+template <int S> struct ObsNormRegs {
+    float mean[S], rstd[S], clip;
+    __device__ inline void load(const ObsNormTable& t) {
+#pragma unroll
+        for (int k = 0; k < S; ++k) { mean[k] = t.tab[k]; rstd[k] = t.tab[S + k]; }
+        clip = t.clip;
+    }
+    __device__ inline float apply(float x, int k) const { return obs_normalize(x, mean[k], rstd[k], clip); }
 };
 // the constants of env slot i, built by the lane that owns it from column i of the table
 template <typename Env>

@@ -92,9 +92,15 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
     int64_t ic = (i < n) ? i : n - 1;
     const int64_t T1 = (int64_t)T + 1;
     constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
+    constexpr bool kObsNorm = EnvTraits<Env>::kObsNorm;
+    const auto& e_arg = env_arg(c_arg);
     typename EnvTraits<Env>::Consts own_c;
-    if constexpr (kPerEnv) own_c = env_constants<Env>(c_arg, n, ic);
-    const auto& c = pick_constants(c_arg, own_c);
+    if constexpr (kPerEnv) own_c = env_constants<Env>(e_arg, n, ic);
+    const auto& c = pick_constants(e_arg, own_c);
+    // kObsNorm: the per-feature table, once per launch.  It belongs to the policy, not to an env: the compaction below moves envs
+    // between lanes and nothing of it follows them.
+    ObsNormRegs<kObsNorm ? S : 1> on;
+    if constexpr (kObsNorm) on.load(c_arg.on);
 
     for (int q = threadIdx.x; q < (n_hh + 2) * H; q += 64 * WPW) bias_s[q] = bias[q];
 
@@ -159,7 +165,7 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
                 alive = true;
                 in_range = (h == 0);
                 ic = i;
-                if constexpr (kPerEnv) own_c = env_constants<Env>(c_arg, n, ic);   // the vehicle follows the env, like the Philox key
+                if constexpr (kPerEnv) own_c = env_constants<Env>(e_arg, n, ic);   // the vehicle follows the env, like the Philox key
             } else {
                 alive = false;
                 in_range = false;                             // an empty slot records nothing
@@ -186,7 +192,9 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
         // ---- layer-1 input: this wave's 64 states as bf16 rows in LDS, read back in B-fragment order ----
 #pragma unroll
         for (int k = 0; k < S; ++k) {
-            const __bf16 b = (__bf16)s[k];
+            __bf16 b;
+            if constexpr (kObsNorm) b = (__bf16)on.apply(s[k], k);      // rounded to bf16 once, as the raw state is
+            else b = (__bf16)s[k];
             my_x[k] = __builtin_bit_cast(unsigned short, b);
         }
         bf16x8 xin[NT][KS], xout[NT][KS];
@@ -337,8 +345,8 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
 }
 
 template <template <typename> class EnvT, int H, int NT, int WPW>
-static int fused_launch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* wfrag, const float* bias, int n_hh,
-                        const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, hipStream_t st) {
+static int fused_launch(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const void* wfrag,
+                        const float* bias, int n_hh, const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, hipStream_t st) {
     using Env = EnvT<float>;
     constexpr int KS = H / 16;
     auto c = Env::C::make(*p);
@@ -348,6 +356,26 @@ static int fused_launch(const tg_env_params* p, const double* d_ptab, const tg_t
     const size_t shmem = (size_t)((NT == 1 && WPW == 4) ? 3 : 4) * KS * 1024 + (size_t)(n_hh + 2) * H * sizeof(float) +
                          (size_t)WPW * 64 * 32 * 2 + 4 * WPW;
     const dim3 grid((unsigned)ceil_div(tr->n, 32 * NT * WPW));
+    if (d_obs_norm != nullptr) {       // tg_fused_rollout_on: the ObsNormed instantiations, with or without the parameter table
+        const ObsNormTable on{d_obs_norm, clip};
+        if (d_ptab != nullptr) {
+            auto kern = fused_rollout_kernel<ObsNormed<PerEnv<Env>>, H, NT, WPW>;
+            static LdsOptIn opt_in_on_dr;
+            if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in_on_dr, "tg_fused_rollout_on")) return rc;
+            hipLaunchKernelGGL(kern, grid, dim3(64 * WPW), shmem, st, ObsNormArg<PerEnvTable>{per_env_table(p, d_ptab), on}, (float*)tr->d_obs,
+                               tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg,
+                               rng, env_offset, p->agents);
+        } else {
+            auto kern = fused_rollout_kernel<ObsNormed<Env>, H, NT, WPW>;
+            static LdsOptIn opt_in_on;
+            if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in_on, "tg_fused_rollout_on")) return rc;
+            hipLaunchKernelGGL(kern, grid, dim3(64 * WPW), shmem, st, ObsNormArg<typename Env::C>{c, on}, (float*)tr->d_obs, tr->d_act,
+                               (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg, rng,
+                               env_offset, p->agents);
+        }
+        TG_LAUNCH_CHECK("tg_fused_rollout_on");
+        return TG_OK;
+    }
     if (d_ptab != nullptr) {           // tg_fused_rollout_dr: the PerEnv instantiation with the parameter table
         auto kern_dr = fused_rollout_kernel<PerEnv<Env>, H, NT, WPW>;
         static LdsOptIn opt_in_dr;
@@ -372,7 +400,7 @@ using namespace tg;
 
 extern "C" {
 
-static int fused_rollout_impl(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+static int fused_rollout_impl(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
                               int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                               int32_t t_begin, int32_t t_end, void* stream) {
     TG_REQUIRE(p && tr && d_wfrag && d_bias && sigma && d_rng, "tg_fused_rollout: null pointer");
@@ -392,8 +420,8 @@ static int fused_rollout_impl(const tg_env_params* p, const double* d_ptab, cons
     // it gives twice as many workgroups).  (NT 2 x 4 waves was measured slower at every size, DESIGN_HISTORY: not instantiated.)
     const int variant = tr->n < 32768 ? 1 : 0;
 #define CALL(E, HH)                                                                                                       \
-    (variant == 0 ? fused_launch<E, HH, 1, 8>(p, d_ptab, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st) \
-                  : fused_launch<E, HH, 1, 4>(p, d_ptab, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st))
+    (variant == 0 ? fused_launch<E, HH, 1, 8>(p, d_ptab, d_obs_norm, clip, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st) \
+                  : fused_launch<E, HH, 1, 4>(p, d_ptab, d_obs_norm, clip, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st))
     switch (p->env_id * 1000 + hidden) {
         case TG_ENV_CARTPOLE * 1000 + 128: return CALL(CartPoleEnv, 128);
         case TG_ENV_CARTPOLE * 1000 + 256: return CALL(CartPoleEnv, 256);
@@ -413,14 +441,23 @@ static int fused_rollout_impl(const tg_env_params* p, const double* d_ptab, cons
 int tg_fused_rollout(const tg_env_params* p, const tg_traj* tr, const void* d_wfrag, const float* d_bias, int32_t hidden,
                      int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t t_begin,
                      int32_t t_end, void* stream) {
-    return fused_rollout_impl(p, nullptr, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
+    return fused_rollout_impl(p, nullptr, nullptr, 0.0f, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
 }
 
 int tg_fused_rollout_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
                         int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                         int32_t t_begin, int32_t t_end, void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_fused_rollout_dr: null parameter table");
-    return fused_rollout_impl(p, d_ptab, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
+    return fused_rollout_impl(p, d_ptab, nullptr, 0.0f, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
+}
+
+int tg_fused_rollout_on(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+                        int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                        int32_t t_begin, int32_t t_end, const float* d_obs_norm, float clip, void* stream) {
+    TG_REQUIRE(d_obs_norm != nullptr, "tg_fused_rollout_on: null observation-normalisation table");
+    TG_REQUIRE(clip > 0.0f, "tg_fused_rollout_on: clip %g (a number > 0; +inf: no clamp)", (double)clip);
+    return fused_rollout_impl(p, d_ptab, d_obs_norm, clip, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end,
+                              stream);
 }
 
 }  // extern "C"

@@ -75,9 +75,13 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
     const int64_t ic = (i < n) ? i : n - 1;
     const int64_t T1 = (int64_t)T + 1;
     constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
+    constexpr bool kObsNorm = EnvTraits<Env>::kObsNorm;
+    const auto& e_arg = env_arg(c_arg);
     typename EnvTraits<Env>::Consts own;                    // kPerEnv: this lane's vehicle, for the whole rollout
-    if constexpr (kPerEnv) own = env_constants<Env>(c_arg, n, ic);
-    const auto& c = pick_constants(c_arg, own);
+    if constexpr (kPerEnv) own = env_constants<Env>(e_arg, n, ic);
+    const auto& c = pick_constants(e_arg, own);
+    ObsNormRegs<kObsNorm ? S : 1> on;                       // kObsNorm: the per-feature table, read once per launch
+    if constexpr (kObsNorm) on.load(c_arg.on);
 
     for (int q = threadIdx.x; q < NTAB; q += 64 * WPW) tab_s[q] = tab[q];
     float w1[R1], wh[NHH > 0 ? NHH : 1][RH];
@@ -107,8 +111,12 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
         for (int q = 0; q < K1 / 8; ++q)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float lo = (8 * q + j < S) ? s[(8 * q + j < S) ? 8 * q + j : 0] : 0.0f;
-                const float hi = (8 * q + 4 + j < S) ? s[(8 * q + 4 + j < S) ? 8 * q + 4 + j : 0] : 0.0f;
+                float lo = (8 * q + j < S) ? s[(8 * q + j < S) ? 8 * q + j : 0] : 0.0f;
+                float hi = (8 * q + 4 + j < S) ? s[(8 * q + 4 + j < S) ? 8 * q + 4 + j : 0] : 0.0f;
+                if constexpr (kObsNorm) {                    // what the policy sees of s (the dynamics keep stepping s itself)
+                    if (8 * q + j < S) lo = on.apply(lo, 8 * q + j);
+                    if (8 * q + 4 + j < S) hi = on.apply(hi, 8 * q + 4 + j);
+                }
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[4 * q + j], h ? hi : lo, acc, 0, 0, 0);
             }
 #pragma unroll
@@ -239,9 +247,13 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
     const int64_t ic = (i < n) ? i : n - 1;
     const int64_t T1 = (int64_t)T + 1;
     constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
+    constexpr bool kObsNorm = EnvTraits<Env>::kObsNorm;
+    const auto& e_arg = env_arg(c_arg);
     typename EnvTraits<Env>::Consts own;                    // kPerEnv: this lane's vehicle, for the whole rollout
-    if constexpr (kPerEnv) own = env_constants<Env>(c_arg, n, ic);
-    const auto& c = pick_constants(c_arg, own);
+    if constexpr (kPerEnv) own = env_constants<Env>(e_arg, n, ic);
+    const auto& c = pick_constants(e_arg, own);
+    ObsNormRegs<kObsNorm ? S : 1> on;                       // kObsNorm: the per-feature table, read once per launch
+    if constexpr (kObsNorm) on.load(c_arg.on);
 
     for (int q = threadIdx.x; q < NTAB; q += 64 * WPW) tab_s[q] = tab[q];
     float w1[2][S1], wh[NHH > 0 ? NHH : 1][2][SH];
@@ -295,6 +307,18 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (4 * r + e < S) x = (g == e) ? s[(4 * r + e < S) ? 4 * r + e : 0] : x;
+            if constexpr (kObsNorm) {
+                // what the policy sees of s: the lane's own feature 4 r + g is selected first (x above, its mean and rstd here), then
+                // normalised once; a padding feature stays 0 ((0 - 0) * 1)
+                float xm = 0.0f, xr = 1.0f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (4 * r + e < S) {
+                        xm = (g == e) ? on.mean[(4 * r + e < S) ? 4 * r + e : 0] : xm;
+                        xr = (g == e) ? on.rstd[(4 * r + e < S) ? 4 * r + e : 0] : xr;
+                    }
+                x = obs_normalize(x, xm, xr, on.clip);
+            }
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[tt][r], x, acc[tt], 0, 0, 0);
         }
@@ -393,7 +417,7 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
 }
 
 template <template <typename> class EnvT, int H, int NHH, int kAct>
-static int fused_f32_launch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* wstream, const float* tab, const float* sigma,
+static int fused_f32_launch(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const float* wstream, const float* tab, const float* sigma,
                             const uint64_t* rng, int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
     using Env = EnvT<float>;
     constexpr int WPW = H / 32, A = Env::A;
@@ -402,38 +426,39 @@ static int fused_f32_launch(const tg_env_params* p, const double* d_ptab, const 
     memset(&sg, 0, sizeof(sg));
     for (int k = 0; k < A; ++k) sg.v[k] = sigma[k];
     static_assert(sizeof(float) * ((NHH + 1) * H + 4 * H + 4 + 2 * H * 32 + 2 * 4 * 2 * WPW * 32) <= 64 * 1024, "LDS budget");
-    if (block_envs == 16) {
-        const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * 16 + 2 * A * 4 * WPW * 16);
-        const dim3 grid((unsigned)ceil_div(tr->n, 16));
-        if (d_ptab != nullptr)
-            hipLaunchKernelGGL((fused_rollout_f32x16_kernel<PerEnv<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, per_env_table(p, d_ptab),
-                               (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg,
-                               rng, env_offset, p->agents);
-        else
-            hipLaunchKernelGGL((fused_rollout_f32x16_kernel<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
-                               (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset,
-                               p->agents);
-    } else {
-        const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * 32 + 2 * A * 2 * WPW * 32);
-        const dim3 grid((unsigned)ceil_div(tr->n, 32));
-        if (d_ptab != nullptr)
-            hipLaunchKernelGGL((fused_rollout_f32_kernel<PerEnv<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, per_env_table(p, d_ptab),
-                               (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg,
-                               rng, env_offset, p->agents);
-        else
-            hipLaunchKernelGGL((fused_rollout_f32_kernel<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act,
-                               (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset,
-                               p->agents);
-    }
+    // d_obs_norm != NULL: the ObsNormed instantiation (tg_fused_rollout_f32_on); d_ptab != NULL: the PerEnv one; both: both
+#define TG_F32_LAUNCH(KERNEL, ENVS)                                                                                                           \
+    do {                                                                                                                                      \
+        const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * ENVS + 2 * A * (64 / ENVS) * WPW * ENVS);           \
+        const dim3 grid((unsigned)ceil_div(tr->n, ENVS));                                                                                     \
+        const ObsNormTable on{d_obs_norm, clip};                                                                                              \
+        if (d_obs_norm != nullptr && d_ptab != nullptr)                                                                                       \
+            hipLaunchKernelGGL((KERNEL<ObsNormed<PerEnv<Env>>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st,                               \
+                               ObsNormArg<PerEnvTable>{per_env_table(p, d_ptab), on}, TG_F32_TAIL);                                           \
+        else if (d_obs_norm != nullptr)                                                                                                       \
+            hipLaunchKernelGGL((KERNEL<ObsNormed<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, ObsNormArg<typename Env::C>{c, on},    \
+                               TG_F32_TAIL);                                                                                                  \
+        else if (d_ptab != nullptr)                                                                                                           \
+            hipLaunchKernelGGL((KERNEL<PerEnv<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, per_env_table(p, d_ptab), TG_F32_TAIL);  \
+        else                                                                                                                                  \
+            hipLaunchKernelGGL((KERNEL<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, TG_F32_TAIL);                                 \
+    } while (0)
+#define TG_F32_TAIL                                                                                                                     \
+    (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset, \
+        p->agents
+    if (block_envs == 16) TG_F32_LAUNCH(fused_rollout_f32x16_kernel, 16);
+    else TG_F32_LAUNCH(fused_rollout_f32_kernel, 32);
+#undef TG_F32_TAIL
+#undef TG_F32_LAUNCH
     TG_LAUNCH_CHECK("tg_fused_rollout_f32");
     return TG_OK;
 }
 
 template <template <typename> class EnvT, int kAct>
-static int fused_f32_dispatch(int hidden, int n_hh, const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* wstream, const float* tab,
+static int fused_f32_dispatch(int hidden, int n_hh, const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const float* wstream, const float* tab,
                               const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
 #define TG_F32_CASE(HH, NN) \
-    case HH * 10 + NN: return fused_f32_launch<EnvT, HH, NN, kAct>(p, d_ptab, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
+    case HH * 10 + NN: return fused_f32_launch<EnvT, HH, NN, kAct>(p, d_ptab, d_obs_norm, clip, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
     switch (hidden * 10 + n_hh) {
         TG_F32_CASE(64, 0) TG_F32_CASE(64, 1) TG_F32_CASE(64, 2) TG_F32_CASE(64, 3)
         TG_F32_CASE(128, 0) TG_F32_CASE(128, 1) TG_F32_CASE(128, 2) TG_F32_CASE(128, 3)
@@ -459,7 +484,7 @@ int tg_fused_rollout_f32_block_envs(int64_t n, int32_t agents) {
     return (n <= (int64_t)16 * device_cus() && agents <= 16) ? 16 : 32;
 }
 
-static int fused_rollout_f32(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
+static int fused_rollout_f32(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
                              int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                              int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
     TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "tg_fused_rollout_f32_act: unknown activation %d", activation);
@@ -479,7 +504,7 @@ static int fused_rollout_f32(const tg_env_params* p, const double* d_ptab, const
     switch (activation * 16 + p->env_id) {
 #define TG_F32_ENV(ACT, ID, ENV)                                                                                                      \
     case ACT * 16 + ID:                                                                                                               \
-        return fused_f32_dispatch<ENV, ACT>(hidden, n_hh, p, d_ptab, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
+        return fused_f32_dispatch<ENV, ACT>(hidden, n_hh, p, d_ptab, d_obs_norm, clip, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
         TG_F32_ENV(TG_ACT_RELU, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
         TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE, QuadPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_PENDULUM, PendulumEnv)
         TG_F32_ENV(TG_ACT_TANH, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
@@ -492,14 +517,14 @@ static int fused_rollout_f32(const tg_env_params* p, const double* d_ptab, const
 int tg_fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
                          int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                          int32_t t_begin, int32_t t_end, void* stream) {
-    return fused_rollout_f32(p, nullptr, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+    return fused_rollout_f32(p, nullptr, nullptr, 0.0f, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
                              TG_ACT_RELU, stream);
 }
 
 int tg_fused_rollout_f32_act(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
                              int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                              int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
-    return fused_rollout_f32(p, nullptr, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+    return fused_rollout_f32(p, nullptr, nullptr, 0.0f, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
                              activation, stream);
 }
 
@@ -507,7 +532,7 @@ int tg_fused_rollout_f32_dr(const tg_env_params* p, const double* d_ptab, const 
                             int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
                             int64_t env_offset, int32_t t_begin, int32_t t_end, void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_fused_rollout_f32_dr: null parameter table");
-    return fused_rollout_f32(p, d_ptab, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+    return fused_rollout_f32(p, d_ptab, nullptr, 0.0f, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
                              TG_ACT_RELU, stream);
 }
 
@@ -515,8 +540,18 @@ int tg_fused_rollout_f32_act_dr(const tg_env_params* p, const double* d_ptab, co
                                 int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
                                 int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_fused_rollout_f32_act_dr: null parameter table");
-    return fused_rollout_f32(p, d_ptab, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
+    return fused_rollout_f32(p, d_ptab, nullptr, 0.0f, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
                              activation, stream);
+}
+
+int tg_fused_rollout_f32_on(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                            int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                            int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, const float* d_obs_norm, float clip,
+                            void* stream) {
+    TG_REQUIRE(d_obs_norm != nullptr, "tg_fused_rollout_f32_on: null observation-normalisation table");
+    TG_REQUIRE(clip > 0.0f, "tg_fused_rollout_f32_on: clip %g (a number > 0; +inf: no clamp)", (double)clip);
+    return fused_rollout_f32(p, d_ptab, d_obs_norm, clip, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset,
+                             t_begin, t_end, activation, stream);
 }
 
 }  // extern "C"

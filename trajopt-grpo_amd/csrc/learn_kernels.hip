@@ -18,6 +18,10 @@
 //                        compute-dtype input row (bf16 or f32, zero padding, the ones column the backward chain wants), the action
 //                        row, and up to two per-row scalars gathered from [T][n] arrays -- the first one optionally normalised on
 //                        the fly with tg_group_normalize's arithmetic (GRPO's advantage: no [T][n] advantage array at all).
+//   tg_obs_moments / tg_obs_norm_merge / tg_obs_normalize_rows / tg_learn_compact_on
+//                        running observation normalisation: the per-feature f64 moments of a trajectory's valid entries in a
+//                        fixed order, Chan's merge into {count, mean, m2} and the f32 table {mean, rstd}, and the normalised
+//                        input rows -- from an SoA slot or row-major rows, or inside the compaction pass.
 #include "tg_common.hpp"
 
 namespace tg {
@@ -251,8 +255,17 @@ __device__ static inline uint32_t pack_bf16x2(float a, float b) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));    // round to nearest even, as torch's copy_
 }
 
-template <typename OT>
-__global__ __launch_bounds__(256) void compact_rows_kernel(CompactArgs a) {
+template <bool ON>
+__device__ static inline float obs_value(float x, const float* __restrict__ on_tab, int S, int s, float on_clip) {
+    if constexpr (ON) return obs_normalize(x, on_tab[s], on_tab[S + s], on_clip);
+    else return x;
+}
+
+// ON: tg_learn_compact_on -- the observation's S columns are obs_normalize(x, mean[s], rstd[s], clip) (tg_common.hpp) of the stored
+// value (an f64 observation rounded to f32 first); the table's entries are read at uniform addresses (scalar loads).  Padding and
+// the ones column are what they were.
+template <typename OT, bool ON>
+__device__ __forceinline__ void compact_rows_body(const CompactArgs a, const float* __restrict__ on_tab, float on_clip) {
     __shared__ uint32_t sh[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t f0 = ((int64_t)blockIdx.x * 256 + tid) * 4;
@@ -285,7 +298,8 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(CompactArgs a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int s = s0 + j;
-                    v[j] = s < a.S ? (float)obs[(int64_t)s * a.obs_feat_stride + f] : (s == a.ones_col ? 1.0f : 0.0f);
+                    v[j] = s < a.S ? obs_value<ON>((float)obs[(int64_t)s * a.obs_feat_stride + f], on_tab, a.S, s, on_clip)
+                                   : (s == a.ones_col ? 1.0f : 0.0f);
                 }
                 *reinterpret_cast<uint4*>(row + s0 / 2) = uint4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
                                                                   pack_bf16x2(v[6], v[7])};
@@ -297,7 +311,8 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(CompactArgs a) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int s = s0 + j;
-                    v[j] = s < a.S ? (float)obs[(int64_t)s * a.obs_feat_stride + f] : (s == a.ones_col ? 1.0f : 0.0f);
+                    v[j] = s < a.S ? obs_value<ON>((float)obs[(int64_t)s * a.obs_feat_stride + f], on_tab, a.S, s, on_clip)
+                                   : (s == a.ones_col ? 1.0f : 0.0f);
                 }
                 *reinterpret_cast<float4*>(row + s0) = float4{v[0], v[1], v[2], v[3]};
             }
@@ -322,6 +337,142 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(CompactArgs a) {
         }
         if (a.dst1) a.dst1[out] = a.src1[f];
         ++out;
+    }
+}
+
+template <typename OT>
+__global__ __launch_bounds__(256) void compact_rows_kernel(CompactArgs a) {
+    compact_rows_body<OT, false>(a, nullptr, 0.0f);
+}
+
+template <typename OT>
+__global__ __launch_bounds__(256) void compact_rows_on_kernel(CompactArgs a, const float* __restrict__ on_tab, float on_clip) {
+    compact_rows_body<OT, true>(a, on_tab, on_clip);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// running observation statistics
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kObsMomentsMaxBlocks = 1024;    // workgroups per feature of the first stage (each walks its chunks in ascending order)
+
+// Stage 1, grid (blocks, S): workgroup (b, s) visits the 1,024-entry chunks b, b + blocks, ... of the flat mask in that order; a
+// thread adds its 4 entries in ascending order, a wave sums by the shuffle tree, the workgroup its 4 waves in order.  Every entry's
+// deviation d = x - c[s] is taken in f64 (exact for an f32 observation).  partial f64 [blocks][S][3] = {count, sum d, sum d^2}.
+template <typename OT>
+__global__ __launch_bounds__(256) void obs_moments_partial_kernel(const uint8_t* __restrict__ mask, const OT* __restrict__ obs,
+                                                                  int64_t feat_stride, int64_t M, const double* __restrict__ center,
+                                                                  double* __restrict__ partial) {
+    __shared__ double sh[3][4];
+    const int tid = threadIdx.x, s = blockIdx.y, S = gridDim.y;
+    const double c = center[s];
+    const OT* plane = obs + (int64_t)s * feat_stride;
+    const int64_t n_chunks = (M + kChunkElems - 1) / kChunkElems;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int64_t ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
+        const int64_t f0 = (ch * 256 + tid) * 4;
+        const uint32_t flags = load_mask4(mask, f0, M);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!((flags >> (8 * k)) & 1u)) continue;
+            const double d = (double)plane[f0 + k] - c;
+            acc[0] += 1.0;
+            acc[1] += d;
+            acc[2] = __builtin_fma(d, d, acc[2]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) sh[j][tid >> 6] = acc[j];
+    }
+    __syncthreads();
+    if (tid < 3) partial[((int64_t)blockIdx.x * S + s) * 3 + tid] = ((sh[tid][0] + sh[tid][1]) + sh[tid][2]) + sh[tid][3];
+}
+
+// Stage 2, one workgroup per feature: the stage-1 partials in a fixed order (thread-strided, shuffle tree, 4 waves in order).
+__global__ __launch_bounds__(256) void obs_moments_final_kernel(const double* __restrict__ partial, int blocks, int S, double* __restrict__ out) {
+    __shared__ double sh[3][4];
+    const int tid = threadIdx.x, s = blockIdx.x;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int b = tid; b < blocks; b += 256) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[j] += partial[((int64_t)b * S + s) * 3 + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) sh[j][tid >> 6] = acc[j];
+    }
+    __syncthreads();
+    if (tid < 3) out[s * 3 + tid] = ((sh[tid][0] + sh[tid][1]) + sh[tid][2]) + sh[tid][3];
+}
+
+// Chan's merge of the batch {n_b, sum d, sum d^2} (deviations from the running mean c) into {count, mean, m2}, one lane per feature,
+// every f64 operation rounded on its own, and the f32 table {(float)mean, (float)(1 / sqrt(m2 / count + eps))} rewritten in place
+// (IEEE sqrt and divide).  count == 0: mean 0, rstd 1.  batch == NULL or n_b == 0: the statistics stand, the table is rewritten.
+__global__ __launch_bounds__(64) void obs_norm_merge_kernel(const double* __restrict__ batch, int S, double eps, double* __restrict__ count,
+                                                            double* __restrict__ mean, double* __restrict__ m2, float* __restrict__ table) {
+#pragma clang fp contract(off)
+    const int s = threadIdx.x;
+    const double na = count[0];
+    double n = na;
+    if (s < S) {
+        double mu = mean[s], q = m2[s];
+        const double nb = batch ? batch[s * 3] : 0.0;
+        if (nb > 0.0) {
+            const double sd = batch[s * 3 + 1], sq = batch[s * 3 + 2];
+            n = na + nb;
+            const double db = sd / nb;                       // batch mean - running mean
+            const double m2b = sq - sd * db;                 // the batch's squared deviations from its own mean
+            mu = mu + db * (nb / n);
+            q = (q + (m2b > 0.0 ? m2b : 0.0)) + (db * db) * (na * (nb / n));
+            mean[s] = mu;
+            m2[s] = q;
+        }
+        table[s] = n > 0.0 ? (float)mu : 0.0f;
+        table[S + s] = n > 0.0 ? (float)(1.0 / sqrt(q / n + eps)) : 1.0f;
+    }
+    __syncthreads();                                         // every lane has read the old count
+    if (s == 0) count[0] = n;
+}
+
+// One thread per row: x[r][k] at x + r * row_stride + k * feat_stride (an SoA slot: row_stride 1; row-major rows: feat_stride 1)
+// -> the normalised, padded compute-dtype input row (tg_learn_compact's row contract).
+template <typename OT>
+__global__ __launch_bounds__(256) void obs_normalize_rows_kernel(const OT* __restrict__ x, int64_t row_stride, int64_t feat_stride, int64_t M,
+                                                                 int S, const float* __restrict__ on_tab, float on_clip, void* __restrict__ xin,
+                                                                 int in_pad, int xin_bf16, int ones_col) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= M) return;
+    const OT* src = x + r * row_stride;
+    auto value = [&](int s) {
+        return s < S ? obs_normalize((float)src[(int64_t)s * feat_stride], on_tab[s], on_tab[S + s], on_clip) : (s == ones_col ? 1.0f : 0.0f);
+    };
+    if (xin_bf16) {
+        uint32_t* row = reinterpret_cast<uint32_t*>(xin) + r * (in_pad / 2);
+        for (int s0 = 0; s0 < in_pad; s0 += 8) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = value(s0 + j);
+            *reinterpret_cast<uint4*>(row + s0 / 2) = uint4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
+                                                              pack_bf16x2(v[6], v[7])};
+        }
+    } else {
+        float* row = reinterpret_cast<float*>(xin) + r * in_pad;
+        for (int s0 = 0; s0 < in_pad; s0 += 4) {
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = value(s0 + j);
+            *reinterpret_cast<float4*>(row + s0) = float4{v[0], v[1], v[2], v[3]};
+        }
     }
 }
 
@@ -386,7 +537,7 @@ int tg_learn_count(const uint8_t* d_mask, int64_t entries, int64_t expected_rows
     return TG_OK;
 }
 
-int tg_learn_compact(const tg_compact_args* p, void* stream) {
+static int learn_compact_impl(const tg_compact_args* p, const float* d_obs_norm, float clip, void* stream) {
     TG_REQUIRE(p && p->d_mask && p->d_offsets && p->d_obs && p->d_xin && p->d_idx, "tg_learn_compact: null pointer");
     TG_REQUIRE(p->n > 0 && p->T > 0 && p->S > 0 && p->S <= 64, "tg_learn_compact: bad sizes (n %lld, T %d, S %d)", (long long)p->n, p->T, p->S);
     TG_REQUIRE(p->obs_dtype == TG_F32 || p->obs_dtype == TG_F64, "tg_learn_compact: obs dtype %d", p->obs_dtype);
@@ -409,9 +560,81 @@ int tg_learn_compact(const tg_compact_args* p, void* stream) {
     if (p->rows_cap == 0) return TG_OK;
     const int64_t n_chunks = ceil_div(a.M, kChunkElems);
     hipStream_t st = (hipStream_t)stream;
-    if (a.obs_f64) hipLaunchKernelGGL(compact_rows_kernel<double>, dim3((unsigned)n_chunks), dim3(256), 0, st, a);
+    if (d_obs_norm != nullptr) {
+        if (a.obs_f64) hipLaunchKernelGGL(compact_rows_on_kernel<double>, dim3((unsigned)n_chunks), dim3(256), 0, st, a, d_obs_norm, clip);
+        else hipLaunchKernelGGL(compact_rows_on_kernel<float>, dim3((unsigned)n_chunks), dim3(256), 0, st, a, d_obs_norm, clip);
+    } else if (a.obs_f64) hipLaunchKernelGGL(compact_rows_kernel<double>, dim3((unsigned)n_chunks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(compact_rows_kernel<float>, dim3((unsigned)n_chunks), dim3(256), 0, st, a);
     TG_LAUNCH_CHECK("tg_learn_compact");
+    return TG_OK;
+}
+
+int tg_learn_compact(const tg_compact_args* p, void* stream) { return learn_compact_impl(p, nullptr, 0.0f, stream); }
+
+int tg_learn_compact_on(const tg_compact_args* p, const float* d_obs_norm, float clip, void* stream) {
+    TG_REQUIRE(d_obs_norm != nullptr, "tg_learn_compact_on: null observation-normalisation table");
+    TG_REQUIRE(clip > 0.0f, "tg_learn_compact_on: clip %g (a number > 0; +inf: no clamp)", (double)clip);
+    return learn_compact_impl(p, d_obs_norm, clip, stream);
+}
+
+static int obs_moments_blocks(int64_t entries) {
+    const int64_t n_chunks = ceil_div(entries > 0 ? entries : 1, kChunkElems);
+    return (int)(n_chunks < kObsMomentsMaxBlocks ? n_chunks : kObsMomentsMaxBlocks);
+}
+
+int64_t tg_obs_moments_workspace(int64_t entries, int32_t S) { return (int64_t)obs_moments_blocks(entries) * (S > 0 ? S : 1) * 3 * (int64_t)sizeof(double); }
+
+int tg_obs_moments(const tg_traj* tr, int32_t S, const double* d_center, void* d_work, int64_t work_bytes, double* d_out, void* stream) {
+    TG_REQUIRE(tr && tr->d_obs && tr->d_mask && d_center && d_work && d_out, "tg_obs_moments: null pointer");
+    TG_REQUIRE(tr->n > 0 && tr->horizon > 0 && S > 0 && S <= 64, "tg_obs_moments: bad sizes (n %lld, T %d, S %d)", (long long)tr->n, tr->horizon, S);
+    TG_REQUIRE(tr->dtype == TG_F32 || tr->dtype == TG_F64, "tg_obs_moments: obs dtype %d", tr->dtype);
+    const int64_t M = (int64_t)tr->horizon * tr->n, feat_stride = ((int64_t)tr->horizon + 1) * tr->n;
+    TG_REQUIRE(work_bytes >= tg_obs_moments_workspace(M, S), "tg_obs_moments: workspace of %lld B < %lld", (long long)work_bytes,
+               (long long)tg_obs_moments_workspace(M, S));
+    const int blocks = obs_moments_blocks(M);
+    hipStream_t st = (hipStream_t)stream;
+    if (tr->dtype == TG_F64)
+        hipLaunchKernelGGL(obs_moments_partial_kernel<double>, dim3((unsigned)blocks, (unsigned)S), dim3(256), 0, st, tr->d_mask, (const double*)tr->d_obs,
+                           feat_stride, M, d_center, (double*)d_work);
+    else
+        hipLaunchKernelGGL(obs_moments_partial_kernel<float>, dim3((unsigned)blocks, (unsigned)S), dim3(256), 0, st, tr->d_mask, (const float*)tr->d_obs,
+                           feat_stride, M, d_center, (double*)d_work);
+    TG_LAUNCH_CHECK("tg_obs_moments");
+    hipLaunchKernelGGL(obs_moments_final_kernel, dim3((unsigned)S), dim3(256), 0, st, (const double*)d_work, blocks, S, d_out);
+    TG_LAUNCH_CHECK("tg_obs_moments(final)");
+    return TG_OK;
+}
+
+int tg_obs_norm_merge(const double* d_batch, int32_t S, double eps, double* d_count, double* d_mean, double* d_m2, float* d_table, void* stream) {
+    TG_REQUIRE(d_count && d_mean && d_m2 && d_table, "tg_obs_norm_merge: null pointer");
+    TG_REQUIRE(S > 0 && S <= 64, "tg_obs_norm_merge: S = %d (1..64)", S);
+    TG_REQUIRE(eps >= 0.0, "tg_obs_norm_merge: eps %g < 0", eps);
+    hipLaunchKernelGGL(obs_norm_merge_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_batch, S, eps, d_count, d_mean, d_m2, d_table);
+    TG_LAUNCH_CHECK("tg_obs_norm_merge");
+    return TG_OK;
+}
+
+int tg_obs_normalize_rows(const void* d_x, int32_t x_dtype, int64_t row_stride, int64_t feat_stride, int64_t rows, int32_t S,
+                          const float* d_obs_norm, float clip, void* d_xin, int32_t in_pad, int32_t xin_bf16, int32_t ones_col, void* stream) {
+    TG_REQUIRE(rows >= 0, "tg_obs_normalize_rows: negative row count");
+    if (rows == 0) return TG_OK;
+    TG_REQUIRE(d_x && d_obs_norm && d_xin, "tg_obs_normalize_rows: null pointer");
+    TG_REQUIRE(x_dtype == TG_F32 || x_dtype == TG_F64, "tg_obs_normalize_rows: dtype %d", x_dtype);
+    TG_REQUIRE(S > 0 && S <= 64 && row_stride >= 1 && feat_stride >= 1, "tg_obs_normalize_rows: bad sizes (S %d, strides %lld / %lld)", S,
+               (long long)row_stride, (long long)feat_stride);
+    TG_REQUIRE(in_pad >= S && in_pad <= 64 && in_pad % (xin_bf16 ? 8 : 4) == 0, "tg_obs_normalize_rows: in_pad %d (a multiple of %d, >= S)", in_pad,
+               xin_bf16 ? 8 : 4);
+    TG_REQUIRE(ones_col < in_pad && (ones_col < 0 || ones_col >= S), "tg_obs_normalize_rows: ones column %d inside the observation", ones_col);
+    TG_REQUIRE(clip > 0.0f, "tg_obs_normalize_rows: clip %g (a number > 0; +inf: no clamp)", (double)clip);
+    const dim3 grid((unsigned)ceil_div(rows, 256));
+    hipStream_t st = (hipStream_t)stream;
+    if (x_dtype == TG_F64)
+        hipLaunchKernelGGL(obs_normalize_rows_kernel<double>, grid, dim3(256), 0, st, (const double*)d_x, row_stride, feat_stride, rows, S, d_obs_norm,
+                           clip, d_xin, in_pad, xin_bf16, ones_col);
+    else
+        hipLaunchKernelGGL(obs_normalize_rows_kernel<float>, grid, dim3(256), 0, st, (const float*)d_x, row_stride, feat_stride, rows, S, d_obs_norm,
+                           clip, d_xin, in_pad, xin_bf16, ones_col);
+    TG_LAUNCH_CHECK("tg_obs_normalize_rows");
     return TG_OK;
 }
 

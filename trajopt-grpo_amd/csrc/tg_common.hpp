@@ -46,6 +46,13 @@ __device__ static inline float rn_div(float a, float b) {
     return a / b;
 }
 
+// The normalised observation, the one definition every path uses (rollout kernels, learner rows, the per-step path; policies.py
+// states it in torch): fp32 subtract, multiply and clamp, each rounded on its own.  clip = +inf: no clamp.  A NaN stays a NaN.
+__device__ static inline float obs_normalize(float x, float mean, float rstd, float clip) {
+    const float v = rn_mul(rn_sub(x, mean), rstd);
+    return v < -clip ? -clip : (v > clip ? clip : v);
+}
+
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- in-kernel clock probe (tg_clock_probe_attach; bench.py's roofline.clock_GHz) ----

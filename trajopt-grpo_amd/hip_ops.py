@@ -93,9 +93,10 @@ def learn_count_workspace(entries: int) -> int:
 
 
 def learn_compact(traj, offsets, rows_cap: int, xin: torch.Tensor, ones_col: int, act_rows, idx, src0=None, dst0=None, src1=None, dst1=None,
-                  moments=None, norm_mode: int = 0, group_size: int = 0) -> None:
+                  moments=None, norm_mode: int = 0, group_size: int = 0, obs_norm=None) -> None:
     """tg_learn_compact on a DeviceTrajectory: the valid rows' flat indices, padded input rows, action rows and up to two per-row
-    scalars (src0 optionally normalised with `moments`), in time-major order, in one launch."""
+    scalars (src0 optionally normalised with `moments`), in time-major order, in one launch.  obs_norm (a policy's ObsNorm):
+    tg_learn_compact_on -- the input rows hold the normalised observation."""
     N.require_cuda(traj.mask, traj.obs, traj.act, xin, act_rows, idx, src0, dst0, src1, dst1, moments)
     assert xin.dim() == 2 and xin.is_contiguous() and xin.dtype in (torch.bfloat16, torch.float32) and xin.shape[0] >= rows_cap
     assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() >= rows_cap
@@ -115,7 +116,59 @@ def learn_compact(traj, offsets, rows_cap: int, xin: torch.Tensor, ones_col: int
     if moments is not None:
         assert moments.dtype == torch.float64 and moments.is_contiguous() and moments.numel() == 3 * (traj.n // group_size)
     a.d_moments, a.group_size, a.rows_cap = N.ptr(moments), int(group_size), int(rows_cap)
+    if obs_norm is not None:
+        assert obs_norm.table.numel() == 2 * traj.S and obs_norm.table.device == xin.device
+        N.check(N.load().tg_learn_compact_on(C.byref(a), obs_norm.table.data_ptr(), obs_norm.clip_value, _st(xin)), "tg_learn_compact_on")
+        return
     N.check(N.load().tg_learn_compact(C.byref(a), _st(xin)), "tg_learn_compact")
+
+
+def obs_moments(traj, center: torch.Tensor, out: torch.Tensor = None, work: torch.Tensor = None) -> torch.Tensor:
+    """tg_obs_moments on a DeviceTrajectory: f64 [S][3] = {count, sum (x - center[s]), sum (x - center[s])^2} over the valid (t, e)
+    entries, per feature, in a fixed order.  center f64 [S]; work: f64 scratch of obs_moments_workspace(T * n, S) bytes."""
+    N.require_cuda(traj.obs, traj.mask, center, out, work)
+    assert center.dtype == torch.float64 and center.is_contiguous() and center.numel() == traj.S
+    assert traj.obs.is_contiguous() and traj.mask.is_contiguous()
+    need = int(N.load().tg_obs_moments_workspace(traj.T * traj.n, traj.S))
+    if work is None:
+        work = torch.empty(need // 8, dtype=torch.float64, device=center.device)
+    if out is None:
+        out = torch.empty(traj.S, 3, dtype=torch.float64, device=center.device)
+    assert work.dtype == torch.float64 and work.numel() * 8 >= need and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 3 * traj.S
+    tr = traj.native()
+    N.check(N.load().tg_obs_moments(C.byref(tr), traj.S, center.data_ptr(), work.data_ptr(), work.numel() * 8, out.data_ptr(), _st(center)),
+            "tg_obs_moments")
+    return out
+
+
+def obs_moments_workspace(entries: int, S: int) -> int:
+    return int(N.load().tg_obs_moments_workspace(int(entries), int(S)))
+
+
+def obs_norm_merge(batch, eps: float, count: torch.Tensor, mean: torch.Tensor, m2: torch.Tensor, table: torch.Tensor) -> None:
+    """tg_obs_norm_merge: Chan's merge of batch f64 [S][3] (None: nothing to merge) into count / mean / m2, and the f32 table [2][S]
+    rewritten in place."""
+    N.require_cuda(batch, count, mean, m2, table)
+    S = mean.numel()
+    for t in (count, mean, m2) + ((batch,) if batch is not None else ()):
+        assert t.dtype == torch.float64 and t.is_contiguous()
+    assert count.numel() == 1 and m2.numel() == S and table.dtype == torch.float32 and table.is_contiguous() and table.numel() == 2 * S
+    assert batch is None or batch.numel() == 3 * S
+    N.check(N.load().tg_obs_norm_merge(N.ptr(batch), S, float(eps), count.data_ptr(), mean.data_ptr(), m2.data_ptr(), table.data_ptr(),
+                                       _st(table)), "tg_obs_norm_merge")
+
+
+def obs_normalize_rows(x: torch.Tensor, obs_norm, xin: torch.Tensor, ones_col: int = -1) -> torch.Tensor:
+    """tg_obs_normalize_rows: x [M][S] f32 / f64 with any two strides (an SoA slot's transposed view, row-major rows) -> xin
+    [M][in_pad] bf16 / f32: the normalised observation, zero padding, 1 in column ones_col (or -1)."""
+    N.require_cuda(x, xin, obs_norm.table)
+    M, S = x.shape
+    assert xin.dim() == 2 and xin.is_contiguous() and xin.shape[0] >= M and xin.dtype in (torch.bfloat16, torch.float32)
+    assert obs_norm.table.numel() == 2 * S and xin.data_ptr() % 16 == 0
+    N.check(N.load().tg_obs_normalize_rows(x.data_ptr(), N.dtype_code(x.dtype), max(x.stride(0), 1), max(x.stride(1), 1), M, S,
+                                           obs_norm.table.data_ptr(), obs_norm.clip_value, xin.data_ptr(), xin.shape[1],
+                                           int(xin.dtype == torch.bfloat16), int(ones_col), _st(xin)), "tg_obs_normalize_rows")
+    return xin
 
 
 def scatter_rows(src: torch.Tensor, idx: torch.Tensor, dst: torch.Tensor) -> None:

@@ -363,9 +363,19 @@ class GemmMLP:
                         N.check(N.load().tg_dx_pack_weights(w.data_ptr(), frag.data_ptr(), w.shape[0], w.shape[1],
                                                             N.stream_ptr(w.device)), "tg_dx_pack_weights")
 
-    def prepare_input(self, X: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    def prepare_input(self, X: torch.Tensor, out: torch.Tensor = None, obs_norm=None) -> torch.Tensor:
         """[M][in_dim] (any float dtype, any strides) -> contiguous [M][in_pad] compute dtype, zero padded
-        (into `out` when given: a [M][in_pad] buffer of the compute dtype)."""
+        (into `out` when given: a [M][in_pad] buffer of the compute dtype).  obs_norm (a policy's ObsNorm): the rows hold the
+        normalised observation -- one tg_obs_normalize_rows launch writes values, padding and the ones column."""
+        if obs_norm is not None:
+            from . import hip_ops as K
+            xp = torch.empty(X.shape[0], self.in_pad, dtype=self.cd, device=X.device) if out is None else out
+            ones = self.in_pad == 32 and self.in_dim < 32 and self._f32 is None
+            if X.dtype not in (torch.float32, torch.float64):
+                X = X.float()
+            K.obs_normalize_rows(X, obs_norm, xp, 31 if ones else -1)
+            set_ones_column(xp, ones)
+            return xp
         xp = torch.zeros(X.shape[0], self.in_pad, dtype=self.cd, device=X.device) if out is None else out.zero_()
         xp[:, :self.in_dim].copy_(X)
         if self.in_pad == 32 and self.in_dim < 32 and self._f32 is None:

@@ -8,6 +8,7 @@ same checkpoint formats (`policy.pt`: bare actor state_dict for the actor-only p
 (hipBLASLt -> MFMA); sampling, log-prob and the loss head are HIP kernels (rollout.py,
 algorithms.py).  The covariance is a diagonal matrix (actor_critic.py:100-103, :247-250): fixed by default, or -- with
 `learn_std=True` -- diag(exp(2 log_std)) of a learned per-dimension `log_std` parameter that the learners train on the device.
+With `normalize_obs=True` every path reads states through running per-feature statistics (`policy.obs_norm`, class ObsNorm).
 """
 from __future__ import annotations
 
@@ -21,6 +22,142 @@ import torch
 
 def default_device():
     return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+
+
+class ObsNorm:
+    """Running observation statistics of a policy built with normalize_obs=True, on the policy's device:
+        count f64 [1], mean f64 [S], m2 f64 [S] (sum of squared deviations; var = m2 / count is the population variance),
+        table f32 [2][S] = {(float)mean, (float)(1 / sqrt(var + eps))} -- ONE allocation for the life of the policy, rewritten in
+        place (count == 0: mean 0, rstd 1), so captured graphs and cached kernel arguments stay valid.
+    The normalised observation is one fp32 expression on every path (rollout kernels, learner rows, this class's normalize()):
+        xn[k] = clamp((x[k] - table[0][k]) * table[1][k], -clip, +clip)
+    subtract, multiply and clamp each rounded on its own; an f64 observation is rounded to f32 first; bf16 paths round xn once.
+    The learners call update(traj) at the entry of learn() unless frozen; trajectories keep the RAW observations.  `clip` and `eps`
+    are fixed at construction (a captured rollout graph holds the clamp by value).  A deepcopy of a policy owns its own statistics;
+    the learners make their old_policy share the policy's object."""
+
+    def __init__(self, dim: int, clip, eps: float, device):
+        self.dim, self._clip, self._eps = int(dim), clip, float(eps)
+        self.frozen = False
+        dev = torch.device(device)
+        self.count = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.mean = torch.zeros(self.dim, dtype=torch.float64, device=dev)
+        self.m2 = torch.zeros(self.dim, dtype=torch.float64, device=dev)
+        self.table = torch.stack([torch.zeros(self.dim), torch.ones(self.dim)]).to(dev, torch.float32).contiguous()
+        self._work = self._batch = None
+
+    @property
+    def clip(self):
+        return self._clip
+
+    @property
+    def eps(self) -> float:
+        return self._eps
+
+    @property
+    def clip_value(self) -> float:
+        """The clamp as the kernels take it: +inf for obs_clip=None."""
+        return math.inf if self.clip is None else float(self.clip)
+
+    @property
+    def var(self) -> torch.Tensor:
+        return self.m2 / self.count.clamp_min(1.0)
+
+    def freeze(self):
+        self.frozen = True
+        return self
+
+    def unfreeze(self):
+        self.frozen = False
+        return self
+
+    def to(self, device):
+        """Moves the statistics (policy.to): a move is a new allocation on the new device -- engines are built after it."""
+        dev = torch.device(device)
+        if dev != self.count.device:
+            self.count, self.mean, self.m2, self.table = (t.to(dev) for t in (self.count, self.mean, self.m2, self.table))
+            self._work = self._batch = None
+        return self
+
+    @torch.no_grad()
+    def _merge(self, batch=None) -> None:
+        """Chan's merge of batch f64 [S][3] = {n_b, sum (x - mean), sum (x - mean)^2} into the statistics, then the table in place:
+        tg_obs_norm_merge on the device; the same operations in torch for a CPU policy (the host path)."""
+        if self.count.is_cuda:
+            from . import hip_ops as K
+            with torch.cuda.device(self.count.device):
+                K.obs_norm_merge(batch, self.eps, self.count, self.mean, self.m2, self.table)
+            return
+        if batch is not None and float(batch[0, 0]) > 0:
+            na, nb, sd, sq = self.count[0].clone(), batch[0, 0], batch[:, 1], batch[:, 2]
+            n = na + nb
+            db = sd / nb
+            m2b = (sq - sd * db).clamp_min(0.0)
+            self.mean.add_(db * (nb / n))
+            self.m2.copy_((self.m2 + m2b) + (db * db) * (na * (nb / n)))
+            self.count.fill_(float(n))
+        if float(self.count[0]) > 0:
+            self.table[0].copy_(self.mean.float())
+            self.table[1].copy_((1.0 / torch.sqrt(self.m2 / self.count + self.eps)).float())
+        else:
+            self.table[0].zero_()
+            self.table[1].fill_(1.0)
+
+    @torch.no_grad()
+    def update(self, traj, process_group=None) -> None:
+        """Merge the valid (t, e) observations of a device trajectory into the statistics and rewrite the table: tg_obs_moments about
+        the current mean (identical on every rank, so one pass is safe), ONE all-reduce of the f64 [S][3], tg_obs_norm_merge.  No
+        host round trip.  Runs whether or not the policy is frozen: the learners ask `frozen` before they call."""
+        from . import distributed as D
+        from . import hip_ops as K
+        if traj.S != self.dim or traj.obs.device != self.count.device:
+            raise ValueError(f"obs_norm.update: a trajectory of {traj.S} features on {traj.obs.device}, statistics of {self.dim} on {self.count.device}")
+        with torch.cuda.device(self.count.device):
+            need = K.obs_moments_workspace(traj.T * traj.n, self.dim) // 8
+            if self._work is None or self._work.numel() < need:
+                self._work = torch.empty(need, dtype=torch.float64, device=self.count.device)
+            if self._batch is None:
+                self._batch = torch.empty(self.dim, 3, dtype=torch.float64, device=self.count.device)
+            K.obs_moments(traj, self.mean, self._batch, self._work)
+            D.allreduce_sum_(self._batch, process_group, "obs_moments")
+            K.obs_norm_merge(self._batch, self.eps, self.count, self.mean, self.m2, self.table)
+
+    @torch.no_grad()
+    def set(self, mean, var, count) -> None:
+        """Statistics from outside (tests, imported normalisers): per-feature mean and population variance of `count` samples."""
+        mean = torch.as_tensor(mean, dtype=torch.float64).reshape(-1)
+        var = torch.as_tensor(var, dtype=torch.float64).reshape(-1)
+        count = float(count)
+        if mean.numel() != self.dim or var.numel() != self.dim or not (count >= 0 and math.isfinite(count)) or bool((var < 0).any()):
+            raise ValueError(f"obs_norm.set: mean and var of {self.dim} features (var >= 0) and a finite count >= 0, got "
+                             f"{tuple(mean.shape)}, {tuple(var.shape)}, {count!r}")
+        self.count.fill_(count)
+        self.mean.copy_(mean)
+        self.m2.copy_(var * count)
+        self._merge(None)
+
+    def normalize(self, x: torch.Tensor) -> torch.Tensor:
+        """The normalised observation of x [..., S] in torch (the host path): float32, the kernels' three operations."""
+        tab = self.table.to(x.device)
+        xn = (x.to(torch.float32) - tab[0]) * tab[1]
+        return xn if self.clip is None else torch.clamp(xn, -float(self.clip), float(self.clip))
+
+    def state(self) -> dict:
+        return {"obs_norm.count": self.count, "obs_norm.mean": self.mean, "obs_norm.m2": self.m2}
+
+    @torch.no_grad()
+    def load_state(self, count, mean, m2) -> None:
+        count, mean, m2 = (torch.as_tensor(t, dtype=torch.float64).reshape(-1) for t in (count, mean, m2))
+        if count.numel() != 1 or mean.numel() != self.dim or m2.numel() != self.dim:
+            raise ValueError(f"obs_norm statistics of shapes {tuple(count.shape)}, {tuple(mean.shape)}, {tuple(m2.shape)} do not fit "
+                             f"{self.dim} features")
+        self.count.copy_(count)
+        self.mean.copy_(mean)
+        self.m2.copy_(m2)
+        self._merge(None)
+
+
+OBS_NORM_KEYS = ("obs_norm.count", "obs_norm.mean", "obs_norm.m2")
 
 
 class NeuralNetwork(torch.nn.Module):
@@ -63,9 +200,17 @@ class ActorCritic:
 class _GaussianBase(ActorCritic):
     has_critic = False
 
-    def __init__(self, input_dim, output_dim, hidden_dims, activation="ReLU", cov=0.1, device=None, learn_std=False):
+    def __init__(self, input_dim, output_dim, hidden_dims, activation="ReLU", cov=0.1, device=None, learn_std=False, *,
+                 normalize_obs=False, obs_clip=10.0, obs_eps=1e-8):
         if not isinstance(learn_std, bool):
             raise ValueError(f"learn_std must be True or False, got {learn_std!r}")
+        if not isinstance(normalize_obs, bool):
+            raise ValueError(f"normalize_obs must be True or False, got {normalize_obs!r}")
+        if obs_clip is not None and (isinstance(obs_clip, bool) or not isinstance(obs_clip, (int, float))
+                                     or not (math.isfinite(obs_clip) and obs_clip > 0)):
+            raise ValueError(f"obs_clip must be None or a finite number > 0, got {obs_clip!r}")
+        if isinstance(obs_eps, bool) or not isinstance(obs_eps, (int, float)) or not (math.isfinite(obs_eps) and obs_eps >= 0):
+            raise ValueError(f"obs_eps must be a finite number >= 0, got {obs_eps!r}")
         self.input_dim, self.output_dim = input_dim, output_dim
         self.hidden_dims, self.activation = hidden_dims, activation
         self.device = torch.device(device) if device is not None else default_device()
@@ -81,6 +226,10 @@ class _GaussianBase(ActorCritic):
             del self._cov                                 # (the constructor's matrix is not the covariance any more)
         self.actor = NeuralNetwork(input_dim, output_dim, hidden_dims, activation).to(self.device)
         self.critic = None
+        # running observation normalisation: None when off (no path then touches a table).  The row kernel takes up to 64 features.
+        if normalize_obs and input_dim > 64:
+            raise ValueError(f"normalize_obs=True supports up to 64 observation features (tg_obs_normalize_rows), got input_dim={input_dim}")
+        self.obs_norm = ObsNorm(input_dim, None if obs_clip is None else float(obs_clip), obs_eps, self.device) if normalize_obs else None
 
     # ---- helpers ----------------------------------------------------------
     @staticmethod
@@ -123,6 +272,8 @@ class _GaussianBase(ActorCritic):
             self.critic.to(self.device)
         if self.log_std is not None:
             self.log_std.data = self.log_std.data.to(self.device)
+        if self.obs_norm is not None:
+            self.obs_norm.to(self.device)
         return self
 
     def _with_log_std(self, params):
@@ -142,10 +293,30 @@ class _GaussianBase(ActorCritic):
         with torch.no_grad():
             self.log_std.copy_(value)
 
+    def _obs_norm_state(self) -> dict:
+        return self.obs_norm.state() if self.obs_norm is not None else {}
+
+    def _load_obs_norm(self, state_dict) -> None:
+        """load_state_dict's `obs_norm.*` entries: they and normalize_obs go together, either way round."""
+        have = [k for k in OBS_NORM_KEYS if k in state_dict]
+        if have and self.obs_norm is None:
+            raise ValueError("the state dict holds observation statistics ('obs_norm.*'), this policy reads raw observations: construct "
+                             "it with normalize_obs=True (or drop the keys)")
+        if self.obs_norm is not None:
+            if len(have) != len(OBS_NORM_KEYS):
+                raise ValueError("this policy normalises its observations, the state dict holds no 'obs_norm.count' / 'obs_norm.mean' / "
+                                 "'obs_norm.m2': it was saved by a policy without normalize_obs=True")
+            self.obs_norm.load_state(*(state_dict[k] for k in OBS_NORM_KEYS))
+
     def _prep(self, x):
         if isinstance(x, np.ndarray):
             x = torch.from_numpy(x).float()
         return x.to(self.device, torch.float32)
+
+    def _prep_obs(self, x):
+        """_prep of an observation: what the nets read -- the normalised observation when normalize_obs is on."""
+        x = self._prep(x)
+        return self.obs_norm.normalize(x) if self.obs_norm is not None else x
 
     def _logp(self, mean, action):
         k = self.output_dim
@@ -169,7 +340,7 @@ class _GaussianBase(ActorCritic):
     def forward(self, state):
         """actor_critic.py:107-138 / :255-289: sample a ~ N(actor(state), cov).
         Returns (action ndarray float32, log_prob Tensor, value Tensor|None)."""
-        state = self._prep(state)
+        state = self._prep_obs(state)
         mean = self.actor(state)
         with torch.no_grad():
             std = torch.exp(self.log_std).to(mean.device) if self.log_std is not None else torch.sqrt(self.var).to(mean.device)
@@ -180,7 +351,7 @@ class _GaussianBase(ActorCritic):
 
     def log_prob(self, observation, action):
         """actor_critic.py:140-160 / :291-311 -> (log_prob, entropy)."""
-        observation, action = self._prep(observation), self._prep(action)
+        observation, action = self._prep_obs(observation), self._prep(action)
         mean = self.actor(observation)
         return self._logp(mean, action), self._entropy(mean.shape[:-1], mean.device)
 
@@ -193,6 +364,7 @@ class _GaussianBase(ActorCritic):
             "cov": self.cov.tolist() if isinstance(self.cov, torch.Tensor) else self.cov,
             "num_parameters": sum(p.numel() for p in self.parameters()),
             **({"learn_std": True} if self.log_std is not None else {}),
+            **({"normalize_obs": True, "obs_clip": self.obs_norm.clip} if self.obs_norm is not None else {}),
         }
 
 
@@ -209,11 +381,15 @@ class GaussianActor_NeuralNetwork(_GaussianBase):
         sd = self.actor.state_dict()
         if self.log_std is not None:
             sd["log_std"] = self.log_std.data                 # (next to the `network.*` keys)
+        sd.update(self._obs_norm_state())
         return sd
 
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         self._load_log_std(state_dict.pop("log_std", None))
+        self._load_obs_norm(state_dict)
+        for k in OBS_NORM_KEYS:
+            state_dict.pop(k, None)
         self.actor.load_state_dict(state_dict)
 
     def save(self, path):
@@ -228,12 +404,14 @@ class GaussianActorCritic_NeuralNetwork(_GaussianBase):
     """policies/actor_critic.py:220-378."""
     has_critic = True
 
-    def __init__(self, input_dim, output_dim, hidden_dims, activation="ReLU", cov=0.1, device=None, learn_std=False):
-        super().__init__(input_dim, output_dim, hidden_dims, activation, cov, device, learn_std)
+    def __init__(self, input_dim, output_dim, hidden_dims, activation="ReLU", cov=0.1, device=None, learn_std=False, *,
+                 normalize_obs=False, obs_clip=10.0, obs_eps=1e-8):
+        super().__init__(input_dim, output_dim, hidden_dims, activation, cov, device, learn_std, normalize_obs=normalize_obs,
+                         obs_clip=obs_clip, obs_eps=obs_eps)
         self.critic = NeuralNetwork(input_dim, 1, hidden_dims, activation).to(self.device)
 
     def value(self, state):
-        return self.critic(self._prep(state)).squeeze()                   # :313-323
+        return self.critic(self._prep_obs(state)).squeeze()               # :313-323
 
     def parameters(self):
         return self._with_log_std(list(self.actor.parameters()) + list(self.critic.parameters()))
@@ -242,10 +420,12 @@ class GaussianActorCritic_NeuralNetwork(_GaussianBase):
         sd = {"actor": self.actor.state_dict(), "critic": self.critic.state_dict()}
         if self.log_std is not None:
             sd["log_std"] = self.log_std.data                 # (top level, next to "actor" / "critic")
+        sd.update(self._obs_norm_state())
         return sd
 
     def load_state_dict(self, state_dict):
         self._load_log_std(state_dict.get("log_std"))
+        self._load_obs_norm(state_dict)
         self.actor.load_state_dict(state_dict["actor"])
         self.critic.load_state_dict(state_dict["critic"])
 

@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 from . import _native as N
 from . import distributed as D
+from . import hip_ops as K
 from . import mlp as M
 
 
@@ -129,6 +130,9 @@ class DeviceRollout:
         elif compute_dtype is not None and compute_dtype != torch.float32:
             self._lowp = [(torch.empty_like(l.weight, dtype=compute_dtype), torch.empty_like(l.bias, dtype=compute_dtype))
                           for l in self._linears]
+        # normalize_obs without a GemmMLP: the normalised f32 rows of a time step (tg_obs_normalize_rows), padded to 4 columns
+        self._xn = (torch.zeros(self.n, (self.S + 3) // 4 * 4, dtype=torch.float32, device=self.device)
+                    if getattr(policy, "obs_norm", None) is not None and self._mlp is None else None)
         self.use_graph = use_graph
         self._graph = None
         self._graph_baked = None
@@ -185,7 +189,15 @@ class DeviceRollout:
     def _actor_mean(self, t: int) -> torch.Tensor:
         """Policy mean for slot t: fp32 [N][>=A] with unit column stride (row stride = .stride(0))."""
         x = self.traj.obs[:, t, :].t()                        # [N][S] view of the SoA slot
-        if self._mlp is not None:
+        on = getattr(self.policy, "obs_norm", None)
+        if on is not None:
+            # normalize_obs: one tg_obs_normalize_rows launch in place of the copy.  It reads the policy's table through its one
+            # allocation (rewritten in place by every update), so a captured graph replays with the current statistics.
+            if self._mlp is not None:
+                K.obs_normalize_rows(x, on, self._xp)
+                return self._mlp.forward(self._xp, keep=False, padded=True)
+            x = K.obs_normalize_rows(x, on, self._xn)[:, :self.S]
+        elif self._mlp is not None:
             self._xp[:, :self.S].copy_(x)
             return self._mlp.forward(self._xp, keep=False, padded=True)
         if self._lowp is None:
@@ -298,7 +310,18 @@ class DeviceRollout:
             ev = N.event_pair()
             ev[0].record()
         pt = None if self.env_params is None else self.env_params.data_ptr()
-        if pt is not None and self._fused_f32:
+        on = getattr(self.policy, "obs_norm", None)
+        if on is not None and self._fused_f32:
+            # normalize_obs: the `_on` entry points (pt: the parameter table of a randomised rollout, or None)
+            N.check(lib.tg_fused_rollout_f32_on(C.byref(self.params), pt, C.byref(tr), self._frag.stream.data_ptr(), self._frag.table.data_ptr(),
+                                                self._fused_H, n_hidden, self._f32_block_envs, self._sigma, self.rng.data_ptr(),
+                                                self.group_offset * self.E, t_begin, t_end, self._f32_act, on.table.data_ptr(), on.clip_value, st),
+                    "tg_fused_rollout_f32_on")
+        elif on is not None:
+            N.check(lib.tg_fused_rollout_on(C.byref(self.params), pt, C.byref(tr), self._frag.stream.data_ptr(), self._frag.bias.data_ptr(),
+                                            self._fused_H, n_hidden, self._sigma, self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end,
+                                            on.table.data_ptr(), on.clip_value, st), "tg_fused_rollout_on")
+        elif pt is not None and self._fused_f32:
             N.check(lib.tg_fused_rollout_f32_act_dr(C.byref(self.params), pt, C.byref(tr), self._frag.stream.data_ptr(),
                                                     self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs, self._sigma,
                                                     self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end, self._f32_act, st),
