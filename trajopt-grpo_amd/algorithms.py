@@ -84,11 +84,30 @@ def device_trajectory(buffer, device) -> DeviceTrajectory:
     return tr
 
 
+class _StepLog:
+    """One float32 row per optimizer step of a learn(), in device blocks of 64 rows: written on the device, read when last_stats asks."""
+    def __init__(self, *width):
+        self.width, self.blocks, self.steps = width, [], 0
+
+    def next_row(self, device) -> torch.Tensor:                             # a [1, *width] view of its block
+        row = self.steps % 64
+        if row == 0:
+            self.blocks.append(torch.empty(64, *self.width, dtype=torch.float32, device=device))
+        self.steps += 1
+        return self.blocks[-1][row:row + 1]
+
+    def rows(self) -> torch.Tensor:
+        return torch.cat(self.blocks)[:self.steps]
+
+
 class _GpuLearner(Algorithm):
     # rows per forward/backward chunk (~8 KiB of activations, masks and dZ per row and net at 256x5 bf16).  One chunk for
     # everything was measured up to 3 % faster and, when the row count grows from one iteration to the next, up to 2x
     # slower (GB-sized blocks outgrow the caching allocator every time); a fixed first chunk keeps the big blocks reusable.
     chunk_rows = 1 << 22
+    # (None until whatever first needs them sets them; class-level, so that every instance reads them plainly)
+    _rollout_stream = _rollout_engine = _old_synced = _sum_rows = None
+    _fold_pending = _differ_table = _count_pending = _count_pinned = None
 
     def _setup(self, policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp=True, max_grad_norm=None):
         self.policy, self.optimizer = policy, optimizer
@@ -97,7 +116,7 @@ class _GpuLearner(Algorithm):
                 raise ValueError(f"max_grad_norm must be None or a finite number > 0, got {max_grad_norm!r}")
             max_grad_norm = float(max_grad_norm)
         self.max_grad_norm = max_grad_norm
-        self._clip_blocks, self._clip_steps = [], 0
+        self._clip_log, self._std_log = _StepLog(2), _StepLog()      # (pre-clip norm | coefficient), sum(log_std): new per learn()
         if chunk_rows is not None:
             self.chunk_rows = int(chunk_rows)
         elif os.environ.get("TG_CHUNK_ROWS"):
@@ -112,6 +131,7 @@ class _GpuLearner(Algorithm):
         self._mlps = {}
         self._ws = M._Workspace()       # per-iteration tensors whose size follows the number of valid rows
         self._stats, self._stats_pending = {}, None
+        self._small_bufs = {}           # ... and those whose size does not (_small)
 
     def learn(self, buffer) -> None:
         """One training iteration on `buffer` (algorithms/grpo.py:50-148, ppo.py:64-186).  The native kernels are
@@ -133,16 +153,15 @@ class _GpuLearner(Algorithm):
                         m._ws.default_cap = max(m._ws.default_cap, cap)
             self._rollout_engine = getattr(getattr(buffer, "rollout_manager", None), "engine", None) if ok else None
             self._check_deferred()
-            self._clip_blocks, self._clip_steps = [], 0
-            self._std_blocks, self._std_steps = [], 0
+            self._clip_log, self._std_log = _StepLog(2), _StepLog()
             obs_count = self._obs_norm_update(buffer)
             self._learn(buffer)
             if obs_count is not None and self._stats_pending is not None:
                 inner0 = self._stats_pending
                 self._stats_pending = lambda: {**inner0(), "obs_count": float(obs_count.item())}
-            if self._clip_steps and self._stats_pending is not None:
-                inner, blocks, steps = self._stats_pending, self._clip_blocks, self._clip_steps
-                self._stats_pending = lambda: {**inner(), "grad_norm": torch.cat(blocks)[:steps, 0].tolist()}
+            if self._clip_log.steps and self._stats_pending is not None:
+                inner, clip_log = self._stats_pending, self._clip_log
+                self._stats_pending = lambda: {**inner(), "grad_norm": clip_log.rows()[:, 0].tolist()}
 
     def _obs_norm_update(self, buffer):
         """normalize_obs: the policy's running statistics take in this rollout's valid observations (one all-reduce across the ranks)
@@ -183,10 +202,8 @@ class _GpuLearner(Algorithm):
         raised in between.  The optimizer steps of that learn() have been applied by then: the error says the weights are suspect, it
         does not roll them back."""
         self._check_row_count()
-        pend = getattr(self, "_fold_pending", None)
-        if pend is not None:
-            self._fold_pending = None
-            host, ev = pend
+        if self._fold_pending is not None:
+            (host, ev), self._fold_pending = self._fold_pending, None
             ev.synchronize()
             if int(host[0]):
                 raise RuntimeError("policy.actor and old_policy.actor held different weights although nothing had written either through "
@@ -199,17 +216,16 @@ class _GpuLearner(Algorithm):
         or when the statistics are): the fold of the old-policy pass relies on version keys, which `.data` writes do not move."""
         a, b = list(self.policy.actor.parameters()), list(self.old_policy.actor.parameters())
         sig = tuple(p.data_ptr() for p in a + b)
-        tab = getattr(self, "_differ_table", None)
-        if tab is None or tab[0] != sig:
+        if self._differ_table is None or self._differ_table[0] != sig:
             rows, first = [], 0
             for p, q in zip(a, b):
                 assert p.shape == q.shape and p.is_contiguous() and q.is_contiguous() and p.dtype == q.dtype == torch.float32
                 rows.append([p.data_ptr(), q.data_ptr(), 0, 0, first])
                 first += p.numel()
             dev = a[0].device
-            self._differ_table = tab = (sig, torch.tensor(rows, dtype=torch.int64).to(dev), len(rows), first,
-                                        torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32).pin_memory())
-        _, table, n, total, flag, host = tab
+            self._differ_table = (sig, torch.tensor(rows, dtype=torch.int64).to(dev), len(rows), first,
+                                  torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32).pin_memory())
+        _, table, n, total, flag, host = self._differ_table
         flag.zero_()
         K.N.check(K.N.load().tg_params_differ(table.data_ptr(), n, total, flag.data_ptr(), K.N.stream_ptr(flag.device)), "tg_params_differ")
         host.copy_(flag, non_blocking=True)
@@ -297,7 +313,7 @@ class _GpuLearner(Algorithm):
     def _old_actor_is_current(self) -> bool:
         """Nothing has written either actor since old_policy <- policy (grpo.py:148): their weights are the same bits, and so are
         their log-probabilities -- the first update's own forward pass can stand in for the old policy's."""
-        return getattr(self, "_old_synced", None) is not None and self._old_synced == self._actor_keys()
+        return self._old_synced is not None and self._old_synced == self._actor_keys()
 
     def sync_old_policy(self) -> None:
         """old_policy <- policy.  The constructors deep-copy the policy BEFORE a checkpoint is loaded into it
@@ -388,11 +404,7 @@ class _GpuLearner(Algorithm):
         flat = self.bucket.flat
         if flat.dtype != torch.float32:
             raise RuntimeError(f"max_grad_norm needs float32 gradients, the bucket holds {flat.dtype}")
-        row = self._clip_steps % 64
-        if row == 0:
-            self._clip_blocks.append(torch.empty(64, 2, dtype=torch.float32, device=flat.device))
-        out2 = self._clip_blocks[-1][row]
-        self._clip_steps += 1
+        out2 = self._clip_log.next_row(flat.device)[0]
         lib = K.N.load()
         work = self._small("clip_work", max(int(lib.tg_grad_clip_workspace(flat.numel())) // 8, 1), torch.float64, flat.device)
         with torch.cuda.device(flat.device):
@@ -409,13 +421,12 @@ class _GpuLearner(Algorithm):
                 self._adam_covers_bucket = all(id(p) in owned for p in self.bucket.params)
         if not self._fused_adam:
             return None
-        extra = [x for x in (getattr(self, "_rollout_stream", None),) if x is not None]
+        extra = [] if self._rollout_stream is None else [self._rollout_stream]
         key = tuple(id(n) for n in nets) + tuple(id(x) for x in extra)
         if self._refresher is None or self._refresher[0] != key:
             self._refresher = (key, O.StreamRefresher(self._fused_adam, [self._mlp(n) for n in nets], extra))
-            eng = getattr(self, "_rollout_engine", None)
-            if extra and eng is not None:
-                eng.entry_refresh = self._refresher[1].run          # the rollout's own entry rebuild: this one gather
+            if extra and self._rollout_engine is not None:
+                self._rollout_engine.entry_refresh = self._refresher[1].run          # the rollout's own entry rebuild: this one gather
         return self._refresher[1]
 
     def _adam_rider(self, net, last, whole_update):
@@ -485,11 +496,9 @@ class _GpuLearner(Algorithm):
     def _check_row_count(self):
         """The flag of the previous learn()'s tg_learn_count, read long after it was written: the valid rows the mask held were not
         the number the rollout's statistic gave the host (a mask edited after sample(), a hand-built trajectory)."""
-        pend = getattr(self, "_count_pending", None)
-        if pend is None:
+        if self._count_pending is None:
             return
-        host, ev, expected = pend
-        self._count_pending = None
+        (host, ev, expected), self._count_pending = self._count_pending, None
         ev.synchronize()
         total = int(host[0])
         if total != expected:
@@ -536,7 +545,7 @@ class _GpuLearner(Algorithm):
             # the rollout's own statistic (on the host without a round trip); the count of the mask itself follows asynchronously and is
             # compared with it at the next learn() entry
             self._check_row_count()
-            if getattr(self, "_count_pinned", None) is None:
+            if self._count_pinned is None:
                 self._count_pinned = torch.empty(2, dtype=torch.int64).pin_memory()
             self._count_pinned.copy_(total, non_blocking=True)
             ev = torch.cuda.Event()
@@ -553,10 +562,9 @@ class _GpuLearner(Algorithm):
 
     def _small(self, name, numel, dtype, device):
         """A cached device buffer whose size does not follow the row count (the row-sized workspace rounds up to a whole chunk)."""
-        cache = self.__dict__.setdefault("_small_bufs", {})
-        t = cache.get(name)
+        t = self._small_bufs.get(name)
         if t is None or t.numel() != numel or t.dtype != dtype or t.device != device:
-            cache[name] = t = torch.empty(numel, dtype=dtype, device=device)
+            self._small_bufs[name] = t = torch.empty(numel, dtype=dtype, device=device)
         return t
 
     # ---- a learned log-std (policies: learn_std=True): the heads read it on the device and leave each row's d loss / d log_std in a
@@ -581,12 +589,7 @@ class _GpuLearner(Algorithm):
 
     def _std_record(self, ls):
         """sum(log_std) BEFORE the coming optimizer step into the next row of this learn()'s [64] blocks (read by last_stats)."""
-        blocks = self._std_blocks
-        row = self._std_steps % 64
-        if row == 0:
-            blocks.append(torch.empty(64, dtype=torch.float32, device=ls.device))
-        torch.sum(ls.detach(), dim=0, keepdim=True, out=blocks[-1][row:row + 1])
-        self._std_steps += 1
+        torch.sum(ls.detach(), dim=0, keepdim=True, out=self._std_log.next_row(ls.device))
 
     def _logp_nograd(self, actor, xin, act, var, out=None):
         if out is None:
@@ -835,7 +838,7 @@ class PPO(_GpuLearner):
         if ls is not None:
             self._std_record(ls)
         # [actor | critic] loss sums: a row of the learn()'s pre-zeroed table when there is one (full batch: one fill per learn(), not per update)
-        both = self._sum_rows.pop() if getattr(self, "_sum_rows", None) else torch.zeros(2, 4, dtype=torch.float64, device=xin.device)
+        both = self._sum_rows.pop() if self._sum_rows else torch.zeros(2, 4, dtype=torch.float64, device=xin.device)
         sums = both[0]
         m_a, m_c = self._mlp(actor), self._mlp(critic)
         fuse = m_a is not None and m_c is not None and m_a.can_fuse_head() and m_c.can_fuse_head()
@@ -1016,7 +1019,7 @@ class PPO(_GpuLearner):
             D.allreduce_sum_(S2, self.process_group, "loss_stats")
             ls = self._learned_std()
             ent = 0.5 * act.shape[1] * (1.0 + math.log(2 * math.pi)) + (0.0 if ls is not None else 0.5 * float(torch.log(var).sum()))
-            std_blocks, std_steps = self._std_blocks, self._std_steps       # (sum log_std before each step, on the device)
+            std_log = self._std_log                                         # (sum log_std before each step, on the device)
             ls_end = ls.detach().clone() if ls is not None else None
             c1, ent_c, kl_c = self.c1, self.entropy, self.kl_coeff
             n_dev = moments[0, 0].clone()                                   # (the buffers above are re-used by the next learn())
@@ -1029,7 +1032,7 @@ class PPO(_GpuLearner):
                 if ls_end is None:
                     ent_out = ent_steps = ent
                 else:                                                       # one entropy per optimizer step, taken before the step
-                    ent_steps = ent + torch.cat(std_blocks)[:std_steps].double()
+                    ent_steps = ent + std_log.rows().double()
                     ent_out = ent_steps.tolist()
                 total = a_loss + c1 * c_loss - ent_c * ent_steps + kl_c * kl
                 out = {"actor_loss": a_loss.tolist(), "critic_loss": c_loss.tolist(), "kl_div": kl.tolist(),

@@ -16,6 +16,11 @@ def _st(t):
     return N.stream_ptr(t.device)
 
 
+def suffixed(base: str, suffix: str, extra):
+    """One optional feature of an entry point: its arguments `extra` (None: off) -> (entry name, those arguments as a tuple)."""
+    return (base, ()) if extra is None else (base + suffix, tuple(extra))
+
+
 def rtg_scan(rew: torch.Tensor, mask: torch.Tensor, gamma: float) -> torch.Tensor:
     """Reward-to-go (algorithms/grpo.py:66-74 == algorithms/ppo.py:100-111).  rew f32 [T][n], mask u8 [T][n]."""
     N.require_cuda(rew, mask)
@@ -116,11 +121,9 @@ def learn_compact(traj, offsets, rows_cap: int, xin: torch.Tensor, ones_col: int
     if moments is not None:
         assert moments.dtype == torch.float64 and moments.is_contiguous() and moments.numel() == 3 * (traj.n // group_size)
     a.d_moments, a.group_size, a.rows_cap = N.ptr(moments), int(group_size), int(rows_cap)
-    if obs_norm is not None:
-        assert obs_norm.table.numel() == 2 * traj.S and obs_norm.table.device == xin.device
-        N.check(N.load().tg_learn_compact_on(C.byref(a), obs_norm.table.data_ptr(), obs_norm.clip_value, _st(xin)), "tg_learn_compact_on")
-        return
-    N.check(N.load().tg_learn_compact(C.byref(a), _st(xin)), "tg_learn_compact")
+    assert obs_norm is None or (obs_norm.table.numel() == 2 * traj.S and obs_norm.table.device == xin.device)
+    name, tail = suffixed("tg_learn_compact", "_on", None if obs_norm is None else (obs_norm.table.data_ptr(), obs_norm.clip_value))
+    N.check(getattr(N.load(), name)(C.byref(a), *tail, _st(xin)), name)
 
 
 def obs_moments(traj, center: torch.Tensor, out: torch.Tensor = None, work: torch.Tensor = None) -> torch.Tensor:
@@ -184,18 +187,7 @@ def ppo_returns(rew, values, mask, gamma: float, lam: float, monte_carlo: bool, 
                 work: torch.Tensor = None) -> torch.Tensor:
     """tg_ppo_returns: fills adv / ret f32 [T][n] (ppo.py:100-124) and returns the f64 [2][3] masked moments {count, sum, sum of
     squares} of the advantages and of the returns -- bit-identical to rtg_scan / `rtg - values` / gae_scan + masked_moments(group = n)."""
-    N.require_cuda(rew, values, mask, adv, ret, work)
-    T, n = rew.shape
-    for t in (rew, values, adv, ret):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == T * n
-    assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == T * n
-    if work is None:
-        work = torch.empty(6 * n, dtype=torch.float64, device=rew.device)
-    assert work.dtype == torch.float64 and work.numel() >= 6 * n
-    moments = torch.empty(2, 3, dtype=torch.float64, device=rew.device)
-    N.check(N.load().tg_ppo_returns(rew.data_ptr(), values.data_ptr(), mask.data_ptr(), float(gamma), float(lam), 1 if monte_carlo else 0,
-                                    adv.data_ptr(), ret.data_ptr(), n, T, moments.data_ptr(), work.data_ptr(), _st(rew)), "tg_ppo_returns")
-    return moments
+    return ppo_returns_boot(rew, values, mask, None, None, gamma, lam, monte_carlo, adv, ret, work)
 
 
 def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: torch.Tensor = None, env_params: torch.Tensor = None):
@@ -217,34 +209,35 @@ def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: tor
     if env_params is not None:
         N.require_cuda(env_params)
         assert env_params.dtype == torch.float64 and env_params.is_contiguous() and tuple(env_params.shape) == (12, traj.n)
-        rc = N.load().tg_rollout_final_state_dr(C.byref(params), env_params.data_ptr(), C.byref(tr), s_final.data_ptr(), timeout.data_ptr(),
-                                                _st(traj.obs))
-    else:
-        rc = N.load().tg_rollout_final_state(C.byref(params), C.byref(tr), s_final.data_ptr(), timeout.data_ptr(), _st(traj.obs))
+    name, table = suffixed("tg_rollout_final_state", "_dr", None if env_params is None else (env_params.data_ptr(),))
+    rc = getattr(N.load(), name)(C.byref(params), *table, C.byref(tr), s_final.data_ptr(), timeout.data_ptr(), _st(traj.obs))
     if rc == N.TG_ERR_UNSUPPORTED:
         raise ValueError(N.load().tg_last_error().decode("utf-8", "replace"))
-    N.check(rc, "tg_rollout_final_state")
+    N.check(rc, name)
     return s_final, timeout
 
 
 def ppo_returns_boot(rew, values, mask, length, boot, gamma: float, lam: float, monte_carlo: bool, adv: torch.Tensor, ret: torch.Tensor,
                      work: torch.Tensor = None) -> torch.Tensor:
     """tg_ppo_returns_boot: ppo_returns() on the rewards with gamma * boot[i] added to the reward of env i's last step
-    (t == length[i] - 1; fp32, each operation rounded on its own) -- `rew` is read, not written.  length i32 [n], boot f32 [n]."""
+    (t == length[i] - 1; fp32, each operation rounded on its own) -- `rew` is read, not written.  length i32 [n], boot f32 [n].
+    (ppo_returns()'s body too: it passes None for both and runs tg_ppo_returns.)"""
     N.require_cuda(rew, values, mask, length, boot, adv, ret, work)
     T, n = rew.shape
     for t in (rew, values, adv, ret):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == T * n
     assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == T * n
-    assert length.dtype == torch.int32 and length.is_contiguous() and length.numel() == n
-    assert boot.dtype == torch.float32 and boot.is_contiguous() and boot.numel() == n
+    assert (length is None) == (boot is None)
+    if boot is not None:
+        assert length.dtype == torch.int32 and length.is_contiguous() and length.numel() == n
+        assert boot.dtype == torch.float32 and boot.is_contiguous() and boot.numel() == n
     if work is None:
         work = torch.empty(6 * n, dtype=torch.float64, device=rew.device)
     assert work.dtype == torch.float64 and work.numel() >= 6 * n
     moments = torch.empty(2, 3, dtype=torch.float64, device=rew.device)
-    N.check(N.load().tg_ppo_returns_boot(rew.data_ptr(), values.data_ptr(), mask.data_ptr(), length.data_ptr(), boot.data_ptr(), float(gamma),
-                                         float(lam), 1 if monte_carlo else 0, adv.data_ptr(), ret.data_ptr(), n, T, moments.data_ptr(),
-                                         work.data_ptr(), _st(rew)), "tg_ppo_returns_boot")
+    name, lb = suffixed("tg_ppo_returns", "_boot", None if boot is None else (length.data_ptr(), boot.data_ptr()))
+    N.check(getattr(N.load(), name)(rew.data_ptr(), values.data_ptr(), mask.data_ptr(), *lb, float(gamma), float(lam), 1 if monte_carlo else 0,
+                                    adv.data_ptr(), ret.data_ptr(), n, T, moments.data_ptr(), work.data_ptr(), _st(rew)), name)
     return moments
 
 
@@ -316,8 +309,7 @@ def surrogate_loss(mean, value, act, logp_old, adv, ret, mask, norm, var, epsilo
         assert value.dtype == torch.float32 and value.is_contiguous() and ret is not None and ret.is_contiguous()
         grad_value = torch.empty_like(value)
         a.d_value, a.d_ret, a.d_grad_value = value.data_ptr(), ret.data_ptr(), grad_value.data_ptr()
-    a.d_mask = N.ptr(mask)
-    a.d_norm = N.ptr(norm)
+    a.d_mask, a.d_norm = N.ptr(mask), N.ptr(norm)
     if coef is not None:
         assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() >= 3 and not want_total
         a.d_coef = coef.data_ptr()
@@ -332,31 +324,39 @@ def surrogate_loss(mean, value, act, logp_old, adv, ret, mask, norm, var, epsilo
     sums = torch.empty(4, dtype=torch.float64, device=mean.device)
     work = torch.empty(4 * N.load().tg_loss_work_blocks(), dtype=torch.float64, device=mean.device)
     a.d_grad_mean, a.d_sums, a.d_work, a.M = grad_mean.data_ptr(), sums.data_ptr(), work.data_ptr(), M
-    use_ref = logp_ref is not None and float(ref_coef) != 0.0
-    if log_std is not None:
-        sd = learned_std(log_std, std_out, M, A)
-        r = None
-        if use_ref:
-            N.require_cuda(logp_ref)
-            assert logp_ref.dtype == torch.float32 and logp_ref.is_contiguous() and logp_ref.numel() == M
-            r = N.RefPenalty()
-            r.d_logp_ref, r.coef = logp_ref.data_ptr(), float(ref_coef)
-        N.check(N.load().tg_surrogate_loss_std(C.byref(a), C.byref(r) if r is not None else None, C.byref(sd), _st(mean)),
-                "tg_surrogate_loss_std")
-        total = ((surr_coef * sums[0] + critic_coef * sums[1] + (-float(ref_coef) if use_ref else kl_coef) * sums[2]).float()
-                 if want_total else None)
-        return total, sums, grad_mean, grad_value
-    if use_ref:
-        N.require_cuda(logp_ref)
-        assert logp_ref.dtype == torch.float32 and logp_ref.is_contiguous() and logp_ref.numel() == M
-        r = N.RefPenalty()
-        r.d_logp_ref, r.coef = logp_ref.data_ptr(), float(ref_coef)
-        N.check(N.load().tg_surrogate_loss_ref(C.byref(a), C.byref(r), _st(mean)), "tg_surrogate_loss_ref")
-        total = (surr_coef * sums[0] + critic_coef * sums[1] - float(ref_coef) * sums[2]).float() if want_total else None
-        return total, sums, grad_mean, grad_value
-    N.check(N.load().tg_surrogate_loss(C.byref(a), _st(mean)), "tg_surrogate_loss")
-    total = (surr_coef * sums[0] + critic_coef * sums[1] + kl_coef * sums[2]).float() if want_total else None
+    ref = ref_penalty(logp_ref, ref_coef, M)
+    sd = learned_std(log_std, std_out, M, A) if log_std is not None else None
+    name, tail = head_entry("tg_surrogate_loss", ref, sd)
+    N.check(getattr(N.load(), name)(C.byref(a), *tail, _st(mean)), name)
+    total = ((surr_coef * sums[0] + critic_coef * sums[1] + (kl_coef if ref is None else -float(ref_coef)) * sums[2]).float()
+             if want_total else None)
     return total, sums, grad_mean, grad_value
+
+
+def ref_penalty(logp_ref: torch.Tensor, coef: float, rows: int) -> "N.RefPenalty":
+    """N.RefPenalty for the `_ref` entry points (logp_ref device f32 [rows]), or None: no reference policy, or a zero coefficient."""
+    if logp_ref is None or float(coef) == 0.0:
+        return None
+    N.require_cuda(logp_ref)
+    assert logp_ref.dtype == torch.float32 and logp_ref.is_contiguous() and logp_ref.numel() == rows
+    r = N.RefPenalty()
+    r.d_logp_ref, r.coef = logp_ref.data_ptr(), float(coef)
+    return r
+
+
+def head_entry(base: str, ref, std, act=None):
+    """(entry name, tail arguments) of a loss head, stand-alone or inside an MLP chain.  ref / std: N.RefPenalty / N.LearnedStd or None;
+    act: the hidden activation (TG_ACT_*) of a family whose kernels take one (the fp32 chain learner), else None.
+        std          -> base_std, or base_act_std   (ref or NULL, std[, act])
+        act != ReLU  -> base_act                    (ref or NULL, act)
+        ref          -> base_ref                    (ref,)
+        none of them -> base                        ()"""
+    rp = None if ref is None else C.byref(ref)
+    if std is not None:
+        return (base + "_std", (rp, C.byref(std))) if act is None else (base + "_act_std", (rp, C.byref(std), act))
+    if act not in (None, N.TG_ACT_RELU):
+        return base + "_act", (rp, act)
+    return suffixed(base, "_ref", None if ref is None else (rp,))
 
 
 def learned_std(log_std: torch.Tensor, out: torch.Tensor, rows: int, act_dim: int) -> "N.LearnedStd":

@@ -32,6 +32,7 @@ import logging
 import torch
 
 from . import _native as N
+from . import hip_ops as K
 
 _ROW_BLOCK = 8192
 
@@ -77,15 +78,37 @@ def _ref_penalty(kind, rows, logp_ref, ref_coef, kl_coef):
     """N.RefPenalty for forward_loss(logp_ref=..., ref_coef=...), or None: no penalty (the plain entry points)."""
     if logp_ref is None or float(ref_coef) == 0.0:
         return None
-    N.require_cuda(logp_ref)
     if kind != 0:
         raise ValueError("the reference-policy penalty is a term of the actor's loss (kind 0)")
     if float(kl_coef) != 0.0:
         raise ValueError("kl_coef must be 0 beside the reference-policy penalty: both use the KL sum")
-    assert logp_ref.dtype == torch.float32 and logp_ref.is_contiguous() and logp_ref.numel() == rows
-    r = N.RefPenalty()
-    r.d_logp_ref, r.coef = logp_ref.data_ptr(), float(ref_coef)
-    return r
+    return K.ref_penalty(logp_ref, ref_coef, rows)
+
+
+# The training heads' four machines: the entry that runs forward + loss head (+ backward data), and whether it takes the hidden
+# activation.  K.head_entry() appends the suffix of whatever optional arguments a call carries.
+_LOSS_ENTRIES = {"bf16": ("tg_mlp_forward_chain_loss", False), "f32": ("tg_mlp_f32_forward_backward", True),
+                 "f32w": ("tg_mlp_f32w_forward_backward", False), "f32r": ("tg_mlp_f32r_forward_backward", False)}
+
+
+def loss_entry(machine: str, act: int, ref, std):
+    """(entry name, tail arguments, the profiled kernel's trailing template arguments) of forward_loss() on `machine` (a key of
+    _LOSS_ENTRIES) with hidden activation `act` (TG_ACT_*), reference penalty `ref` and learned log-std `std` (structs or None)."""
+    base, takes_act = _LOSS_ENTRIES[machine]
+    assert takes_act or act == N.TG_ACT_RELU, f"{base}: ReLU only"
+    name, tail = K.head_entry(base, ref, std, act if takes_act else None)
+    if machine == "bf16":
+        targs = (",true,true" if ref else ",false,true") if std else (",true" if ref else "")
+    else:
+        targs = (",true" if ref is not None else (",false" if act else "")) + (f",{act}>" if act else ">")
+    return name, tail, targs
+
+
+def forward_entry(machine: str, act: int):
+    """(entry name, tail arguments) of the fp32 learners' no-grad forward pass (machine: "f32", "f32w" or "f32r")."""
+    base = _LOSS_ENTRIES[machine][0].replace("_forward_backward", "_forward")
+    assert machine != "bf16" and (machine == "f32" or act == N.TG_ACT_RELU), f"{base}: ReLU only"
+    return K.suffixed(base, "_act", None if act == N.TG_ACT_RELU else (act,))
 
 
 def lin_ok(l) -> bool:
@@ -414,18 +437,12 @@ class GemmMLP:
             f = self._f32
             assert xp.dtype == torch.float32 and xp.is_contiguous() and xp.shape[1] == f.in_pad
             out = torch.empty(xp.shape[0], 4, dtype=torch.float32, device=xp.device)
-            if f.res:
-                N.check(N.load().tg_mlp_f32r_forward(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.w0.data_ptr(), f.table.data_ptr(), f.H, f.n_hidden,
-                                                     f.out_dim, xp.shape[0], out.data_ptr(), N.stream_ptr(xp.device)), "tg_mlp_f32r_forward")
-            elif f.wide:
-                N.check(N.load().tg_mlp_f32w_forward(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.table.data_ptr(), f.n_hidden, xp.shape[0],
-                                                     out.data_ptr(), N.stream_ptr(xp.device)), "tg_mlp_f32w_forward")
-            elif f.act != 0:
-                N.check(N.load().tg_mlp_f32_forward_act(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.H, f.n_hidden, xp.shape[0],
-                                                        out.data_ptr(), f.act, N.stream_ptr(xp.device)), "tg_mlp_f32_forward_act")
-            else:
-                N.check(N.load().tg_mlp_f32_forward(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.H, f.n_hidden, xp.shape[0],
-                                                    out.data_ptr(), N.stream_ptr(xp.device)), "tg_mlp_f32_forward")
+            # (common: input, its padding, weight stream; then what each machine's weights and shape need; then rows, output)
+            shape = ((f.w0.data_ptr(), f.table.data_ptr(), f.H, f.n_hidden, f.out_dim) if f.res else
+                     (f.table.data_ptr(), f.n_hidden) if f.wide else (f.H, f.n_hidden))
+            name, tail = forward_entry(f.machine, f.act)
+            N.check(getattr(N.load(), name)(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), *shape, xp.shape[0], out.data_ptr(), *tail,
+                                            N.stream_ptr(xp.device)), name)
             self._acts = self._bits = None
             return out if padded else out[:, :self.out_dim].contiguous()
         if self._chain is not None and xp.shape[0] > 0:
@@ -508,8 +525,7 @@ class GemmMLP:
         if log_std is not None:
             if kind != 0:
                 raise ValueError("the learned log-std is a term of the actor's loss (kind 0)")
-            from .hip_ops import learned_std
-            std = learned_std(log_std, std_out, xp.shape[0], self.out_dim)
+            std = K.learned_std(log_std, std_out, xp.shape[0], self.out_dim)
         if self._f32 is not None:
             return self._forward_loss_f32(xp, kind, act, logp_old, adv, ret, norm, var, epsilon, surr_coef, critic_coef, kl_coef, sums_out,
                                           logp_old_out, norm8, ref, std)
@@ -533,28 +549,19 @@ class GemmMLP:
         a.d_dout8, a.d_head_slabs, a.d_work, a.d_bias_partial = dz_head.data_ptr(), slabs.data_ptr(), work.data_ptr(), bpart.data_ptr()
         ptrs = (N.C.c_void_p * (L - 1))(*[N.ptr(t) or None for t in hid])
         mptrs = (N.C.c_void_p * (L - 1))(*[t.data_ptr() for t in bits])
+        name, tail, targs = loss_entry("bf16", N.TG_ACT_RELU, ref, std)
         ev = None
         if self.fwd_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        if std is not None:
-            N.check(lib.tg_mlp_forward_chain_loss_std(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1,
-                                                      rows, ptrs, mptrs, N.C.byref(a), N.C.byref(ref) if ref is not None else None,
-                                                      N.C.byref(std), N.stream_ptr(dev)), "tg_mlp_forward_chain_loss_std")
-        elif ref is None:
-            N.check(lib.tg_mlp_forward_chain_loss(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1,
-                                                  rows, ptrs, mptrs, N.C.byref(a), N.stream_ptr(dev)), "tg_mlp_forward_chain_loss")
-        else:
-            N.check(lib.tg_mlp_forward_chain_loss_ref(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1,
-                                                      rows, ptrs, mptrs, N.C.byref(a), N.C.byref(ref), N.stream_ptr(dev)),
-                    "tg_mlp_forward_chain_loss_ref")
+        N.check(getattr(lib, name)(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1, rows, ptrs, mptrs,
+                                   N.C.byref(a), *tail, N.stream_ptr(dev)), name)
         if ev is not None:
             ev[1].record()
             stored = sum(1 for t in hid if t is not None)
             per_row = (2 * self.in_pad + stored * 2 * H + (L - 1) * (H // 8) + 16 + (4 * self.out_dim + 8 if kind == 0 else 4) + (4 if ref else 0)
                        + (16 if std else 0))
-            tail = (",true,true" if ref else ",false,true") if std else (",true" if ref else "")
-            self.fwd_events.append((ev[0], ev[1], rows, per_row, f"tg::mlp_fwd_chain_kernel<{H},8,true,4,false,true{tail}>"))
+            self.fwd_events.append((ev[0], ev[1], rows, per_row, f"tg::mlp_fwd_chain_kernel<{H},8,true,4,false,true{targs}>"))
         grid = min(nblk, -(-rows // 256))
         lin = self.linears[-1]
         # the head's partial weight / bias gradients (rows >= 4 of a slab are never written) and -- with sums_out -- the loss sums are
@@ -643,51 +650,17 @@ class GemmMLP:
         a.d_dout8, a.d_work = dout.data_ptr(), self._head_ws.data_ptr()
         ptrs = (N.C.c_void_p * nh)(*[N.ptr(t) for t in acts])
         zptrs = (N.C.c_void_p * nh)(*[N.ptr(t) for t in dzs])
+        if f.act != N.TG_ACT_RELU:          # Tanh: everything stored, no mask bits
+            assert tmask is None and all(t is not None for t in acts + dzs)
+        # (common: input, its padding, weight stream; then what each machine's weights and shape need; then rows and the buffers)
+        shape = (f.w0.data_ptr(), f.table.data_ptr(), H, nh) if f.res else (f.table.data_ptr(), nh) if f.wide else (H, nh)
+        name, tail, targs = loss_entry(f.machine, f.act, ref, std)
         ev = None
         if self.fwd_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        if std is not None:                 # the policy's learned log-std: the `_std` entries (a nullable reference penalty beside it)
-            rp = N.C.byref(ref) if ref is not None else None
-            if f.act != 0:
-                assert tmask is None and all(t is not None for t in acts + dzs)
-            if f.res:
-                N.check(lib.tg_mlp_f32r_forward_backward_std(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.w0.data_ptr(), f.table.data_ptr(), H,
-                                                             nh, rows, ptrs, zptrs, N.ptr(tmask), N.C.byref(a), rp, N.C.byref(std),
-                                                             N.stream_ptr(dev)), "tg_mlp_f32r_forward_backward_std")
-            elif f.wide:
-                N.check(lib.tg_mlp_f32w_forward_backward_std(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.table.data_ptr(), nh, rows, ptrs,
-                                                             zptrs, N.C.byref(a), rp, N.C.byref(std), N.stream_ptr(dev)),
-                        "tg_mlp_f32w_forward_backward_std")
-            else:
-                N.check(lib.tg_mlp_f32_forward_backward_act_std(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), H, nh, rows, ptrs, zptrs,
-                                                                N.ptr(tmask), N.C.byref(a), rp, N.C.byref(std), f.act, N.stream_ptr(dev)),
-                        "tg_mlp_f32_forward_backward_act_std")
-        elif f.act != 0:                    # Tanh: the `_act` entry (plain head or reference penalty); everything stored, no mask bits
-            assert tmask is None and all(t is not None for t in acts + dzs)
-            N.check(lib.tg_mlp_f32_forward_backward_act(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), H, nh, rows, ptrs, zptrs, None,
-                                                        N.C.byref(a), N.C.byref(ref) if ref is not None else None, f.act,
-                                                        N.stream_ptr(dev)), "tg_mlp_f32_forward_backward_act")
-        elif ref is not None:               # (the same launches with GRPO's reference-policy penalty in the head)
-            if f.res:
-                N.check(lib.tg_mlp_f32r_forward_backward_ref(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.w0.data_ptr(), f.table.data_ptr(), H,
-                                                             nh, rows, ptrs, zptrs, N.ptr(tmask), N.C.byref(a), N.C.byref(ref), N.stream_ptr(dev)),
-                        "tg_mlp_f32r_forward_backward_ref")
-            elif f.wide:
-                N.check(lib.tg_mlp_f32w_forward_backward_ref(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.table.data_ptr(), nh, rows, ptrs,
-                                                             zptrs, N.C.byref(a), N.C.byref(ref), N.stream_ptr(dev)), "tg_mlp_f32w_forward_backward_ref")
-            else:
-                N.check(lib.tg_mlp_f32_forward_backward_ref(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), H, nh, rows, ptrs, zptrs, N.ptr(tmask),
-                                                            N.C.byref(a), N.C.byref(ref), N.stream_ptr(dev)), "tg_mlp_f32_forward_backward_ref")
-        elif f.res:
-            N.check(lib.tg_mlp_f32r_forward_backward(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.w0.data_ptr(), f.table.data_ptr(), H, nh, rows,
-                                                     ptrs, zptrs, N.ptr(tmask), N.C.byref(a), N.stream_ptr(dev)), "tg_mlp_f32r_forward_backward")
-        elif f.wide:
-            N.check(lib.tg_mlp_f32w_forward_backward(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), f.table.data_ptr(), nh, rows, ptrs, zptrs,
-                                                     N.C.byref(a), N.stream_ptr(dev)), "tg_mlp_f32w_forward_backward")
-        else:
-            N.check(lib.tg_mlp_f32_forward_backward(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), H, nh, rows, ptrs, zptrs, N.ptr(tmask),
-                                                    N.C.byref(a), N.stream_ptr(dev)), "tg_mlp_f32_forward_backward")
+        N.check(getattr(lib, name)(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), *shape, rows, ptrs, zptrs, *(() if f.wide else (N.ptr(tmask),)),
+                                   N.C.byref(a), *tail, N.stream_ptr(dev)), name)
         if ev is not None:
             ev[1].record()
             # matrix-core flops per row: first layer + forward and backward products of the H x H layers (head: vector unit)
@@ -695,8 +668,7 @@ class GemmMLP:
             self.fwd_events.append((ev[0], ev[1], rows, 2 * H * self.in_dim + 4 * (nh - 1) * H * H + 4 * H * self.out_dim,
                                     ("tg::mlp_f32_wide_kernel<true" if f.wide else
                                      (f"tg::mlp_f32_res_kernel<{H},{f.in_pad // 4},true" if f.res else f"tg::mlp_f32_chain_kernel<{H},true"))
-                                    + (",true" if ref is not None else (",false" if f.act else ""))
-                                    + (f",{f.act}>" if f.act else ">")))
+                                    + targs))
         grid = lib.tg_mlp_f32r_grid(rows) if f.res else min(nblk, -(-rows // (64 if f.wide else 256)))      # (the launchers' own grids)
         self._acts, self._bits, self._dz_head, self._tmask = [xp] + acts, dzs, dout, tmask
         assert getattr(self, "_loss_rider", None) is None, "forward_loss(sums_out=...) must be followed by backward_fused()"
@@ -1255,7 +1227,7 @@ class F32ResStream:
               W_1[16 t + 4 g + e][16 ko + i]            (nothing with one hidden layer)
       w0:     [8 mo][in_pad / 4 steps s][64 lanes]: W0[16 mo + i][4 s + g]              (zero beyond the inputs)
       table:  [2][128] hidden biases | [4][128] head weights (rows >= A zero) | [4] head bias | 12 zeros"""
-    wide, res, act = False, True, 0                 # (act: TG_ACT_RELU -- the resident kernel is ReLU-only)
+    wide, res, act, machine = False, True, 0, "f32r"        # (act: TG_ACT_RELU -- the resident kernel is ReLU-only)
 
     def __init__(self, net):
         lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
@@ -1339,7 +1311,7 @@ class F32WideStream:
       forward, layer l = 1 .. nh - 1, block mo, piece t:  W_l[16 mo + i][16 t + 4 g + e]
       backward, layer l = nh - 1 .. 1, block ko, piece t: W_l[16 t + 4 g + e][16 ko + i]
     then the tables: [5][256] hidden biases | [4][256] head weights (rows >= A zero) | [4] head bias | 12 zeros."""
-    wide, res, act = True, False, 0                 # (act: TG_ACT_RELU -- the H = 256 kernel is ReLU-only)
+    wide, res, act, machine = True, False, 0, "f32w"        # (act: TG_ACT_RELU -- the H = 256 kernel is ReLU-only)
 
     def __init__(self, net):
         lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
@@ -1398,7 +1370,7 @@ class F32WideStream:
 
 
 class F32ChainStream:
-    wide, res = False, False
+    wide, res, machine = False, False, "f32"
 
     """The fp32 weight stream of the chain learner, refreshed from the master weights with ONE gather:
       [first layer, MFMA fragment order: H/32 tiles x k2/4 groups x 64 lanes x 4]  lane (i, kk), step s = 4 g + e of tile mo holds

@@ -87,6 +87,27 @@ class DeviceTrajectory:
         return obs, act, rew, ln, mask
 
 
+def fused_entry(f32: bool, act: int, ptab, obs_norm):
+    """(entry name, arguments after the env parameters, tail arguments) of the persistent rollout launch.  f32: the fp32 kernel
+    (its entries beyond the plain one take the hidden activation `act`, TG_ACT_*); ptab: the per-env parameter table's address or
+    None; obs_norm: (table address, clip value) or None.  `_on` takes the table, NULL when the rollout is not randomised."""
+    base = "tg_fused_rollout_f32" if f32 else "tg_fused_rollout"
+    act_arg = (act,) if f32 else ()
+    if obs_norm is not None:
+        return base + "_on", (ptab,), act_arg + tuple(obs_norm)
+    if ptab is not None:
+        return base + ("_act_dr" if f32 else "_dr"), (ptab,), act_arg
+    if f32 and act != N.TG_ACT_RELU:
+        return base + "_act", (), act_arg
+    return base, (), ()
+
+
+def step_entry(forced: bool, ptab):
+    """(entry name, arguments after the env parameters) of a per-step launch (tg_rollout_step) or of the one-launch teacher-forced
+    replay (tg_rollout_forced): `_dr` with the per-env parameter table of a randomised rollout."""
+    return K.suffixed("tg_rollout_forced" if forced else "tg_rollout_step", "_dr", None if ptab is None else (ptab,))
+
+
 class DeviceRollout:
     """Runs `num_groups x episodes_per_group` episodes of `env` under `policy` on one GPU.
 
@@ -305,45 +326,18 @@ class DeviceRollout:
             if hook is None or not hasattr(self._frag, "segments") or not hook():
                 self._frag.refresh()
         n_hidden = len(self._linears) - 1
+        on = getattr(self.policy, "obs_norm", None)
+        name, table, tail = fused_entry(self._fused_f32, self._f32_act, None if self.env_params is None else self.env_params.data_ptr(),
+                                        None if on is None else (on.table.data_ptr(), on.clip_value))
+        # (the fp32 kernel reads biases and head from a table and takes its envs per workgroup; the bf16 kernel reads a bias stream)
+        weights = ((self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs) if self._fused_f32 else
+                   (self._frag.bias.data_ptr(), self._fused_H, n_hidden))
         ev = None
         if self.step_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        pt = None if self.env_params is None else self.env_params.data_ptr()
-        on = getattr(self.policy, "obs_norm", None)
-        if on is not None and self._fused_f32:
-            # normalize_obs: the `_on` entry points (pt: the parameter table of a randomised rollout, or None)
-            N.check(lib.tg_fused_rollout_f32_on(C.byref(self.params), pt, C.byref(tr), self._frag.stream.data_ptr(), self._frag.table.data_ptr(),
-                                                self._fused_H, n_hidden, self._f32_block_envs, self._sigma, self.rng.data_ptr(),
-                                                self.group_offset * self.E, t_begin, t_end, self._f32_act, on.table.data_ptr(), on.clip_value, st),
-                    "tg_fused_rollout_f32_on")
-        elif on is not None:
-            N.check(lib.tg_fused_rollout_on(C.byref(self.params), pt, C.byref(tr), self._frag.stream.data_ptr(), self._frag.bias.data_ptr(),
-                                            self._fused_H, n_hidden, self._sigma, self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end,
-                                            on.table.data_ptr(), on.clip_value, st), "tg_fused_rollout_on")
-        elif pt is not None and self._fused_f32:
-            N.check(lib.tg_fused_rollout_f32_act_dr(C.byref(self.params), pt, C.byref(tr), self._frag.stream.data_ptr(),
-                                                    self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs, self._sigma,
-                                                    self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end, self._f32_act, st),
-                    "tg_fused_rollout_f32_act_dr")
-        elif pt is not None:
-            N.check(lib.tg_fused_rollout_dr(C.byref(self.params), pt, C.byref(tr), self._frag.stream.data_ptr(),
-                                            self._frag.bias.data_ptr(), self._fused_H, n_hidden, self._sigma, self.rng.data_ptr(),
-                                            self.group_offset * self.E, t_begin, t_end, st), "tg_fused_rollout_dr")
-        elif self._fused_f32 and self._f32_act != N.TG_ACT_RELU:
-            N.check(lib.tg_fused_rollout_f32_act(C.byref(self.params), C.byref(tr), self._frag.stream.data_ptr(),
-                                                 self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs, self._sigma,
-                                                 self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end, self._f32_act, st),
-                    "tg_fused_rollout_f32_act")
-        elif self._fused_f32:
-            N.check(lib.tg_fused_rollout_f32(C.byref(self.params), C.byref(tr), self._frag.stream.data_ptr(),
-                                             self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs, self._sigma,
-                                             self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end, st),
-                    "tg_fused_rollout_f32")
-        else:
-            N.check(lib.tg_fused_rollout(C.byref(self.params), C.byref(tr), self._frag.stream.data_ptr(),
-                                         self._frag.bias.data_ptr(), self._fused_H, n_hidden, self._sigma, self.rng.data_ptr(),
-                                         self.group_offset * self.E, t_begin, t_end, st), "tg_fused_rollout")
+        N.check(getattr(lib, name)(C.byref(self.params), *table, C.byref(tr), self._frag.stream.data_ptr(), *weights, self._sigma,
+                                   self.rng.data_ptr(), self.group_offset * self.E, t_begin, t_end, *tail, st), name)
         if ev is not None:
             ev[1].record()
             self.step_events.append((None, ev[0], ev[1]))
@@ -355,53 +349,36 @@ class DeviceRollout:
                 "tg_rollout_finish_stats")
         self.traj.stats_fresh = True
 
+    def _launch_step(self, t, tr, st, *args):
+        """One tg_rollout_step launch for time step t -- t None: the whole teacher-forced replay in one tg_rollout_forced launch --
+        (`_dr`: a randomised rollout), bracketed by timing events when step_events is a list."""
+        name, table = step_entry(t is None, None if self.env_params is None else self.env_params.data_ptr())
+        ev = None
+        if self.step_events is not None:
+            ev = N.event_pair()
+            ev[0].record()
+        N.check(getattr(self.lib, name)(C.byref(self.params), *table, C.byref(tr), *args, st), name)
+        if ev is not None:
+            ev[1].record()
+            self.step_events.append((t, ev[0], ev[1]))
+
     def _enqueue_steps(self, sample: bool, entry: bool = False):
-        lib, tr, st = self.lib, self.traj.native(), N.stream_ptr(self.device)
-        p = C.byref(self.params)
-        pt = None if self.env_params is None else self.env_params.data_ptr()      # randomised: the `_dr` entry points
+        tr, st = self.traj.native(), N.stream_ptr(self.device)
+        env_offset = self.group_offset * self.E
         if sample:
             self._refresh_weights(entry)
         elif not self.forced_per_step:
             # teacher-forced replay: every time step in ONE launch, the state in registers between steps (tg_rollout_forced;
             # bit-identical to T launches of tg_rollout_step)
-            ev = None
-            if self.step_events is not None:
-                ev = N.event_pair()
-                ev[0].record()
-            if pt is not None:
-                N.check(lib.tg_rollout_forced_dr(p, pt, C.byref(tr), 0, self.T, st), "tg_rollout_forced_dr")
-            else:
-                N.check(lib.tg_rollout_forced(p, C.byref(tr), 0, self.T, st), "tg_rollout_forced")
-            if ev is not None:
-                ev[1].record()
-                self.step_events.append((None, ev[0], ev[1]))
+            self._launch_step(None, tr, st, 0, self.T)
             self._enqueue_finish(tr, st)
             return
-        env_offset = self.group_offset * self.E
         for t in range(self.T):
-            ev = None
             if sample:
                 mean = self._actor_mean(t)
-                if self.step_events is not None:
-                    ev = N.event_pair()
-                    ev[0].record()
-                if pt is not None:
-                    N.check(lib.tg_rollout_step_dr(p, pt, C.byref(tr), t, mean.data_ptr(), mean.stride(0), self._sigma,
-                                                   self.rng.data_ptr(), env_offset, st), "tg_rollout_step_dr")
-                else:
-                    N.check(lib.tg_rollout_step(p, C.byref(tr), t, mean.data_ptr(), mean.stride(0), self._sigma,
-                                                self.rng.data_ptr(), env_offset, st), "tg_rollout_step")
+                self._launch_step(t, tr, st, t, mean.data_ptr(), mean.stride(0), self._sigma, self.rng.data_ptr(), env_offset)
             else:
-                if self.step_events is not None:
-                    ev = N.event_pair()
-                    ev[0].record()
-                if pt is not None:
-                    N.check(lib.tg_rollout_step_dr(p, pt, C.byref(tr), t, None, 0, None, None, env_offset, st), "tg_rollout_step_dr")
-                else:
-                    N.check(lib.tg_rollout_step(p, C.byref(tr), t, None, 0, None, None, env_offset, st), "tg_rollout_step")
-            if ev is not None:
-                ev[1].record()
-                self.step_events.append((t, ev[0], ev[1]))
+                self._launch_step(t, tr, st, t, None, 0, None, None, env_offset)
         self._enqueue_finish(tr, st)
 
     # ---- hipGraph replay of the whole T-step loop ---------------------------------------------
