@@ -263,7 +263,10 @@ int  tg_fused_rollout_f32_act_dr(const tg_env_params* p, const double* d_ptab, c
 int  tg_rtg_scan(const float* d_rew, const uint8_t* d_mask, float gamma, float* d_rtg,
                  int64_t n, int32_t T, void* stream);
 
-/* GAE branch (ppo.py:112-124): adv and ret = values + adv */
+/* GAE branch (ppo.py:112-124): adv and ret = values + adv.
+ * The coefficient of A[t+1] is rn_mul(gamma, lam) of the two floats passed in.  The reference's `gamma * lam * adv` rounds the
+ * DOUBLE product once to fp32: the same number for most pairs (every shipped one), one ulp apart for e.g. (0.995, 0.97) --
+ * 0.96515006 here against 0.96515.  Where the two agree the scan is the reference's bit for bit. */
 int  tg_gae_scan(const float* d_rew, const float* d_values, const uint8_t* d_mask, float gamma,
                  float lam, float* d_adv, float* d_ret, int64_t n, int32_t T, void* stream);
 

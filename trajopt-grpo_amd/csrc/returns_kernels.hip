@@ -44,6 +44,8 @@ __global__ __launch_bounds__(256) void rtg_scan_kernel(const float* __restrict__
 
 // GAE, ppo.py:112-124:  delta_t = r_t + gamma V_{t+1} m_{t+1} - V_t   (UNMASKED r_t),
 // A_t = delta_t + gamma lam A_{t+1} m_{t+1};  ret = V + A.
+// The coefficient is rn_mul(gamma, lam) of the two fp32 arguments; the reference rounds the double product once.  Same fp32 number
+// for most pairs, one ulp apart for e.g. (0.995, 0.97): 0.96515006 here, 0.96515 there.
 __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__ rew, const float* __restrict__ val,
                                                        const uint8_t* __restrict__ mask, float gamma, float lam,
                                                        float* __restrict__ adv, float* __restrict__ ret, int64_t n,
