@@ -844,6 +844,28 @@ int  tg_ppo_norm(const double* d_moments, double c1, double kl_coeff, float* d_n
 int  tg_gather_rows2(const int64_t* d_idx, int64_t rows, const float* d_src0, float* d_dst0, const float* d_src1, float* d_dst1,
                      void* stream);
 
+/* ---- Running value normalisation (policies: normalize_value=True; PPO) ----
+ * The policy owns {count, mean, m2} f64 [1] each (m2 = sum of squared deviations of every return merged so far) and a derived f32
+ * table [4] = {(float)mean, (float)sigma, (float)(1 / sigma), 0}, sigma = sqrt(m2 / count + eps) in f64 (count == 0: {0, 1, 1, 0}).
+ * The critic predicts (R - mean) / sigma; wherever its output enters a return it is denormalised first, v * table[1] + table[0],
+ * in fp32 with the multiply and the add each rounded on its own (no FMA).  The tables are read on the device.
+ * tg_scatter_rows_affine: tg_scatter_rows with d_dst[d_idx[r]] = d_src[r * src_stride] * d_table[1] + d_table[0]; entries no row
+ *   points at are not written (the zeroed grid stays 0 there).
+ * tg_boot_values_affine: the bootstrap rows, d_out[i] = (d_v[i * v_stride] * d_table[1] + d_table[0]) * (float)d_timeout[i] for
+ *   i < n in one launch -- the product torch.mul(v, timeout) forms, with the denormalisation in front (d_timeout u8 [n]).
+ * tg_value_norm_merge: Chan's merge of d_moments3 f64 [3] = {n_b, sum, sum of squares} of a batch of returns (the second row of
+ *   tg_ppo_returns' d_moments, all-reduced; batch variance max(s2 - s1 * (s1 / n_b), 0)) into d_count / d_mean / d_m2, and the
+ *   table rewritten IN PLACE; one single-threaded launch, f64 operations rounded one by one, IEEE divide and sqrt.
+ *   d_moments3 == NULL (or n_b == 0): the statistics keep their bits, only the table is rewritten.  d_norm8 != NULL: entries 2 and
+ *   3 of tg_ppo_norm's f32 [8] become d_table[0] and d_table[2] (the critic's regression target is then (R - mean) / sigma of the
+ *   merged statistics); launch it after tg_ppo_norm, and after the last scatter that reads the table, on the same stream. */
+int  tg_scatter_rows_affine(const float* d_src, int64_t src_stride, const int64_t* d_idx, int64_t rows, const float* d_table,
+                            float* d_dst, void* stream);
+int  tg_boot_values_affine(const float* d_v, int64_t v_stride, const uint8_t* d_timeout, int64_t n, const float* d_table, float* d_out,
+                           void* stream);
+int  tg_value_norm_merge(const double* d_moments3, double eps, double* d_count, double* d_mean, double* d_m2, float* d_table,
+                         float* d_norm8, void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

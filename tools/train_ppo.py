@@ -2,12 +2,16 @@
 """End-to-end learning check: PPO with the reference factories' hyper-parameters but 4,096 parallel episodes per
 epoch instead of 50-80.
 
-    python3 tools/train_ppo.py [epochs] [CartPole|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
+    python3 tools/train_ppo.py [epochs] [CartPole|Pendulum|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
+                               [--learn-std] [--normalize-obs] [--normalize-value] [--gae]
+
+--normalize-value: running value normalisation (policy.value_norm): the critic regresses onto returns standardised with running
+statistics and is denormalised wherever it enters a return.  --gae: monte_carlo=False (GAE(gamma, 0.95) advantages).
 
 --randomize (repeatable): per-env domain randomisation, e.g. `--randomize mass=0.8:1.25 --randomize tether_length=0.5:2` -- every
 env slot draws its own factor on that physical parameter in every rollout (Env.randomize).
 
-CartPole / QuadPole2D (pipelines/cartpole_pipeline_ppo.py, quadpole2d_pipeline_ppo.py): 128x3 actor-critic, cov 0.5,
+CartPole / QuadPole2D (pipelines/cartpole_pipeline_ppo.py, quadpole2d_pipeline_ppo.py; Pendulum takes the same): 128x3 actor-critic, cov 0.5,
 eps 0.2, gamma 0.99, 24 full-batch updates, Adam 2e-4 (published curves: -37 -> ~800 and -70 -> ~1047).
 QuadPole (quadpole_pipeline_ppo.py): 256x5, cov 0.3, gamma 0.999, 32 updates, Adam 3e-4, bf16 policy compute."""
 import os
@@ -45,6 +49,9 @@ def main():
     sys.argv = [a for a in sys.argv if a != "--learn-std"]
     normalize_obs = "--normalize-obs" in sys.argv                 # running observation normalisation (policy.obs_norm)
     sys.argv = [a for a in sys.argv if a != "--normalize-obs"]
+    normalize_value = "--normalize-value" in sys.argv             # running value normalisation (policy.value_norm)
+    gae = "--gae" in sys.argv                                     # monte_carlo=False
+    sys.argv = [a for a in sys.argv if a not in ("--normalize-value", "--gae")]
     epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 120
     name = sys.argv[2] if len(sys.argv) > 2 else "CartPole"
     dev = torch.device("cuda", 0)
@@ -54,19 +61,20 @@ def main():
         if len(sys.argv) > 3 and sys.argv[3] == "fp32":          # the reference's own precision: the H = 256 fp32 chain learner
             cdt = None
     else:
-        S, A = (5, 1) if name == "CartPole" else (10, 2)
+        S, A = {"CartPole": (5, 1), "Pendulum": (3, 1)}.get(name, (10, 2))
         hidden, cov, lr, upd, gamma, cdt = (128, 128, 128), 0.5, 2e-4, 24, 0.99, None
         if len(sys.argv) > 3 and sys.argv[3] == "bf16":          # bf16 policy compute: fused bf16 rollout + chain kernels at H = 128
             cdt = torch.bfloat16
     pol = tg.GaussianActorCritic_NeuralNetwork(S, A, hidden, cov=cov, device=dev, **({"learn_std": True} if learn_std else {}),
-                                               **({"normalize_obs": True} if normalize_obs else {}))
+                                               **({"normalize_obs": True} if normalize_obs else {}),
+                                               **({"normalize_value": True} if normalize_value else {}))
     tg.environments.ENV_CLASSES[name]().randomize(ranges)         # (refuses a bad name or range before anything is allocated)
     mgr = tg.RolloutManager(lambda: tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, num_workers=64, num_episodes_per_worker=64,
                             seed=0, compute_dtype=cdt)
     buf = tg.Rollout_Buffer(mgr)
     algo = tg.PPO(epsilon=0.2, policy=pol, optimizer=torch.optim.Adam(pol.parameters(), lr=lr), ref_model=None,
                   updates_per_iter=upd, c1=0.5, kl_coeff=0.5, gamma=gamma, lam=0.95, entropy=0.01, batch_size=None,
-                  autocast_dtype=cdt)
+                  autocast_dtype=cdt, **({"monte_carlo": False} if gae else {}))
     t0 = time.time()
     for ep in range(epochs):
         buf.sample()
@@ -75,7 +83,9 @@ def main():
             print(f"epoch {ep:4d}  avg return {float(buf.avg_reward[-1]):9.2f}  mean len {float(buf.device_traj.len.float().mean()):6.1f}  "
                   f"elapsed {time.time() - t0:6.1f}s"
                   + (f"  log_std {[round(v, 4) for v in algo.last_stats['log_std']]}" if learn_std else "")
-                  + (f"  obs_count {algo.last_stats['obs_count']:.0f}" if normalize_obs else ""), flush=True)
+                  + (f"  obs_count {algo.last_stats['obs_count']:.0f}" if normalize_obs else "")
+                  + (f"  value mean {algo.last_stats['value_mean']:.2f} std {algo.last_stats['value_std']:.2f}"
+                     f" ev {algo.last_stats['explained_variance']:.3f}" if normalize_value else ""), flush=True)
     print("first -> last:", float(buf.avg_reward[0]), "->", float(buf.avg_reward[-1]), " max", float(max(buf.avg_reward)))
 
 

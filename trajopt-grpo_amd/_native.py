@@ -259,6 +259,9 @@ SIGNATURES = {
     "tg_ppo_returns_boot": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _I64, _I32, _VP, _VP, _VP]),
     "tg_ppo_norm": (C.c_int, [_VP, C.c_double, C.c_double, _VP, _VP]),
     "tg_gather_rows2": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _VP]),
+    "tg_scatter_rows_affine": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _VP]),
+    "tg_boot_values_affine": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _VP]),
+    "tg_value_norm_merge": (C.c_int, [_VP, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),

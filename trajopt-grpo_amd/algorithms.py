@@ -286,21 +286,26 @@ class _GpuLearner(Algorithm):
 
     @staticmethod
     def _weights_state(pol) -> dict:
-        """pol.state_dict() without the observation statistics: old_policy SHARES the policy's obs_norm object, there is nothing to copy."""
-        return {k: v for k, v in pol.state_dict().items() if k not in P.OBS_NORM_KEYS}
+        """pol.state_dict() without the observation / return statistics: old_policy SHARES the policy's obs_norm and value_norm objects,
+        there is nothing to copy."""
+        return {k: v for k, v in pol.state_dict().items() if k not in P.OBS_NORM_KEYS and k not in P.VALUE_NORM_KEYS}
 
     def _load_old(self, weights) -> None:
         """old_policy.load_state_dict(weights) past its check that statistics come with a normalised policy (they are shared)."""
-        on, self.old_policy.obs_norm = self.old_policy.obs_norm, None
+        old = self.old_policy
+        on, vn = old.obs_norm, getattr(old, "value_norm", None)
+        old.obs_norm = old.value_norm = None
         try:
-            self.old_policy.load_state_dict(weights)
+            old.load_state_dict(weights)
         finally:
-            self.old_policy.obs_norm = on
+            old.obs_norm, old.value_norm = on, vn
 
     def _make_old_policy(self):
-        """A deep copy of the policy (grpo.py:48, ppo.py:62) that reads states through the policy's own obs_norm object."""
+        """A deep copy of the policy (grpo.py:48, ppo.py:62) that reads states through the policy's own obs_norm object (and values
+        through its value_norm object)."""
         old = copy.deepcopy(self.policy)
         old.obs_norm = getattr(self.policy, "obs_norm", None)
+        old.value_norm = getattr(self.policy, "value_norm", None)
         return old
 
     def _actor_keys(self):
@@ -790,6 +795,19 @@ class GRPO(_GpuLearner):
                 "updates_per_iter": self.updates_per_iter, **self._clip_metadata()}
 
 
+def _value_norm_stats(stat3, moments, eps) -> dict:
+    """last_stats' entries of a value-normalised PPO.learn(), from device copies of its {count, mean, m2} after the merge and of the
+    all-reduced moments [2][3] = {n, sum, sum of squares} of the valid advantages and returns.  value_std is the table's sigma,
+    sqrt(m2 / count + eps) (1 while count == 0); explained_variance = 1 - var(adv) / var(ret) with population variances
+    (s2 - s1 (s1 / n)) / n clamped at 0 -- adv = ret - V on the valid rows in both modes -- and NaN when var(ret) == 0."""
+    count, mean, m2 = stat3.tolist()
+    (na, a1, a2), (nr, r1, r2) = moments.tolist()
+    var_a = max(a2 - a1 * (a1 / na), 0.0) / na if na > 0 else float("nan")
+    var_r = max(r2 - r1 * (r1 / nr), 0.0) / nr if nr > 0 else float("nan")
+    return {"value_mean": mean if count > 0 else 0.0, "value_std": math.sqrt(m2 / count + eps) if count > 0 else 1.0, "value_count": count,
+            "explained_variance": 1.0 - var_a / var_r if var_r > 0 else float("nan")}
+
+
 class PPO(_GpuLearner):
     """Proximal Policy Optimization.  algorithms/ppo.py:8-225.
 
@@ -801,7 +819,13 @@ class PPO(_GpuLearner):
     advantages are those of the rewards with gamma * V(s_final) added to the episode's last step, Monte Carlo and GAE alike, computed
     on the device in the prologue; the trajectory's rewards are not modified.  last_stats gains "n_bootstrapped" (episodes
     bootstrapped, over all ranks).  Needs the buffer's rollout engine (the env parameters); swarm envs are refused.  False: the
-    launches of a learner without the keyword."""
+    launches of a learner without the keyword.
+
+    A policy built with normalize_value=True (policy.value_norm; INTEGRATION.md, "Value normalisation"): the critic predicts returns
+    standardised with RUNNING statistics.  Every critic value that enters a return -- the valid rows on the [T][n] grid, the bootstrap
+    rows -- is denormalised on the device with the table as it stands at the entry of learn(); the returns' all-reduced moments are
+    merged into the statistics (unless frozen) and the critic regresses onto (R - mean) / sigma of the merged statistics, in place of
+    the batch's own mean and std.  last_stats gains "value_mean", "value_std", "value_count", "explained_variance".  GRPO ignores it."""
 
     def __init__(self, epsilon: float, policy, optimizer, ref_model, updates_per_iter: int, c1: float = 0.5,
                  kl_coeff: float = 0.5, gamma: float = 0.99, lam: float = 0.95, entropy: float = 0.01,
@@ -913,6 +937,9 @@ class PPO(_GpuLearner):
             v = m_c.forward(xin, keep=False, padded=True)[:, 0]
         else:
             v = self._forward(critic, s_final if on is None else on.normalize(s_final)).reshape(-1)
+        vn = getattr(self.policy, "value_norm", None)
+        if vn is not None:                                  # (V(s_final) in the returns' units: the table of this learn()'s entry)
+            return K.boot_values_affine(v, timeout, vn.table, out=self._small("boot_value", n, torch.float32, dev)), timeout
         return torch.mul(v, timeout, out=self._small("boot_value", n, torch.float32, dev)), timeout
 
     def _learn(self, buffer) -> None:
@@ -952,12 +979,17 @@ class PPO(_GpuLearner):
             idx, X, act = self._gather_valid(traj)
             xin = self._prep(actor, X, cap)
         n_rows = xin.shape[0]
+        # normalize_value: the critic's outputs are denormalised where they enter a return -- with the statistics the critic was last
+        # trained against (the table as it stands here; the identity on the first call) -- and the table moves only after that
+        vn = getattr(self.policy, "value_norm", None)
+        if vn is not None and (not vn.table.is_cuda or vn.table.device != dev):
+            raise ValueError(f"policy.value_norm lives on {vn.table.device}, the trajectory on {dev}")
         # ppo.py:93: V of the valid rows (padded rows are masked in both scans), scattered onto the [T][n] grid by the launch that
         # follows each chunk's no-grad pass
         for lo in range(0, n_rows, self.chunk_rows):
             hi = min(lo + self.chunk_rows, n_rows)
             out = m_c.forward(xin[lo:hi], keep=False, padded=True) if m_c is not None else self._forward(critic, xin[lo:hi])
-            K.scatter_rows(out, idx[lo:hi], V)
+            K.scatter_rows(out, idx[lo:hi], V, table=None if vn is None else vn.table)
         # ppo.py:100-124 + the masked moments of :138-139 in two launches; the ranks' sums in one all-reduce; the normalisation
         # constants and 1 / n on the device (tg_ppo_norm): nothing of this visits the host
         n_boot = None
@@ -972,6 +1004,12 @@ class PPO(_GpuLearner):
         D.allreduce_sum_(moments, self.process_group, "ppo_moments")
         norm8 = K.ppo_norm(moments, self.c1, self.kl_coeff, out=self._small("norm8", 8, torch.float32, dev))
         self.norm8 = norm8                                                  # (diagnostics: this learn()'s constants, on the device)
+        vn_stats = None
+        if vn is not None:
+            # the returns' moments (row 1, all-reduced above: no collective of its own) into the running statistics, the table in
+            # place, and the critic's target constants norm8[2:4] <- {mean, 1 / sigma} of the merged statistics: one launch
+            vn._merge(None if vn.frozen else moments[1], norm8)
+            vn_stats = (torch.cat([vn.count, vn.mean, vn.m2]), moments.clone(), vn.eps)      # (copies: read when last_stats is)
         adv = self._ws.get("row0", n_rows, 1, torch.float32, dev, cap).view(-1)
         ret = self._ws.get("row1", n_rows, 1, torch.float32, dev, cap).view(-1)
         K.gather_rows2(idx, adv_full, adv, ret_full, ret)
@@ -1041,6 +1079,8 @@ class PPO(_GpuLearner):
                     out["log_std"] = ls_end.tolist()
                 if n_boot is not None:
                     out["n_bootstrapped"] = int(n_boot.item())
+                if vn_stats is not None:
+                    out.update(_value_norm_stats(*vn_stats))
                 return out
             self._stats_pending = stats
 

@@ -22,6 +22,9 @@
 //                        running observation normalisation: the per-feature f64 moments of a trajectory's valid entries in a
 //                        fixed order, Chan's merge into {count, mean, m2} and the f32 table {mean, rstd}, and the normalised
 //                        input rows -- from an SoA slot or row-major rows, or inside the compaction pass.
+//   tg_scatter_rows_affine / tg_boot_values_affine / tg_value_norm_merge
+//                        running value normalisation (policies.ValueNorm): the critic's values denormalised where they enter a
+//                        return, and Chan's merge of the returns' all-reduced moments into {count, mean, m2} and the f32 table.
 #include "tg_common.hpp"
 
 namespace tg {
@@ -484,6 +487,61 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restri
         dst[idx[r]] = src[r * stride];
 }
 
+// tg_scatter_rows with the value denormalised on the way: dst[idx[r]] = src[r * stride] * table[1] + table[0], multiply and add each
+// rounded on its own (no FMA), table = ValueNorm's f32 [4] {mean, sigma, 1 / sigma, 0} read on the device
+__global__ __launch_bounds__(256) void scatter_rows_affine_kernel(const float* __restrict__ src, int64_t stride, const int64_t* __restrict__ idx,
+                                                                  int64_t rows, const float* __restrict__ table, float* __restrict__ dst) {
+    const float mean = table[0], sigma = table[1];
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x)
+        dst[idx[r]] = rn_add(rn_mul(src[r * stride], sigma), mean);
+}
+
+// the bootstrap rows of a value-normalised critic: out[i] = (v[i * stride] * table[1] + table[0]) * (float)timeout[i] -- the product
+// `torch.mul(v, timeout)` forms, with the denormalisation in front; three separately rounded fp32 operations
+__global__ __launch_bounds__(256) void boot_values_affine_kernel(const float* __restrict__ v, int64_t stride, const uint8_t* __restrict__ timeout,
+                                                                 int64_t n, const float* __restrict__ table, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = rn_mul(rn_add(rn_mul(v[i * stride], table[1]), table[0]), (float)timeout[i]);
+}
+
+// Chan's merge of one batch of returns {n_b, sum, sum of squares} into the running {count, mean, m2} (m2: sum of squared deviations),
+// every f64 operation rounded on its own, IEEE divide and sqrt; then the f32 table {(float)mean, (float)sigma, (float)(1 / sigma), 0}
+// with sigma = sqrt(m2 / count + eps) rewritten in place (count == 0: {0, 1, 1, 0}) and, when given, entries 2 and 3 of tg_ppo_norm's
+// f32 [8] overwritten with table[0] and table[2].  moments == NULL or n_b == 0: the statistics keep their bits.  Single-threaded.
+__global__ void value_norm_merge_kernel(const double* __restrict__ moments, double eps, double* __restrict__ count, double* __restrict__ mean,
+                                        double* __restrict__ m2, float* __restrict__ table, float* __restrict__ norm8) {
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double n = count[0], mu = mean[0], q = m2[0];
+    const double nb = moments ? moments[0] : 0.0;
+    if (nb > 0.0) {
+        const double s1 = moments[1], s2 = moments[2], na = n;
+        const double mb = s1 / nb;                           // the batch's mean
+        const double m2b = s2 - s1 * mb;                     // its squared deviations from that mean
+        n = na + nb;
+        const double w = nb / n;
+        const double db = mb - mu;
+        mu = mu + db * w;
+        q = (q + (m2b > 0.0 ? m2b : 0.0)) + (db * db) * (na * w);
+        count[0] = n;
+        mean[0] = mu;
+        m2[0] = q;
+    }
+    float t0 = 0.0f, t1 = 1.0f, t2 = 1.0f;
+    if (n > 0.0) {
+        const double sigma = sqrt(q / n + eps);
+        t0 = (float)mu;
+        t1 = (float)sigma;
+        t2 = (float)(1.0 / sigma);
+    }
+    table[0] = t0; table[1] = t1; table[2] = t2; table[3] = 0.0f;
+    if (norm8) {
+        norm8[2] = t0;
+        norm8[3] = t2;
+    }
+}
+
 // dst0[r] = src0[idx[r]], dst1[r] = src1[idx[r]]: `adv[mask]`, `returns[mask]` (ppo.py:126-135) in one launch
 __global__ __launch_bounds__(256) void gather_rows2_kernel(const int64_t* __restrict__ idx, int64_t rows, const float* __restrict__ src0,
                                                            float* __restrict__ dst0, const float* __restrict__ src1, float* __restrict__ dst1) {
@@ -645,6 +703,39 @@ int tg_scatter_rows(const float* d_src, int64_t src_stride, const int64_t* d_idx
     const unsigned grid = (unsigned)(ceil_div(rows, 256) < 4096 ? ceil_div(rows, 256) : 4096);
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_src, src_stride, d_idx, rows, d_dst);
     TG_LAUNCH_CHECK("tg_scatter_rows");
+    return TG_OK;
+}
+
+int tg_scatter_rows_affine(const float* d_src, int64_t src_stride, const int64_t* d_idx, int64_t rows, const float* d_table, float* d_dst,
+                           void* stream) {
+    TG_REQUIRE(rows >= 0 && src_stride >= 1, "tg_scatter_rows_affine: bad sizes");
+    TG_REQUIRE(d_table != nullptr, "tg_scatter_rows_affine: null value-normalisation table");
+    if (rows == 0) return TG_OK;
+    TG_REQUIRE(d_src && d_idx && d_dst, "tg_scatter_rows_affine: null pointer");
+    const unsigned grid = (unsigned)(ceil_div(rows, 256) < 4096 ? ceil_div(rows, 256) : 4096);
+    hipLaunchKernelGGL(scatter_rows_affine_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_src, src_stride, d_idx, rows, d_table, d_dst);
+    TG_LAUNCH_CHECK("tg_scatter_rows_affine");
+    return TG_OK;
+}
+
+int tg_boot_values_affine(const float* d_v, int64_t v_stride, const uint8_t* d_timeout, int64_t n, const float* d_table, float* d_out,
+                          void* stream) {
+    TG_REQUIRE(n >= 0 && v_stride >= 1, "tg_boot_values_affine: bad sizes");
+    TG_REQUIRE(d_table != nullptr, "tg_boot_values_affine: null value-normalisation table");
+    if (n == 0) return TG_OK;
+    TG_REQUIRE(d_v && d_timeout && d_out, "tg_boot_values_affine: null pointer");
+    hipLaunchKernelGGL(boot_values_affine_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, d_v, v_stride, d_timeout, n,
+                       d_table, d_out);
+    TG_LAUNCH_CHECK("tg_boot_values_affine");
+    return TG_OK;
+}
+
+int tg_value_norm_merge(const double* d_moments3, double eps, double* d_count, double* d_mean, double* d_m2, float* d_table, float* d_norm8,
+                        void* stream) {
+    TG_REQUIRE(d_count && d_mean && d_m2 && d_table, "tg_value_norm_merge: null pointer");
+    TG_REQUIRE(eps >= 0.0, "tg_value_norm_merge: eps %g < 0", eps);
+    hipLaunchKernelGGL(value_norm_merge_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_moments3, eps, d_count, d_mean, d_m2, d_table, d_norm8);
+    TG_LAUNCH_CHECK("tg_value_norm_merge");
     return TG_OK;
 }
 

@@ -174,13 +174,46 @@ def obs_normalize_rows(x: torch.Tensor, obs_norm, xin: torch.Tensor, ones_col: i
     return xin
 
 
-def scatter_rows(src: torch.Tensor, idx: torch.Tensor, dst: torch.Tensor) -> None:
-    """dst.view(-1)[idx[r]] = src[r][0] (tg_scatter_rows): src f32 [rows][>= 1] with any row stride, idx int64 [rows], dst f32."""
-    N.require_cuda(src, idx, dst)
+def scatter_rows(src: torch.Tensor, idx: torch.Tensor, dst: torch.Tensor, table: torch.Tensor = None) -> None:
+    """dst.view(-1)[idx[r]] = src[r][0] (tg_scatter_rows): src f32 [rows][>= 1] with any row stride, idx int64 [rows], dst f32.
+    table (a ValueNorm's f32 [4]): tg_scatter_rows_affine -- the value written is src[r][0] * table[1] + table[0], two roundings."""
+    N.require_cuda(src, idx, dst, table)
     rows = idx.numel()
     assert src.dtype == dst.dtype == torch.float32 and idx.dtype == torch.int64 and idx.is_contiguous() and dst.is_contiguous()
     assert src.dim() == 2 and src.shape[0] >= rows
-    N.check(N.load().tg_scatter_rows(src.data_ptr(), src.stride(0), idx.data_ptr(), rows, dst.data_ptr(), _st(dst)), "tg_scatter_rows")
+    assert table is None or (table.dtype == torch.float32 and table.is_contiguous() and table.numel() == 4 and table.device == dst.device)
+    name, tab = suffixed("tg_scatter_rows", "_affine", None if table is None else (table.data_ptr(),))
+    N.check(getattr(N.load(), name)(src.data_ptr(), src.stride(0), idx.data_ptr(), rows, *tab, dst.data_ptr(), _st(dst)), name)
+
+
+def boot_values_affine(v: torch.Tensor, timeout: torch.Tensor, table: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """tg_boot_values_affine: out[i] = (v[i] * table[1] + table[0]) * timeout[i], each fp32 operation rounded on its own.  v f32 [n]
+    with any stride, timeout u8 [n], table a ValueNorm's f32 [4]."""
+    N.require_cuda(v, timeout, table, out)
+    n = timeout.numel()
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=v.device)
+    assert v.dtype == out.dtype == torch.float32 and v.dim() == 1 and v.numel() == n and out.is_contiguous() and out.numel() == n
+    assert timeout.dtype == torch.uint8 and timeout.is_contiguous()
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.numel() == 4
+    N.check(N.load().tg_boot_values_affine(v.data_ptr(), max(v.stride(0), 1), timeout.data_ptr(), n, table.data_ptr(), out.data_ptr(), _st(out)),
+            "tg_boot_values_affine")
+    return out
+
+
+def value_norm_merge(moments3, eps: float, count: torch.Tensor, mean: torch.Tensor, m2: torch.Tensor, table: torch.Tensor,
+                     norm8: torch.Tensor = None) -> None:
+    """tg_value_norm_merge: Chan's merge of moments3 f64 [3] = {n, sum, sum of squares} of a batch of returns (None: nothing to
+    merge) into count / mean / m2 f64 [1], the f32 table [4] rewritten in place, and -- norm8 given -- entries 2 and 3 of tg_ppo_norm's
+    f32 [8] overwritten with table[0] and table[2]."""
+    N.require_cuda(moments3, count, mean, m2, table, norm8)
+    for t in (count, mean, m2):
+        assert t.dtype == torch.float64 and t.numel() == 1
+    assert moments3 is None or (moments3.dtype == torch.float64 and moments3.is_contiguous() and moments3.numel() == 3)
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.numel() == 4
+    assert norm8 is None or (norm8.dtype == torch.float32 and norm8.is_contiguous() and norm8.numel() == 8)
+    N.check(N.load().tg_value_norm_merge(N.ptr(moments3), float(eps), count.data_ptr(), mean.data_ptr(), m2.data_ptr(), table.data_ptr(),
+                                         N.ptr(norm8), _st(table)), "tg_value_norm_merge")
 
 
 def ppo_returns(rew, values, mask, gamma: float, lam: float, monte_carlo: bool, adv: torch.Tensor, ret: torch.Tensor,

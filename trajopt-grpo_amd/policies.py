@@ -9,6 +9,8 @@ same checkpoint formats (`policy.pt`: bare actor state_dict for the actor-only p
 algorithms.py).  The covariance is a diagonal matrix (actor_critic.py:100-103, :247-250): fixed by default, or -- with
 `learn_std=True` -- diag(exp(2 log_std)) of a learned per-dimension `log_std` parameter that the learners train on the device.
 With `normalize_obs=True` every path reads states through running per-feature statistics (`policy.obs_norm`, class ObsNorm).
+With `normalize_value=True` (actor-critic only) the critic predicts returns standardised with running statistics
+(`policy.value_norm`, class ValueNorm); `policy.value()` keeps returning returns.
 """
 from __future__ import annotations
 
@@ -160,6 +162,119 @@ class ObsNorm:
 OBS_NORM_KEYS = ("obs_norm.count", "obs_norm.mean", "obs_norm.m2")
 
 
+class ValueNorm:
+    """Running statistics of the returns a critic is trained on (normalize_value=True; MAPPO's ValueNorm, "PopArt without the Pop":
+    the critic head is NOT rescaled when the statistics move), on the policy's device:
+        count, mean, m2 f64 [1] each (m2: sum of squared deviations; var = m2 / count is the population variance),
+        table f32 [4] = {(float)mean, (float)sigma, (float)(1 / sigma), 0}, sigma = sqrt(m2 / count + eps) in f64 -- ONE allocation for
+        the life of the policy, rewritten in place (count == 0: {0, 1, 1, 0}, the identity).
+    The critic predicts (R - mean) / sigma.  denormalize(v) = v * table[1] + table[0] and normalize(r) = (r - table[0]) * table[2] are
+    fp32 expressions of two separately rounded operations, on the device kernels and here alike.  PPO.learn() denormalises every
+    critic value that enters a return with the table as it stands at its entry, then merges the batch's returns (unless frozen) and
+    regresses the critic onto normalize(R) of the merged statistics.  `eps` is fixed at construction.  A deepcopy of a policy owns
+    its own statistics; the learners make their old_policy share the policy's object."""
+
+    def __init__(self, eps: float, device):
+        self._eps = float(eps)
+        self.frozen = False
+        dev = torch.device(device)
+        self.count = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.mean = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.m2 = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.table = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float32).to(dev)
+
+    @property
+    def eps(self) -> float:
+        return self._eps
+
+    @property
+    def var(self) -> torch.Tensor:
+        return self.m2 / self.count.clamp_min(1.0)
+
+    def freeze(self):
+        self.frozen = True
+        return self
+
+    def unfreeze(self):
+        self.frozen = False
+        return self
+
+    def to(self, device):
+        """Moves the statistics (policy.to): a move is a new allocation on the new device."""
+        dev = torch.device(device)
+        if dev != self.count.device:
+            self.count, self.mean, self.m2, self.table = (t.to(dev) for t in (self.count, self.mean, self.m2, self.table))
+        return self
+
+    @torch.no_grad()
+    def _merge(self, moments=None, norm8=None) -> None:
+        """Chan's merge of moments f64 [3] = {n_b, sum, sum of squares} of a batch of returns into the statistics, then the table in
+        place and -- norm8 given (tg_ppo_norm's f32 [8]) -- its entries 2 and 3 <- table[0], table[2]: tg_value_norm_merge on the
+        device; the same operations in torch for a CPU policy (the host path)."""
+        if self.count.is_cuda:
+            from . import hip_ops as K
+            with torch.cuda.device(self.count.device):
+                K.value_norm_merge(moments, self.eps, self.count, self.mean, self.m2, self.table, norm8)
+            return
+        if moments is not None and float(moments[0]) > 0:
+            na, nb, s1, s2 = self.count[0].clone(), moments[0], moments[1], moments[2]
+            mb = s1 / nb
+            m2b = (s2 - s1 * mb).clamp_min(0.0)
+            n = na + nb
+            w = nb / n
+            db = mb - self.mean[0]
+            self.mean.add_(db * w)
+            self.m2.copy_((self.m2 + m2b) + (db * db) * (na * w))
+            self.count.fill_(float(n))
+        if float(self.count[0]) > 0:
+            sigma = torch.sqrt(self.m2 / self.count + self.eps)
+            self.table[0:1].copy_(self.mean.float())
+            self.table[1:2].copy_(sigma.float())
+            self.table[2:3].copy_((1.0 / sigma).float())
+        else:
+            self.table.copy_(torch.tensor([0.0, 1.0, 1.0, 0.0]))
+        self.table[3] = 0.0
+        if norm8 is not None:
+            norm8[2], norm8[3] = self.table[0], self.table[2]
+
+    @torch.no_grad()
+    def set(self, mean, var, count) -> None:
+        """Statistics from outside (tests, imported normalisers): mean and population variance of `count` returns."""
+        mean, var, count = float(mean), float(var), float(count)
+        if not (math.isfinite(mean) and math.isfinite(var) and var >= 0 and math.isfinite(count) and count >= 0):
+            raise ValueError(f"value_norm.set: a finite mean, a finite var >= 0 and a finite count >= 0, got {mean!r}, {var!r}, {count!r}")
+        self.count.fill_(count)
+        self.mean.fill_(mean)
+        self.m2.copy_(torch.tensor([var], dtype=torch.float64) * count)
+        self._merge(None)
+
+    def denormalize(self, v: torch.Tensor) -> torch.Tensor:
+        """The return a critic output stands for: v * sigma + mean in float32, multiply and add each rounded on its own."""
+        tab = self.table.to(v.device)
+        return v.to(torch.float32) * tab[1] + tab[0]
+
+    def normalize(self, r: torch.Tensor) -> torch.Tensor:
+        """The critic's target for a return: (r - mean) * (1 / sigma) in float32, the loss heads' two operations."""
+        tab = self.table.to(r.device)
+        return (r.to(torch.float32) - tab[0]) * tab[2]
+
+    def state(self) -> dict:
+        return {"value_norm.count": self.count, "value_norm.mean": self.mean, "value_norm.m2": self.m2}
+
+    @torch.no_grad()
+    def load_state(self, count, mean, m2) -> None:
+        count, mean, m2 = (torch.as_tensor(t, dtype=torch.float64).reshape(-1) for t in (count, mean, m2))
+        if count.numel() != 1 or mean.numel() != 1 or m2.numel() != 1:
+            raise ValueError(f"value_norm statistics of shapes {tuple(count.shape)}, {tuple(mean.shape)}, {tuple(m2.shape)}: one number each")
+        self.count.copy_(count)
+        self.mean.copy_(mean)
+        self.m2.copy_(m2)
+        self._merge(None)
+
+
+VALUE_NORM_KEYS = ("value_norm.count", "value_norm.mean", "value_norm.m2")
+
+
 class NeuralNetwork(torch.nn.Module):
     """Sequential(Linear, act, ..., Linear).  models/neural_network.py:4-77
     (parameter names `network.{0,2,...}.{weight,bias}` match the reference checkpoints)."""
@@ -230,6 +345,7 @@ class _GaussianBase(ActorCritic):
         if normalize_obs and input_dim > 64:
             raise ValueError(f"normalize_obs=True supports up to 64 observation features (tg_obs_normalize_rows), got input_dim={input_dim}")
         self.obs_norm = ObsNorm(input_dim, None if obs_clip is None else float(obs_clip), obs_eps, self.device) if normalize_obs else None
+        self.value_norm = None                              # (running value normalisation: the actor-critic's keyword)
 
     # ---- helpers ----------------------------------------------------------
     @staticmethod
@@ -274,6 +390,8 @@ class _GaussianBase(ActorCritic):
             self.log_std.data = self.log_std.data.to(self.device)
         if self.obs_norm is not None:
             self.obs_norm.to(self.device)
+        if self.value_norm is not None:
+            self.value_norm.to(self.device)
         return self
 
     def _with_log_std(self, params):
@@ -365,6 +483,7 @@ class _GaussianBase(ActorCritic):
             "num_parameters": sum(p.numel() for p in self.parameters()),
             **({"learn_std": True} if self.log_std is not None else {}),
             **({"normalize_obs": True, "obs_clip": self.obs_norm.clip} if self.obs_norm is not None else {}),
+            **({"normalize_value": True, "value_eps": self.value_norm.eps} if self.value_norm is not None else {}),
         }
 
 
@@ -405,27 +524,49 @@ class GaussianActorCritic_NeuralNetwork(_GaussianBase):
     has_critic = True
 
     def __init__(self, input_dim, output_dim, hidden_dims, activation="ReLU", cov=0.1, device=None, learn_std=False, *,
-                 normalize_obs=False, obs_clip=10.0, obs_eps=1e-8):
+                 normalize_obs=False, obs_clip=10.0, obs_eps=1e-8, normalize_value=False, value_eps=1e-8):
+        if not isinstance(normalize_value, bool):
+            raise ValueError(f"normalize_value must be True or False, got {normalize_value!r}")
+        if isinstance(value_eps, bool) or not isinstance(value_eps, (int, float)) or not (math.isfinite(value_eps) and value_eps >= 0):
+            raise ValueError(f"value_eps must be a finite number >= 0, got {value_eps!r}")
         super().__init__(input_dim, output_dim, hidden_dims, activation, cov, device, learn_std, normalize_obs=normalize_obs,
                          obs_clip=obs_clip, obs_eps=obs_eps)
         self.critic = NeuralNetwork(input_dim, 1, hidden_dims, activation).to(self.device)
+        # running value normalisation: None when off (the critic then predicts whatever its learner regresses it onto)
+        self.value_norm = ValueNorm(value_eps, self.device) if normalize_value else None
 
     def value(self, state):
-        return self.critic(self._prep_obs(state)).squeeze()               # :313-323
+        v = self.critic(self._prep_obs(state)).squeeze()                  # :313-323
+        return v if self.value_norm is None else self.value_norm.denormalize(v)
 
     def parameters(self):
         return self._with_log_std(list(self.actor.parameters()) + list(self.critic.parameters()))
+
+    def _load_value_norm(self, state_dict) -> None:
+        """load_state_dict's `value_norm.*` entries: they and normalize_value go together, either way round."""
+        have = [k for k in VALUE_NORM_KEYS if k in state_dict]
+        if have and self.value_norm is None:
+            raise ValueError("the state dict holds return statistics ('value_norm.*'), this policy's critic predicts unnormalised "
+                             "targets: construct it with normalize_value=True (or drop the keys)")
+        if self.value_norm is not None:
+            if len(have) != len(VALUE_NORM_KEYS):
+                raise ValueError("this policy normalises its value targets, the state dict holds no 'value_norm.count' / "
+                                 "'value_norm.mean' / 'value_norm.m2': it was saved by a policy without normalize_value=True")
+            self.value_norm.load_state(*(state_dict[k] for k in VALUE_NORM_KEYS))
 
     def state_dict(self):
         sd = {"actor": self.actor.state_dict(), "critic": self.critic.state_dict()}
         if self.log_std is not None:
             sd["log_std"] = self.log_std.data                 # (top level, next to "actor" / "critic")
         sd.update(self._obs_norm_state())
+        if self.value_norm is not None:
+            sd.update(self.value_norm.state())
         return sd
 
     def load_state_dict(self, state_dict):
         self._load_log_std(state_dict.get("log_std"))
         self._load_obs_norm(state_dict)
+        self._load_value_norm(state_dict)
         self.actor.load_state_dict(state_dict["actor"])
         self.critic.load_state_dict(state_dict["critic"])
 
