@@ -866,6 +866,30 @@ int  tg_boot_values_affine(const float* d_v, int64_t v_stride, const uint8_t* d_
 int  tg_value_norm_merge(const double* d_moments3, double eps, double* d_count, double* d_mean, double* d_m2, float* d_table,
                          float* d_norm8, void* stream);
 
+/* ---- Privileged critic (policies: privileged_critic={name: (lo, hi)}; PPO) ----
+ * The critic of an asymmetric actor-critic reads, behind the observation, the physical parameters its env slot was rolled out with
+ * (tg_env_randomize's table), each as a feature on [-1, 1].  tg_privileged_rows forms those input rows from the actor's prepared rows.
+ * Row r of d_dst [rows][dst_pad] (bf16 != 0: bf16, else f32; d_src [rows][src_pad] has the same type; both 16-byte aligned):
+ *   columns [0, S)      the BITS of d_src[r][0 .. S) -- the actor's prepared row, normalised or not;
+ *   column S + k        (float)(((d_ptab[index[k] * n + e] / nominal[k]) - center[k]) * scale[k]), k < count: f64, IEEE divide, every
+ *                       operation rounded on its own (no FMA), rounded once to f32 and, on bf16 rows, once more to bf16 (nearest even);
+ *                       e = d_idx[r] % n (d_idx: tg_learn_compact's flat t * n + e), or e = r when d_idx == NULL (rows <= n);
+ *   the other columns   0, and 1 in ones_col unless it is -1.
+ * Every element of every row is written; d_ptab is the f64 [12][n] table.  Refused (TG_ERR_ARG): a null pointer other than d_idx, count
+ * outside [1, 12], an index outside [0, 12) or listed twice, S < 1, S > src_pad, S + count > dst_pad, ones_col inside [0, S + count) or
+ * >= dst_pad, a pad that is not a multiple of 8 (bf16) / 4 (f32) or above 64, a nominal value that is 0 or not finite, a centre or scale
+ * that is not finite, n <= 0, rows < 0.  rows == 0: TG_OK without a launch. */
+typedef struct tg_privileged_spec {
+    int32_t count;          /* privileged columns, 1..12 */
+    int32_t index[12];      /* p[] index of column k */
+    double  nominal[12];    /* the env's nominal p[index[k]]: the table holds nominal * factor */
+    double  center[12];     /* (lo + hi) / 2 of the factor's range */
+    double  scale[12];      /* 2 / (hi - lo), 0 for hi == lo */
+} tg_privileged_spec;
+int  tg_privileged_rows(const void* d_src, int32_t src_pad, int32_t S, const int64_t* d_idx, int64_t rows, int64_t n,
+                        const double* d_ptab, const tg_privileged_spec* spec, void* d_dst, int32_t dst_pad, int32_t bf16,
+                        int32_t ones_col, void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

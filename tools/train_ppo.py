@@ -3,13 +3,15 @@
 epoch instead of 50-80.
 
     python3 tools/train_ppo.py [epochs] [CartPole|Pendulum|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
-                               [--learn-std] [--normalize-obs] [--normalize-value] [--gae]
+                               [--learn-std] [--normalize-obs] [--normalize-value] [--gae] [--privileged-critic]
 
 --normalize-value: running value normalisation (policy.value_norm): the critic regresses onto returns standardised with running
 statistics and is denormalised wherever it enters a return.  --gae: monte_carlo=False (GAE(gamma, 0.95) advantages).
 
 --randomize (repeatable): per-env domain randomisation, e.g. `--randomize mass=0.8:1.25 --randomize tether_length=0.5:2` -- every
 env slot draws its own factor on that physical parameter in every rollout (Env.randomize).
+--privileged-critic: the critic also reads each env slot's drawn parameters (the policy's privileged_critic takes the --randomize
+ranges); an error without --randomize.
 
 CartPole / QuadPole2D (pipelines/cartpole_pipeline_ppo.py, quadpole2d_pipeline_ppo.py; Pendulum takes the same): 128x3 actor-critic, cov 0.5,
 eps 0.2, gamma 0.99, 24 full-batch updates, Adam 2e-4 (published curves: -37 -> ~800 and -70 -> ~1047).
@@ -51,7 +53,10 @@ def main():
     sys.argv = [a for a in sys.argv if a != "--normalize-obs"]
     normalize_value = "--normalize-value" in sys.argv             # running value normalisation (policy.value_norm)
     gae = "--gae" in sys.argv                                     # monte_carlo=False
-    sys.argv = [a for a in sys.argv if a not in ("--normalize-value", "--gae")]
+    privileged = "--privileged-critic" in sys.argv                # an asymmetric actor-critic: the critic reads the drawn parameters
+    sys.argv = [a for a in sys.argv if a not in ("--normalize-value", "--gae", "--privileged-critic")]
+    if privileged and not ranges:
+        raise SystemExit("--privileged-critic needs at least one --randomize name=lo:hi: the critic reads the randomised parameters")
     epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 120
     name = sys.argv[2] if len(sys.argv) > 2 else "CartPole"
     dev = torch.device("cuda", 0)
@@ -67,7 +72,8 @@ def main():
             cdt = torch.bfloat16
     pol = tg.GaussianActorCritic_NeuralNetwork(S, A, hidden, cov=cov, device=dev, **({"learn_std": True} if learn_std else {}),
                                                **({"normalize_obs": True} if normalize_obs else {}),
-                                               **({"normalize_value": True} if normalize_value else {}))
+                                               **({"normalize_value": True} if normalize_value else {}),
+                                               **({"privileged_critic": ranges} if privileged else {}))
     tg.environments.ENV_CLASSES[name]().randomize(ranges)         # (refuses a bad name or range before anything is allocated)
     mgr = tg.RolloutManager(lambda: tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, num_workers=64, num_episodes_per_worker=64,
                             seed=0, compute_dtype=cdt)

@@ -115,6 +115,13 @@ class RandomizeSpec(C.Structure):
     _fields_ = [("count", C.c_int32), ("index", C.c_int32 * 12), ("lo", C.c_double * 12), ("hi", C.c_double * 12), ("seed", C.c_uint64)]
 
 
+class PrivilegedSpec(C.Structure):
+    """tg_privileged_spec (include/trajopt_grpo_hip.h): which p[] entries tg_privileged_rows turns into critic input columns, in column
+    order, with the env's nominal values and the centre and scale of each factor range."""
+    _fields_ = [("count", C.c_int32), ("index", C.c_int32 * 12), ("nominal", C.c_double * 12), ("center", C.c_double * 12),
+                ("scale", C.c_double * 12)]
+
+
 class CompactArgs(C.Structure):
     """tg_compact_args (include/trajopt_grpo_hip.h)."""
     _fields_ = [("d_mask", C.c_void_p), ("d_offsets", C.c_void_p), ("n", C.c_int64), ("T", C.c_int32), ("S", C.c_int32), ("A", C.c_int32),
@@ -262,6 +269,7 @@ SIGNATURES = {
     "tg_scatter_rows_affine": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _VP]),
     "tg_boot_values_affine": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _VP]),
     "tg_value_norm_merge": (C.c_int, [_VP, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tg_privileged_rows": (C.c_int, [_VP, _I32, _I32, _VP, _I64, _I64, _VP, _P(PrivilegedSpec), _VP, _I32, _I32, _I32, _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),

@@ -808,8 +808,33 @@ def _value_norm_stats(stat3, moments, eps) -> dict:
             "explained_variance": 1.0 - var_a / var_r if var_r > 0 else float("nan")}
 
 
+def privileged_spec(policy, env, params=None) -> "K.N.PrivilegedSpec":
+    """tg_privileged_spec of a policy's privileged_critic for `env`: column k is the mapping's k-th name (the mapping's order, not
+    p[]'s), index[k] its p[] slot (env.RANDOMIZABLE), nominal[k] the env's own value there (params: its tg_env_params, default
+    env.native_params()), centre and scale the policy's.  ValueError names a parameter the env does not have."""
+    want = policy.privileged_critic
+    unknown = [name for name in want if name not in env.RANDOMIZABLE]
+    if unknown:
+        raise ValueError(f"privileged_critic names {unknown}, which {type(env).__name__} cannot randomise "
+                         f"(randomisable: {', '.join(env.RANDOMIZABLE)})")
+    if params is None:
+        params = env.native_params()
+    spec = K.N.PrivilegedSpec()
+    spec.count = len(want)
+    for k, name in enumerate(want):
+        spec.index[k] = env.RANDOMIZABLE[name]
+        spec.nominal[k] = float(params.p[spec.index[k]])
+        spec.center[k], spec.scale[k] = policy.privileged_center[k], policy.privileged_scale[k]
+    return spec
+
+
 class PPO(_GpuLearner):
     """Proximal Policy Optimization.  algorithms/ppo.py:8-225.
+
+    A policy built with privileged_critic={name: (lo, hi)} ("Privileged critic"): the critic also reads the physical
+    parameters each env slot was rolled out with (Env.randomize with the same mapping; the buffer's rollout engine holds the table).
+    The actor's rows are prepared as always; one tg_privileged_rows launch forms the critic's rows from them, and the two nets keep
+    their own learners and input pads.  A plain policy: not one launch, allocation or entry point more.
 
     max_grad_norm: as GRPO's -- one norm over the actor's and the critic's gradients together (one optimizer), before every optimizer
     step (every minibatch's in minibatch mode); last_stats gains "grad_norm", one entry per step.
@@ -846,13 +871,16 @@ class PPO(_GpuLearner):
         # None = torch.randperm on the device from `seed` (the reference draws torch.randperm on the CPU, ppo.py:148)
         self.permutation_fn = None
 
-    def _step(self, xin, act, adv, ret, old_logp, norm8, var, sums_out, host=None, last=True, write_old=False):
-        """One optimizer step on the given rows (all local rows, or one minibatch).  norm8: the device f32 [8] of tg_ppo_norm -- the
+    def _step(self, xin, act, adv, ret, old_logp, norm8, var, sums_out, host=None, last=True, write_old=False, xin_c=None):
+        """One optimizer step on the given rows (all local rows, or one minibatch).  xin_c: the critic's own input rows (a privileged
+        critic), None: the critic reads `xin`.  norm8: the device f32 [8] of tg_ppo_norm -- the
         normalisation constants of ppo.py:138-139 and the 1 / n of :165-179, read by the loss heads on the device.  host: minibatch
         mode only -- (the four normalisation constants as a list, this step's global row count): the 1 / n of a minibatch is its own.
         write_old: this is the first step of a full-batch learn() on a chain learner -- its forward pass WRITES `old_logp` (ppo.py:142-143
         takes the old log-probabilities from the current policy: the same numbers) instead of reading it."""
         actor, critic = self.policy.actor, self.policy.critic
+        if xin_c is None:
+            xin_c = xin
         self._zero_grads()
         ls = self._learned_std()
         # the entropy bonus (ppo.py:172,179): H = A/2 (1 + log 2 pi) + sum log_std, so -entropy * mean(H) adds exactly -entropy to every
@@ -883,12 +911,12 @@ class PPO(_GpuLearner):
                     self._std_reduce(ls, std_rows, ent_add)
                     ent_add = 0.0
                 m_a.backward_fused()
-                m_c.forward_loss(xin[lo:hi], 1, ret=ret[lo:hi], norm=nh[2:4] if host else None, critic_coef=coefs[1], sums_out=both[1],
+                m_c.forward_loss(xin_c[lo:hi], 1, ret=ret[lo:hi], norm=nh[2:4] if host else None, critic_coef=coefs[1], sums_out=both[1],
                                  norm8=dev8)
                 m_c.backward_fused()
                 continue
             mean = self._forward(actor, xin[lo:hi], train=True, view=True)         # the loss kernel takes a row stride
-            vout = self._forward(critic, xin[lo:hi], train=True)
+            vout = self._forward(critic, xin_c[lo:hi], train=True)
             value = vout.reshape(-1).contiguous()
             _, s, g_mean, g_val = K.surrogate_loss(mean.detach(), value.detach(), act[lo:hi], old_logp[lo:hi], adv[lo:hi],
                                                    ret[lo:hi], None, norm8[:4], var, self.epsilon, coefs[0], coefs[1], coefs[2],
@@ -905,6 +933,55 @@ class PPO(_GpuLearner):
         self.bucket.allreduce(self.process_group)                            # one RCCL all-reduce / step
         self._optimizer_step(actor, critic, last=last)
         sums_out.append(both)
+
+    # ---- a privileged critic (policies: privileged_critic={name: (lo, hi)}): the critic's input rows are the actor's prepared rows with
+    # the env slot's randomised parameters behind them (tg_privileged_rows); every critic pass reads those rows, every actor pass its own
+    def _privileged_setup(self, buffer, traj):
+        """None for a plain policy (nothing below is touched); else (tg_privileged_spec, the parameter table f64 [12][n] of the rollout
+        that filled `buffer`), after checking that the env draws exactly the parameters and ranges the critic was built for."""
+        want = getattr(self.policy, "privileged_critic", None)
+        if want is None:
+            return None
+        engine = getattr(getattr(buffer, "rollout_manager", None), "engine", None)
+        if engine is None or getattr(engine, "params", None) is None:
+            raise ValueError("a policy with privileged_critic reads each env slot's parameters from buffer.rollout_manager.engine.env_params: "
+                             "this buffer has no rollout engine (hand-built tensors?)")
+        have = engine.env.randomization
+        if have != want:
+            raise ValueError(f"the policy's privileged_critic {want} is not the env's randomisation {have}: "
+                             f"{type(engine.env).__name__}.randomize() must draw exactly the parameters and ranges the critic was built for")
+        table = engine.env_params
+        if (not torch.is_tensor(table) or table.dtype != torch.float64 or tuple(table.shape) != (12, traj.n) or not table.is_contiguous()
+                or table.device != traj.mask.device):
+            raise ValueError(f"privileged_critic needs engine.env_params as a contiguous f64 [12][{traj.n}] table on {traj.mask.device} (the "
+                             f"rollout's own), got {None if table is None else (table.dtype, tuple(table.shape), table.device)}")
+        return privileged_spec(self.policy, engine.env, engine.params), table
+
+    def _privileged_rows(self, priv, src, S, idx, n, out, ones_col):
+        """The one launch that forms the critic's rows: `out` [rows][dst_pad] <- src's first S columns, the parameter features, padding."""
+        spec, table = priv
+        return K.privileged_rows(src, S, idx, n, table, spec, out, ones_col)
+
+    def _critic_rows(self, priv, xin, idx, S, n, m_a, m_c, get):
+        """What the critic's passes read for the actor's prepared rows `xin` (idx: their flat t * n + e, None: row i is env i).  A critic
+        on a GemmMLP: [rows][m_c.in_pad] in its compute dtype with its own ones-column rule, marked as set_ones_column marks it; a
+        critic on autograd: the [:, :S + P] view of f32 rows padded to a multiple of 4.  An actor without a GemmMLP (or of another
+        compute dtype) first has its rows copied into rows padded the same way.  get(name, rows, cols, dtype): the workspace."""
+        P, rows = priv[0].count, xin.shape[0]
+        if m_c is not None:
+            dt, pad = m_c.cd, m_c.in_pad
+            ones = 31 if (pad == 32 and m_c.in_dim < 32 and m_c._f32 is None) else -1
+        else:
+            dt, pad, ones = torch.float32, M._round_up(S + P, 4), -1
+        src = xin
+        if m_a is None or xin.dtype != dt:
+            src = get("priv_src", rows, M._round_up(S, 8 if dt == torch.bfloat16 else 4), dt).zero_()
+            src[:, :S].copy_(xin[:, :S])
+        xc = self._privileged_rows(priv, src, S, idx, n, get("xin_c", rows, pad, dt), ones)
+        if m_c is None:
+            return xc[:, :S + P]
+        M.set_ones_column(xc, ones >= 0)
+        return xc
 
     def _bootstrap_params(self, buffer):
         """The env parameters tg_rollout_final_state steps with: those of the engine that rolled the buffer's trajectory out."""
@@ -924,15 +1001,25 @@ class PPO(_GpuLearner):
         each slot was rolled out with."""
         return getattr(buffer.rollout_manager.engine, "env_params", None)
 
-    def _bootstrap_values(self, params, traj, critic, m_c, env_params=None):
+    def _bootstrap_values(self, params, traj, critic, m_c, env_params=None, priv=None):
         """(b f32 [n], timeout u8 [n]): b[i] = V(s_final[i]) where the clock ended episode i, else 0 -- the re-step launch, the
-        critic's input rows prepared as the valid rows are, one no-grad pass over n rows, one multiply.  Enqueued; no host read."""
+        critic's input rows prepared as the valid rows are, one no-grad pass over n rows, one multiply.  Enqueued; no host read.
+        priv (a privileged critic): the rows are prepared as the ACTOR's are and each gets its own env's parameters (row i is env i)."""
         n, dev = traj.n, traj.mask.device
         s_final, timeout = K.rollout_final_state(params, traj, self._small("boot_state", n * traj.S, torch.float32, dev).view(n, traj.S),
                                                  self._small("boot_timeout", n, torch.uint8, dev),
                                                  env_params=env_params)
         on = getattr(self.policy, "obs_norm", None)        # (this learn()'s table: the update ran at the entry)
-        if m_c is not None:
+        if priv is not None:
+            m_a = self._mlp(self.policy.actor)
+            if m_a is not None:
+                xa = m_a.prepare_input(s_final, out=self._small("boot_xin_a", n * m_a.in_pad, m_a.cd, dev).view(n, m_a.in_pad), obs_norm=on)
+            else:
+                xa = s_final if on is None else on.normalize(s_final)
+            xc = self._critic_rows(priv, xa, None, traj.S, n, m_a, m_c,
+                                   lambda name, r, c, dt: self._small("boot_" + name, r * c, dt, dev).view(r, c))
+            v = m_c.forward(xc, keep=False, padded=True)[:, 0] if m_c is not None else self._forward(critic, xc).reshape(-1)
+        elif m_c is not None:
             xin = m_c.prepare_input(s_final, out=self._small("boot_xin", n * m_c.in_pad, m_c.cd, dev).view(n, m_c.in_pad), obs_norm=on)
             v = m_c.forward(xin, keep=False, padded=True)[:, 0]
         else:
@@ -952,7 +1039,10 @@ class PPO(_GpuLearner):
         rew = traj.rew if traj.rew.dtype == torch.float32 else traj.rew.float()
         actor, critic = self.policy.actor, self.policy.critic
         m_a, m_c = self._mlp(actor), self._mlp(critic)
-        if m_a is not None and m_c is not None and m_a.in_pad != m_c.in_pad:
+        # a privileged critic (policy.privileged_critic): (spec, parameter table) -- its input rows are the actor's plus the env's
+        # parameters, formed by one launch into a workspace of their own; the two nets keep their own learners and pads.  None: off
+        priv = self._privileged_setup(buffer, traj)
+        if priv is None and m_a is not None and m_c is not None and m_a.in_pad != m_c.in_pad:
             # (only one of the two fits the fp32 chain learner: both take the per-layer path, so that they keep sharing ONE prepared
             # input -- a Tanh net has no per-layer path and goes back to torch autograd instead)
             for net, m in ((actor, m_a), (critic, m_c)):
@@ -962,8 +1052,8 @@ class PPO(_GpuLearner):
         # the valid rows (ppo.py:126-135): index, padded input row (actor and critic share input width / compute dtype), action --
         # enqueued on the buffers' capacity; the host asks for the row count (and waits for the rollout) only after everything that
         # does not depend on it has been enqueued too
-        shared = m_c is not None and m_a is not None and m_c.in_pad == m_a.in_pad and m_c.cd == m_a.cd
-        handle = self._prepare_enqueue(traj, m_a) if shared else None
+        shared = priv is None and m_c is not None and m_a is not None and m_c.in_pad == m_a.in_pad and m_c.cd == m_a.cd
+        handle = self._prepare_enqueue(traj, m_a) if (shared or priv is not None) else None
         self._entry_refresh(actor, critic)
         _ = self.bucket                                                     # (the gradient windows exist before can_fuse_head() asks)
         dev = traj.mask.device
@@ -979,6 +1069,8 @@ class PPO(_GpuLearner):
             idx, X, act = self._gather_valid(traj)
             xin = self._prep(actor, X, cap)
         n_rows = xin.shape[0]
+        xin_c = xin if priv is None else self._critic_rows(priv, xin, idx, traj.S, n, m_a, m_c,
+                                                           lambda name, r, c, dt: self._ws.get(name, r, c, dt, dev, cap))
         # normalize_value: the critic's outputs are denormalised where they enter a return -- with the statistics the critic was last
         # trained against (the table as it stands here; the identity on the first call) -- and the table moves only after that
         vn = getattr(self.policy, "value_norm", None)
@@ -988,7 +1080,7 @@ class PPO(_GpuLearner):
         # follows each chunk's no-grad pass
         for lo in range(0, n_rows, self.chunk_rows):
             hi = min(lo + self.chunk_rows, n_rows)
-            out = m_c.forward(xin[lo:hi], keep=False, padded=True) if m_c is not None else self._forward(critic, xin[lo:hi])
+            out = m_c.forward(xin_c[lo:hi], keep=False, padded=True) if m_c is not None else self._forward(critic, xin_c[lo:hi])
             K.scatter_rows(out, idx[lo:hi], V, table=None if vn is None else vn.table)
         # ppo.py:100-124 + the masked moments of :138-139 in two launches; the ranks' sums in one all-reduce; the normalisation
         # constants and 1 / n on the device (tg_ppo_norm): nothing of this visits the host
@@ -997,7 +1089,7 @@ class PPO(_GpuLearner):
             moments = K.ppo_returns(rew, V, traj.mask, self.gamma, self.lam, self.monte_carlo, adv_full, ret_full, work)
         else:
             # time-limit bootstrapping: the same two launches on r + gamma * V(s_final) at each clock-ended episode's last step
-            boot, timeout = self._bootstrap_values(boot_params, traj, critic, m_c, env_params=boot_table)
+            boot, timeout = self._bootstrap_values(boot_params, traj, critic, m_c, env_params=boot_table, priv=priv)
             moments = K.ppo_returns_boot(rew, V, traj.mask, traj.len, boot, self.gamma, self.lam, self.monte_carlo, adv_full, ret_full, work)
             n_boot = timeout.sum(dtype=torch.int64).reshape(1)              # (a new tensor: read when last_stats is)
             D.allreduce_sum_(n_boot, self.process_group, "n_bootstrapped")
@@ -1030,7 +1122,8 @@ class PPO(_GpuLearner):
             final = u == self.updates_per_iter - 1
             if self.batch_size is None:
                 # full batch: the reference permutes and takes one "minibatch" of everything (ppo.py:147-150)
-                self._step(xin, act, adv, ret, old_logp, norm8, var, all_sums, last=final, write_old=fold_old and u == 0)
+                self._step(xin, act, adv, ret, old_logp, norm8, var, all_sums, last=final, write_old=fold_old and u == 0,
+                           xin_c=None if priv is None else xin_c)
             else:
                 if self.permutation_fn is not None:
                     perm = self.permutation_fn(n_rows, dev)
@@ -1049,7 +1142,8 @@ class PPO(_GpuLearner):
                     # (the minibatch's rows are copies: they keep the prepared input's ones column, and say so)
                     self._step(M.inherit_ones_column(xin.index_select(0, b), xin), act.index_select(0, b), adv.index_select(0, b),
                                ret.index_select(0, b), old_logp.index_select(0, b), norm8, var, all_sums,
-                               host=(norm_host, float(sizes[k])), last=final and k == n_steps - 1)
+                               host=(norm_host, float(sizes[k])), last=final and k == n_steps - 1,
+                               xin_c=None if priv is None else M.inherit_ones_column(xin_c.index_select(0, b), xin_c))
         self._check_deferred()                                              # (this learn()'s own row count: landed long ago)
         self._copy_policy_to_old()                                          # ppo.py:186
         if all_sums:

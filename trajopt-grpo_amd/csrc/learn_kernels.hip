@@ -25,6 +25,10 @@
 //   tg_scatter_rows_affine / tg_boot_values_affine / tg_value_norm_merge
 //                        running value normalisation (policies.ValueNorm): the critic's values denormalised where they enter a
 //                        return, and Chan's merge of the returns' all-reduced moments into {count, mean, m2} and the f32 table.
+//   tg_privileged_rows   the privileged critic's input rows: the actor's prepared rows with each env's randomised parameters, scaled
+//                        onto [-1, 1], in the columns behind the observation.
+#include <cmath>
+
 #include "tg_common.hpp"
 
 namespace tg {
@@ -542,6 +546,91 @@ __global__ void value_norm_merge_kernel(const double* __restrict__ moments, doub
     }
 }
 
+// The privileged critic's input rows (tg_privileged_rows): a streaming pass in which a lane owns ONE 16-byte piece of a destination row --
+// a row is `dst_chunks` adjacent lanes, so a wave stores up to 1 KiB of consecutive bytes and loads the matching pieces of the source
+// rows (consecutive within a row, rows `src_chunks` pieces apart).  A workgroup takes kPrivGroups groups of 256 / dst_chunks whole rows
+// (lane -> row and piece by one 32-bit divide; the few lanes left over when dst_chunks does not divide 256 idle) and every lane issues
+// the loads of all its groups before it uses any: unconditional loads from clamped addresses, so that they are in flight together.
+// A piece that lies inside the actor's columns [0, S) is the source's bits; the piece(s) that straddle or follow S take, element by
+// element, the source's bits, a parameter feature, the ones column or zero.  Feature k of env e: ((ptab[index[k]][e] / nominal[k]) -
+// center[k]) * scale[k] in f64 -- IEEE divide, every operation rounded on its own -- then rounded once to f32 (and once more to bf16).
+// The parameter table is [12][n] f64: a gather of 8 B per feature out of a row of 8 n bytes that stays in L2.  `spec` is only read (a
+// write into a by-value argument struct would send it to scratch).
+constexpr int kPrivGroups = 4;
+
+template <bool BF16>
+__global__ __launch_bounds__(256) void privileged_rows_kernel(const uint4* __restrict__ src, int src_chunks, int S, const int64_t* __restrict__ idx,
+                                                              int64_t rows, int64_t n, const double* __restrict__ ptab, const tg_privileged_spec spec,
+                                                              uint4* __restrict__ dst, int dst_chunks, int group_rows, int ones_col) {
+#pragma clang fp contract(off)
+    constexpr int kElems = BF16 ? 8 : 4;                     // elements of a 16-byte piece
+    const unsigned lr = threadIdx.x / (unsigned)dst_chunks;  // row within a group, piece within the row
+    const int c = (int)(threadIdx.x - lr * (unsigned)dst_chunks);
+    if (lr >= (unsigned)group_rows) return;
+    const int col0 = c * kElems, P = spec.count;
+    const bool from_src = col0 < S;                          // (col0 < S <= src_pad and both are multiples of kElems: the piece exists)
+    const bool mixed = col0 + kElems > S, feat = mixed && col0 < S + P;
+    const int cs = from_src ? c : 0;
+    const int64_t r0 = (int64_t)blockIdx.x * (kPrivGroups * group_rows) + lr;
+    uint4 v[kPrivGroups];
+    int64_t f[kPrivGroups];
+#pragma unroll
+    for (int k = 0; k < kPrivGroups; ++k) {
+        const int64_t r = r0 + (int64_t)k * group_rows, rc = r < rows ? r : rows - 1;
+        v[k] = src[rc * src_chunks + cs];
+        f[k] = idx != nullptr ? idx[rc] : rc;
+    }
+    if (mixed) {
+        uint32_t w[kPrivGroups][4];
+        int64_t e[kPrivGroups];
+#pragma unroll
+        for (int k = 0; k < kPrivGroups; ++k) {
+            w[k][0] = from_src ? v[k].x : 0u; w[k][1] = from_src ? v[k].y : 0u; w[k][2] = from_src ? v[k].z : 0u; w[k][3] = from_src ? v[k].w : 0u;
+            e[k] = 0;
+            if (feat) {                                      // (only the lanes that form a feature pay for the modulo; unsigned: always inside [0, n))
+                const uint64_t uf = (uint64_t)f[k], un = (uint64_t)n;
+                e[k] = (int64_t)(((uf | un) >> 32) ? uf % un : (uint64_t)((uint32_t)uf % (uint32_t)un));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+            const int col = col0 + j;
+            if (col < S) continue;
+            float x[kPrivGroups];
+            if (col < S + P) {
+                const int kk = col - S;
+                const double* __restrict__ prow = ptab + (int64_t)spec.index[kk] * n;
+                const double nominal = spec.nominal[kk], center = spec.center[kk], scale = spec.scale[kk];
+#pragma unroll
+                for (int k = 0; k < kPrivGroups; ++k) {
+                    const double q = prow[e[k]] / nominal;
+                    const double d = q - center;
+                    x[k] = (float)(d * scale);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < kPrivGroups; ++k) x[k] = col == ones_col ? 1.0f : 0.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < kPrivGroups; ++k) {
+                if (BF16) {
+                    const uint32_t h = (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)x[k]);       // round to nearest even
+                    w[k][j >> 1] = (j & 1) ? ((w[k][j >> 1] & 0x0000ffffu) | (h << 16)) : ((w[k][j >> 1] & 0xffff0000u) | h);
+                } else {
+                    w[k][j] = __float_as_uint(x[k]);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kPrivGroups; ++k) v[k] = uint4{w[k][0], w[k][1], w[k][2], w[k][3]};
+    }
+#pragma unroll
+    for (int k = 0; k < kPrivGroups; ++k) {
+        const int64_t r = r0 + (int64_t)k * group_rows;
+        if (r < rows) dst[r * dst_chunks + c] = v[k];
+    }
+}
+
 // dst0[r] = src0[idx[r]], dst1[r] = src1[idx[r]]: `adv[mask]`, `returns[mask]` (ppo.py:126-135) in one launch
 __global__ __launch_bounds__(256) void gather_rows2_kernel(const int64_t* __restrict__ idx, int64_t rows, const float* __restrict__ src0,
                                                            float* __restrict__ dst0, const float* __restrict__ src1, float* __restrict__ dst1) {
@@ -736,6 +825,48 @@ int tg_value_norm_merge(const double* d_moments3, double eps, double* d_count, d
     TG_REQUIRE(eps >= 0.0, "tg_value_norm_merge: eps %g < 0", eps);
     hipLaunchKernelGGL(value_norm_merge_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_moments3, eps, d_count, d_mean, d_m2, d_table, d_norm8);
     TG_LAUNCH_CHECK("tg_value_norm_merge");
+    return TG_OK;
+}
+
+int tg_privileged_rows(const void* d_src, int32_t src_pad, int32_t S, const int64_t* d_idx, int64_t rows, int64_t n, const double* d_ptab,
+                       const tg_privileged_spec* spec, void* d_dst, int32_t dst_pad, int32_t bf16, int32_t ones_col, void* stream) {
+    TG_REQUIRE(d_src && d_ptab && spec && d_dst, "tg_privileged_rows: null pointer");
+    TG_REQUIRE(spec->count >= 1 && spec->count <= 12, "tg_privileged_rows: %d privileged columns (1..12)", spec->count);
+    const int P = spec->count, mult = bf16 ? 8 : 4;
+    uint32_t seen = 0;
+    for (int k = 0; k < P; ++k) {
+        const int i = spec->index[k];
+        TG_REQUIRE(i >= 0 && i < 12, "tg_privileged_rows: column %d reads p[%d] (0..11)", k, i);
+        TG_REQUIRE(!(seen & (1u << i)), "tg_privileged_rows: p[%d] is listed twice", i);
+        seen |= 1u << i;
+        TG_REQUIRE(std::isfinite(spec->nominal[k]) && spec->nominal[k] != 0.0, "tg_privileged_rows: nominal value %g of column %d (finite, not 0)",
+                   spec->nominal[k], k);
+        TG_REQUIRE(std::isfinite(spec->center[k]) && std::isfinite(spec->scale[k]), "tg_privileged_rows: centre %g / scale %g of column %d",
+                   spec->center[k], spec->scale[k], k);
+    }
+    TG_REQUIRE(src_pad > 0 && src_pad <= 64 && src_pad % mult == 0 && dst_pad > 0 && dst_pad <= 64 && dst_pad % mult == 0,
+               "tg_privileged_rows: pads %d / %d (multiples of %d, at most 64)", src_pad, dst_pad, mult);
+    TG_REQUIRE(S >= 1 && S <= src_pad && S + P <= dst_pad, "tg_privileged_rows: S %d with %d privileged columns does not fit pads %d / %d", S, P,
+               src_pad, dst_pad);
+    TG_REQUIRE(ones_col == -1 || (ones_col >= S + P && ones_col < dst_pad), "tg_privileged_rows: ones column %d (-1, or in [%d, %d))", ones_col,
+               S + P, dst_pad);
+    TG_REQUIRE(n > 0 && rows >= 0, "tg_privileged_rows: bad sizes (n %lld, rows %lld)", (long long)n, (long long)rows);
+    TG_REQUIRE(d_idx != nullptr || rows <= n, "tg_privileged_rows: %lld rows of %lld envs without an index", (long long)rows, (long long)n);
+    TG_REQUIRE((uintptr_t)d_src % 16 == 0 && (uintptr_t)d_dst % 16 == 0, "tg_privileged_rows: rows not aligned to 16 bytes");
+    if (rows == 0) return TG_OK;
+    const int elem = bf16 ? 2 : 4, src_chunks = src_pad * elem / 16, dst_chunks = dst_pad * elem / 16;
+    const int group_rows = 256 / dst_chunks;                 // whole rows per 256 lanes
+    const int64_t blocks = ceil_div(rows, (int64_t)kPrivGroups * group_rows);
+    TG_REQUIRE(blocks < ((int64_t)1 << 31), "tg_privileged_rows: %lld rows are too many for one launch", (long long)rows);
+    const dim3 grid((unsigned)blocks);
+    hipStream_t st = (hipStream_t)stream;
+    if (bf16)
+        hipLaunchKernelGGL(privileged_rows_kernel<true>, grid, dim3(256), 0, st, (const uint4*)d_src, src_chunks, S, d_idx, rows, n, d_ptab, *spec,
+                           (uint4*)d_dst, dst_chunks, group_rows, ones_col);
+    else
+        hipLaunchKernelGGL(privileged_rows_kernel<false>, grid, dim3(256), 0, st, (const uint4*)d_src, src_chunks, S, d_idx, rows, n, d_ptab, *spec,
+                           (uint4*)d_dst, dst_chunks, group_rows, ones_col);
+    TG_LAUNCH_CHECK("tg_privileged_rows");
     return TG_OK;
 }
 

@@ -216,6 +216,24 @@ def value_norm_merge(moments3, eps: float, count: torch.Tensor, mean: torch.Tens
                                          N.ptr(norm8), _st(table)), "tg_value_norm_merge")
 
 
+def privileged_rows(src: torch.Tensor, S: int, idx, n: int, env_params: torch.Tensor, spec: "N.PrivilegedSpec", out: torch.Tensor,
+                    ones_col: int = -1) -> torch.Tensor:
+    """tg_privileged_rows: the privileged critic's input rows.  src [rows][src_pad] bf16 / f32 (the actor's prepared rows), out
+    [>= rows][dst_pad] of the same dtype: columns [0, S) of a row are src's bits, column S + k is env e's parameter spec.index[k] as a
+    feature on [-1, 1], the rest 0 with 1 in ones_col (or -1).  idx int64 [rows] holds the rows' flat t * n + e (e = idx % n), or None:
+    row r is env r.  env_params: DeviceRollout.env_params, f64 [12][n]."""
+    N.require_cuda(src, idx, env_params, out)
+    rows = src.shape[0]
+    assert src.dim() == 2 and out.dim() == 2 and src.is_contiguous() and out.is_contiguous() and out.shape[0] >= rows
+    assert src.dtype == out.dtype and src.dtype in (torch.bfloat16, torch.float32)
+    assert idx is None or (idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == rows)
+    assert env_params.dtype == torch.float64 and env_params.is_contiguous() and tuple(env_params.shape) == (12, int(n))
+    N.check(N.load().tg_privileged_rows(src.data_ptr(), src.shape[1], int(S), N.ptr(idx), rows, int(n), env_params.data_ptr(), C.byref(spec),
+                                        out.data_ptr(), out.shape[1], int(src.dtype == torch.bfloat16), int(ones_col), _st(out)),
+            "tg_privileged_rows")
+    return out[:rows]
+
+
 def ppo_returns(rew, values, mask, gamma: float, lam: float, monte_carlo: bool, adv: torch.Tensor, ret: torch.Tensor,
                 work: torch.Tensor = None) -> torch.Tensor:
     """tg_ppo_returns: fills adv / ret f32 [T][n] (ppo.py:100-124) and returns the f64 [2][3] masked moments {count, sum, sum of

@@ -519,25 +519,115 @@ class GaussianActor_NeuralNetwork(_GaussianBase):
         self.load_state_dict(torch.load(os.path.join(path, "policy.pt"), weights_only=True, map_location=self.device))
 
 
+def _check_privileged(ranges):
+    """privileged_critic's argument, validated as Env.randomize() validates its ranges: {name: (lo, hi)} in the caller's order, or None
+    for None / {} (off).  The names are the env's business: the learner checks them against the env that rolled the buffer out."""
+    if ranges is None or (hasattr(ranges, "items") and len(ranges) == 0):
+        return None
+    if not hasattr(ranges, "items"):
+        raise ValueError(f"privileged_critic must map parameter names to (lo, hi), as Env.randomize() takes them, got {ranges!r}")
+    if len(ranges) > 12:
+        raise ValueError(f"privileged_critic: {len(ranges)} parameters, an env has at most 12")
+    checked = {}
+    for name, rng in ranges.items():
+        if not isinstance(name, str):
+            raise ValueError(f"privileged_critic: parameter names are strings, got {name!r}")
+        try:
+            lo, hi = (float(v) for v in rng)
+        except (TypeError, ValueError):
+            raise ValueError(f"privileged_critic: the range of {name!r} must be a (lo, hi) pair of numbers, got {rng!r}") from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+            raise ValueError(f"privileged_critic: the factor range of {name!r} must be finite with 0 < lo <= hi, got ({lo}, {hi})")
+        checked[name] = (lo, hi)
+    return checked
+
+
 class GaussianActorCritic_NeuralNetwork(_GaussianBase):
-    """policies/actor_critic.py:220-378."""
+    """policies/actor_critic.py:220-378.
+
+    privileged_critic={name: (lo, hi)} (the mapping one passes to Env.randomize; None / {}: off): an asymmetric actor-critic.  The
+    actor reads the observation; the critic, which only training uses, reads P = len(mapping) more columns behind it, one per
+    randomised physical parameter in the mapping's order.  For a multiplicative factor f on the nominal value the column holds
+    x = (f - c) * s with c = 0.5 * (lo + hi), s = 2 / (hi - lo) (0 when hi == lo): the drawn range on [-1, 1], formed in f64 with
+    every operation rounded on its own and rounded once to f32.  These columns pass neither obs_norm nor its clamp."""
     has_critic = True
 
     def __init__(self, input_dim, output_dim, hidden_dims, activation="ReLU", cov=0.1, device=None, learn_std=False, *,
-                 normalize_obs=False, obs_clip=10.0, obs_eps=1e-8, normalize_value=False, value_eps=1e-8):
+                 normalize_obs=False, obs_clip=10.0, obs_eps=1e-8, normalize_value=False, value_eps=1e-8, privileged_critic=None):
         if not isinstance(normalize_value, bool):
             raise ValueError(f"normalize_value must be True or False, got {normalize_value!r}")
         if isinstance(value_eps, bool) or not isinstance(value_eps, (int, float)) or not (math.isfinite(value_eps) and value_eps >= 0):
             raise ValueError(f"value_eps must be a finite number >= 0, got {value_eps!r}")
+        privileged_critic = _check_privileged(privileged_critic)
         super().__init__(input_dim, output_dim, hidden_dims, activation, cov, device, learn_std, normalize_obs=normalize_obs,
                          obs_clip=obs_clip, obs_eps=obs_eps)
-        self.critic = NeuralNetwork(input_dim, 1, hidden_dims, activation).to(self.device)
+        # None when off: the critic then reads what the actor reads, and nothing below is touched
+        self.privileged_critic = privileged_critic
+        self.privileged_center = [0.5 * (lo + hi) for lo, hi in (privileged_critic or {}).values()]          # (Python floats, once)
+        self.privileged_scale = [2.0 / (hi - lo) if hi > lo else 0.0 for lo, hi in (privileged_critic or {}).values()]
+        self.critic = NeuralNetwork(input_dim + len(self.privileged_center), 1, hidden_dims, activation).to(self.device)
         # running value normalisation: None when off (the critic then predicts whatever its learner regresses it onto)
         self.value_norm = ValueNorm(value_eps, self.device) if normalize_value else None
 
-    def value(self, state):
-        v = self.critic(self._prep_obs(state)).squeeze()                  # :313-323
+    def privileged_features(self, factors, shape=()) -> torch.Tensor:
+        """The critic's privileged columns f32 [..., P] of multiplicative factors [..., P] in column order (None: the nominal vehicle,
+        every factor 1, broadcast to `shape`): (f - c) * s in f64, subtract and multiply each rounded on its own, one rounding to f32."""
+        P = len(self.privileged_center)
+        if factors is None:
+            f = torch.ones(tuple(shape) + (P,), dtype=torch.float64, device=self.device)
+        else:
+            if isinstance(factors, np.ndarray):
+                factors = torch.from_numpy(factors)
+            f = torch.as_tensor(factors).to(self.device, torch.float64)
+            if f.shape[-1:] != (P,):
+                raise ValueError(f"factors must hold {P} columns (privileged_critic: {', '.join(self.privileged_critic)}), got shape {tuple(f.shape)}")
+        c = torch.tensor(self.privileged_center, dtype=torch.float64, device=self.device)
+        s = torch.tensor(self.privileged_scale, dtype=torch.float64, device=self.device)
+        return ((f - c) * s).to(torch.float32)
+
+    def _critic_input(self, obs, factors):
+        """What the critic reads: the prepared observation, and the privileged columns behind it when there are any."""
+        if self.privileged_critic is None:
+            if factors is not None:
+                raise ValueError("factors were given, this policy's critic is not privileged: construct it with privileged_critic={...}")
+            return obs
+        x = self.privileged_features(factors, obs.shape[:-1])
+        return torch.cat([obs, x.expand(obs.shape[:-1] + x.shape[-1:])], dim=-1)
+
+    def forward(self, state, factors=None):
+        """_GaussianBase.forward with the critic's value taken of (state, factors): factors [..., P] in column order, None = nominal."""
+        if self.privileged_critic is None and factors is None:
+            return super().forward(state)
+        state = self._prep_obs(state)
+        mean = self.actor(state)
+        with torch.no_grad():
+            std = torch.exp(self.log_std).to(mean.device) if self.log_std is not None else torch.sqrt(self.var).to(mean.device)
+            action = mean + std * torch.randn(mean.shape, device=mean.device)
+        return action.detach().cpu().numpy(), self._logp(mean, action), self.critic(self._critic_input(state, factors))
+
+    def value(self, state, factors=None):
+        v = self.critic(self._critic_input(self._prep_obs(state), factors)).squeeze()                  # :313-323
         return v if self.value_norm is None else self.value_norm.denormalize(v)
+
+    def metadata(self):
+        md = super().metadata()
+        if self.privileged_critic is not None:
+            md["privileged_critic"] = {k: [lo, hi] for k, (lo, hi) in self.privileged_critic.items()}
+        return md
+
+    def _check_critic_width(self, state_dict) -> None:
+        """load_state_dict's guard: the checkpoint's critic reads input_dim + P columns, or the error names privileged_critic."""
+        w = state_dict.get("critic", {}).get("network.0.weight") if hasattr(state_dict.get("critic", None), "get") else None
+        if w is None:
+            return
+        have, want, P = int(w.shape[1]), self.critic.network[0].in_features, len(self.privileged_center)
+        if have == want:
+            return
+        if P == 0:
+            raise ValueError(f"the checkpoint's critic reads {have} columns, this policy's {want}: it was saved by a policy with "
+                             f"privileged_critic of {have - self.input_dim} parameter(s) -- construct this one with the same privileged_critic mapping")
+        raise ValueError(f"the checkpoint's critic reads {have} columns, this policy's critic {self.input_dim} + {P} = {want} "
+                         f"(privileged_critic: {', '.join(self.privileged_critic)}): the privileged_critic mappings differ")
 
     def parameters(self):
         return self._with_log_std(list(self.actor.parameters()) + list(self.critic.parameters()))
@@ -564,6 +654,7 @@ class GaussianActorCritic_NeuralNetwork(_GaussianBase):
         return sd
 
     def load_state_dict(self, state_dict):
+        self._check_critic_width(state_dict)
         self._load_log_std(state_dict.get("log_std"))
         self._load_obs_norm(state_dict)
         self._load_value_norm(state_dict)
