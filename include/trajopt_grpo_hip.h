@@ -890,6 +890,46 @@ int  tg_privileged_rows(const void* d_src, int32_t src_pad, int32_t S, const int
                         const double* d_ptab, const tg_privileged_spec* spec, void* d_dst, int32_t dst_pad, int32_t bf16,
                         int32_t ones_col, void* stream);
 
+/* ---- Deterministic evaluation and parameter sweeps (Evaluator) ----
+ * A mean-action rollout needs no kernel of its own: every sampling site forms a[k] = rn_add(mu[k], rn_mul(sigma[k], eps[k])) with a
+ * finite eps (Philox::u01 is in (0, 1]), so the entry points above called with a sigma of exactly 0.0f record a == mu (a mean of -0
+ * may come out as +0).  What an evaluation adds is below; `episodes_per_cell` = E, the n env slots of the trajectory are C = n / E
+ * cells of E consecutive slots.
+ *
+ * tg_env_param_grid: a third source of the per-env table d_ptab f64 [12][n] (beside "absent" and tg_env_randomize).  Slot i belongs
+ *   to cell c = (env_offset + i) / E.  c is decoded row-major over the swept parameters taken in p[] order (ascending index,
+ *   whatever order the struct lists them in): the parameter with the largest index runs fastest, level = c % levels, c /= levels, and
+ *   so on down.  Row r of column i = p->p[r], times -- when r is swept -- d_values[first(r) + level(r)], where first(r) is where r's
+ *   factor list starts in d_values (the lists are concatenated in the struct's listing order).  Plain IEEE double, no contraction:
+ *   a factor of 1.0 reproduces p->p[r] bit for bit, so such a table gives the plain entry point's trajectory bit for bit (above).
+ *   Refused (TG_ERR_ARG, nothing launched): a null pointer (d_values may be NULL only with count == 0), count outside [0, 12], an
+ *   index outside [0, 12) or listed twice, a level count < 1, episodes_per_cell < 1, n not a multiple of episodes_per_cell,
+ *   env_offset < 0, envs that reach beyond the grid's last cell.  The factors themselves live on the device and are not looked at.
+ * tg_eval_tile_states: obs[k][0][i] = obs[k][0][i % E] for k < S, E <= i < n, one launch, f32 and f64 trajectories: every cell
+ *   starts from the E initial states of cell 0 (drawn there by tg_env_reset).  Nothing else of the trajectory is touched.
+ * tg_eval_cells: two launches.
+ *   d_returns f64 [n]: [i] = the sum of rew[t][i] over t < len[i], t ascending, each reward converted to f64 and added in f64 (no
+ *     contraction); 0 for a slot that is not counted.  A slot is counted when 1 <= len[i] <= T.
+ *   d_cells f64 [C][8], row c over the counted slots of cell c = {episodes, sum of returns, sum of squared returns (r * r rounded,
+ *     then added), smallest return, largest return, sum of lengths, clock-ended episodes (d_timeout[i] != 0, as
+ *     tg_rollout_final_state writes it), episodes ended early (counted and not clock-ended)}.
+ *   Summation order of a cell, for both sums: 256 partials, partial j = 0.0 plus the counted slots e = j, j + 256, j + 512, ... of
+ *     the cell added in that order; then for s = 128, 64, ..., 1: partial[j] += partial[j + s] for every j < s.  Row value =
+ *     partial[0].  No floating-point atomics: the bits depend on the trajectory alone.
+ *   A cell without a counted slot reports episodes = 0, sums 0, smallest return +inf and largest return -inf.
+ *   Reads d_rew and d_len of the trajectory (not d_mask: len says the same) and d_timeout u8 [n]; writes nothing into it. */
+typedef struct tg_param_grid {
+    int32_t       count;             /* swept parameters, <= 12 */
+    int32_t       index[12];         /* which p[] each of them scales */
+    int32_t       levels[12];        /* how many factors each has, >= 1 */
+    const double* d_values;          /* DEVICE f64 [sum of levels]: the factor lists, concatenated in listing order */
+    int64_t       episodes_per_cell; /* E >= 1 */
+} tg_param_grid;
+int  tg_env_param_grid(const tg_env_params* p, const tg_param_grid* g, double* d_ptab, int64_t n, int64_t env_offset, void* stream);
+int  tg_eval_tile_states(const tg_traj* tr, int32_t S, int64_t episodes_per_cell, void* stream);
+int  tg_eval_cells(const tg_traj* tr, const uint8_t* d_timeout, int64_t episodes_per_cell, double* d_returns, double* d_cells,
+                   void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

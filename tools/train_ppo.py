@@ -4,6 +4,11 @@ epoch instead of 50-80.
 
     python3 tools/train_ppo.py [epochs] [CartPole|Pendulum|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
                                [--learn-std] [--normalize-obs] [--normalize-value] [--gae] [--privileged-critic]
+                               [--eval-every N] [--eval-episodes E] [--eval-sweep name=f1,f2,... ...]
+
+--eval-every N: every N epochs a deterministic evaluation (trajopt_grpo_amd.Evaluator: mean actions, its own seed and RNG stream) of
+--eval-episodes E episodes per cell (default 256) is printed beside the sampled training return.  --eval-sweep (repeatable): the
+evaluation runs one cell per combination of the listed factors on those physical parameters, e.g. `--eval-sweep mass=0.8,1,1.25`.
 
 --normalize-value: running value normalisation (policy.value_norm): the critic regresses onto returns standardised with running
 statistics and is denormalised wherever it enters a return.  --gae: monte_carlo=False (GAE(gamma, 0.95) advantages).
@@ -45,8 +50,51 @@ def pop_randomize(argv):
     return ranges, rest
 
 
+def pop_valued(argv, flag):
+    """Removes every `flag value` / `flag=value` from argv; -> ([value, ...], the rest)."""
+    values, rest, k = [], [], 0
+    while k < len(argv):
+        if argv[k] == flag:
+            if k + 1 >= len(argv):
+                raise SystemExit(f"{flag} expects a value")
+            values.append(argv[k + 1])
+            k += 2
+        elif argv[k].startswith(flag + "="):
+            values.append(argv[k].split("=", 1)[1])
+            k += 1
+        else:
+            rest.append(argv[k])
+            k += 1
+    return values, rest
+
+
+def pop_eval(argv):
+    """-> (eval_every or None, eval_episodes, sweep {name: [factor, ...]} or None, the rest of argv)."""
+    every, argv = pop_valued(argv, "--eval-every")
+    episodes, argv = pop_valued(argv, "--eval-episodes")
+    items, argv = pop_valued(argv, "--eval-sweep")
+    sweep = {}
+    for item in items:
+        try:
+            name, vals = item.split("=", 1)
+            sweep[name] = [float(v) for v in vals.split(",")]
+        except ValueError:
+            raise SystemExit(f"--eval-sweep expects name=f1,f2,..., got {item!r}")
+    try:
+        every = int(every[-1]) if every else None
+        episodes = int(episodes[-1]) if episodes else 256
+    except ValueError:
+        raise SystemExit("--eval-every and --eval-episodes expect integers")
+    if every is not None and every < 1:
+        raise SystemExit("--eval-every expects a positive integer")
+    if every is None and (sweep or items):
+        raise SystemExit("--eval-sweep needs --eval-every N")
+    return every, episodes, sweep or None, argv
+
+
 def main():
     ranges, sys.argv[1:] = pop_randomize(sys.argv[1:])
+    eval_every, eval_episodes, eval_sweep, sys.argv[1:] = pop_eval(sys.argv[1:])
     learn_std = "--learn-std" in sys.argv                         # a learned per-dimension log-std instead of the fixed covariance
     sys.argv = [a for a in sys.argv if a != "--learn-std"]
     normalize_obs = "--normalize-obs" in sys.argv                 # running observation normalisation (policy.obs_norm)
@@ -81,10 +129,23 @@ def main():
     algo = tg.PPO(epsilon=0.2, policy=pol, optimizer=torch.optim.Adam(pol.parameters(), lr=lr), ref_model=None,
                   updates_per_iter=upd, c1=0.5, kl_coeff=0.5, gamma=gamma, lam=0.95, entropy=0.01, batch_size=None,
                   autocast_dtype=cdt, **({"monte_carlo": False} if gae else {}))
+    evaluator = None
+    if eval_every is not None:                                    # (refuses a bad sweep before the first epoch)
+        evaluator = tg.Evaluator(tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, episodes=eval_episodes, sweep=eval_sweep,
+                                 seed=1, compute_dtype=cdt)
     t0 = time.time()
     for ep in range(epochs):
         buf.sample()
         algo.learn(buf)
+        if evaluator is not None and (ep + 1) % eval_every == 0:
+            res = evaluator.evaluate()
+            s = res.summary
+            print(f"epoch {ep:4d}  eval return {s['return_mean']:9.2f} +- {s['return_std']:.2f}  len {s['length_mean']:6.1f}  "
+                  f"timeout {s['timeout_frac']:.3f}  {res.early_name} {s['early_frac']:.3f}", flush=True)
+            if eval_sweep:
+                for row in res.table:
+                    print("      " + "  ".join(f"{n} x{f:g}" for n, f in zip(res.sweep_names, row["factors"]))
+                          + f"  return {row['return_mean']:9.2f}  len {row['length_mean']:6.1f}  timeout {row['timeout_frac']:.3f}", flush=True)
         if ep % 10 == 0 or ep == epochs - 1:
             print(f"epoch {ep:4d}  avg return {float(buf.avg_reward[-1]):9.2f}  mean len {float(buf.device_traj.len.float().mean()):6.1f}  "
                   f"elapsed {time.time() - t0:6.1f}s"

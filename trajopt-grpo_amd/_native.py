@@ -122,6 +122,13 @@ class PrivilegedSpec(C.Structure):
                 ("scale", C.c_double * 12)]
 
 
+class ParamGrid(C.Structure):
+    """tg_param_grid (include/trajopt_grpo_hip.h): the swept p[] entries of an evaluation, how many factors each has, the device array
+    that holds the factor lists one after the other, and the episodes of a cell."""
+    _fields_ = [("count", C.c_int32), ("index", C.c_int32 * 12), ("levels", C.c_int32 * 12), ("d_values", C.c_void_p),
+                ("episodes_per_cell", C.c_int64)]
+
+
 class CompactArgs(C.Structure):
     """tg_compact_args (include/trajopt_grpo_hip.h)."""
     _fields_ = [("d_mask", C.c_void_p), ("d_offsets", C.c_void_p), ("n", C.c_int64), ("T", C.c_int32), ("S", C.c_int32), ("A", C.c_int32),
@@ -270,6 +277,9 @@ SIGNATURES = {
     "tg_boot_values_affine": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _VP]),
     "tg_value_norm_merge": (C.c_int, [_VP, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tg_privileged_rows": (C.c_int, [_VP, _I32, _I32, _VP, _I64, _I64, _VP, _P(PrivilegedSpec), _VP, _I32, _I32, _I32, _VP]),
+    "tg_env_param_grid": (C.c_int, [_P(EnvParams), _P(ParamGrid), _VP, _I64, _I64, _VP]),
+    "tg_eval_tile_states": (C.c_int, [_P(Traj), _I32, _I64, _VP]),
+    "tg_eval_cells": (C.c_int, [_P(Traj), _VP, _I64, _VP, _VP, _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),

@@ -268,6 +268,58 @@ def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: tor
     return s_final, timeout
 
 
+def param_grid(indices, levels, values: torch.Tensor, episodes_per_cell: int) -> "N.ParamGrid":
+    """tg_param_grid: the swept p[] indices, the number of factors of each, the device f64 array of the concatenated factor lists
+    (kept alive by the caller) and the episodes of a cell."""
+    N.require_cuda(values)
+    assert values.dtype == torch.float64 and values.is_contiguous() and values.numel() == sum(int(v) for v in levels)
+    assert len(indices) == len(levels) <= 12
+    g = N.ParamGrid()
+    g.count, g.d_values, g.episodes_per_cell = len(indices), values.data_ptr(), int(episodes_per_cell)
+    for k, (i, l) in enumerate(zip(indices, levels)):
+        g.index[k], g.levels[k] = int(i), int(l)
+    g._values = values                                   # (the struct holds a raw address: keep the factors alive with it)
+    return g
+
+
+def env_param_grid(params, grid: "N.ParamGrid", out: torch.Tensor, env_offset: int = 0) -> torch.Tensor:
+    """tg_env_param_grid: the per-env parameter table f64 [12][n] of a sweep -- env slot i steps the vehicle of cell
+    (env_offset + i) / episodes_per_cell, the cell decoded row-major over the swept parameters in p[] order."""
+    N.require_cuda(out)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == 12
+    N.check(N.load().tg_env_param_grid(C.byref(params), C.byref(grid), out.data_ptr(), out.shape[1], int(env_offset), _st(out)),
+            "tg_env_param_grid")
+    return out
+
+
+def eval_tile_states(traj, episodes_per_cell: int) -> None:
+    """tg_eval_tile_states: slot 0 of obs of the first `episodes_per_cell` envs copied to every other cell, in place."""
+    N.require_cuda(traj.obs)
+    assert traj.obs.is_contiguous()
+    tr = traj.native()
+    N.check(N.load().tg_eval_tile_states(C.byref(tr), traj.S, int(episodes_per_cell), _st(traj.obs)), "tg_eval_tile_states")
+
+
+def eval_cells(traj, timeout: torch.Tensor, episodes_per_cell: int, returns: torch.Tensor = None, cells: torch.Tensor = None):
+    """tg_eval_cells on a DeviceTrajectory: (returns f64 [n], cells f64 [n / E][8]) -- per episode the f64 sum of its rewards, per cell
+    {episodes, sum of returns, sum of squared returns, min, max, sum of lengths, clock-ended, ended early} in the fixed summation
+    order of the header.  timeout: u8 [n] from rollout_final_state."""
+    N.require_cuda(traj.rew, traj.len, timeout, returns, cells)
+    E = int(episodes_per_cell)
+    assert traj.rew.is_contiguous() and traj.len.is_contiguous() and traj.len.dtype == torch.int32
+    assert timeout.dtype == torch.uint8 and timeout.is_contiguous() and timeout.numel() == traj.n
+    dev = traj.rew.device
+    if returns is None:
+        returns = torch.empty(traj.n, dtype=torch.float64, device=dev)
+    if cells is None:
+        cells = torch.empty(max(traj.n // max(E, 1), 1), 8, dtype=torch.float64, device=dev)
+    assert returns.dtype == torch.float64 and returns.is_contiguous() and returns.numel() == traj.n
+    assert cells.dtype == torch.float64 and cells.is_contiguous() and cells.numel() >= 8 * (traj.n // max(E, 1))
+    tr = traj.native()
+    N.check(N.load().tg_eval_cells(C.byref(tr), timeout.data_ptr(), E, returns.data_ptr(), cells.data_ptr(), _st(traj.rew)), "tg_eval_cells")
+    return returns, cells
+
+
 def ppo_returns_boot(rew, values, mask, length, boot, gamma: float, lam: float, monte_carlo: bool, adv: torch.Tensor, ret: torch.Tensor,
                      work: torch.Tensor = None) -> torch.Tensor:
     """tg_ppo_returns_boot: ppo_returns() on the rewards with gamma * boot[i] added to the reward of env i's last step

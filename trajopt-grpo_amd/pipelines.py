@@ -9,6 +9,7 @@ Checkpoint layout: ./archive/<env>/<test>/<ckpt>/{policy.pt, optimizer.pt|pth, r
 """
 from __future__ import annotations
 
+import csv
 import datetime
 import json
 import os
@@ -38,6 +39,12 @@ class Pipeline:
         self.visualizer, self.publisher, self.logger = visualizer, publisher, logger
         self.load_path, self.save_freq, self.render_freq = load_path, save_freq, render_freq
         self.today = datetime.datetime.now().strftime("%Y-%m-%d %H:%M:%S")
+        # evaluation (evaluate(), train(eval_every=...)): an evaluation.Evaluator, or anything with its evaluate(); None: one of the
+        # defaults is built at the first evaluate().  epochs_done counts the epochs train() has finished; best_return is the best
+        # overall return_mean an evaluation of train() has seen (the checkpoint under <archive>/best/)
+        self.evaluator = None
+        self.epochs_done = 0
+        self.best_return = None
         if load_path is not None:
             self.load()
         self.initialize()
@@ -69,13 +76,16 @@ class Pipeline:
         alone writes the checkpoint (torch.save is not atomic); the others wait for it."""
         rank, world = rank_world()
         if rank == 0:
-            self.algorithm.save(path)
-            self.policy.save(path)
-            self.buffer.save(path)
-            with open(os.path.join(path, "metadata.json"), "w") as f:
-                json.dump(self.get_metadata(), f, indent=4)
+            self._write_checkpoint(path)
         if world > 1:
             torch.distributed.barrier()
+
+    def _write_checkpoint(self, path: str) -> None:
+        self.algorithm.save(path)
+        self.policy.save(path)
+        self.buffer.save(path)
+        with open(os.path.join(path, "metadata.json"), "w") as f:
+            json.dump(self.get_metadata(), f, indent=4)
 
     def get_metadata(self) -> Dict[str, Any]:
         meta = {
@@ -99,10 +109,23 @@ class Pipeline:
         with open(path, "r") as f:
             return json.load(f)
 
-    def train(self, epochs: int) -> None:
+    def train(self, epochs: int, eval_every: Optional[int] = None) -> None:
+        """eval_every=N: after every N-th epoch rank 0 runs evaluate() and, when the overall return_mean beats every earlier
+        evaluation of this pipeline, writes the checkpoint to <archive>/best/.  None (the default): the reference's loop."""
+        if eval_every is not None and (isinstance(eval_every, bool) or not isinstance(eval_every, int) or eval_every < 1):
+            raise ValueError(f"train(): eval_every must be a positive integer or None, got {eval_every!r}")
         for epoch in range(epochs):
             self.buffer.sample()
             self.algorithm.learn(self.buffer)
+            self.epochs_done = getattr(self, "epochs_done", 0) + 1
+            if eval_every is not None and (epoch + 1) % eval_every == 0 and rank_world()[0] == 0:
+                score = self.evaluate().summary["return_mean"]
+                best = getattr(self, "best_return", None)
+                if score == score and (best is None or score > best):          # (NaN: no episode ended -- never an improvement)
+                    self.best_return = score
+                    best_path = os.path.join(self.archive_path, "best")
+                    os.makedirs(best_path, exist_ok=True)
+                    self._write_checkpoint(best_path)
             if hasattr(self.visualizer, "plot"):
                 self.visualizer.plot()
             if self.visualizer is not None and epoch % self.render_freq == 0:
@@ -123,6 +146,28 @@ class Pipeline:
 
     def test(self) -> None:
         self.buffer.sample()
+
+    EVAL_COLUMNS = ("episodes", "return_mean", "return_std", "return_min", "return_max", "length_mean", "timeout_frac", "early_frac")
+
+    def evaluate(self):
+        """One evaluation by `self.evaluator` (None: Evaluator(self.env, self.policy) -- 256 mean-action episodes of the nominal env,
+        or of randomly drawn vehicles when the env randomises).  Returns its result and appends its per-cell table to
+        <archive>/evaluation.csv: one row per epoch x cell, the swept factors in columns of their own."""
+        if getattr(self, "evaluator", None) is None:
+            from .evaluation import Evaluator
+            self.evaluator = Evaluator(self.env, self.policy)
+        res = self.evaluator.evaluate()
+        names = list(getattr(res, "sweep_names", ()))
+        path = os.path.join(self.archive_path, "evaluation.csv")
+        fresh = not os.path.exists(path)
+        with open(path, "a", newline="") as f:
+            w = csv.writer(f)
+            if fresh:
+                w.writerow(["epoch", "cell"] + names + list(self.EVAL_COLUMNS))
+            for row in res.table:
+                w.writerow([getattr(self, "epochs_done", 0), row["cell"]] + [repr(float(v)) for v in row["factors"]]
+                           + [row[k] for k in self.EVAL_COLUMNS])
+        return res
 
     def publish(self) -> None:
         os.makedirs(self.publish_path, exist_ok=True)

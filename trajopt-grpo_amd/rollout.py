@@ -195,6 +195,9 @@ class DeviceRollout:
         # by tg_env_randomize right after the reset, read by the `_dr` entry points on every path; None while randomisation is off
         self.env_params = None
         self._rand_spec = None
+        # callable (native trajectory, stream) an Evaluator installs: runs after the reset and the random draw of every rollout's
+        # prologue and may fill `env_params` (tg_env_param_grid) and edit slot 0 (tg_eval_tile_states); None everywhere else
+        self._param_source = None
 
     # ---- policy mean for time step t -------------------------------------------------
     def _refresh_weights(self, entry: bool = False):
@@ -256,18 +259,20 @@ class DeviceRollout:
                                           self.E if self.restart else 1, st), "tg_env_randomize")
 
     @torch.no_grad()
-    def run(self, initial_states=None, forced_actions=None) -> DeviceTrajectory:
+    def run(self, initial_states=None, forced_actions=None, deterministic: bool = False) -> DeviceTrajectory:
         """One rollout.  `initial_states` (N,S) and `forced_actions` (N,T,A) or (G,E,T,A)
-        replace the RNG draws (teacher-forced parity runs)."""
+        replace the RNG draws (teacher-forced parity runs).  deterministic=True: the action of every step is the actor's mean --
+        the same kernels with a sigma of exactly 0.0f, on every path (a = rn_add(mu, rn_mul(0, eps)) == mu: eps is finite)."""
         self.params = self.env.native_params()
         self._rand_spec = self.env.randomize_spec()
-        if self._rand_spec is None:
+        if self._rand_spec is None and self._param_source is None:
             self.env_params = None                        # off (again): no table on any path below, the graph replay included
         self.traj.host_valid_rows = None                 # (set again by Rollout_Buffer.sample for THIS rollout)
         self.traj.stats_fresh = False
         # the policy's covariance is read fresh every rollout (the reference reads self.cov in every forward,
         # actor_critic.py:131-136; the learner reads policy.var in every learn())
-        self._sigma = (C.c_float * self.A)(*[float(v) for v in torch.sqrt(self.policy.var)])
+        self._sigma = ((C.c_float * self.A)(*([0.0] * self.A)) if deterministic else
+                       (C.c_float * self.A)(*[float(v) for v in torch.sqrt(self.policy.var)]))
         if not hasattr(self, "_stream_host"):
             self._seed_host, self._stream_host = int(self.rng[0].item()), 0
         sample = forced_actions is None
@@ -275,12 +280,13 @@ class DeviceRollout:
             with torch.cuda.device(self.device):
                 self._enqueue_prepare(initial_states)
                 self._enqueue_fused(0, self.T)
-        elif (self.use_graph and sample and initial_states is None and self._rand_spec is None
-              and getattr(self.policy, "log_std", None) is None):
+        elif (self.use_graph and sample and initial_states is None and self._rand_spec is None and self._param_source is None
+              and not deterministic and getattr(self.policy, "log_std", None) is None):
             # (a randomised rollout does not take the graph: its parameter draw depends on the host stream id, like the reset, and
             #  the captured launches would be the plain entry points.  Nor does a learned-std policy: sigma is baked into the
             #  captured kernel arguments and moves with every learn(), so every rollout would pay a new capture -- it takes the
-            #  plain per-step launches below instead)
+            #  plain per-step launches below instead.  Nor does a deterministic run: its zero sigma is not the captured one, and it
+            #  leaves the captured sampling graph as it is)
             self._run_graph()
         else:
             with torch.cuda.device(self.device):
@@ -304,6 +310,8 @@ class DeviceRollout:
             init = torch.as_tensor(np.asarray(initial_states), dtype=self.dtype).reshape(self.n, self.S)
             self.traj.obs[:, 0, :].copy_(init.t().to(self.device))
         self._randomize(st)
+        if self._param_source is not None:
+            self._param_source(tr, st)                    # (an Evaluator: the parameter grid and the cells' common initial states)
 
     def _enqueue_fused(self, t_begin: int, t_end: int):
         """All steps [t_begin, t_end) in one persistent launch (tg_fused_rollout)."""
