@@ -2,9 +2,10 @@
 """Per-kernel register / scratch / code-size table of a built libtrajopt_grpo_hip.so, read from its gfx950 code objects (no GPU).
 
     tools/kernel_resources.py LIB.so [--match REGEX]            # one TSV line per kernel
-    tools/kernel_resources.py NEW.so --against OLD.so [--match REGEX]
+    tools/kernel_resources.py NEW.so --against OLD.so [--match REGEX] [--size-may-differ REGEX]
         # every kernel of OLD must exist in NEW under the same mangled name with the same .vgpr_count, .sgpr_count,
         # .private_segment_fixed_size and code size; exit status 1 and one line per difference otherwise
+        # --size-may-differ: kernels whose name matches may differ in code size alone (one SIZE line each, not a failure)
 
 The library's .hip_fatbin section is a run of clang offload bundles (one per translation unit); each holds one ELF code object
 whose AMDGPU metadata note lists the kernels.  Needs llvm-objcopy / llvm-readelf (ROCM_LLVM_BIN, default /opt/rocm/llvm/bin).
@@ -73,6 +74,7 @@ def main():
     ap.add_argument("lib")
     ap.add_argument("--against")
     ap.add_argument("--match", default=".")
+    ap.add_argument("--size-may-differ", default=None, metavar="REGEX")
     a = ap.parse_args()
     new = kernels(a.lib)
     pat = re.compile(a.match)
@@ -86,6 +88,8 @@ def main():
     old = kernels(a.against)
     bad = 0
     checked = 0
+    resized = 0
+    size_pat = re.compile(a.size_may_differ) if a.size_may_differ else None
     for name in sorted(old):
         if not pat.search(name):
             continue
@@ -93,10 +97,15 @@ def main():
         if name not in new:
             print(f"MISSING\t{name}")
             bad += 1
+        elif size_pat is not None and size_pat.search(name) and dict(new[name], size=0) == dict(old[name], size=0):
+            if new[name]["size"] != old[name]["size"]:
+                print(f"SIZE\t{name}\t{old[name]['size']} -> {new[name]['size']} ({new[name]['size'] - old[name]['size']:+d})\t{old[name]}")
+                resized += 1
         elif new[name] != old[name]:
             print(f"DIFFERS\t{name}\told {old[name]}\tnew {new[name]}")
             bad += 1
-    print(f"{checked} kernels of {a.against} checked against {a.lib}: {bad} differ; {len(set(new) - set(old))} kernels are new")
+    print(f"{checked} kernels of {a.against} checked against {a.lib}: {bad} differ"
+          + (f", {resized} differ in code size alone" if size_pat is not None else "") + f"; {len(set(new) - set(old))} kernels are new")
     return 1 if bad else 0
 
 

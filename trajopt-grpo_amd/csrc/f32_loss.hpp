@@ -1,7 +1,7 @@
-// The loss head of the fp32 chain learners (mlp_f32_chain.hip: H = 64 / 128; mlp_f32_wide.hip: H = 256): the arithmetic of
-// loss_kernels.hip::surrogate_loss_kernel (algorithms/ppo.py:159-179, grpo.py:122-140) for ONE row whose head outputs a lane holds.
+// The loss head of the fp32 chain learners (mlp_f32_chain.hip: H = 64 / 128; mlp_f32_wide.hip: H = 256) for ONE row whose head
+// outputs a lane holds: the loads, the stores and the workgroup's loss sums around loss_row.hpp's arithmetic.
 #pragma once
-#include "tg_common.hpp"
+#include "loss_row.hpp"
 
 namespace tg {
 
@@ -22,44 +22,11 @@ struct F32Loss {            // (as ChainLoss of mlp_fwd_chain.hip)
     const float* log_std; float* std_out;
 };
 
-// host: tg_chain_loss (+ the reference policy's penalty, or null) -> F32Loss
+// host: tg_chain_loss (+ the reference policy's penalty and the learned log-std, or null) -> F32Loss
 static inline void fill_f32_loss(F32Loss& L, const tg_chain_loss* loss, const tg_ref_penalty* ref = nullptr, const tg_learned_std* std = nullptr) {
-    L.kind = loss->kind; L.A = loss->act_dim;
-    L.act = loss->kind == 0 ? loss->d_act : loss->d_ret;
-    L.logp_old = loss->d_logp_old; L.adv = loss->d_adv; L.logp_old_out = loss->kind == 0 ? loss->d_logp_old_out : nullptr;
-    L.n_m = loss->norm_mean; L.n_i = loss->norm_inv; L.norm8 = loss->d_norm8;
-    float logdet = 0.f;
-    for (int k = 0; k < 4; ++k) {
-        L.inv_var[k] = (k < loss->act_dim && std == nullptr) ? 1.0f / loss->var[k] : 0.f;
-        if (k < loss->act_dim && std == nullptr) logdet += logf(loss->var[k]);
-    }
-    L.log_std = std != nullptr ? std->d_log_std : nullptr; L.std_out = std != nullptr ? std->d_out : nullptr;
-    L.logp_const = -0.5f * (float)loss->act_dim * 1.8378770664093453f - 0.5f * logdet;
-    L.epsilon = loss->epsilon; L.surr_coef = loss->surr_coef; L.critic_coef = loss->critic_coef; L.kl_coef = loss->kl_coef;
+    fill_loss_common(L, loss, ref, std);
+    L.logp_old_out = loss->kind == 0 ? loss->d_logp_old_out : nullptr;
     L.dout4 = (float*)loss->d_dout8; L.work = loss->d_work;
-    L.logp_ref = ref != nullptr ? ref->d_logp_ref : nullptr; L.ref_coef = ref != nullptr ? ref->coef : 0.f;
-}
-
-// device, at kernel entry: the normalisation pair and the coefficients from the device when PPO keeps them there
-// kStd: also the Gaussian's constants from the policy's log_std (uniform loads; columns >= A keep inv_var = 0)
-template <bool kStd = false>
-__device__ static inline void f32_loss_from_device(F32Loss& L) {
-    if (L.norm8 != nullptr) {
-        const int q = L.kind == 1 ? 2 : 0;
-        L.n_m = L.norm8[q]; L.n_i = L.norm8[q + 1];
-        L.surr_coef = L.norm8[4]; L.critic_coef = L.norm8[5]; L.kl_coef = L.norm8[6];
-    }
-    if constexpr (kStd) {
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < L.A) {
-                const float ls = L.log_std[k];
-                L.inv_var[k] = expf(-2.0f * ls);
-                sum += ls;
-            }
-        L.logp_const = -0.5f * (float)L.A * 1.8378770664093453f - sum;
-    }
 }
 
 // The per-row inputs of the loss head, loadable ahead of the row's products (f32_loss_load) ...
@@ -91,23 +58,17 @@ __device__ static inline F32LossIn f32_loss_load(const F32Loss& L, int64_t rowc)
 // `writer` decide what is written (one lane per row writes).  kZeroInvalid: a lane past the last row gets g = 0 (mlp_f32_chain.hip);
 // false: it keeps the clamped row's own g -- the 16-row kernels let such lanes recompute and re-store the last row's values
 // (identical bytes), so that every store instruction is issued whatever the row count.
-// kRef: GRPO's penalty to the reference policy, x = lp_ref - lp, D = exp(x) - x - 1 (grpo.py:133): D joins the KL sum and
-// d loss / d lp gains ref_coef (exp(x) - 1), ref_coef = coef * beta (the term enters J as - beta D).
-// kStd: the row's contribution to d loss / d log_std, dlp (dmu_k^2 inv_var_k - 1), to std_out[row][4] (valid rows, the writer lane)
+// kRef: GRPO's penalty to the reference policy joins c_kl and g.
+// kStd: the row's contribution to d loss / d log_std goes to std_out[row][4] (valid rows, the writer lane)
 template <bool kZeroInvalid = true, bool kRef = false, bool kStd = false>
 __device__ static inline void f32_loss_compute(const F32Loss& L, const F32LossIn& in, const float (&o)[4], int64_t row, bool valid, bool writer,
                                                float (&g)[4], float& c_surr, float& c_crit, float& c_kl) {
     g[0] = g[1] = g[2] = g[3] = 0.f;
     c_surr = c_crit = c_kl = 0.f;
     if (L.kind == 0) {
-        float quad = 0.f, dmu[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float d = (k < L.A ? in.act[k] : 0.f) - o[k];
-            dmu[k] = d;
-            quad += d * d * L.inv_var[k];
-        }
-        const float lp = -0.5f * quad + L.logp_const;
+        const Gauss4 G = loss_gauss4(L);
+        float dmu[4];
+        const float lp = gauss4_logp([&](int k) { return k < L.A ? in.act[k] : 0.f; }, [&](int k) { return o[k]; }, G, dmu);
         float lpo;
         if (L.logp_old_out != nullptr) {
             lpo = lp;
@@ -115,39 +76,16 @@ __device__ static inline void f32_loss_compute(const F32Loss& L, const F32LossIn
         } else {
             lpo = in.lpo;
         }
-        const float adv = (in.adv - L.n_m) * L.n_i;
-        const float rho = expf(lp - lpo);
-        const float lo = 1.0f - L.epsilon, hi = 1.0f + L.epsilon;
-        const float surr1 = rho * adv, surr2 = fminf(fmaxf(rho, lo), hi) * adv;
-        const bool inside = (rho >= lo) && (rho <= hi);
-        const float w = inside ? 1.0f : (surr1 < surr2 ? 1.0f : 0.0f);
-        c_surr = fminf(surr1, surr2);
-        float dlp = L.surr_coef * adv * rho * w;
-        if (L.kl_coef != 0.0f) {
-            const float eo = expf(lpo);
-            c_kl = eo * (lpo - lp);
-            dlp -= L.kl_coef * eo;
-        }
-        if constexpr (kRef) {
-            const float x = in.lref - lp;
-            const float em1 = expf(x) - 1.0f;
-            c_kl += em1 - x;
-            dlp += L.ref_coef * em1;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) g[k] = dlp * dmu[k] * L.inv_var[k];
+        const ActorTerms t = loss_actor_terms<kRef>(lp, lpo, (in.adv - L.n_m) * L.n_i, L.epsilon, L.surr_coef, L.kl_coef, in.lref, L.ref_coef);
+        c_surr = t.c_surr; c_kl = t.c_kl;
+        gauss4_mean_grad(t.dlp, dmu, G, g);
         if constexpr (kStd) {
-            if (valid && writer) {
-                float gs[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) gs[k] = k < L.A ? dlp * (dmu[k] * dmu[k] * L.inv_var[k] - 1.0f) : 0.f;
-                *reinterpret_cast<float4*>(L.std_out + row * 4) = float4{gs[0], gs[1], gs[2], gs[3]};
-            }
+            if (valid && writer) *reinterpret_cast<float4*>(L.std_out + row * 4) = gauss4_log_std_grad(t.dlp, dmu, G, L.A);
         }
     } else {
-        const float d = o[0] - (in.act[0] - L.n_m) * L.n_i;
-        c_crit = d * d;
-        g[0] = L.critic_coef * 2.0f * d;
+        const CriticTerms t = loss_critic_terms(o[0], in.act[0], L.n_m, L.n_i, L.critic_coef);
+        c_crit = t.c_crit;
+        g[0] = t.g0;
     }
     if constexpr (kZeroInvalid) {
         if (!valid) { g[0] = g[1] = g[2] = g[3] = 0.f; }
@@ -160,6 +98,29 @@ __device__ static inline void f32_loss_row(const F32Loss& L, const float (&o)[4]
                                            float (&g)[4], float& c_surr, float& c_crit, float& c_kl) {
     const F32LossIn in = f32_loss_load<kRef>(L, rowc);
     f32_loss_compute<kZeroInvalid, kRef, kStd>(L, in, o, row, valid, writer, g, c_surr, c_crit, c_kl);
+}
+
+// The workgroup's four f64 loss sums: lanes -> wave (fixed shuffle tree) -> workgroup (waves in index order): deterministic.
+// `red_s`: kWaves x 4 doubles of LDS; `work`: the grid's f64 [grid][4]; every thread of the workgroup calls.
+template <int kWaves>
+__device__ static inline void f32_loss_sums_store(double (&v)[4], double* red_s, double* work) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
+    }
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) red_s[wave * 4 + k] = v[k];
+    }
+    __syncthreads();
+    if (tid < 4) {
+        double t = 0.0;
+        for (int w = 0; w < kWaves; ++w) t += red_s[w * 4 + tid];
+        work[(int64_t)blockIdx.x * 4 + tid] = t;
+    }
 }
 
 }  // namespace tg

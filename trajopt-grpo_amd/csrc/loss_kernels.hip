@@ -7,7 +7,7 @@
 // its inputs and one write of the gradient instead of ~15 elementwise launches.
 // Loss scalars are reduced deterministically: wavefront shuffle -> per-block partial in
 // fp64 -> fixed-order final pass (no float atomics).
-#include "tg_common.hpp"
+#include "loss_row.hpp"
 
 namespace tg {
 
@@ -15,6 +15,29 @@ constexpr int kLossBlocks = 1024;   // persistent grid-stride blocks
 constexpr int kLossThreads = 256;
 
 struct Var8 { float inv_var[8]; float logp_const; };
+
+// Four f64 sums of a 256-thread block, deterministic: lanes -> wave (fixed shuffle tree) -> the four waves as ((w0 + w1) + w2) + w3.
+// Thread j < 4 returns sum j, the others 0.
+__device__ static inline double block_sum4_f64(double (&acc)[4]) {
+    __shared__ double sh[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sh[j][w] = acc[j];
+    }
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x < 4) {
+        const int j = threadIdx.x;
+        t = ((sh[j][0] + sh[j][1]) + sh[j][2]) + sh[j][3];
+    }
+    return t;
+}
 
 __device__ static inline float gaussian_logp(const float* mu, const float* a, const Var8& v, int A) {
     float quad = 0.0f;
@@ -50,19 +73,19 @@ struct LossK {
     const float* log_std; float* std_out;       // kStd only (tg_learned_std): device log_std [A]; out f32 [M][4]
 };
 
-// kRef: GRPO's KL penalty to a frozen reference policy (tg_surrogate_loss_ref): x = lp_ref - lp, D = exp(x) - x - 1 into the KL sum,
-// d total / d logp += ref_coef (exp(x) - 1)
+// The row arithmetic is loss_row.hpp's; here: the A-templated strided loads, the mask, the stores and the f64 sums.
+// kRef: GRPO's KL penalty to a frozen reference policy (tg_surrogate_loss_ref)
 // kStd: the policy's learned log-std (tg_surrogate_loss_std): inv_var / logp_const are formed here from the device's log_std, and
-// the row's contribution to d total / d log_std, dlp (dmu_k^2 inv_var_k - 1), goes to std_out[row][4] (zeros for a masked row)
+// the row's contribution to d total / d log_std goes to std_out[row][4] (zeros for a masked row)
 template <int A, bool kRef = false, bool kStd = false>
 __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
-    __shared__ double sh[4][4];
+    static_assert(!kStd || A <= 4, "a learned log-std has at most four columns");
     Var8 v = p.v;
     if constexpr (kStd) {
-        float sum = 0.f;
+        const Gauss4 G = gauss4_from_log_std([&](int k) { return p.log_std[k]; }, A, Gauss4{});
 #pragma unroll
-        for (int k = 0; k < A; ++k) { const float ls = p.log_std[k]; v.inv_var[k] = expf(-2.0f * ls); sum += ls; }
-        v.logp_const = -0.5f * (float)A * 1.8378770664093453f - sum;
+        for (int k = 0; k < A; ++k) v.inv_var[k] = G.inv_var[k];
+        v.logp_const = G.logp_const;
     }
     double s_surr = 0, s_crit = 0, s_kl = 0, s_cnt = 0;
     float n_am = 0.f, n_ai = 1.f, n_rm = 0.f, n_ri = 1.f;
@@ -71,7 +94,6 @@ __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
     float surr_coef = p.surr_coef, critic_coef = p.critic_coef, kl_coef = p.kl_coef;
     if (p.coef != nullptr) { surr_coef = p.coef[0]; critic_coef = p.coef[1]; kl_coef = p.coef[2]; }
     [[maybe_unused]] const float ref_coef = kRef ? p.ref_coef : 0.0f;
-    const float lo = 1.0f - p.epsilon, hi = 1.0f + p.epsilon;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.M; i += (int64_t)gridDim.x * blockDim.x) {
         const bool valid = p.mask == nullptr || p.mask[i] != 0;
         float g[A];
@@ -84,39 +106,23 @@ __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
 #pragma unroll
             for (int k = 0; k < A; ++k) { mu[k] = p.mean[i * p.mean_rs + k]; a[k] = p.act[i * p.act_rs + k * p.act_cs]; }
             const float lp = gaussian_logp(mu, a, v, A);
-            const float lpo = p.logp_old[i];
-            const float adv = (p.adv[i] - n_am) * n_ai;
-            const float rho = expf(lp - lpo);
-            const float surr1 = rho * adv;
-            const float surr2 = fminf(fmaxf(rho, lo), hi) * adv;
-            // torch.min / torch.clamp subgradients: inside the clip range both branches carry A
-            // (tie -> half each); outside, only the unclipped branch when it is the smaller one.
-            const bool inside = (rho >= lo) && (rho <= hi);
-            const float w = inside ? 1.0f : (surr1 < surr2 ? 1.0f : 0.0f);
-            s_surr += (double)fminf(surr1, surr2);
-            // d total / d logp
-            float dlp = surr_coef * adv * rho * w;
-            if (kl_coef != 0.0f) {
-                const float eo = expf(lpo);
-                s_kl += (double)(eo * (lpo - lp));
-                dlp -= kl_coef * eo;
-            }
-            if constexpr (kRef) {
-                const float x = p.logp_ref[i] - lp;
-                const float em1 = expf(x) - 1.0f;
-                s_kl += (double)(em1 - x);
-                dlp += ref_coef * em1;
-            }
+            float lref = 0.f;
+            if constexpr (kRef) lref = p.logp_ref[i];
+            const ActorTerms t = loss_actor_terms<kRef>(lp, p.logp_old[i], (p.adv[i] - n_am) * n_ai, p.epsilon, surr_coef, kl_coef, lref, ref_coef);
+            s_surr += (double)t.c_surr;
+            // (the old-policy term and the reference term are added in float first: ref_penalty_check refuses kl_coef != 0 beside a
+            // reference penalty, so at most one of the two is ever non-zero and the sum is that term's own value)
+            s_kl += (double)t.c_kl;
 #pragma unroll
-            for (int k = 0; k < A; ++k) g[k] = dlp * (a[k] - mu[k]) * v.inv_var[k];   // d logp / d mu_k
+            for (int k = 0; k < A; ++k) g[k] = gauss_mean_grad(t.dlp, a[k] - mu[k], v.inv_var[k]);   // d logp / d mu_k
             if constexpr (kStd) {
 #pragma unroll
-                for (int k = 0; k < (A < 4 ? A : 4); ++k) gs[k] = dlp * ((a[k] - mu[k]) * (a[k] - mu[k]) * v.inv_var[k] - 1.0f);
+                for (int k = 0; k < A; ++k) gs[k] = gauss_log_std_grad(t.dlp, a[k] - mu[k], v.inv_var[k]);
             }
             if (p.value != nullptr) {
-                const float d = p.value[i] - (p.ret[i] - n_rm) * n_ri;
-                s_crit += (double)(d * d);
-                gv = critic_coef * 2.0f * d;
+                const CriticTerms c = loss_critic_terms(p.value[i], p.ret[i], n_rm, n_ri, critic_coef);
+                s_crit += (double)c.c_crit;
+                gv = c.g0;
             }
             s_cnt += 1.0;
         }
@@ -126,45 +132,18 @@ __global__ __launch_bounds__(256) void surrogate_loss_kernel(LossK p) {
         if constexpr (kStd) *reinterpret_cast<float4*>(p.std_out + i * 4) = float4{gs[0], gs[1], gs[2], gs[3]};
     }
     double acc[4] = {s_surr, s_crit, s_kl, s_cnt};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sh[j][w] = acc[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int j = threadIdx.x;
-        p.work[(int64_t)blockIdx.x * 4 + j] = ((sh[j][0] + sh[j][1]) + sh[j][2]) + sh[j][3];
-    }
+    const double t = block_sum4_f64(acc);
+    if (threadIdx.x < 4) p.work[(int64_t)blockIdx.x * 4 + threadIdx.x] = t;
 }
 
 __global__ __launch_bounds__(256) void loss_final_kernel(const double* __restrict__ work, int nblocks, double* __restrict__ sums) {
-    __shared__ double sh[4][4];
     double acc[4] = {0, 0, 0, 0};
     for (int b = threadIdx.x; b < nblocks; b += blockDim.x) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] += work[(int64_t)b * 4 + j];
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sh[j][w] = acc[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int j = threadIdx.x;
-        sums[j] = ((sh[j][0] + sh[j][1]) + sh[j][2]) + sh[j][3];
-    }
+    const double t = block_sum4_f64(acc);
+    if (threadIdx.x < 4) sums[threadIdx.x] = t;
 }
 
 // d loss / d log_std: column sums of the heads' [rows][4] side output in f64, fixed order: a grid-stride pass into per-block
@@ -172,27 +151,13 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const double* __restric
 constexpr int kStdBlocks = 256;
 
 __global__ __launch_bounds__(256) void log_std_partial_kernel(const float4* __restrict__ rows4, int64_t rows, double* __restrict__ work) {
-    __shared__ double sh[4][4];
     double acc[4] = {0, 0, 0, 0};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {
         const float4 r = rows4[i];
         acc[0] += (double)r.x; acc[1] += (double)r.y; acc[2] += (double)r.z; acc[3] += (double)r.w;
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sh[j][w] = acc[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int j = threadIdx.x;
-        work[(int64_t)blockIdx.x * 4 + j] = ((sh[j][0] + sh[j][1]) + sh[j][2]) + sh[j][3];
-    }
+    const double t = block_sum4_f64(acc);
+    if (threadIdx.x < 4) work[(int64_t)blockIdx.x * 4 + threadIdx.x] = t;
 }
 
 __global__ __launch_bounds__(64) void log_std_final_kernel(const double* __restrict__ work, int nblocks, int A, float add, float* __restrict__ grad) {

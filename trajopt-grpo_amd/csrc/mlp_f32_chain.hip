@@ -105,7 +105,7 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
     // (a LOCAL copy: writing into the by-value argument struct itself sends all of it to scratch -- 272 B per lane and 23 more
     // registers in this kernel, 9 % of a small PPO epoch, measured in round 5)
     F32Loss L = a.loss;
-    if constexpr (kTrain) f32_loss_from_device<kStd>(L);
+    if constexpr (kTrain) loss_from_device<kStd>(L);
     const bool resident = a.resident != 0;
     // LDS (f32_chain_lds() on the host computes the same sizes): the block ring (2 blocks) or the whole resident stream, the
     // first layer's fragments, bias / head tables, the ReLU mask bits of the (n_hh + 1) hidden layers, the loss-sum scratch
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
         if constexpr (!kTrain) {
             if (valid && h == 0) *reinterpret_cast<float4*>(a.out + row * 4) = float4{o[0], o[1], o[2], o[3]};
         } else {
-            // ---- loss head (loss_kernels.hip::surrogate_loss_kernel, same arithmetic), evaluated by both lane halves ----
+            // ---- loss head (f32_loss.hpp), evaluated by both lane halves ----
             float g[4], c_surr, c_crit, c_kl;
             f32_loss_row<true, kRef, kStd>(L, o, row, rowc, valid, h == 0, g, c_surr, c_crit, c_kl);
             if (valid && h == 0) {
@@ -391,24 +391,8 @@ __global__ __launch_bounds__(512, 2) void mlp_f32_chain_kernel(F32ChainArgs a) {
 #undef TG_F32_BLOCK_BEGIN
 #undef TG_F32_BLOCK_END
     if constexpr (kTrain) {
-        // loss sums: lanes -> wave (fixed shuffle tree) -> workgroup (waves in order): deterministic
         double v[4] = {s_surr, s_crit, s_kl, s_cnt};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-        }
-        __syncthreads();
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red_s[wave * 4 + k] = v[k];
-        }
-        __syncthreads();
-        if (tid < 4) {
-            double t = 0.0;
-            for (int w = 0; w < 8; ++w) t += red_s[w * 4 + tid];
-            L.work[(int64_t)blockIdx.x * 4 + tid] = t;
-        }
+        f32_loss_sums_store<8>(v, red_s, L.work);
     }
     if constexpr (kTrain) { TG_CLOCK_PROBE_END(g_probe_f32_chain) }
 }

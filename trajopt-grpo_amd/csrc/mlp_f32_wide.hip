@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_wide_kernel(F32WideArgs a) {
     const int64_t n_rounds = (rows + 63) / 64;
     F32Loss L = a.loss;                                                       // (a local copy: scalars in registers, not a re-read kernarg)
     if constexpr (kTrain) {
-        f32_loss_from_device<kStd>(L);
+        loss_from_device<kStd>(L);
         TG_CLOCK_PROBE_BEGIN(g_probe_f32_wide)
     }
     // a.acts[l] / a.dz[l] with a run-time l would put the whole argument struct into scratch: uniform selects instead
@@ -318,24 +318,8 @@ __global__ __launch_bounds__(256, 2) void mlp_f32_wide_kernel(F32WideArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #undef TG_WIDE_HEAD
     if constexpr (kTrain) {
-        // loss sums: lanes -> wave (fixed shuffle tree) -> workgroup (waves in order): deterministic
         double v[4] = {s_surr, s_crit, s_kl, s_cnt};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-        }
-        __syncthreads();
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red_s[wave * 4 + k] = v[k];
-        }
-        __syncthreads();
-        if (tid < 4) {
-            double t = 0.0;
-            for (int w = 0; w < WPW; ++w) t += red_s[w * 4 + tid];
-            L.work[(int64_t)blockIdx.x * 4 + tid] = t;
-        }
+        f32_loss_sums_store<WPW>(v, red_s, L.work);
         TG_CLOCK_PROBE_END(g_probe_f32_wide)
     }
 }
@@ -432,7 +416,7 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
     const int64_t n_wr = (rows + 15) / 16;                               // wave-rounds of 16 rows
     F32Loss L = a.loss;
     if constexpr (kTrain) {
-        f32_loss_from_device<kStd>(L);
+        loss_from_device<kStd>(L);
         TG_CLOCK_PROBE_BEGIN(g_probe_f32_res)
     }
     for (int q = tid; q < n_stream * BLK; q += 64 * WPW) strm[q] = a.stream[q];
@@ -656,22 +640,7 @@ __global__ __launch_bounds__(64 * res_waves(kTrain)) void mlp_f32_res_kernel(F32
     }
     if constexpr (kTrain) {
         double v[4] = {s_surr, s_crit, s_kl, s_cnt};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-        }
-        __syncthreads();
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red_s[wave * 4 + k] = v[k];
-        }
-        __syncthreads();
-        if (tid < 4) {
-            double t = 0.0;
-            for (int w = 0; w < WPW; ++w) t += red_s[w * 4 + tid];
-            L.work[(int64_t)blockIdx.x * 4 + tid] = t;
-        }
+        f32_loss_sums_store<WPW>(v, red_s, L.work);
         TG_CLOCK_PROBE_END(g_probe_f32_res)
     }
 }

@@ -26,6 +26,7 @@
 //     per row in place of the head output, the loss sums, and the head's weight / bias gradient contracted on chip with the
 //     top activation, which is then never written (see ChainLoss below).
 #include "mfma_ring.hpp"
+#include "loss_row.hpp"
 
 namespace tg {
 
@@ -37,10 +38,10 @@ TG_CLOCK_PROBE_VAR(g_probe_fwd_chain_plain, attach_probe_fwd_chain_plain)  // ev
 struct ChainActs { uint16_t* p[kChainMaxHidden]; uint32_t* m[kChainMaxHidden]; };   // activations, ReLU mask bits (or null)
 
 // kHead: the loss head and the head's weight gradient inside the forward pass (tg_mlp_forward_chain_loss).  The clipped-surrogate
-// / squared-error gradient of a row is a function of the head output the lane holds and of per-row inputs (loss_kernels.hip: the
-// same arithmetic), so d loss / d output is known one block after the top activation: the eight waves pass that activation
-// block by block through shared LDS tiles and split the product dOut^T . a_top over the OUTPUT (as mlp_bwd_chain.hip does for the
-// first layer): the top activation is never written (-512 B per row) and tg_mlp_weight_grad has no DH job (-528 B per row).
+// / squared-error gradient of a row is a function of the head output the lane holds and of per-row inputs (loss_row.hpp), so
+// d loss / d output is known one block after the top activation: the eight waves pass that activation block by block through
+// shared LDS tiles and split the product dOut^T . a_top over the OUTPUT (as mlp_bwd_chain.hip does for the first layer): the
+// top activation is never written (-512 B per row) and tg_mlp_weight_grad has no DH job (-528 B per row).
 struct ChainLoss {                          // (kept small: every field is a scalar register for the whole kernel)
     int32_t kind, A;                        // 0: actor (clipped surrogate + KL-ish penalty), 1: critic (squared error); A <= 4 outputs
                                             // 2: actor whose old policy is the current one: `logp_old` is WRITTEN (the row's own
@@ -207,24 +208,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     static_assert(!kStd || kHead, "the learned log-std is a term of the fused head");
     // (written into the by-value argument as norm8's values are below: the compiler's resource report shows 0 B of scratch and no
     // vector-register spill for every instantiation of this kernel, the kStd ones included -- the fields stay scalar registers)
-    if constexpr (kStd) {                                               // (uniform scalar loads, as norm8's below)
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < L.A) {
-                const float ls = L.log_std[k];
-                L.inv_var[k] = expf(-2.0f * ls);
-                sum += ls;
-            }
-        L.logp_const = -0.5f * (float)L.A * 1.8378770664093453f - sum;
-    }
-    if constexpr (kHead) {
-        if (L.norm8 != nullptr) {                                       // (uniform scalar loads, before anything is in flight)
-            const int q = L.kind == 1 ? 2 : 0;
-            L.n_m = L.norm8[q]; L.n_i = L.norm8[q + 1];
-            L.surr_coef = L.norm8[4]; L.critic_coef = L.norm8[5]; L.kl_coef = L.norm8[6];
-        }
-    }
+    if constexpr (kHead) loss_from_device<kStd>(L);
     constexpr int MT = H / 32, KS = H / 16, K8 = H / 32;               // blocks per layer, 1-KiB pieces per block, k-steps per block
     constexpr int P = D - 1;
     // counted wait for block c: all but the youngest N vector-memory operations have retired.  Behind DMA(c) there are
@@ -437,9 +421,9 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
             }
             if constexpr (kHead) {
                 TG_HEAD_LDS
-                // ---- the loss head (loss_kernels.hip::surrogate_loss_kernel, same arithmetic): the g == 0 lanes hold outputs 0..3 of
-                // their two rows; d loss / d output goes to dout8 (for the backward chain) and, padded to 16 columns, to this
-                // wave's LDS tile (the A operand of the head's weight gradient) ----
+                // ---- the loss head (loss_row.hpp's arithmetic): the g == 0 lanes hold outputs 0..3 of their two rows;
+                // d loss / d output goes to dout8 (for the backward chain) and, padded to 16 columns, to this wave's LDS tile (the A
+                // operand of the head's weight gradient) ----
                 char* dt = dtiles + wave * 1024;
                 if (grp == 0) {
                     // (few values live at a time: the kernel has no registers to spare, and a spill here costs the whole ring)
@@ -449,52 +433,32 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                         const int rl = 16 * c + col;
                         const bool valid = row0 + rl < rows;              // clamped duplicates of the last row contribute nothing
                         float g[4] = {0.f, 0.f, 0.f, 0.f};
+                        // (the tile's values picked by explicit selects: indexed by the loop counter, the two arrays go to scratch)
+                        const f32x4 mu = c == 0 ? acc[0] : acc[1];
+                        const int64_t rc = c == 0 ? rowc[0] : rowc[1];
                         if (valid) {
                             if (L.kind != 1) {
-                                float quad = 0.f, dmu[4];
-#pragma unroll
-                                for (int k = 0; k < 4; ++k) {              // (inv_var is 0 beyond the net's outputs; the tile slots hold zeros)
-                                    const float d = (k < L.A ? lds_loadf(lin + 32 * k + rl) : 0.f) - acc[c][k];
-                                    dmu[k] = d;
-                                    quad += d * d * L.inv_var[k];
-                                }
-                                const float lp = -0.5f * quad + L.logp_const;
+                                const Gauss4 G = loss_gauss4(L);
+                                float dmu[4];               // (the tile slots of the columns >= A hold zeros)
+                                const float lp = gauss4_logp([&](int k) { return k < L.A ? lds_loadf(lin + 32 * k + rl) : 0.f; },
+                                                             [mu](int k) { return mu[k]; }, G, dmu);
                                 float lpo = lds_loadf(lin + 32 * 4 + rl);
                                 if (L.kind == 2) {
                                     lpo = lp;
-                                    const_cast<float*>(L.logp_old)[rowc[c]] = lp;      // (valid rows only: inside `if (valid)`)
+                                    const_cast<float*>(L.logp_old)[rc] = lp;      // (valid rows only: inside `if (valid)`)
                                 }
                                 const float adv = (lds_loadf(lin + 32 * 5 + rl) - L.n_m) * L.n_i;
-                                const float rho = expf(lp - lpo);
-                                const float lo = 1.0f - L.epsilon, hi = 1.0f + L.epsilon;
-                                const float surr1 = rho * adv, surr2 = fminf(fmaxf(rho, lo), hi) * adv;
-                                const bool inside = (rho >= lo) && (rho <= hi);
-                                const float w = inside ? 1.0f : (surr1 < surr2 ? 1.0f : 0.0f);
-                                c_surr = fminf(surr1, surr2);
-                                float dlp = L.surr_coef * adv * rho * w;
-                                if (L.kl_coef != 0.0f) {
-                                    const float eo = expf(lpo);
-                                    c_kl = eo * (lpo - lp);
-                                    dlp -= L.kl_coef * eo;
-                                }
-                                if constexpr (kRef) {          // x = lp_ref - lp, D = exp(x) - x - 1 (f32_loss.hpp: the same arithmetic)
-                                    const float x = lds_loadf(lin + 32 * 6 + rl) - lp;
-                                    const float em1 = expf(x) - 1.0f;
-                                    c_kl += em1 - x;
-                                    dlp += L.ref_coef * em1;
-                                }
-#pragma unroll
-                                for (int k = 0; k < 4; ++k) g[k] = dlp * dmu[k] * L.inv_var[k];
-                                if constexpr (kStd) {          // (one more store behind the head's: the counted waits only get stricter)
-                                    *reinterpret_cast<float4*>(L.std_out + rowc[c] * 4) =
-                                        float4{dlp * (dmu[0] * dmu[0] * L.inv_var[0] - 1.0f), L.A > 1 ? dlp * (dmu[1] * dmu[1] * L.inv_var[1] - 1.0f) : 0.f,
-                                               L.A > 2 ? dlp * (dmu[2] * dmu[2] * L.inv_var[2] - 1.0f) : 0.f,
-                                               L.A > 3 ? dlp * (dmu[3] * dmu[3] * L.inv_var[3] - 1.0f) : 0.f};
-                                }
+                                float lref = 0.f;
+                                if constexpr (kRef) lref = lds_loadf(lin + 32 * 6 + rl);
+                                const ActorTerms t = loss_actor_terms<kRef>(lp, lpo, adv, L.epsilon, L.surr_coef, L.kl_coef, lref, L.ref_coef);
+                                c_surr = t.c_surr; c_kl = t.c_kl;
+                                gauss4_mean_grad(t.dlp, dmu, G, g);
+                                if constexpr (kStd)            // (one more store behind the head's: the counted waits only get stricter)
+                                    *reinterpret_cast<float4*>(L.std_out + rc * 4) = gauss4_log_std_grad(t.dlp, dmu, G, L.A);
                             } else {
-                                const float d = acc[c][0] - (lds_loadf(lin + rl) - L.n_m) * L.n_i;
-                                c_crit = d * d;
-                                g[0] = L.critic_coef * 2.0f * d;
+                                const CriticTerms t = loss_critic_terms(mu[0], lds_loadf(lin + rl), L.n_m, L.n_i, L.critic_coef);
+                                c_crit = t.c_crit;
+                                g[0] = t.g0;
                             }
                             c_cnt = 1.0f;
                         }
@@ -513,7 +477,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                         typedef float f32x2 __attribute__((ext_vector_type(2)));
                         const uint4 o = {__builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{g[0], g[1]}, bf16x2)),
                                          __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{g[2], g[3]}, bf16x2)), 0u, 0u};
-                        if (valid) *reinterpret_cast<uint4*>(L.dout8 + rowc[c] * 8) = o;     // (a clamped duplicate must not zero the last row)
+                        if (valid) *reinterpret_cast<uint4*>(L.dout8 + rc * 8) = o;     // (a clamped duplicate must not zero the last row)
                         lds_store16(dt + rl * 32, o);
                         lds_store16(dt + rl * 32 + 16, uint4{0u, 0u, 0u, 0u});
                     }
@@ -681,24 +645,12 @@ static int forward_chain_loss(const void* d_x, const void* d_wfrag, const float*
     }
     TG_REQUIRE(!d_acts[0], "tg_mlp_forward_chain_loss: the first activation is recomputed by tg_mlp_weight_grad, not stored");
     ChainLoss L{};
-    L.kind = loss->kind; L.A = loss->act_dim;
-    L.act = loss->kind == 0 ? loss->d_act : loss->d_ret;
-    L.logp_old = loss->d_logp_old; L.adv = loss->d_adv;
+    fill_loss_common(L, loss, use_ref ? ref : nullptr, use_std ? std : nullptr);
     if (loss->kind == 0 && loss->d_logp_old_out != nullptr) {      // the old policy is the current one: this pass writes the old log-probabilities
         L.kind = 2;
         L.logp_old = loss->d_logp_old_out;
     }
-    L.n_m = loss->norm_mean; L.n_i = loss->norm_inv; L.norm8 = loss->d_norm8;
-    float logdet = 0.f;
-    for (int k = 0; k < 4; ++k) {
-        L.inv_var[k] = (k < loss->act_dim && !use_std) ? 1.0f / loss->var[k] : 0.f;
-        if (k < loss->act_dim && !use_std) logdet += logf(loss->var[k]);
-    }
-    L.logp_const = -0.5f * (float)loss->act_dim * 1.8378770664093453f - 0.5f * logdet;
-    L.log_std = use_std ? std->d_log_std : nullptr; L.std_out = use_std ? std->d_out : nullptr;
-    L.epsilon = loss->epsilon; L.surr_coef = loss->surr_coef; L.critic_coef = loss->critic_coef; L.kl_coef = loss->kl_coef;
     L.dout8 = (uint16_t*)loss->d_dout8; L.head_slabs = loss->d_head_slabs; L.work = loss->d_work; L.bias_partial = loss->d_bias_partial;
-    L.logp_ref = use_ref ? ref->d_logp_ref : nullptr; L.ref_coef = use_ref ? ref->coef : 0.0f;
     hipStream_t st = (hipStream_t)stream;
     const int n_hh = n_hidden_layers - 1;
     if (use_std) {                                      // (separate instantiations: the plain heads below are untouched)
