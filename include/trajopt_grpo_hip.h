@@ -474,6 +474,31 @@ int  tg_log_std_grad_blocks(void);
 int  tg_log_std_grad(const float* d_rows4, int64_t rows, int32_t act_dim, float add, float* d_grad, double* d_work, void* stream);
 /* (the fp32 chain learners' `_std` entry points are declared beside their plain ones below) */
 
+/* ---- How far the updates of a learn() moved the policy, and the learning rate that follows (rsl_rl's schedule="adaptive") ----
+ * tg_policy_shift, one chunk of rows: lp = the Gaussian log-probability of the row's action under d_mean (float32, the row
+ * arithmetic of tg_gaussian_logp; strides as there), with either `var` (HOST float [act_dim], act_dim <= 8) or `d_log_std` (DEVICE
+ * float [act_dim], act_dim <= 4, read at kernel entry as the `_std` heads read it: no host read of a learned std) -- exactly one of
+ * the two is non-NULL.  Per row, in float64: d = lp - logp_old (exact), k3 = expm1(d) - d (>= 0: an estimate of KL(old || new)),
+ * clipped = d < log_lo || d > log_hi (the caller forms log_lo = log1p(-epsilon), log_hi = log1p(epsilon) in double).
+ * Workgroup b of the launch covers rows [4096 b, 4096 (b + 1)) (at most 1024 workgroups, grid-stride beyond) and leaves ONE partial
+ *   d_partials[slot + b][4] = {rows, sum k3, clipped rows, sum d}
+ * added in a fixed order (shuffle tree, then the four waves in wave order; no floating-point atomics): which rows a thread adds
+ * depends on `rows` alone.  tg_policy_shift_blocks(rows) partials are written (0 for rows == 0: nothing is launched); the caller
+ * gives each chunk its own `slot`.
+ * tg_policy_shift_finish (one workgroup): d_sums[4] = the n_partials partials added in index order (zeros for n_partials == 0).
+ * tg_lr_adapt (one thread, float64): d_out4 = {kl, clip_fraction, lr_in, lr_out} from the (all-reduced) sums,
+ *   kl = sums[1] / sums[0], clip_fraction = sums[2] / sums[0], lr_in = lr, and with rows = sums[0]
+ *   lr_out = fmax(lr / factor, lr_min)   if desired_kl > 0 && rows > 0 && kl > 2 desired_kl
+ *            fmin(lr * factor, lr_max)   if desired_kl > 0 && rows > 0 && kl < desired_kl / 2
+ *            lr                          otherwise (a NaN kl included: every comparison is false; desired_kl <= 0: measure only). */
+int  tg_policy_shift_blocks(int64_t rows);
+int  tg_policy_shift(const float* d_mean, int64_t mean_row_stride, const float* d_act, int64_t act_row_stride, int64_t act_col_stride,
+                     const float* d_logp_old, const float* var, const float* d_log_std, int act_dim, double log_lo, double log_hi,
+                     int64_t rows, double* d_partials, int64_t slot, void* stream);
+int  tg_policy_shift_finish(const double* d_partials, int32_t n_partials, double* d_sums, void* stream);
+int  tg_lr_adapt(const double* d_sums, double desired_kl, double factor, double lr_min, double lr_max, double lr, double* d_out4,
+                 void* stream);
+
 /* ---- MLP backward-data pass, all hidden layers in one persistent launch ----
  * For Linear(in, H) ReLU [Linear(H, H) ReLU]^(n_hidden_layers-1) Linear(H, out <= 8), H in {128, 256}, 3..6 hidden
  * layers, bf16:

@@ -4,7 +4,10 @@ epoch instead of 50-80.
 
     python3 tools/train_ppo.py [epochs] [CartPole|Pendulum|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
                                [--learn-std] [--normalize-obs] [--normalize-value] [--gae] [--privileged-critic]
-                               [--eval-every N] [--eval-episodes E] [--eval-sweep name=f1,f2,... ...]
+                               [--eval-every N] [--eval-episodes E] [--eval-sweep name=f1,f2,... ...] [--desired-kl KL]
+
+--desired-kl KL: the KL-adaptive learning rate (PPO(desired_kl=KL), e.g. 0.01): once per learn() the rate is divided by 1.5 when the
+measured KL between the policy before and after the updates exceeds 2 KL and multiplied by 1.5 when it is below KL / 2.
 
 --eval-every N: every N epochs a deterministic evaluation (trajopt_grpo_amd.Evaluator: mean actions, its own seed and RNG stream) of
 --eval-episodes E episodes per cell (default 256) is printed beside the sampled training return.  --eval-sweep (repeatable): the
@@ -95,6 +98,11 @@ def pop_eval(argv):
 def main():
     ranges, sys.argv[1:] = pop_randomize(sys.argv[1:])
     eval_every, eval_episodes, eval_sweep, sys.argv[1:] = pop_eval(sys.argv[1:])
+    desired_kl, sys.argv[1:] = pop_valued(sys.argv[1:], "--desired-kl")
+    try:
+        desired_kl = float(desired_kl[-1]) if desired_kl else None    # the KL-adaptive learning rate (PPO(desired_kl=...))
+    except ValueError:
+        raise SystemExit("--desired-kl expects a number")
     learn_std = "--learn-std" in sys.argv                         # a learned per-dimension log-std instead of the fixed covariance
     sys.argv = [a for a in sys.argv if a != "--learn-std"]
     normalize_obs = "--normalize-obs" in sys.argv                 # running observation normalisation (policy.obs_norm)
@@ -128,7 +136,7 @@ def main():
     buf = tg.Rollout_Buffer(mgr)
     algo = tg.PPO(epsilon=0.2, policy=pol, optimizer=torch.optim.Adam(pol.parameters(), lr=lr), ref_model=None,
                   updates_per_iter=upd, c1=0.5, kl_coeff=0.5, gamma=gamma, lam=0.95, entropy=0.01, batch_size=None,
-                  autocast_dtype=cdt, **({"monte_carlo": False} if gae else {}))
+                  autocast_dtype=cdt, **({"monte_carlo": False} if gae else {}), desired_kl=desired_kl)
     evaluator = None
     if eval_every is not None:                                    # (refuses a bad sweep before the first epoch)
         evaluator = tg.Evaluator(tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, episodes=eval_episodes, sweep=eval_sweep,
@@ -151,6 +159,8 @@ def main():
                   f"elapsed {time.time() - t0:6.1f}s"
                   + (f"  log_std {[round(v, 4) for v in algo.last_stats['log_std']]}" if learn_std else "")
                   + (f"  obs_count {algo.last_stats['obs_count']:.0f}" if normalize_obs else "")
+                  + (f"  kl {algo.last_stats['approx_kl']:.4f} clip {algo.last_stats['clip_fraction']:.3f} lr {algo.last_stats['lr']:.2e}"
+                     if desired_kl is not None else "")
                   + (f"  value mean {algo.last_stats['value_mean']:.2f} std {algo.last_stats['value_std']:.2f}"
                      f" ev {algo.last_stats['explained_variance']:.3f}" if normalize_value else ""), flush=True)
     print("first -> last:", float(buf.avg_reward[0]), "->", float(buf.avg_reward[-1]), " max", float(max(buf.avg_reward)))

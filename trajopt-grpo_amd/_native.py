@@ -186,6 +186,10 @@ SIGNATURES = {
     "tg_surrogate_loss_std": (C.c_int, [_P(LossArgs), _P(RefPenalty), _P(LearnedStd), _VP]),
     "tg_log_std_grad_blocks": (C.c_int, []),
     "tg_log_std_grad": (C.c_int, [_VP, _I64, _I32, _F, _VP, _VP, _VP]),
+    "tg_policy_shift_blocks": (C.c_int, [_I64]),
+    "tg_policy_shift": (C.c_int, [_VP, _I64, _VP, _I64, _I64, _VP, _P(_F), _VP, C.c_int, C.c_double, C.c_double, _I64, _VP, _I64, _VP]),
+    "tg_policy_shift_finish": (C.c_int, [_VP, _I32, _VP, _VP]),
+    "tg_lr_adapt": (C.c_int, [_VP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _VP, _VP]),
     "tg_relu_bwd_bias_blocks": (C.c_int, []),
     "tg_relu_bwd_bias": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "tg_head_bwd_relu_bias": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),

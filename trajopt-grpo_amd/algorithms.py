@@ -109,8 +109,10 @@ class _GpuLearner(Algorithm):
     _rollout_stream = _rollout_engine = _old_synced = _sum_rows = None
     _fold_pending = _differ_table = _count_pending = _count_pinned = None
 
-    def _setup(self, policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp=True, max_grad_norm=None):
+    def _setup(self, policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp=True, max_grad_norm=None,
+               kl_stats=False, desired_kl=None, lr_bounds=(1e-5, 1e-2), lr_factor=1.5):
         self.policy, self.optimizer = policy, optimizer
+        self._kl_setup(kl_stats, desired_kl, lr_bounds, lr_factor)
         if max_grad_norm is not None:
             if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
                 raise ValueError(f"max_grad_norm must be None or a finite number > 0, got {max_grad_norm!r}")
@@ -153,9 +155,13 @@ class _GpuLearner(Algorithm):
                         m._ws.default_cap = max(m._ws.default_cap, cap)
             self._rollout_engine = getattr(getattr(buffer, "rollout_manager", None), "engine", None) if ok else None
             self._check_deferred()
+            self._kl_entry_check()
             self._clip_log, self._std_log = _StepLog(2), _StepLog()
             obs_count = self._obs_norm_update(buffer)
             self._learn(buffer)
+            if self.kl_stats:
+                inner_kl = self._stats_pending or dict                      # (no update ran: the measurement is all there is)
+                self._stats_pending = lambda: {**inner_kl(), **self._kl_stats_read()}
             if obs_count is not None and self._stats_pending is not None:
                 inner0 = self._stats_pending
                 self._stats_pending = lambda: {**inner0(), "obs_count": float(obs_count.item())}
@@ -605,6 +611,101 @@ class _GpuLearner(Algorithm):
             K.gaussian_logp(mean, act[lo:hi], var, out=out[lo:hi])
         return out
 
+    # ---- kl_stats / desired_kl: how far this learn() moved the policy, measured ONCE after its last optimizer step, and rsl_rl's
+    # adaptive learning rate from it ("KL-adaptive learning rate").  Off: nothing below runs ----
+    def _kl_setup(self, kl_stats, desired_kl, lr_bounds, lr_factor):
+        def number(x):
+            return not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x)
+        if not isinstance(kl_stats, bool):
+            raise ValueError(f"kl_stats must be True or False, got {kl_stats!r}")
+        if desired_kl is not None and not (number(desired_kl) and desired_kl > 0):
+            raise ValueError(f"desired_kl must be None or a finite number > 0, got {desired_kl!r}")
+        try:
+            lo, hi = lr_bounds
+        except (TypeError, ValueError):
+            raise ValueError(f"lr_bounds must be a pair (lr_min, lr_max), got {lr_bounds!r}") from None
+        if not (number(lo) and number(hi) and 0 < lo <= hi):
+            raise ValueError(f"lr_bounds must be finite numbers with 0 < lr_min <= lr_max, got {lr_bounds!r}")
+        if not (number(lr_factor) and lr_factor > 1):
+            raise ValueError(f"lr_factor must be a finite number > 1, got {lr_factor!r}")
+        self.kl_stats = kl_stats or desired_kl is not None
+        self.desired_kl = None if desired_kl is None else float(desired_kl)
+        self.lr_bounds, self.lr_factor = (float(lo), float(hi)), float(lr_factor)
+        self._kl_pending = self._kl_pinned = self._kl_host = None
+        self._kl_bounds_checked = False
+        if self.desired_kl is not None:
+            self._kl_group_lr()
+
+    def _kl_group_lr(self) -> float:
+        """The one learning rate of the optimizer's param groups (desired_kl scales ONE number)."""
+        lrs = [float(g["lr"]) for g in self.optimizer.param_groups]
+        if any(lr != lrs[0] for lr in lrs):
+            raise ValueError(f"desired_kl adapts one learning rate, the optimizer's param groups hold {sorted(set(lrs))}")
+        return lrs[0]
+
+    def _kl_entry_check(self):
+        """First learn() with desired_kl: the optimizer's lr must lie inside lr_bounds (the rule clamps only what it changes)."""
+        if self.desired_kl is None or self._kl_bounds_checked:
+            return
+        lr, (lo, hi) = self._kl_group_lr(), self.lr_bounds
+        if not lo <= lr <= hi:
+            raise ValueError(f"the optimizer's lr = {lr} lies outside lr_bounds = {self.lr_bounds}")
+        self._kl_bounds_checked = True
+
+    def _measure_shift(self, actor, xin, act, old_logp, var, ls, cap):
+        """After the last optimizer step, before old_policy <- policy: one no-grad actor pass over this learn()'s rows, chunk by chunk,
+        each chunk's means into tg_policy_shift with the actions and the old log-probabilities (a learned log_std stays on the
+        device); the partials' sums, all-reduced, into tg_lr_adapt with the current lr BY VALUE; {sums, kl, clip fraction, lr_in,
+        lr_out} to pinned memory behind an event.  Nothing here waits, and nothing it writes is read by an update."""
+        dev, rows = xin.device, xin.shape[0]
+        chunks = [(lo, min(lo + self.chunk_rows, rows)) for lo in range(0, rows, self.chunk_rows)]
+        cap = max(cap, rows, 1)                                             # (sized for the largest iteration this buffer can bring)
+        n_part = (cap // self.chunk_rows) * K.policy_shift_blocks(self.chunk_rows) + K.policy_shift_blocks(cap % self.chunk_rows)
+        partials = self._small("shift_partials", 4 * n_part, torch.float64, dev).view(-1, 4)
+        out8 = self._small("shift_out", 8, torch.float64, dev)              # sums [4] | {kl, clip_fraction, lr_in, lr_out}
+        log_lo, log_hi = math.log1p(-float(self.epsilon)), math.log1p(float(self.epsilon))
+        slot = 0
+        for lo, hi in chunks:
+            mean = self._forward(actor, xin[lo:hi], view=True)
+            slot += K.policy_shift(mean, act[lo:hi], old_logp[lo:hi], var, log_lo, log_hi, partials, slot, log_std=ls)
+        K.policy_shift_finish(partials, slot, out8[:4])
+        D.allreduce_sum_(out8[:4], self.process_group, "policy_shift")
+        adapt = self.desired_kl is not None
+        lr = self._kl_group_lr() if adapt else float(self.optimizer.param_groups[0]["lr"])
+        K.lr_adapt(out8[:4], self.desired_kl if adapt else 0.0, self.lr_factor, *self.lr_bounds, lr, out8[4:])
+        if self._kl_pinned is None:
+            self._kl_pinned = torch.empty(8, dtype=torch.float64).pin_memory()
+        self._kl_pinned.copy_(out8, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        self._kl_pending = (self._kl_pinned, ev)
+
+    def _kl_sync(self):
+        """The last measurement, once its copy has landed (it was enqueued behind the updates of the learn() that made it; the next
+        learn() asks only after it has waited for the next rollout's row count, which runs behind them): lr_out into every param group
+        that still holds lr_in -- a group the user has changed since keeps the user's value."""
+        if self._kl_pending is None:
+            return
+        (host, ev), self._kl_pending = self._kl_pending, None
+        ev.synchronize()
+        n, _, _, s_d, kl, clip_fraction, lr_in, lr_out = host.tolist()
+        if self.desired_kl is not None:
+            for g in self.optimizer.param_groups:
+                if float(g["lr"]) == lr_in:
+                    g["lr"] = lr_out
+        self._kl_host = {"approx_kl": kl, "clip_fraction": clip_fraction, "log_ratio_mean": s_d / n if n > 0 else float("nan")}
+
+    def _kl_stats_read(self) -> dict:
+        self._kl_sync()
+        return {**(self._kl_host or {}), "lr": float(self.optimizer.param_groups[0]["lr"])}
+
+    def _kl_metadata(self) -> dict:
+        if not self.kl_stats:
+            return {}
+        if self.desired_kl is None:
+            return {"kl_stats": True}
+        return {"desired_kl": self.desired_kl, "lr_bounds": list(self.lr_bounds), "lr_factor": self.lr_factor}
+
 
 def _check_ref_model(ref_model, policy):
     """GRPO's reference policy: one of the project's Gaussian policies, on the policy's device, with the policy's input and output
@@ -646,16 +747,26 @@ class GRPO(_GpuLearner):
     max_grad_norm (a finite number > 0): `torch.nn.utils.clip_grad_norm_(policy.parameters(), max_grad_norm)` between backward() and
     optimizer.step() of every update, on the device ("Gradient clipping"): the norm of the all-reduced gradient
     bucket, the step on g * min(1, max_grad_norm / (norm + 1e-6)); last_stats gains "grad_norm" (the pre-clip norm of each update).
-    None: no clipping, the launches of a learner without the keyword."""
+    None: no clipping, the launches of a learner without the keyword.
+
+    desired_kl (a finite number > 0; lr_bounds, lr_factor): rsl_rl's adaptive learning rate, once per learn() (INTEGRATION.md,
+    "KL-adaptive learning rate").  Behind the last optimizer step one no-grad actor pass measures, on this iteration's valid rows of
+    all ranks, d = log pi(a|s) - logp_old: last_stats gains "approx_kl" (mean expm1(d) - d), "clip_fraction" (share of rows with
+    exp(d) outside 1 -+ epsilon), "log_ratio_mean" and "lr"; kl > 2 desired_kl divides the optimizer's lr by lr_factor, kl <
+    desired_kl / 2 multiplies it, inside lr_bounds, applied before the next learn()'s first optimizer step (and by last_stats and
+    save()) without a stall.  kl_stats=True: measure and report only.  Off: no launch, allocation, collective or entry point more,
+    and on, the updates themselves are those of a learner without the keywords, bit for bit."""
 
     def __init__(self, epsilon: float, beta: float, gamma: float, policy, optimizer, ref_model=None,
                  updates_per_iter: int = 10, *, maximize: bool = False, chunk_rows=None, autocast_dtype=None,
-                 process_group=None, fused_mlp: bool = True, max_grad_norm=None):
+                 process_group=None, fused_mlp: bool = True, max_grad_norm=None, kl_stats: bool = False, desired_kl=None,
+                 lr_bounds=(1e-5, 1e-2), lr_factor: float = 1.5):
         self.epsilon, self.beta, self.gamma = epsilon, beta, gamma
         self.ref_model = _check_ref_model(ref_model, policy)
         self.updates_per_iter = updates_per_iter
         self.maximize = maximize
-        self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm)
+        self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm,
+                    kl_stats, desired_kl, lr_bounds, lr_factor)
         self.old_policy = self._make_old_policy()                           # grpo.py:48
         self._old_synced = self._actor_keys()
 
@@ -716,6 +827,7 @@ class GRPO(_GpuLearner):
         if self.updates_per_iter > 0:
             self._zero_grads()                                              # (the first update's, ahead of the wait below)
         prepared = self._prepare_finish(handle)
+        self._kl_sync()                                                     # (the last learn()'s adapted lr: landed long ago)
         if prepared is not None:
             idx, xin, act, adv, _ = prepared
         else:
@@ -771,6 +883,8 @@ class GRPO(_GpuLearner):
             self.bucket.allreduce(self.process_group)                        # one RCCL all-reduce / step
             self._optimizer_step(actor, last=last)
         self._check_deferred()                                              # (this learn()'s own row count / fold flag: landed long ago)
+        if self.kl_stats:
+            self._measure_shift(actor, xin, act, old_logp, var, ls, traj.T * traj.n)
         self._copy_policy_to_old()                                          # grpo.py:148
         if self.updates_per_iter > 0:
             allJ = all_sums
@@ -785,6 +899,7 @@ class GRPO(_GpuLearner):
                                                "kl_ref": (allJ[:, 2] / allJ[:, 3].clamp_min(1.0)).tolist(), **extra()}
 
     def save(self, path: str) -> None:
+        self._kl_sync()                                                     # (the checkpoint holds the adapted lr)
         torch.save(self.optimizer.state_dict(), os.path.join(path, "optimizer.pth"))   # grpo.py:154
 
     def load(self, path: str) -> None:
@@ -792,7 +907,7 @@ class GRPO(_GpuLearner):
 
     def metadata(self):
         return {"algorithm": "GRPO", "epsilon": self.epsilon, "beta": self.beta,
-                "updates_per_iter": self.updates_per_iter, **self._clip_metadata()}
+                "updates_per_iter": self.updates_per_iter, **self._clip_metadata(), **self._kl_metadata()}
 
 
 def _value_norm_stats(stat3, moments, eps) -> dict:
@@ -850,12 +965,16 @@ class PPO(_GpuLearner):
     standardised with RUNNING statistics.  Every critic value that enters a return -- the valid rows on the [T][n] grid, the bootstrap
     rows -- is denormalised on the device with the table as it stands at the entry of learn(); the returns' all-reduced moments are
     merged into the statistics (unless frozen) and the critic regresses onto (R - mean) / sigma of the merged statistics, in place of
-    the batch's own mean and std.  last_stats gains "value_mean", "value_std", "value_count", "explained_variance".  GRPO ignores it."""
+    the batch's own mean and std.  last_stats gains "value_mean", "value_std", "value_count", "explained_variance".  GRPO ignores it.
+
+    kl_stats, desired_kl, lr_bounds, lr_factor: as GRPO's -- measured once per learn() behind its last optimizer step (the last
+    minibatch's in minibatch mode), over all valid rows.  ("kl_div" stays the reference's own penalty term.)"""
 
     def __init__(self, epsilon: float, policy, optimizer, ref_model, updates_per_iter: int, c1: float = 0.5,
                  kl_coeff: float = 0.5, gamma: float = 0.99, lam: float = 0.95, entropy: float = 0.01,
                  batch_size: int = 64, monte_carlo: bool = True, *, chunk_rows=None, autocast_dtype=None,
-                 process_group=None, seed: int = 0, fused_mlp: bool = True, max_grad_norm=None, bootstrap_truncated: bool = False):
+                 process_group=None, seed: int = 0, fused_mlp: bool = True, max_grad_norm=None, bootstrap_truncated: bool = False,
+                 kl_stats: bool = False, desired_kl=None, lr_bounds=(1e-5, 1e-2), lr_factor: float = 1.5):
         if not isinstance(bootstrap_truncated, bool):
             raise ValueError(f"bootstrap_truncated must be True or False, got {bootstrap_truncated!r}")
         self.bootstrap_truncated = bootstrap_truncated
@@ -863,7 +982,8 @@ class PPO(_GpuLearner):
         self.updates_per_iter = updates_per_iter
         self.gamma, self.lam, self.entropy = gamma, lam, entropy
         self.batch_size, self.kl_coeff, self.monte_carlo = batch_size, kl_coeff, monte_carlo
-        self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm)
+        self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm,
+                    kl_stats, desired_kl, lr_bounds, lr_factor)
         self.old_policy = self._make_old_policy()                           # ppo.py:62 (never read in learn)
         self._seed = seed
         self._gen = None
@@ -1063,6 +1183,7 @@ class PPO(_GpuLearner):
         ret_full = self._ws.get("ret_full", cap, 1, torch.float32, dev, cap).view(T, n)
         work = self._small("ppo_work", 6 * n, torch.float64, dev)
         prepared = self._prepare_finish(handle)
+        self._kl_sync()                                                     # (the last learn()'s adapted lr: landed long ago)
         if prepared is not None:
             idx, xin, act, _, _ = prepared
         else:
@@ -1145,6 +1266,8 @@ class PPO(_GpuLearner):
                                host=(norm_host, float(sizes[k])), last=final and k == n_steps - 1,
                                xin_c=None if priv is None else M.inherit_ones_column(xin_c.index_select(0, b), xin_c))
         self._check_deferred()                                              # (this learn()'s own row count: landed long ago)
+        if self.kl_stats:
+            self._measure_shift(actor, xin, act, old_logp, var, self._learned_std(), cap)
         self._copy_policy_to_old()                                          # ppo.py:186
         if all_sums:
             S2 = table if table is not None else torch.stack(all_sums)      # [steps][actor | critic][4]
@@ -1181,10 +1304,11 @@ class PPO(_GpuLearner):
     def metadata(self) -> dict:
         return {"algorithm": "PPO", "epsilon": self.epsilon, "c1": self.c1, "kl_coeff": self.kl_coeff,
                 "gamma": self.gamma, "lam": self.lam, "entropy": self.entropy, "batch_size": self.batch_size,
-                "updates_per_iter": self.updates_per_iter, **self._clip_metadata(),
+                "updates_per_iter": self.updates_per_iter, **self._clip_metadata(), **self._kl_metadata(),
                 **({"bootstrap_truncated": True} if self.bootstrap_truncated else {})}
 
     def save(self, path: str) -> None:
+        self._kl_sync()                                                     # (the checkpoint holds the adapted lr)
         torch.save(self.optimizer.state_dict(), os.path.join(path, "optimizer.pt"))    # ppo.py:214
 
     def load(self, path: str) -> None:

@@ -14,40 +14,7 @@ namespace tg {
 constexpr int kLossBlocks = 1024;   // persistent grid-stride blocks
 constexpr int kLossThreads = 256;
 
-struct Var8 { float inv_var[8]; float logp_const; };
-
-// Four f64 sums of a 256-thread block, deterministic: lanes -> wave (fixed shuffle tree) -> the four waves as ((w0 + w1) + w2) + w3.
-// Thread j < 4 returns sum j, the others 0.
-__device__ static inline double block_sum4_f64(double (&acc)[4]) {
-    __shared__ double sh[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sh[j][w] = acc[j];
-    }
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x < 4) {
-        const int j = threadIdx.x;
-        t = ((sh[j][0] + sh[j][1]) + sh[j][2]) + sh[j][3];
-    }
-    return t;
-}
-
-__device__ static inline float gaussian_logp(const float* mu, const float* a, const Var8& v, int A) {
-    float quad = 0.0f;
-#pragma unroll 4
-    for (int k = 0; k < A; ++k) {
-        const float d = a[k] - mu[k];
-        quad += d * d * v.inv_var[k];
-    }
-    return -0.5f * quad + v.logp_const;
-}
+// (Var8, gaussian_logp(), make_var() and block_sum4_f64() are loss_row.hpp's: policy_shift.hip compiles them too)
 
 template <int A>
 __global__ __launch_bounds__(256) void gaussian_logp_kernel(const float* __restrict__ mean, int64_t mean_rs,
@@ -166,19 +133,6 @@ __global__ __launch_bounds__(64) void log_std_final_kernel(const double* __restr
     double t = 0.0;
     for (int b = 0; b < nblocks; ++b) t += work[(int64_t)b * 4 + j];
     grad[j] = (float)((double)grad[j] + t + (double)add);
-}
-
-static int make_var(const float* var, int A, Var8& v, const char* who) {
-    if (A < 1 || A > 8) return set_error(TG_ERR_ARG, "%s: act_dim %d outside 1..8", who, A);
-    double logdet = 0;
-    for (int k = 0; k < 8; ++k) v.inv_var[k] = 0.f;
-    for (int k = 0; k < A; ++k) {
-        if (!(var[k] > 0.f)) return set_error(TG_ERR_ARG, "%s: var[%d] must be positive", who, k);
-        v.inv_var[k] = 1.0f / var[k];
-        logdet += log((double)var[k]);
-    }
-    v.logp_const = (float)(-0.5 * A * log(2.0 * 3.141592653589793) - 0.5 * logdet);
-    return TG_OK;
 }
 
 }  // namespace tg

@@ -54,6 +54,56 @@ __device__ static inline CriticTerms loss_critic_terms(float value, float ret, f
 __device__ static inline float gauss_mean_grad(float dlp, float dmu, float inv_var) { return dlp * dmu * inv_var; }                  // d total / d mu_k
 __device__ static inline float gauss_log_std_grad(float dlp, float dmu, float inv_var) { return dlp * (dmu * dmu * inv_var - 1.0f); } // d total / d log_std_k
 
+// ---- ... up to eight columns with a host-given variance (tg_gaussian_logp, tg_surrogate_loss, tg_policy_shift) ... ----
+struct Var8 { float inv_var[8]; float logp_const; };
+
+__device__ static inline float gaussian_logp(const float* mu, const float* a, const Var8& v, int A) {
+    float quad = 0.0f;
+#pragma unroll 4
+    for (int k = 0; k < A; ++k) {
+        const float d = a[k] - mu[k];
+        quad += d * d * v.inv_var[k];
+    }
+    return -0.5f * quad + v.logp_const;
+}
+
+// host: Var8 from the caller's variance array
+static inline int make_var(const float* var, int A, Var8& v, const char* who) {
+    if (A < 1 || A > 8) return set_error(TG_ERR_ARG, "%s: act_dim %d outside 1..8", who, A);
+    double logdet = 0;
+    for (int k = 0; k < 8; ++k) v.inv_var[k] = 0.f;
+    for (int k = 0; k < A; ++k) {
+        if (!(var[k] > 0.f)) return set_error(TG_ERR_ARG, "%s: var[%d] must be positive", who, k);
+        v.inv_var[k] = 1.0f / var[k];
+        logdet += log((double)var[k]);
+    }
+    v.logp_const = (float)(-0.5 * A * log(2.0 * 3.141592653589793) - 0.5 * logdet);
+    return TG_OK;
+}
+
+// Four f64 sums of a 256-thread block, deterministic: lanes -> wave (fixed shuffle tree) -> the four waves as ((w0 + w1) + w2) + w3.
+// Thread j < 4 returns sum j, the others 0.
+__device__ static inline double block_sum4_f64(double (&acc)[4]) {
+    __shared__ double sh[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sh[j][w] = acc[j];
+    }
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x < 4) {
+        const int j = threadIdx.x;
+        t = ((sh[j][0] + sh[j][1]) + sh[j][2]) + sh[j][3];
+    }
+    return t;
+}
+
 // ---- ... and the four columns of a chain head (inv_var is 0 beyond the net's outputs) ----
 struct Gauss4 { float inv_var[4]; float logp_const; };
 

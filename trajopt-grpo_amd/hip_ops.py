@@ -390,6 +390,55 @@ def gaussian_logp(mean: torch.Tensor, act: torch.Tensor, var, out: torch.Tensor 
     return out
 
 
+def policy_shift_blocks(rows: int) -> int:
+    """How many f64 [4] partials tg_policy_shift leaves for a chunk of `rows` rows (host arithmetic of the library)."""
+    return int(N.load().tg_policy_shift_blocks(int(rows)))
+
+
+def policy_shift(mean: torch.Tensor, act: torch.Tensor, logp_old: torch.Tensor, var, log_lo: float, log_hi: float, partials: torch.Tensor,
+                 slot: int = 0, log_std: torch.Tensor = None) -> int:
+    """tg_policy_shift on one chunk of rows: per row d = logp(act; mean) - logp_old in float64, and the workgroups' partials
+    {rows, sum expm1(d) - d, rows with d outside [log_lo, log_hi], sum d} into partials[slot:slot + blocks] (f64 [*][4]).  mean, act as
+    gaussian_logp() takes them; `var` a host sequence [A <= 8], or log_std a DEVICE f32 [A <= 4] (then `var` is not looked at: no host
+    read of a learned std).  Returns the number of partials written."""
+    N.require_cuda(mean, act, logp_old, partials, log_std)
+    assert mean.dtype == act.dtype == logp_old.dtype == torch.float32 and mean.dim() == 2 and (mean.shape[0] == 0 or mean.stride(1) == 1)
+    rows, A = mean.shape
+    assert act.dim() == 2 and tuple(act.shape) == (rows, A) and logp_old.is_contiguous() and logp_old.numel() == rows
+    blocks = policy_shift_blocks(rows)
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.dim() == 2 and partials.shape[1] == 4
+    assert slot >= 0 and slot + blocks <= partials.shape[0]
+    if log_std is not None:
+        assert log_std.dtype == torch.float32 and log_std.is_contiguous() and log_std.numel() == A
+        va = None
+    else:
+        va, k = _var_array(var)
+        assert k == A
+    N.check(N.load().tg_policy_shift(mean.data_ptr(), mean.stride(0), act.data_ptr(), act.stride(0), act.stride(1), logp_old.data_ptr(),
+                                     va, N.ptr(log_std), A, float(log_lo), float(log_hi), rows, partials.data_ptr(), int(slot), _st(mean)),
+            "tg_policy_shift")
+    return blocks
+
+
+def policy_shift_finish(partials: torch.Tensor, n_partials: int, sums: torch.Tensor) -> torch.Tensor:
+    """tg_policy_shift_finish: sums f64 [4] <- the first n_partials rows of `partials`, added in index order."""
+    N.require_cuda(partials, sums)
+    assert partials.dtype == sums.dtype == torch.float64 and partials.is_contiguous() and sums.is_contiguous() and sums.numel() == 4
+    assert 0 <= n_partials <= partials.shape[0] and partials.dim() == 2 and partials.shape[1] == 4
+    N.check(N.load().tg_policy_shift_finish(partials.data_ptr(), int(n_partials), sums.data_ptr(), _st(sums)), "tg_policy_shift_finish")
+    return sums
+
+
+def lr_adapt(sums: torch.Tensor, desired_kl: float, factor: float, lr_min: float, lr_max: float, lr: float, out: torch.Tensor) -> torch.Tensor:
+    """tg_lr_adapt: out f64 [4] = {kl, clip_fraction, lr_in, lr_out} from the (all-reduced) sums of policy_shift_finish(); desired_kl
+    <= 0 measures only (lr_out = lr_in)."""
+    N.require_cuda(sums, out)
+    assert sums.dtype == out.dtype == torch.float64 and sums.is_contiguous() and out.is_contiguous() and sums.numel() == 4 and out.numel() == 4
+    N.check(N.load().tg_lr_adapt(sums.data_ptr(), float(desired_kl), float(factor), float(lr_min), float(lr_max), float(lr), out.data_ptr(),
+                                 _st(sums)), "tg_lr_adapt")
+    return out
+
+
 def surrogate_loss(mean, value, act, logp_old, adv, ret, mask, norm, var, epsilon, surr_coef, critic_coef, kl_coef,
                    want_total: bool = True, coef: torch.Tensor = None, logp_ref: torch.Tensor = None, ref_coef: float = 0.0,
                    log_std: torch.Tensor = None, std_out: torch.Tensor = None):
