@@ -2163,7 +2163,8 @@ def test_fused_adam_is_bit_identical_to_torch(tg, dev, lr, betas, eps):
     assert not O.FusedAdam(patched).usable()
 
 
-@pytest.mark.parametrize("cdt,hidden", [(torch.bfloat16, (256,) * 5), (torch.bfloat16, (128,) * 3), (None, (128, 128)), (None, (64,) * 4)])
+@pytest.mark.parametrize("cdt,hidden", [(torch.bfloat16, (256,) * 5), (torch.bfloat16, (128,) * 3), (None, (128, 128)), (None, (64,) * 4),
+                                        (None, (256, 256))])
 def test_stream_refresher_equals_the_per_stream_refresh(tg, dev, cdt, hidden, monkeypatch):
     """optim.StreamRefresher (tg_gather_streams: every derived weight layout of actor and critic in one launch) leaves exactly the
     bytes FragmentStream.refresh() / F32ChainStream.refresh() build, and learn() with the fused optimizer step equals learn() with

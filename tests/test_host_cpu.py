@@ -199,7 +199,7 @@ def test_workspace_is_sized_for_its_capacity_once():
 
 
 def test_derived_layout_keys_follow_torch_version_counters_and_raw_writes():
-    """The key every derived weight layout is stamped with (mlp.GemmMLP._key / RegisterStreamF32._key): changes with any in-place
+    """The key every derived weight layout is stamped with (mlp.weights_key: GemmMLP._key, WeightStream.mark_fresh): changes with any in-place
     write through torch, with a re-bound parameter and with _native.RAW_PARAM_WRITES (the fused Adam launch), and with nothing else."""
     from trajopt_grpo_amd import _native as N
     from trajopt_grpo_amd import mlp as M
@@ -207,7 +207,7 @@ def test_derived_layout_keys_follow_torch_version_counters_and_raw_writes():
     lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
     key = lambda: (tuple((p.data_ptr(), p._version) for l in lin for p in (l.weight, l.bias)), N.RAW_PARAM_WRITES[0])
     obj = types.SimpleNamespace(linears=lin, lin=lin)
-    assert M.GemmMLP._key(obj) == key() == M.RegisterStreamF32._key(obj)
+    assert M.GemmMLP._key(obj) == key() == M.weights_key(lin)
     k0 = key()
     assert M.GemmMLP._key(obj) == k0                      # reading changes nothing
     with torch.no_grad():

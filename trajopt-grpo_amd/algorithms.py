@@ -142,7 +142,8 @@ class _GpuLearner(Algorithm):
             # the fused fp32 rollout's weight stream of THIS policy's actor, if the buffer's manager has one: rebuilt by the launch
             # that follows every optimizer step, so the next rollout starts without a refresh of its own
             frag = getattr(getattr(getattr(buffer, "rollout_manager", None), "engine", None), "_frag", None)
-            ok = hasattr(frag, "segments") and getattr(frag, "lin", None) == [m for m in self.policy.actor.network if isinstance(m, torch.nn.Linear)]
+            ok = (frag is not None and frag.rides_on_optimizer_step
+                  and frag.lin == [m for m in self.policy.actor.network if isinstance(m, torch.nn.Linear)])
             self._rollout_stream = frag if ok else None
             # every per-row workspace (activations, dZ, mask bits, gathered rows) is allocated ONCE for the largest chunk an
             # iteration of this buffer can bring: 288 GB of HBM are there to be used, and growth by re-allocation stalls the queue
@@ -274,11 +275,12 @@ class _GpuLearner(Algorithm):
                 if mn is None or mo is None:
                     continue
                 k = mn._key()
-                for what, attr, fields in (("f32", "_f32", ("stream",)), ("chain", "_chain", ("stream", "bias"))):
-                    sn, so = getattr(mn, attr, None), getattr(mo, attr, None)
+                new_s, old_s = dict(mn.streams()), dict(mo.streams())
+                for what in ("f32", "chain"):
+                    sn, so = new_s.get(what), old_s.get(what)
                     if sn is None or so is None or what in mn._stale or mn._built.get(what) != k:
                         continue
-                    ts = [(getattr(sn, f_), getattr(so, f_)) for f_ in fields]
+                    ts = [(a, b) for (a, _), (b, _) in zip(sn.outputs, so.outputs)]
                     if all(a.shape == b.shape and a.dtype == b.dtype for a, b in ts):
                         src += [a for a, _ in ts]
                         dst += [b for _, b in ts]

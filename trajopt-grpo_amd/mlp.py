@@ -187,6 +187,24 @@ def hidden_activation(net):
     return None
 
 
+def _linears(net):
+    return [m for m in net.network if isinstance(m, torch.nn.Linear)]
+
+
+def _mlp_shape(net):
+    """(S, H, n_hidden, A, activation) if `net` is Linear(S, H) act [Linear(H, H) act]* Linear(H, A) with one hidden activation
+    (hidden_activation(): "ReLU" or "Tanh") and equal hidden widths, else None.  Every `*_supported` predicate of a kernel family is
+    a range check on this tuple."""
+    act = hidden_activation(net)
+    if act is None:
+        return None
+    lin = _linears(net)
+    H = lin[0].out_features
+    if any(l.out_features != H for l in lin[:-1]) or any(l.in_features != H for l in lin[1:]):
+        return None
+    return lin[0].in_features, H, len(lin) - 1, lin[-1].out_features, act
+
+
 def _round_up(x, m):
     return (x + m - 1) // m * m
 
@@ -319,12 +337,8 @@ class GemmMLP:
         if shape in _LOGGED_SHAPES:
             return
         _LOGGED_SHAPES.add(shape)
-        if self._f32 is not None and self._f32.wide:
-            _LOG.info("%s: fp32 chain learner at H = 256 (tg_mlp_f32w_forward / _forward_backward / tg_mlp_f32_weight_grad)", shape)
-        elif self._f32 is not None and self.act == "Tanh":
-            _LOG.info("%s Tanh: fp32 chain learner (tg_mlp_f32_forward_act / _forward_backward_act / _weight_grad)", shape)
-        elif self._f32 is not None:
-            _LOG.info("%s: fp32 chain learner (tg_mlp_f32_forward / _forward_backward / _weight_grad)", shape)
+        if self._f32 is not None:
+            _LOG.info("%s%s", shape, self._f32.log_line())
         elif self._chain is not None and self._bchain is not None:
             _LOG.info("%s: bf16 chain kernels (tg_mlp_forward_chain[_loss] / tg_mlp_backward_chain / tg_mlp_weight_grad)", shape)
         else:
@@ -352,10 +366,13 @@ class GemmMLP:
         self._fresh("f32" if self._f32 is not None else ("chain" if self._chain is not None else "w"))
 
     def _key(self):
-        """What every derived operand is a function of: the master tensors' storage and torch version counters, and the count of
-        raw-pointer parameter writes (the fused Adam launch bypasses the version counters).  refresh() marks stale only what was
-        built from a different key, so a learn() that starts with the weights its last optimizer step left rebuilds nothing."""
-        return (tuple((p.data_ptr(), p._version) for l in self.linears for p in (l.weight, l.bias)), N.RAW_PARAM_WRITES[0])
+        """weights_key() of this net: refresh() marks stale only what was built from a different key, so a learn() that starts with
+        the weights its last optimizer step left rebuilds nothing."""
+        return weights_key(self.linears)
+
+    def streams(self):
+        """[(what, WeightStream)] of the derived layouts this net has -- `what` as refresh() and mark_built() name them."""
+        return [ws for ws in (("chain", self._chain), ("bchain", self._bchain), ("f32", self._f32)) if ws[1] is not None]
 
     def mark_built(self, what: str) -> None:
         """`what` has just been rebuilt from the current weights by someone else (optim.StreamRefresher, a copy of an identical
@@ -373,13 +390,9 @@ class GemmMLP:
                     w[:l.out_features, :l.in_features].copy_(l.weight)
                     b[:l.out_features].copy_(l.bias)
                 self.bias_out_f32[:self.out_dim].copy_(self.linears[-1].bias)
-            elif what == "chain":
-                self._chain.refresh()
-            elif what == "bchain":
-                self._bchain.refresh()
-            elif what == "f32":
-                self._f32.refresh()
-            elif what == "dx":
+            elif what != "dx":
+                dict(self.streams())[what].refresh()
+            else:
                 self._fresh("w")
                 for w, frag in zip(self.w, self._dxfrag):
                     if frag is not None:
@@ -437,12 +450,9 @@ class GemmMLP:
             f = self._f32
             assert xp.dtype == torch.float32 and xp.is_contiguous() and xp.shape[1] == f.in_pad
             out = torch.empty(xp.shape[0], 4, dtype=torch.float32, device=xp.device)
-            # (common: input, its padding, weight stream; then what each machine's weights and shape need; then rows, output)
-            shape = ((f.w0.data_ptr(), f.table.data_ptr(), f.H, f.n_hidden, f.out_dim) if f.res else
-                     (f.table.data_ptr(), f.n_hidden) if f.wide else (f.H, f.n_hidden))
             name, tail = forward_entry(f.machine, f.act)
-            N.check(getattr(N.load(), name)(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), *shape, xp.shape[0], out.data_ptr(), *tail,
-                                            N.stream_ptr(xp.device)), name)
+            N.check(getattr(N.load(), name)(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), *f.forward_args(), xp.shape[0], out.data_ptr(),
+                                            *tail, N.stream_ptr(xp.device)), name)
             self._acts = self._bits = None
             return out if padded else out[:, :self.out_dim].contiguous()
         if self._chain is not None and xp.shape[0] > 0:
@@ -637,39 +647,33 @@ class GemmMLP:
         assert xp.dtype == torch.float32 and xp.is_contiguous() and xp.shape[1] == f.in_pad
         # with >= 2 hidden layers the first activation and the top layer's dZ are neither written nor read: the weight-gradient job
         # that needs them rebuilds them from the input row / from d loss / d output + the top layer's mask bits (16 B per row)
-        # (the H = 256 learner's weight-gradient jobs read every operand back: nothing is rebuilt there yet)
-        rec = nh >= 2 and not self.f32_store_all and not f.wide
+        rec = nh >= 2 and not self.f32_store_all and f.rebuilds_on_chip
         acts = [None if (rec and i == 0) else self._ws.get(f"fa{i}", rows, H, torch.float32, dev) for i in range(nh)]
         dzs = [None if (rec and i == nh - 1) else self._ws.get(f"fz{i}", rows, H, torch.float32, dev) for i in range(nh)]
         tmask = self._ws.get("fmask", rows, 4, torch.int32, dev) if rec else None
         dout = self._ws.get("fz_head", rows, 4, torch.float32, dev)
-        nblk = lib.tg_mlp_f32w_blocks() if f.wide else lib.tg_mlp_f32_blocks()
         if self._head_ws is None:
-            self._head_ws = torch.empty(nblk * 4, dtype=torch.float64, device=dev)
+            self._head_ws = torch.empty(f.blocks() * 4, dtype=torch.float64, device=dev)
         a = self._loss_args(kind, rows, act, logp_old, adv, ret, norm, var, epsilon, surr_coef, critic_coef, kl_coef, logp_old_out, norm8)
         a.d_dout8, a.d_work = dout.data_ptr(), self._head_ws.data_ptr()
         ptrs = (N.C.c_void_p * nh)(*[N.ptr(t) for t in acts])
         zptrs = (N.C.c_void_p * nh)(*[N.ptr(t) for t in dzs])
         if f.act != N.TG_ACT_RELU:          # Tanh: everything stored, no mask bits
             assert tmask is None and all(t is not None for t in acts + dzs)
-        # (common: input, its padding, weight stream; then what each machine's weights and shape need; then rows and the buffers)
-        shape = (f.w0.data_ptr(), f.table.data_ptr(), H, nh) if f.res else (f.table.data_ptr(), nh) if f.wide else (H, nh)
         name, tail, targs = loss_entry(f.machine, f.act, ref, std)
         ev = None
         if self.fwd_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        N.check(getattr(lib, name)(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), *shape, rows, ptrs, zptrs, *(() if f.wide else (N.ptr(tmask),)),
-                                   N.C.byref(a), *tail, N.stream_ptr(dev)), name)
+        N.check(getattr(lib, name)(xp.data_ptr(), f.in_pad, f.stream.data_ptr(), *f.loss_args(), rows, ptrs, zptrs,
+                                   *((N.ptr(tmask),) if f.takes_mask_bits else ()), N.C.byref(a), *tail, N.stream_ptr(dev)), name)
         if ev is not None:
             ev[1].record()
             # matrix-core flops per row: first layer + forward and backward products of the H x H layers (head: vector unit)
             # algorithmic flops per row (un-padded): forward first layer + H x H layers + head, backward head + H x H layers
             self.fwd_events.append((ev[0], ev[1], rows, 2 * H * self.in_dim + 4 * (nh - 1) * H * H + 4 * H * self.out_dim,
-                                    ("tg::mlp_f32_wide_kernel<true" if f.wide else
-                                     (f"tg::mlp_f32_res_kernel<{H},{f.in_pad // 4},true" if f.res else f"tg::mlp_f32_chain_kernel<{H},true"))
-                                    + targs))
-        grid = lib.tg_mlp_f32r_grid(rows) if f.res else min(nblk, -(-rows // (64 if f.wide else 256)))      # (the launchers' own grids)
+                                    f.kernel_prefix() + targs))
+        grid = f.grid(rows)
         self._acts, self._bits, self._dz_head, self._tmask = [xp] + acts, dzs, dout, tmask
         assert getattr(self, "_loss_rider", None) is None, "forward_loss(sums_out=...) must be followed by backward_fused()"
         if sums_out is not None:
@@ -728,10 +732,7 @@ class GemmMLP:
         if ev is not None:
             ev[1].record()
             # algorithmic flops per row (un-padded): every layer's dZ^T A
-            one_job = H == 128 and nh == 2
-            self.dw_events.append((ev[0], ev[1], rows, 2 * (nh - 1) * H * H + 2 * H * self.in_dim + 2 * H * self.out_dim,
-                                   "tg::mlp_f32_wide_dw_kernel + finish" if f.wide else
-                                   (f"tg::mlp_f32_dw_fused8_kernel<{H},...> + finish" if one_job else f"tg::mlp_f32_dw_kernel<{H}> + finish")))
+            self.dw_events.append((ev[0], ev[1], rows, 2 * (nh - 1) * H * H + 2 * H * self.in_dim + 2 * H * self.out_dim, f.dw_kernel()))
         self._acts = self._bits = self._dz_head = self._tmask = None
 
     @torch.no_grad()
@@ -965,13 +966,100 @@ class GemmMLP:
 # ---------------------------------------------------------------------------------------------
 def fused_rollout_supported(net, obs_dim: int, act_dim: int) -> int:
     """Hidden width H if `net` is Linear(S,H) ReLU [Linear(H,H) ReLU]* Linear(H,A) with H in {128,256}, else 0."""
-    if not supports(net) or obs_dim > 32 or act_dim > 4:
-        return 0
-    lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-    H = lin[0].out_features
-    if H not in (128, 256) or any(l.out_features != H for l in lin[:-1]) or any(l.in_features != H for l in lin[1:]):
-        return 0
-    return H
+    s = _mlp_shape(net)
+    return s[1] if s and s[4] == "ReLU" and s[1] in (128, 256) and obs_dim <= 32 and act_dim <= 4 else 0
+
+
+def weights_key(lin):
+    """What every derived operand is a function of: the master tensors' storage and torch version counters, and the count of
+    raw-pointer parameter writes (the fused Adam launch bypasses the version counters)."""
+    return (tuple((p.data_ptr(), p._version) for l in lin for p in (l.weight, l.bias)), N.RAW_PARAM_WRITES[0])
+
+
+class WeightStream:
+    """A kernel family's weights in the order its lanes read them, kept current from the fp32 masters by ONE gather.
+    Source: the masters of `self.lin` laid end to end -- every weight row-major, then every bias, then one zero that every padded
+    position points at.  A subclass sets `lin` (and what its kernels ask of it), says in _layout() which source element each
+    position of each buffer holds, and calls _build(); the refresh, the gather codes of optim.StreamRefresher and the freshness key
+    are written here once.
+      outputs: [(destination, is_bf16)] -- one flat buffer per allocation, in the order of `_idx`, whose sizes partition it."""
+    rides_on_optimizer_step = False     # a rollout engine's stream that joins the learner's gather (StreamRefresher extra_streams)
+                                        # and is then trusted as fresh at the next rollout's entry: the fp32 fused rollout's only
+
+    def _layout(self, woff, boff, zero_at, dev):
+        """[(is_bf16, [(attribute, [index pieces]), ...])], one entry per allocation: the first attribute names the whole buffer,
+        every later one a view of its own range.  woff[i] / boff[i]: where weight / bias i of `lin` starts in the source."""
+        raise NotImplementedError
+
+    def _build(self):
+        lin = self.lin
+        dev = lin[0].weight.device
+        sizes = [l.weight.numel() for l in lin] + [l.bias.numel() for l in lin]
+        starts = [sum(sizes[:i]) for i in range(len(sizes) + 1)]
+        idx, self.outputs, self._stage = [], [], []
+        for is_bf16, parts in self._layout(starts[:len(lin)], starts[len(lin):-1], starts[-1], dev):
+            flat = [torch.cat([p.reshape(-1) for p in pieces] + [torch.empty(0, dtype=torch.int64, device=dev)]) for _, pieces in parts]
+            buf = torch.empty(sum(f.numel() for f in flat), dtype=torch.bfloat16 if is_bf16 else torch.float32, device=dev)
+            setattr(self, parts[0][0], buf)
+            at = flat[0].numel()
+            for (attr, _), f in zip(parts[1:], flat[1:]):
+                setattr(self, attr, buf[at:at + f.numel()])
+                at += f.numel()
+            idx += flat
+            self.outputs.append((buf, is_bf16))
+            self._stage.append(torch.empty(buf.numel(), dtype=torch.float32, device=dev) if is_bf16 else None)
+        self._idx = torch.cat(idx)
+        self._zero = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._fresh_key = None
+
+    def refresh(self):
+        self._refresh()
+        self.mark_fresh()
+
+    @torch.no_grad()
+    def _refresh(self):
+        """Concatenate the masters, then one gather per buffer (+ the conversion of a bf16 one): 2 launches for one fp32 buffer."""
+        src = torch.cat([l.weight.reshape(-1) for l in self.lin] + [l.bias for l in self.lin] + [self._zero])
+        src = src if src.dtype == torch.float32 else src.float()
+        at = 0
+        for (dst, is_bf16), stage in zip(self.outputs, self._stage):
+            torch.index_select(src, 0, self._idx[at:at + dst.numel()], out=stage if is_bf16 else dst)
+            if is_bf16:
+                dst.copy_(stage)
+            at += dst.numel()
+
+    def segments(self, tensor_ids):
+        """The buffers as tg_gather_streams segments: [(dst, int32 code per element, is_bf16)], code = master tensor << 24 | offset,
+        -1 = zero.  tensor_ids: optim.FusedAdam's id(param) -> (group, tensor); a master outside group 0 is an AssertionError and one
+        the optimizer does not hold a KeyError (optim.StreamRefresher remembers either as a layout its launch cannot cover)."""
+        codes = []
+        for p in [l.weight for l in self.lin] + [l.bias for l in self.lin]:
+            gi, ti = tensor_ids[id(p)]
+            assert gi == 0
+            codes.append((ti << 24) + torch.arange(p.numel(), dtype=torch.int64))
+        codes.append(torch.tensor([-1], dtype=torch.int64))
+        codes = torch.cat(codes).to(self._idx.device)[self._idx].to(torch.int32)
+        segs, at = [], 0
+        for dst, is_bf16 in self.outputs:
+            segs.append((dst, codes[at:at + dst.numel()].contiguous(), int(is_bf16)))
+            at += dst.numel()
+        return segs
+
+    def mark_fresh(self) -> None:
+        self._fresh_key = weights_key(self.lin)
+
+    def is_fresh(self) -> bool:
+        return not N.ALWAYS_REBUILD and self._fresh_key == weights_key(self.lin)
+
+
+def _head_table(lin, woff, boff, zero_at, dev, bias_rows: int, head_rows: int, head_bias: int):
+    """Index pieces of the fp32 kernels' table [bias_rows][H] hidden biases | [head_rows][H] head weights | [head_bias] head bias;
+    rows and entries the net does not have are zero."""
+    H, nh, A = lin[0].out_features, len(lin) - 1, lin[-1].out_features
+    j, zeros = torch.arange(H, device=dev), torch.full((H,), zero_at, device=dev)
+    return ([boff[l] + j if l < nh else zeros for l in range(bias_rows)]
+            + [woff[nh] + a * H + j if a < A else zeros for a in range(head_rows)]
+            + [torch.tensor([boff[nh] + a if a < A else zero_at for a in range(head_bias)], device=dev)])
 
 
 def _fragment_index(k_pad: int, device):
@@ -1000,36 +1088,37 @@ def _chain_fragment_index(k_pad: int, device):
     return chain_row, natural_row, col
 
 
-class FragmentStream:
+class FragmentStream(WeightStream):
     """bf16 weight stream + f32 bias table in the layout tg_fused_rollout (layout="rollout", 32x32x16 MFMA) or the chain
     kernels (layout="chain", 16x16x32 MFMA: tg_mlp_forward_chain, tg_mlp_backward_chain, tg_mlp_weight_grad's recompute)
-    consume, refreshed from the fp32 master weights with one gather (the permutation is built once).
+    consume (refresh: three launches + one for the bias table).
     rollout: blocks = the first layer's output tiles (2 k-steps each), then one block per 32-row output tile of every later
       layer; a block = its k-steps x 64 lanes x 8 bf16 (1 KiB per k-step); lane (m, h) holds 8 weights of output row 32*tile + m.
     chain: every block is H/16 pieces of 1 KiB.  A matrix with K <= 32 (the first layer; the backward stream's W_head^T) is ONE
       block [output block mt][half f]; a matrix with K = H is one block per 32 output features, [k-step ks][half f]
-      (_chain_fragment_index documents the lane map); the forward head keeps its <= 16 outputs in half 0, natural order."""
+      (_chain_fragment_index documents the lane map); the forward head keeps its <= 16 outputs in half 0, natural order.
+    bias: [layers][H], zero padded."""
 
     def __init__(self, net, H: int, layout: str = "rollout", transposed: bool = False):
         """transposed=True: the stream of the backward chain (tg_mlp_backward_chain): the head first, then the
-        hidden-to-hidden layers from the top down, every matrix transposed ([in][out]); no bias table."""
+        hidden-to-hidden layers from the top down, every matrix transposed ([in][out]); no bias table (`bias` stays zero)."""
         assert layout in ("rollout", "chain")
-        lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-        self.transposed = transposed
+        lin = _linears(net)
+        self.H, self.layout, self.transposed = H, layout, transposed
         self.lin = lin[:0:-1] if transposed else lin            # head, L-2, ..., 1  |  0, 1, ..., head
-        dev = lin[0].weight.device
-        self.H = H
+        self._build()
+        self.bias = (torch.zeros(len(self.lin), H, dtype=torch.float32, device=self.stream.device) if transposed else
+                     self.bias.view(len(self.lin), H))
+        self.refresh()
+
+    def _layout(self, woff, boff, zero_at, dev):
+        transposed = self.transposed
         m = torch.arange(64, device=dev) & 31
-        # One gather builds the stream: source = the master weights laid end to end (row-major, unpadded) + the biases +
-        # one zero that every padded position points at.
-        flat_idx, off = [], 0
-        n_src = sum(l.weight.numel() for l in self.lin)
-        n_bias = sum(l.bias.numel() for l in self.lin)
-        zero_at = n_src + n_bias
+        stream = []
         for li, l in enumerate(self.lin):
             rows_, cols_ = (l.in_features, l.out_features) if transposed else (l.out_features, l.in_features)
             m_pad, k_pad = _round_up(rows_, 32), _round_up(cols_, 32)
-            if layout == "rollout":
+            if self.layout == "rollout":
                 kidx = _fragment_index(k_pad, dev)
                 rmap = m.view(1, -1, 1).expand_as(kidx)
             else:
@@ -1038,32 +1127,13 @@ class FragmentStream:
             for mo in range(m_pad // 32):
                 r = 32 * mo + rmap                                             # row / column of the (transposed) padded matrix
                 c = kidx
-                src = off + (c * l.in_features + r if transposed else r * l.in_features + c)   # weight is [out][in]
-                flat_idx.append(torch.where((r < rows_) & (c < cols_), src, torch.full_like(src, zero_at)).reshape(-1))
-            off += l.weight.numel()
-        n_stream = sum(t.numel() for t in flat_idx)
-        if not transposed:                                                     # bias table [layers][H], zero padded
-            boff = n_src
-            for l in self.lin:
-                j = torch.arange(H, device=dev)
-                flat_idx.append(torch.where(j < l.out_features, boff + j, torch.full_like(j, zero_at)))
-                boff += l.bias.numel()
-        self._idx = torch.cat(flat_idx)
-        self._n_stream = n_stream
-        self._zero = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._gath = torch.empty(self._idx.numel(), dtype=torch.float32, device=dev)
-        self.stream = torch.empty(n_stream, dtype=torch.bfloat16, device=dev)
-        self.bias = torch.zeros(len(self.lin), H, dtype=torch.float32, device=dev)
-        self.refresh()
-
-    @torch.no_grad()
-    def refresh(self):
-        """Three launches: concatenate the master tensors, gather, convert to bf16 (+ one copy for the bias table)."""
-        src = torch.cat([l.weight.reshape(-1) for l in self.lin] + [l.bias for l in self.lin] + [self._zero])
-        torch.index_select(src.float() if src.dtype != torch.float32 else src, 0, self._idx, out=self._gath)
-        self.stream.copy_(self._gath[:self._n_stream])
-        if not self.transposed:
-            self.bias.view(-1).copy_(self._gath[self._n_stream:])
+                src = woff[li] + (c * l.in_features + r if transposed else r * l.in_features + c)   # weight is [out][in]
+                stream.append(torch.where((r < rows_) & (c < cols_), src, torch.full_like(src, zero_at)))
+        if transposed:
+            return [(True, [("stream", stream)])]
+        j = torch.arange(self.H, device=dev)
+        bias = [torch.where(j < l.out_features, boff[li] + j, torch.full_like(j, zero_at)) for li, l in enumerate(self.lin)]
+        return [(True, [("stream", stream)]), (False, [("bias", bias)])]
 
 
 def fragment_stream(net, H: int):
@@ -1079,113 +1149,45 @@ def fused_rollout_f32_supported(net, obs_dim: int, act_dim: int, activations=("R
     """Hidden width H if `net` is Linear(S,H) act [Linear(H,H) act]* Linear(H,A) with act in `activations` (hidden_activation();
     the kernels have "ReLU" and "Tanh": DeviceRollout asks for both, the default keeps the ReLU-only meaning of tg_fused_rollout_f32),
     H in {64,128} and 1..4 hidden layers (what tg_fused_rollout_f32[_act] has kernels for), else 0."""
-    act = hidden_activation(net)
-    if act is None or act not in activations or act not in ACTIVATIONS or obs_dim > 32 or act_dim > 4:
-        return 0
-    lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-    H = lin[0].out_features
-    if H not in (64, 128) or not (1 <= len(lin) - 1 <= 4):
-        return 0
-    if any(l.out_features != H for l in lin[:-1]) or any(l.in_features != H for l in lin[1:]):
-        return 0
-    return H
+    s = _mlp_shape(net)
+    return s[1] if (s and s[4] in activations and s[4] in ACTIVATIONS and s[1] in (64, 128) and 1 <= s[2] <= 4
+                    and obs_dim <= 32 and act_dim <= 4) else 0
 
 
-class RegisterStreamF32:
-    """fp32 weights in the order tg_fused_rollout_f32 loads them into registers, refreshed from the master weights
-    with one gather: [H/32 waves][K1/2 + n_hh*H/2 registers][64 lanes] (first layer: K1 = in_features rounded up to 8, zero beyond).
+class RegisterStreamF32(WeightStream):
+    """fp32 weights in the order tg_fused_rollout_f32 loads them into registers:
+    [H/32 waves][K1/2 + n_hh*H/2 registers][64 lanes] (first layer: K1 = in_features rounded up to 8, zero beyond).
     block_envs 32: register 4q + j of lane (m, kh) of wave w holds W[32w + m][8q + 4kh + j];
     block_envs 16: register tt * (k / 4) + s of lane (i, g) holds W[32w + 16 tt + i][first layer: 4 s + g; H x H: 16 (s >> 2) + 4 g + (s & 3)].
-    `table` = [n_hidden*H hidden biases][4*H head weights][4 head biases]."""
+    `table` = [n_hidden*H hidden biases][4*H head weights][4 head biases].  Refresh: three launches (two buffers)."""
+    rides_on_optimizer_step = True
 
     def __init__(self, net, H: int, block_envs: int = 32):
         assert block_envs in (16, 32)
         self.block_envs = block_envs
-        lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-        self.lin, self.H = lin, H
-        dev = lin[0].weight.device
-        n_hidden = len(lin) - 1
-        k1 = _round_up(lin[0].in_features, 8)
-        self._k = [k1] + [H] * (n_hidden - 1)
+        self.lin, self.H = _linears(net), H
+        self._build()
+        self.refresh()
+
+    def _layout(self, woff, boff, zero_at, dev):
+        H, lin = self.H, self.lin
         lane = torch.arange(64, device=dev).view(1, 1, -1)
         wave = torch.arange(H // 32, device=dev).view(-1, 1, 1)
-        idx, off = [], 0
-        for li, k in enumerate(self._k):
+        regs = []
+        for li, l in enumerate(lin[:-1]):
+            k = _round_up(l.in_features, 8)
             r = torch.arange(k // 2, device=dev).view(1, -1, 1)
-            if block_envs == 32:
+            if self.block_envs == 32:
                 row = 32 * wave + (lane & 31)
                 colk = 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3)
             else:
                 tt, s_ = r // (k // 4), r % (k // 4)
                 row = 32 * wave + 16 * tt + (lane & 15)
                 colk = 4 * s_ + (lane >> 4) if li == 0 else 16 * (s_ >> 2) + 4 * (lane >> 4) + (s_ & 3)
-            idx.append(off + row * k + colk)                   # [waves][k/2][64]
-            off += H * k
-        self._idx = torch.cat(idx, dim=1).reshape(-1)
-        self._wflat = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.stream = torch.empty(self._idx.numel(), dtype=torch.float32, device=dev)
-        self.table = torch.zeros(n_hidden * H + 4 * H + 4, dtype=torch.float32, device=dev)
-        self._fresh_key = None
-        self.refresh()
-
-    def _key(self):
-        """What the stream is a function of: the parameters' storage and torch version counters, and the count of raw-pointer
-        parameter writes (the fused Adam launch bypasses the version counters)."""
-        return (tuple((p.data_ptr(), p._version) for l in self.lin for p in (l.weight, l.bias)), N.RAW_PARAM_WRITES[0])
-
-    def mark_fresh(self) -> None:
-        self._fresh_key = self._key()
-
-    def is_fresh(self) -> bool:
-        return not N.ALWAYS_REBUILD and self._fresh_key == self._key()
-
-    def segments(self, tensor_ids):
-        """The stream and the table as tg_gather_streams segments: [(dst, int32 code per element, is_bf16)], code = master tensor
-        << 24 | offset, -1 = zero (optim.StreamRefresher: rebuilt in the launch that follows an optimizer step)."""
-        H, lin = self.H, self.lin
-        n_hidden = len(lin) - 1
-        flat = torch.full((self._wflat.numel(),), -1, dtype=torch.int64)
-        off = 0
-        for l, k in zip(lin[:-1], self._k):
-            gi, ti = tensor_ids[id(l.weight)]
-            assert gi == 0
-            r, c = torch.arange(H).view(H, 1), torch.arange(k).view(1, k)
-            flat[off:off + H * k] = torch.where(c < l.in_features, (ti << 24) + r * l.in_features + c, -1).reshape(-1)
-            off += H * k
-        dev = self.stream.device
-        s_codes = flat[self._idx.cpu()].to(torch.int32).to(dev)
-        t = torch.full((self.table.numel(),), -1, dtype=torch.int64)
-        for li, l in enumerate(lin[:-1]):
-            gi, ti = tensor_ids[id(l.bias)]
-            assert gi == 0
-            t[li * H:(li + 1) * H] = (ti << 24) + torch.arange(H)
-        head = lin[-1]
-        gi, tw = tensor_ids[id(head.weight)]
-        gi2, tb = tensor_ids[id(head.bias)]
-        assert gi == 0 and gi2 == 0
-        for a in range(head.out_features):
-            t[n_hidden * H + a * H:n_hidden * H + (a + 1) * H] = (tw << 24) + a * H + torch.arange(H)
-            t[n_hidden * H + 4 * H + a] = (tb << 24) + a
-        return [(self.stream, s_codes, 0), (self.table, t.to(torch.int32).to(dev), 0)]
-
-    def refresh(self):
-        self._refresh()
-        self.mark_fresh()
-
-    @torch.no_grad()
-    def _refresh(self):
-        H, off = self.H, 0
-        n_hidden = len(self.lin) - 1
-        for l, k in zip(self.lin[:-1], self._k):
-            self._wflat[off:off + H * k].view(H, k)[:, :l.in_features].copy_(l.weight)
-            off += H * k
-        torch.index_select(self._wflat, 0, self._idx, out=self.stream)
-        for li, l in enumerate(self.lin[:-1]):
-            self.table[li * H:(li + 1) * H].copy_(l.bias)
-        head = self.lin[-1]
-        hw = self.table[n_hidden * H:n_hidden * H + 4 * H].view(4, H)
-        hw[:head.out_features].copy_(head.weight)
-        self.table[n_hidden * H + 4 * H:n_hidden * H + 4 * H + head.out_features].copy_(head.bias)
+            src = woff[li] + row * l.in_features + colk                               # [waves][k/2][64]
+            regs.append(torch.where(colk < l.in_features, src, torch.full_like(src, zero_at)))
+        return [(False, [("stream", [torch.cat(regs, dim=1)])]),
+                (False, [("table", _head_table(lin, woff, boff, zero_at, dev, len(lin) - 1, 4, 4))])]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1195,184 +1197,27 @@ def f32_chain_supported(net) -> int:
     """Hidden width H if `net` is Linear(S<=32, H) act [Linear(H, H) act]{0..3} Linear(H, A<=4), act = ReLU or Tanh
     (hidden_activation()), with H in {64, 128} -- the reference's own policy shapes (pipelines/cartpole_pipeline_grpo.py:54-76,
     cartpole_pipeline_ppo.py:54-79) -- else 0."""
-    if hidden_activation(net) is None:
-        return 0
-    lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-    H = lin[0].out_features
-    if H not in (64, 128) or not (1 <= len(lin) - 1 <= 4) or lin[0].in_features > 32 or lin[-1].out_features > 4:
-        return 0
-    if any(l.out_features != H for l in lin[:-1]) or any(l.in_features != H for l in lin[1:]):
-        return 0
-    return H
+    s = _mlp_shape(net)
+    return s[1] if s and s[1] in (64, 128) and 1 <= s[2] <= 4 and s[0] <= 32 and s[3] <= 4 else 0
 
 
 def f32_res_supported(net) -> int:
     """128 if `net` is Linear(S<=32, 128) ReLU [Linear(128, 128) ReLU]{0..1} Linear(128, A<=4) -- BASELINE configs[1]'s policy
     (5-128-128-1) and its like: the whole weight stream fits the LDS beside the tables -- else 0."""
-    if not supports(net):
-        return 0
-    lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-    H = lin[0].out_features
-    if H != 128 or not (1 <= len(lin) - 1 <= 2) or lin[0].in_features > 32 or lin[-1].out_features > 4:
-        return 0
-    if any(l.out_features != H for l in lin[:-1]) or any(l.in_features != H for l in lin[1:]):
-        return 0
-    return H if N.load().tg_mlp_f32r_supported(H, len(lin) - 1, _round_up(lin[0].in_features, 8)) else 0
-
-
-class F32ResStream:
-    """Weight stream, first-layer table and bias / head table of the resident 16-row kernel (csrc/mlp_f32_wide.hip, mlp_f32_res_kernel),
-    ONE buffer refreshed with one gather: lane = (i = lane & 15, g = lane >> 4)
-      stream: forward blocks [8 mo][8 t][64 lanes][4]: W_1[16 mo + i][16 t + 4 g + e]; backward blocks [8 ko][8 t][64][4]:
-              W_1[16 t + 4 g + e][16 ko + i]            (nothing with one hidden layer)
-      w0:     [8 mo][in_pad / 4 steps s][64 lanes]: W0[16 mo + i][4 s + g]              (zero beyond the inputs)
-      table:  [2][128] hidden biases | [4][128] head weights (rows >= A zero) | [4] head bias | 12 zeros"""
-    wide, res, act, machine = False, True, 0, "f32r"        # (act: TG_ACT_RELU -- the resident kernel is ReLU-only)
-
-    def __init__(self, net):
-        lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-        self.lin, self.H = lin, 128
-        H, NT = 128, 8
-        dev = lin[0].weight.device
-        nh = len(lin) - 1
-        self.n_hidden, self.in_dim, self.out_dim = nh, lin[0].in_features, lin[-1].out_features
-        self.in_pad = _round_up(self.in_dim, 8)
-        K4 = self.in_pad // 4
-        woff, off = [], 0
-        for l in lin:
-            woff.append(off)
-            off += l.weight.numel()
-        boff = []
-        for l in lin:
-            boff.append(off)
-            off += l.bias.numel()
-        zero_at = off
-        lane = torch.arange(64, device=dev).view(1, 64, 1)
-        i, g = lane & 15, lane >> 4
-        e = torch.arange(4, device=dev).view(1, 1, 4)
-        t = torch.arange(NT, device=dev).view(NT, 1, 1)
-        k = (16 * t + 4 * g + e).expand(NT, 64, 4)
-        idx = []
-        for l in range(1, nh):                                                       # forward: W_l[16 mo + i][k]
-            for mo in range(NT):
-                idx.append((woff[l] + (16 * mo + i) * H + k).reshape(-1))
-        for l in range(nh - 1, 0, -1):                                               # backward: W_l[k][16 ko + i]
-            for ko in range(NT):
-                idx.append((woff[l] + k * H + (16 * ko + i)).reshape(-1))
-        n_stream = sum(x.numel() for x in idx)
-        s4 = torch.arange(K4, device=dev).view(K4, 1)
-        ln = torch.arange(64, device=dev).view(1, 64)
-        col = (4 * s4 + (ln >> 4)).expand(K4, 64)
-        for mo in range(NT):
-            src = woff[0] + (16 * mo + (ln & 15)).expand(K4, 64) * self.in_dim + col
-            idx.append(torch.where(col < self.in_dim, src, torch.full_like(src, zero_at)).reshape(-1))
-        n_w0 = NT * K4 * 64
-        for l in range(2):
-            idx.append(boff[l] + torch.arange(H, device=dev) if l < nh else torch.full((H,), zero_at, device=dev))
-        for a in range(4):
-            idx.append(woff[nh] + a * H + torch.arange(H, device=dev) if a < self.out_dim else torch.full((H,), zero_at, device=dev))
-        idx.append(torch.tensor([boff[nh] + a if a < self.out_dim else zero_at for a in range(4)] + [zero_at] * 12, device=dev))
-        self._idx = torch.cat([x.reshape(-1) for x in idx])
-        lib = N.load()
-        assert n_stream == lib.tg_mlp_f32r_stream_floats(H, nh) and n_w0 == lib.tg_mlp_f32r_w0_floats(H, self.in_pad)
-        assert self._idx.numel() - n_stream - n_w0 == lib.tg_mlp_f32r_table_floats(H)
-        self._zero = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.stream = torch.empty(self._idx.numel(), dtype=torch.float32, device=dev)          # blocks, first-layer table, tables
-        self.w0 = self.stream[n_stream:n_stream + n_w0]
-        self.table = self.stream[n_stream + n_w0:]
-        self.refresh()
-
-    @torch.no_grad()
-    def refresh(self):
-        """Two launches: concatenate the master tensors, gather."""
-        src = torch.cat([l.weight.reshape(-1) for l in self.lin] + [l.bias for l in self.lin] + [self._zero])
-        torch.index_select(src if src.dtype == torch.float32 else src.float(), 0, self._idx, out=self.stream)
+    s = _mlp_shape(net)
+    ok = s and s[4] == "ReLU" and s[1] == 128 and 1 <= s[2] <= 2 and s[0] <= 32 and s[3] <= 4
+    return 128 if ok and N.load().tg_mlp_f32r_supported(128, s[2], _round_up(s[0], 8)) else 0
 
 
 def f32_wide_supported(net) -> int:
     """256 if `net` is Linear(S<=32, 256) ReLU [Linear(256, 256) ReLU]{0..4} Linear(256, A<=4) -- the reference's QuadPole factory
     (pipelines/quadpole_pipeline_ppo.py:54-58: 20-256x5-{4,1}) -- else 0."""
-    if not supports(net):
-        return 0
-    lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-    H = lin[0].out_features
-    if H != 256 or not (1 <= len(lin) - 1 <= 5) or lin[0].in_features > 32 or lin[-1].out_features > 4:
-        return 0
-    if any(l.out_features != H for l in lin[:-1]) or any(l.in_features != H for l in lin[1:]):
-        return 0
-    return H
+    s = _mlp_shape(net)
+    return 256 if s and s[4] == "ReLU" and s[1] == 256 and 1 <= s[2] <= 5 and s[0] <= 32 and s[3] <= 4 else 0
 
 
-class F32WideStream:
-    """The fp32 weight stream + tables of the H = 256 chain learner (csrc/mlp_f32_wide.hip), refreshed from the master weights with ONE
-    gather.  16-KiB blocks of 16 pieces x 64 lanes x 16 B, lane = (i = lane & 15, g = lane >> 4); a lane's 16 B are four consecutive
-    floats of a weight row (forward) or of a weight column (backward):
-      first layer, 2 blocks: block b, piece 2 tt + q:     W0[16 (8 b + tt) + i][8 g + 4 q + e]      (zero beyond the inputs)
-      forward, layer l = 1 .. nh - 1, block mo, piece t:  W_l[16 mo + i][16 t + 4 g + e]
-      backward, layer l = nh - 1 .. 1, block ko, piece t: W_l[16 t + 4 g + e][16 ko + i]
-    then the tables: [5][256] hidden biases | [4][256] head weights (rows >= A zero) | [4] head bias | 12 zeros."""
-    wide, res, act, machine = True, False, 0, "f32w"        # (act: TG_ACT_RELU -- the H = 256 kernel is ReLU-only)
-
-    def __init__(self, net):
-        lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-        self.lin, self.H = lin, 256
-        H = 256
-        dev = lin[0].weight.device
-        nh = len(lin) - 1
-        self.n_hidden, self.in_dim, self.out_dim = nh, lin[0].in_features, lin[-1].out_features
-        self.in_pad = _round_up(self.in_dim, 8)
-        woff, off = [], 0
-        for l in lin:
-            woff.append(off)
-            off += l.weight.numel()
-        boff = []
-        for l in lin:
-            boff.append(off)
-            off += l.bias.numel()
-        zero_at = off
-        lane = torch.arange(64, device=dev).view(1, 64, 1)
-        i, g = lane & 15, lane >> 4
-        e = torch.arange(4, device=dev).view(1, 1, 4)
-        idx = []
-        # first layer: 16 tiles x 2 pieces
-        q = torch.arange(2, device=dev).view(2, 1, 1)
-        for mo in range(16):
-            col = (8 * g + 4 * q + e).expand(2, 64, 4)
-            src = woff[0] + (16 * mo + i) * self.in_dim + col
-            idx.append(torch.where(col < self.in_dim, src, torch.full_like(src, zero_at)).reshape(-1))
-        t = torch.arange(16, device=dev).view(16, 1, 1)
-        k = (16 * t + 4 * g + e).expand(16, 64, 4)                                   # the contraction index of piece t, lane group g
-        for l in range(1, nh):                                                       # forward: W_l[16 mo + i][k]
-            for mo in range(16):
-                idx.append((woff[l] + (16 * mo + i) * H + k).reshape(-1))
-        for l in range(nh - 1, 0, -1):                                               # backward: W_l[k][16 ko + i]
-            for ko in range(16):
-                idx.append((woff[l] + k * H + (16 * ko + i)).reshape(-1))
-        n_stream = sum(x.numel() for x in idx)
-        for l in range(5):
-            idx.append(boff[l] + torch.arange(H, device=dev) if l < nh else torch.full((H,), zero_at, device=dev))
-        for a in range(4):
-            idx.append(woff[nh] + a * H + torch.arange(H, device=dev) if a < self.out_dim else torch.full((H,), zero_at, device=dev))
-        idx.append(torch.tensor([boff[nh] + a if a < self.out_dim else zero_at for a in range(4)] + [zero_at] * 12, device=dev))
-        self._idx = torch.cat([x.reshape(-1) for x in idx])
-        lib = N.load()
-        assert n_stream == lib.tg_mlp_f32w_stream_floats(nh) and self._idx.numel() - n_stream == lib.tg_mlp_f32w_table_floats()
-        self._zero = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.stream = torch.empty(self._idx.numel(), dtype=torch.float32, device=dev)          # blocks, then the tables
-        self.table = self.stream[n_stream:]
-        self.refresh()
-
-    @torch.no_grad()
-    def refresh(self):
-        """Two launches: concatenate the master tensors, gather."""
-        src = torch.cat([l.weight.reshape(-1) for l in self.lin] + [l.bias for l in self.lin] + [self._zero])
-        torch.index_select(src if src.dtype == torch.float32 else src.float(), 0, self._idx, out=self.stream)
-
-
-class F32ChainStream:
-    wide, res, machine = False, False, "f32"
-
-    """The fp32 weight stream of the chain learner, refreshed from the master weights with ONE gather:
+class F32ChainStream(WeightStream):
+    """The fp32 weight stream of the chain learner (refresh: two launches):
       [first layer, MFMA fragment order: H/32 tiles x k2/4 groups x 64 lanes x 4]  lane (i, kk), step s = 4 g + e of tile mo holds
                                                                                  W0[32 mo + i][s + kk k2]   (k2 = in_pad / 2)
       [hidden biases: n_hidden x H]  [head weights: 4 x H, rows >= A zero]  [head bias: 4]          (natural order)
@@ -1380,26 +1225,30 @@ class F32ChainStream:
                          W_l[32 mo + i][32 mt + F(t, kk)],  F(t, kk) = (t & 3) + 8 (t >> 2) + 4 kk  -- register t of the two lane
                          halves of the previous layer's accumulator tile mt (v_mfma_f32_32x32x2_f32: see the kernel's header)
       [backward blocks]  layer l = n_hh..1 (top first), output tile ko over the layer's INPUT features:
-                         W_l[32 mt + F(t, kk)][32 ko + i]"""
+                         W_l[32 mt + F(t, kk)][32 ko + i]
+    The methods say what GemmMLP needs to know of an fp32 learner machine besides its weights; F32ResStream and F32WideStream
+    override what differs on theirs."""
+    wide, res, machine = False, False, "f32"
+    tile_rows = 256                 # rows per workgroup pass: the launchers' grid is min(blocks(), ceil(rows / tile_rows))
+    takes_mask_bits = True          # the training entry takes the pointer of the top layer's ReLU mask bits ...
+    rebuilds_on_chip = True         # ... for the weight-gradient jobs that rebuild the first activation and the top dZ on chip
 
     def __init__(self, net, H: int, activation: str = "ReLU"):
-        lin = [m for m in net.network if isinstance(m, torch.nn.Linear)]
-        self.lin, self.H = lin, H
         self.act = ACTIVATIONS[activation]          # the kernels' hidden activation (TG_ACT_*): the stream itself does not depend on it
-        dev = lin[0].weight.device
-        nh = len(lin) - 1
-        self.n_hidden, self.in_dim, self.out_dim = nh, lin[0].in_features, lin[-1].out_features
+        self._dims(net, H)
+        self._build()
+        n = N.load().tg_mlp_f32_stream_floats(H, self.n_hidden, self.in_pad)
+        assert self.stream.numel() == n, (self.stream.numel(), n)
+        self.refresh()
+
+    def _dims(self, net, H):
+        self.lin, self.H = _linears(net), H
+        self.n_hidden, self.in_dim, self.out_dim = len(self.lin) - 1, self.lin[0].in_features, self.lin[-1].out_features
         self.in_pad = _round_up(self.in_dim, 8)
+
+    def _layout(self, woff, boff, zero_at, dev):
+        H, nh = self.H, self.n_hidden
         K2, MT = self.in_pad // 2, H // 32
-        woff, off = [], 0
-        for l in lin:
-            woff.append(off)
-            off += l.weight.numel()
-        boff = []
-        for l in lin:
-            boff.append(off)
-            off += l.bias.numel()
-        zero_at = off
         lane = torch.arange(64, device=dev).view(1, 64, 1)
         i, kk = lane & 31, lane >> 5
         e = torch.arange(4, device=dev).view(1, 1, 4)
@@ -1410,13 +1259,8 @@ class F32ChainStream:
         for mo in range(MT):
             row = (32 * mo + i).expand(K2 // 4, 64, 4)
             src = woff[0] + row * self.in_dim + col
-            idx.append(torch.where(col.expand_as(src) < self.in_dim, src, torch.full_like(src, zero_at)).reshape(-1))
-        # hidden biases, head weights (4 rows), head bias (4)
-        for l in range(nh):
-            idx.append(boff[l] + torch.arange(H, device=dev))
-        for a in range(4):
-            idx.append(woff[nh] + a * H + torch.arange(H, device=dev) if a < self.out_dim else torch.full((H,), zero_at, device=dev))
-        idx.append(torch.tensor([boff[nh] + a if a < self.out_dim else zero_at for a in range(4)], device=dev))
+            idx.append(torch.where(col.expand_as(src) < self.in_dim, src, torch.full_like(src, zero_at)))
+        idx += _head_table(self.lin, woff, boff, zero_at, dev, nh, 4, 4)
         # H x H blocks
         g = torch.arange(H // 8, device=dev).view(-1, 1, 1)
         s = 4 * g + e
@@ -1424,19 +1268,150 @@ class F32ChainStream:
         feat = (32 * mt + (t & 3) + 8 * (t >> 2) + 4 * kk).expand(H // 8, 64, 4)      # the contraction index of step s, lane half kk
         for l in range(1, nh):                                                          # forward: W_l[32 mo + i][feat]
             for mo in range(MT):
-                idx.append((woff[l] + (32 * mo + i) * H + feat).reshape(-1))
+                idx.append(woff[l] + (32 * mo + i) * H + feat)
         for l in range(nh - 1, 0, -1):                                                  # backward: W_l[feat][32 ko + i]
             for ko in range(MT):
-                idx.append((woff[l] + feat * H + (32 * ko + i)).reshape(-1))
-        self._idx = torch.cat([x.reshape(-1) for x in idx])
-        n = N.load().tg_mlp_f32_stream_floats(H, nh, self.in_pad)
-        assert self._idx.numel() == n, (self._idx.numel(), n)
-        self._zero = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.stream = torch.empty(n, dtype=torch.float32, device=dev)
+                idx.append(woff[l] + feat * H + (32 * ko + i))
+        return [(False, [("stream", idx)])]
+
+    # (common to every entry: input, its padding, weight stream; then these; then rows and the buffers)
+    def forward_args(self):
+        """What the no-grad entry (forward_entry) takes of this machine's weights and shape."""
+        return self.H, self.n_hidden
+
+    def loss_args(self):
+        """... and the training entry (loss_entry)."""
+        return self.H, self.n_hidden
+
+    def blocks(self) -> int:
+        return N.load().tg_mlp_f32_blocks()
+
+    def grid(self, rows: int) -> int:
+        """Workgroups of the training entry at `rows` (the launcher's own grid): the partial loss sums it leaves."""
+        return min(self.blocks(), -(-rows // self.tile_rows))
+
+    def kernel_prefix(self) -> str:
+        """The training kernel as the profiler names it, up to loss_entry()'s trailing template arguments."""
+        return f"tg::mlp_f32_chain_kernel<{self.H},true"
+
+    def dw_kernel(self) -> str:
+        """The weight-gradient launch as the profiler names it."""
+        one_job = self.H == 128 and self.n_hidden == 2
+        return f"tg::mlp_f32_dw_fused8_kernel<{self.H},...> + finish" if one_job else f"tg::mlp_f32_dw_kernel<{self.H}> + finish"
+
+    def log_line(self) -> str:
+        if self.act == N.TG_ACT_TANH:
+            return " Tanh: fp32 chain learner (tg_mlp_f32_forward_act / _forward_backward_act / _weight_grad)"
+        return ": fp32 chain learner (tg_mlp_f32_forward / _forward_backward / _weight_grad)"
+
+
+def _f32_16x16_blocks(woff, nh, H, dev):
+    """Index pieces of the H x H blocks the 16x16x4 fp32 MFMA kernels (resident, H = 256) share, lane = (i = lane & 15, g = lane >> 4),
+    [H/16 pieces t][64 lanes][4 e] per block: forward, layer l = 1 .. nh - 1, block mo: W_l[16 mo + i][16 t + 4 g + e]; then
+    backward, layer l = nh - 1 .. 1, block ko: W_l[16 t + 4 g + e][16 ko + i]."""
+    NT = H // 16
+    lane = torch.arange(64, device=dev).view(1, 64, 1)
+    i, g = lane & 15, lane >> 4
+    e = torch.arange(4, device=dev).view(1, 1, 4)
+    t = torch.arange(NT, device=dev).view(NT, 1, 1)
+    k = (16 * t + 4 * g + e).expand(NT, 64, 4)                                       # the contraction index of piece t, lane group g
+    return ([woff[l] + (16 * mo + i) * H + k for l in range(1, nh) for mo in range(NT)]
+            + [woff[l] + k * H + (16 * ko + i) for l in range(nh - 1, 0, -1) for ko in range(NT)])
+
+
+class F32ResStream(F32ChainStream):
+    """Weight stream, first-layer table and bias / head table of the resident 16-row kernel (csrc/mlp_f32_wide.hip, mlp_f32_res_kernel),
+    ONE buffer (refresh: two launches): lane = (i = lane & 15, g = lane >> 4)
+      stream: forward blocks [8 mo][8 t][64 lanes][4]: W_1[16 mo + i][16 t + 4 g + e]; backward blocks [8 ko][8 t][64][4]:
+              W_1[16 t + 4 g + e][16 ko + i]            (nothing with one hidden layer)
+      w0:     [8 mo][in_pad / 4 steps s][64 lanes]: W0[16 mo + i][4 s + g]              (zero beyond the inputs)
+      table:  [2][128] hidden biases | [4][128] head weights (rows >= A zero) | [4] head bias | 12 zeros
+    `stream` is the whole buffer, `w0` and `table` are views of it."""
+    wide, res, act, machine = False, True, 0, "f32r"        # (act: TG_ACT_RELU -- the resident kernel is ReLU-only)
+
+    def __init__(self, net):
+        self._dims(net, 128)
+        self._build()
+        lib, H, nh = N.load(), 128, self.n_hidden
+        assert self.stream.numel() - self.w0.numel() - self.table.numel() == lib.tg_mlp_f32r_stream_floats(H, nh)
+        assert self.w0.numel() == lib.tg_mlp_f32r_w0_floats(H, self.in_pad) and self.table.numel() == lib.tg_mlp_f32r_table_floats(H)
         self.refresh()
 
-    @torch.no_grad()
-    def refresh(self):
-        """Two launches: concatenate the master tensors, gather."""
-        src = torch.cat([l.weight.reshape(-1) for l in self.lin] + [l.bias for l in self.lin] + [self._zero])
-        torch.index_select(src if src.dtype == torch.float32 else src.float(), 0, self._idx, out=self.stream)
+    def _layout(self, woff, boff, zero_at, dev):
+        K4 = self.in_pad // 4
+        blocks = _f32_16x16_blocks(woff, self.n_hidden, 128, dev)
+        s4 = torch.arange(K4, device=dev).view(K4, 1)
+        ln = torch.arange(64, device=dev).view(1, 64)
+        col = (4 * s4 + (ln >> 4)).expand(K4, 64)
+        w0 = []
+        for mo in range(8):
+            src = woff[0] + (16 * mo + (ln & 15)).expand(K4, 64) * self.in_dim + col
+            w0.append(torch.where(col < self.in_dim, src, torch.full_like(src, zero_at)))
+        # (with one hidden layer there are no blocks: the buffer then starts with the first-layer table)
+        parts = [("stream", blocks), ("w0", w0), ("table", _head_table(self.lin, woff, boff, zero_at, dev, 2, 4, 16))]
+        return [(False, parts)]
+
+    def forward_args(self):
+        return self.w0.data_ptr(), self.table.data_ptr(), self.H, self.n_hidden, self.out_dim
+
+    def loss_args(self):
+        return self.w0.data_ptr(), self.table.data_ptr(), self.H, self.n_hidden
+
+    def grid(self, rows: int) -> int:
+        return N.load().tg_mlp_f32r_grid(rows)
+
+    def kernel_prefix(self) -> str:
+        return f"tg::mlp_f32_res_kernel<{self.H},{self.in_pad // 4},true"
+
+
+class F32WideStream(F32ChainStream):
+    """The fp32 weight stream + tables of the H = 256 chain learner (csrc/mlp_f32_wide.hip), ONE buffer (refresh: two launches).
+    16-KiB blocks of 16 pieces x 64 lanes x 16 B, lane = (i = lane & 15, g = lane >> 4); a lane's 16 B are four consecutive
+    floats of a weight row (forward) or of a weight column (backward):
+      first layer, 2 blocks: block b, piece 2 tt + q:     W0[16 (8 b + tt) + i][8 g + 4 q + e]      (zero beyond the inputs)
+      forward, layer l = 1 .. nh - 1, block mo, piece t:  W_l[16 mo + i][16 t + 4 g + e]
+      backward, layer l = nh - 1 .. 1, block ko, piece t: W_l[16 t + 4 g + e][16 ko + i]
+    then the tables (`table`, a view): [5][256] hidden biases | [4][256] head weights (rows >= A zero) | [4] head bias | 12 zeros."""
+    wide, res, act, machine = True, False, 0, "f32w"        # (act: TG_ACT_RELU -- the H = 256 kernel is ReLU-only)
+    tile_rows = 64
+    takes_mask_bits = False         # (the H = 256 learner's weight-gradient jobs read every operand back: nothing is rebuilt there yet)
+    rebuilds_on_chip = False
+
+    def __init__(self, net):
+        self._dims(net, 256)
+        self._build()
+        lib = N.load()
+        assert self.stream.numel() - self.table.numel() == lib.tg_mlp_f32w_stream_floats(self.n_hidden)
+        assert self.table.numel() == lib.tg_mlp_f32w_table_floats()
+        self.refresh()
+
+    def _layout(self, woff, boff, zero_at, dev):
+        lane = torch.arange(64, device=dev).view(1, 64, 1)
+        i, g = lane & 15, lane >> 4
+        e = torch.arange(4, device=dev).view(1, 1, 4)
+        q = torch.arange(2, device=dev).view(2, 1, 1)
+        col = (8 * g + 4 * q + e).expand(2, 64, 4)
+        first = []
+        for mo in range(16):                                                         # first layer: 16 tiles x 2 pieces
+            src = woff[0] + (16 * mo + i) * self.in_dim + col
+            first.append(torch.where(col < self.in_dim, src, torch.full_like(src, zero_at)))
+        blocks = _f32_16x16_blocks(woff, self.n_hidden, 256, dev)
+        return [(False, [("stream", first + blocks), ("table", _head_table(self.lin, woff, boff, zero_at, dev, 5, 4, 16))])]
+
+    def forward_args(self):
+        return self.table.data_ptr(), self.n_hidden
+
+    def loss_args(self):
+        return self.table.data_ptr(), self.n_hidden
+
+    def blocks(self) -> int:
+        return N.load().tg_mlp_f32w_blocks()
+
+    def kernel_prefix(self) -> str:
+        return "tg::mlp_f32_wide_kernel<true"
+
+    def dw_kernel(self) -> str:
+        return "tg::mlp_f32_wide_dw_kernel + finish"
+
+    def log_line(self) -> str:
+        return ": fp32 chain learner at H = 256 (tg_mlp_f32w_forward / _forward_backward / tg_mlp_f32_weight_grad)"

@@ -190,8 +190,9 @@ class StreamRefresher:
     against a FusedAdam's tensor table (the masters' pointers); rebuilt when that table changes."""
 
     def __init__(self, adam: FusedAdam, mlps, extra_streams=()):
-        """extra_streams: objects with segments(tensor_ids) -> [(dst, int32 codes, is_bf16)] and mark_fresh() (the fused fp32
-        rollout's register stream: the next rollout then starts without a refresh of its own)."""
+        """Every layout is an mlp.WeightStream, seen only through outputs, segments(tensor_ids) and mark_fresh().
+        extra_streams: streams no GemmMLP owns (the fused fp32 rollout's register stream, `rides_on_optimizer_step`: the next rollout
+        then starts without a refresh of its own)."""
         self.adam, self.mlps = adam, [m for m in mlps if m is not None]
         self.extra = [x for x in extra_streams if x is not None]
         self._sig = None
@@ -244,33 +245,16 @@ class StreamRefresher:
         for x in self.extra:
             x.mark_fresh()
 
-    def _codes(self, stream_obj, group):
-        """int32 code per element of `stream_obj._idx` (FragmentStream / F32ChainStream): master tensor << 24 | offset, -1 = zero."""
-        lin = stream_obj.lin
-        parts = []
-        for l in lin:
-            gi, ti = self.adam.tensor_ids[id(l.weight)]
-            assert gi == group
-            parts.append((ti << 24) + torch.arange(l.weight.numel(), dtype=torch.int64))
-        for l in lin:
-            gi, ti = self.adam.tensor_ids[id(l.bias)]
-            assert gi == group
-            parts.append((ti << 24) + torch.arange(l.bias.numel(), dtype=torch.int64))
-        parts.append(torch.tensor([-1], dtype=torch.int64))
-        src = torch.cat(parts).to(stream_obj._idx.device)
-        return src[stream_obj._idx].to(torch.int32)
+    def _streams(self):
+        """[(GemmMLP or None, what, stream)]: every net's layouts (GemmMLP.streams()), then the extra streams."""
+        return [(m, what, s) for m in self.mlps for what, s in m.streams()] + [(None, None, x) for x in self.extra]
 
     def _signature(self):
         """What the cached segment table is a function of: the optimizer's tensor table (the masters' pointers) AND every
         destination buffer -- a stream that was dropped or re-allocated since (GemmMLP.disable_f32_chain, a re-created rollout
         engine) must not be written through its old address."""
-        dst = []
-        for m in self.mlps:
-            for s_ in (m._chain, m._bchain, m._f32):
-                dst.append(None if s_ is None else (s_.stream.data_ptr(), getattr(s_, "bias", s_.stream).data_ptr()))
-        for x in self.extra:
-            dst.append((x.stream.data_ptr(), x.table.data_ptr()))
-        return (self.adam._sig, tuple(dst))
+        return (self.adam._sig, tuple([dst.data_ptr() for m in self.mlps for _, s in m.streams() for dst, _ in s.outputs]
+                                      + [dst.data_ptr() for x in self.extra for dst, _ in x.outputs]))
 
     def _build(self):
         sig = self._signature()
@@ -279,29 +263,12 @@ class StreamRefresher:
         self._sig, self._seg, self._marks, self._push = sig, None, [], None
         segs, keep, first = [], [], 0
         dev = None
-        for m in self.mlps:
-            streams = []
-            if m._chain is not None:
-                c = self._codes(m._chain, 0)
-                ns = m._chain._n_stream
-                streams += [(m._chain.stream, c[:ns].contiguous(), 1), (m._chain.bias.view(-1), c[ns:].contiguous(), 0)]
-                self._marks.append((m, "chain"))
-            if m._bchain is not None:
-                streams += [(m._bchain.stream, self._codes(m._bchain, 0).contiguous(), 1)]
-                self._marks.append((m, "bchain"))
-            if m._f32 is not None:
-                streams += [(m._f32.stream, self._codes(m._f32, 0).contiguous(), 0)]
-                self._marks.append((m, "f32"))
-            for dst, code, is_bf16 in streams:
-                assert code.numel() == dst.numel() and dst.is_contiguous()
-                segs.append([dst.data_ptr(), code.data_ptr(), first, is_bf16])      # (is_bf16 | pad) share one int64: little endian
-                keep.append(code)
-                first += dst.numel()
-                dev = dst.device
-        for x in self.extra:
-            for dst, code, is_bf16 in x.segments({k: v for k, v in self.adam.tensor_ids.items()}):
+        for m, what, s in self._streams():
+            if m is not None:
+                self._marks.append((m, what))
+            for dst, code, is_bf16 in s.segments(self.adam.tensor_ids):
                 assert code.numel() == dst.numel() and dst.is_contiguous() and code.dtype == torch.int32
-                segs.append([dst.data_ptr(), code.data_ptr(), first, is_bf16])
+                segs.append([dst.data_ptr(), code.data_ptr(), first, is_bf16])      # (is_bf16 | pad) share one int64: little endian
                 keep.append(code)
                 first += dst.numel()
                 dev = dst.device

@@ -325,13 +325,13 @@ class DeviceRollout:
                 self._frag = M.RegisterStreamF32(self.policy.actor, self._fused_H, self._f32_block_envs)
             else:
                 self._frag = M.FragmentStream(self.policy.actor, self._fused_H)
-        elif N.TRUST_KEYS and getattr(self._frag, "is_fresh", lambda: False)():
+        elif N.TRUST_KEYS and self._frag.rides_on_optimizer_step and self._frag.is_fresh():
             pass                                                  # (the learner's last launch rebuilt this stream, and the keys are trusted)
         else:
             # weights change every learn(); a write through `.data` leaves no trace in any key, so the stream is rebuilt at every
             # entry: by the learner's one gather launch when it has registered one (entry_refresh), else by the stream's own refresh
-            hook = getattr(self, "entry_refresh", None)
-            if hook is None or not hasattr(self._frag, "segments") or not hook():
+            hook = self.entry_refresh
+            if hook is None or not self._frag.rides_on_optimizer_step or not hook():
                 self._frag.refresh()
         n_hidden = len(self._linears) - 1
         on = getattr(self.policy, "obs_norm", None)
