@@ -396,6 +396,20 @@ int  tg_dx_relu_bias(const void* d_dz_in, const void* d_wfrag, const void* d_act
 int  tg_mlp_forward_chain(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden,
                           int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_masks,
                           float* d_out, int32_t out_cols, void* stream);
+/* Layout of the learner's INTERNAL [rows][H] bf16 tensors -- the stored activations and the dZ, whose one reader is
+ * tg_mlp_weight_grad.  TG_LAYOUT_ROWS: row-major (what every entry point without a layout argument writes and reads).
+ * TG_LAYOUT_PANEL: "panel order", the weight-gradient kernel's own LDS panel image per 32-row tile: the 16-byte chunk c (features
+ * 8 c .. 8 c + 7) of row r sits at byte
+ *     (r / 32) * 64 H  +  (r % 32 / 4) * (H / 32 * 256)  +  (c / 4) * 256  +  (r % 4) * 64  +  (c % 4) * 16
+ * Rows stay time-major; a buffer holds ceil(rows / 32) WHOLE tiles (64 H bytes each) and the producers fill the pad rows of the
+ * last tile with copies of the last row (finite; the consumer multiplies them by zeros).  The `_ex` entry points of the three
+ * producers take the layout they write; tg_dw_job.layout says which operands of a job are stored so.  Same values, same sums:
+ * only addresses differ. */
+enum { TG_LAYOUT_ROWS = 0, TG_LAYOUT_PANEL = 1 };
+/* tg_mlp_forward_chain with the layout of d_acts as an argument (TG_LAYOUT_PANEL: d_acts non-NULL, n_hidden_layers >= 2) */
+int  tg_mlp_forward_chain_ex(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden,
+                             int32_t n_hidden_layers, int64_t rows, void* const* d_acts, void* const* d_masks,
+                             float* d_out, int32_t out_cols, int32_t layout, void* stream);
 
 /* The training forward pass with the LOSS HEAD and the head's weight gradient inside it.  The clipped-surrogate / squared-error
  * gradient of a row (what tg_surrogate_loss + tg_head_prep produce: algorithms/ppo.py:159-179, grpo.py:122-140) is a function of the
@@ -470,6 +484,11 @@ int  tg_surrogate_loss_std(const tg_loss_args* a, const tg_ref_penalty* ref, con
 int  tg_mlp_forward_chain_loss_std(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
                                    int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
                                    const tg_ref_penalty* ref, const tg_learned_std* std, void* stream);
+/* tg_mlp_forward_chain_loss_std (ref, std nullable) with the layout of d_acts as an argument; TG_LAYOUT_PANEL is built for the plain
+ * head (ref == NULL or coef 0, std == NULL) and refused otherwise. */
+int  tg_mlp_forward_chain_loss_ex(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                                  int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
+                                  const tg_ref_penalty* ref, const tg_learned_std* std, int32_t layout, void* stream);
 int  tg_log_std_grad_blocks(void);
 int  tg_log_std_grad(const float* d_rows4, int64_t rows, int32_t act_dim, float add, float* d_grad, double* d_work, void* stream);
 /* (the fp32 chain learners' `_std` entry points are declared beside their plain ones below) */
@@ -529,6 +548,12 @@ int  tg_mlp_backward_chain_w0(const void* d_dout8, const void* d_wfrag, int32_t 
                               void* const* d_dz, const void* const* d_masks, const void* d_x, float* d_w0_slabs, int64_t slab_floats,
                               int32_t* n_slabs, void* stream);
 
+/* Either of the two with the layout of d_dz as an argument: d_x == NULL (d_w0_slabs, slab_floats, n_slabs ignored):
+ * tg_mlp_backward_chain without column sums; otherwise tg_mlp_backward_chain_w0. */
+int  tg_mlp_backward_chain_ex(const void* d_dout8, const void* d_wfrag, int32_t hidden, int32_t n_hidden_layers, int64_t rows,
+                              void* const* d_dz, const void* const* d_masks, const void* d_x, float* d_w0_slabs, int64_t slab_floats,
+                              int32_t* n_slabs, int32_t layout, void* stream);
+
 /* ---- MLP weight gradients, every layer in one persistent launch (what `loss.backward()` leaves in Linear.weight.grad /
  *      .bias.grad: algorithms/ppo.py:181-183, algorithms/grpo.py:143-145) ----
  *   wgrad[m][n] += sum over rows r of P[r][m] * Q[r][n]   (m < m_out, n < n_out)      bgrad[m] += sum over rows of P[r][m]
@@ -561,6 +586,8 @@ typedef struct tg_dw_job {
     int64_t     wgrad_ld;
     int32_t     kind;
     int32_t     m_out, n_out;
+    int32_t     layout;       /* (in what used to be padding: 0 = both row-major) bit 0: P, bit 1: Q is a [rows][H] operand in panel
+                               * order (TG_LAYOUT_PANEL; never the [rows][8] / [rows][32] operands of DH / RH / HX / HR) */
     const void* d_aux;        /* RH: the top hidden layer's ReLU mask bits; otherwise unused */
 } tg_dw_job;
 int64_t tg_mlp_weight_grad_workspace(int32_t hidden);

@@ -53,10 +53,13 @@ class LossArgs(C.Structure):
 
 class DwJob(C.Structure):
     _fields_ = [("d_p", C.c_void_p), ("d_q", C.c_void_p), ("d_wgrad", C.c_void_p), ("d_bgrad", C.c_void_p),
-                ("wgrad_ld", C.c_int64), ("kind", C.c_int32), ("m_out", C.c_int32), ("n_out", C.c_int32), ("d_aux", C.c_void_p)]
+                ("wgrad_ld", C.c_int64), ("kind", C.c_int32), ("m_out", C.c_int32), ("n_out", C.c_int32), ("layout", C.c_int32),
+                ("d_aux", C.c_void_p)]
 
 
 TG_DW_HH, TG_DW_HX, TG_DW_DH, TG_DW_HR, TG_DW_RH = 0, 1, 2, 3, 4
+TG_LAYOUT_ROWS, TG_LAYOUT_PANEL = 0, 1          # layout of the learner's internal [rows][H] bf16 tensors (see the header)
+DW_P_PANEL, DW_Q_PANEL = 1, 2                   # bits of tg_dw_job.layout
 
 
 class SlabSum(C.Structure):
@@ -201,11 +204,17 @@ SIGNATURES = {
     "tg_mlp_backward_chain": (C.c_int, [_VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP, _VP]),
     "tg_mlp_backward_chain_w0": (C.c_int, [_VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP, _VP, _I64,
                                            C.POINTER(C.c_int32), _VP]),
+    "tg_mlp_backward_chain_ex": (C.c_int, [_VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP, _VP, _I64,
+                                           C.POINTER(C.c_int32), _I32, _VP]),
     "tg_mlp_weight_grad_workspace": (C.c_int64, [_I32]),
     "tg_mlp_weight_grad": (C.c_int, [_I32, C.POINTER(DwJob), _I32, _I64, _VP, _VP, _VP, _VP, _I64, _VP]),
     "tg_mlp_weight_grad_ex": (C.c_int, [_I32, C.POINTER(DwJob), _I32, _I64, _VP, _VP, _VP, _VP, _I64, C.POINTER(SlabSum), _I32, _VP, _I32, _VP, _VP]),
     "tg_mlp_forward_chain": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP, _I32,
                                        _VP]),
+    "tg_mlp_forward_chain_ex": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _VP, _I32,
+                                          _I32, _VP]),
+    "tg_mlp_forward_chain_loss_ex": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                               C.POINTER(ChainLoss), _P(RefPenalty), _P(LearnedStd), _I32, _VP]),
     "tg_mlp_forward_chain_blocks": (C.c_int, []),
     "tg_mlp_forward_chain_loss": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                             C.POINTER(ChainLoss), _VP]),

@@ -33,6 +33,39 @@ __device__ static inline void act_store16(act_u32x4 v, act_u32x4* p) {
     __builtin_nontemporal_store(v, p);
 }
 
+// Panel order: the layout of the learner's INTERNAL [rows][H] bf16 tensors (stored activations, dZ), whose one reader is the
+// weight-gradient kernel (mlp_dw.hip).  A 32-row tile is stored as that kernel's plain LDS panel image
+// [row / 4][32-column group][row % 4][64 B] (DwGeom<H>): the 16-byte chunk c (features 8 c .. 8 c + 7) of row r sits at
+//     (r / 32) * 64 H  +  (r % 32 / 4) * (H / 32 * 256)  +  (c / 4) * 256  +  (r % 4) * 64  +  (c % 4) * 16
+// Rows stay time-major; a tensor is padded to whole tiles.  The chain kernels' lane (col, g) holds chunk 4 mt + g of its rows
+// after block mt, so it stores its 16 bytes as they stand (no LDS transpose): one instruction covers 16 rows x 64 B = four
+// 256-byte runs of whole lines; the consumer's 1-KiB LDS-DMA pieces are contiguous in memory.
+// Rows past the end: their lanes computed the last row over again (every input is clamped).  A lane whose row lies inside the
+// padded last tile writes that copy into ITS OWN pad slot -- never a valid row's bytes, and the consumer then reads finite
+// pad rows, which it multiplies by masked-out dZ; a lane beyond the padded end (a wave whose whole tile is past the end)
+// falls back on the last valid row, which it rewrites with the identical bytes the row's own lane stores.
+template <int H>
+struct PanelOrder {
+    static constexpr int CG = H / 32;                 // 32-column groups per row
+    static constexpr int ROWQ = CG * 256;             // bytes per 4-row group
+    static constexpr int PANEL = 8 * ROWQ;            // bytes per 32-row tile (= 32 * 2 H)
+    __host__ __device__ static constexpr int64_t chunk_off(int64_t row, int c) {
+        return (row >> 5) * PANEL + ((row >> 2) & 7) * ROWQ + (c >> 2) * 256 + (row & 3) * 64 + (c & 3) * 16;
+    }
+    __host__ __device__ static constexpr int64_t store_row(int64_t row, int64_t rows) {
+        return row < ((rows + 31) & ~(int64_t)31) ? row : rows - 1;
+    }
+};
+// the chain kernels' store of block mt: `off[c]` = chunk_off(store_row(the lane's row of column tile c), g), once per round
+template <int H>
+__device__ static inline void store_panel(uint16_t* __restrict__ g, const int64_t (&off)[2], int mt, const bf16x8 (&v)[2]) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const uint4 u = __builtin_bit_cast(uint4, v[c]);
+        act_store16(act_u32x4{u.x, u.y, u.z, u.w}, reinterpret_cast<act_u32x4*>(reinterpret_cast<char*>(g) + off[c] + mt * 256));
+    }
+}
+
 // ReLU + bf16 pack of 8 accumulators: round first (v_cvt_pk_bf16_f32, 2 per instruction), then clamp the PACKED halves
 // with v_pk_max_i16(x, 0) -- a negative bf16 (and -0) is a negative int16.  relu(round(x)) == round(relu(x)); 4 + 4
 // instructions instead of 8 v_med3_f32 + 4 conversions (A/B on one box: rollout 8.3 -> 8.1 ms, chain with stores -1.5 %).

@@ -82,13 +82,20 @@ __device__ static inline uint4 lds_read_b128_opaque(const uint4* p) {
     return v;
 }
 
-template <int H, int WPW, bool kFuse0>
+// kPanel: the dZ are stored in panel order (mfma_ring.hpp PanelOrder) instead of row-major.
+template <int H, int WPW, bool kFuse0, bool kPanel = false>
 __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4* __restrict__ dzh, const uint4* __restrict__ wfrag,
                                                                     int32_t n_layers, int64_t rows, BwdChainPtrs ptrs) {
     constexpr int MT = H / 32, KS = H / 16, K8 = H / 32;
     // ring of 3 slots, 2 blocks in flight (4 / 3 measured the same; the LDS goes to the store staging instead).  Behind
     // the block a wait is for: the DMA of the one later block and the stores of the last two blocks, one of them odd
     // (4 stores; the head block's 16 only add to that).
+    // kPanel: a storing block issues two stores (store_panel), whatever its parity: two storing blocks in front of a site are the
+    // same 4 stores, so kWaitN keeps its value -- but a site with only ONE storing block in front of it has 2 stores behind the
+    // DMA it waits for where the row-major form has 4 (when that block is odd) or none.  Those sites wait for the DMA alone:
+    // blocks 0 and 1 of the first hidden-to-hidden layer without the head block's stores (in front of them: the head block and
+    // the previous round's last block), and kFuse0's last layer from its SECOND block on (in front of block 1: block 0, which
+    // writes LDS tiles, and the last block of the layer above).
     constexpr int D = 3, P = D - 1;
     constexpr int kWaitN = (P - 1) * (KS / WPW) + 4;
     static_assert(KS % WPW == 0, "every wave moves the same number of 1-KiB pieces per block");
@@ -211,6 +218,11 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
         const int64_t row0 = round * (32 * WPW) + wave * 32;
         bf16x8 xin[2][K8], xout[2][K8];
         uint32_t mw[2][WPL];
+        [[maybe_unused]] int64_t poff[2];             // kPanel: byte offset of the lane's chunk g of its two rows (block 0)
+        if constexpr (kPanel) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) poff[c] = PanelOrder<H>::chunk_off(PanelOrder<H>::store_row(row0 + 16 * c + col, rows), grp);
+        }
 
         // ---- head: dZ_top^T = W_head^T . dOut^T; one block holds all MT output blocks (K padded to 32: one k-step) ----
         {
@@ -240,7 +252,12 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
                 }
 #pragma unroll
                 for (int c = 0; c < 2; ++c) xout[c][mt] = masked_pack(acc[0][c], acc[1][c], mw[c][mt >> 1], mt);
-                if ((mt & 1) && store_top) {
+                if constexpr (kPanel) {
+                    if (store_top) {
+                        const bf16x8 pv[2] = {xout[0][mt], xout[1][mt]};
+                        store_panel<H>(ptrs.dz[0], poff, mt, pv);
+                    }
+                } else if ((mt & 1) && store_top) {
                     const bf16x8 pa[2] = {xout[0][mt - 1], xout[1][mt - 1]}, pb[2] = {xout[0][mt], xout[1][mt]};
                     store_pair(stage, ptrs.dz[0] + 32 * (mt - 1), row0, rows, H, lane, pa, pb);
                 }
@@ -262,7 +279,8 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
                 if constexpr (kFuse0) {
                     if (fused_layer) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's tile writes are done
                 }
-                if ((mt == 1 && j == 1 && !store_top) || (kFuse0 && mt == 0 && j == 1 && !store_top) || (fused_layer && mt >= 2)) {
+                if ((mt == 1 && j == 1 && !store_top) || ((kFuse0 || kPanel) && mt == 0 && j == 1 && !store_top) ||
+                    (fused_layer && mt >= (kPanel ? 1 : 2))) {
                     TG_RING_WAIT((P - 1) * (KS / WPW))
                 } else {
                     TG_RING_WAIT(kWaitN)
@@ -304,6 +322,9 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
                         if (row0 + row >= rows) o = uint4{0u, 0u, 0u, 0u};
                         lds_store16(tw + (row >> 2) * 256 + (row & 3) * 64 + ((grp ^ ((row >> 2) & 3)) * 16), o);
                     }
+                } else if constexpr (kPanel) {
+                    const bf16x8 pv[2] = {xout[0][mt], xout[1][mt]};
+                    store_panel<H>(ptrs.dz[j], poff, mt, pv);
                 } else if (mt & 1) {
                     const bf16x8 pa[2] = {xout[0][mt - 1], xout[1][mt - 1]}, pb[2] = {xout[0][mt], xout[1][mt]};
                     store_pair(stage, ptrs.dz[j] + 32 * (mt - 1), row0, rows, H, lane, pa, pb);
@@ -373,7 +394,11 @@ using namespace tg;
 
 template <int H>
 static int launch_bwd_chain(const void* d_dout8, const void* d_wfrag, int32_t n_hidden_layers, int64_t rows, void* const* d_dz,
-                            const void* const* d_masks, float* d_partial, const void* d_x, float* d_w0_slabs, hipStream_t st) {
+                            const void* const* d_masks, float* d_partial, const void* d_x, float* d_w0_slabs, hipStream_t st,
+                            int32_t layout = TG_LAYOUT_ROWS) {
+    TG_REQUIRE(layout == TG_LAYOUT_ROWS || layout == TG_LAYOUT_PANEL, "tg_mlp_backward_chain_ex: layout %d", layout);
+    TG_REQUIRE(layout == TG_LAYOUT_ROWS || !d_partial, "tg_mlp_backward_chain_ex: the column sums read row-major dZ");
+    const bool panel = layout == TG_LAYOUT_PANEL;
     constexpr int WPW = 8, KS = H / 16;
     const int grid_max = bwd_chain_blocks();
     if (rows == 0) {
@@ -390,11 +415,23 @@ static int launch_bwd_chain(const void* d_dout8, const void* d_wfrag, int32_t n_
     }
     ptrs.x = (const uint4*)d_x;
     ptrs.w0_slabs = d_w0_slabs;
-    const size_t shmem = (size_t)3 * KS * 1024 + (size_t)WPW * 32 * 128 + (size_t)WPW * 1024 + (size_t)WPW * 3 * 1024 +
-                         (d_x ? (size_t)WPW * 2048 : 0);
+    // (the 32-KiB staging area: row-major stores transpose through it, the fused first layer keeps its shared tiles there)
+    const size_t shmem = (size_t)3 * KS * 1024 + (panel && !d_x ? 0 : (size_t)WPW * 32 * 128) + (size_t)WPW * 1024 +
+                         (size_t)WPW * 3 * 1024 + (d_x ? (size_t)WPW * 2048 : 0);
     const int64_t n_rounds = ceil_div(rows, (int64_t)32 * WPW);
     const unsigned grid = (unsigned)(n_rounds < grid_max ? n_rounds : grid_max);
-    if (d_x) {
+    if (panel) {                         // (separate instantiations: the row-major ones below are untouched)
+        auto launch = [&](auto kern, LdsOptIn& opt_in) {
+            if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_backward_chain_ex")) return rc;
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WPW), shmem, st, (const uint4*)d_dout8, (const uint4*)d_wfrag, n_hidden_layers,
+                               rows, ptrs);
+            return (int)TG_OK;
+        };
+        static LdsOptIn opt_in_w0, opt_in_plain;
+        const int rc = d_x ? launch(mlp_bwd_chain_kernel<H, WPW, true, true>, opt_in_w0)
+                           : launch(mlp_bwd_chain_kernel<H, WPW, false, true>, opt_in_plain);
+        if (rc != TG_OK) return rc;
+    } else if (d_x) {
         auto kern = mlp_bwd_chain_kernel<H, WPW, true>;
         static LdsOptIn opt_in;
         if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_backward_chain_w0")) return rc;
@@ -433,9 +470,9 @@ int tg_mlp_backward_chain(const void* d_dout8, const void* d_wfrag, int32_t hidd
                          : launch_bwd_chain<128>(d_dout8, d_wfrag, n_hidden_layers, rows, d_dz, d_masks, d_partial, nullptr, nullptr, st);
 }
 
-int tg_mlp_backward_chain_w0(const void* d_dout8, const void* d_wfrag, int32_t hidden, int32_t n_hidden_layers, int64_t rows,
+static int backward_chain_w0(const void* d_dout8, const void* d_wfrag, int32_t hidden, int32_t n_hidden_layers, int64_t rows,
                              void* const* d_dz, const void* const* d_masks, const void* d_x, float* d_w0_slabs, int64_t slab_floats,
-                             int32_t* n_slabs, void* stream) {
+                             int32_t* n_slabs, int32_t layout, void* stream) {
     TG_REQUIRE(d_dout8 && d_wfrag && d_dz && d_masks && d_x && d_w0_slabs && n_slabs, "tg_mlp_backward_chain_w0: null pointer");
     TG_REQUIRE(hidden == 256 || hidden == 128, "tg_mlp_backward_chain_w0: hidden width %d unsupported (128, 256)", hidden);
     TG_REQUIRE(n_hidden_layers >= 3 && n_hidden_layers <= kBwdMaxLayers, "tg_mlp_backward_chain_w0: %d hidden layers outside 3..%d",
@@ -448,8 +485,33 @@ int tg_mlp_backward_chain_w0(const void* d_dout8, const void* d_wfrag, int32_t h
                (long long)slab_floats, (long long)2 * bwd_chain_blocks() * hidden * 32);
     if (rows == 0) return TG_OK;
     hipStream_t st = (hipStream_t)stream;
-    return hidden == 256 ? launch_bwd_chain<256>(d_dout8, d_wfrag, n_hidden_layers, rows, d_dz, d_masks, nullptr, d_x, d_w0_slabs, st)
-                         : launch_bwd_chain<128>(d_dout8, d_wfrag, n_hidden_layers, rows, d_dz, d_masks, nullptr, d_x, d_w0_slabs, st);
+    return hidden == 256 ? launch_bwd_chain<256>(d_dout8, d_wfrag, n_hidden_layers, rows, d_dz, d_masks, nullptr, d_x, d_w0_slabs, st, layout)
+                         : launch_bwd_chain<128>(d_dout8, d_wfrag, n_hidden_layers, rows, d_dz, d_masks, nullptr, d_x, d_w0_slabs, st, layout);
+}
+
+int tg_mlp_backward_chain_w0(const void* d_dout8, const void* d_wfrag, int32_t hidden, int32_t n_hidden_layers, int64_t rows,
+                             void* const* d_dz, const void* const* d_masks, const void* d_x, float* d_w0_slabs, int64_t slab_floats,
+                             int32_t* n_slabs, void* stream) {
+    return backward_chain_w0(d_dout8, d_wfrag, hidden, n_hidden_layers, rows, d_dz, d_masks, d_x, d_w0_slabs, slab_floats, n_slabs,
+                             TG_LAYOUT_ROWS, stream);
+}
+
+/* both of the above with the layout of the dZ they write as an argument (TG_LAYOUT_*); d_x == NULL: tg_mlp_backward_chain */
+int tg_mlp_backward_chain_ex(const void* d_dout8, const void* d_wfrag, int32_t hidden, int32_t n_hidden_layers, int64_t rows,
+                             void* const* d_dz, const void* const* d_masks, const void* d_x, float* d_w0_slabs, int64_t slab_floats,
+                             int32_t* n_slabs, int32_t layout, void* stream) {
+    if (d_x == nullptr) {
+        TG_REQUIRE(d_dout8 && d_wfrag && d_dz && d_masks, "tg_mlp_backward_chain_ex: null pointer");
+        TG_REQUIRE(hidden == 256 || hidden == 128, "tg_mlp_backward_chain_ex: hidden width %d unsupported (128, 256)", hidden);
+        TG_REQUIRE(n_hidden_layers >= 3 && n_hidden_layers <= kBwdMaxLayers, "tg_mlp_backward_chain_ex: %d hidden layers outside 3..%d",
+                   n_hidden_layers, kBwdMaxLayers);
+        TG_REQUIRE(rows >= 0, "tg_mlp_backward_chain_ex: negative row count");
+        hipStream_t st = (hipStream_t)stream;
+        return hidden == 256 ? launch_bwd_chain<256>(d_dout8, d_wfrag, n_hidden_layers, rows, d_dz, d_masks, nullptr, nullptr, nullptr, st, layout)
+                             : launch_bwd_chain<128>(d_dout8, d_wfrag, n_hidden_layers, rows, d_dz, d_masks, nullptr, nullptr, nullptr, st, layout);
+    }
+    return backward_chain_w0(d_dout8, d_wfrag, hidden, n_hidden_layers, rows, d_dz, d_masks, d_x, d_w0_slabs, slab_floats, n_slabs, layout,
+                             stream);
 }
 
 }  // extern "C"

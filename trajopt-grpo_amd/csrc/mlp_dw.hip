@@ -55,7 +55,7 @@ struct DwJob {
     const uint16_t* p;        // bf16 [rows][H] (HH, HX, HR) or [rows][8] (DH, RH)
     const uint16_t* q;        // bf16 [rows][H] (HH, DH, RH) or [rows][32] (HX, HR)
     const uint32_t* aux;      // RH: ReLU mask bits of the top hidden layer, u32 [rows][H/32]
-    int32_t kind;
+    int32_t kind;             // DW_*, | kDwPanelP / kDwPanelQ: the [rows][H] operand p / q is stored in panel order (PanelOrder<H>)
     int32_t first_block;      // workgroups [first_block, first_block + n_blocks) work on this job
     int32_t n_blocks;
     int32_t slab_len;         // floats per slab
@@ -115,13 +115,14 @@ __device__ static inline bf16x8 mask_rows(bf16x8 f, int64_t first, int64_t rows)
     return __builtin_bit_cast(bf16x8, uint4{d[0], d[1], d[2], d[3]});
 }
 
-enum : int32_t { DW_HH = 0, DW_HX = 1, DW_DH = 2, DW_HR = 3, DW_RH = 4 };
+enum : int32_t { DW_HH = 0, DW_HX = 1, DW_DH = 2, DW_HR = 3, DW_RH = 4, kDwKindMask = 0xFF, kDwPanelP = 0x100, kDwPanelQ = 0x200 };
 
 template <int H>
 struct DwGeom {
-    static constexpr int CG = H / 32;                 // 32-column groups per row of a wide panel
-    static constexpr int ROWQ = CG * 256;             // bytes per 4-row group of a wide panel
-    static constexpr int PANEL = 8 * ROWQ;            // 32 rows
+    // the plain image of a wide panel is one tile of the panel-order layout (mfma_ring.hpp)
+    static constexpr int CG = PanelOrder<H>::CG;      // 32-column groups per row of a wide panel
+    static constexpr int ROWQ = PanelOrder<H>::ROWQ;  // bytes per 4-row group of a wide panel
+    static constexpr int PANEL = PanelOrder<H>::PANEL;   // 32 rows
     static constexpr int NPW = H / 128;               // 1-KiB DMA pieces per wave and wide panel
     static constexpr int MA = H / 128, NB = H / 64;   // HH: 32-row / 32-column output tiles per wave (4 x 2 waves)
     static constexpr int LDS_BYTES = 160 * 1024;      // the whole CU: one workgroup per CU
@@ -150,19 +151,34 @@ struct DwRing {
 };
 
 // ---- LDS-DMA of one stage (every call issues the same number of instructions per wave) ----
-template <int H>
+// kTiled: the operand is stored in panel order -- the stage IS tile row0 / 32 of it, image for image, so piece `piece` is the
+// contiguous KiB at piece * 1024 of the tile and lane L moves its bytes 16 L: the same instructions with the same destinations as
+// the row-major gather, whose piece is four 256-byte runs.  A stage past the end re-reads the last tile (whose pad rows the
+// producers filled with copies of the last row) where the row-major form re-reads the last row.
+// A compile-time argument (dw_run is instantiated per kind AND layout): as a run-time flag the address selection cost the
+// kernel 2.5 % in BOTH layouts (extra address arithmetic in front of every stage's DMA), as a branch 11 % (it splits the stage's
+// basic block, and the products lose their interleaving with the fragment reads) -- profiles/r06_panel_order_ab.md.
+template <int H, bool kTiled>
 __device__ static inline void dma_wide(const uint16_t* __restrict__ g, int64_t row0, int64_t rows, char* panel, int wave, int lane) {
     using G = DwGeom<H>;
+    // aux = 2: non-temporal -- every byte of the wide panels is read once (same-box A/B over the cache-policy bits: -1.3 %)
+    constexpr int kPanelLoadAux = 2;
+    if constexpr (kTiled) {
+        const int64_t tile = (row0 < rows ? row0 : rows - 1) >> 5;
+        const uint4* src = reinterpret_cast<const uint4*>(g) + tile * (G::PANEL / 16) + wave * G::NPW * 64 + lane;
 #pragma unroll
-    for (int t = 0; t < G::NPW; ++t) {
-        const int piece = wave * G::NPW + t;
-        const int rquad = piece / (G::CG / 4), ch = piece % (G::CG / 4);
-        int64_t r = row0 + 4 * rquad + ((lane >> 2) & 3);
-        r = r < rows ? r : rows - 1;
-        const uint4* src = reinterpret_cast<const uint4*>(g) + r * (H / 8) + (4 * ch + (lane >> 4)) * 4 + (lane & 3);
-        // aux = 2: non-temporal -- every byte of the wide panels is read once (same-box A/B over the cache-policy bits: -1.3 %)
-        constexpr int kPanelLoadAux = 2;
-        __builtin_amdgcn_global_load_lds(src, (lds_void*)(panel + piece * 1024), 16, 0, kPanelLoadAux);
+        for (int t = 0; t < G::NPW; ++t)
+            __builtin_amdgcn_global_load_lds(src + t * 64, (lds_void*)(panel + (wave * G::NPW + t) * 1024), 16, 0, kPanelLoadAux);
+    } else {
+#pragma unroll
+        for (int t = 0; t < G::NPW; ++t) {
+            const int piece = wave * G::NPW + t;
+            const int rquad = piece / (G::CG / 4), ch = piece % (G::CG / 4);
+            int64_t r = row0 + 4 * rquad + ((lane >> 2) & 3);
+            r = r < rows ? r : rows - 1;
+            const uint4* src = reinterpret_cast<const uint4*>(g) + r * (H / 8) + (4 * ch + (lane >> 4)) * 4 + (lane & 3);
+            __builtin_amdgcn_global_load_lds(src, (lds_void*)(panel + piece * 1024), 16, 0, kPanelLoadAux);
+        }
     }
 }
 // kSwz (HR, whose recompute reads the panel as MFMA B fragments, 16 rows x one 16-B chunk per 16 lanes: 4 rows share a bank group
@@ -204,26 +220,28 @@ __device__ static inline void dma_rh_aux(const uint16_t* __restrict__ dout, cons
     }
 }
 
-template <int H, int KIND>
+// LAYOUT: bit 0: P, bit 1: Q is stored in panel order (only ever set for a [rows][H] operand)
+template <int H, int KIND, int LAYOUT>
 __device__ static inline void dw_issue(const DwJob& job, int64_t sg, int64_t rows, char* slot, int wave, int lane) {
     using R = DwRing<H, KIND>;
     const int64_t row0 = sg * kDwStageRows;
+    constexpr bool kP = (LAYOUT & 1) != 0, kQ = (LAYOUT & 2) != 0;
     if constexpr (KIND == DW_HH) {
-        dma_wide<H>(job.p, row0, rows, slot + R::P_OFF, wave, lane);
-        dma_wide<H>(job.q, row0, rows, slot + R::Q_OFF, wave, lane);
+        dma_wide<H, kP>(job.p, row0, rows, slot + R::P_OFF, wave, lane);
+        dma_wide<H, kQ>(job.q, row0, rows, slot + R::Q_OFF, wave, lane);
     } else if constexpr (KIND == DW_HX || KIND == DW_HR) {
-        dma_wide<H>(job.p, row0, rows, slot + R::P_OFF, wave, lane);
+        dma_wide<H, kP>(job.p, row0, rows, slot + R::P_OFF, wave, lane);
         dma_x<KIND == DW_HR>(job.q, row0, rows, slot + R::Q_OFF, wave, lane);
     } else if constexpr (KIND == DW_RH) {
-        dma_wide<H>(job.q, row0, rows, slot + R::Q_OFF, wave, lane);
+        dma_wide<H, kQ>(job.q, row0, rows, slot + R::Q_OFF, wave, lane);
         dma_rh_aux<H>(job.p, job.aux, row0, rows, slot + R::AUX_OFF, wave, lane);
     } else {
         dma_d8(job.p, row0, rows, slot + R::P_OFF, lane);
-        dma_wide<H>(job.q, row0, rows, slot + R::Q_OFF, wave, lane);
+        dma_wide<H, kQ>(job.q, row0, rows, slot + R::Q_OFF, wave, lane);
     }
 }
 
-template <int H, int KIND>
+template <int H, int KIND, int LAYOUT = 0>
 __device__ static void dw_run(const DwArgs& args, const DwJob& job, int64_t rows, float* __restrict__ ws, char* lds_c) {
     using G = DwGeom<H>;
     using R = DwRing<H, KIND>;
@@ -314,7 +332,7 @@ __device__ static void dw_run(const DwArgs& args, const DwJob& job, int64_t rows
     int slot_issue = 0;
 #pragma unroll 1
     for (int i = 0; i < P; ++i) {
-        dw_issue<H, KIND>(job, sg_issue, rows, lds_c + slot_issue * R::SLOT, wave, lane);
+        dw_issue<H, KIND, LAYOUT>(job, sg_issue, rows, lds_c + slot_issue * R::SLOT, wave, lane);
         sg_issue += nb;
         slot_issue = slot_issue + 1 == D ? 0 : slot_issue + 1;
     }
@@ -378,7 +396,7 @@ __device__ static void dw_run(const DwArgs& args, const DwJob& job, int64_t rows
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWait) : "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        dw_issue<H, KIND>(job, sg_issue, rows, lds_c + slot_issue * R::SLOT, wave, lane);
+        dw_issue<H, KIND, LAYOUT>(job, sg_issue, rows, lds_c + slot_issue * R::SLOT, wave, lane);
         sg_issue += nb;
         slot_issue = slot_issue + 1 == D ? 0 : slot_issue + 1;
 
@@ -538,12 +556,30 @@ __global__ __launch_bounds__(512, 2) void dw_kernel(DwArgs args, int64_t rows, f
     for (int t = 1; t < kDwMaxJobs; ++t)
         if (t < args.n_jobs && (int)blockIdx.x >= args.job[t].first_block) j = t;
     const DwJob job = args.job[j];
-    switch (job.kind) {
-        case DW_HH: dw_run<H, DW_HH>(args, job, rows, ws, lds_c); break;
-        case DW_HX: dw_run<H, DW_HX>(args, job, rows, ws, lds_c); break;
-        case DW_DH: dw_run<H, DW_DH>(args, job, rows, ws, lds_c); break;
-        case DW_RH: dw_run<H, DW_RH>(args, job, rows, ws, lds_c); break;
-        default: dw_run<H, DW_HR>(args, job, rows, ws, lds_c); break;
+    const bool pp = (job.kind & kDwPanelP) != 0, pq = (job.kind & kDwPanelQ) != 0;       // (the host sets them for [rows][H] operands only)
+    switch (job.kind & kDwKindMask) {
+        case DW_HH:
+            if (pp && pq) dw_run<H, DW_HH, 3>(args, job, rows, ws, lds_c);
+            else if (pp) dw_run<H, DW_HH, 1>(args, job, rows, ws, lds_c);
+            else if (pq) dw_run<H, DW_HH, 2>(args, job, rows, ws, lds_c);
+            else dw_run<H, DW_HH>(args, job, rows, ws, lds_c);
+            break;
+        case DW_HX:
+            if (pp) dw_run<H, DW_HX, 1>(args, job, rows, ws, lds_c);
+            else dw_run<H, DW_HX>(args, job, rows, ws, lds_c);
+            break;
+        case DW_DH:
+            if (pq) dw_run<H, DW_DH, 2>(args, job, rows, ws, lds_c);
+            else dw_run<H, DW_DH>(args, job, rows, ws, lds_c);
+            break;
+        case DW_RH:
+            if (pq) dw_run<H, DW_RH, 2>(args, job, rows, ws, lds_c);
+            else dw_run<H, DW_RH>(args, job, rows, ws, lds_c);
+            break;
+        default:
+            if (pp) dw_run<H, DW_HR, 1>(args, job, rows, ws, lds_c);
+            else dw_run<H, DW_HR>(args, job, rows, ws, lds_c);
+            break;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     TG_CLOCK_PROBE_END(g_probe_weight_grad)
@@ -687,6 +723,10 @@ int tg_mlp_weight_grad_ex(int32_t hidden, const tg_dw_job* jobs, int32_t n_jobs,
         TG_REQUIRE(jb.kind != TG_DW_DH || !jb.d_bgrad, "tg_mlp_weight_grad: job %d: the head's bias gradient comes from tg_head_prep", j);
         TG_REQUIRE(jb.kind != TG_DW_HR || (d_w0frag && d_b0), "tg_mlp_weight_grad: job %d recomputes the first layer: weights / bias missing", j);
         TG_REQUIRE(jb.kind != TG_DW_RH || (d_whfrag && jb.d_aux), "tg_mlp_weight_grad: job %d recomputes the top dZ: head weights / mask bits missing", j);
+        // panel order is a layout of the [rows][H] operands: P of HH / HX / HR, Q of HH / DH / RH
+        const int wide = (jb.kind == TG_DW_HH ? 3 : (jb.kind == TG_DW_HX || jb.kind == TG_DW_HR ? 1 : 2));
+        TG_REQUIRE((jb.layout & ~wide) == 0, "tg_mlp_weight_grad: job %d (kind %d): layout bits %d name an operand that is not [rows][H]", j, jb.kind,
+                   jb.layout);
         wsum += dw_row_cost(H, jb.kind);
     }
     // workgroups per job in proportion to its bytes per row (largest remainders), at least one, at most one per 4 stages
@@ -726,7 +766,7 @@ int tg_mlp_weight_grad_ex(int32_t hidden, const tg_dw_job* jobs, int32_t n_jobs,
         dj.p = (const uint16_t*)jb.d_p;
         dj.q = (const uint16_t*)jb.d_q;
         dj.aux = (const uint32_t*)jb.d_aux;
-        dj.kind = jb.kind;
+        dj.kind = jb.kind | ((jb.layout & 1) ? kDwPanelP : 0) | ((jb.layout & 2) ? kDwPanelQ : 0);
         dj.first_block = grid;
         dj.n_blocks = alloc[j] < cap ? alloc[j] : cap;
         dj.slab_len = dw_slab_len(H, jb.kind);

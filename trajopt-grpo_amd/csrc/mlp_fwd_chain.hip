@@ -198,7 +198,8 @@ __device__ static inline int wave_of(unsigned tid) { return (int)(tid >> 6); }
 // per-row input, one expf per row.
 // kStd (with kHead): the policy's learned log-std (tg_mlp_forward_chain_loss_std): the Gaussian's constants come from the device, and
 // each valid actor row stores dlp (dmu_k^2 inv_var_k - 1), its contribution to d loss / d log_std (one more 16-B store per row).
-template <int H, int WPW, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false>
+// kPanel (with kStore): the activations are stored in panel order (mfma_ring.hpp PanelOrder) instead of row-major.
+template <int H, int WPW, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false, bool kPanel = false>
 __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16_t* __restrict__ x, const uint4* __restrict__ wfrag,
                                                                     const float* __restrict__ bias, int32_t n_hh, int64_t rows,
                                                                     ChainActs acts, float* __restrict__ out, int32_t out_cols,
@@ -206,6 +207,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     static_assert(!kHead || (kStore && !kA0), "the fused head belongs to the learner's training pass");
     static_assert(!kRef || kHead, "the reference penalty is a term of the fused head");
     static_assert(!kStd || kHead, "the learned log-std is a term of the fused head");
+    static_assert(!kPanel || (kStore && D == 4), "panel order is a layout of the stored activations; its wait counts are for P = 3");
     // (written into the by-value argument as norm8's values are below: the compiler's resource report shows 0 B of scratch and no
     // vector-register spill for every instantiation of this kernel, the kStd ones included -- the fields stay scalar registers)
     if constexpr (kHead) loss_from_device<kStd>(L);
@@ -221,6 +223,21 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     // kA0 == false: the first hidden activation is not stored (tg_mlp_weight_grad recomputes it, kind HR), so the
     // first-layer block has no stores behind it; the three sites whose window would count them wait for the DMAs alone
     constexpr int kWaitMin = (P - 1) * (KS / WPW);
+    // kPanel: a hidden block that stores issues exactly TWO stores (store_panel: one per 16-row column tile) right behind its
+    // products, whatever its parity, so behind DMA(c) lie the P - 1 later DMAs and 2 s stores, s = the storing blocks among the
+    // P = 3 blocks c - 3 .. c - 1 (TG_PANEL_WAIT(s)).  Blocks counted as storing nothing: the head block (its 0-4 output / mask
+    // stores only add), the first-layer block (2 MT stores with kA0, none without) and, with kHead, the top layer's.  Per site:
+    //   first-layer block: in front of it the head and the last layer's blocks MT - 1, MT - 2: s = 2 (kHead: 0) -- the same
+    //     numbers as kWaitOdd / kWaitMin of the row-major form at P = 3, so that site is shared;
+    //   block mt of layer 0: its own mt earlier blocks, then the first-layer block and the head: s = min(mt, 3);
+    //   block mt of a layer above (not kHead's top layer): three storing blocks, of its own layer or the one below: s = 3;
+    //   block mt of kHead's top layer: its own blocks store nothing, the layer below did: s = 3 - min(mt, 3);
+    //   head block: the last layer's final three blocks: s = 3 (kHead: 0).  (At least one hidden-to-hidden layer: the entry
+    //     points require it.)
+    // More stores than counted (mask words, kStd's rows, the first layer's with kA0) only make a wait stricter.
+#define TG_PANEL_WAIT(S)                                                                    \
+    if ((S) == 0) { TG_RING_WAIT(kWaitMin) } else if ((S) == 1) { TG_RING_WAIT(kWaitMin + 2) } \
+    else if ((S) == 2) { TG_RING_WAIT(kWaitMin + 4) } else { TG_RING_WAIT(kWaitMin + 6) }
     static_assert(KS % WPW == 0, "every wave moves the same number of 1-KiB pieces per block");
     extern __shared__ uint4 lds[];
     uint4* ring = lds;                                                  // D * KS * 64 uint4
@@ -313,6 +330,11 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
             rowc[c] = rowc[c] < rows ? rowc[c] : rows - 1;
         }
         bf16x8 xin[2][K8], xout[2][K8];
+        [[maybe_unused]] int64_t poff[2];             // kPanel: byte offset of the lane's chunk g of its two rows (block 0)
+        if constexpr (kPanel) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) poff[c] = PanelOrder<H>::chunk_off(PanelOrder<H>::store_row(row0 + 16 * c + col, rows), grp);
+        }
 
         // ---- layer 0: [H x 32] . [32 x 32 rows]; one block holds all MT output blocks (one k-step, 2 halves each) ----
         {
@@ -339,7 +361,12 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                 for (int c = 0; c < 2; ++c)
                     xout[c][mt] = relu_pack_bf16(acc[0][c][0], acc[0][c][1], acc[0][c][2], acc[0][c][3], acc[1][c][0], acc[1][c][1],
                                                  acc[1][c][2], acc[1][c][3]);
-                if (kStore && kA0 && (mt & 1)) {
+                if constexpr (kPanel) {
+                    if (kA0) {
+                        const bf16x8 pv[2] = {xout[0][mt], xout[1][mt]};
+                        store_panel<H>(acts.p[0], poff, mt, pv);
+                    }
+                } else if (kStore && kA0 && (mt & 1)) {
                     const bf16x8 pa[2] = {xout[0][mt - 1], xout[1][mt - 1]}, pb[2] = {xout[0][mt], xout[1][mt]};
                     store_pair(stage, acts.p[0] + 32 * (mt - 1), row0, rows, H, lane, pa, pb);
                 }
@@ -360,7 +387,10 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                 // (kHead: the top layer stores nothing: from its fourth block on only DMAs lie behind a block, behind its third
                 // one stored pair of the layer below)
                 const bool top_layer = kHead && l == n_hh - 1;
-                if ((kStore && !kA0 && l == 0 && mt < 3) || (top_layer && mt >= 3)) {
+                if constexpr (kPanel) {
+                    const int same = mt < 3 ? mt : 3;                  // (a constant of the unrolled loop)
+                    if (top_layer) { TG_PANEL_WAIT(3 - same) } else if (l == 0) { TG_PANEL_WAIT(same) } else { TG_PANEL_WAIT(3) }
+                } else if ((kStore && !kA0 && l == 0 && mt < 3) || (top_layer && mt >= 3)) {
                     TG_RING_WAIT(kWaitMin)
                 } else if ((mt & 1) || (top_layer && mt == 2)) {
                     TG_RING_WAIT(kWaitOdd)
@@ -376,7 +406,13 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                 chain_block<K8>(cur, bl + 32 * mt, xin, o, lane);
                 xout[0][mt] = o[0];
                 xout[1][mt] = o[1];
-                if (mt & 1) {
+                if constexpr (kPanel) {
+                    if (mt == MT - 1 && acts.m[l]) {
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) store_mask_words<MT>(acts.m[l], rowc[c], grp, mw[c]);
+                    }
+                    if (!top_layer) store_panel<H>(acts.p[l + 1], poff, mt, o);
+                } else if (mt & 1) {
                     // (with the mask stores more stores sit behind this block than the wait sites count: stricter, never weaker)
                     if (kStore && mt == MT - 1 && acts.m[l]) {
 #pragma unroll
@@ -395,7 +431,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
         }
         // ---- head: <= 16 outputs in half 0 of the block, natural order: register r of lane group g is output 4 g + r ----
         {
-            if constexpr (kHead) { TG_RING_WAIT(kWaitMin) } else { TG_RING_WAIT(kWaitEven) }
+            if constexpr (kHead) { TG_RING_WAIT(kWaitMin) } else if constexpr (kPanel) { TG_PANEL_WAIT(3) } else { TG_RING_WAIT(kWaitEven) }
             TG_RING_NEXT
             if (kStore && acts.m[n_hh]) {                       // the last hidden activation's mask bits
 #pragma unroll
@@ -560,13 +596,14 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     if constexpr (kHead) { TG_CLOCK_PROBE_END(g_probe_fwd_chain) } else { TG_CLOCK_PROBE_END(g_probe_fwd_chain_plain) }
 }
 
-template <int H, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false>
+template <int H, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false, bool kPanel = false>
 static int chain_launch(const void* x, const void* wfrag, const float* bias, int n_hh, int64_t rows, const ChainActs& acts, float* out,
                         int out_cols, hipStream_t st, const ChainLoss& loss = ChainLoss{}) {
     constexpr int WPW = 8, KS = H / 16;
+    // (the store staging area: row-major stores transpose through it, the head phase keeps its shared tiles there)
     const size_t shmem = (size_t)D * KS * 1024 + (size_t)(n_hh + 2) * H * sizeof(float) + (size_t)WPW * 2048 +
-                         (size_t)WPW * 32 * 128 + (kHead ? (size_t)2 * WPW * 1024 + (size_t)WPW * 16 * 48 + (size_t)WPW * (H / 32) * 16 * 16 : 0);
-    auto kern = mlp_fwd_chain_kernel<H, WPW, kStore, D, kA0, kHead, kRef, kStd>;
+                         (kPanel && !kHead ? 0 : (size_t)WPW * 32 * 128) + (kHead ? (size_t)2 * WPW * 1024 + (size_t)WPW * 16 * 48 + (size_t)WPW * (H / 32) * 16 * 16 : 0);
+    auto kern = mlp_fwd_chain_kernel<H, WPW, kStore, D, kA0, kHead, kRef, kStd, kPanel>;
     static LdsOptIn opt_in;
     if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_forward_chain")) return rc;
     const int cus = device_cus();
@@ -584,8 +621,9 @@ using namespace tg;
 
 extern "C" {
 
-int tg_mlp_forward_chain(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
-                         int64_t rows, void* const* d_acts, void* const* d_masks, float* d_out, int32_t out_cols, void* stream) {
+static int forward_chain(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                         int64_t rows, void* const* d_acts, void* const* d_masks, float* d_out, int32_t out_cols, int32_t layout,
+                         void* stream) {
     TG_REQUIRE(d_x && d_wfrag && d_bias && d_out, "tg_mlp_forward_chain: null pointer");
     TG_REQUIRE(hidden == 128 || hidden == 256, "tg_mlp_forward_chain: hidden width %d unsupported (128, 256)", hidden);
     TG_REQUIRE(n_hidden_layers >= 1 && n_hidden_layers <= kChainMaxHidden, "tg_mlp_forward_chain: %d hidden layers outside 1..%d",
@@ -606,6 +644,15 @@ int tg_mlp_forward_chain(const void* d_x, const void* d_wfrag, const float* d_bi
 #define TG_CHAIN_ARGS d_x, d_wfrag, d_bias, n_hh, rows, acts, d_out, out_cols, st
     // ring of 4 slots, 3 blocks in flight (6 slots / 5 in flight measured the same: 2.94 vs 2.96 ms)
     const bool a0 = d_acts && d_acts[0];             // the first activation may be left out (recomputed by tg_mlp_weight_grad)
+    TG_REQUIRE(layout == TG_LAYOUT_ROWS || layout == TG_LAYOUT_PANEL, "tg_mlp_forward_chain_ex: layout %d", layout);
+    if (layout == TG_LAYOUT_PANEL) {                 // (separate instantiations: the row-major ones above are untouched)
+        TG_REQUIRE(d_acts && n_hidden_layers >= 2, "tg_mlp_forward_chain_ex: panel order is a layout of >= 2 stored activations");
+        if (hidden == 256)
+            return a0 ? chain_launch<256, true, 4, true, false, false, false, true>(TG_CHAIN_ARGS)
+                      : chain_launch<256, true, 4, false, false, false, false, true>(TG_CHAIN_ARGS);
+        return a0 ? chain_launch<128, true, 4, true, false, false, false, true>(TG_CHAIN_ARGS)
+                  : chain_launch<128, true, 4, false, false, false, false, true>(TG_CHAIN_ARGS);
+    }
     if (hidden == 256)
         return !d_acts ? chain_launch<256, false, 4, true>(TG_CHAIN_ARGS)
                        : (a0 ? chain_launch<256, true, 4, true>(TG_CHAIN_ARGS) : chain_launch<256, true, 4, false>(TG_CHAIN_ARGS));
@@ -614,12 +661,24 @@ int tg_mlp_forward_chain(const void* d_x, const void* d_wfrag, const float* d_bi
 #undef TG_CHAIN_ARGS
 }
 
+int tg_mlp_forward_chain(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                         int64_t rows, void* const* d_acts, void* const* d_masks, float* d_out, int32_t out_cols, void* stream) {
+    return forward_chain(d_x, d_wfrag, d_bias, hidden, n_hidden_layers, rows, d_acts, d_masks, d_out, out_cols, TG_LAYOUT_ROWS, stream);
+}
+
+int tg_mlp_forward_chain_ex(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                            int64_t rows, void* const* d_acts, void* const* d_masks, float* d_out, int32_t out_cols, int32_t layout,
+                            void* stream) {
+    return forward_chain(d_x, d_wfrag, d_bias, hidden, n_hidden_layers, rows, d_acts, d_masks, d_out, out_cols, layout, stream);
+}
+
 int tg_mlp_forward_chain_blocks(void) { return device_cus(); }
 
 static int forward_chain_loss(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
                               int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss, const tg_ref_penalty* ref,
-                              void* stream, const tg_learned_std* std = nullptr) {
+                              void* stream, const tg_learned_std* std = nullptr, int32_t layout = TG_LAYOUT_ROWS) {
     TG_REQUIRE(loss, "tg_mlp_forward_chain_loss: null pointer");
+    TG_REQUIRE(layout == TG_LAYOUT_ROWS || layout == TG_LAYOUT_PANEL, "tg_mlp_forward_chain_loss_ex: layout %d", layout);
     const int use_ref = ref_penalty_check(ref, loss->kind != 0, loss->kl_coef, "tg_mlp_forward_chain_loss_ref");
     if (use_ref < 0) return use_ref;
     const int use_std = learned_std_check(std, loss->kind != 0, loss->act_dim, "tg_mlp_forward_chain_loss_std");
@@ -653,6 +712,11 @@ static int forward_chain_loss(const void* d_x, const void* d_wfrag, const float*
     L.dout8 = (uint16_t*)loss->d_dout8; L.head_slabs = loss->d_head_slabs; L.work = loss->d_work; L.bias_partial = loss->d_bias_partial;
     hipStream_t st = (hipStream_t)stream;
     const int n_hh = n_hidden_layers - 1;
+    if (layout == TG_LAYOUT_PANEL) {                    // (separate instantiations again)
+        TG_REQUIRE(!use_std && !use_ref, "tg_mlp_forward_chain_loss_ex: panel order is built for the plain head only");
+        return hidden == 256 ? chain_launch<256, true, 4, false, true, false, false, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L)
+                             : chain_launch<128, true, 4, false, true, false, false, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L);
+    }
     if (use_std) {                                      // (separate instantiations: the plain heads below are untouched)
         if (use_ref)
             return hidden == 256 ? chain_launch<256, true, 4, false, true, true, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L)
@@ -682,6 +746,12 @@ int tg_mlp_forward_chain_loss_std(const void* d_x, const void* d_wfrag, const fl
                                   int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
                                   const tg_ref_penalty* ref, const tg_learned_std* std, void* stream) {
     return forward_chain_loss(d_x, d_wfrag, d_bias, hidden, n_hidden_layers, rows, d_acts, d_masks, loss, ref, stream, std);
+}
+
+int tg_mlp_forward_chain_loss_ex(const void* d_x, const void* d_wfrag, const float* d_bias, int32_t hidden, int32_t n_hidden_layers,
+                                 int64_t rows, void* const* d_acts, void* const* d_masks, const tg_chain_loss* loss,
+                                 const tg_ref_penalty* ref, const tg_learned_std* std, int32_t layout, void* stream) {
+    return forward_chain_loss(d_x, d_wfrag, d_bias, hidden, n_hidden_layers, rows, d_acts, d_masks, loss, ref, stream, std, layout);
 }
 
 }  // extern "C"

@@ -122,11 +122,16 @@ def weight_grad(hidden: int, jobs, rows: int, workspace: torch.Tensor, w0frag: t
     fixed-order reduction.  jobs = [(kind, P, Q, wgrad, bgrad or None[, aux])]; P / Q bf16 row-major [rows][*], wgrad a 2-D
     fp32 view with unit column stride (e.g. a window of the learner's flat gradient bucket).  Kind HR rebuilds its Q (the first
     hidden activation) from the net input with `w0frag` / `b0`; kind RH rebuilds its P (the top layer's dZ) from d loss / d head
-    output, the layer's ReLU mask bits (`aux`) and `whfrag` (the backward chain's weight stream)."""
+    output, the layer's ReLU mask bits (`aux`) and `whfrag` (the backward chain's weight stream).  A seventh job element
+    (N.DW_P_PANEL | N.DW_Q_PANEL) names the [rows][H] operands that are stored in panel order (whole 32-row tiles, see the header)
+    instead of row-major."""
     arr = (N.DwJob * len(jobs))()
     for slot, job in zip(arr, jobs):
         kind, p, q, wgrad, bgrad = job[:5]
         aux = job[5] if len(job) > 5 else None
+        slot.layout = job[6] if len(job) > 6 else 0
+        assert not (slot.layout & N.DW_P_PANEL) or p.shape[0] >= _round_up(rows, 32)
+        assert not (slot.layout & N.DW_Q_PANEL) or q.shape[0] >= _round_up(rows, 32)
         N.require_cuda(p, q, wgrad, bgrad, aux)
         assert (kind == N.TG_DW_RH) == (aux is not None)
         slot.d_aux = N.ptr(aux)
@@ -205,6 +210,11 @@ def _mlp_shape(net):
     return lin[0].in_features, H, len(lin) - 1, lin[-1].out_features, act
 
 
+# forward_loss() of the bf16 chain learner stores its activations in panel order (the loss-head pass; False: that pass stays
+# row-major, and so do the dZ unless GemmMLP.panel_mixed asks for them)
+PANEL_ORDER_HEAD_PASS = True
+
+
 def _round_up(x, m):
     return (x + m - 1) // m * m
 
@@ -254,6 +264,13 @@ class GemmMLP:
         # (parity tests: every hidden activation and dZ of the fp32 chain learner written to HBM, so that each can be compared with
         # fp64; the product rebuilds the first activation and the top dZ on chip instead)
         self.f32_store_all = False
+        # the bf16 chain learner (forward_loss() / backward_fused()) keeps its internal workspaces -- the stored activations and the
+        # dZ, which only tg_mlp_weight_grad reads -- in panel order (include/trajopt_grpo_hip.h TG_LAYOUT_PANEL); False: row-major,
+        # the same values at other addresses.  forward(keep=True) / backward() always store row-major: callers may read those.
+        self.panel_order = True
+        # ... the dZ only where the activations are (the plain loss head): a weight-gradient job with ONE operand in panel order ran
+        # 6 % slower than with both or neither (profiles/r06_panel_order_ab.md).  True: the dZ regardless (tools/panel_order_probe.py)
+        self.panel_mixed = False
         if self.act == "Tanh":
             # (the resident 16-row kernel and the H = 256 kernel are ReLU-only: a Tanh net of the resident shape runs the chain kernel;
             # nothing is rebuilt from mask bits, so every activation and dZ is stored)
@@ -484,6 +501,7 @@ class GemmMLP:
                                         f"tg::mlp_fwd_chain_kernel<{H},8,true,4,{'true' if stored == L - 1 else 'false'}>"))
             self._acts = [xp] + hid if keep else None
             self._bits = [None] + bits if keep else None
+            self._acts_panel = False
             return out if padded else out[:, :self.out_dim].contiguous()
         if self.act != "ReLU":
             raise NotImplementedError(f"GemmMLP.forward(keep={keep}) of a {self.act} net: the per-layer GEMM path applies ReLU; a {self.act} net "
@@ -544,7 +562,10 @@ class GemmMLP:
         self._fresh("chain")
         L = len(self.linears)
         rows, H, dev = xp.shape[0], self._chain.H, xp.device
-        hid = [None if i in (0, L - 2) else self._ws.get(f"a{i}", rows, H, self.cd, dev) for i in range(L - 1)]
+        # (panel order: whole 32-row tiles; built for the plain head -- the reference-penalty and learned-std heads store row-major)
+        panel = bool(self.panel_order) and PANEL_ORDER_HEAD_PASS and ref is None and std is None
+        hid = [None if i in (0, L - 2) else self._ws.get(f"a{i}", _round_up(rows, 32) if panel else rows, H, self.cd, dev)
+               for i in range(L - 1)]
         bits = [self._ws.get(f"m{i}", rows, H // 32, torch.int32, dev) for i in range(L - 1)]
         dz_head = self._ws.get("z_head", rows, self.out_pad, self.cd, dev)
         nblk = lib.tg_mlp_forward_chain_blocks()
@@ -560,12 +581,15 @@ class GemmMLP:
         ptrs = (N.C.c_void_p * (L - 1))(*[N.ptr(t) or None for t in hid])
         mptrs = (N.C.c_void_p * (L - 1))(*[t.data_ptr() for t in bits])
         name, tail, targs = loss_entry("bf16", N.TG_ACT_RELU, ref, std)
+        if panel:
+            name, tail, targs = "tg_mlp_forward_chain_loss_ex", (None, None, N.TG_LAYOUT_PANEL), ",false,false,true"
         ev = None
         if self.fwd_events is not None:
             ev = N.event_pair()
             ev[0].record()
         N.check(getattr(lib, name)(xp.data_ptr(), self._chain.stream.data_ptr(), self._chain.bias.data_ptr(), H, L - 1, rows, ptrs, mptrs,
                                    N.C.byref(a), *tail, N.stream_ptr(dev)), name)
+        self._acts_panel = panel
         if ev is not None:
             ev[1].record()
             stored = sum(1 for t in hid if t is not None)
@@ -745,7 +769,8 @@ class GemmMLP:
         assert adam is None, "the optimizer step rides only on the fp32 chain learner's reduction"
         acts, bits = self._acts, self._bits
         assert acts is not None and self._dz_head is not None, "backward_fused() needs forward_loss()"
-        self._backward_chain(self._dz_head, acts, bits, acts[0].shape[0], acts[0].device)
+        self._backward_chain(self._dz_head, acts, bits, acts[0].shape[0], acts[0].device, acts_panel=getattr(self, "_acts_panel", False),
+                             dz_panel=bool(self.panel_order) and (getattr(self, "_acts_panel", False) or self.panel_mixed))
         self._dz_head = None
 
     def _dw(self, dz: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
@@ -801,16 +826,17 @@ class GemmMLP:
                                       grad.data_ptr(), grad.stride(0), grad.shape[0], grad.shape[1], N.stream_ptr(dz.device)),
                 "tg_dw_finish")
 
-    def _backward_chain(self, dz_head, acts, bits, rows, device):
+    def _backward_chain(self, dz_head, acts, bits, rows, device, acts_panel=False, dz_panel=False):
         """All hidden layers' dZ in one launch (tg_mlp_backward_chain), then every weight and hidden bias gradient in one
-        more (tg_mlp_weight_grad: each dZ and activation is read once; the bias sums ride in the same contraction)."""
+        more (tg_mlp_weight_grad: each dZ and activation is read once; the bias sums ride in the same contraction).
+        acts_panel: the stored activations are in panel order; dz_panel: the dZ are written (and read) in panel order."""
         lib = N.load()
         self._fresh("bchain")
         L = len(self.linears)
         nh = L - 1                                             # hidden layers; chain order = top (i = L-2) down to i = 0
         H = self._bchain.H
         # the top layer's dZ is neither written nor read: tg_mlp_weight_grad rebuilds it from dz_head and the mask bits (kind RH)
-        dzs = [self._ws.get(f"z{j}", rows, H, self.cd, device) if j > 0 else None for j in range(nh)]
+        dzs = [self._ws.get(f"z{j}", _round_up(rows, 32) if dz_panel else rows, H, self.cd, device) if j > 0 else None for j in range(nh)]
         dz_ptrs = (N.C.c_void_p * nh)(*[N.ptr(t) for t in dzs])
         m_ptrs = (N.C.c_void_p * nh)(*[bits[L - 1 - j].data_ptr() for j in range(nh)])     # bits[i + 1] masks hidden layer i
         # the first layer's weight (and, through the ones column of the input, bias) gradient is formed inside the backward chain
@@ -828,8 +854,13 @@ class GemmMLP:
         if self.dx_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        if fuse0:
-            n_slabs = N.C.c_int32(0)
+        n_slabs = N.C.c_int32(0)
+        if dz_panel:
+            N.check(lib.tg_mlp_backward_chain_ex(dz_head.data_ptr(), self._bchain.stream.data_ptr(), H, nh, rows, dz_ptrs, m_ptrs,
+                                                 xin.data_ptr() if fuse0 else None, N.ptr(self._w0_slabs) if fuse0 else None,
+                                                 self._w0_slabs.numel() if fuse0 else 0, N.C.byref(n_slabs), N.TG_LAYOUT_PANEL,
+                                                 N.stream_ptr(device)), "tg_mlp_backward_chain_ex")
+        elif fuse0:
             N.check(lib.tg_mlp_backward_chain_w0(dz_head.data_ptr(), self._bchain.stream.data_ptr(), H, nh, rows, dz_ptrs, m_ptrs,
                                                  xin.data_ptr(), self._w0_slabs.data_ptr(), self._w0_slabs.numel(),
                                                  N.C.byref(n_slabs), N.stream_ptr(device)), "tg_mlp_backward_chain_w0")
@@ -840,7 +871,7 @@ class GemmMLP:
             ev[1].record()
             n_stored = nh - 1 - (1 if fuse0 else 0)
             self.dx_events.append((ev[0], ev[1], rows, 16 + nh * (H // 8) + n_stored * 2 * H + (64 if fuse0 else 0),
-                                   f"tg::mlp_bwd_chain_kernel<{H},8,{'true' if fuse0 else 'false'}>"))
+                                   f"tg::mlp_bwd_chain_kernel<{H},8,{'true' if fuse0 else 'false'}{',true' if dz_panel else ''}>"))
         riders, loss_rider = getattr(self, "_riders", None) or ([], None)
         self._riders = None
         if fuse0 and rows > 0:
@@ -853,17 +884,19 @@ class GemmMLP:
         lin = self.linears
         # head (bias: tg_head_prep) -- unless forward_loss() already formed its gradient and did not store the top activation
         jobs = [(N.TG_DW_DH, dz_head, acts[L - 1], lin[L - 1].weight.grad, None)] if acts[L - 1] is not None else []
+        lp, lq = (N.DW_P_PANEL if dz_panel else 0), (N.DW_Q_PANEL if acts_panel else 0)      # layout of the [rows][H] operands
+        assert not (acts_panel and jobs), "the head job reads a row-major top activation"
         for j in range(nh - 1):
             i = L - 2 - j                                                                      # hidden-to-hidden layer i
             if j == 0:                                                                         # top layer: dZ not stored
                 assert acts[i] is not None
-                jobs.append((N.TG_DW_RH, dz_head, acts[i], lin[i].weight.grad, lin[i].bias.grad, bits[L - 1]))
+                jobs.append((N.TG_DW_RH, dz_head, acts[i], lin[i].weight.grad, lin[i].bias.grad, bits[L - 1], lq))
             elif acts[i] is None:                                                              # i == 1: input not stored
-                jobs.append((N.TG_DW_HR, dzs[j], acts[0], lin[i].weight.grad, lin[i].bias.grad))
+                jobs.append((N.TG_DW_HR, dzs[j], acts[0], lin[i].weight.grad, lin[i].bias.grad, None, lp))
             else:
-                jobs.append((N.TG_DW_HH, dzs[j], acts[i], lin[i].weight.grad, lin[i].bias.grad))
+                jobs.append((N.TG_DW_HH, dzs[j], acts[i], lin[i].weight.grad, lin[i].bias.grad, None, lp | lq))
         if not fuse0:
-            jobs.append((N.TG_DW_HX, dzs[nh - 1], acts[0], lin[0].weight.grad, lin[0].bias.grad))
+            jobs.append((N.TG_DW_HX, dzs[nh - 1], acts[0], lin[0].weight.grad, lin[0].bias.grad, None, lp))
         ev = None
         if self.dw_events is not None:
             ev = N.event_pair()
