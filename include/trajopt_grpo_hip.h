@@ -835,6 +835,24 @@ int  tg_learn_count(const uint8_t* d_mask, int64_t entries, int64_t expected_row
                     void* stream);
 int  tg_learn_compact(const tg_compact_args* args, void* stream);
 
+/* ---- GRPO's per-time-step group baseline (GRPO(baseline="step")) ----
+ * tg_grpo_step_advantage: d_rtg f32 [T][n] (tg_rtg_scan / tg_returns_moments) and d_mask u8 [T][n] (any byte pattern; non-zero =
+ *   valid) -> d_adv f32 [T][n], two launches, no floating-point atomics, deterministic.  Segment (g, t) = the group_size
+ *   consecutive entries at t*n + g*group_size; with V its valid entries and c = |V|:
+ *     s1 = sum_V (double)R, mean = s1 / c in f64, b = (float)mean, d = R - b (one rounded f32 subtraction; +0 where invalid),
+ *     q = sum_V (double)d * (double)d; a segment with c = 0 contributes nothing.
+ *   Per group, in ascending t: Q = sum q, C = sum c, K = the number of steps with c >= 1 (the fitted means);
+ *     std = sqrt(Q / (C - K)) in f64, 0 when C - K <= 0.
+ *   mode 1: d_adv = d / ((float)std + 1e-8f), both operations rounded f32 (tg_group_normalize's mode 1); mode 0: d_adv = d.
+ *   Invalid entries are +0.  No NaN / Inf from finite returns (group_size 1, singleton, empty and constant segments included).
+ *   The order of the two segment sums: quads of 4 consecutive entries; W = min(64, the smallest power of two >= the number of
+ *   quads) lanes; lane l adds the entries of quads l, l + W, ... in ascending index to a sum that starts at +0; then a
+ *   __shfl_down tree with offsets W / 2 .. 1 (lane l += lane l + off), the result in lane 0.
+ *   d_work: f64 [3][n / group_size][T] scratch (left holding {c, mean, q} per (group, step)); d_group f64 [n / group_size][3] =
+ *   {Q, C, K}.  n == 0: TG_OK, nothing is launched. */
+int  tg_grpo_step_advantage(const float* d_rtg, const uint8_t* d_mask, int64_t n, int32_t T, int64_t group_size, int mode,
+                            double* d_work, float* d_adv, double* d_group, void* stream);
+
 /* ---- Running observation normalisation (policies: normalize_obs=True) ----
  * The policy owns {count f64 [1], mean f64 [S], m2 f64 [S] = sum of squared deviations} and a derived f32 table [2][S] =
  * {(float)mean, (float)(1 / sqrt(m2 / count + eps))} (count == 0: {0, 1}).  The normalised observation, wherever a policy reads a

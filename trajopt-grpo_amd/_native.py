@@ -273,6 +273,7 @@ SIGNATURES = {
     "tg_learn_count_workspace": (C.c_int64, [_I64]),
     "tg_learn_count": (C.c_int, [_VP, _I64, _I64, _VP, _I64, _VP, _VP]),
     "tg_learn_compact": (C.c_int, [C.POINTER(CompactArgs), _VP]),
+    "tg_grpo_step_advantage": (C.c_int, [_VP, _VP, _I64, _I32, _I64, C.c_int, _VP, _VP, _VP, _VP]),
     "tg_obs_moments_workspace": (C.c_int64, [_I64, _I32]),
     "tg_obs_moments": (C.c_int, [_P(Traj), _I32, _VP, _VP, _I64, _VP, _VP]),
     "tg_obs_norm_merge": (C.c_int, [_VP, _I32, C.c_double, _VP, _VP, _VP, _VP, _VP]),

@@ -757,12 +757,31 @@ class GRPO(_GpuLearner):
     exp(d) outside 1 -+ epsilon), "log_ratio_mean" and "lr"; kl > 2 desired_kl divides the optimizer's lr by lr_factor, kl <
     desired_kl / 2 multiplies it, inside lr_bounds, applied before the next learn()'s first optimizer step (and by last_stats and
     save()) without a stall.  kl_stats=True: measure and report only.  Off: no launch, allocation, collective or entry point more,
-    and on, the updates themselves are those of a learner without the keywords, bit for bit."""
+    and on, the updates themselves are those of a learner without the keywords, bit for bit.
+
+    baseline="step" ("GRPO step baselines"): the advantage of a valid (episode, t) is its return-to-go minus the mean
+    return-to-go of the episodes of ITS group that are alive at step t -- with restart groups a Monte-Carlo estimate of the value
+    there -- in place of the reference's one mean over all of the group's (episode, t) (grpo.py:110-115, baseline="group", the
+    default).  adv_scale="std" divides the residuals by one pooled within-step std per group (+ 1e-8), "none" leaves them as they
+    are.  One entry point, tg_grpo_step_advantage (two launches), ahead of the row compaction; the groups are whole on a rank, so
+    no collective per update is added.  last_stats gains "baseline" and "baseline_explained", the share of the return-to-go's
+    within-group variance that the step means remove.  baseline="group": the launches of a learner without the keyword."""
+
+    BASELINES, ADV_SCALES = ("group", "step"), ("std", "none")
 
     def __init__(self, epsilon: float, beta: float, gamma: float, policy, optimizer, ref_model=None,
                  updates_per_iter: int = 10, *, maximize: bool = False, chunk_rows=None, autocast_dtype=None,
                  process_group=None, fused_mlp: bool = True, max_grad_norm=None, kl_stats: bool = False, desired_kl=None,
-                 lr_bounds=(1e-5, 1e-2), lr_factor: float = 1.5):
+                 lr_bounds=(1e-5, 1e-2), lr_factor: float = 1.5, baseline: str = "group", adv_scale: str = "std"):
+        if baseline not in self.BASELINES:
+            raise ValueError(f"baseline must be one of {self.BASELINES}, got {baseline!r}")
+        if adv_scale not in self.ADV_SCALES:
+            raise ValueError(f"adv_scale must be one of {self.ADV_SCALES}, got {adv_scale!r}")
+        if baseline == "group" and adv_scale != "std":
+            raise ValueError(f"baseline='group' divides by the group's std (adv_scale='std'), got adv_scale={adv_scale!r}: "
+                             "adv_scale chooses the divisor of baseline='step'")
+        self.baseline, self.adv_scale = baseline, adv_scale
+        self._baseline_sums = None
         self.epsilon, self.beta, self.gamma = epsilon, beta, gamma
         self.ref_model = _check_ref_model(ref_model, policy)
         self.updates_per_iter = updates_per_iter
@@ -791,6 +810,23 @@ class GRPO(_GpuLearner):
             return X
         return m.prepare_input(X, out=self._ws.get("xin_ref", X.shape[0], m.in_pad, m.cd, X.device, cap))
 
+    def _advantage_source(self, traj, rtg, moments):
+        """(src0, moments or None, norm_mode) of the row compaction: the [T][n] array the valid rows' advantages are gathered from,
+        and the group moments it is normalised with on the way (None: gathered as it is).  "group": the returns-to-go and their
+        moments, grpo.py:110-115.  "step": tg_grpo_step_advantage's array, which is the advantage already; the two sums of
+        baseline_explained (sum_g Q_g and sum_g (s2 - s1^2 / cnt), the within-group squared deviations after and before the step
+        means) stay on the device for last_stats."""
+        if self.baseline == "group":
+            return rtg, moments, 0
+        dev, G = rtg.device, traj.n // traj.E
+        adv, group = K.grpo_step_advantage(rtg, traj.mask, traj.E, scale=self.adv_scale == "std",
+                                           out=self._ws.get("step_adv", traj.T * traj.n, 1, torch.float32, dev, traj.T * traj.n).view(traj.T, traj.n),
+                                           work=self._small("step_work", max(3 * G * traj.T, 1), torch.float64, dev),
+                                           group=self._small("step_group", 3 * G, torch.float64, dev).view(G, 3))
+        cnt, s1, s2 = moments.unbind(1)
+        self._baseline_sums = torch.stack((group[:, 0].sum(), (s2 - s1 * (s1 / cnt.clamp_min(1.0))).sum()))
+        return adv, None, 0
+
     def _learn(self, buffer) -> None:
         traj = device_trajectory(buffer, self.policy.device)
         var = self.policy.var
@@ -805,7 +841,8 @@ class GRPO(_GpuLearner):
         # the valid rows: index, padded input row, action and group-relative advantage (grpo.py:76-115) in one pass over the mask --
         # enqueued here; the host asks for the row count (and waits for the rollout's statistic) only after everything that does not
         # depend on it has been enqueued too
-        handle = self._prepare_enqueue(traj, m_actor, src0=rtg, moments=moments, norm_mode=0, group_size=traj.E)
+        src0, src_moments, norm_mode = self._advantage_source(traj, rtg, moments)
+        handle = self._prepare_enqueue(traj, m_actor, src0=src0, moments=src_moments, norm_mode=norm_mode, group_size=traj.E)
         _, world = D.rank_world(self.process_group)
         G_global = traj.G * world
         coef = (-1.0 if self.maximize else 1.0) / G_global                  # J /= group_size, descent on J
@@ -833,7 +870,7 @@ class GRPO(_GpuLearner):
         if prepared is not None:
             idx, xin, act, adv, _ = prepared
         else:
-            adv_full = K.group_normalize(rtg, traj.mask, moments, 0, traj.E)
+            adv_full = src0 if src_moments is None else K.group_normalize(src0, traj.mask, src_moments, norm_mode, traj.E)
             idx, X, act = self._gather_valid(traj)
             adv = adv_full.reshape(-1).index_select(0, idx)
             xin = self._prep(actor, X, traj.T * traj.n)
@@ -899,6 +936,15 @@ class GRPO(_GpuLearner):
                 beta = float(self.beta)
                 self._stats_pending = lambda: {"J": ((allJ[:, 0] - beta * allJ[:, 2]) / G_global).tolist(), "n_valid": allJ[0, 3].item(),
                                                "kl_ref": (allJ[:, 2] / allJ[:, 3].clamp_min(1.0)).tolist(), **extra()}
+        if self.baseline != "group":
+            sums, self._baseline_sums = self._baseline_sums, None
+            D.allreduce_sum_(sums, self.process_group, "baseline_explained")   # (the one collective of the feature: two f64 per learn())
+            inner, name = self._stats_pending or dict, self.baseline
+
+            def with_baseline():
+                q, dev2 = sums.tolist()
+                return {**inner(), "baseline": name, "baseline_explained": 1.0 - q / dev2 if dev2 > 0 else float("nan")}
+            self._stats_pending = with_baseline
 
     def save(self, path: str) -> None:
         self._kl_sync()                                                     # (the checkpoint holds the adapted lr)
@@ -909,7 +955,8 @@ class GRPO(_GpuLearner):
 
     def metadata(self):
         return {"algorithm": "GRPO", "epsilon": self.epsilon, "beta": self.beta,
-                "updates_per_iter": self.updates_per_iter, **self._clip_metadata(), **self._kl_metadata()}
+                "updates_per_iter": self.updates_per_iter, **self._clip_metadata(), **self._kl_metadata(),
+                **({} if self.baseline == "group" else {"baseline": self.baseline, "adv_scale": self.adv_scale})}
 
 
 def _value_norm_stats(stat3, moments, eps) -> dict:

@@ -66,6 +66,29 @@ def group_normalize(x, mask, moments, mode: int, group_size: int) -> torch.Tenso
     return out
 
 
+def grpo_step_advantage(rtg: torch.Tensor, mask: torch.Tensor, group_size: int, scale: bool = True, out=None, work=None, group=None):
+    """tg_grpo_step_advantage: (adv f32 [T][n], group f64 [n / group_size][3] = {Q, C, K}) -- every valid return-to-go minus the mean of
+    its group's valid entries at its time step; scale: divided by the group's pooled within-step std + 1e-8.  Invalid entries +0.
+    out / work (f64, 3 * (n / group_size) * T) / group: reused buffers."""
+    N.require_cuda(rtg, mask, out, work, group)
+    assert rtg.dtype == torch.float32 and mask.dtype == torch.uint8 and rtg.is_contiguous() and mask.is_contiguous() and rtg.shape == mask.shape
+    T, n = rtg.shape
+    G = n // int(group_size) if group_size >= 1 else 0
+    if out is None:
+        out = torch.empty_like(rtg)
+    if work is None:
+        work = torch.empty(max(3 * G * T, 1), dtype=torch.float64, device=rtg.device)
+    if group is None:
+        group = torch.empty(G, 3, dtype=torch.float64, device=rtg.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == rtg.shape and out.data_ptr() != rtg.data_ptr()
+    assert work.dtype == group.dtype == torch.float64 and work.numel() >= 3 * G * T and group.is_contiguous() and group.numel() == 3 * G
+    if n == 0:                                                             # (an empty tensor has no address to pass)
+        return out, group
+    N.check(N.load().tg_grpo_step_advantage(rtg.data_ptr(), mask.data_ptr(), n, T, int(group_size), 1 if scale else 0, work.data_ptr(),
+                                            out.data_ptr(), group.data_ptr(), _st(rtg)), "tg_grpo_step_advantage")
+    return out, group
+
+
 def returns_moments(rew: torch.Tensor, mask: torch.Tensor, gamma: float, group_size: int):
     """(rtg, moments) = (rtg_scan(rew, mask, gamma), masked_moments(rtg, mask, group_size)), bit-identical, in two launches built for
     rollouts of a few thousand envs (tg_returns_moments: LDS-staged strips, one lane per env on the recurrence)."""

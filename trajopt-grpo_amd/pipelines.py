@@ -200,13 +200,13 @@ def _assemble(test_name, checkpoint_name, env_fn, policy, algorithm, rollout_man
 
 def create_cartpole_pipeline_grpo(test_name, checkpoint_name, env_fn=None, policy=None, algorithm=None,
                                   rollout_manager=None, buffer=None, visualizer=None, publisher=None, logger=None,
-                                  load_path=None) -> Pipeline:
-    """pipelines/cartpole_pipeline_grpo.py:21-105 defaults."""
+                                  load_path=None, *, baseline="group", adv_scale="std") -> Pipeline:
+    """pipelines/cartpole_pipeline_grpo.py:21-105 defaults.  baseline / adv_scale: GRPO's ("GRPO step baselines")."""
     env_fn = env_fn or (lambda: CartPole())
     policy = policy or GaussianActor_NeuralNetwork(input_dim=5, output_dim=1, hidden_dims=(128, 128, 128, 128), cov=0.5)
     algorithm = algorithm or GRPO(epsilon=0.15, beta=0.5, gamma=0.5, policy=policy,
                                   optimizer=torch.optim.Adam(policy.parameters(), lr=3e-4), ref_model=None,
-                                  updates_per_iter=1)
+                                  updates_per_iter=1, baseline=baseline, adv_scale=adv_scale)
     rollout_manager = rollout_manager or RolloutManager(env_fn=env_fn, worker_class=RolloutWorker, policy=policy,
                                                         num_workers=10, num_episodes_per_worker=10, restart=False)
     return _assemble(test_name, checkpoint_name, env_fn, policy, algorithm, rollout_manager, buffer, visualizer,
