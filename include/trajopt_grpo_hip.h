@@ -160,7 +160,8 @@ int  tg_rollout_forced(const tg_env_params* p, const tg_traj* tr, int32_t t_begi
 int  tg_rollout_final_state(const tg_env_params* p, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout, void* stream);
 
 /* counters[0] = sum of episode lengths (= env-steps executed = sum of mask),
- * counters[1] = episodes ended.  rollout/rollout_worker.py:67-68 */
+ * counters[1] = episodes ended.  rollout/rollout_worker.py:67-68.  A slot with len <= 0 has not ended (Pendulum keeps minus its
+ * balanced-step count there while an episode runs): it counts as 0 steps and no episode, the rule of tg_rollout_finish_stats. */
 int  tg_rollout_finish(const tg_traj* tr, void* stream);
 
 /* tg_rollout_finish + tg_rng_advance (d_rng may be NULL) + the statistics Rollout_Buffer.sample() reads

@@ -311,14 +311,15 @@ __global__ __launch_bounds__(256) void final_state_kernel(typename Env::C c_arg,
     timeout[i] = (ended && !Env::failed(o, c) && (Env::time_rule(L, c) || L == T)) ? 1 : 0;
 }
 
-// sum of episode lengths (= env-steps executed = sum of mask) and #episodes ended
+// sum of episode lengths (= env-steps executed = sum of mask) and #episodes ended.  A non-positive len is a slot whose episode has
+// not ended (Pendulum keeps minus its balanced-step count there while it runs): it adds nothing, finish_stats_kernel's rule.
 __global__ __launch_bounds__(256) void rollout_finish_kernel(const int32_t* __restrict__ len, int64_t n,
                                                              uint64_t* __restrict__ counters) {
     __shared__ unsigned long long s_sum[4], s_done[4];
     unsigned long long sum = 0, done = 0;
     for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
         const int32_t l = len[i];
-        sum += (unsigned long long)l;
+        sum += (unsigned long long)(l > 0 ? l : 0);
         done += (l > 0);
     }
 #pragma unroll

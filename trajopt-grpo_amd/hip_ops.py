@@ -206,7 +206,8 @@ def scatter_rows(src: torch.Tensor, idx: torch.Tensor, dst: torch.Tensor, table:
     assert src.dim() == 2 and src.shape[0] >= rows
     assert table is None or (table.dtype == torch.float32 and table.is_contiguous() and table.numel() == 4 and table.device == dst.device)
     name, tab = suffixed("tg_scatter_rows", "_affine", None if table is None else (table.data_ptr(),))
-    N.check(getattr(N.load(), name)(src.data_ptr(), src.stride(0), idx.data_ptr(), rows, *tab, dst.data_ptr(), _st(dst)), name)
+    # (max: an empty src may carry a row stride of 0, which the entry points refuse before they see rows == 0)
+    N.check(getattr(N.load(), name)(src.data_ptr(), max(src.stride(0), 1), idx.data_ptr(), rows, *tab, dst.data_ptr(), _st(dst)), name)
 
 
 def boot_values_affine(v: torch.Tensor, timeout: torch.Tensor, table: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
