@@ -326,17 +326,20 @@ int  tg_surrogate_loss(const tg_loss_args* a, void* stream);
 /* ---- MLP backward glue (models/neural_network.py:67-77 under torch autograd in the reference) ----
  * dZ = dA * (A > 0) in place (A = post-ReLU activations) fused with the bias-gradient column sums:
  * d_partial f32 [tg_relu_bwd_bias_blocks()][cols]; the caller sums it over axis 0.
- * Row-major [rows][cols]; bf16 needs cols % 8 == 0, f32 cols % 4 == 0. */
+ * Row-major [rows][cols]; bf16 needs cols % 8 == 0, f32 cols % 4 == 0; cols <= tg_relu_bwd_bias_max_cols(is_bf16)
+ * (one workgroup of 256 threads x 16 bytes holds a row: 2048 in bf16, 1024 in f32). */
 int  tg_relu_bwd_bias_blocks(void);
+int  tg_relu_bwd_bias_max_cols(int32_t is_bf16);
 int  tg_relu_bwd_bias(void* d_dA, const void* d_A, int64_t rows, int32_t cols, int32_t is_bf16,
                       float* d_partial, void* stream);
 
 /* The head's backward-data product fused into the top hidden layer's ReLU backward:
  *   dZ[r][c] = (sum_{k<act_dim} dout[r][k] * Whead[k][c]) * (A[r][c] > 0),  d_partial as tg_relu_bwd_bias.
  * d_dout f32 [rows][act_dim] (contiguous), d_whead f32 [act_dim][cols] (the head's master weights),
- * d_act / d_dz [rows][cols] bf16 (is_bf16) or f32; cols % 8 == 0.
+ * d_act / d_dz [rows][cols] bf16 (is_bf16) or f32; cols % 8 == 0, cols <= tg_head_bwd_relu_bias_max_cols() (2048, both dtypes).
  * d_maskbits (optional, bf16, cols 128 / 256): the layer's ReLU mask bits from tg_mlp_forward_chain (cols / 8 bytes
  * per row) are read instead of d_act (which may then be NULL): 4 B instead of 16 B per thread. */
+int  tg_head_bwd_relu_bias_max_cols(void);
 int  tg_head_bwd_relu_bias(const float* d_dout, int32_t act_dim, const float* d_whead, const void* d_act,
                            const void* d_maskbits, void* d_dz, int64_t rows, int32_t cols, int32_t is_bf16,
                            float* d_partial, void* stream);

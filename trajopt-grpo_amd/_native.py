@@ -194,6 +194,8 @@ SIGNATURES = {
     "tg_policy_shift_finish": (C.c_int, [_VP, _I32, _VP, _VP]),
     "tg_lr_adapt": (C.c_int, [_VP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _VP, _VP]),
     "tg_relu_bwd_bias_blocks": (C.c_int, []),
+    "tg_relu_bwd_bias_max_cols": (C.c_int, [_I32]),
+    "tg_head_bwd_relu_bias_max_cols": (C.c_int, []),
     "tg_relu_bwd_bias": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "tg_head_bwd_relu_bias": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "tg_dx_relu_bias_supported": (C.c_int, [_I32, _I32]),

@@ -346,8 +346,11 @@ class _GpuLearner(Algorithm):
     def _mlp(self, net):
         key = id(net)
         if key not in self._mlps:
-            ok = ((self.fused_mlp and M.supports(net)) or self._tanh_native(net)) and next(net.parameters()).is_cuda
-            self._mlps[key] = M.GemmMLP(net, self.autocast_dtype or torch.float32) if ok else None
+            cd = self.autocast_dtype or torch.float32
+            ok = ((self.fused_mlp and M.supports(net, cd)) or self._tanh_native(net)) and next(net.parameters()).is_cuda
+            self._mlps[key] = M.GemmMLP(net, cd) if ok else None
+            if not ok and self.fused_mlp:
+                M.log_too_wide(net, cd)
             if self._mlps[key] is not None:
                 self._mlps[key]._ws.default_cap = self._ws.default_cap
         return self._mlps[key]

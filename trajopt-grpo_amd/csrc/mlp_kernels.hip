@@ -5,6 +5,10 @@
 namespace tg {
 
 constexpr int kReluBlocks = 2048;
+// One workgroup holds a whole row: 256 threads x 16 bytes (8 bf16 / 4 f32; the head kernel: 8 columns in either dtype).  The widest
+// rows the launches below accept -- mlp.supports() reads them through tg_*_max_cols() and keeps wider nets on torch autograd.
+constexpr int kRowThreads = 256;
+constexpr int kReluPerBf16 = 8, kReluPerF32 = 4, kHeadPer = 8;
 
 __device__ static inline float bf16_to_f32(uint16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 
@@ -289,12 +293,16 @@ extern "C" {
 
 int tg_relu_bwd_bias_blocks(void) { return kReluBlocks; }
 
+int tg_relu_bwd_bias_max_cols(int32_t is_bf16) { return kRowThreads * (is_bf16 ? kReluPerBf16 : kReluPerF32); }
+
+int tg_head_bwd_relu_bias_max_cols(void) { return kRowThreads * kHeadPer; }
+
 int tg_relu_bwd_bias(void* d_dA, const void* d_A, int64_t rows, int32_t cols, int32_t is_bf16, float* d_partial,
                      void* stream) {
     TG_REQUIRE(d_dA && d_A && d_partial, "tg_relu_bwd_bias: null pointer");
-    const int per = is_bf16 ? 8 : 4;
-    TG_REQUIRE(rows >= 0 && cols > 0 && cols % per == 0 && cols / per <= 256,
-               "tg_relu_bwd_bias: cols=%d must be a multiple of %d and <= %d", cols, per, 256 * per);
+    const int per = is_bf16 ? kReluPerBf16 : kReluPerF32;
+    TG_REQUIRE(rows >= 0 && cols > 0 && cols % per == 0 && cols <= tg_relu_bwd_bias_max_cols(is_bf16),
+               "tg_relu_bwd_bias: cols=%d must be a multiple of %d and <= %d", cols, per, tg_relu_bwd_bias_max_cols(is_bf16));
     const int tpr = cols / per, rpp = 256 / tpr;
     const size_t shmem = (size_t)rpp * cols * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
@@ -315,8 +323,8 @@ int tg_head_bwd_relu_bias(const float* d_dout, int32_t act_dim, const float* d_w
     TG_REQUIRE(!d_maskbits || (is_bf16 && (cols == 128 || cols == 256)),
                "tg_head_bwd_relu_bias: mask bits need bf16 and 128 or 256 columns (tg_mlp_forward_chain writes them)");
     TG_REQUIRE(act_dim >= 1 && act_dim <= 8, "tg_head_bwd_relu_bias: act_dim %d outside 1..8", act_dim);
-    TG_REQUIRE(rows >= 0 && cols > 0 && cols % 8 == 0 && cols / 8 <= 256, "tg_head_bwd_relu_bias: cols=%d must be a multiple of 8 and <= 2048",
-               cols);
+    TG_REQUIRE(rows >= 0 && cols > 0 && cols % kHeadPer == 0 && cols <= tg_head_bwd_relu_bias_max_cols(),
+               "tg_head_bwd_relu_bias: cols=%d must be a multiple of %d and <= %d", cols, kHeadPer, tg_head_bwd_relu_bias_max_cols());
     const int tpr = cols / 8, rpp = 256 / tpr;
     const size_t shmem = (size_t)rpp * cols * sizeof(float);
     hipStream_t st = (hipStream_t)stream;

@@ -160,7 +160,18 @@ def weight_grad_workspace(hidden: int, device) -> torch.Tensor:
     return torch.empty(N.load().tg_mlp_weight_grad_workspace(hidden) // 4, dtype=torch.float32, device=device)
 
 
-def supports(net) -> bool:
+def per_layer_width_limits(compute_dtype, out_dim: int):
+    """(widest hidden layer below the top one, widest top hidden layer) the per-layer backward can run in `compute_dtype`: the
+    limits of tg_relu_bwd_bias (2048 columns in bf16, 1024 in fp32) and, for the top hidden layer of a net with <= 8 outputs, of
+    tg_head_bwd_relu_bias (2048 in either dtype) -- asked of the library, which checks the same numbers at every launch."""
+    lib = N.load()
+    relu = lib.tg_relu_bwd_bias_max_cols(1 if compute_dtype == torch.bfloat16 else 0)
+    return relu, (lib.tg_head_bwd_relu_bias_max_cols() if out_dim <= 8 else relu)
+
+
+def supports(net, compute_dtype=torch.float32) -> bool:
+    """`net` is Linear [ReLU Linear]+ with hidden widths that are multiples of 8 and within per_layer_width_limits(): every such net
+    can run GemmMLP's per-layer path (the chain kernels take subsets of them).  A wider net stays on torch autograd."""
     mods = list(net.network)
     if len(mods) < 3 or len(mods) % 2 == 0:
         return False
@@ -169,7 +180,27 @@ def supports(net) -> bool:
             return False
         if i % 2 == 1 and not isinstance(m, torch.nn.ReLU):
             return False
-    return all(l.out_features % 8 == 0 for l in mods[0:-1:2])
+    widths = [l.out_features for l in mods[0:-1:2]]
+    if any(w % 8 != 0 for w in widths):
+        return False
+    below, top = per_layer_width_limits(compute_dtype, mods[-1].out_features)
+    return widths[-1] <= top and all(w <= below for w in widths[:-1])
+
+
+def log_too_wide(net, compute_dtype) -> None:
+    """One INFO line (logger `trajopt_grpo_amd`) for a ReLU net that supports() turns away for its width alone."""
+    if hidden_activation(net) != "ReLU":
+        return
+    lin = _linears(net)
+    widths = [l.out_features for l in lin[:-1]]
+    if any(w % 8 != 0 for w in widths) or supports(net, compute_dtype):
+        return
+    below, top = per_layer_width_limits(compute_dtype, lin[-1].out_features)
+    shape = f"{lin[0].in_features}-" + "-".join(str(w) for w in widths) + f"-{lin[-1].out_features} {str(compute_dtype).replace('torch.', '')}"
+    if (shape, "width") not in _LOGGED_SHAPES:
+        _LOGGED_SHAPES.add((shape, "width"))
+        _LOG.info("%s: a hidden layer is wider than the per-layer backward kernels take (%d, the top hidden layer %d) -- its update "
+                  "runs on torch autograd", shape, below, top)
 
 
 # hidden activations of the fp32 kernels' `_act` entry points (include/trajopt_grpo_hip.h TG_ACT_*)
@@ -253,7 +284,7 @@ class GemmMLP:
                 raise ValueError("GemmMLP runs a Tanh net only in float32 on the fp32 chain learner (Linear(S<=32, H) Tanh "
                                  "[Linear(H, H) Tanh]{0..3} Linear(H, A<=4), H in {64, 128})")
         else:
-            assert supports(net)
+            assert supports(net, compute_dtype)
         self.net = net
         self.cd = compute_dtype
         self.linears = [m for m in net.network if isinstance(m, torch.nn.Linear)]

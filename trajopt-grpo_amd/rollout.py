@@ -144,7 +144,7 @@ class DeviceRollout:
         self._linears = [m for m in policy.actor.network if isinstance(m, torch.nn.Linear)]
         self._lowp = None
         self._mlp = None
-        if M.supports(policy.actor):
+        if M.supports(policy.actor, compute_dtype or torch.float32):
             # hand-scheduled GEMM chain (bias+ReLU in the GEMM epilogue, padded K / head): mlp.py
             self._mlp = M.GemmMLP(policy.actor, compute_dtype or torch.float32)
             self._xp = torch.zeros(self.n, self._mlp.in_pad, dtype=self._mlp.cd, device=self.device)
