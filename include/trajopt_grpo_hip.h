@@ -521,6 +521,16 @@ int  tg_policy_shift(const float* d_mean, int64_t mean_row_stride, const float* 
 int  tg_policy_shift_finish(const double* d_partials, int32_t n_partials, double* d_sums, void* stream);
 int  tg_lr_adapt(const double* d_sums, double desired_kl, double factor, double lr_min, double lr_max, double lr, double* d_out4,
                  void* stream);
+/* tg_kl_control (one thread, float64): a check BETWEEN the optimizer steps of a learn() acts on a device control block
+ *   d_ctl f64 [8] = {stopped, lr, stop_update, kl_at_stop, last_kl, last_clip_fraction, checks, 0}
+ * which the `_ctl` optimizer launches read (tg_adam_step_ctl).  The caller initialises it to {0, lr, 0, 0, nan, nan, 0, 0}.  In order:
+ *   1. d_ctl[0] != 0 (latched): the block is left as it is, byte for byte;
+ *   2. kl and clip_fraction as tg_lr_adapt forms them, into slots 4 and 5; slot 6 += 1;
+ *   3. desired_kl > 0: tg_lr_adapt's rule on d_ctl[1] (the check that latches applies it too);
+ *   4. target_kl > 0 && rows > 0 && kl > stop_factor * target_kl (strict): d_ctl[0] = 1, d_ctl[2] = update, d_ctl[3] = kl.
+ * update: the 1-based count of optimizer steps applied so far.  A NaN kl or rows == 0 neither adapts nor stops. */
+int  tg_kl_control(const double* d_sums, double target_kl, double stop_factor, double desired_kl, double factor, double lr_min,
+                   double lr_max, int64_t update, double* d_ctl, void* stream);
 
 /* ---- MLP backward-data pass, all hidden layers in one persistent launch ----
  * For Linear(in, H) ReLU [Linear(H, H) ReLU]^(n_hidden_layers-1) Linear(H, out <= 8), H in {128, 256}, 3..6 hidden
@@ -783,6 +793,26 @@ int  tg_adam_step_clip(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t
 int  tg_adam_step_push_clip(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2,
                             double eps, int64_t step, int32_t zero_grads, const tg_gather_segment* d_segments, int32_t n_segments,
                             const int32_t* d_inv_start, const int32_t* d_inv_dst, const float* d_coef, void* stream);
+/* The four launches above behind tg_kl_control's device control block d_ctl (f64 [8], 8-byte aligned; see tg_kl_control): separate
+ * kernels, the same update.  Every thread reads d_ctl[0]; nonzero (a check has latched target_kl's stop): no parameter, moment or
+ * derived layout is written, the gradient element is zeroed if zero_grads != 0 and left as it is otherwise (a clip product is not
+ * written back).  lr_from_ctl == 1: the step size is (float)((d_ctl[1] / bc1) * -1.0), formed in double on the device, where
+ * bc1 = 1 - beta1^step comes from the host by value -- the division tg_adam_step does on the host, so a block that holds `lr` gives
+ * tg_adam_step's bits; `lr` itself is then not read.  lr_from_ctl == 0: `lr` by value, as in the plain launch (param groups with
+ * rates of their own).  bc1 must lie in (0, 1]. */
+int  tg_adam_step_ctl(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2, double eps,
+                      int64_t step, int32_t zero_grads, const double* d_ctl, int32_t lr_from_ctl, double bc1, void* stream);
+int  tg_adam_step_push_ctl(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2,
+                           double eps, int64_t step, int32_t zero_grads, const tg_gather_segment* d_segments, int32_t n_segments,
+                           const int32_t* d_inv_start, const int32_t* d_inv_dst, const double* d_ctl, int32_t lr_from_ctl, double bc1,
+                           void* stream);
+int  tg_adam_step_ctl_clip(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2,
+                           double eps, int64_t step, int32_t zero_grads, const float* d_coef, const double* d_ctl, int32_t lr_from_ctl,
+                           double bc1, void* stream);
+int  tg_adam_step_push_ctl_clip(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2,
+                                double eps, int64_t step, int32_t zero_grads, const tg_gather_segment* d_segments, int32_t n_segments,
+                                const int32_t* d_inv_start, const int32_t* d_inv_dst, const float* d_coef, const double* d_ctl,
+                                int32_t lr_from_ctl, double bc1, void* stream);
 /* tg_mlp_f32_weight_grad with the optimizer step RIDING on its reduction launch: the thread that completes a gradient element applies
  * tg_adam_step's update to its parameter and (push tables given) tg_adam_step_push's layout writes, then leaves the gradient zeroed
  * (zero_grads) or holding the accumulated value -- what `loss.backward(); optimizer.step()` (algorithms/grpo.py:144-145) leaves, bit

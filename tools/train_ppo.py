@@ -5,9 +5,14 @@ epoch instead of 50-80.
     python3 tools/train_ppo.py [epochs] [CartPole|Pendulum|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
                                [--learn-std] [--normalize-obs] [--normalize-value] [--gae] [--privileged-critic]
                                [--eval-every N] [--eval-episodes E] [--eval-sweep name=f1,f2,... ...] [--desired-kl KL]
+                               [--target-kl KL] [--kl-every N]
 
 --desired-kl KL: the KL-adaptive learning rate (PPO(desired_kl=KL), e.g. 0.01): once per learn() the rate is divided by 1.5 when the
 measured KL between the policy before and after the updates exceeds 2 KL and multiplied by 1.5 when it is below KL / 2.
+
+--target-kl KL: early stopping of a learn()'s updates (PPO(target_kl=KL), e.g. 0.02): after every --kl-every N-th update (default 1) the
+KL is measured on the device, and once it exceeds 1.5 KL the remaining updates of that learn() change nothing.  --kl-every with
+--desired-kl makes the rate follow the rule at every such check instead of once per learn().
 
 --eval-every N: every N epochs a deterministic evaluation (trajopt_grpo_amd.Evaluator: mean actions, its own seed and RNG stream) of
 --eval-episodes E episodes per cell (default 256) is printed beside the sampled training return.  --eval-sweep (repeatable): the
@@ -103,6 +108,13 @@ def main():
         desired_kl = float(desired_kl[-1]) if desired_kl else None    # the KL-adaptive learning rate (PPO(desired_kl=...))
     except ValueError:
         raise SystemExit("--desired-kl expects a number")
+    target_kl, sys.argv[1:] = pop_valued(sys.argv[1:], "--target-kl")
+    kl_every, sys.argv[1:] = pop_valued(sys.argv[1:], "--kl-every")
+    try:
+        target_kl = float(target_kl[-1]) if target_kl else None       # early stopping (PPO(target_kl=...))
+        kl_every = int(kl_every[-1]) if kl_every else None            # a check behind every kl_every-th update
+    except ValueError:
+        raise SystemExit("--target-kl expects a number, --kl-every an integer")
     learn_std = "--learn-std" in sys.argv                         # a learned per-dimension log-std instead of the fixed covariance
     sys.argv = [a for a in sys.argv if a != "--learn-std"]
     normalize_obs = "--normalize-obs" in sys.argv                 # running observation normalisation (policy.obs_norm)
@@ -136,7 +148,8 @@ def main():
     buf = tg.Rollout_Buffer(mgr)
     algo = tg.PPO(epsilon=0.2, policy=pol, optimizer=torch.optim.Adam(pol.parameters(), lr=lr), ref_model=None,
                   updates_per_iter=upd, c1=0.5, kl_coeff=0.5, gamma=gamma, lam=0.95, entropy=0.01, batch_size=None,
-                  autocast_dtype=cdt, **({"monte_carlo": False} if gae else {}), desired_kl=desired_kl)
+                  autocast_dtype=cdt, **({"monte_carlo": False} if gae else {}), desired_kl=desired_kl,
+                  **({"target_kl": target_kl} if target_kl is not None else {}), **({"kl_every": kl_every} if kl_every is not None else {}))
     evaluator = None
     if eval_every is not None:                                    # (refuses a bad sweep before the first epoch)
         evaluator = tg.Evaluator(tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, episodes=eval_episodes, sweep=eval_sweep,
@@ -161,6 +174,7 @@ def main():
                   + (f"  obs_count {algo.last_stats['obs_count']:.0f}" if normalize_obs else "")
                   + (f"  kl {algo.last_stats['approx_kl']:.4f} clip {algo.last_stats['clip_fraction']:.3f} lr {algo.last_stats['lr']:.2e}"
                      if desired_kl is not None else "")
+                  + (f"  updates {algo.last_stats['n_updates']}/{upd}" if target_kl is not None else "")
                   + (f"  value mean {algo.last_stats['value_mean']:.2f} std {algo.last_stats['value_std']:.2f}"
                      f" ev {algo.last_stats['explained_variance']:.3f}" if normalize_value else ""), flush=True)
     print("first -> last:", float(buf.avg_reward[0]), "->", float(buf.avg_reward[-1]), " max", float(max(buf.avg_reward)))

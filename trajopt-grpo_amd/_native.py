@@ -270,6 +270,14 @@ SIGNATURES = {
     "tg_adam_step_clip": (C.c_int, [_VP, _I32, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I32, _VP, _VP]),
     "tg_adam_step_push_clip": (C.c_int, [_VP, _I32, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I32, _VP, _I32, _VP, _VP, _VP,
                                          _VP]),
+    "tg_kl_control": (C.c_int, [_VP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _VP, _VP]),
+    "tg_adam_step_ctl": (C.c_int, [_VP, _I32, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I32, _VP, _I32, C.c_double, _VP]),
+    "tg_adam_step_push_ctl": (C.c_int, [_VP, _I32, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I32, _VP, _I32, _VP, _VP, _VP,
+                                        _I32, C.c_double, _VP]),
+    "tg_adam_step_ctl_clip": (C.c_int, [_VP, _I32, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I32, _VP, _VP, _I32, C.c_double,
+                                        _VP]),
+    "tg_adam_step_push_ctl_clip": (C.c_int, [_VP, _I32, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I32, _VP, _I32, _VP, _VP,
+                                             _VP, _VP, _I32, C.c_double, _VP]),
     "tg_returns_moments_max_horizon": (C.c_int, []),
     "tg_returns_moments": (C.c_int, [_VP, _VP, _F, _VP, _I64, _I32, _I64, _VP, _VP, _VP]),
     "tg_learn_count_workspace": (C.c_int64, [_I64]),

@@ -110,9 +110,9 @@ class _GpuLearner(Algorithm):
     _fold_pending = _differ_table = _count_pending = _count_pinned = None
 
     def _setup(self, policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp=True, max_grad_norm=None,
-               kl_stats=False, desired_kl=None, lr_bounds=(1e-5, 1e-2), lr_factor=1.5):
+               kl_stats=False, desired_kl=None, lr_bounds=(1e-5, 1e-2), lr_factor=1.5, target_kl=None, kl_stop_factor=1.5, kl_every=None):
         self.policy, self.optimizer = policy, optimizer
-        self._kl_setup(kl_stats, desired_kl, lr_bounds, lr_factor)
+        self._kl_setup(kl_stats, desired_kl, lr_bounds, lr_factor, target_kl, kl_stop_factor, kl_every)
         if max_grad_norm is not None:
             if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
                 raise ValueError(f"max_grad_norm must be None or a finite number > 0, got {max_grad_norm!r}")
@@ -157,6 +157,7 @@ class _GpuLearner(Algorithm):
             self._rollout_engine = getattr(getattr(buffer, "rollout_manager", None), "engine", None) if ok else None
             self._check_deferred()
             self._kl_entry_check()
+            self._kl_run = None
             self._clip_log, self._std_log = _StepLog(2), _StepLog()
             obs_count = self._obs_norm_update(buffer)
             self._learn(buffer)
@@ -169,6 +170,14 @@ class _GpuLearner(Algorithm):
             if self._clip_log.steps and self._stats_pending is not None:
                 inner, clip_log = self._stats_pending, self._clip_log
                 self._stats_pending = lambda: {**inner(), "grad_norm": clip_log.rows()[:, 0].tolist()}
+            if self._kl_ctl and self._stats_pending is not None:
+                inner_all, keys = self._stats_pending, self._KL_LIST_KEYS
+
+                def cut():                  # the per-step lists end with the last step that was applied
+                    st = inner_all()
+                    n = st.get("n_updates")
+                    return st if n is None else {k: v[:n] if (k in keys and isinstance(v, list)) else v for k, v in st.items()}
+                self._stats_pending = cut
 
     def _obs_norm_update(self, buffer):
         """normalize_obs: the policy's running statistics take in this rollout's valid observations (one all-reduce across the ranks)
@@ -403,12 +412,23 @@ class _GpuLearner(Algorithm):
         in_step = coef is not None and bool(self._fused_adam) and self._adam_covers_bucket
         if coef is not None and not in_step:
             self.bucket.flat.mul_(coef)
+        # target_kl / kl_every: the fused step reads the control block on the device (a latched block: the launch changes nothing)
+        run = self._kl_run
         stepped = bool(self._fused_adam) and self._fused_adam.step(zero_grads=not last and self._adam_covers_bucket, refresher=refresher,
-                                                                   clip_coef=coef if in_step else None)
+                                                                   clip_coef=coef if in_step else None,
+                                                                   ctl=None if run is None else (run["ctl"], self._kl_adapt_checks))
         if not stepped:
             if in_step:                     # (refused before any launch: nothing has been scaled yet)
                 self.bucket.flat.mul_(coef)
+            if run is not None:
+                # the waiting path: torch's own step cannot read the block, so the host reads the newest check first -- and does
+                # not step behind a latch (the lr of that check is in the param groups by now)
+                run["fused"] = False
+                if run["checks"] and self._kl_read(len(run["checks"]) - 1):
+                    return
             self.optimizer.step()
+        if run is not None:
+            run["enqueued"] += 1
         self._refresh(*nets)
         if stepped and not self._fused_adam.pushed:
             refresher.run()
@@ -448,12 +468,15 @@ class _GpuLearner(Algorithm):
     def _adam_rider(self, net, last, whole_update):
         """`optimizer.step()` (grpo.py:145) as a rider of the backward pass's last launch, where nothing stands between the gradients
         and the step: the fp32 chain learner, one rank (no all-reduce), the update's rows in ONE chunk, and an optimizer that holds
-        exactly this net's parameters.  None otherwise -- the caller then all-reduces and calls _optimizer_step() as before."""
+        exactly this net's parameters.  None otherwise -- the caller then all-reduces and calls _optimizer_step() as before.
+        It declines while a control block is active (target_kl / kl_every): there is no rider form of the `_ctl` step."""
         m = self._mlp(net)
         if not (whole_update and m is not None and m._f32 is not None) or D.rank_world(self.process_group)[1] != 1 or D._ALWAYS:
             return None                     # (TG_COLLECTIVES_AT_WORLD_1=1: the gradient all-reduce is wanted even at one rank)
         if self.max_grad_norm is not None:
             return None                     # (the norm needs every gradient element finished before any parameter moves)
+        if self._kl_run is not None:
+            return None                     # (the step must read the control block: tg_adam_step*_ctl)
         refresher = self._optimizer_setup(net)
         if refresher is None or not self._adam_covers_bucket:
             return None
@@ -618,7 +641,13 @@ class _GpuLearner(Algorithm):
 
     # ---- kl_stats / desired_kl: how far this learn() moved the policy, measured ONCE after its last optimizer step, and rsl_rl's
     # adaptive learning rate from it ("KL-adaptive learning rate").  Off: nothing below runs ----
-    def _kl_setup(self, kl_stats, desired_kl, lr_bounds, lr_factor):
+    # ---- target_kl / kl_every: the same measurement BETWEEN the optimizer steps of a learn() ("Per-update KL
+    # control"): tg_kl_control acts on a device control block, the optimizer launches read it, and the host only ever follows ----
+    _KL_BREAK_LAG = 1               # the host reads the check this many checks back before it enqueues more (None: it never breaks)
+    _KL_LIST_KEYS = ("J", "kl_ref", "actor_loss", "critic_loss", "kl_div", "total_loss", "entropy", "grad_norm")     # one entry per step
+    _kl_run = None
+
+    def _kl_setup(self, kl_stats, desired_kl, lr_bounds, lr_factor, target_kl=None, kl_stop_factor=1.5, kl_every=None):
         def number(x):
             return not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x)
         if not isinstance(kl_stats, bool):
@@ -633,10 +662,23 @@ class _GpuLearner(Algorithm):
             raise ValueError(f"lr_bounds must be finite numbers with 0 < lr_min <= lr_max, got {lr_bounds!r}")
         if not (number(lr_factor) and lr_factor > 1):
             raise ValueError(f"lr_factor must be a finite number > 1, got {lr_factor!r}")
-        self.kl_stats = kl_stats or desired_kl is not None
+        if target_kl is not None and not (number(target_kl) and target_kl > 0):
+            raise ValueError(f"target_kl must be None or a finite number > 0, got {target_kl!r}")
+        if not (number(kl_stop_factor) and kl_stop_factor > 0):
+            raise ValueError(f"kl_stop_factor must be a finite number > 0, got {kl_stop_factor!r}")
+        if kl_every is not None and (isinstance(kl_every, bool) or not isinstance(kl_every, int) or kl_every < 1):
+            raise ValueError(f"kl_every must be None or an integer >= 1, got {kl_every!r}")
+        if kl_every is not None and target_kl is None and desired_kl is None:
+            raise ValueError(f"kl_every = {kl_every!r} schedules checks that nothing acts on: give target_kl or desired_kl with it")
+        self.kl_stats = kl_stats or desired_kl is not None or target_kl is not None
         self.desired_kl = None if desired_kl is None else float(desired_kl)
         self.lr_bounds, self.lr_factor = (float(lo), float(hi)), float(lr_factor)
-        self._kl_pending = self._kl_pinned = self._kl_host = None
+        self.target_kl = None if target_kl is None else float(target_kl)
+        self.kl_stop_factor, self.kl_every = float(kl_stop_factor), kl_every
+        self._kl_ctl = target_kl is not None or kl_every is not None        # checks between the optimizer steps, a control block
+        self._kl_adapt_checks = desired_kl is not None and kl_every is not None      # ... whose lr the optimizer launches read
+        self._kl_rows = []                                                  # pinned f64 [64][8] blocks: one row per check of a learn()
+        self._kl_pending = self._kl_pinned = self._kl_host = self._kl_run = None
         self._kl_bounds_checked = False
         if self.desired_kl is not None:
             self._kl_group_lr()
@@ -657,48 +699,145 @@ class _GpuLearner(Algorithm):
             raise ValueError(f"the optimizer's lr = {lr} lies outside lr_bounds = {self.lr_bounds}")
         self._kl_bounds_checked = True
 
-    def _measure_shift(self, actor, xin, act, old_logp, var, ls, cap):
-        """After the last optimizer step, before old_policy <- policy: one no-grad actor pass over this learn()'s rows, chunk by chunk,
-        each chunk's means into tg_policy_shift with the actions and the old log-probabilities (a learned log_std stays on the
-        device); the partials' sums, all-reduced, into tg_lr_adapt with the current lr BY VALUE; {sums, kl, clip fraction, lr_in,
-        lr_out} to pinned memory behind an event.  Nothing here waits, and nothing it writes is read by an update."""
+    def _shift_sums(self, actor, xin, act, old_logp, var, ls, cap):
+        """What a check and the end-of-learn() measurement share: one no-grad actor pass over this learn()'s rows, chunk by chunk, each
+        chunk's means into tg_policy_shift with the actions and the old log-probabilities (a learned log_std stays on the device), the
+        partials' sums, all-reduced.  Returns the device f64 buffer whose first four entries they are: sums [4] | tg_lr_adapt's {kl,
+        clip_fraction, lr_in, lr_out} | with checks between the steps, the control block [8]."""
         dev, rows = xin.device, xin.shape[0]
         chunks = [(lo, min(lo + self.chunk_rows, rows)) for lo in range(0, rows, self.chunk_rows)]
         cap = max(cap, rows, 1)                                             # (sized for the largest iteration this buffer can bring)
         n_part = (cap // self.chunk_rows) * K.policy_shift_blocks(self.chunk_rows) + K.policy_shift_blocks(cap % self.chunk_rows)
         partials = self._small("shift_partials", 4 * n_part, torch.float64, dev).view(-1, 4)
-        out8 = self._small("shift_out", 8, torch.float64, dev)              # sums [4] | {kl, clip_fraction, lr_in, lr_out}
+        out = self._small("shift_out", 16 if self._kl_ctl else 8, torch.float64, dev)
         log_lo, log_hi = math.log1p(-float(self.epsilon)), math.log1p(float(self.epsilon))
         slot = 0
         for lo, hi in chunks:
             mean = self._forward(actor, xin[lo:hi], view=True)
             slot += K.policy_shift(mean, act[lo:hi], old_logp[lo:hi], var, log_lo, log_hi, partials, slot, log_std=ls)
-        K.policy_shift_finish(partials, slot, out8[:4])
-        D.allreduce_sum_(out8[:4], self.process_group, "policy_shift")
+        K.policy_shift_finish(partials, slot, out[:4])
+        D.allreduce_sum_(out[:4], self.process_group, "policy_shift")
+        return out
+
+    def _measure_shift(self, actor, xin, act, old_logp, var, ls, cap):
+        """After the last optimizer step, before old_policy <- policy: _shift_sums(), then tg_lr_adapt with the current lr BY VALUE;
+        {sums, kl, clip fraction, lr_in, lr_out} to pinned memory behind an event.  Nothing here waits, and nothing it writes is read
+        by an update.  With per-update adaptation (desired_kl and kl_every) the rate lives in the control block: tg_kl_control applies
+        the rule there (target_kl = 0: nothing is left to stop; a latched block stays -- its last check measured these very weights)
+        and tg_lr_adapt only measures.  The control block travels behind the eight numbers."""
+        out = self._shift_sums(actor, xin, act, old_logp, var, ls, cap)
+        dev, run = xin.device, self._kl_run
         adapt = self.desired_kl is not None
-        lr = self._kl_group_lr() if adapt else float(self.optimizer.param_groups[0]["lr"])
-        K.lr_adapt(out8[:4], self.desired_kl if adapt else 0.0, self.lr_factor, *self.lr_bounds, lr, out8[4:])
+        if run is not None and self._kl_adapt_checks:
+            K.kl_control(out[:4], 0.0, 1.0, self.desired_kl, self.lr_factor, *self.lr_bounds, max(run["enqueued"], 1), run["ctl"])
+            K.lr_adapt(out[:4], 0.0, self.lr_factor, *self.lr_bounds, run["lr"], out[4:8])
+        else:
+            lr = self._kl_group_lr() if adapt else float(self.optimizer.param_groups[0]["lr"])
+            K.lr_adapt(out[:4], self.desired_kl if adapt else 0.0, self.lr_factor, *self.lr_bounds, lr, out[4:8])
         if self._kl_pinned is None:
-            self._kl_pinned = torch.empty(8, dtype=torch.float64).pin_memory()
-        self._kl_pinned.copy_(out8, non_blocking=True)
+            self._kl_pinned = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
+        self._kl_pinned.copy_(out, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        self._kl_pending = (self._kl_pinned, ev)
+        self._kl_pending, self._kl_run = (self._kl_pinned, ev, run), None
+
+    def _kl_begin(self, actor, xin, act, old_logp, var, ls, cap):
+        """target_kl / kl_every: this learn()'s control block {0, lr, 0, 0, nan, nan, 0, 0} -- one copy from pinned memory, no wait --
+        and the arguments every check of it takes.  Called once the rows are prepared and the last learn()'s result has been applied."""
+        if not self._kl_ctl:
+            return
+        dev = xin.device
+        lr = self._kl_group_lr() if self._kl_adapt_checks else float(self.optimizer.param_groups[0]["lr"])
+        ctl = self._small("shift_out", 16, torch.float64, dev)[8:]
+        nan = float("nan")
+        # (a new pinned tensor: the host allocator keeps its block until the copy has run)
+        ctl.copy_(torch.tensor([0.0, lr, 0.0, 0.0, nan, nan, 0.0, 0.0], dtype=torch.float64).pin_memory(), non_blocking=True)
+        self._kl_run = {"ctl": ctl, "lr": lr, "lr_host": lr, "enqueued": 0, "checks": [], "latched": False, "fused": True,
+                        "args": (actor, xin, act, old_logp, var, ls, cap), "every": self.kl_every or 1}
+
+    def _kl_check(self):
+        """One check: _shift_sums(), tg_kl_control on the control block, the block to this check's own pinned row behind its own event."""
+        run = self._kl_run
+        out = self._shift_sums(*run["args"])
+        K.kl_control(out[:4], self.target_kl or 0.0, self.kl_stop_factor, self.desired_kl if self._kl_adapt_checks else 0.0, self.lr_factor,
+                     *self.lr_bounds, run["enqueued"], run["ctl"])
+        i = len(run["checks"])
+        if i // 64 >= len(self._kl_rows):
+            self._kl_rows.append(torch.empty(64, 8, dtype=torch.float64).pin_memory())
+        row = self._kl_rows[i // 64][i % 64]
+        row.copy_(run["ctl"], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(out.device))
+        run["checks"].append((row, ev))
+
+    def _kl_read(self, i) -> bool:
+        """Wait for check i of this learn() and read its row: True when the device has latched.  On the waiting path (an optimizer
+        the fused step does not take) the row's lr goes into the param groups right here."""
+        run = self._kl_run
+        row, ev = run["checks"][i]
+        ev.synchronize()
+        if not run["fused"] and self._kl_adapt_checks:
+            lr = float(row[1])
+            for g in self.optimizer.param_groups:
+                if float(g["lr"]) == run["lr_host"]:
+                    g["lr"] = lr
+            run["lr_host"] = lr
+        run["latched"] = float(row[0]) != 0.0
+        return run["latched"]
+
+    def _kl_after_step(self, last) -> bool:
+        """Called behind every optimizer step of a learn(); True: leave the update loop(s).  Enqueues the check that follows every
+        kl_every-th step but the last, then reads the check _KL_BREAK_LAG checks back -- every rank the same all-reduced bits, so all
+        ranks leave at the same step.  The device has decided long before: the steps enqueued behind a latch change nothing."""
+        run = self._kl_run
+        if run is None:
+            return False
+        if run["latched"]:                  # (the waiting path read the latch in front of this step and did not take it)
+            return True
+        if last or run["enqueued"] % run["every"]:
+            return False
+        self._kl_check()
+        lag = self._KL_BREAK_LAG if run["fused"] else 0
+        if lag is None or len(run["checks"]) <= lag:
+            return False
+        return self._kl_read(len(run["checks"]) - 1 - lag)
 
     def _kl_sync(self):
         """The last measurement, once its copy has landed (it was enqueued behind the updates of the learn() that made it; the next
         learn() asks only after it has waited for the next rollout's row count, which runs behind them): lr_out into every param group
-        that still holds lr_in -- a group the user has changed since keeps the user's value."""
+        that still holds lr_in -- a group the user has changed since keeps the user's value.  With a control block: the CPU step
+        counters, advanced per enqueued step, go back to steps at entry + steps applied, and the rate is the block's."""
         if self._kl_pending is None:
             return
-        (host, ev), self._kl_pending = self._kl_pending, None
+        (host, ev, run), self._kl_pending = self._kl_pending, None
         ev.synchronize()
-        n, _, _, s_d, kl, clip_fraction, lr_in, lr_out = host.tolist()
+        vals = host.tolist()
+        n, _, _, s_d, kl, clip_fraction, lr_in, lr_out = vals[:8]
+        info = {}
+        if run is not None:
+            ctl = vals[8:16]
+            stopped = ctl[0] != 0.0
+            applied = int(ctl[2]) if stopped else run["enqueued"]
+            if run["enqueued"] > applied:
+                for g in self.optimizer.param_groups:
+                    for p in g["params"]:
+                        if "step" in self.optimizer.state.get(p, {}):
+                            self.optimizer.state[p]["step"] -= run["enqueued"] - applied
+            if self._kl_adapt_checks:
+                lr_in, lr_out = run["lr_host"], ctl[1]
+            kls, lrs = [], []
+            for row, _ in run["checks"]:    # (the rows behind a latch repeat it)
+                r = row.tolist()
+                kls.append(r[4])
+                lrs.append(r[1])
+                if r[0] != 0.0:
+                    break
+            info = {"n_updates": applied, "kl_stopped": stopped, "kl_checks": kls, "lr_checks": lrs}
         if self.desired_kl is not None:
             for g in self.optimizer.param_groups:
                 if float(g["lr"]) == lr_in:
                     g["lr"] = lr_out
-        self._kl_host = {"approx_kl": kl, "clip_fraction": clip_fraction, "log_ratio_mean": s_d / n if n > 0 else float("nan")}
+        self._kl_host = {"approx_kl": kl, "clip_fraction": clip_fraction, "log_ratio_mean": s_d / n if n > 0 else float("nan"), **info}
 
     def _kl_stats_read(self) -> dict:
         self._kl_sync()
@@ -707,9 +846,14 @@ class _GpuLearner(Algorithm):
     def _kl_metadata(self) -> dict:
         if not self.kl_stats:
             return {}
-        if self.desired_kl is None:
-            return {"kl_stats": True}
-        return {"desired_kl": self.desired_kl, "lr_bounds": list(self.lr_bounds), "lr_factor": self.lr_factor}
+        out = {}
+        if self.target_kl is not None:
+            out.update({"target_kl": self.target_kl, "kl_stop_factor": self.kl_stop_factor})
+        if self.kl_every is not None:
+            out["kl_every"] = self.kl_every
+        if self.desired_kl is not None:
+            out.update({"desired_kl": self.desired_kl, "lr_bounds": list(self.lr_bounds), "lr_factor": self.lr_factor})
+        return out or {"kl_stats": True}
 
 
 def _check_ref_model(ref_model, policy):
@@ -762,6 +906,14 @@ class GRPO(_GpuLearner):
     save()) without a stall.  kl_stats=True: measure and report only.  Off: no launch, allocation, collective or entry point more,
     and on, the updates themselves are those of a learner without the keywords, bit for bit.
 
+    target_kl (a finite number > 0; kl_stop_factor, kl_every): early stopping of the updates of a learn() ("Per-update
+    KL control").  Behind every kl_every-th optimizer step but the last (default: every one) a check runs the same measurement;
+    once a check's approx_kl exceeds kl_stop_factor * target_kl, no further optimizer step of this learn() changes anything: the
+    verdict lives in a device control block (tg_kl_control) that the optimizer launches read (tg_adam_step*_ctl), and the host
+    follows _KL_BREAK_LAG checks behind.  desired_kl with an integer kl_every applies the lr rule at every check, on the device,
+    instead of once per learn().  last_stats gains "n_updates", "kl_stopped", "kl_checks", "lr_checks" and its per-update lists end
+    with the last update applied; .grad after an early stop holds whatever the last enqueued update left.  Off: nothing more runs.
+
     baseline="step" ("GRPO step baselines"): the advantage of a valid (episode, t) is its return-to-go minus the mean
     return-to-go of the episodes of ITS group that are alive at step t -- with restart groups a Monte-Carlo estimate of the value
     there -- in place of the reference's one mean over all of the group's (episode, t) (grpo.py:110-115, baseline="group", the
@@ -775,7 +927,8 @@ class GRPO(_GpuLearner):
     def __init__(self, epsilon: float, beta: float, gamma: float, policy, optimizer, ref_model=None,
                  updates_per_iter: int = 10, *, maximize: bool = False, chunk_rows=None, autocast_dtype=None,
                  process_group=None, fused_mlp: bool = True, max_grad_norm=None, kl_stats: bool = False, desired_kl=None,
-                 lr_bounds=(1e-5, 1e-2), lr_factor: float = 1.5, baseline: str = "group", adv_scale: str = "std"):
+                 lr_bounds=(1e-5, 1e-2), lr_factor: float = 1.5, baseline: str = "group", adv_scale: str = "std", target_kl=None,
+                 kl_stop_factor: float = 1.5, kl_every=None):
         if baseline not in self.BASELINES:
             raise ValueError(f"baseline must be one of {self.BASELINES}, got {baseline!r}")
         if adv_scale not in self.ADV_SCALES:
@@ -790,7 +943,7 @@ class GRPO(_GpuLearner):
         self.updates_per_iter = updates_per_iter
         self.maximize = maximize
         self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm,
-                    kl_stats, desired_kl, lr_bounds, lr_factor)
+                    kl_stats, desired_kl, lr_bounds, lr_factor, target_kl, kl_stop_factor, kl_every)
         self.old_policy = self._make_old_policy()                           # grpo.py:48
         self._old_synced = self._actor_keys()
 
@@ -885,6 +1038,7 @@ class GRPO(_GpuLearner):
             in_dim = next(m for m in ref_actor.network if isinstance(m, torch.nn.Linear)).in_features
             ref_logp = self._logp_nograd(ref_actor, self._ref_input(ref_actor, xin, in_dim, traj.T * traj.n, traj, idx), act, self.ref_model.var,
                                          out=self._ws.get("ref_logp", X.shape[0], 1, torch.float32, X.device, traj.T * traj.n).view(-1))
+        self._kl_begin(actor, xin, act, old_logp, var, ls, traj.T * traj.n)
         for u in range(self.updates_per_iter):
             if u > 0:
                 self._zero_grads()
@@ -924,6 +1078,8 @@ class GRPO(_GpuLearner):
                 continue
             self.bucket.allreduce(self.process_group)                        # one RCCL all-reduce / step
             self._optimizer_step(actor, last=last)
+            if self._kl_after_step(last):                                   # (target_kl: the device has stopped, the host follows)
+                break
         self._check_deferred()                                              # (this learn()'s own row count / fold flag: landed long ago)
         if self.kl_stats:
             self._measure_shift(actor, xin, act, old_logp, var, ls, traj.T * traj.n)
@@ -1020,13 +1176,17 @@ class PPO(_GpuLearner):
     the batch's own mean and std.  last_stats gains "value_mean", "value_std", "value_count", "explained_variance".  GRPO ignores it.
 
     kl_stats, desired_kl, lr_bounds, lr_factor: as GRPO's -- measured once per learn() behind its last optimizer step (the last
-    minibatch's in minibatch mode), over all valid rows.  ("kl_div" stays the reference's own penalty term.)"""
+    minibatch's in minibatch mode), over all valid rows.  ("kl_div" stays the reference's own penalty term.)
+
+    target_kl, kl_stop_factor, kl_every: as GRPO's -- in minibatch mode a check follows every kl_every-th minibatch step, a stop
+    leaves both loops, and "n_updates" counts optimizer steps."""
 
     def __init__(self, epsilon: float, policy, optimizer, ref_model, updates_per_iter: int, c1: float = 0.5,
                  kl_coeff: float = 0.5, gamma: float = 0.99, lam: float = 0.95, entropy: float = 0.01,
                  batch_size: int = 64, monte_carlo: bool = True, *, chunk_rows=None, autocast_dtype=None,
                  process_group=None, seed: int = 0, fused_mlp: bool = True, max_grad_norm=None, bootstrap_truncated: bool = False,
-                 kl_stats: bool = False, desired_kl=None, lr_bounds=(1e-5, 1e-2), lr_factor: float = 1.5):
+                 kl_stats: bool = False, desired_kl=None, lr_bounds=(1e-5, 1e-2), lr_factor: float = 1.5, target_kl=None,
+                 kl_stop_factor: float = 1.5, kl_every=None):
         if not isinstance(bootstrap_truncated, bool):
             raise ValueError(f"bootstrap_truncated must be True or False, got {bootstrap_truncated!r}")
         self.bootstrap_truncated = bootstrap_truncated
@@ -1035,7 +1195,7 @@ class PPO(_GpuLearner):
         self.gamma, self.lam, self.entropy = gamma, lam, entropy
         self.batch_size, self.kl_coeff, self.monte_carlo = batch_size, kl_coeff, monte_carlo
         self._setup(policy, optimizer, chunk_rows, autocast_dtype, process_group, fused_mlp, max_grad_norm,
-                    kl_stats, desired_kl, lr_bounds, lr_factor)
+                    kl_stats, desired_kl, lr_bounds, lr_factor, target_kl, kl_stop_factor, kl_every)
         self.old_policy = self._make_old_policy()                           # ppo.py:62 (never read in learn)
         self._seed = seed
         self._gen = None
@@ -1291,12 +1451,17 @@ class PPO(_GpuLearner):
                  if self.batch_size is None and self.updates_per_iter > 0 else None)
         self._sum_rows = list(table.unbind(0))[::-1] if table is not None else None
         norm_host = None
+        self._kl_begin(actor, xin, act, old_logp, var, self._learned_std(), cap)
+        stop = False
         for u in range(self.updates_per_iter):
             final = u == self.updates_per_iter - 1
+            if stop:
+                break
             if self.batch_size is None:
                 # full batch: the reference permutes and takes one "minibatch" of everything (ppo.py:147-150)
                 self._step(xin, act, adv, ret, old_logp, norm8, var, all_sums, last=final, write_old=fold_old and u == 0,
                            xin_c=None if priv is None else xin_c)
+                stop = self._kl_after_step(final)                           # (target_kl: the device has stopped, the host follows)
             else:
                 if self.permutation_fn is not None:
                     perm = self.permutation_fn(n_rows, dev)
@@ -1317,12 +1482,16 @@ class PPO(_GpuLearner):
                                ret.index_select(0, b), old_logp.index_select(0, b), norm8, var, all_sums,
                                host=(norm_host, float(sizes[k])), last=final and k == n_steps - 1,
                                xin_c=None if priv is None else M.inherit_ones_column(xin_c.index_select(0, b), xin_c))
+                    stop = self._kl_after_step(final and k == n_steps - 1)
+                    if stop:
+                        break
         self._check_deferred()                                              # (this learn()'s own row count: landed long ago)
         if self.kl_stats:
             self._measure_shift(actor, xin, act, old_logp, var, self._learned_std(), cap)
         self._copy_policy_to_old()                                          # ppo.py:186
         if all_sums:
-            S2 = table if table is not None else torch.stack(all_sums)      # [steps][actor | critic][4]
+            # [steps][actor | critic][4] (the steps that were enqueued: the host may have left the loop behind a target_kl stop)
+            S2 = table[:len(all_sums)] if table is not None else torch.stack(all_sums)
             D.allreduce_sum_(S2, self.process_group, "loss_stats")
             ls = self._learned_std()
             ent = 0.5 * act.shape[1] * (1.0 + math.log(2 * math.pi)) + (0.0 if ls is not None else 0.5 * float(torch.log(var).sum()))

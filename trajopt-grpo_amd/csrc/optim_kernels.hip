@@ -43,6 +43,40 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict_
     if constexpr (kPush) adam_push(e, p, seg, inv_start, inv_dst);
 }
 
+// adam_kernel behind tg_kl_control's device control block (policy_shift.hip; ctl f64 [8], ctl[0] = stopped, ctl[1] = lr): kernels of
+// their own, so that the four above keep their code.  Every thread reads ctl[0], a uniform load: once a check has latched it, a
+// launch that was already enqueued writes no parameter, no moment and no derived layout -- it zeroes its gradient element if
+// zero_grads asks and leaves the gradient as it is otherwise (the clip product is not written back).
+// lr_from_ctl: step_size is formed here, in double, from the device's rate and the host's bc1 = 1 - beta1^step, by the division
+// adam_scalars() does: a block that holds the host's lr gives the plain launch's bits.
+template <bool kPush, bool kClip>
+__global__ __launch_bounds__(256) void adam_ctl_kernel(const AdamTensor* __restrict__ table, int32_t n_tensors, int64_t total, AdamScalars a,
+                                                       int32_t zero_grads, const GatherSegment* __restrict__ seg,
+                                                       const int32_t* __restrict__ inv_start, const int32_t* __restrict__ inv_dst,
+                                                       const float* __restrict__ coef, const double* __restrict__ ctl, int32_t lr_from_ctl,
+                                                       double bc1) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    int k = 0;
+    for (int t = 1; t < n_tensors; ++t)
+        if (e >= table[t].first) k = t;
+    const AdamTensor d = table[k];
+    const int64_t i = e - d.first;
+    if (ctl[0] != 0.0) {
+        if (zero_grads) d.g[i] = 0.0f;
+        return;
+    }
+    if (lr_from_ctl) a.step_size = (float)((ctl[1] / bc1) * -1.0);
+    float g = d.g[i];
+    if constexpr (kClip) g = rn_mul(g, *coef);
+    float m = d.m[i], v = d.v[i];
+    const float p = adam_update(g, m, v, d.p[i], a);
+    d.m[i] = m; d.v[i] = v; d.p[i] = p;
+    if (zero_grads) d.g[i] = 0.0f;
+    else if constexpr (kClip) d.g[i] = g;
+    if constexpr (kPush) adam_push(e, p, seg, inv_start, inv_dst);
+}
+
 // flag[0] |= 1 when any element of tensor pair (p, g) of the table differs bitwise (the learner's check that "old_policy is the
 // policy" really held when it let the first update stand in for the old policy's pass)
 __global__ __launch_bounds__(256) void params_differ_kernel(const AdamTensor* __restrict__ table, int32_t n_tensors, int64_t total,
@@ -191,6 +225,58 @@ int tg_adam_step_push_clip(const tg_adam_tensor* d_table, int32_t n_tensors, int
                        reinterpret_cast<const GatherSegment*>(d_segments), d_inv_start, d_inv_dst, d_coef);
     TG_LAUNCH_CHECK("tg_adam_step_push_clip");
     return TG_OK;
+}
+
+}  // extern "C"
+
+// the four `_ctl` entry points: the plain entry point's checks, the control block's, one launch of adam_ctl_kernel
+template <bool kPush, bool kClip>
+static int adam_step_ctl(const char* who, const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2,
+                         double eps, int64_t step, int32_t zero_grads, const tg_gather_segment* d_segments, int32_t n_segments,
+                         const int32_t* d_inv_start, const int32_t* d_inv_dst, const float* d_coef, const double* d_ctl, int32_t lr_from_ctl,
+                         double bc1, void* stream) {
+    if (int rc = adam_args_ok(who, d_table, n_tensors, total, beta1, step, kPush, d_segments, n_segments, d_inv_start, d_inv_dst)) return rc;
+    if (kClip) TG_REQUIRE(d_coef, "%s: null d_coef", who);
+    TG_REQUIRE(d_ctl && ((uintptr_t)d_ctl & 7) == 0, "%s: d_ctl is null or not 8-B aligned", who);
+    TG_REQUIRE(lr_from_ctl == 0 || lr_from_ctl == 1, "%s: lr_from_ctl = %d is neither 0 nor 1", who, lr_from_ctl);
+    TG_REQUIRE(bc1 > 0.0 && bc1 <= 1.0, "%s: bc1 = %g outside (0, 1] (1 - beta1^step)", who, bc1);
+    if (total == 0) return TG_OK;
+    hipLaunchKernelGGL((adam_ctl_kernel<kPush, kClip>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const AdamTensor*>(d_table), n_tensors, total, adam_scalars(lr, beta1, beta2, eps, step), zero_grads,
+                       reinterpret_cast<const GatherSegment*>(d_segments), d_inv_start, d_inv_dst, d_coef, d_ctl, lr_from_ctl, bc1);
+    TG_LAUNCH_CHECK(who);
+    return TG_OK;
+}
+
+extern "C" {
+
+int tg_adam_step_ctl(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2, double eps,
+                     int64_t step, int32_t zero_grads, const double* d_ctl, int32_t lr_from_ctl, double bc1, void* stream) {
+    return adam_step_ctl<false, false>("tg_adam_step_ctl", d_table, n_tensors, total, lr, beta1, beta2, eps, step, zero_grads, nullptr, 0, nullptr,
+                                       nullptr, nullptr, d_ctl, lr_from_ctl, bc1, stream);
+}
+
+int tg_adam_step_ctl_clip(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2, double eps,
+                          int64_t step, int32_t zero_grads, const float* d_coef, const double* d_ctl, int32_t lr_from_ctl, double bc1,
+                          void* stream) {
+    return adam_step_ctl<false, true>("tg_adam_step_ctl_clip", d_table, n_tensors, total, lr, beta1, beta2, eps, step, zero_grads, nullptr, 0,
+                                      nullptr, nullptr, d_coef, d_ctl, lr_from_ctl, bc1, stream);
+}
+
+int tg_adam_step_push_ctl(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2, double eps,
+                          int64_t step, int32_t zero_grads, const tg_gather_segment* d_segments, int32_t n_segments,
+                          const int32_t* d_inv_start, const int32_t* d_inv_dst, const double* d_ctl, int32_t lr_from_ctl, double bc1,
+                          void* stream) {
+    return adam_step_ctl<true, false>("tg_adam_step_push_ctl", d_table, n_tensors, total, lr, beta1, beta2, eps, step, zero_grads, d_segments,
+                                      n_segments, d_inv_start, d_inv_dst, nullptr, d_ctl, lr_from_ctl, bc1, stream);
+}
+
+int tg_adam_step_push_ctl_clip(const tg_adam_tensor* d_table, int32_t n_tensors, int64_t total, double lr, double beta1, double beta2,
+                               double eps, int64_t step, int32_t zero_grads, const tg_gather_segment* d_segments, int32_t n_segments,
+                               const int32_t* d_inv_start, const int32_t* d_inv_dst, const float* d_coef, const double* d_ctl,
+                               int32_t lr_from_ctl, double bc1, void* stream) {
+    return adam_step_ctl<true, true>("tg_adam_step_push_ctl_clip", d_table, n_tensors, total, lr, beta1, beta2, eps, step, zero_grads, d_segments,
+                                     n_segments, d_inv_start, d_inv_dst, d_coef, d_ctl, lr_from_ctl, bc1, stream);
 }
 
 int64_t tg_grad_clip_workspace(int64_t n) { return norm_blocks(n) * (int64_t)sizeof(double); }

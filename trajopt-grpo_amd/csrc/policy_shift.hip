@@ -7,6 +7,8 @@
 // Workgroup b covers rows [b * 4096, (b + 1) * 4096) (grid-stride beyond 1024 workgroups): which rows a thread adds, and the order of
 // every addition after that, depend on `rows` alone.
 // tg_policy_shift_finish: one workgroup adds all partials in index order.  tg_lr_adapt: one thread, the rule in float64.
+// tg_kl_control: the same thread's work for a check BETWEEN the updates of a learn(): the rule on the rate held in a device control
+// block, and target_kl's latch, which the optimizer launches that follow read (optim_kernels.hip: adam_ctl_kernel).
 #include "loss_row.hpp"
 
 namespace tg {
@@ -102,6 +104,26 @@ __global__ __launch_bounds__(64) void lr_adapt_kernel(const double* __restrict__
     out4[0] = kl; out4[1] = clip_fraction; out4[2] = lr; out4[3] = lr_out;
 }
 
+// ctl f64 [8] = {stopped, lr, stop_update, kl_at_stop, last_kl, last_clip_fraction, checks, 0}.  A latched block is left as it is,
+// byte for byte; else tg_lr_adapt's rule on ctl[1] (the check that latches applies it too), then the latch.  A NaN kl or rows == 0
+// neither adapts nor stops: every comparison is false.
+__global__ __launch_bounds__(64) void kl_control_kernel(const double* __restrict__ sums, double target_kl, double stop_factor,
+                                                        double desired_kl, double factor, double lr_min, double lr_max, double update,
+                                                        double* __restrict__ ctl) {
+    if (threadIdx.x != 0) return;
+    if (ctl[0] != 0.0) return;
+    const double rows = sums[0];
+    const double kl = sums[1] / rows, clip_fraction = sums[2] / rows;
+    const double lr = ctl[1];
+    double lr_out = lr;
+    if (desired_kl > 0.0 && rows > 0.0) {
+        if (kl > 2.0 * desired_kl) lr_out = fmax(lr / factor, lr_min);
+        else if (kl < 0.5 * desired_kl) lr_out = fmin(lr * factor, lr_max);
+    }
+    ctl[1] = lr_out; ctl[4] = kl; ctl[5] = clip_fraction; ctl[6] = ctl[6] + 1.0; ctl[7] = 0.0;
+    if (target_kl > 0.0 && rows > 0.0 && kl > stop_factor * target_kl) { ctl[0] = 1.0; ctl[2] = update; ctl[3] = kl; }
+}
+
 template <int A, bool kStd>
 static void launch_shift_std(const ShiftK& k, unsigned grid, bool vec, hipStream_t st) {
     if constexpr (A % 4 == 0) {
@@ -183,6 +205,23 @@ int tg_lr_adapt(const double* d_sums, double desired_kl, double factor, double l
                factor, lr_min, lr_max);
     hipLaunchKernelGGL(lr_adapt_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_sums, desired_kl, factor, lr_min, lr_max, lr, d_out4);
     TG_LAUNCH_CHECK("tg_lr_adapt");
+    return TG_OK;
+}
+
+int tg_kl_control(const double* d_sums, double target_kl, double stop_factor, double desired_kl, double factor, double lr_min,
+                  double lr_max, int64_t update, double* d_ctl, void* stream) {
+    TG_REQUIRE(d_sums && d_ctl, "tg_kl_control: null pointer");
+    TG_REQUIRE(((uintptr_t)d_sums & 7) == 0 && ((uintptr_t)d_ctl & 7) == 0, "tg_kl_control: the sums / the control block are not 8-B aligned");
+    // (target_kl <= 0: never stops, stop_factor is not looked at; desired_kl <= 0: the rate stays, the bounds and the factor are not)
+    TG_REQUIRE(!(target_kl > 0.0) || (__builtin_isfinite(target_kl) && __builtin_isfinite(stop_factor) && stop_factor > 0.0),
+               "tg_kl_control: target_kl = %g must be finite and stop_factor = %g finite and > 0", target_kl, stop_factor);
+    TG_REQUIRE(!(desired_kl > 0.0) || (factor > 1.0 && lr_min <= lr_max), "tg_kl_control: factor = %g must be > 1 and lr_min = %g <= lr_max = %g",
+               factor, lr_min, lr_max);
+    TG_REQUIRE(target_kl == target_kl && desired_kl == desired_kl, "tg_kl_control: target_kl / desired_kl is NaN");
+    TG_REQUIRE(update >= 1 && update < ((int64_t)1 << 53), "tg_kl_control: update = %lld must be the 1-based count of optimizer steps", (long long)update);
+    hipLaunchKernelGGL(kl_control_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_sums, target_kl, stop_factor, desired_kl, factor, lr_min,
+                       lr_max, (double)update, d_ctl);
+    TG_LAUNCH_CHECK("tg_kl_control");
     return TG_OK;
 }
 

@@ -463,6 +463,18 @@ def lr_adapt(sums: torch.Tensor, desired_kl: float, factor: float, lr_min: float
     return out
 
 
+def kl_control(sums: torch.Tensor, target_kl: float, stop_factor: float, desired_kl: float, factor: float, lr_min: float, lr_max: float,
+               update: int, ctl: torch.Tensor) -> torch.Tensor:
+    """tg_kl_control: one check between the optimizer steps of a learn() on the device control block ctl f64 [8] = {stopped, lr,
+    stop_update, kl_at_stop, last_kl, last_clip_fraction, checks, 0} from the (all-reduced) sums of policy_shift_finish().  target_kl
+    <= 0 never stops, desired_kl <= 0 leaves the rate; a latched block is left as it is."""
+    N.require_cuda(sums, ctl)
+    assert sums.dtype == ctl.dtype == torch.float64 and sums.is_contiguous() and ctl.is_contiguous() and sums.numel() == 4 and ctl.numel() == 8
+    N.check(N.load().tg_kl_control(sums.data_ptr(), float(target_kl), float(stop_factor), float(desired_kl), float(factor), float(lr_min),
+                                   float(lr_max), int(update), ctl.data_ptr(), _st(sums)), "tg_kl_control")
+    return ctl
+
+
 def surrogate_loss(mean, value, act, logp_old, adv, ret, mask, norm, var, epsilon, surr_coef, critic_coef, kl_coef,
                    want_total: bool = True, coef: torch.Tensor = None, logp_ref: torch.Tensor = None, ref_coef: float = 0.0,
                    log_std: torch.Tensor = None, std_out: torch.Tensor = None):

@@ -137,7 +137,7 @@ class FusedAdam:
         return r
 
     @torch.no_grad()
-    def step(self, zero_grads: bool = False, refresher: "StreamRefresher" = None, clip_coef: torch.Tensor = None) -> bool:
+    def step(self, zero_grads: bool = False, refresher: "StreamRefresher" = None, clip_coef: torch.Tensor = None, ctl=None) -> bool:
         """One optimizer step; False (nothing done) when the fused form does not apply -- the caller then runs optimizer.step().
         zero_grads: the launch also zeroes every .grad it has consumed (the next update's optimizer.zero_grad() -- grpo.py:143,
         ppo.py:181 -- folded in); `grads_zeroed` then tells the caller that its own zeroing launch can be skipped.
@@ -146,7 +146,11 @@ class FusedAdam:
         position derived from it) and marks them fresh -- `self.pushed` says so; otherwise the caller runs refresher.run().
         clip_coef: one device float32 (tg_grad_clip_coef's coefficient) -- the step is taken on g * clip_coef (tg_adam_step[_push]_clip)
         and a gradient that is not zeroed is left clipped.  There is no rider() form of this: the norm needs every gradient element
-        finished before any parameter moves."""
+        finished before any parameter moves.
+        ctl: (device float64 [8], lr_from_ctl) -- tg_kl_control's control block: the `_ctl` variants of the same four launches.  Once
+        the block is latched the launch changes no parameter, moment or layout (gradients are still zeroed when asked); with
+        lr_from_ctl the rate is the block's, not the param group's.  The host-side counters advance as for any step: the caller
+        corrects them once it has read the block.  No rider() form either."""
         self.grads_zeroed = False
         self.pushed = False
         if not self.usable():
@@ -160,23 +164,28 @@ class FusedAdam:
         if clip_coef is not None:
             assert clip_coef.dtype == torch.float32 and clip_coef.is_cuda and clip_coef.numel() == 1
         clip = () if clip_coef is None else (clip_coef.data_ptr(),)
-        sfx = "" if clip_coef is None else "_clip"
+        sfx = ("" if ctl is None else "_ctl") + ("" if clip_coef is None else "_clip")
+        if ctl is not None:
+            block, lr_from_ctl = ctl
+            assert block.dtype == torch.float64 and block.is_cuda and block.numel() == 8 and block.is_contiguous()
         for gi, ((tab, n, total), g) in enumerate(zip(self._tables, self.opt.param_groups)):
             for p in g["params"]:
                 self.opt.state[p]["step"] += 1
             step = int(self.opt.state[g["params"][0]]["step"])
             dev = g["params"][0].device
+            # (bc1 as torch/optim/adam.py and adam_scalars() form it: the device divides the block's rate by it)
+            tail = () if ctl is None else (block.data_ptr(), 1 if lr_from_ctl else 0, 1.0 - g["betas"][0] ** step)
             with torch.cuda.device(dev):
                 if push is not None and gi == 0:
                     seg, n_seg, inv_start, inv_dst = push
                     fn = getattr(lib, "tg_adam_step_push" + sfx)
                     N.check(fn(tab.data_ptr(), n, total, g["lr"], g["betas"][0], g["betas"][1], g["eps"], step,
-                               1 if zero_grads else 0, seg.data_ptr(), n_seg, inv_start.data_ptr(), inv_dst.data_ptr(), *clip,
+                               1 if zero_grads else 0, seg.data_ptr(), n_seg, inv_start.data_ptr(), inv_dst.data_ptr(), *clip, *tail,
                                N.stream_ptr(dev)), "tg_adam_step_push" + sfx)
                 else:
                     fn = getattr(lib, "tg_adam_step" + sfx)
                     N.check(fn(tab.data_ptr(), n, total, g["lr"], g["betas"][0], g["betas"][1], g["eps"], step,
-                               1 if zero_grads else 0, *clip, N.stream_ptr(dev)), "tg_adam_step" + sfx)
+                               1 if zero_grads else 0, *clip, *tail, N.stream_ptr(dev)), "tg_adam_step" + sfx)
         N.RAW_PARAM_WRITES[0] += 1
         self.grads_zeroed = bool(zero_grads)
         if push is not None:
