@@ -969,6 +969,17 @@ int  tg_boot_values_affine(const float* d_v, int64_t v_stride, const uint8_t* d_
                            void* stream);
 int  tg_value_norm_merge(const double* d_moments3, double eps, double* d_count, double* d_mean, double* d_m2, float* d_table,
                          float* d_norm8, void* stream);
+/* PopArt (policies: normalize_value=True, popart=True): tg_value_norm_merge and, in the same launch of one workgroup of 256 threads,
+ * the rescale of the critic's last layer d_head_w f32 [hidden], d_head_b f32 [1] that keeps every denormalised prediction where it
+ * was while the statistics move from (mean_a, sigma_a) to (mean_n, sigma_n), sigma = sqrt(m2 / count + eps) in f64:
+ *   w'[k] = (float)((double)w[k] * r), r = sigma_a / sigma_n;   b' = (float)(((double)b * sigma_a + (mean_a - mean_n)) / sigma_n),
+ * every f64 operation rounded on its own.  d_count / d_mean / d_m2 / d_table / d_norm8[2:4] come out bit for bit as
+ * tg_value_norm_merge writes them.  The head keeps its bits, and nothing is stored to it, when d_moments3 == NULL, when n_b == 0,
+ * when the count before the merge is 0 (a critic never trained against a table has nothing to preserve), or when sigma_a or sigma_n
+ * is not a positive finite number.  Refused (TG_ERR_ARG) before any launch: a null statistics, table or head pointer, eps < 0,
+ * hidden < 1.  The masters are written by raw pointer: every weight layout derived from the head is stale afterwards. */
+int  tg_value_norm_merge_popart(const double* d_moments3, double eps, double* d_count, double* d_mean, double* d_m2, float* d_table,
+                                float* d_norm8, float* d_head_w, int32_t hidden, float* d_head_b, void* stream);
 
 /* ---- Privileged critic (policies: privileged_critic={name: (lo, hi)}; PPO) ----
  * The critic of an asymmetric actor-critic reads, behind the observation, the physical parameters its env slot was rolled out with

@@ -3,7 +3,7 @@
 epoch instead of 50-80.
 
     python3 tools/train_ppo.py [epochs] [CartPole|Pendulum|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
-                               [--learn-std] [--normalize-obs] [--normalize-value] [--gae] [--privileged-critic]
+                               [--learn-std] [--normalize-obs] [--normalize-value] [--popart] [--gae] [--privileged-critic]
                                [--eval-every N] [--eval-episodes E] [--eval-sweep name=f1,f2,... ...] [--desired-kl KL]
                                [--target-kl KL] [--kl-every N]
 
@@ -19,7 +19,8 @@ KL is measured on the device, and once it exceeds 1.5 KL the remaining updates o
 evaluation runs one cell per combination of the listed factors on those physical parameters, e.g. `--eval-sweep mass=0.8,1,1.25`.
 
 --normalize-value: running value normalisation (policy.value_norm): the critic regresses onto returns standardised with running
-statistics and is denormalised wherever it enters a return.  --gae: monte_carlo=False (GAE(gamma, 0.95) advantages).
+statistics and is denormalised wherever it enters a return.  --popart (with --normalize-value): the critic head is rescaled when
+those statistics move (policy.value_norm.popart).  --gae: monte_carlo=False (GAE(gamma, 0.95) advantages).
 
 --randomize (repeatable): per-env domain randomisation, e.g. `--randomize mass=0.8:1.25 --randomize tether_length=0.5:2` -- every
 env slot draws its own factor on that physical parameter in every rollout (Env.randomize).
@@ -120,9 +121,10 @@ def main():
     normalize_obs = "--normalize-obs" in sys.argv                 # running observation normalisation (policy.obs_norm)
     sys.argv = [a for a in sys.argv if a != "--normalize-obs"]
     normalize_value = "--normalize-value" in sys.argv             # running value normalisation (policy.value_norm)
+    popart = "--popart" in sys.argv                               # PopArt's rescale of the critic head (needs --normalize-value)
     gae = "--gae" in sys.argv                                     # monte_carlo=False
     privileged = "--privileged-critic" in sys.argv                # an asymmetric actor-critic: the critic reads the drawn parameters
-    sys.argv = [a for a in sys.argv if a not in ("--normalize-value", "--gae", "--privileged-critic")]
+    sys.argv = [a for a in sys.argv if a not in ("--normalize-value", "--popart", "--gae", "--privileged-critic")]
     if privileged and not ranges:
         raise SystemExit("--privileged-critic needs at least one --randomize name=lo:hi: the critic reads the randomised parameters")
     epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 120
@@ -141,6 +143,7 @@ def main():
     pol = tg.GaussianActorCritic_NeuralNetwork(S, A, hidden, cov=cov, device=dev, **({"learn_std": True} if learn_std else {}),
                                                **({"normalize_obs": True} if normalize_obs else {}),
                                                **({"normalize_value": True} if normalize_value else {}),
+                                               **({"popart": True} if popart else {}),
                                                **({"privileged_critic": ranges} if privileged else {}))
     tg.environments.ENV_CLASSES[name]().randomize(ranges)         # (refuses a bad name or range before anything is allocated)
     mgr = tg.RolloutManager(lambda: tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, num_workers=64, num_episodes_per_worker=64,

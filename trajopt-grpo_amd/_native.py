@@ -300,6 +300,7 @@ SIGNATURES = {
     "tg_scatter_rows_affine": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _VP]),
     "tg_boot_values_affine": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _VP]),
     "tg_value_norm_merge": (C.c_int, [_VP, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tg_value_norm_merge_popart": (C.c_int, [_VP, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
     "tg_privileged_rows": (C.c_int, [_VP, _I32, _I32, _VP, _I64, _I64, _VP, _P(PrivilegedSpec), _VP, _I32, _I32, _I32, _VP]),
     "tg_env_param_grid": (C.c_int, [_P(EnvParams), _P(ParamGrid), _VP, _I64, _I64, _VP]),
     "tg_eval_tile_states": (C.c_int, [_P(Traj), _I32, _I64, _VP]),

@@ -211,6 +211,19 @@ class _GpuLearner(Algorithm):
             if m is not None:
                 m.refresh(force=True)
 
+    def _masters_written(self, net):
+        """A launch of the learner's own has just written fp32 masters of `net` by raw pointer (PopArt's rescale of the critic head):
+        what optim.FusedAdam does after its raw writes -- the counter that stands in for torch's version keys moves, and every
+        layout derived from the net is rebuilt from the masters.  The streams the optimizer step's own launch keeps current are
+        rebuilt here (that launch marks them fresh whether or not a path has read them since); the per-layer copies and the packed
+        backward-data fragments by the first path that reads them.  A net on torch autograd reads the masters themselves."""
+        M.N.RAW_PARAM_WRITES[0] += 1
+        m = self._mlp(net)
+        if m is not None:
+            m.refresh(force=True)
+            for what, _ in m.streams():
+                m._fresh(what)
+
     def _check_deferred(self):
         """Checks whose answers are copied to the host asynchronously: the mask's own row count against the rollout's statistic, the
         bitwise comparison behind the folded old-policy pass.  Read at the END of the learn() that enqueued them (both were written
@@ -1118,17 +1131,27 @@ class GRPO(_GpuLearner):
                 **({} if self.baseline == "group" else {"baseline": self.baseline, "adv_scale": self.adv_scale})}
 
 
-def _value_norm_stats(stat3, moments, eps) -> dict:
+def _value_norm_stats(stat3, moments, eps, stat_a=None) -> dict:
     """last_stats' entries of a value-normalised PPO.learn(), from device copies of its {count, mean, m2} after the merge and of the
     all-reduced moments [2][3] = {n, sum, sum of squares} of the valid advantages and returns.  value_std is the table's sigma,
     sqrt(m2 / count + eps) (1 while count == 0); explained_variance = 1 - var(adv) / var(ret) with population variances
-    (s2 - s1 (s1 / n)) / n clamped at 0 -- adv = ret - V on the valid rows in both modes -- and NaN when var(ret) == 0."""
+    (s2 - s1 (s1 / n)) / n clamped at 0 -- adv = ret - V on the valid rows in both modes -- and NaN when var(ret) == 0.
+    stat_a (a PopArt policy: {count, mean, m2} before the merge): "popart_scale" = sigma_a / sigma_n and "popart_shift" = mean_a - mean_n
+    of the rescale this learn() applied to the critic head, in the kernel's f64 operations; 1 and 0 where the head kept its bits."""
     count, mean, m2 = stat3.tolist()
     (na, a1, a2), (nr, r1, r2) = moments.tolist()
     var_a = max(a2 - a1 * (a1 / na), 0.0) / na if na > 0 else float("nan")
     var_r = max(r2 - r1 * (r1 / nr), 0.0) / nr if nr > 0 else float("nan")
-    return {"value_mean": mean if count > 0 else 0.0, "value_std": math.sqrt(m2 / count + eps) if count > 0 else 1.0, "value_count": count,
-            "explained_variance": 1.0 - var_a / var_r if var_r > 0 else float("nan")}
+    out = {"value_mean": mean if count > 0 else 0.0, "value_std": math.sqrt(m2 / count + eps) if count > 0 else 1.0, "value_count": count,
+           "explained_variance": 1.0 - var_a / var_r if var_r > 0 else float("nan")}
+    if stat_a is not None:
+        count_a, mean_a, m2_a = stat_a.tolist()
+        out["popart_scale"], out["popart_shift"] = 1.0, 0.0
+        if count_a > 0 and count > count_a:                                 # (a batch was merged into statistics that were not empty)
+            sigma_a, sigma_n = math.sqrt(m2_a / count_a + eps), math.sqrt(m2 / count + eps)
+            if 0 < sigma_a < math.inf and 0 < sigma_n < math.inf:
+                out["popart_scale"], out["popart_shift"] = sigma_a / sigma_n, mean_a - mean
+    return out
 
 
 def privileged_spec(policy, env, params=None) -> "K.N.PrivilegedSpec":
@@ -1174,6 +1197,12 @@ class PPO(_GpuLearner):
     rows -- is denormalised on the device with the table as it stands at the entry of learn(); the returns' all-reduced moments are
     merged into the statistics (unless frozen) and the critic regresses onto (R - mean) / sigma of the merged statistics, in place of
     the batch's own mean and std.  last_stats gains "value_mean", "value_std", "value_count", "explained_variance".  GRPO ignores it.
+
+    ... and with popart=True as well ("PopArt"): the launch that merges the statistics also rescales the critic's last
+    layer, w' = w sigma / sigma', b' = (b sigma + mean - mean') / sigma', so that the critic read with the merged table predicts what
+    it predicted with the old one; the critic's derived weight layouts are rebuilt from the rescaled masters before the first update,
+    Adam's moments of the head are left alone.  last_stats gains "popart_scale" and "popart_shift".  Frozen statistics, and the
+    first learn() (empty statistics): no rescale.  GRPO ignores it.
 
     kl_stats, desired_kl, lr_bounds, lr_factor: as GRPO's -- measured once per learn() behind its last optimizer step (the last
     minibatch's in minibatch mode), over all valid rows.  ("kl_div" stays the reference's own penalty term.)
@@ -1433,8 +1462,19 @@ class PPO(_GpuLearner):
         if vn is not None:
             # the returns' moments (row 1, all-reduced above: no collective of its own) into the running statistics, the table in
             # place, and the critic's target constants norm8[2:4] <- {mean, 1 / sigma} of the merged statistics: one launch
-            vn._merge(None if vn.frozen else moments[1], norm8)
-            vn_stats = (torch.cat([vn.count, vn.mean, vn.m2]), moments.clone(), vn.eps)      # (copies: read when last_stats is)
+            if not vn.popart:
+                vn._merge(None if vn.frozen else moments[1], norm8)
+                popart = ()
+            else:
+                # PopArt: the same launch also rescales the critic's last layer, so that the critic read with the merged table
+                # predicts what it predicted with the old one.  Everything above read the old head with the old table, every update
+                # below reads the new head with the new constants; frozen statistics: nothing is merged, nothing rescaled
+                stat_a = torch.cat([vn.count, vn.mean, vn.m2])              # (the statistics before the merge: for last_stats)
+                vn._merge(None if vn.frozen else moments[1], norm8, head=None if vn.frozen else critic.network[-1])
+                if not vn.frozen:
+                    self._masters_written(critic)
+                popart = (stat_a,)
+            vn_stats = (torch.cat([vn.count, vn.mean, vn.m2]), moments.clone(), vn.eps, *popart)    # (copies: read when last_stats is)
         adv = self._ws.get("row0", n_rows, 1, torch.float32, dev, cap).view(-1)
         ret = self._ws.get("row1", n_rows, 1, torch.float32, dev, cap).view(-1)
         K.gather_rows2(idx, adv_full, adv, ret_full, ret)

@@ -25,6 +25,9 @@
 //   tg_scatter_rows_affine / tg_boot_values_affine / tg_value_norm_merge
 //                        running value normalisation (policies.ValueNorm): the critic's values denormalised where they enter a
 //                        return, and Chan's merge of the returns' all-reduced moments into {count, mean, m2} and the f32 table.
+//   tg_value_norm_merge_popart
+//                        that merge with PopArt's rescale of the critic's last layer in the same launch: the denormalised
+//                        predictions stay where they were while the statistics move.
 //   tg_privileged_rows   the privileged critic's input rows: the actor's prepared rows with each env's randomised parameters, scaled
 //                        onto [-1, 1], in the columns behind the observation.
 #include <cmath>
@@ -546,6 +549,66 @@ __global__ void value_norm_merge_kernel(const double* __restrict__ moments, doub
     }
 }
 
+// value_norm_merge_kernel with PopArt's rescale of the critic's last layer behind it, in the same launch: thread 0 runs the merge above
+// operation for operation (the statistics, the table and norm8[2:4] come out with the same bits), keeps (mean_a, sigma_a) of the
+// statistics before the merge and (mean_n, sigma_n) of those after it -- sigma = sqrt(m2 / count + eps) in f64, the table's expression
+// -- and hands them to the workgroup through LDS behind one barrier.  Then w'[k] = (float)((double)w[k] * r), r = sigma_a / sigma_n,
+// strided over `hidden`, and b' = (float)(((double)b * sigma_a + (mean_a - mean_n)) / sigma_n) by thread 0: sigma_n (w' . h + b') +
+// mean_n stays sigma_a (w . h + b) + mean_a for every h, up to the roundings.  Nothing is stored to the head unless a batch was
+// merged (moments given, n_b > 0) into statistics that were not empty and both sigmas are positive and finite.
+__global__ __launch_bounds__(256) void value_norm_merge_popart_kernel(const double* __restrict__ moments, double eps, double* __restrict__ count,
+                                                                      double* __restrict__ mean, double* __restrict__ m2,
+                                                                      float* __restrict__ table, float* __restrict__ norm8,
+                                                                      float* __restrict__ head_w, int hidden, float* __restrict__ head_b) {
+#pragma clang fp contract(off)
+    __shared__ double s_pair[4];                             // {mean_a, sigma_a, mean_n, sigma_n}
+    __shared__ int s_rescale;
+    if (threadIdx.x == 0) {
+        double n = count[0], mu = mean[0], q = m2[0];
+        const double na = n, mean_a = mu;
+        const double sigma_a = na > 0.0 ? sqrt(q / na + eps) : 0.0;
+        const double nb = moments ? moments[0] : 0.0;
+        if (nb > 0.0) {
+            const double s1 = moments[1], s2 = moments[2];
+            const double mb = s1 / nb;                       // the batch's mean
+            const double m2b = s2 - s1 * mb;                 // its squared deviations from that mean
+            n = na + nb;
+            const double w = nb / n;
+            const double db = mb - mu;
+            mu = mu + db * w;
+            q = (q + (m2b > 0.0 ? m2b : 0.0)) + (db * db) * (na * w);
+            count[0] = n;
+            mean[0] = mu;
+            m2[0] = q;
+        }
+        float t0 = 0.0f, t1 = 1.0f, t2 = 1.0f;
+        double sigma_n = 0.0;
+        if (n > 0.0) {
+            sigma_n = sqrt(q / n + eps);
+            t0 = (float)mu;
+            t1 = (float)sigma_n;
+            t2 = (float)(1.0 / sigma_n);
+        }
+        table[0] = t0; table[1] = t1; table[2] = t2; table[3] = 0.0f;
+        if (norm8) {
+            norm8[2] = t0;
+            norm8[3] = t2;
+        }
+        s_pair[0] = mean_a; s_pair[1] = sigma_a; s_pair[2] = mu; s_pair[3] = sigma_n;
+        // (x > 0 && x <= DBL_MAX: a positive finite number -- false for NaN and for infinity)
+        s_rescale = nb > 0.0 && na > 0.0 && sigma_a > 0.0 && sigma_a <= 1.7976931348623157e308 && sigma_n > 0.0 &&
+                    sigma_n <= 1.7976931348623157e308;
+    }
+    __syncthreads();
+    if (!s_rescale) return;
+    const double sigma_a = s_pair[1], sigma_n = s_pair[3];
+    const double r = sigma_a / sigma_n;
+    for (int k = threadIdx.x; k < hidden; k += blockDim.x)
+        head_w[k] = (float)((double)head_w[k] * r);
+    if (threadIdx.x == 0)
+        head_b[0] = (float)(((double)head_b[0] * sigma_a + (s_pair[0] - s_pair[2])) / sigma_n);
+}
+
 // The privileged critic's input rows (tg_privileged_rows): a streaming pass in which a lane owns ONE 16-byte piece of a destination row --
 // a row is `dst_chunks` adjacent lanes, so a wave stores up to 1 KiB of consecutive bytes and loads the matching pieces of the source
 // rows (consecutive within a row, rows `src_chunks` pieces apart).  A workgroup takes kPrivGroups groups of 256 / dst_chunks whole rows
@@ -825,6 +888,18 @@ int tg_value_norm_merge(const double* d_moments3, double eps, double* d_count, d
     TG_REQUIRE(eps >= 0.0, "tg_value_norm_merge: eps %g < 0", eps);
     hipLaunchKernelGGL(value_norm_merge_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_moments3, eps, d_count, d_mean, d_m2, d_table, d_norm8);
     TG_LAUNCH_CHECK("tg_value_norm_merge");
+    return TG_OK;
+}
+
+int tg_value_norm_merge_popart(const double* d_moments3, double eps, double* d_count, double* d_mean, double* d_m2, float* d_table,
+                               float* d_norm8, float* d_head_w, int32_t hidden, float* d_head_b, void* stream) {
+    TG_REQUIRE(d_count && d_mean && d_m2 && d_table, "tg_value_norm_merge_popart: null pointer");
+    TG_REQUIRE(d_head_w && d_head_b, "tg_value_norm_merge_popart: null critic head");
+    TG_REQUIRE(eps >= 0.0, "tg_value_norm_merge_popart: eps %g < 0", eps);
+    TG_REQUIRE(hidden >= 1, "tg_value_norm_merge_popart: hidden %d < 1", hidden);
+    hipLaunchKernelGGL(value_norm_merge_popart_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, d_moments3, eps, d_count, d_mean, d_m2,
+                       d_table, d_norm8, d_head_w, (int)hidden, d_head_b);
+    TG_LAUNCH_CHECK("tg_value_norm_merge_popart");
     return TG_OK;
 }
 

@@ -240,6 +240,25 @@ def value_norm_merge(moments3, eps: float, count: torch.Tensor, mean: torch.Tens
                                          N.ptr(norm8), _st(table)), "tg_value_norm_merge")
 
 
+def value_norm_merge_popart(moments3, eps: float, count: torch.Tensor, mean: torch.Tensor, m2: torch.Tensor, table: torch.Tensor,
+                            norm8, head_w: torch.Tensor, head_b: torch.Tensor) -> None:
+    """tg_value_norm_merge_popart: value_norm_merge and, in the same launch, PopArt's rescale of the critic's last layer -- head_w f32
+    [1][H] and head_b f32 [1], the fp32 MASTERS, written in place by raw pointer (torch's version counters do not move: the caller
+    bumps N.RAW_PARAM_WRITES and marks the layouts derived from them stale)."""
+    N.require_cuda(moments3, count, mean, m2, table, norm8, head_w, head_b)
+    for t in (count, mean, m2):
+        assert t.dtype == torch.float64 and t.numel() == 1
+    assert moments3 is None or (moments3.dtype == torch.float64 and moments3.is_contiguous() and moments3.numel() == 3)
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.numel() == 4
+    assert norm8 is None or (norm8.dtype == torch.float32 and norm8.is_contiguous() and norm8.numel() == 8)
+    assert head_w.dtype == head_b.dtype == torch.float32 and head_w.is_contiguous() and head_b.is_contiguous()
+    assert head_w.dim() == 2 and head_w.shape[0] == 1 and head_w.shape[1] >= 1 and tuple(head_b.shape) == (1,)
+    assert head_w.device == head_b.device == count.device
+    N.check(N.load().tg_value_norm_merge_popart(N.ptr(moments3), float(eps), count.data_ptr(), mean.data_ptr(), m2.data_ptr(),
+                                                table.data_ptr(), N.ptr(norm8), head_w.data_ptr(), int(head_w.shape[1]),
+                                                head_b.data_ptr(), _st(table)), "tg_value_norm_merge_popart")
+
+
 def privileged_rows(src: torch.Tensor, S: int, idx, n: int, env_params: torch.Tensor, spec: "N.PrivilegedSpec", out: torch.Tensor,
                     ones_col: int = -1) -> torch.Tensor:
     """tg_privileged_rows: the privileged critic's input rows.  src [rows][src_pad] bf16 / f32 (the actor's prepared rows), out

@@ -10,7 +10,8 @@ algorithms.py).  The covariance is a diagonal matrix (actor_critic.py:100-103, :
 `learn_std=True` -- diag(exp(2 log_std)) of a learned per-dimension `log_std` parameter that the learners train on the device.
 With `normalize_obs=True` every path reads states through running per-feature statistics (`policy.obs_norm`, class ObsNorm).
 With `normalize_value=True` (actor-critic only) the critic predicts returns standardised with running statistics
-(`policy.value_norm`, class ValueNorm); `policy.value()` keeps returning returns.
+(`policy.value_norm`, class ValueNorm); `policy.value()` keeps returning returns.  With `popart=True` as well, PPO rescales the
+critic's last layer whenever those statistics move, so that the denormalised predictions stay where they were.
 """
 from __future__ import annotations
 
@@ -163,8 +164,7 @@ OBS_NORM_KEYS = ("obs_norm.count", "obs_norm.mean", "obs_norm.m2")
 
 
 class ValueNorm:
-    """Running statistics of the returns a critic is trained on (normalize_value=True; MAPPO's ValueNorm, "PopArt without the Pop":
-    the critic head is NOT rescaled when the statistics move), on the policy's device:
+    """Running statistics of the returns a critic is trained on (normalize_value=True; MAPPO's ValueNorm), on the policy's device:
         count, mean, m2 f64 [1] each (m2: sum of squared deviations; var = m2 / count is the population variance),
         table f32 [4] = {(float)mean, (float)sigma, (float)(1 / sigma), 0}, sigma = sqrt(m2 / count + eps) in f64 -- ONE allocation for
         the life of the policy, rewritten in place (count == 0: {0, 1, 1, 0}, the identity).
@@ -172,11 +172,18 @@ class ValueNorm:
     fp32 expressions of two separately rounded operations, on the device kernels and here alike.  PPO.learn() denormalises every
     critic value that enters a return with the table as it stands at its entry, then merges the batch's returns (unless frozen) and
     regresses the critic onto normalize(R) of the merged statistics.  `eps` is fixed at construction.  A deepcopy of a policy owns
-    its own statistics; the learners make their old_policy share the policy's object."""
+    its own statistics; the learners make their old_policy share the policy's object.
 
-    def __init__(self, eps: float, device):
+    popart=False (the default): the critic head is NOT rescaled when the statistics move -- the function the critic represents, read
+    in return units, jumps by (sigma' - sigma) v + (mean' - mean) at every merge.  popart=True (PopArt, "preserve outputs
+    precisely"): a merge that is handed the critic's last Linear rewrites it in the same step, w' = w sigma / sigma',
+    b' = (b sigma + mean - mean') / sigma', so that every denormalised prediction stays where it was ("PopArt").
+    Only _merge() with a head rescales; set() and load_state() never do (a checkpoint's weights and statistics already agree)."""
+
+    def __init__(self, eps: float, device, popart: bool = False):
         self._eps = float(eps)
         self.frozen = False
+        self.popart = bool(popart)
         dev = torch.device(device)
         self.count = torch.zeros(1, dtype=torch.float64, device=dev)
         self.mean = torch.zeros(1, dtype=torch.float64, device=dev)
@@ -207,16 +214,34 @@ class ValueNorm:
         return self
 
     @torch.no_grad()
-    def _merge(self, moments=None, norm8=None) -> None:
+    def _merge(self, moments=None, norm8=None, head=None) -> None:
         """Chan's merge of moments f64 [3] = {n_b, sum, sum of squares} of a batch of returns into the statistics, then the table in
         place and -- norm8 given (tg_ppo_norm's f32 [8]) -- its entries 2 and 3 <- table[0], table[2]: tg_value_norm_merge on the
-        device; the same operations in torch for a CPU policy (the host path)."""
+        device; the same operations in torch for a CPU policy (the host path).
+        head (the critic's last Linear, [1][H] weight and [1] bias in fp32; None: the plain merge): PopArt's rescale with the merge --
+        tg_value_norm_merge_popart on the device, which writes the masters by raw pointer (the caller sees to the derived layouts);
+        the same f64 operations in torch on the host.  The head keeps its bits when nothing was merged, when the statistics were
+        empty before the merge, or when either sigma is not a positive finite number."""
+        if head is not None:
+            w, b = head.weight, head.bias
+            if not (w.dtype == b.dtype == torch.float32 and w.is_contiguous() and b.is_contiguous() and w.dim() == 2 and w.shape[0] == 1
+                    and tuple(b.shape) == (1,) and w.device == b.device == self.count.device):
+                raise ValueError(f"PopArt rescales a contiguous fp32 head of weight [1][H] and bias [1] on {self.count.device}, got weight "
+                                 f"{w.dtype} {tuple(w.shape)} on {w.device}, bias {b.dtype} {tuple(b.shape)} on {b.device}")
         if self.count.is_cuda:
             from . import hip_ops as K
             with torch.cuda.device(self.count.device):
-                K.value_norm_merge(moments, self.eps, self.count, self.mean, self.m2, self.table, norm8)
+                if head is None:
+                    K.value_norm_merge(moments, self.eps, self.count, self.mean, self.m2, self.table, norm8)
+                else:
+                    K.value_norm_merge_popart(moments, self.eps, self.count, self.mean, self.m2, self.table, norm8, head.weight, head.bias)
             return
-        if moments is not None and float(moments[0]) > 0:
+        merged = moments is not None and float(moments[0]) > 0
+        if head is not None and merged and float(self.count[0]) > 0:
+            mean_a, sigma_a = self.mean.clone(), torch.sqrt(self.m2 / self.count + self.eps)
+        else:
+            head = None
+        if merged:
             na, nb, s1, s2 = self.count[0].clone(), moments[0], moments[1], moments[2]
             mb = s1 / nb
             m2b = (s2 - s1 * mb).clamp_min(0.0)
@@ -236,6 +261,12 @@ class ValueNorm:
         self.table[3] = 0.0
         if norm8 is not None:
             norm8[2], norm8[3] = self.table[0], self.table[2]
+        if head is not None:
+            sigma_n = torch.sqrt(self.m2 / self.count + self.eps)
+            if all(math.isfinite(float(s)) and float(s) > 0 for s in (sigma_a, sigma_n)):
+                # (every f64 operation a torch op of its own: rounded one by one, as the kernel's)
+                head.weight.copy_((head.weight.double() * (sigma_a / sigma_n)).float())
+                head.bias.copy_(((head.bias.double() * sigma_a + (mean_a - self.mean)) / sigma_n).float())
 
     @torch.no_grad()
     def set(self, mean, var, count) -> None:
@@ -553,9 +584,14 @@ class GaussianActorCritic_NeuralNetwork(_GaussianBase):
     has_critic = True
 
     def __init__(self, input_dim, output_dim, hidden_dims, activation="ReLU", cov=0.1, device=None, learn_std=False, *,
-                 normalize_obs=False, obs_clip=10.0, obs_eps=1e-8, normalize_value=False, value_eps=1e-8, privileged_critic=None):
+                 normalize_obs=False, obs_clip=10.0, obs_eps=1e-8, normalize_value=False, value_eps=1e-8, privileged_critic=None,
+                 popart=False):
         if not isinstance(normalize_value, bool):
             raise ValueError(f"normalize_value must be True or False, got {normalize_value!r}")
+        if not isinstance(popart, bool):
+            raise ValueError(f"popart must be True or False, got {popart!r}")
+        if popart and not normalize_value:
+            raise ValueError("popart=True rescales the critic head when the return statistics move: it needs normalize_value=True")
         if isinstance(value_eps, bool) or not isinstance(value_eps, (int, float)) or not (math.isfinite(value_eps) and value_eps >= 0):
             raise ValueError(f"value_eps must be a finite number >= 0, got {value_eps!r}")
         privileged_critic = _check_privileged(privileged_critic)
@@ -567,7 +603,8 @@ class GaussianActorCritic_NeuralNetwork(_GaussianBase):
         self.privileged_scale = [2.0 / (hi - lo) if hi > lo else 0.0 for lo, hi in (privileged_critic or {}).values()]
         self.critic = NeuralNetwork(input_dim + len(self.privileged_center), 1, hidden_dims, activation).to(self.device)
         # running value normalisation: None when off (the critic then predicts whatever its learner regresses it onto)
-        self.value_norm = ValueNorm(value_eps, self.device) if normalize_value else None
+        # (popart=True: PPO hands the merge the critic's last layer, which is then rescaled with the statistics)
+        self.value_norm = ValueNorm(value_eps, self.device, popart) if normalize_value else None
 
     def privileged_features(self, factors, shape=()) -> torch.Tensor:
         """The critic's privileged columns f32 [..., P] of multiplicative factors [..., P] in column order (None: the nominal vehicle,
@@ -611,6 +648,8 @@ class GaussianActorCritic_NeuralNetwork(_GaussianBase):
 
     def metadata(self):
         md = super().metadata()
+        if self.value_norm is not None and self.value_norm.popart:
+            md["popart"] = True
         if self.privileged_critic is not None:
             md["privileged_critic"] = {k: [lo, hi] for k, (lo, hi) in self.privileged_critic.items()}
         return md
