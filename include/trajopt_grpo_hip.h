@@ -922,6 +922,42 @@ int  tg_fused_rollout_f32_on(const tg_env_params* p, const double* d_ptab, const
                              int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, const float* d_obs_norm, float clip,
                              void* stream);
 
+/* ---- Control decimation: `substeps` physics steps per policy step (additions to ABI 13) ----
+ * An env with substeps = k applies each policy action for up to k consecutive calls of the env's own step and stops after the first
+ * call that reports `truncated`; call j (from 0) of control step t runs with steps_after = t k + j + 1.  Transition t of the
+ * trajectory holds the observation before the first call (slot t), the one sampled action, the state after the last executed call
+ * (slot t + 1; zeros when the episode ended), rew[t] = the left-to-right sum of the executed calls' rewards in the trajectory dtype
+ * (no contraction), and mask / len in CONTROL steps.  The Philox key stays (env, t) with t the control step: one policy evaluation
+ * and one draw per control step.
+ * `p` describes the PHYSICS clock: p->timestep is the physics step and p->max_steps = tr->horizon * substeps is required
+ * (TG_ERR_ARG otherwise; the entry points without `_sub` refuse such a `p` through their horizon == max_steps check).  Run
+ * tg_env_finalize_params on it.  t, t_begin and t_end count control steps.
+ * The identity the tests pin: such a rollout with forced actions a[t] is, bit for bit, the plain rollout of the same env with
+ * max_steps = k T driven with a[p / k] at physics step p and read at every k-th step.  substeps == 1 gives the bits of the sibling
+ * entry point.
+ * Each entry takes the arguments of its sibling plus `substeps`; d_ptab (the per-env parameter table of the `_dr` entries) and, for
+ * the fused ones, d_obs_norm / clip (tg_fused_rollout_on) may be NULL: one entry per path covers the crossings.
+ * tg_rollout_final_state_sub re-runs the last control step -- up to k calls from (obs[:, L-1], act[:, L-1]), starting at physics
+ *   count (L-1) k + 1: d_s_final is the state after the last executed call, timeout = !failed(s_final) && (time_rule(the count it
+ *   stopped at) || L == T).
+ * Limits, refused before any launch: substeps outside [1, 64] (TG_ERR_ARG); swarm envs, agents > 1 (TG_ERR_UNSUPPORTED: the bodies
+ * of an env would have to stop at the same physics step); Pendulum (TG_ERR_UNSUPPORTED: its balance terminal and the running count
+ * it keeps in len count single steps). */
+int  tg_rollout_step_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean,
+                         int64_t mean_row_stride, const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t substeps,
+                         void* stream);
+int  tg_rollout_forced_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end,
+                           int32_t substeps, void* stream);
+int  tg_rollout_final_state_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
+                                int32_t substeps, void* stream);
+int  tg_fused_rollout_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+                          int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                          int32_t t_begin, int32_t t_end, const float* d_obs_norm, float clip, int32_t substeps, void* stream);
+int  tg_fused_rollout_f32_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                              int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                              int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, const float* d_obs_norm, float clip,
+                              int32_t substeps, void* stream);
+
 /* ---- PPO's prologue (algorithms/ppo.py:93-139) without a host round trip ----
  * tg_scatter_rows: d_dst[d_idx[r]] = d_src[r * src_stride] for r < rows -- the critic's values of the valid rows (the no-grad
  *   forward's padded output, column 0) back onto the zeroed [T][n] grid (ppo.py:93 evaluated on the valid rows only).

@@ -5,7 +5,10 @@ epoch instead of 50-80.
     python3 tools/train_ppo.py [epochs] [CartPole|Pendulum|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
                                [--learn-std] [--normalize-obs] [--normalize-value] [--popart] [--gae] [--privileged-critic]
                                [--eval-every N] [--eval-episodes E] [--eval-sweep name=f1,f2,... ...] [--desired-kl KL]
-                               [--target-kl KL] [--kl-every N]
+                               [--target-kl KL] [--kl-every N] [--substeps K]
+
+--substeps K: control decimation (Env.substeps = K, 1..64): K physics steps of timestep / K per policy step, so the control period,
+the horizon in policy steps and the learner's cost stay what they are and only the integration gets finer.  Not for Pendulum.
 
 --desired-kl KL: the KL-adaptive learning rate (PPO(desired_kl=KL), e.g. 0.01): once per learn() the rate is divided by 1.5 when the
 measured KL between the policy before and after the updates exceeds 2 KL and multiplied by 1.5 when it is below KL / 2.
@@ -116,6 +119,11 @@ def main():
         kl_every = int(kl_every[-1]) if kl_every else None            # a check behind every kl_every-th update
     except ValueError:
         raise SystemExit("--target-kl expects a number, --kl-every an integer")
+    substeps, sys.argv[1:] = pop_valued(sys.argv[1:], "--substeps")
+    try:
+        substeps = int(substeps[-1]) if substeps else 1
+    except ValueError:
+        raise SystemExit("--substeps expects an integer")
     learn_std = "--learn-std" in sys.argv                         # a learned per-dimension log-std instead of the fixed covariance
     sys.argv = [a for a in sys.argv if a != "--learn-std"]
     normalize_obs = "--normalize-obs" in sys.argv                 # running observation normalisation (policy.obs_norm)
@@ -145,8 +153,16 @@ def main():
                                                **({"normalize_value": True} if normalize_value else {}),
                                                **({"popart": True} if popart else {}),
                                                **({"privileged_critic": ranges} if privileged else {}))
-    tg.environments.ENV_CLASSES[name]().randomize(ranges)         # (refuses a bad name or range before anything is allocated)
-    mgr = tg.RolloutManager(lambda: tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, num_workers=64, num_episodes_per_worker=64,
+
+    def make_env():
+        env = tg.environments.ENV_CLASSES[name]().randomize(ranges)
+        if substeps != 1:
+            env.substeps = substeps                               # (ValueError: Pendulum, or K outside 1..64)
+            env.timestep = env.timestep / substeps                # the control period stays the reference's
+        return env
+
+    make_env()                                                    # (refuses a bad name, range or K before anything is allocated)
+    mgr = tg.RolloutManager(make_env, pol, num_workers=64, num_episodes_per_worker=64,
                             seed=0, compute_dtype=cdt)
     buf = tg.Rollout_Buffer(mgr)
     algo = tg.PPO(epsilon=0.2, policy=pol, optimizer=torch.optim.Adam(pol.parameters(), lr=lr), ref_model=None,
@@ -155,7 +171,7 @@ def main():
                   **({"target_kl": target_kl} if target_kl is not None else {}), **({"kl_every": kl_every} if kl_every is not None else {}))
     evaluator = None
     if eval_every is not None:                                    # (refuses a bad sweep before the first epoch)
-        evaluator = tg.Evaluator(tg.environments.ENV_CLASSES[name]().randomize(ranges), pol, episodes=eval_episodes, sweep=eval_sweep,
+        evaluator = tg.Evaluator(make_env(), pol, episodes=eval_episodes, sweep=eval_sweep,
                                  seed=1, compute_dtype=cdt)
     t0 = time.time()
     for ep in range(epochs):

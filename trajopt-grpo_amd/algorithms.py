@@ -1362,14 +1362,19 @@ class PPO(_GpuLearner):
         each slot was rolled out with."""
         return getattr(buffer.rollout_manager.engine, "env_params", None)
 
-    def _bootstrap_values(self, params, traj, critic, m_c, env_params=None, priv=None):
+    @staticmethod
+    def _bootstrap_substeps(buffer):
+        """The physics steps per policy step the engine rolled out with (Env.substeps): the re-step runs the last CONTROL step."""
+        return int(getattr(buffer.rollout_manager.engine, "substeps", 1))
+
+    def _bootstrap_values(self, params, traj, critic, m_c, env_params=None, priv=None, substeps=1):
         """(b f32 [n], timeout u8 [n]): b[i] = V(s_final[i]) where the clock ended episode i, else 0 -- the re-step launch, the
         critic's input rows prepared as the valid rows are, one no-grad pass over n rows, one multiply.  Enqueued; no host read.
         priv (a privileged critic): the rows are prepared as the ACTOR's are and each gets its own env's parameters (row i is env i)."""
         n, dev = traj.n, traj.mask.device
         s_final, timeout = K.rollout_final_state(params, traj, self._small("boot_state", n * traj.S, torch.float32, dev).view(n, traj.S),
                                                  self._small("boot_timeout", n, torch.uint8, dev),
-                                                 env_params=env_params)
+                                                 env_params=env_params, **({"substeps": substeps} if substeps != 1 else {}))
         on = getattr(self.policy, "obs_norm", None)        # (this learn()'s table: the update ran at the entry)
         if priv is not None:
             m_a = self._mlp(self.policy.actor)
@@ -1393,6 +1398,7 @@ class PPO(_GpuLearner):
     def _learn(self, buffer) -> None:
         boot_params = self._bootstrap_params(buffer) if self.bootstrap_truncated else None
         boot_table = self._bootstrap_table(buffer) if self.bootstrap_truncated else None
+        boot_substeps = self._bootstrap_substeps(buffer) if self.bootstrap_truncated else 1
         traj = device_trajectory(buffer, self.policy.device)
         var = self.policy.var
         T, n = traj.T, traj.n
@@ -1451,7 +1457,7 @@ class PPO(_GpuLearner):
             moments = K.ppo_returns(rew, V, traj.mask, self.gamma, self.lam, self.monte_carlo, adv_full, ret_full, work)
         else:
             # time-limit bootstrapping: the same two launches on r + gamma * V(s_final) at each clock-ended episode's last step
-            boot, timeout = self._bootstrap_values(boot_params, traj, critic, m_c, env_params=boot_table, priv=priv)
+            boot, timeout = self._bootstrap_values(boot_params, traj, critic, m_c, env_params=boot_table, priv=priv, substeps=boot_substeps)
             moments = K.ppo_returns_boot(rew, V, traj.mask, traj.len, boot, self.gamma, self.lam, self.monte_carlo, adv_full, ret_full, work)
             n_boot = timeout.sum(dtype=torch.int64).reshape(1)              # (a new tensor: read when last_stats is)
             D.allreduce_sum_(n_boot, self.process_group, "n_bootstrapped")

@@ -75,12 +75,32 @@ template <typename Env> struct PerEnv : Env {
 template <typename Env> struct EnvTraits {
     static constexpr bool kPerEnv = false;
     static constexpr bool kObsNorm = false;
+    static constexpr bool kSubsteps = false;
     using Consts = typename Env::C;
 };
 template <typename Env> struct EnvTraits<PerEnv<Env>> {
     static constexpr bool kPerEnv = true;
     static constexpr bool kObsNorm = false;
+    static constexpr bool kSubsteps = false;
     using Consts = typename Env::C;
+};
+// Control decimation (the `_sub` entry points): `k` physics steps per policy step.  Substepped<Env> -- Env a plain env or PerEnv<...>,
+// and ObsNormed<> goes AROUND it -- rides on the Env type for PerEnv's reason: the kernel's argument becomes {Env's own argument, k},
+// its instantiation IS the kSubsteps = true kernel (the step call site runs substep_loop below in place of one Env::step), and every
+// existing instantiation keeps name and code.  The constants describe the PHYSICS clock (max_steps = horizon * k, dt = the physics
+// step); the kernel's t, T, the Philox key and len count control steps.
+template <typename BaseC> struct SubstepArg {
+    BaseC base;
+    int32_t k;
+};
+template <typename Env> struct Substepped : Env {
+    using C = SubstepArg<typename Env::C>;
+};
+template <typename Env> struct EnvTraits<Substepped<Env>> {
+    static constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
+    static constexpr bool kObsNorm = false;
+    static constexpr bool kSubsteps = true;
+    using Consts = typename EnvTraits<Env>::Consts;
 };
 // Running observation normalisation (the `_on` entry points of the fused rollouts).  ObsNormed<Env> -- Env a plain env or PerEnv<...>
 // -- rides on the Env type for PerEnv's reason: the kernel's argument becomes {Env's own argument, the f32 table [2][S] = {mean,
@@ -99,11 +119,16 @@ template <typename Env> struct ObsNormed : Env {
 template <typename Env> struct EnvTraits<ObsNormed<Env>> {
     static constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
     static constexpr bool kObsNorm = true;
+    static constexpr bool kSubsteps = EnvTraits<Env>::kSubsteps;
     using Consts = typename EnvTraits<Env>::Consts;
 };
 // the env's own kernel argument (by-value constants or the parameter table) inside whatever the kernel was handed
 template <typename C> __device__ static inline const C& env_arg(const C& c) { return c; }
-template <typename B> __device__ static inline const B& env_arg(const ObsNormArg<B>& c) { return c.base; }
+template <typename B> __device__ static inline const B& env_arg(const SubstepArg<B>& c) { return c.base; }
+template <typename B> __device__ static inline const auto& env_arg(const ObsNormArg<B>& c) { return env_arg(c.base); }
+// the physics steps per control step of a kSubsteps kernel, from the same argument
+template <typename B> __device__ static inline int substeps_of(const SubstepArg<B>& c) { return c.k; }
+template <typename B> __device__ static inline int substeps_of(const ObsNormArg<B>& c) { return substeps_of(c.base); }
 // The policy's view of a state: the table's 2 S floats, read once per launch (uniform addresses: scalar loads), and the one
 // definition of the normalised observation (obs_normalize, tg_common.hpp) applied to the register-resident state where it becomes
 // the first layer's operand.  The table is per FEATURE, not per env: a compaction that moves envs between lanes moves nothing here.
@@ -129,6 +154,42 @@ template <typename C> __device__ static inline const C& pick_constants(const C& 
 template <typename C> __device__ static inline const C& pick_constants(const PerEnvTable&, const C& own) { return own; }
 static inline PerEnvTable per_env_table(const tg_env_params* p, const double* d_ptab) {
     return PerEnvTable{d_ptab, p->timestep, p->max_steps, p->time_trunc_step};
+}
+
+// One control step of a kSubsteps kernel: the action `a` applied for up to `k` consecutive calls of the env's own Env::step, call j
+// (from 0) of control step t with steps_after = t k + j + 1, stopping after the first call that reports `truncated`.  Returns the
+// last executed call's StepOut, with its state in `o`, the left-to-right sum of the executed calls' rewards in `reward` (in R,
+// contraction off) and the physics count it stopped at in `count`.  The loop is wave-uniform: a lane that has stopped (or never ran:
+// `alive` false) sits the remaining calls out, and the wave leaves when none of its lanes runs.  k = 1 is one Env::step, bit for bit.
+template <typename Env, typename R, typename C>
+__device__ static inline StepOut substep_loop(const R (&s)[Env::S], const float (&a)[Env::A], const C& c, int t, int k, bool alive,
+                                              R (&o)[Env::S], R& reward, int& count) {
+#pragma clang fp contract(off)
+    constexpr int S = Env::S;
+#pragma unroll
+    for (int i = 0; i < S; ++i) o[i] = s[i];
+    StepOut out;
+    out.truncated = false; out.balanced = false;
+    R sum = (R)0;
+    int cnt = t * k;
+    bool running = alive;
+#pragma clang loop unroll(disable)
+    for (int j = 0; j < k; ++j) {
+        if (__ballot(running) == 0ull) break;
+        R nx[S], r;
+        const StepOut so = Env::step(o, a, c, t * k + j + 1, nx, r);
+        if (running) {
+            out = so;
+            sum = (j == 0) ? r : sum + r;
+            cnt = t * k + j + 1;
+#pragma unroll
+            for (int i = 0; i < S; ++i) o[i] = nx[i];
+        }
+        running = running && !so.truncated;
+    }
+    reward = sum;
+    count = cnt;
+    return out;
 }
 
 // ---------------------------------------------------------------------------

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c_arg
     const int32_t my_len = len[ic];
     constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;        // (domain randomisation: Env = PerEnv<...>, c_arg = the parameter table)
     typename EnvTraits<Env>::Consts own;
-    if constexpr (kPerEnv && kSpec) own = env_constants<Env>(c_arg, n, ic);
+    if constexpr (kPerEnv && kSpec) own = env_constants<Env>(env_arg(c_arg), n, ic);
     if constexpr (kSpec) {
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = obs[(k * T1 + t) * n + ic];
@@ -139,8 +139,8 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c_arg
     // wavefront-wide termination: if all 64 envs of this wave have ended, leave before touching the
     // trajectory again (wave-uniform branch, no divergence)
     if (__ballot(alive) == 0ull) return;
-    if constexpr (kPerEnv && !kSpec) own = env_constants<Env>(c_arg, n, ic);
-    const auto& c = pick_constants(c_arg, own);
+    if constexpr (kPerEnv && !kSpec) own = env_constants<Env>(env_arg(c_arg), n, ic);
+    const auto& c = pick_constants(env_arg(c_arg), own);
     if constexpr (!kSpec) {
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = alive ? obs[(k * T1 + t) * n + ic] : (R)0;
@@ -172,7 +172,13 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c_arg
     }
 
     R r;
-    const StepOut out = Env::step(s, a, c, t + 1, o, r);
+    StepOut out;
+    if constexpr (EnvTraits<Env>::kSubsteps) {               // (control decimation: up to k calls of Env::step, rewards summed)
+        int count;
+        out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
+    } else {
+        out = Env::step(s, a, c, t + 1, o, r);
+    }
     // the worker also stops at t == max_steps (rollout_worker.py:51); a swarm stops when any of its bodies does
     bool ended = out.truncated;
     int balanced_steps = 0;
@@ -222,8 +228,8 @@ __global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c_ar
     const int64_t T1 = (int64_t)T + 1;
     constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;        // (domain randomisation: Env = PerEnv<...>, c_arg = the parameter table)
     typename EnvTraits<Env>::Consts own;
-    if constexpr (kPerEnv) own = env_constants<Env>(c_arg, n, ic);   // this lane's vehicle, for all the steps of the range
-    const auto& c = pick_constants(c_arg, own);
+    if constexpr (kPerEnv) own = env_constants<Env>(env_arg(c_arg), n, ic);   // this lane's vehicle, for all the steps of the range
+    const auto& c = pick_constants(env_arg(c_arg), own);
     int32_t my_len = len[ic];
     bool alive = in_range && (Env::kBalanceTerminates ? my_len <= 0 : my_len == 0);
     R s[S];
@@ -250,7 +256,13 @@ __global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c_ar
             for (int k = 0; k < A; ++k) a[k] = ab[q][k];
             load_actions(t + kForcedAhead, ab[q]);
             R o[S], r;
-            const StepOut out = Env::step(s, a, c, t + 1, o, r);
+            StepOut out;
+            if constexpr (EnvTraits<Env>::kSubsteps) {
+                int count;
+                out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
+            } else {
+                out = Env::step(s, a, c, t + 1, o, r);
+            }
             bool ended = out.truncated;
             int balanced_steps = 0;
             if constexpr (Env::kBalanceTerminates) {
@@ -292,8 +304,8 @@ __global__ __launch_bounds__(256) void final_state_kernel(typename Env::C c_arg,
     if (i >= n) return;
     constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;        // (domain randomisation: Env = PerEnv<...>, c_arg = the parameter table)
     typename EnvTraits<Env>::Consts own;
-    if constexpr (kPerEnv) own = env_constants<Env>(c_arg, n, i);
-    const auto& c = pick_constants(c_arg, own);
+    if constexpr (kPerEnv) own = env_constants<Env>(env_arg(c_arg), n, i);
+    const auto& c = pick_constants(env_arg(c_arg), own);
     const int64_t T1 = (int64_t)T + 1;
     const int32_t L = len[i];
     const bool ended = L >= 1 && L <= T;
@@ -305,10 +317,12 @@ __global__ __launch_bounds__(256) void final_state_kernel(typename Env::C c_arg,
 #pragma unroll
     for (int k = 0; k < A; ++k) a[k] = act[((int64_t)k * T + t) * n + i];
     R r;
-    (void)Env::step(s, a, c, t + 1, o, r);
+    int count = L;                                            // the clock the time rule reads: physics steps under kSubsteps
+    if constexpr (EnvTraits<Env>::kSubsteps) (void)substep_loop<Env>(s, a, c, t, substeps_of(c_arg), true, o, r, count);
+    else (void)Env::step(s, a, c, t + 1, o, r);
 #pragma unroll
     for (int k = 0; k < S; ++k) s_final[i * S + k] = ended ? (float)o[k] : 0.0f;
-    timeout[i] = (ended && !Env::failed(o, c) && (Env::time_rule(L, c) || L == T)) ? 1 : 0;
+    timeout[i] = (ended && !Env::failed(o, c) && (Env::time_rule(count, c) || L == T)) ? 1 : 0;
 }
 
 // sum of episode lengths (= env-steps executed = sum of mask) and #episodes ended.  A non-positive len is a slot whose episode has
@@ -536,6 +550,82 @@ static int final_state_dispatch(const tg_env_params* p, const double* d_ptab, co
     TG_LAUNCH_CHECK("tg_rollout_final_state");
     return TG_OK;
 }
+
+// ---- control decimation (the `_sub` entry points): the kernels' Substepped instantiations, argument {constants or table, k} ----
+template <template <typename> class EnvT, typename R>
+static int rollout_dispatch_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* mean, int64_t mean_rs,
+                                const float* sigma, const uint64_t* rng, int64_t env_offset, int32_t k, hipStream_t st) {
+    int block;
+    dim3 grid = env_grid(tr->n, block);
+    const SubstepArg<typename EnvT<R>::C> c{EnvT<R>::C::make(*p), k};
+    const SubstepArg<PerEnvTable> pe{per_env_table(p, d_ptab), k};
+    Sigma sg;
+    memset(&sg, 0, sizeof(sg));
+    const bool spec = tr->n <= ((int64_t)1 << 18);
+#define TG_RS(SAMPLE, SPEC)                                                                                            \
+    if (d_ptab != nullptr)                                                                                             \
+        hipLaunchKernelGGL((rollout_step_kernel<Substepped<PerEnv<EnvT<R>>>, R, SAMPLE, SPEC>), grid, dim3(block), 0, st, pe, (R*)tr->d_obs, \
+                           tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs, sg, rng, \
+                           env_offset, p->agents);                                                                     \
+    else                                                                                                               \
+        hipLaunchKernelGGL((rollout_step_kernel<Substepped<EnvT<R>>, R, SAMPLE, SPEC>), grid, dim3(block), 0, st, c, (R*)tr->d_obs,  \
+                           tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs, sg, rng, \
+                           env_offset, p->agents)
+    if (mean != nullptr) {
+        for (int q = 0; q < EnvT<R>::A; ++q) sg.v[q] = sigma[q];
+        if (spec) { TG_RS(true, true); } else { TG_RS(true, false); }
+    } else {
+        if (spec) { TG_RS(false, true); } else { TG_RS(false, false); }
+    }
+#undef TG_RS
+    TG_LAUNCH_CHECK("tg_rollout_step_sub");
+    return TG_OK;
+}
+
+template <template <typename> class EnvT, typename R>
+static int forced_dispatch_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, int32_t k,
+                               hipStream_t st) {
+    const dim3 grid((unsigned)ceil_div(tr->n, 64));
+    if (d_ptab != nullptr)
+        hipLaunchKernelGGL((rollout_forced_kernel<Substepped<PerEnv<EnvT<R>>>, R>), grid, dim3(64), 0, st,
+                           SubstepArg<PerEnvTable>{per_env_table(p, d_ptab), k}, (R*)tr->d_obs, (const float*)tr->d_act, (R*)tr->d_rew, tr->d_mask,
+                           tr->d_len, tr->n, tr->horizon, t_begin, t_end, p->agents);
+    else
+        hipLaunchKernelGGL((rollout_forced_kernel<Substepped<EnvT<R>>, R>), grid, dim3(64), 0, st,
+                           SubstepArg<typename EnvT<R>::C>{EnvT<R>::C::make(*p), k}, (R*)tr->d_obs, (const float*)tr->d_act, (R*)tr->d_rew,
+                           tr->d_mask, tr->d_len, tr->n, tr->horizon, t_begin, t_end, p->agents);
+    TG_LAUNCH_CHECK("tg_rollout_forced_sub");
+    return TG_OK;
+}
+
+template <template <typename> class EnvT, typename R>
+static int final_state_dispatch_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* s_final, uint8_t* timeout, int32_t k,
+                                    hipStream_t st) {
+    int block;
+    dim3 grid = env_grid(tr->n, block);
+    if (d_ptab != nullptr)
+        hipLaunchKernelGGL((final_state_kernel<Substepped<PerEnv<EnvT<R>>>, R>), grid, dim3(block), 0, st,
+                           SubstepArg<PerEnvTable>{per_env_table(p, d_ptab), k}, (const R*)tr->d_obs, (const float*)tr->d_act,
+                           (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
+    else
+        hipLaunchKernelGGL((final_state_kernel<Substepped<EnvT<R>>, R>), grid, dim3(block), 0, st,
+                           SubstepArg<typename EnvT<R>::C>{EnvT<R>::C::make(*p), k}, (const R*)tr->d_obs, (const float*)tr->d_act,
+                           (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
+    TG_LAUNCH_CHECK("tg_rollout_final_state_sub");
+    return TG_OK;
+}
+
+// (no Pendulum: substeps_check refuses it before any launch)
+#define TG_ENV_SWITCH_SUB(env_id, dtype, CALL)                                                 \
+    switch ((env_id) * 2 + (dtype)) {                                                          \
+        case TG_ENV_CARTPOLE * 2 + TG_F32: return CALL(CartPoleEnv, float);                    \
+        case TG_ENV_CARTPOLE * 2 + TG_F64: return CALL(CartPoleEnv, double);                   \
+        case TG_ENV_QUADPOLE2D * 2 + TG_F32: return CALL(QuadPole2DEnv, float);                \
+        case TG_ENV_QUADPOLE2D * 2 + TG_F64: return CALL(QuadPole2DEnv, double);               \
+        case TG_ENV_QUADPOLE * 2 + TG_F32: return CALL(QuadPoleEnv, float);                    \
+        case TG_ENV_QUADPOLE * 2 + TG_F64: return CALL(QuadPoleEnv, double);                   \
+        default: return set_error(TG_ERR_UNSUPPORTED, "unsupported env_id %d / dtype %d", (int)(env_id), (int)(dtype)); \
+    }
 
 #define TG_ENV_SWITCH(env_id, dtype, CALL)                                                     \
     switch ((env_id) * 2 + (dtype)) {                                                          \
@@ -805,6 +895,45 @@ int tg_rollout_final_state_dr(const tg_env_params* p, const double* d_ptab, cons
                               void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_rollout_final_state_dr: null parameter table");
     return final_state_impl(p, d_ptab, tr, d_s_final, d_timeout, stream);
+}
+
+// ---- control decimation: `p` describes the PHYSICS clock (p->max_steps = tr->horizon * substeps), t / t_begin / t_end count control steps ----
+int tg_rollout_step_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean, int64_t mean_row_stride,
+                        const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t substeps, void* stream) {
+    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_rollout_step_sub: null pointer");
+    if (int rc = substeps_check("tg_rollout_step_sub", p, tr, substeps)) return rc;
+    TG_REQUIRE(tr->n > 0 && t >= 0 && t < tr->horizon, "tg_rollout_step_sub: t=%d outside horizon %d", t, tr->horizon);
+    if (d_mean != nullptr) {
+        int S, A;
+        tg_env_dims(p->env_id, &S, &A);
+        TG_REQUIRE(sigma != nullptr && d_rng != nullptr, "tg_rollout_step_sub: sampling needs sigma and d_rng");
+        TG_REQUIRE(mean_row_stride >= A, "tg_rollout_step_sub: mean_row_stride %lld < act_dim %d", (long long)mean_row_stride, A);
+    }
+#define CALL(E, R) rollout_dispatch_sub<E, R>(p, d_ptab, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, substeps, (hipStream_t)stream)
+    TG_ENV_SWITCH_SUB(p->env_id, tr->dtype, CALL)
+#undef CALL
+}
+
+int tg_rollout_forced_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, int32_t substeps,
+                          void* stream) {
+    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_rollout_forced_sub: null pointer");
+    if (int rc = substeps_check("tg_rollout_forced_sub", p, tr, substeps)) return rc;
+    TG_REQUIRE(tr->n > 0 && t_begin >= 0 && t_begin <= t_end && t_end <= tr->horizon, "tg_rollout_forced_sub: steps [%d, %d) outside horizon %d",
+               t_begin, t_end, tr->horizon);
+    if (t_begin == t_end) return TG_OK;
+#define CALL(E, R) forced_dispatch_sub<E, R>(p, d_ptab, tr, t_begin, t_end, substeps, (hipStream_t)stream)
+    TG_ENV_SWITCH_SUB(p->env_id, tr->dtype, CALL)
+#undef CALL
+}
+
+int tg_rollout_final_state_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
+                               int32_t substeps, void* stream) {
+    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_len && d_s_final && d_timeout, "tg_rollout_final_state_sub: null pointer");
+    if (int rc = substeps_check("tg_rollout_final_state_sub", p, tr, substeps)) return rc;
+    TG_REQUIRE(tr->n > 0, "tg_rollout_final_state_sub: bad sizes n=%lld T=%d", (long long)tr->n, tr->horizon);
+#define CALL(E, R) final_state_dispatch_sub<E, R>(p, d_ptab, tr, d_s_final, d_timeout, substeps, (hipStream_t)stream)
+    TG_ENV_SWITCH_SUB(p->env_id, tr->dtype, CALL)
+#undef CALL
 }
 
 int tg_rollout_finish(const tg_traj* tr, void* stream) {

@@ -319,7 +319,13 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
             for (int k = 0; k < A; ++k) a[k] = rn_add(mu[k], rn_mul(sigma.v[k], eps[k]));
         }
         float o[S], r;
-        const StepOut out = Env::step(s, a, c, t + 1, o, r);
+        StepOut out;
+        if constexpr (EnvTraits<Env>::kSubsteps) {           // (control decimation: up to k calls of Env::step, rewards summed)
+            int count;
+            out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
+        } else {
+            out = Env::step(s, a, c, t + 1, o, r);
+        }
         bool ended = out.truncated;
         if constexpr (Env::kBalanceTerminates) {
             balanced_steps = out.balanced ? balanced_steps + 1 : 0;
@@ -394,6 +400,44 @@ static int fused_launch(const tg_env_params* p, const double* d_ptab, const floa
     return TG_OK;
 }
 
+// ---- control decimation (tg_fused_rollout_sub): the Substepped instantiations, ObsNormed<> around them when the table is given ----
+template <typename EnvK, int H, int NT, int WPW>
+static int fused_launch_sub_one(const typename EnvK::C& arg, size_t shmem, const tg_traj* tr, const void* wfrag, const float* bias, int n_hh,
+                                const SigmaF& sg, const uint64_t* rng, int64_t env_offset, int t0, int t1, int agents, hipStream_t st) {
+    auto kern = fused_rollout_kernel<EnvK, H, NT, WPW>;
+    static LdsOptIn opt_in;                            // (one per instantiation of this template: one per kernel)
+    if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_fused_rollout_sub")) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(tr->n, 32 * NT * WPW)), dim3(64 * WPW), shmem, st, arg, (float*)tr->d_obs, tr->d_act,
+                       (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg, rng, env_offset,
+                       agents);
+    TG_LAUNCH_CHECK("tg_fused_rollout_sub");
+    return TG_OK;
+}
+
+template <template <typename> class EnvT, int H, int NT, int WPW>
+static int fused_launch_sub(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, int32_t k, const tg_traj* tr,
+                            const void* wfrag, const float* bias, int n_hh, const float* sigma, const uint64_t* rng, int64_t env_offset, int t0,
+                            int t1, hipStream_t st) {
+    using Env = EnvT<float>;
+    constexpr int KS = H / 16;
+    SigmaF sg;
+    memset(&sg, 0, sizeof(sg));
+    for (int q = 0; q < Env::A; ++q) sg.v[q] = sigma[q];
+    const size_t shmem = (size_t)((NT == 1 && WPW == 4) ? 3 : 4) * KS * 1024 + (size_t)(n_hh + 2) * H * sizeof(float) +
+                         (size_t)WPW * 64 * 32 * 2 + 4 * WPW;
+    const SubstepArg<typename Env::C> c{Env::C::make(*p), k};
+    const SubstepArg<PerEnvTable> pe{per_env_table(p, d_ptab), k};
+    const ObsNormTable on{d_obs_norm, clip};
+#define TG_SUB_TAIL shmem, tr, wfrag, bias, n_hh, sg, rng, env_offset, t0, t1, p->agents, st
+    if (d_obs_norm != nullptr && d_ptab != nullptr)
+        return fused_launch_sub_one<ObsNormed<Substepped<PerEnv<Env>>>, H, NT, WPW>(ObsNormArg<SubstepArg<PerEnvTable>>{pe, on}, TG_SUB_TAIL);
+    if (d_obs_norm != nullptr)
+        return fused_launch_sub_one<ObsNormed<Substepped<Env>>, H, NT, WPW>(ObsNormArg<SubstepArg<typename Env::C>>{c, on}, TG_SUB_TAIL);
+    if (d_ptab != nullptr) return fused_launch_sub_one<Substepped<PerEnv<Env>>, H, NT, WPW>(pe, TG_SUB_TAIL);
+    return fused_launch_sub_one<Substepped<Env>, H, NT, WPW>(c, TG_SUB_TAIL);
+#undef TG_SUB_TAIL
+}
+
 }  // namespace tg
 
 using namespace tg;
@@ -458,6 +502,40 @@ int tg_fused_rollout_on(const tg_env_params* p, const double* d_ptab, const tg_t
     TG_REQUIRE(clip > 0.0f, "tg_fused_rollout_on: clip %g (a number > 0; +inf: no clamp)", (double)clip);
     return fused_rollout_impl(p, d_ptab, d_obs_norm, clip, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end,
                               stream);
+}
+
+int tg_fused_rollout_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+                         int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                         int32_t t_begin, int32_t t_end, const float* d_obs_norm, float clip, int32_t substeps, void* stream) {
+    TG_REQUIRE(p && tr && d_wfrag && d_bias && sigma && d_rng, "tg_fused_rollout_sub: null pointer");
+    TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_fused_rollout_sub: null trajectory pointer");
+    if (int rc = substeps_check("tg_fused_rollout_sub", p, tr, substeps)) return rc;
+    TG_REQUIRE(d_obs_norm == nullptr || clip > 0.0f, "tg_fused_rollout_sub: clip %g (a number > 0; +inf: no clamp)", (double)clip);
+    TG_REQUIRE(tr->dtype == TG_F32, "tg_fused_rollout_sub: float32 trajectories only");
+    TG_REQUIRE(tr->n > 0 && 0 <= t_begin && t_begin <= t_end && t_end <= tr->horizon, "tg_fused_rollout_sub: bad step range [%d, %d)", t_begin,
+               t_end);
+    TG_REQUIRE(n_hidden_layers >= 1 && n_hidden_layers <= 16, "tg_fused_rollout_sub: %d hidden layers unsupported", n_hidden_layers);
+    if (t_begin == t_end) return TG_OK;
+    const int n_hh = n_hidden_layers - 1;
+    hipStream_t st = (hipStream_t)stream;
+    const int variant = tr->n < 32768 ? 1 : 0;          // (tg_fused_rollout's choice)
+#define CALL(E, HH)                                                                                                                          \
+    (variant == 0 ? fused_launch_sub<E, HH, 1, 8>(p, d_ptab, d_obs_norm, clip, substeps, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, \
+                                                  t_begin, t_end, st)                                                                        \
+                  : fused_launch_sub<E, HH, 1, 4>(p, d_ptab, d_obs_norm, clip, substeps, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, \
+                                                  t_begin, t_end, st))
+    switch (p->env_id * 1000 + hidden) {
+        case TG_ENV_CARTPOLE * 1000 + 128: return CALL(CartPoleEnv, 128);
+        case TG_ENV_CARTPOLE * 1000 + 256: return CALL(CartPoleEnv, 256);
+        case TG_ENV_QUADPOLE2D * 1000 + 128: return CALL(QuadPole2DEnv, 128);
+        case TG_ENV_QUADPOLE2D * 1000 + 256: return CALL(QuadPole2DEnv, 256);
+        case TG_ENV_QUADPOLE * 1000 + 128: return CALL(QuadPoleEnv, 128);
+        case TG_ENV_QUADPOLE * 1000 + 256: return CALL(QuadPoleEnv, 256);
+        default:
+            return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_sub: env %d with hidden width %d is not instantiated "
+                             "(widths 128 and 256)", p->env_id, hidden);
+    }
+#undef CALL
 }
 
 }  // extern "C"

@@ -190,7 +190,13 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
             for (int k = 0; k < A; ++k) a[k] = rn_add(mu[k], rn_mul(sigma.v[k], eps[k]));
         }
         float o[S], r;
-        const StepOut out = Env::step(s, a, c, t + 1, o, r);
+        StepOut out;
+        if constexpr (EnvTraits<Env>::kSubsteps) {           // (control decimation: up to k calls of Env::step, rewards summed)
+            int count;
+            out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
+        } else {
+            out = Env::step(s, a, c, t + 1, o, r);
+        }
         bool ended = out.truncated;
         if constexpr (Env::kBalanceTerminates) {
             balanced_steps = out.balanced ? balanced_steps + 1 : 0;
@@ -392,7 +398,13 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
 #pragma unroll
         for (int k = 0; k < A; ++k) a[k] = rn_add(mu[k], rn_mul(sigma.v[k], eps[k]));
         float o[S], r;
-        const StepOut out = Env::step(s, a, c, t + 1, o, r);
+        StepOut out;
+        if constexpr (EnvTraits<Env>::kSubsteps) {           // (control decimation: up to k calls of Env::step, rewards summed)
+            int count;
+            out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
+        } else {
+            out = Env::step(s, a, c, t + 1, o, r);
+        }
         bool ended = out.truncated;
         if constexpr (Env::kBalanceTerminates) {
             balanced_steps = out.balanced ? balanced_steps + 1 : 0;
@@ -466,6 +478,61 @@ static int fused_f32_dispatch(int hidden, int n_hh, const tg_env_params* p, cons
     }
 #undef TG_F32_CASE
     return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_f32: hidden width %d with %d hidden layers is not instantiated "
+                     "(widths 64 / 128, 1..4 hidden layers)", hidden, n_hh + 1);
+}
+
+// ---- control decimation (tg_fused_rollout_f32_sub): the Substepped instantiations, ObsNormed<> around them when the table is given ----
+template <template <typename> class EnvT, int H, int NHH, int kAct>
+static int fused_f32_launch_sub(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, int32_t k, const tg_traj* tr,
+                                const float* wstream, const float* tab, const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1,
+                                int block_envs, hipStream_t st) {
+    using Env = EnvT<float>;
+    constexpr int WPW = H / 32, A = Env::A;
+    SigmaF32 sg;
+    memset(&sg, 0, sizeof(sg));
+    for (int q = 0; q < A; ++q) sg.v[q] = sigma[q];
+    const SubstepArg<typename Env::C> c{Env::C::make(*p), k};
+    const SubstepArg<PerEnvTable> pe{per_env_table(p, d_ptab), k};
+    const ObsNormTable on{d_obs_norm, clip};
+#define TG_F32_TAIL                                                                                                                     \
+    (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset, \
+        p->agents
+#define TG_F32_LAUNCH(KERNEL, ENVS)                                                                                                           \
+    do {                                                                                                                                      \
+        const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * ENVS + 2 * A * (64 / ENVS) * WPW * ENVS);           \
+        const dim3 grid((unsigned)ceil_div(tr->n, ENVS));                                                                                     \
+        if (d_obs_norm != nullptr && d_ptab != nullptr)                                                                                       \
+            hipLaunchKernelGGL((KERNEL<ObsNormed<Substepped<PerEnv<Env>>>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st,                   \
+                               ObsNormArg<SubstepArg<PerEnvTable>>{pe, on}, TG_F32_TAIL);                                                     \
+        else if (d_obs_norm != nullptr)                                                                                                       \
+            hipLaunchKernelGGL((KERNEL<ObsNormed<Substepped<Env>>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st,                           \
+                               ObsNormArg<SubstepArg<typename Env::C>>{c, on}, TG_F32_TAIL);                                                  \
+        else if (d_ptab != nullptr)                                                                                                           \
+            hipLaunchKernelGGL((KERNEL<Substepped<PerEnv<Env>>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, pe, TG_F32_TAIL);            \
+        else                                                                                                                                  \
+            hipLaunchKernelGGL((KERNEL<Substepped<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, TG_F32_TAIL);                     \
+    } while (0)
+    if (block_envs == 16) TG_F32_LAUNCH(fused_rollout_f32x16_kernel, 16);
+    else TG_F32_LAUNCH(fused_rollout_f32_kernel, 32);
+#undef TG_F32_TAIL
+#undef TG_F32_LAUNCH
+    TG_LAUNCH_CHECK("tg_fused_rollout_f32_sub");
+    return TG_OK;
+}
+
+template <template <typename> class EnvT, int kAct>
+static int fused_f32_dispatch_sub(int hidden, int n_hh, const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, int32_t k,
+                                  const tg_traj* tr, const float* wstream, const float* tab, const float* sigma, const uint64_t* rng,
+                                  int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
+#define TG_F32_CASE(HH, NN) \
+    case HH * 10 + NN: return fused_f32_launch_sub<EnvT, HH, NN, kAct>(p, d_ptab, d_obs_norm, clip, k, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
+    switch (hidden * 10 + n_hh) {
+        TG_F32_CASE(64, 0) TG_F32_CASE(64, 1) TG_F32_CASE(64, 2) TG_F32_CASE(64, 3)
+        TG_F32_CASE(128, 0) TG_F32_CASE(128, 1) TG_F32_CASE(128, 2) TG_F32_CASE(128, 3)
+        default: break;
+    }
+#undef TG_F32_CASE
+    return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_f32_sub: hidden width %d with %d hidden layers is not instantiated "
                      "(widths 64 / 128, 1..4 hidden layers)", hidden, n_hh + 1);
 }
 
@@ -552,6 +619,36 @@ int tg_fused_rollout_f32_on(const tg_env_params* p, const double* d_ptab, const 
     TG_REQUIRE(clip > 0.0f, "tg_fused_rollout_f32_on: clip %g (a number > 0; +inf: no clamp)", (double)clip);
     return fused_rollout_f32(p, d_ptab, d_obs_norm, clip, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset,
                              t_begin, t_end, activation, stream);
+}
+
+int tg_fused_rollout_f32_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                             int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                             int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, const float* d_obs_norm, float clip,
+                             int32_t substeps, void* stream) {
+    TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "tg_fused_rollout_f32_sub: unknown activation %d", activation);
+    TG_REQUIRE(p && tr && d_wstream && d_tab && sigma && d_rng, "tg_fused_rollout_f32_sub: null pointer");
+    TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_fused_rollout_f32_sub: null trajectory pointer");
+    if (int rc = substeps_check("tg_fused_rollout_f32_sub", p, tr, substeps)) return rc;
+    TG_REQUIRE(d_obs_norm == nullptr || clip > 0.0f, "tg_fused_rollout_f32_sub: clip %g (a number > 0; +inf: no clamp)", (double)clip);
+    TG_REQUIRE(tr->dtype == TG_F32, "tg_fused_rollout_f32_sub: float32 trajectories only");
+    TG_REQUIRE(tr->n > 0 && 0 <= t_begin && t_begin <= t_end && t_end <= tr->horizon, "tg_fused_rollout_f32_sub: bad step range [%d, %d)",
+               t_begin, t_end);
+    TG_REQUIRE(block_envs == 16 || block_envs == 32, "tg_fused_rollout_f32_sub: %d envs per workgroup (16 or 32: the layout of d_wstream)",
+               block_envs);
+    if (t_begin == t_end) return TG_OK;
+    const int n_hh = n_hidden_layers - 1;
+    hipStream_t st = (hipStream_t)stream;
+    switch (activation * 16 + p->env_id) {
+#define TG_F32_ENV(ACT, ID, ENV)                                                                                                      \
+    case ACT * 16 + ID:                                                                                                               \
+        return fused_f32_dispatch_sub<ENV, ACT>(hidden, n_hh, p, d_ptab, d_obs_norm, clip, substeps, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
+        TG_F32_ENV(TG_ACT_RELU, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
+        TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE, QuadPoleEnv)
+        TG_F32_ENV(TG_ACT_TANH, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
+        TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE, QuadPoleEnv)
+#undef TG_F32_ENV
+        default: return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_f32_sub: env %d is not instantiated", p->env_id);
+    }
 }
 
 }  // extern "C"

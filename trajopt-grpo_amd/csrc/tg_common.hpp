@@ -137,6 +137,20 @@ static inline int learned_std_check(const tg_learned_std* std, bool critic, int 
     if (act_dim < 1 || act_dim > 4) return set_error(TG_ERR_ARG, "%s: a learned log-std needs 1..4 action dimensions, got %d", who, act_dim);
     return 1;
 }
+// The control decimation of a `_sub` entry point: 0 = accepted, < 0 = refused (nothing is launched).  `p` describes the physics clock.
+static inline int substeps_check(const char* who, const tg_env_params* p, const tg_traj* tr, int32_t substeps) {
+    if (substeps < 1 || substeps > 64) return set_error(TG_ERR_ARG, "%s: substeps=%d outside [1, 64]", who, substeps);
+    if (p->agents > 1)
+        return set_error(TG_ERR_UNSUPPORTED, "%s: swarm envs (agents=%d) are not supported: the bodies of an env would have to stop at the "
+                         "same physics step", who, p->agents);
+    if (p->env_id == TG_ENV_PENDULUM)
+        return set_error(TG_ERR_UNSUPPORTED, "%s: Pendulum is not supported: its balance terminal and the running count kept in len "
+                         "count single steps", who);
+    if (tr->horizon <= 0 || (int64_t)tr->horizon * substeps != (int64_t)p->max_steps)
+        return set_error(TG_ERR_ARG, "%s: trajectory horizon %d x substeps %d != env.max_steps %d (the params describe the physics clock)",
+                         who, tr->horizon, substeps, p->max_steps);
+    return TG_OK;
+}
 struct LdsOptIn { size_t bytes[kMaxDevices] = {}; };
 static inline int reserve_dynamic_lds(const void* kernel, size_t bytes, LdsOptIn& cache, const char* what) {
     if (bytes > 160 * 1024) return set_error(TG_ERR_ARG, "%s: %zu B of LDS needed (> 160 KiB)", what, bytes);

@@ -78,6 +78,47 @@ class Env:
     def _fill_params(self, p):
         raise NotImplementedError
 
+    # -- control decimation -------------------------------------------------
+    MAX_SUBSTEPS = 64
+    _substeps = 1
+
+    @property
+    def substeps(self) -> int:
+        """Physics steps per policy step (default 1).  With `substeps = k` every action is applied for up to k consecutive steps of
+        this env's own step function -- it stops after the first one that reports `truncated` -- and the transition a learner sees
+        holds the observation before the first, the summed reward and the state after the last.  `timestep` is the physics step,
+        `max_steps` stays the number of POLICY steps (the trajectory horizon) and the episode's clock is `max_steps * k` physics
+        steps ("Control decimation").  An int in [1, 64]; Pendulum and swarm envs take 1 only: ValueError."""
+        return self._substeps
+
+    @substeps.setter
+    def substeps(self, k):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"substeps must be an int in [1, {self.MAX_SUBSTEPS}], got {k!r}")
+        k = int(k)
+        if not 1 <= k <= self.MAX_SUBSTEPS:
+            raise ValueError(f"substeps must be an int in [1, {self.MAX_SUBSTEPS}], got {k}")
+        if k != 1 and self.ENV_ID == N.TG_ENV_PENDULUM:
+            raise ValueError("substeps: Pendulum is not supported (its balance terminal counts single steps)")
+        if k != 1 and int(getattr(self, "n_agents", 1)) > 1:
+            raise ValueError("substeps: swarm envs (n_agents > 1) are not supported (the bodies of an env would have to stop at the "
+                             "same physics step)")
+        self._substeps = k
+
+    @property
+    def control_timestep(self) -> float:
+        """Time between two policy actions: `timestep * substeps`."""
+        return self.timestep * self._substeps
+
+    def physics_params(self) -> N.EnvParams:
+        """tg_env_params of the physics clock, what the `_sub` entry points take: native_params() with `max_steps * substeps` steps
+        of `timestep`, finalised.  With substeps == 1 it is native_params()."""
+        p = N.default_params(self.ENV_ID, int(self.max_steps) * self._substeps)
+        p.timestep = float(self.timestep)
+        self._fill_params(p)
+        N.check(N.load().tg_env_finalize_params(C.byref(p)), "tg_env_finalize_params")
+        return p
+
     # -- per-env domain randomisation (device rollouts) --------------------
     def randomize(self, ranges=None, *, seed: int = 0):
         """Each env slot of a device rollout steps its own vehicle: `ranges` maps a physical parameter (a name of
@@ -278,6 +319,8 @@ class Env:
         """Advance the scalar env by one tg_env_step; returns (reward, truncated) and updates the bookkeeping."""
         if self._state is None:
             raise RuntimeError("step() before reset()")
+        if self._substeps != 1:
+            return self._native_substeps(action)
         p = self.native_params()
         a = torch.as_tensor(np.asarray(action, dtype=np.float32).reshape(self.act_dim, 1), device=self._device)
         self._act_t.copy_(a)
@@ -291,6 +334,30 @@ class Env:
         self._time_balanced = float(self._tb_t.item())
         self._sync_state_dict()
         return float(self._rew_t.item()), bool(self._trunc_t.item())
+
+    def _native_substeps(self, action):
+        """One policy step of an env with substeps = k: up to k tg_env_step launches on the physics clock (the device step counter
+        counts physics steps), stopping after the first that truncates; the rewards are summed left to right in the env's dtype."""
+        p = self.physics_params()
+        a = torch.as_tensor(np.asarray(action, dtype=np.float32).reshape(self.act_dim, 1), device=self._device)
+        self._act_t.copy_(a)
+        total, truncated = None, False
+        for _ in range(self._substeps):
+            with torch.cuda.device(self._device):
+                N.check(N.load().tg_env_step(C.byref(p), N.dtype_code(self._dtype), self._state.data_ptr(), 1,
+                                             self._act_t.data_ptr(), 1, self._state.data_ptr(), 1, self._steps_t.data_ptr(),
+                                             self._tb_t.data_ptr(), self._rew_t.data_ptr(), self._trunc_t.data_ptr(), 1,
+                                             N.stream_ptr(self._device)), "tg_env_step")
+            self._time += self.timestep
+            r = self._rew_t.cpu()[0]
+            total = r if total is None else total + r
+            truncated = bool(self._trunc_t.item())
+            if truncated:
+                break
+        self._steps += 1
+        self._time_balanced = float(self._tb_t.item())
+        self._sync_state_dict()
+        return float(total), truncated
 
     def render(self, *a, **k):
         raise NotImplementedError("render() is matplotlib plotting in the reference and is out of scope here")

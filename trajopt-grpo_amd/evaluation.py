@@ -194,6 +194,7 @@ class Evaluator:
             eng._seed_host, eng._stream_host = self.seed, 0
             eng.rng[1].zero_()
             traj = eng.run(deterministic=self.deterministic)
-            self._s_final, self._timeout = K.rollout_final_state(eng.params, traj, self._s_final, self._timeout, env_params=eng.env_params)
+            self._s_final, self._timeout = K.rollout_final_state(eng.params, traj, self._s_final, self._timeout, env_params=eng.env_params,
+                                                                 **({"substeps": eng.substeps} if eng.substeps != 1 else {}))
             returns, cells = K.eval_cells(traj, self._timeout, self.episodes)
         return EvalResult(cells, returns, self._sweep, self.episodes, self.early_name)

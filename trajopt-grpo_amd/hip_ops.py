@@ -284,12 +284,15 @@ def ppo_returns(rew, values, mask, gamma: float, lam: float, monte_carlo: bool, 
     return ppo_returns_boot(rew, values, mask, None, None, gamma, lam, monte_carlo, adv, ret, work)
 
 
-def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: torch.Tensor = None, env_params: torch.Tensor = None):
+def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: torch.Tensor = None, env_params: torch.Tensor = None,
+                        substeps: int = 1):
     """tg_rollout_final_state on a DeviceTrajectory: (s_final f32 [n][S], timeout u8 [n]) -- the state each episode's last step
     produced (Env.step on obs[:, len-1], act[:, len-1]: tg_env_step's bits) and whether the clock, not a failure, ended the episode.
     params: the env's tg_env_params (DeviceRollout.params / Env.native_params()).  A swarm env is refused: ValueError.
     env_params: the per-env parameter table of a randomised rollout (DeviceRollout.env_params, f64 [12][n]): every slot is re-stepped
-    with its own vehicle (tg_rollout_final_state_dr)."""
+    with its own vehicle (tg_rollout_final_state_dr).
+    substeps != 1 (DeviceRollout.substeps; params are then those of the physics clock): the last CONTROL step is re-run, up to
+    `substeps` calls that stop at the first truncation (tg_rollout_final_state_sub, which takes the table or NULL)."""
     N.require_cuda(traj.obs, traj.act, traj.len, s_final, timeout)
     assert traj.obs.is_contiguous() and traj.act.is_contiguous() and traj.len.is_contiguous() and traj.len.dtype == torch.int32
     dev = traj.obs.device
@@ -303,8 +306,13 @@ def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: tor
     if env_params is not None:
         N.require_cuda(env_params)
         assert env_params.dtype == torch.float64 and env_params.is_contiguous() and tuple(env_params.shape) == (12, traj.n)
-    name, table = suffixed("tg_rollout_final_state", "_dr", None if env_params is None else (env_params.data_ptr(),))
-    rc = getattr(N.load(), name)(C.byref(params), *table, C.byref(tr), s_final.data_ptr(), timeout.data_ptr(), _st(traj.obs))
+    ptab = None if env_params is None else env_params.data_ptr()
+    if substeps != 1:
+        name, table, tail = "tg_rollout_final_state_sub", (ptab,), (int(substeps),)
+    else:
+        name, table = suffixed("tg_rollout_final_state", "_dr", None if ptab is None else (ptab,))
+        tail = ()
+    rc = getattr(N.load(), name)(C.byref(params), *table, C.byref(tr), s_final.data_ptr(), timeout.data_ptr(), *tail, _st(traj.obs))
     if rc == N.TG_ERR_UNSUPPORTED:
         raise ValueError(N.load().tg_last_error().decode("utf-8", "replace"))
     N.check(rc, name)

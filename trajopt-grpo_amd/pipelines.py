@@ -103,6 +103,8 @@ class Pipeline:
         rand = self.env.randomize_metadata()
         if rand is not None:                       # only when domain randomisation is on: Env.randomize(**meta["randomize"]) restores it
             meta["randomize"] = rand
+        if int(getattr(self.env, "substeps", 1)) != 1:   # only when control decimation is on: `env.substeps = meta["substeps"]` restores it
+            meta["substeps"] = int(self.env.substeps)
         return meta
 
     def load_metadata(self, path: str) -> Dict[str, Any]:

@@ -87,12 +87,15 @@ class DeviceTrajectory:
         return obs, act, rew, ln, mask
 
 
-def fused_entry(f32: bool, act: int, ptab, obs_norm):
+def fused_entry(f32: bool, act: int, ptab, obs_norm, substeps: int = 1):
     """(entry name, arguments after the env parameters, tail arguments) of the persistent rollout launch.  f32: the fp32 kernel
     (its entries beyond the plain one take the hidden activation `act`, TG_ACT_*); ptab: the per-env parameter table's address or
-    None; obs_norm: (table address, clip value) or None.  `_on` takes the table, NULL when the rollout is not randomised."""
+    None; obs_norm: (table address, clip value) or None.  `_on` takes the table, NULL when the rollout is not randomised.
+    substeps != 1: the `_sub` entry, which takes the table, the obs-norm pair (either may be NULL) and `substeps`."""
     base = "tg_fused_rollout_f32" if f32 else "tg_fused_rollout"
     act_arg = (act,) if f32 else ()
+    if substeps != 1:
+        return base + "_sub", (ptab,), act_arg + (tuple(obs_norm) if obs_norm is not None else (None, 0.0)) + (int(substeps),)
     if obs_norm is not None:
         return base + "_on", (ptab,), act_arg + tuple(obs_norm)
     if ptab is not None:
@@ -102,10 +105,19 @@ def fused_entry(f32: bool, act: int, ptab, obs_norm):
     return base, (), ()
 
 
-def step_entry(forced: bool, ptab):
+def step_entry(forced: bool, ptab, substeps: int = 1):
     """(entry name, arguments after the env parameters) of a per-step launch (tg_rollout_step) or of the one-launch teacher-forced
-    replay (tg_rollout_forced): `_dr` with the per-env parameter table of a randomised rollout."""
-    return K.suffixed("tg_rollout_forced" if forced else "tg_rollout_step", "_dr", None if ptab is None else (ptab,))
+    replay (tg_rollout_forced): `_dr` with the per-env parameter table of a randomised rollout.  substeps != 1: the `_sub` entry,
+    which takes the table (or NULL) there and `substeps` as its last argument before the stream (sub_tail)."""
+    base = "tg_rollout_forced" if forced else "tg_rollout_step"
+    if substeps != 1:
+        return K.suffixed(base, "_sub", (ptab,))
+    return K.suffixed(base, "_dr", None if ptab is None else (ptab,))
+
+
+def sub_tail(substeps: int):
+    """What a per-step `_sub` entry takes in front of the stream: () for the entries of substeps == 1."""
+    return () if substeps == 1 else (int(substeps),)
 
 
 class DeviceRollout:
@@ -133,13 +145,13 @@ class DeviceRollout:
         self.device = torch.device(device) if device is not None else policy.device
         if self.device.type != "cuda":
             raise N.NativeLibraryError("DeviceRollout needs an MI355X (cuda) device; there is no CPU fallback")
-        self.S, self.A, self.T = env.obs_dim, env.act_dim, int(env.max_steps)
+        self.S, self.A, self.T = env.obs_dim, env.act_dim, int(env.max_steps)       # T: policy steps, whatever env.substeps
         self.dtype = dtype
         self.compute_dtype = compute_dtype
         self.group_offset = int(group_offset)
         self.traj = DeviceTrajectory(self.S, self.A, self.T, self.n, self.G, self.E, dtype, self.device)
         self.rng = torch.tensor([int(seed), 0], dtype=torch.int64, device=self.device)
-        self.params = env.native_params()
+        self._read_env()
         self._sigma = (C.c_float * self.A)(*[float(v) for v in torch.sqrt(policy.var)])
         self._linears = [m for m in policy.actor.network if isinstance(m, torch.nn.Linear)]
         self._lowp = None
@@ -198,6 +210,12 @@ class DeviceRollout:
         # callable (native trajectory, stream) an Evaluator installs: runs after the reset and the random draw of every rollout's
         # prologue and may fill `env_params` (tg_env_param_grid) and edit slot 0 (tg_eval_tile_states); None everywhere else
         self._param_source = None
+
+    def _read_env(self):
+        """The env's parameters as this rollout steps with them: with env.substeps = k != 1 those of the physics clock (max_steps * k
+        steps of env.timestep) and k, which every launch below passes to its `_sub` entry point."""
+        self.substeps = int(getattr(self.env, "substeps", 1))
+        self.params = self.env.native_params() if self.substeps == 1 else self.env.physics_params()
 
     # ---- policy mean for time step t -------------------------------------------------
     def _refresh_weights(self, entry: bool = False):
@@ -263,7 +281,7 @@ class DeviceRollout:
         """One rollout.  `initial_states` (N,S) and `forced_actions` (N,T,A) or (G,E,T,A)
         replace the RNG draws (teacher-forced parity runs).  deterministic=True: the action of every step is the actor's mean --
         the same kernels with a sigma of exactly 0.0f, on every path (a = rn_add(mu, rn_mul(0, eps)) == mu: eps is finite)."""
-        self.params = self.env.native_params()
+        self._read_env()
         self._rand_spec = self.env.randomize_spec()
         if self._rand_spec is None and self._param_source is None:
             self.env_params = None                        # off (again): no table on any path below, the graph replay included
@@ -336,7 +354,7 @@ class DeviceRollout:
         n_hidden = len(self._linears) - 1
         on = getattr(self.policy, "obs_norm", None)
         name, table, tail = fused_entry(self._fused_f32, self._f32_act, None if self.env_params is None else self.env_params.data_ptr(),
-                                        None if on is None else (on.table.data_ptr(), on.clip_value))
+                                        None if on is None else (on.table.data_ptr(), on.clip_value), self.substeps)
         # (the fp32 kernel reads biases and head from a table and takes its envs per workgroup; the bf16 kernel reads a bias stream)
         weights = ((self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs) if self._fused_f32 else
                    (self._frag.bias.data_ptr(), self._fused_H, n_hidden))
@@ -360,12 +378,12 @@ class DeviceRollout:
     def _launch_step(self, t, tr, st, *args):
         """One tg_rollout_step launch for time step t -- t None: the whole teacher-forced replay in one tg_rollout_forced launch --
         (`_dr`: a randomised rollout), bracketed by timing events when step_events is a list."""
-        name, table = step_entry(t is None, None if self.env_params is None else self.env_params.data_ptr())
+        name, table = step_entry(t is None, None if self.env_params is None else self.env_params.data_ptr(), self.substeps)
         ev = None
         if self.step_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        N.check(getattr(self.lib, name)(C.byref(self.params), *table, C.byref(tr), *args, st), name)
+        N.check(getattr(self.lib, name)(C.byref(self.params), *table, C.byref(tr), *args, *sub_tail(self.substeps), st), name)
         if ev is not None:
             ev[1].record()
             self.step_events.append((t, ev[0], ev[1]))
@@ -399,7 +417,7 @@ class DeviceRollout:
             # tg_rollout_step takes sigma (and the env parameters) BY VALUE in its kernel arguments: a captured graph replays the
             # values of its capture.  A covariance annealed or restored since then (the learner reads policy.var afresh in every
             # learn(), actor_critic.py:131-136 reads self.cov in every forward) means a new capture.
-            baked = (tuple(self._sigma), bytes(self.params))
+            baked = (tuple(self._sigma), bytes(self.params), self.substeps)
             if self._graph is not None and baked != self._graph_baked:
                 self._graph = None
             if self._graph is None:
