@@ -156,6 +156,39 @@ static inline PerEnvTable per_env_table(const tg_env_params* p, const double* d_
     return PerEnvTable{d_ptab, p->timestep, p->max_steps, p->time_trunc_step};
 }
 
+// The variant of a rollout kernel that an entry point asked for, and the ONE place that turns it into the kernel's Env type and
+// by-value first argument.  The wrappers nest in a fixed order -- PerEnv<> innermost, Substepped<> around it, ObsNormed<> around both
+// -- and every launch of a kernel templated on the Env type goes through with_env_variant, so no caller spells a nesting out.
+struct EnvVariant {
+    const tg_env_params* p;
+    const double* d_ptab;        // non-null (the `_dr` entries): PerEnv<>, the table in place of the constants
+    const float* d_obs_norm;     // non-null (the `_on` entries): ObsNormed<>, with `clip`
+    float clip;
+    int32_t substeps;
+    bool sub;                    // entered through a `_sub` entry: Substepped<>, also at substeps == 1
+};
+template <typename EnvK> struct EnvTag { using type = EnvK; };
+// Calls f(EnvTag<EnvK>{}, arg) -- arg the `typename EnvK::C` of the variant -- for the one EnvK in {Env, PerEnv<Env>, ObsNormed<..>,
+// Substepped<..>, ObsNormed<Substepped<..>>} that `v` names, and returns f's status.  kMayObsNorm / kMaySubstep = false prune the
+// wrapper at compile time (a kernel family or an env without those instantiations); a variant that asks for a pruned one is refused.
+template <typename Env, bool kMayObsNorm, bool kMaySubstep = Env::kMaySubstep, typename F>
+static inline int with_env_variant(const EnvVariant& v, F&& f) {
+    auto normed = [&](auto tag, const auto& arg) -> int {
+        using E = typename decltype(tag)::type;
+        if (v.d_obs_norm == nullptr) return f(tag, arg);
+        if constexpr (kMayObsNorm) return f(EnvTag<ObsNormed<E>>{}, ObsNormArg<typename E::C>{arg, ObsNormTable{v.d_obs_norm, v.clip}});
+        else return set_error(TG_ERR_UNSUPPORTED, "observation normalisation is not instantiated for this kernel");
+    };
+    auto substepped = [&](auto tag, const auto& arg) -> int {
+        using E = typename decltype(tag)::type;
+        if (!v.sub) return normed(tag, arg);
+        if constexpr (kMaySubstep) return normed(EnvTag<Substepped<E>>{}, SubstepArg<typename E::C>{arg, v.substeps});
+        else return set_error(TG_ERR_UNSUPPORTED, "substeps are not instantiated for this env");
+    };
+    if (v.d_ptab != nullptr) return substepped(EnvTag<PerEnv<Env>>{}, per_env_table(v.p, v.d_ptab));
+    return substepped(EnvTag<Env>{}, Env::C::make(*v.p));
+}
+
 // One control step of a kSubsteps kernel: the action `a` applied for up to `k` consecutive calls of the env's own Env::step, call j
 // (from 0) of control step t with steps_after = t k + j + 1, stopping after the first call that reports `truncated`.  Returns the
 // last executed call's StepOut, with its state in `o`, the left-to-right sum of the executed calls' rewards in `reward` (in R,
@@ -198,6 +231,7 @@ __device__ static inline StepOut substep_loop(const R (&s)[Env::S], const float 
 template <typename R> struct CartPoleEnv {
     static constexpr int S = 5, A = 1;
     static constexpr bool kBalanceTerminates = false;
+    static constexpr bool kMaySubstep = true;
     struct C {
         R mc, mp, l, g, dt;
         int max_steps, time_trunc_step;
@@ -267,6 +301,7 @@ template <typename R> struct CartPoleEnv {
 template <typename R> struct QuadPole2DEnv {
     static constexpr int S = 10, A = 2;
     static constexpr bool kBalanceTerminates = false;
+    static constexpr bool kMaySubstep = true;
     struct C {
         R mq_Lp, mpLp, M, g, dt, bound, balance_radius;
         float hover32, Lq_over_I32, dt32;
@@ -364,6 +399,7 @@ template <typename R> __device__ static inline void quat_mult(const R (&q)[4], c
 template <typename R> struct QuadPoleEnv {
     static constexpr int S = 20, A = 4;
     static constexpr bool kBalanceTerminates = false;
+    static constexpr bool kMaySubstep = true;
     struct C {
         R m0, m_p, g, L, Ixx, Iyy, Izz, arm, dt, bound, tension_k, m0L, inv_m0, s22, mpL2;
         float hover32, tc32;
@@ -544,6 +580,7 @@ template <typename R> struct QuadPoleEnv {
 template <typename R> struct PendulumEnv {
     static constexpr int S = 3, A = 1;
     static constexpr bool kBalanceTerminates = true;
+    static constexpr bool kMaySubstep = false;   // (substeps_check: the balance count kept in len counts single steps)
     struct C {
         R mgl, inv_ml2, dt;
         int max_steps, time_trunc_step, term_steps, swingup;

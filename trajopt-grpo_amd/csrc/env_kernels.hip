@@ -490,143 +490,63 @@ static int step_dispatch(const tg_env_params* p, const void* state, int64_t ld, 
     return TG_OK;
 }
 
-// d_ptab != NULL in the three dispatchers below: the `_dr` entry point -- the kernel's PerEnv instantiation with the table.
+// The three dispatchers below launch the kernel instantiation that the variant names (with_env_variant, env_dynamics.hpp): the plain
+// env, PerEnv<> with a parameter table (`_dr`), Substepped<> through a `_sub` entry.  (No ObsNormed<>: the policy runs outside.)
+// `who`: the entry point's name in the launch check.
 template <template <typename> class EnvT, typename R>
-static int rollout_dispatch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* mean, int64_t mean_rs,
+static int rollout_dispatch(const char* who, const EnvVariant& v, const tg_traj* tr, int32_t t, const float* mean, int64_t mean_rs,
                             const float* sigma, const uint64_t* rng, int64_t env_offset, hipStream_t st) {
     int block;
     dim3 grid = env_grid(tr->n, block);
-    auto c = EnvT<R>::C::make(*p);
-    const PerEnvTable pe = per_env_table(p, d_ptab);
     Sigma sg;
     memset(&sg, 0, sizeof(sg));
-    const bool spec = tr->n <= ((int64_t)1 << 18);
-#define TG_RS(SAMPLE, SPEC)                                                                                            \
-    if (d_ptab != nullptr)                                                                                             \
-        hipLaunchKernelGGL((rollout_step_kernel<PerEnv<EnvT<R>>, R, SAMPLE, SPEC>), grid, dim3(block), 0, st, pe, (R*)tr->d_obs, \
-                           tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs, sg, rng, \
-                           env_offset, p->agents);                                                                     \
-    else                                                                                                               \
-        hipLaunchKernelGGL((rollout_step_kernel<EnvT<R>, R, SAMPLE, SPEC>), grid, dim3(block), 0, st, c, (R*)tr->d_obs,  \
-                           tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs, sg, rng, \
-                           env_offset, p->agents)
-    if (mean != nullptr) {
+    if (mean != nullptr)
         for (int k = 0; k < EnvT<R>::A; ++k) sg.v[k] = sigma[k];
-        if (spec) { TG_RS(true, true); } else { TG_RS(true, false); }
-    } else {
-        if (spec) { TG_RS(false, true); } else { TG_RS(false, false); }
-    }
-#undef TG_RS
-    TG_LAUNCH_CHECK("tg_rollout_step");
-    return TG_OK;
-}
-
-template <template <typename> class EnvT, typename R>
-static int forced_dispatch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, hipStream_t st) {
-    auto c = EnvT<R>::C::make(*p);
-    if (d_ptab != nullptr)
-        hipLaunchKernelGGL((rollout_forced_kernel<PerEnv<EnvT<R>>, R>), dim3((unsigned)ceil_div(tr->n, 64)), dim3(64), 0, st,
-                           per_env_table(p, d_ptab), (R*)tr->d_obs, (const float*)tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n,
-                           tr->horizon, t_begin, t_end, p->agents);
-    else
-        hipLaunchKernelGGL((rollout_forced_kernel<EnvT<R>, R>), dim3((unsigned)ceil_div(tr->n, 64)), dim3(64), 0, st, c, (R*)tr->d_obs,
-                           (const float*)tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t_begin, t_end, p->agents);
-    TG_LAUNCH_CHECK("tg_rollout_forced");
-    return TG_OK;
-}
-
-template <template <typename> class EnvT, typename R>
-static int final_state_dispatch(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* s_final, uint8_t* timeout,
-                                hipStream_t st) {
-    int block;
-    dim3 grid = env_grid(tr->n, block);
-    auto c = EnvT<R>::C::make(*p);
-    if (d_ptab != nullptr)
-        hipLaunchKernelGGL((final_state_kernel<PerEnv<EnvT<R>>, R>), grid, dim3(block), 0, st, per_env_table(p, d_ptab), (const R*)tr->d_obs,
-                           (const float*)tr->d_act, (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
-    else
-        hipLaunchKernelGGL((final_state_kernel<EnvT<R>, R>), grid, dim3(block), 0, st, c, (const R*)tr->d_obs, (const float*)tr->d_act,
-                           (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
-    TG_LAUNCH_CHECK("tg_rollout_final_state");
-    return TG_OK;
-}
-
-// ---- control decimation (the `_sub` entry points): the kernels' Substepped instantiations, argument {constants or table, k} ----
-template <template <typename> class EnvT, typename R>
-static int rollout_dispatch_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* mean, int64_t mean_rs,
-                                const float* sigma, const uint64_t* rng, int64_t env_offset, int32_t k, hipStream_t st) {
-    int block;
-    dim3 grid = env_grid(tr->n, block);
-    const SubstepArg<typename EnvT<R>::C> c{EnvT<R>::C::make(*p), k};
-    const SubstepArg<PerEnvTable> pe{per_env_table(p, d_ptab), k};
-    Sigma sg;
-    memset(&sg, 0, sizeof(sg));
     const bool spec = tr->n <= ((int64_t)1 << 18);
-#define TG_RS(SAMPLE, SPEC)                                                                                            \
-    if (d_ptab != nullptr)                                                                                             \
-        hipLaunchKernelGGL((rollout_step_kernel<Substepped<PerEnv<EnvT<R>>>, R, SAMPLE, SPEC>), grid, dim3(block), 0, st, pe, (R*)tr->d_obs, \
-                           tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs, sg, rng, \
-                           env_offset, p->agents);                                                                     \
-    else                                                                                                               \
-        hipLaunchKernelGGL((rollout_step_kernel<Substepped<EnvT<R>>, R, SAMPLE, SPEC>), grid, dim3(block), 0, st, c, (R*)tr->d_obs,  \
-                           tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs, sg, rng, \
-                           env_offset, p->agents)
-    if (mean != nullptr) {
-        for (int q = 0; q < EnvT<R>::A; ++q) sg.v[q] = sigma[q];
-        if (spec) { TG_RS(true, true); } else { TG_RS(true, false); }
-    } else {
-        if (spec) { TG_RS(false, true); } else { TG_RS(false, false); }
-    }
-#undef TG_RS
-    TG_LAUNCH_CHECK("tg_rollout_step_sub");
-    return TG_OK;
+    return with_env_variant<EnvT<R>, false>(v, [&](auto tag, const auto& arg) -> int {
+        using EnvK = typename decltype(tag)::type;
+        auto launch = [&](auto sample, auto speculative) {
+            hipLaunchKernelGGL((rollout_step_kernel<EnvK, R, decltype(sample)::value, decltype(speculative)::value>), grid, dim3(block), 0,
+                               st, arg, (R*)tr->d_obs, tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t, mean, mean_rs,
+                               sg, rng, env_offset, v.p->agents);
+        };
+        using Yes = std::true_type;
+        using No = std::false_type;
+        if (mean != nullptr) {
+            if (spec) launch(Yes{}, Yes{}); else launch(Yes{}, No{});
+        } else {
+            if (spec) launch(No{}, Yes{}); else launch(No{}, No{});
+        }
+        TG_LAUNCH_CHECK(who);
+        return TG_OK;
+    });
 }
 
 template <template <typename> class EnvT, typename R>
-static int forced_dispatch_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, int32_t k,
-                               hipStream_t st) {
-    const dim3 grid((unsigned)ceil_div(tr->n, 64));
-    if (d_ptab != nullptr)
-        hipLaunchKernelGGL((rollout_forced_kernel<Substepped<PerEnv<EnvT<R>>>, R>), grid, dim3(64), 0, st,
-                           SubstepArg<PerEnvTable>{per_env_table(p, d_ptab), k}, (R*)tr->d_obs, (const float*)tr->d_act, (R*)tr->d_rew, tr->d_mask,
-                           tr->d_len, tr->n, tr->horizon, t_begin, t_end, p->agents);
-    else
-        hipLaunchKernelGGL((rollout_forced_kernel<Substepped<EnvT<R>>, R>), grid, dim3(64), 0, st,
-                           SubstepArg<typename EnvT<R>::C>{EnvT<R>::C::make(*p), k}, (R*)tr->d_obs, (const float*)tr->d_act, (R*)tr->d_rew,
-                           tr->d_mask, tr->d_len, tr->n, tr->horizon, t_begin, t_end, p->agents);
-    TG_LAUNCH_CHECK("tg_rollout_forced_sub");
-    return TG_OK;
+static int forced_dispatch(const char* who, const EnvVariant& v, const tg_traj* tr, int32_t t_begin, int32_t t_end, hipStream_t st) {
+    return with_env_variant<EnvT<R>, false>(v, [&](auto tag, const auto& arg) -> int {
+        using EnvK = typename decltype(tag)::type;
+        hipLaunchKernelGGL((rollout_forced_kernel<EnvK, R>), dim3((unsigned)ceil_div(tr->n, 64)), dim3(64), 0, st, arg, (R*)tr->d_obs,
+                           (const float*)tr->d_act, (R*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t_begin, t_end, v.p->agents);
+        TG_LAUNCH_CHECK(who);
+        return TG_OK;
+    });
 }
 
 template <template <typename> class EnvT, typename R>
-static int final_state_dispatch_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* s_final, uint8_t* timeout, int32_t k,
-                                    hipStream_t st) {
+static int final_state_dispatch(const char* who, const EnvVariant& v, const tg_traj* tr, float* s_final, uint8_t* timeout, hipStream_t st) {
     int block;
     dim3 grid = env_grid(tr->n, block);
-    if (d_ptab != nullptr)
-        hipLaunchKernelGGL((final_state_kernel<Substepped<PerEnv<EnvT<R>>>, R>), grid, dim3(block), 0, st,
-                           SubstepArg<PerEnvTable>{per_env_table(p, d_ptab), k}, (const R*)tr->d_obs, (const float*)tr->d_act,
+    return with_env_variant<EnvT<R>, false>(v, [&](auto tag, const auto& arg) -> int {
+        using EnvK = typename decltype(tag)::type;
+        hipLaunchKernelGGL((final_state_kernel<EnvK, R>), grid, dim3(block), 0, st, arg, (const R*)tr->d_obs, (const float*)tr->d_act,
                            (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
-    else
-        hipLaunchKernelGGL((final_state_kernel<Substepped<EnvT<R>>, R>), grid, dim3(block), 0, st,
-                           SubstepArg<typename EnvT<R>::C>{EnvT<R>::C::make(*p), k}, (const R*)tr->d_obs, (const float*)tr->d_act,
-                           (const int32_t*)tr->d_len, tr->n, tr->horizon, s_final, timeout);
-    TG_LAUNCH_CHECK("tg_rollout_final_state_sub");
-    return TG_OK;
+        TG_LAUNCH_CHECK(who);
+        return TG_OK;
+    });
 }
 
-// (no Pendulum: substeps_check refuses it before any launch)
-#define TG_ENV_SWITCH_SUB(env_id, dtype, CALL)                                                 \
-    switch ((env_id) * 2 + (dtype)) {                                                          \
-        case TG_ENV_CARTPOLE * 2 + TG_F32: return CALL(CartPoleEnv, float);                    \
-        case TG_ENV_CARTPOLE * 2 + TG_F64: return CALL(CartPoleEnv, double);                   \
-        case TG_ENV_QUADPOLE2D * 2 + TG_F32: return CALL(QuadPole2DEnv, float);                \
-        case TG_ENV_QUADPOLE2D * 2 + TG_F64: return CALL(QuadPole2DEnv, double);               \
-        case TG_ENV_QUADPOLE * 2 + TG_F32: return CALL(QuadPoleEnv, float);                    \
-        case TG_ENV_QUADPOLE * 2 + TG_F64: return CALL(QuadPoleEnv, double);                   \
-        default: return set_error(TG_ERR_UNSUPPORTED, "unsupported env_id %d / dtype %d", (int)(env_id), (int)(dtype)); \
-    }
-
+// (a Pendulum through a `_sub` entry never gets here: substeps_check refuses it, and Pendulum's kMaySubstep = false instantiates nothing)
 #define TG_ENV_SWITCH(env_id, dtype, CALL)                                                     \
     switch ((env_id) * 2 + (dtype)) {                                                          \
         case TG_ENV_CARTPOLE * 2 + TG_F32: return CALL(CartPoleEnv, float);                    \
@@ -820,120 +740,110 @@ int tg_rollout_begin(const tg_traj* tr, int obs_dim, int act_dim, void* stream) 
     return TG_OK;
 }
 
-static int rollout_step_impl(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean,
+// The three per-step families, each behind one impl: `v` is the variant the entry point asked for, `who` the name its messages carry
+// (the plain entry's through `_dr`, the entry's own through `_sub`).  Through a `_sub` entry `v.p` describes the PHYSICS clock
+// (p->max_steps = tr->horizon * substeps: substeps_check) and t / t_begin / t_end count control steps.
+static EnvVariant plain_variant(const tg_env_params* p, const double* d_ptab) { return EnvVariant{p, d_ptab, nullptr, 0.0f, 1, false}; }
+static EnvVariant sub_variant(const tg_env_params* p, const double* d_ptab, int32_t substeps) {
+    return EnvVariant{p, d_ptab, nullptr, 0.0f, substeps, true};
+}
+
+static int rollout_step_impl(const char* who, const EnvVariant& v, const tg_traj* tr, int32_t t, const float* d_mean,
                              int64_t mean_row_stride, const float* sigma, const uint64_t* d_rng, int64_t env_offset, void* stream) {
-    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_rollout_step: null pointer");
-    TG_REQUIRE(tr->n > 0 && tr->horizon > 0 && t >= 0 && t < tr->horizon, "tg_rollout_step: t=%d outside horizon %d", t,
-               tr->horizon);
-    TG_REQUIRE(tr->horizon == p->max_steps, "tg_rollout_step: trajectory horizon %d != env.max_steps %d", tr->horizon,
-               p->max_steps);
+    const tg_env_params* p = v.p;
+    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "%s: null pointer", who);
+    if (v.sub)
+        if (int rc = substeps_check(who, p, tr, v.substeps)) return rc;
+    TG_REQUIRE(tr->n > 0 && tr->horizon > 0 && t >= 0 && t < tr->horizon, "%s: t=%d outside horizon %d", who, t, tr->horizon);
+    if (!v.sub) TG_REQUIRE(tr->horizon == p->max_steps, "%s: trajectory horizon %d != env.max_steps %d", who, tr->horizon, p->max_steps);
     TG_REQUIRE(p->agents <= 1 || (p->agents <= 64 && (p->agents & (p->agents - 1)) == 0 && tr->n % p->agents == 0),
-               "tg_rollout_step: agents=%d must be a power of two <= 64 dividing n", p->agents);
+               "%s: agents=%d must be a power of two <= 64 dividing n", who, p->agents);
     if (d_mean != nullptr) {
         int S, A;
         tg_env_dims(p->env_id, &S, &A);
-        TG_REQUIRE(sigma != nullptr && d_rng != nullptr, "tg_rollout_step: sampling needs sigma and d_rng");
-        TG_REQUIRE(mean_row_stride >= A, "tg_rollout_step: mean_row_stride %lld < act_dim %d", (long long)mean_row_stride, A);
+        TG_REQUIRE(sigma != nullptr && d_rng != nullptr, "%s: sampling needs sigma and d_rng", who);
+        TG_REQUIRE(mean_row_stride >= A, "%s: mean_row_stride %lld < act_dim %d", who, (long long)mean_row_stride, A);
     }
-#define CALL(E, R) rollout_dispatch<E, R>(p, d_ptab, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, (hipStream_t)stream)
+#define CALL(E, R) rollout_dispatch<E, R>(who, v, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, (hipStream_t)stream)
     TG_ENV_SWITCH(p->env_id, tr->dtype, CALL)
 #undef CALL
 }
 
 int tg_rollout_step(const tg_env_params* p, const tg_traj* tr, int32_t t, const float* d_mean, int64_t mean_row_stride,
                     const float* sigma, const uint64_t* d_rng, int64_t env_offset, void* stream) {
-    return rollout_step_impl(p, nullptr, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, stream);
+    return rollout_step_impl("tg_rollout_step", plain_variant(p, nullptr), tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, stream);
 }
 
 int tg_rollout_step_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean,
                        int64_t mean_row_stride, const float* sigma, const uint64_t* d_rng, int64_t env_offset, void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_rollout_step_dr: null parameter table");
-    return rollout_step_impl(p, d_ptab, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, stream);
+    return rollout_step_impl("tg_rollout_step", plain_variant(p, d_ptab), tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, stream);
 }
 
-static int rollout_forced_impl(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream) {
-    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_rollout_forced: null pointer");
+int tg_rollout_step_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean, int64_t mean_row_stride,
+                        const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t substeps, void* stream) {
+    return rollout_step_impl("tg_rollout_step_sub", sub_variant(p, d_ptab, substeps), tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset,
+                             stream);
+}
+
+static int rollout_forced_impl(const char* who, const EnvVariant& v, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream) {
+    const tg_env_params* p = v.p;
+    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "%s: null pointer", who);
+    if (v.sub)
+        if (int rc = substeps_check(who, p, tr, v.substeps)) return rc;
     TG_REQUIRE(tr->n > 0 && tr->horizon > 0 && t_begin >= 0 && t_begin <= t_end && t_end <= tr->horizon,
-               "tg_rollout_forced: steps [%d, %d) outside horizon %d", t_begin, t_end, tr->horizon);
-    TG_REQUIRE(tr->horizon == p->max_steps, "tg_rollout_forced: trajectory horizon %d != env.max_steps %d", tr->horizon, p->max_steps);
+               "%s: steps [%d, %d) outside horizon %d", who, t_begin, t_end, tr->horizon);
+    if (!v.sub) TG_REQUIRE(tr->horizon == p->max_steps, "%s: trajectory horizon %d != env.max_steps %d", who, tr->horizon, p->max_steps);
     TG_REQUIRE(p->agents <= 1 || (p->agents <= 64 && (p->agents & (p->agents - 1)) == 0 && tr->n % p->agents == 0),
-               "tg_rollout_forced: agents=%d must be a power of two <= 64 dividing n", p->agents);
+               "%s: agents=%d must be a power of two <= 64 dividing n", who, p->agents);
     if (t_begin == t_end) return TG_OK;
-#define CALL(E, R) forced_dispatch<E, R>(p, d_ptab, tr, t_begin, t_end, (hipStream_t)stream)
+#define CALL(E, R) forced_dispatch<E, R>(who, v, tr, t_begin, t_end, (hipStream_t)stream)
     TG_ENV_SWITCH(p->env_id, tr->dtype, CALL)
 #undef CALL
 }
 
 int tg_rollout_forced(const tg_env_params* p, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream) {
-    return rollout_forced_impl(p, nullptr, tr, t_begin, t_end, stream);
+    return rollout_forced_impl("tg_rollout_forced", plain_variant(p, nullptr), tr, t_begin, t_end, stream);
 }
 
 int tg_rollout_forced_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_rollout_forced_dr: null parameter table");
-    return rollout_forced_impl(p, d_ptab, tr, t_begin, t_end, stream);
+    return rollout_forced_impl("tg_rollout_forced", plain_variant(p, d_ptab), tr, t_begin, t_end, stream);
 }
 
-static int final_state_impl(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
-                            void* stream) {
-    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_len && d_s_final && d_timeout, "tg_rollout_final_state: null pointer");
-    TG_REQUIRE(tr->n > 0 && tr->horizon > 0, "tg_rollout_final_state: bad sizes n=%lld T=%d", (long long)tr->n, tr->horizon);
-    TG_REQUIRE(tr->horizon == p->max_steps, "tg_rollout_final_state: trajectory horizon %d != env.max_steps %d", tr->horizon,
-               p->max_steps);
+int tg_rollout_forced_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, int32_t substeps,
+                          void* stream) {
+    return rollout_forced_impl("tg_rollout_forced_sub", sub_variant(p, d_ptab, substeps), tr, t_begin, t_end, stream);
+}
+
+static int final_state_impl(const char* who, const EnvVariant& v, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout, void* stream) {
+    const tg_env_params* p = v.p;
+    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_len && d_s_final && d_timeout, "%s: null pointer", who);
+    if (v.sub)
+        if (int rc = substeps_check(who, p, tr, v.substeps)) return rc;
+    TG_REQUIRE(tr->n > 0 && tr->horizon > 0, "%s: bad sizes n=%lld T=%d", who, (long long)tr->n, tr->horizon);
+    if (!v.sub) TG_REQUIRE(tr->horizon == p->max_steps, "%s: trajectory horizon %d != env.max_steps %d", who, tr->horizon, p->max_steps);
     if (p->agents > 1)
-        return set_error(TG_ERR_UNSUPPORTED, "tg_rollout_final_state: swarm envs (agents=%d) are not supported: a swarm episode ends "
-                         "when any of its bodies does, which a body's own final state does not tell", p->agents);
-#define CALL(E, R) final_state_dispatch<E, R>(p, d_ptab, tr, d_s_final, d_timeout, (hipStream_t)stream)
+        return set_error(TG_ERR_UNSUPPORTED, "%s: swarm envs (agents=%d) are not supported: a swarm episode ends "
+                         "when any of its bodies does, which a body's own final state does not tell", who, p->agents);
+#define CALL(E, R) final_state_dispatch<E, R>(who, v, tr, d_s_final, d_timeout, (hipStream_t)stream)
     TG_ENV_SWITCH(p->env_id, tr->dtype, CALL)
 #undef CALL
 }
 
 int tg_rollout_final_state(const tg_env_params* p, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout, void* stream) {
-    return final_state_impl(p, nullptr, tr, d_s_final, d_timeout, stream);
+    return final_state_impl("tg_rollout_final_state", plain_variant(p, nullptr), tr, d_s_final, d_timeout, stream);
 }
 
 int tg_rollout_final_state_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
                               void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_rollout_final_state_dr: null parameter table");
-    return final_state_impl(p, d_ptab, tr, d_s_final, d_timeout, stream);
-}
-
-// ---- control decimation: `p` describes the PHYSICS clock (p->max_steps = tr->horizon * substeps), t / t_begin / t_end count control steps ----
-int tg_rollout_step_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean, int64_t mean_row_stride,
-                        const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t substeps, void* stream) {
-    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_rollout_step_sub: null pointer");
-    if (int rc = substeps_check("tg_rollout_step_sub", p, tr, substeps)) return rc;
-    TG_REQUIRE(tr->n > 0 && t >= 0 && t < tr->horizon, "tg_rollout_step_sub: t=%d outside horizon %d", t, tr->horizon);
-    if (d_mean != nullptr) {
-        int S, A;
-        tg_env_dims(p->env_id, &S, &A);
-        TG_REQUIRE(sigma != nullptr && d_rng != nullptr, "tg_rollout_step_sub: sampling needs sigma and d_rng");
-        TG_REQUIRE(mean_row_stride >= A, "tg_rollout_step_sub: mean_row_stride %lld < act_dim %d", (long long)mean_row_stride, A);
-    }
-#define CALL(E, R) rollout_dispatch_sub<E, R>(p, d_ptab, tr, t, d_mean, mean_row_stride, sigma, d_rng, env_offset, substeps, (hipStream_t)stream)
-    TG_ENV_SWITCH_SUB(p->env_id, tr->dtype, CALL)
-#undef CALL
-}
-
-int tg_rollout_forced_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, int32_t substeps,
-                          void* stream) {
-    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_rollout_forced_sub: null pointer");
-    if (int rc = substeps_check("tg_rollout_forced_sub", p, tr, substeps)) return rc;
-    TG_REQUIRE(tr->n > 0 && t_begin >= 0 && t_begin <= t_end && t_end <= tr->horizon, "tg_rollout_forced_sub: steps [%d, %d) outside horizon %d",
-               t_begin, t_end, tr->horizon);
-    if (t_begin == t_end) return TG_OK;
-#define CALL(E, R) forced_dispatch_sub<E, R>(p, d_ptab, tr, t_begin, t_end, substeps, (hipStream_t)stream)
-    TG_ENV_SWITCH_SUB(p->env_id, tr->dtype, CALL)
-#undef CALL
+    return final_state_impl("tg_rollout_final_state", plain_variant(p, d_ptab), tr, d_s_final, d_timeout, stream);
 }
 
 int tg_rollout_final_state_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
                                int32_t substeps, void* stream) {
-    TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_len && d_s_final && d_timeout, "tg_rollout_final_state_sub: null pointer");
-    if (int rc = substeps_check("tg_rollout_final_state_sub", p, tr, substeps)) return rc;
-    TG_REQUIRE(tr->n > 0, "tg_rollout_final_state_sub: bad sizes n=%lld T=%d", (long long)tr->n, tr->horizon);
-#define CALL(E, R) final_state_dispatch_sub<E, R>(p, d_ptab, tr, d_s_final, d_timeout, substeps, (hipStream_t)stream)
-    TG_ENV_SWITCH_SUB(p->env_id, tr->dtype, CALL)
-#undef CALL
+    return final_state_impl("tg_rollout_final_state_sub", sub_variant(p, d_ptab, substeps), tr, d_s_final, d_timeout, stream);
 }
 
 int tg_rollout_finish(const tg_traj* tr, void* stream) {

@@ -350,92 +350,35 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup's LDS allocation
 }
 
-template <template <typename> class EnvT, int H, int NT, int WPW>
-static int fused_launch(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const void* wfrag,
-                        const float* bias, int n_hh, const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, hipStream_t st) {
-    using Env = EnvT<float>;
+// One launch function per kernel instantiation (so one LdsOptIn each); `label`: the entry point's name in the LDS and launch checks.
+template <typename EnvK, int H, int NT, int WPW>
+static int fused_launch_one(const char* label, const typename EnvK::C& arg, const tg_traj* tr, const void* wfrag, const float* bias, int n_hh,
+                            const SigmaF& sg, const uint64_t* rng, int64_t env_offset, int t0, int t1, int agents, hipStream_t st) {
     constexpr int KS = H / 16;
-    auto c = Env::C::make(*p);
-    SigmaF sg;
-    memset(&sg, 0, sizeof(sg));
-    for (int k = 0; k < Env::A; ++k) sg.v[k] = sigma[k];
     const size_t shmem = (size_t)((NT == 1 && WPW == 4) ? 3 : 4) * KS * 1024 + (size_t)(n_hh + 2) * H * sizeof(float) +
                          (size_t)WPW * 64 * 32 * 2 + 4 * WPW;
-    const dim3 grid((unsigned)ceil_div(tr->n, 32 * NT * WPW));
-    if (d_obs_norm != nullptr) {       // tg_fused_rollout_on: the ObsNormed instantiations, with or without the parameter table
-        const ObsNormTable on{d_obs_norm, clip};
-        if (d_ptab != nullptr) {
-            auto kern = fused_rollout_kernel<ObsNormed<PerEnv<Env>>, H, NT, WPW>;
-            static LdsOptIn opt_in_on_dr;
-            if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in_on_dr, "tg_fused_rollout_on")) return rc;
-            hipLaunchKernelGGL(kern, grid, dim3(64 * WPW), shmem, st, ObsNormArg<PerEnvTable>{per_env_table(p, d_ptab), on}, (float*)tr->d_obs,
-                               tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg,
-                               rng, env_offset, p->agents);
-        } else {
-            auto kern = fused_rollout_kernel<ObsNormed<Env>, H, NT, WPW>;
-            static LdsOptIn opt_in_on;
-            if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in_on, "tg_fused_rollout_on")) return rc;
-            hipLaunchKernelGGL(kern, grid, dim3(64 * WPW), shmem, st, ObsNormArg<typename Env::C>{c, on}, (float*)tr->d_obs, tr->d_act,
-                               (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg, rng,
-                               env_offset, p->agents);
-        }
-        TG_LAUNCH_CHECK("tg_fused_rollout_on");
-        return TG_OK;
-    }
-    if (d_ptab != nullptr) {           // tg_fused_rollout_dr: the PerEnv instantiation with the parameter table
-        auto kern_dr = fused_rollout_kernel<PerEnv<Env>, H, NT, WPW>;
-        static LdsOptIn opt_in_dr;
-        if (int rc = reserve_dynamic_lds((const void*)kern_dr, shmem, opt_in_dr, "tg_fused_rollout_dr")) return rc;
-        hipLaunchKernelGGL(kern_dr, grid, dim3(64 * WPW), shmem, st, per_env_table(p, d_ptab), (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew,
-                           tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg, rng, env_offset, p->agents);
-        TG_LAUNCH_CHECK("tg_fused_rollout_dr");
-        return TG_OK;
-    }
-    auto kern = fused_rollout_kernel<Env, H, NT, WPW>;
-    static LdsOptIn opt_in;
-    if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_fused_rollout")) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WPW), shmem, st, c, (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask,
-                       tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg, rng, env_offset, p->agents);
-    TG_LAUNCH_CHECK("tg_fused_rollout");
-    return TG_OK;
-}
-
-// ---- control decimation (tg_fused_rollout_sub): the Substepped instantiations, ObsNormed<> around them when the table is given ----
-template <typename EnvK, int H, int NT, int WPW>
-static int fused_launch_sub_one(const typename EnvK::C& arg, size_t shmem, const tg_traj* tr, const void* wfrag, const float* bias, int n_hh,
-                                const SigmaF& sg, const uint64_t* rng, int64_t env_offset, int t0, int t1, int agents, hipStream_t st) {
     auto kern = fused_rollout_kernel<EnvK, H, NT, WPW>;
-    static LdsOptIn opt_in;                            // (one per instantiation of this template: one per kernel)
-    if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_fused_rollout_sub")) return rc;
+    static LdsOptIn opt_in;
+    if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, label)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(tr->n, 32 * NT * WPW)), dim3(64 * WPW), shmem, st, arg, (float*)tr->d_obs, tr->d_act,
                        (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, (const uint4*)wfrag, bias, n_hh, sg, rng, env_offset,
                        agents);
-    TG_LAUNCH_CHECK("tg_fused_rollout_sub");
+    TG_LAUNCH_CHECK(label);
     return TG_OK;
 }
 
+// The kernel instantiation that the variant names (with_env_variant, env_dynamics.hpp): any of the eight.
 template <template <typename> class EnvT, int H, int NT, int WPW>
-static int fused_launch_sub(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, int32_t k, const tg_traj* tr,
-                            const void* wfrag, const float* bias, int n_hh, const float* sigma, const uint64_t* rng, int64_t env_offset, int t0,
-                            int t1, hipStream_t st) {
+static int fused_launch(const char* label, const EnvVariant& v, const tg_traj* tr, const void* wfrag, const float* bias, int n_hh,
+                        const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, hipStream_t st) {
     using Env = EnvT<float>;
-    constexpr int KS = H / 16;
     SigmaF sg;
     memset(&sg, 0, sizeof(sg));
-    for (int q = 0; q < Env::A; ++q) sg.v[q] = sigma[q];
-    const size_t shmem = (size_t)((NT == 1 && WPW == 4) ? 3 : 4) * KS * 1024 + (size_t)(n_hh + 2) * H * sizeof(float) +
-                         (size_t)WPW * 64 * 32 * 2 + 4 * WPW;
-    const SubstepArg<typename Env::C> c{Env::C::make(*p), k};
-    const SubstepArg<PerEnvTable> pe{per_env_table(p, d_ptab), k};
-    const ObsNormTable on{d_obs_norm, clip};
-#define TG_SUB_TAIL shmem, tr, wfrag, bias, n_hh, sg, rng, env_offset, t0, t1, p->agents, st
-    if (d_obs_norm != nullptr && d_ptab != nullptr)
-        return fused_launch_sub_one<ObsNormed<Substepped<PerEnv<Env>>>, H, NT, WPW>(ObsNormArg<SubstepArg<PerEnvTable>>{pe, on}, TG_SUB_TAIL);
-    if (d_obs_norm != nullptr)
-        return fused_launch_sub_one<ObsNormed<Substepped<Env>>, H, NT, WPW>(ObsNormArg<SubstepArg<typename Env::C>>{c, on}, TG_SUB_TAIL);
-    if (d_ptab != nullptr) return fused_launch_sub_one<Substepped<PerEnv<Env>>, H, NT, WPW>(pe, TG_SUB_TAIL);
-    return fused_launch_sub_one<Substepped<Env>, H, NT, WPW>(c, TG_SUB_TAIL);
-#undef TG_SUB_TAIL
+    for (int k = 0; k < Env::A; ++k) sg.v[k] = sigma[k];
+    return with_env_variant<Env, true>(v, [&](auto tag, const auto& arg) -> int {
+        return fused_launch_one<typename decltype(tag)::type, H, NT, WPW>(label, arg, tr, wfrag, bias, n_hh, sg, rng, env_offset, t0, t1,
+                                                                          v.p->agents, st);
+    });
 }
 
 }  // namespace tg
@@ -444,28 +387,32 @@ using namespace tg;
 
 extern "C" {
 
-static int fused_rollout_impl(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
-                              int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
-                              int32_t t_begin, int32_t t_end, void* stream) {
-    TG_REQUIRE(p && tr && d_wfrag && d_bias && sigma && d_rng, "tg_fused_rollout: null pointer");
-    TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_fused_rollout: null trajectory pointer");
-    TG_REQUIRE(tr->dtype == TG_F32, "tg_fused_rollout: float32 trajectories only");
-    TG_REQUIRE(tr->n > 0 && tr->horizon == p->max_steps, "tg_fused_rollout: horizon %d != env.max_steps %d", tr->horizon,
-               p->max_steps);
-    TG_REQUIRE(0 <= t_begin && t_begin <= t_end && t_end <= tr->horizon, "tg_fused_rollout: bad step range [%d, %d)", t_begin,
-               t_end);
-    TG_REQUIRE(n_hidden_layers >= 1 && n_hidden_layers <= 16, "tg_fused_rollout: %d hidden layers unsupported", n_hidden_layers);
+// `who`: the name in the argument messages (the plain entry's through `_dr` and `_on`, the entry's own through `_sub`); `label`: the
+// entry point's own name, in the launch checks.  Through `_sub`, `v.p` describes the physics clock (substeps_check).
+static int fused_rollout_impl(const char* who, const char* label, const EnvVariant& v, const tg_traj* tr, const void* d_wfrag,
+                              const float* d_bias, int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng,
+                              int64_t env_offset, int32_t t_begin, int32_t t_end, void* stream) {
+    const tg_env_params* p = v.p;
+    TG_REQUIRE(p && tr && d_wfrag && d_bias && sigma && d_rng, "%s: null pointer", who);
+    TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "%s: null trajectory pointer", who);
+    if (v.sub)
+        if (int rc = substeps_check(who, p, tr, v.substeps)) return rc;
+    TG_REQUIRE(v.d_obs_norm == nullptr || v.clip > 0.0f, "%s: clip %g (a number > 0; +inf: no clamp)", who, (double)v.clip);
+    TG_REQUIRE(tr->dtype == TG_F32, "%s: float32 trajectories only", who);
+    if (!v.sub) TG_REQUIRE(tr->n > 0 && tr->horizon == p->max_steps, "%s: horizon %d != env.max_steps %d", who, tr->horizon, p->max_steps);
+    TG_REQUIRE(tr->n > 0 && 0 <= t_begin && t_begin <= t_end && t_end <= tr->horizon, "%s: bad step range [%d, %d)", who, t_begin, t_end);
+    TG_REQUIRE(n_hidden_layers >= 1 && n_hidden_layers <= 16, "%s: %d hidden layers unsupported", who, n_hidden_layers);
     TG_REQUIRE(p->agents <= 1 || (p->agents <= 32 && (p->agents & (p->agents - 1)) == 0 && tr->n % p->agents == 0),
-               "tg_fused_rollout: agents=%d must be a power of two <= 32 dividing n", p->agents);
+               "%s: agents=%d must be a power of two <= 32 dividing n", who, p->agents);
     if (t_begin == t_end) return TG_OK;
     const int n_hh = n_hidden_layers - 1;
     hipStream_t st = (hipStream_t)stream;
     // variant: 0 = NT 1 x 8 waves (default), 1 = NT 1 x 4 waves (two workgroups per CU; default below 32,768 envs, where
     // it gives twice as many workgroups).  (NT 2 x 4 waves was measured slower at every size, DESIGN_HISTORY: not instantiated.)
     const int variant = tr->n < 32768 ? 1 : 0;
-#define CALL(E, HH)                                                                                                       \
-    (variant == 0 ? fused_launch<E, HH, 1, 8>(p, d_ptab, d_obs_norm, clip, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st) \
-                  : fused_launch<E, HH, 1, 4>(p, d_ptab, d_obs_norm, clip, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st))
+#define CALL(E, HH)                                                                                                                \
+    (variant == 0 ? fused_launch<E, HH, 1, 8>(label, v, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st) \
+                  : fused_launch<E, HH, 1, 4>(label, v, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, t_begin, t_end, st))
     switch (p->env_id * 1000 + hidden) {
         case TG_ENV_CARTPOLE * 1000 + 128: return CALL(CartPoleEnv, 128);
         case TG_ENV_CARTPOLE * 1000 + 256: return CALL(CartPoleEnv, 256);
@@ -473,11 +420,11 @@ static int fused_rollout_impl(const tg_env_params* p, const double* d_ptab, cons
         case TG_ENV_QUADPOLE2D * 1000 + 256: return CALL(QuadPole2DEnv, 256);
         case TG_ENV_QUADPOLE * 1000 + 128: return CALL(QuadPoleEnv, 128);
         case TG_ENV_QUADPOLE * 1000 + 256: return CALL(QuadPoleEnv, 256);
-        case TG_ENV_PENDULUM * 1000 + 128: return CALL(PendulumEnv, 128);
+        case TG_ENV_PENDULUM * 1000 + 128: return CALL(PendulumEnv, 128);      // (never through `_sub`: substeps_check)
         case TG_ENV_PENDULUM * 1000 + 256: return CALL(PendulumEnv, 256);
         default:
-            return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout: env %d with hidden width %d is not instantiated "
-                             "(widths 128 and 256)", p->env_id, hidden);
+            return set_error(TG_ERR_UNSUPPORTED, "%s: env %d with hidden width %d is not instantiated (widths 128 and 256)", who, p->env_id,
+                             hidden);
     }
 #undef CALL
 }
@@ -485,14 +432,16 @@ static int fused_rollout_impl(const tg_env_params* p, const double* d_ptab, cons
 int tg_fused_rollout(const tg_env_params* p, const tg_traj* tr, const void* d_wfrag, const float* d_bias, int32_t hidden,
                      int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t t_begin,
                      int32_t t_end, void* stream) {
-    return fused_rollout_impl(p, nullptr, nullptr, 0.0f, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
+    return fused_rollout_impl("tg_fused_rollout", "tg_fused_rollout", EnvVariant{p, nullptr, nullptr, 0.0f, 1, false}, tr, d_wfrag, d_bias, hidden,
+                              n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
 }
 
 int tg_fused_rollout_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
                         int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                         int32_t t_begin, int32_t t_end, void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_fused_rollout_dr: null parameter table");
-    return fused_rollout_impl(p, d_ptab, nullptr, 0.0f, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
+    return fused_rollout_impl("tg_fused_rollout", "tg_fused_rollout_dr", EnvVariant{p, d_ptab, nullptr, 0.0f, 1, false}, tr, d_wfrag, d_bias, hidden,
+                              n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
 }
 
 int tg_fused_rollout_on(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
@@ -500,42 +449,15 @@ int tg_fused_rollout_on(const tg_env_params* p, const double* d_ptab, const tg_t
                         int32_t t_begin, int32_t t_end, const float* d_obs_norm, float clip, void* stream) {
     TG_REQUIRE(d_obs_norm != nullptr, "tg_fused_rollout_on: null observation-normalisation table");
     TG_REQUIRE(clip > 0.0f, "tg_fused_rollout_on: clip %g (a number > 0; +inf: no clamp)", (double)clip);
-    return fused_rollout_impl(p, d_ptab, d_obs_norm, clip, tr, d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end,
-                              stream);
+    return fused_rollout_impl("tg_fused_rollout", "tg_fused_rollout_on", EnvVariant{p, d_ptab, d_obs_norm, clip, 1, false}, tr, d_wfrag, d_bias,
+                              hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
 }
 
 int tg_fused_rollout_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
                          int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                          int32_t t_begin, int32_t t_end, const float* d_obs_norm, float clip, int32_t substeps, void* stream) {
-    TG_REQUIRE(p && tr && d_wfrag && d_bias && sigma && d_rng, "tg_fused_rollout_sub: null pointer");
-    TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_fused_rollout_sub: null trajectory pointer");
-    if (int rc = substeps_check("tg_fused_rollout_sub", p, tr, substeps)) return rc;
-    TG_REQUIRE(d_obs_norm == nullptr || clip > 0.0f, "tg_fused_rollout_sub: clip %g (a number > 0; +inf: no clamp)", (double)clip);
-    TG_REQUIRE(tr->dtype == TG_F32, "tg_fused_rollout_sub: float32 trajectories only");
-    TG_REQUIRE(tr->n > 0 && 0 <= t_begin && t_begin <= t_end && t_end <= tr->horizon, "tg_fused_rollout_sub: bad step range [%d, %d)", t_begin,
-               t_end);
-    TG_REQUIRE(n_hidden_layers >= 1 && n_hidden_layers <= 16, "tg_fused_rollout_sub: %d hidden layers unsupported", n_hidden_layers);
-    if (t_begin == t_end) return TG_OK;
-    const int n_hh = n_hidden_layers - 1;
-    hipStream_t st = (hipStream_t)stream;
-    const int variant = tr->n < 32768 ? 1 : 0;          // (tg_fused_rollout's choice)
-#define CALL(E, HH)                                                                                                                          \
-    (variant == 0 ? fused_launch_sub<E, HH, 1, 8>(p, d_ptab, d_obs_norm, clip, substeps, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, \
-                                                  t_begin, t_end, st)                                                                        \
-                  : fused_launch_sub<E, HH, 1, 4>(p, d_ptab, d_obs_norm, clip, substeps, tr, d_wfrag, d_bias, n_hh, sigma, d_rng, env_offset, \
-                                                  t_begin, t_end, st))
-    switch (p->env_id * 1000 + hidden) {
-        case TG_ENV_CARTPOLE * 1000 + 128: return CALL(CartPoleEnv, 128);
-        case TG_ENV_CARTPOLE * 1000 + 256: return CALL(CartPoleEnv, 256);
-        case TG_ENV_QUADPOLE2D * 1000 + 128: return CALL(QuadPole2DEnv, 128);
-        case TG_ENV_QUADPOLE2D * 1000 + 256: return CALL(QuadPole2DEnv, 256);
-        case TG_ENV_QUADPOLE * 1000 + 128: return CALL(QuadPoleEnv, 128);
-        case TG_ENV_QUADPOLE * 1000 + 256: return CALL(QuadPoleEnv, 256);
-        default:
-            return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_sub: env %d with hidden width %d is not instantiated "
-                             "(widths 128 and 256)", p->env_id, hidden);
-    }
-#undef CALL
+    return fused_rollout_impl("tg_fused_rollout_sub", "tg_fused_rollout_sub", EnvVariant{p, d_ptab, d_obs_norm, clip, substeps, true}, tr, d_wfrag,
+                              d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
 }
 
 }  // extern "C"

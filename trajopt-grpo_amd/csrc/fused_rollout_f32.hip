@@ -428,112 +428,46 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
     if (Env::kBalanceTerminates && in_range && alive) len[i] = -balanced_steps;   // a later segment [t1, ..) picks the count up
 }
 
+// The kernel instantiation that the variant names (with_env_variant, env_dynamics.hpp), at 16 or 32 envs per workgroup.
+// `who`: the name in the launch check and the refusals (the plain entry's, or tg_fused_rollout_f32_sub's).
 template <template <typename> class EnvT, int H, int NHH, int kAct>
-static int fused_f32_launch(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const float* wstream, const float* tab, const float* sigma,
+static int fused_f32_launch(const char* who, const EnvVariant& v, const tg_traj* tr, const float* wstream, const float* tab, const float* sigma,
                             const uint64_t* rng, int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
     using Env = EnvT<float>;
     constexpr int WPW = H / 32, A = Env::A;
-    auto c = Env::C::make(*p);
     SigmaF32 sg;
     memset(&sg, 0, sizeof(sg));
     for (int k = 0; k < A; ++k) sg.v[k] = sigma[k];
     static_assert(sizeof(float) * ((NHH + 1) * H + 4 * H + 4 + 2 * H * 32 + 2 * 4 * 2 * WPW * 32) <= 64 * 1024, "LDS budget");
-    // d_obs_norm != NULL: the ObsNormed instantiation (tg_fused_rollout_f32_on); d_ptab != NULL: the PerEnv one; both: both
-#define TG_F32_LAUNCH(KERNEL, ENVS)                                                                                                           \
-    do {                                                                                                                                      \
-        const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * ENVS + 2 * A * (64 / ENVS) * WPW * ENVS);           \
-        const dim3 grid((unsigned)ceil_div(tr->n, ENVS));                                                                                     \
-        const ObsNormTable on{d_obs_norm, clip};                                                                                              \
-        if (d_obs_norm != nullptr && d_ptab != nullptr)                                                                                       \
-            hipLaunchKernelGGL((KERNEL<ObsNormed<PerEnv<Env>>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st,                               \
-                               ObsNormArg<PerEnvTable>{per_env_table(p, d_ptab), on}, TG_F32_TAIL);                                           \
-        else if (d_obs_norm != nullptr)                                                                                                       \
-            hipLaunchKernelGGL((KERNEL<ObsNormed<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, ObsNormArg<typename Env::C>{c, on},    \
-                               TG_F32_TAIL);                                                                                                  \
-        else if (d_ptab != nullptr)                                                                                                           \
-            hipLaunchKernelGGL((KERNEL<PerEnv<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, per_env_table(p, d_ptab), TG_F32_TAIL);  \
-        else                                                                                                                                  \
-            hipLaunchKernelGGL((KERNEL<Env, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, TG_F32_TAIL);                                 \
-    } while (0)
-#define TG_F32_TAIL                                                                                                                     \
-    (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset, \
-        p->agents
-    if (block_envs == 16) TG_F32_LAUNCH(fused_rollout_f32x16_kernel, 16);
-    else TG_F32_LAUNCH(fused_rollout_f32_kernel, 32);
-#undef TG_F32_TAIL
-#undef TG_F32_LAUNCH
-    TG_LAUNCH_CHECK("tg_fused_rollout_f32");
-    return TG_OK;
+    return with_env_variant<Env, true>(v, [&](auto tag, const auto& arg) -> int {
+        using EnvK = typename decltype(tag)::type;
+        auto launch = [&](auto kernel, int envs) {
+            const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * envs + 2 * A * (64 / envs) * WPW * envs);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(tr->n, envs)), dim3(64 * WPW), shmem, st, arg, (float*)tr->d_obs, tr->d_act,
+                               (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset,
+                               v.p->agents);
+        };
+        if (block_envs == 16) launch(fused_rollout_f32x16_kernel<EnvK, H, NHH, kAct>, 16);
+        else launch(fused_rollout_f32_kernel<EnvK, H, NHH, kAct>, 32);
+        TG_LAUNCH_CHECK(who);
+        return TG_OK;
+    });
 }
 
 template <template <typename> class EnvT, int kAct>
-static int fused_f32_dispatch(int hidden, int n_hh, const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const float* wstream, const float* tab,
-                              const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
+static int fused_f32_dispatch(const char* who, int hidden, int n_hh, const EnvVariant& v, const tg_traj* tr, const float* wstream,
+                              const float* tab, const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1, int block_envs,
+                              hipStream_t st) {
 #define TG_F32_CASE(HH, NN) \
-    case HH * 10 + NN: return fused_f32_launch<EnvT, HH, NN, kAct>(p, d_ptab, d_obs_norm, clip, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
+    case HH * 10 + NN: return fused_f32_launch<EnvT, HH, NN, kAct>(who, v, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
     switch (hidden * 10 + n_hh) {
         TG_F32_CASE(64, 0) TG_F32_CASE(64, 1) TG_F32_CASE(64, 2) TG_F32_CASE(64, 3)
         TG_F32_CASE(128, 0) TG_F32_CASE(128, 1) TG_F32_CASE(128, 2) TG_F32_CASE(128, 3)
         default: break;
     }
 #undef TG_F32_CASE
-    return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_f32: hidden width %d with %d hidden layers is not instantiated "
-                     "(widths 64 / 128, 1..4 hidden layers)", hidden, n_hh + 1);
-}
-
-// ---- control decimation (tg_fused_rollout_f32_sub): the Substepped instantiations, ObsNormed<> around them when the table is given ----
-template <template <typename> class EnvT, int H, int NHH, int kAct>
-static int fused_f32_launch_sub(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, int32_t k, const tg_traj* tr,
-                                const float* wstream, const float* tab, const float* sigma, const uint64_t* rng, int64_t env_offset, int t0, int t1,
-                                int block_envs, hipStream_t st) {
-    using Env = EnvT<float>;
-    constexpr int WPW = H / 32, A = Env::A;
-    SigmaF32 sg;
-    memset(&sg, 0, sizeof(sg));
-    for (int q = 0; q < A; ++q) sg.v[q] = sigma[q];
-    const SubstepArg<typename Env::C> c{Env::C::make(*p), k};
-    const SubstepArg<PerEnvTable> pe{per_env_table(p, d_ptab), k};
-    const ObsNormTable on{d_obs_norm, clip};
-#define TG_F32_TAIL                                                                                                                     \
-    (float*)tr->d_obs, tr->d_act, (float*)tr->d_rew, tr->d_mask, tr->d_len, tr->n, tr->horizon, t0, t1, wstream, tab, sg, rng, env_offset, \
-        p->agents
-#define TG_F32_LAUNCH(KERNEL, ENVS)                                                                                                           \
-    do {                                                                                                                                      \
-        const size_t shmem = sizeof(float) * ((size_t)(NHH + 1) * H + 4 * H + 4 + 2 * H * ENVS + 2 * A * (64 / ENVS) * WPW * ENVS);           \
-        const dim3 grid((unsigned)ceil_div(tr->n, ENVS));                                                                                     \
-        if (d_obs_norm != nullptr && d_ptab != nullptr)                                                                                       \
-            hipLaunchKernelGGL((KERNEL<ObsNormed<Substepped<PerEnv<Env>>>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st,                   \
-                               ObsNormArg<SubstepArg<PerEnvTable>>{pe, on}, TG_F32_TAIL);                                                     \
-        else if (d_obs_norm != nullptr)                                                                                                       \
-            hipLaunchKernelGGL((KERNEL<ObsNormed<Substepped<Env>>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st,                           \
-                               ObsNormArg<SubstepArg<typename Env::C>>{c, on}, TG_F32_TAIL);                                                  \
-        else if (d_ptab != nullptr)                                                                                                           \
-            hipLaunchKernelGGL((KERNEL<Substepped<PerEnv<Env>>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, pe, TG_F32_TAIL);            \
-        else                                                                                                                                  \
-            hipLaunchKernelGGL((KERNEL<Substepped<Env>, H, NHH, kAct>), grid, dim3(64 * WPW), shmem, st, c, TG_F32_TAIL);                     \
-    } while (0)
-    if (block_envs == 16) TG_F32_LAUNCH(fused_rollout_f32x16_kernel, 16);
-    else TG_F32_LAUNCH(fused_rollout_f32_kernel, 32);
-#undef TG_F32_TAIL
-#undef TG_F32_LAUNCH
-    TG_LAUNCH_CHECK("tg_fused_rollout_f32_sub");
-    return TG_OK;
-}
-
-template <template <typename> class EnvT, int kAct>
-static int fused_f32_dispatch_sub(int hidden, int n_hh, const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, int32_t k,
-                                  const tg_traj* tr, const float* wstream, const float* tab, const float* sigma, const uint64_t* rng,
-                                  int64_t env_offset, int t0, int t1, int block_envs, hipStream_t st) {
-#define TG_F32_CASE(HH, NN) \
-    case HH * 10 + NN: return fused_f32_launch_sub<EnvT, HH, NN, kAct>(p, d_ptab, d_obs_norm, clip, k, tr, wstream, tab, sigma, rng, env_offset, t0, t1, block_envs, st);
-    switch (hidden * 10 + n_hh) {
-        TG_F32_CASE(64, 0) TG_F32_CASE(64, 1) TG_F32_CASE(64, 2) TG_F32_CASE(64, 3)
-        TG_F32_CASE(128, 0) TG_F32_CASE(128, 1) TG_F32_CASE(128, 2) TG_F32_CASE(128, 3)
-        default: break;
-    }
-#undef TG_F32_CASE
-    return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_f32_sub: hidden width %d with %d hidden layers is not instantiated "
-                     "(widths 64 / 128, 1..4 hidden layers)", hidden, n_hh + 1);
+    return set_error(TG_ERR_UNSUPPORTED, "%s: hidden width %d with %d hidden layers is not instantiated (widths 64 / 128, 1..4 hidden layers)",
+                     who, hidden, n_hh + 1);
 }
 
 }  // namespace tg
@@ -551,64 +485,73 @@ int tg_fused_rollout_f32_block_envs(int64_t n, int32_t agents) {
     return (n <= (int64_t)16 * device_cus() && agents <= 16) ? 16 : 32;
 }
 
-static int fused_rollout_f32(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
+// `who`: the name in every message (tg_fused_rollout_f32 through the plain, `_act`, `_dr` and `_on` entries, the entry's own through
+// `_sub`).  Through `_sub`, `v.p` describes the physics clock (substeps_check).
+static int fused_rollout_f32(const char* who, const EnvVariant& v, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
                              int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                              int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
-    TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "tg_fused_rollout_f32_act: unknown activation %d", activation);
-    TG_REQUIRE(p && tr && d_wstream && d_tab && sigma && d_rng, "tg_fused_rollout_f32: null pointer");
-    TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_fused_rollout_f32: null trajectory pointer");
-    TG_REQUIRE(tr->dtype == TG_F32, "tg_fused_rollout_f32: float32 trajectories only");
-    TG_REQUIRE(tr->n > 0 && tr->horizon == p->max_steps, "tg_fused_rollout_f32: horizon %d != env.max_steps %d", tr->horizon,
-               p->max_steps);
-    TG_REQUIRE(0 <= t_begin && t_begin <= t_end && t_end <= tr->horizon, "tg_fused_rollout_f32: bad step range [%d, %d)", t_begin,
-               t_end);
-    TG_REQUIRE(block_envs == 16 || block_envs == 32, "tg_fused_rollout_f32: %d envs per workgroup (16 or 32: the layout of d_wstream)", block_envs);
+    const tg_env_params* p = v.p;
+    TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "%s: unknown activation %d", v.sub ? who : "tg_fused_rollout_f32_act",
+               activation);
+    TG_REQUIRE(p && tr && d_wstream && d_tab && sigma && d_rng, "%s: null pointer", who);
+    TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "%s: null trajectory pointer", who);
+    if (v.sub)
+        if (int rc = substeps_check(who, p, tr, v.substeps)) return rc;
+    TG_REQUIRE(v.d_obs_norm == nullptr || v.clip > 0.0f, "%s: clip %g (a number > 0; +inf: no clamp)", who, (double)v.clip);
+    TG_REQUIRE(tr->dtype == TG_F32, "%s: float32 trajectories only", who);
+    if (!v.sub) TG_REQUIRE(tr->n > 0 && tr->horizon == p->max_steps, "%s: horizon %d != env.max_steps %d", who, tr->horizon, p->max_steps);
+    TG_REQUIRE(tr->n > 0 && 0 <= t_begin && t_begin <= t_end && t_end <= tr->horizon, "%s: bad step range [%d, %d)", who, t_begin, t_end);
+    TG_REQUIRE(block_envs == 16 || block_envs == 32, "%s: %d envs per workgroup (16 or 32: the layout of d_wstream)", who, block_envs);
     TG_REQUIRE(p->agents <= 1 || (p->agents <= block_envs && (p->agents & (p->agents - 1)) == 0 && tr->n % p->agents == 0),
-               "tg_fused_rollout_f32: agents=%d must be a power of two <= %d dividing n", p->agents, block_envs);
+               "%s: agents=%d must be a power of two <= %d dividing n", who, p->agents, block_envs);
     if (t_begin == t_end) return TG_OK;
     const int n_hh = n_hidden_layers - 1;
     hipStream_t st = (hipStream_t)stream;
     switch (activation * 16 + p->env_id) {
 #define TG_F32_ENV(ACT, ID, ENV)                                                                                                      \
     case ACT * 16 + ID:                                                                                                               \
-        return fused_f32_dispatch<ENV, ACT>(hidden, n_hh, p, d_ptab, d_obs_norm, clip, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
+        return fused_f32_dispatch<ENV, ACT>(who, hidden, n_hh, v, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
         TG_F32_ENV(TG_ACT_RELU, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
         TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE, QuadPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_PENDULUM, PendulumEnv)
         TG_F32_ENV(TG_ACT_TANH, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
         TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE, QuadPoleEnv) TG_F32_ENV(TG_ACT_TANH, TG_ENV_PENDULUM, PendulumEnv)
 #undef TG_F32_ENV
-        default: return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_f32: env %d is not instantiated", p->env_id);
+        default: return set_error(TG_ERR_UNSUPPORTED, "%s: env %d is not instantiated", who, p->env_id);
     }
+}
+
+static EnvVariant f32_variant(const tg_env_params* p, const double* d_ptab, const float* d_obs_norm, float clip) {
+    return EnvVariant{p, d_ptab, d_obs_norm, clip, 1, false};
 }
 
 int tg_fused_rollout_f32(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
                          int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                          int32_t t_begin, int32_t t_end, void* stream) {
-    return fused_rollout_f32(p, nullptr, nullptr, 0.0f, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
-                             TG_ACT_RELU, stream);
+    return fused_rollout_f32("tg_fused_rollout_f32", f32_variant(p, nullptr, nullptr, 0.0f), tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs,
+                             sigma, d_rng, env_offset, t_begin, t_end, TG_ACT_RELU, stream);
 }
 
 int tg_fused_rollout_f32_act(const tg_env_params* p, const tg_traj* tr, const float* d_wstream, const float* d_tab, int32_t hidden,
                              int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
                              int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
-    return fused_rollout_f32(p, nullptr, nullptr, 0.0f, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
-                             activation, stream);
+    return fused_rollout_f32("tg_fused_rollout_f32", f32_variant(p, nullptr, nullptr, 0.0f), tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs,
+                             sigma, d_rng, env_offset, t_begin, t_end, activation, stream);
 }
 
 int tg_fused_rollout_f32_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
                             int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
                             int64_t env_offset, int32_t t_begin, int32_t t_end, void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_fused_rollout_f32_dr: null parameter table");
-    return fused_rollout_f32(p, d_ptab, nullptr, 0.0f, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
-                             TG_ACT_RELU, stream);
+    return fused_rollout_f32("tg_fused_rollout_f32", f32_variant(p, d_ptab, nullptr, 0.0f), tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs,
+                             sigma, d_rng, env_offset, t_begin, t_end, TG_ACT_RELU, stream);
 }
 
 int tg_fused_rollout_f32_act_dr(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
                                 int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
                                 int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, void* stream) {
     TG_REQUIRE(d_ptab != nullptr, "tg_fused_rollout_f32_act_dr: null parameter table");
-    return fused_rollout_f32(p, d_ptab, nullptr, 0.0f, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end,
-                             activation, stream);
+    return fused_rollout_f32("tg_fused_rollout_f32", f32_variant(p, d_ptab, nullptr, 0.0f), tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs,
+                             sigma, d_rng, env_offset, t_begin, t_end, activation, stream);
 }
 
 int tg_fused_rollout_f32_on(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
@@ -617,38 +560,16 @@ int tg_fused_rollout_f32_on(const tg_env_params* p, const double* d_ptab, const 
                             void* stream) {
     TG_REQUIRE(d_obs_norm != nullptr, "tg_fused_rollout_f32_on: null observation-normalisation table");
     TG_REQUIRE(clip > 0.0f, "tg_fused_rollout_f32_on: clip %g (a number > 0; +inf: no clamp)", (double)clip);
-    return fused_rollout_f32(p, d_ptab, d_obs_norm, clip, tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset,
-                             t_begin, t_end, activation, stream);
+    return fused_rollout_f32("tg_fused_rollout_f32", f32_variant(p, d_ptab, d_obs_norm, clip), tr, d_wstream, d_tab, hidden, n_hidden_layers, block_envs,
+                             sigma, d_rng, env_offset, t_begin, t_end, activation, stream);
 }
 
 int tg_fused_rollout_f32_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
                              int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
                              int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, const float* d_obs_norm, float clip,
                              int32_t substeps, void* stream) {
-    TG_REQUIRE(activation == TG_ACT_RELU || activation == TG_ACT_TANH, "tg_fused_rollout_f32_sub: unknown activation %d", activation);
-    TG_REQUIRE(p && tr && d_wstream && d_tab && sigma && d_rng, "tg_fused_rollout_f32_sub: null pointer");
-    TG_REQUIRE(tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "tg_fused_rollout_f32_sub: null trajectory pointer");
-    if (int rc = substeps_check("tg_fused_rollout_f32_sub", p, tr, substeps)) return rc;
-    TG_REQUIRE(d_obs_norm == nullptr || clip > 0.0f, "tg_fused_rollout_f32_sub: clip %g (a number > 0; +inf: no clamp)", (double)clip);
-    TG_REQUIRE(tr->dtype == TG_F32, "tg_fused_rollout_f32_sub: float32 trajectories only");
-    TG_REQUIRE(tr->n > 0 && 0 <= t_begin && t_begin <= t_end && t_end <= tr->horizon, "tg_fused_rollout_f32_sub: bad step range [%d, %d)",
-               t_begin, t_end);
-    TG_REQUIRE(block_envs == 16 || block_envs == 32, "tg_fused_rollout_f32_sub: %d envs per workgroup (16 or 32: the layout of d_wstream)",
-               block_envs);
-    if (t_begin == t_end) return TG_OK;
-    const int n_hh = n_hidden_layers - 1;
-    hipStream_t st = (hipStream_t)stream;
-    switch (activation * 16 + p->env_id) {
-#define TG_F32_ENV(ACT, ID, ENV)                                                                                                      \
-    case ACT * 16 + ID:                                                                                                               \
-        return fused_f32_dispatch_sub<ENV, ACT>(hidden, n_hh, p, d_ptab, d_obs_norm, clip, substeps, tr, d_wstream, d_tab, sigma, d_rng, env_offset, t_begin, t_end, block_envs, st);
-        TG_F32_ENV(TG_ACT_RELU, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
-        TG_F32_ENV(TG_ACT_RELU, TG_ENV_QUADPOLE, QuadPoleEnv)
-        TG_F32_ENV(TG_ACT_TANH, TG_ENV_CARTPOLE, CartPoleEnv) TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE2D, QuadPole2DEnv)
-        TG_F32_ENV(TG_ACT_TANH, TG_ENV_QUADPOLE, QuadPoleEnv)
-#undef TG_F32_ENV
-        default: return set_error(TG_ERR_UNSUPPORTED, "tg_fused_rollout_f32_sub: env %d is not instantiated", p->env_id);
-    }
+    return fused_rollout_f32("tg_fused_rollout_f32_sub", EnvVariant{p, d_ptab, d_obs_norm, clip, substeps, true}, tr, d_wstream, d_tab, hidden,
+                             n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end, activation, stream);
 }
 
 }  // extern "C"
