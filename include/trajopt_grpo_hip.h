@@ -958,6 +958,44 @@ int  tg_fused_rollout_f32_sub(const tg_env_params* p, const double* d_ptab, cons
                               int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, const float* d_obs_norm, float clip,
                               int32_t substeps, void* stream);
 
+/* ---- Actuator lag: a first-order rotor lag in front of every physics step (additions to ABI 13) ----
+ * Build-defined, like `_sub` and `_dr`.  p->p[10] = tau, the motor time constant in seconds (slot 10 is read by no env's constants;
+ * with a parameter table it is row 10, column i for env slot i).  Every env slot carries a motor state m[A] in float32, in
+ * normalised action units (0 = hover thrust), 0 at the reset.  With dt = p->timestep (the physics step),
+ *     alpha = (float)(dt / (tau_i + dt))          one IEEE double add and divide, rounded to float once
+ * and in front of EVERY call of the env's own step -- each of the up to `substeps` calls of a control step; a lane that has stopped
+ * filters no more --
+ *     m[k] <- m[k] + alpha * (clip(a[k], -1, 1) - m[k])      three float32 operations, each rounded on its own
+ * then step(state, m): the step function is untouched (m lies in [-1, 1], so its clip is the identity).  `act` records the
+ * COMMANDED action a; a teacher-forced replay takes commanded actions and filters them again.  mask, len, rewards, the Philox key
+ * and termination are those of `_sub`.
+ * d_motor: f32 [A][T+1][n], env fastest, obs's conventions: slot t = m at the start of control step t (slot 0: zeros, written by
+ * the caller), slot t + 1 = m after step t's executed physics steps while the episode carries on, else 0.
+ * The identity the tests pin: a lagged rollout is, bit for bit, tg_rollout_forced on the k T physics steps fed the filtered commands.
+ * Each entry takes the arguments of its `_sub` sibling (substeps == 1 included) plus d_motor:
+ * tg_rollout_step_lag reads slot t and writes slot t + 1; tg_rollout_forced_lag reads slot t_begin and writes every later slot of
+ * its range; the fused entries read slot t_begin, so split launches compose; tg_rollout_final_state_lag reads slot L - 1.
+ * With a parameter table the host sees only the nominal p[10]: EVERY entry of the table's row 10 must be finite and >= 0 (the
+ * caller's duty; tg_env_randomize and tg_env_param_grid keep it, their factors being finite and > 0).  A negative entry gives a gain
+ * above 1 or, at -dt, a division by zero in the lane that reads it.
+ * Limits, refused before any launch, beside those of `_sub`: envs other than QUADPOLE2D and QUADPOLE and swarm envs
+ * (TG_ERR_UNSUPPORTED); a null d_motor, a non-finite or negative p[10], p[10] == 0 without a table (TG_ERR_ARG: 0 is off). */
+int  tg_rollout_step_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean,
+                         int64_t mean_row_stride, const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t substeps,
+                         float* d_motor, void* stream);
+int  tg_rollout_forced_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end,
+                           int32_t substeps, float* d_motor, void* stream);
+int  tg_rollout_final_state_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
+                                int32_t substeps, const float* d_motor, void* stream);
+int  tg_fused_rollout_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+                          int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                          int32_t t_begin, int32_t t_end, const float* d_obs_norm, float clip, int32_t substeps, float* d_motor,
+                          void* stream);
+int  tg_fused_rollout_f32_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                              int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                              int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, const float* d_obs_norm, float clip,
+                              int32_t substeps, float* d_motor, void* stream);
+
 /* ---- PPO's prologue (algorithms/ppo.py:93-139) without a host round trip ----
  * tg_scatter_rows: d_dst[d_idx[r]] = d_src[r * src_stride] for r < rows -- the critic's values of the valid rows (the no-grad
  *   forward's padded output, column 0) back onto the zeroed [T][n] grid (ppo.py:93 evaluated on the valid rows only).

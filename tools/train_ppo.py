@@ -5,10 +5,13 @@ epoch instead of 50-80.
     python3 tools/train_ppo.py [epochs] [CartPole|Pendulum|QuadPole2D|QuadPole] [bf16|fp32] [--randomize name=lo:hi ...]
                                [--learn-std] [--normalize-obs] [--normalize-value] [--popart] [--gae] [--privileged-critic]
                                [--eval-every N] [--eval-episodes E] [--eval-sweep name=f1,f2,... ...] [--desired-kl KL]
-                               [--target-kl KL] [--kl-every N] [--substeps K]
+                               [--target-kl KL] [--kl-every N] [--substeps K] [--motor-tau SECONDS]
 
 --substeps K: control decimation (Env.substeps = K, 1..64): K physics steps of timestep / K per policy step, so the control period,
 the horizon in policy steps and the learner's cost stay what they are and only the integration gets finer.  Not for Pendulum.
+
+--motor-tau SECONDS: a first-order rotor lag (Env.motor_time_constant, e.g. 0.05) in front of every physics step; QuadPole2D and
+QuadPole only.  `--randomize motor_time_constant=0.5:2` then draws every env slot's own time constant.
 
 --desired-kl KL: the KL-adaptive learning rate (PPO(desired_kl=KL), e.g. 0.01): once per learn() the rate is divided by 1.5 when the
 measured KL between the policy before and after the updates exceeds 2 KL and multiplied by 1.5 when it is below KL / 2.
@@ -104,6 +107,27 @@ def pop_eval(argv):
     return every, episodes, sweep or None, argv
 
 
+def pop_motor_tau(argv):
+    """(--motor-tau SECONDS or 0.0, the remaining arguments); SystemExit on a value that is not a number."""
+    vals, argv = pop_valued(argv, "--motor-tau")
+    try:
+        return (float(vals[-1]) if vals else 0.0), argv
+    except ValueError:
+        raise SystemExit("--motor-tau expects a number of seconds")
+
+
+def build_env(name, ranges, substeps=1, motor_tau=0.0):
+    """The env a run trains on.  The lag is set before the ranges are: "motor_time_constant" is a randomisable name only while it is on."""
+    env = tg.environments.ENV_CLASSES[name]()
+    if motor_tau != 0.0:
+        env.motor_time_constant = motor_tau                       # (ValueError: an env without rotors, a negative or non-finite value)
+    env.randomize(ranges)
+    if substeps != 1:
+        env.substeps = substeps                                   # (ValueError: Pendulum, or K outside 1..64)
+        env.timestep = env.timestep / substeps                    # the control period stays the reference's
+    return env
+
+
 def main():
     ranges, sys.argv[1:] = pop_randomize(sys.argv[1:])
     eval_every, eval_episodes, eval_sweep, sys.argv[1:] = pop_eval(sys.argv[1:])
@@ -124,6 +148,7 @@ def main():
         substeps = int(substeps[-1]) if substeps else 1
     except ValueError:
         raise SystemExit("--substeps expects an integer")
+    motor_tau, sys.argv[1:] = pop_motor_tau(sys.argv[1:])
     learn_std = "--learn-std" in sys.argv                         # a learned per-dimension log-std instead of the fixed covariance
     sys.argv = [a for a in sys.argv if a != "--learn-std"]
     normalize_obs = "--normalize-obs" in sys.argv                 # running observation normalisation (policy.obs_norm)
@@ -155,11 +180,7 @@ def main():
                                                **({"privileged_critic": ranges} if privileged else {}))
 
     def make_env():
-        env = tg.environments.ENV_CLASSES[name]().randomize(ranges)
-        if substeps != 1:
-            env.substeps = substeps                               # (ValueError: Pendulum, or K outside 1..64)
-            env.timestep = env.timestep / substeps                # the control period stays the reference's
-        return env
+        return build_env(name, ranges, substeps, motor_tau)
 
     make_env()                                                    # (refuses a bad name, range or K before anything is allocated)
     mgr = tg.RolloutManager(make_env, pol, num_workers=64, num_episodes_per_worker=64,

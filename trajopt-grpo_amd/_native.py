@@ -298,6 +298,13 @@ SIGNATURES = {
     "tg_fused_rollout_sub": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _VP, _F, _I32, _VP]),
     "tg_fused_rollout_f32_sub": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _I32, _VP,
                                            _F, _I32, _VP]),
+    "tg_rollout_step_lag": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _I32, _VP, _I64, _P(_F), _VP, _I64, _I32, _VP, _VP]),
+    "tg_rollout_forced_lag": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _I32, _I32, _I32, _VP, _VP]),
+    "tg_rollout_final_state_lag": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _VP, _VP]),
+    "tg_fused_rollout_lag": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _VP, _F, _I32, _VP,
+                                       _VP]),
+    "tg_fused_rollout_f32_lag": (C.c_int, [_P(EnvParams), _VP, _P(Traj), _VP, _VP, _I32, _I32, _I32, _P(_F), _VP, _I64, _I32, _I32, _I32, _VP,
+                                           _F, _I32, _VP, _VP]),
     "tg_scatter_rows": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP]),
     "tg_ppo_returns": (C.c_int, [_VP, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _I64, _I32, _VP, _VP, _VP]),
     "tg_ppo_returns_boot": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _F, _F, C.c_int, _VP, _VP, _I64, _I32, _VP, _VP, _VP]),

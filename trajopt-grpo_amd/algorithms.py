@@ -1156,19 +1156,20 @@ def _value_norm_stats(stat3, moments, eps, stat_a=None) -> dict:
 
 def privileged_spec(policy, env, params=None) -> "K.N.PrivilegedSpec":
     """tg_privileged_spec of a policy's privileged_critic for `env`: column k is the mapping's k-th name (the mapping's order, not
-    p[]'s), index[k] its p[] slot (env.RANDOMIZABLE), nominal[k] the env's own value there (params: its tg_env_params, default
+    p[]'s), index[k] its p[] slot (env.parameter_slots()), nominal[k] the env's own value there (params: its tg_env_params, default
     env.native_params()), centre and scale the policy's.  ValueError names a parameter the env does not have."""
     want = policy.privileged_critic
-    unknown = [name for name in want if name not in env.RANDOMIZABLE]
+    slots = env.parameter_slots()
+    unknown = [name for name in want if name not in slots]
     if unknown:
         raise ValueError(f"privileged_critic names {unknown}, which {type(env).__name__} cannot randomise "
-                         f"(randomisable: {', '.join(env.RANDOMIZABLE)})")
+                         f"(randomisable: {', '.join(slots)})")
     if params is None:
         params = env.native_params()
     spec = K.N.PrivilegedSpec()
     spec.count = len(want)
     for k, name in enumerate(want):
-        spec.index[k] = env.RANDOMIZABLE[name]
+        spec.index[k] = slots[name]
         spec.nominal[k] = float(params.p[spec.index[k]])
         spec.center[k], spec.scale[k] = policy.privileged_center[k], policy.privileged_scale[k]
     return spec
@@ -1374,7 +1375,8 @@ class PPO(_GpuLearner):
         n, dev = traj.n, traj.mask.device
         s_final, timeout = K.rollout_final_state(params, traj, self._small("boot_state", n * traj.S, torch.float32, dev).view(n, traj.S),
                                                  self._small("boot_timeout", n, torch.uint8, dev),
-                                                 env_params=env_params, **({"substeps": substeps} if substeps != 1 else {}))
+                                                 env_params=env_params, **({"substeps": substeps} if substeps != 1 else {}),
+                                                 **({"motor": traj.motor} if getattr(traj, "motor", None) is not None else {}))
         on = getattr(self.policy, "obs_norm", None)        # (this learn()'s table: the update ran at the entry)
         if priv is not None:
             m_a = self._mlp(self.policy.actor)

@@ -76,12 +76,14 @@ template <typename Env> struct EnvTraits {
     static constexpr bool kPerEnv = false;
     static constexpr bool kObsNorm = false;
     static constexpr bool kSubsteps = false;
+    static constexpr bool kLag = false;
     using Consts = typename Env::C;
 };
 template <typename Env> struct EnvTraits<PerEnv<Env>> {
     static constexpr bool kPerEnv = true;
     static constexpr bool kObsNorm = false;
     static constexpr bool kSubsteps = false;
+    static constexpr bool kLag = false;
     using Consts = typename Env::C;
 };
 // Control decimation (the `_sub` entry points): `k` physics steps per policy step.  Substepped<Env> -- Env a plain env or PerEnv<...>,
@@ -100,8 +102,37 @@ template <typename Env> struct EnvTraits<Substepped<Env>> {
     static constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
     static constexpr bool kObsNorm = false;
     static constexpr bool kSubsteps = true;
+    static constexpr bool kLag = false;
     using Consts = typename EnvTraits<Env>::Consts;
 };
+// Actuator lag (the `_lag` entry points): a first-order rotor lag in front of every physics step.  Lagged<Env> -- Env ALWAYS a
+// Substepped<...> (also at k = 1: the lag lives in the substep loop, so it adds one instantiation per substepped one, not two), and
+// ObsNormed<> goes around it -- rides on the Env type for PerEnv's reason.  The kernel's argument becomes {Substepped's argument, the
+// motor record f32 [A][T+1][n] (env fastest; slot t = the motor state at the start of control step t), alpha}: `alpha` is the
+// filter gain of the one vehicle of a launch without a parameter table, lag_alpha(p[10], timestep) built on the host; with a table
+// the lane builds its own from row 10 (lag_alpha_of), where it builds its own constants.
+template <typename BaseC> struct LagArg {
+    BaseC base;
+    float* motor;
+    float alpha;
+};
+template <typename Env> struct Lagged : Env {
+    using C = LagArg<typename Env::C>;
+};
+template <typename Env> struct EnvTraits<Lagged<Env>> {
+    static constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
+    static constexpr bool kObsNorm = false;
+    static constexpr bool kSubsteps = true;
+    static constexpr bool kLag = true;
+    using Consts = typename EnvTraits<Env>::Consts;
+};
+constexpr int kLagSlot = 10;                                // the p[] slot (and parameter-table row) that holds the time constant
+// alpha = dt / (tau + dt), the backward-Euler gain of dm/dt = (c - m) / tau: one IEEE double add and divide, rounded to float once
+// -- the same bits on the host and in a lane (C::build relies on the same).
+__host__ __device__ static inline float lag_alpha(double tau, double dt) {
+#pragma clang fp contract(off)
+    return (float)(dt / (tau + dt));
+}
 // Running observation normalisation (the `_on` entry points of the fused rollouts).  ObsNormed<Env> -- Env a plain env or PerEnv<...>
 // -- rides on the Env type for PerEnv's reason: the kernel's argument becomes {Env's own argument, the f32 table [2][S] = {mean,
 // rstd}, the clamp}, its instantiation IS the kObsNorm = true kernel, and every existing instantiation keeps name and code.
@@ -120,15 +151,21 @@ template <typename Env> struct EnvTraits<ObsNormed<Env>> {
     static constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;
     static constexpr bool kObsNorm = true;
     static constexpr bool kSubsteps = EnvTraits<Env>::kSubsteps;
+    static constexpr bool kLag = EnvTraits<Env>::kLag;
     using Consts = typename EnvTraits<Env>::Consts;
 };
 // the env's own kernel argument (by-value constants or the parameter table) inside whatever the kernel was handed
 template <typename C> __device__ static inline const C& env_arg(const C& c) { return c; }
 template <typename B> __device__ static inline const B& env_arg(const SubstepArg<B>& c) { return c.base; }
+template <typename B> __device__ static inline const auto& env_arg(const LagArg<B>& c) { return env_arg(c.base); }
 template <typename B> __device__ static inline const auto& env_arg(const ObsNormArg<B>& c) { return env_arg(c.base); }
 // the physics steps per control step of a kSubsteps kernel, from the same argument
 template <typename B> __device__ static inline int substeps_of(const SubstepArg<B>& c) { return c.k; }
+template <typename B> __device__ static inline int substeps_of(const LagArg<B>& c) { return substeps_of(c.base); }
 template <typename B> __device__ static inline int substeps_of(const ObsNormArg<B>& c) { return substeps_of(c.base); }
+// the motor record and the uniform gain of a kLag kernel, from the same argument
+template <typename B> __device__ static inline const LagArg<B>& lag_of(const LagArg<B>& c) { return c; }
+template <typename B> __device__ static inline const auto& lag_of(const ObsNormArg<B>& c) { return lag_of(c.base); }
 // The policy's view of a state: the table's 2 S floats, read once per launch (uniform addresses: scalar loads), and the one
 // definition of the normalised observation (obs_normalize, tg_common.hpp) applied to the register-resident state where it becomes
 // the first layer's operand.  The table is per FEATURE, not per env: a compaction that moves envs between lanes moves nothing here.
@@ -152,6 +189,15 @@ __device__ static inline typename EnvTraits<Env>::Consts env_constants(const Per
 // The constants a kernel steps with: its by-value argument (kPerEnv = false), or the lane's own (kPerEnv = true).
 template <typename C> __device__ static inline const C& pick_constants(const C& uniform, const C&) { return uniform; }
 template <typename C> __device__ static inline const C& pick_constants(const PerEnvTable&, const C& own) { return own; }
+// the filter gain of env slot i of a kLag kernel: the launch's one (no table), or built from column i of row kLagSlot
+template <typename Env, typename CArg> __device__ static inline float lag_alpha_of(const CArg& c_arg, int64_t n, int64_t i) {
+    if constexpr (EnvTraits<Env>::kPerEnv) {
+        const PerEnvTable& pe = env_arg(c_arg);
+        return lag_alpha(pe.ptab[kLagSlot * n + i], pe.timestep);
+    } else {
+        return lag_of(c_arg).alpha;
+    }
+}
 static inline PerEnvTable per_env_table(const tg_env_params* p, const double* d_ptab) {
     return PerEnvTable{d_ptab, p->timestep, p->max_steps, p->time_trunc_step};
 }
@@ -165,12 +211,14 @@ struct EnvVariant {
     const float* d_obs_norm;     // non-null (the `_on` entries): ObsNormed<>, with `clip`
     float clip;
     int32_t substeps;
-    bool sub;                    // entered through a `_sub` entry: Substepped<>, also at substeps == 1
+    bool sub;                    // entered through a `_sub` or `_lag` entry: Substepped<>, also at substeps == 1
+    float* d_motor = nullptr;    // non-null (the `_lag` entries, which set `sub`): Lagged<> around Substepped<>
 };
 template <typename EnvK> struct EnvTag { using type = EnvK; };
 // Calls f(EnvTag<EnvK>{}, arg) -- arg the `typename EnvK::C` of the variant -- for the one EnvK in {Env, PerEnv<Env>, ObsNormed<..>,
-// Substepped<..>, ObsNormed<Substepped<..>>} that `v` names, and returns f's status.  kMayObsNorm / kMaySubstep = false prune the
-// wrapper at compile time (a kernel family or an env without those instantiations); a variant that asks for a pruned one is refused.
+// Substepped<..>, Lagged<Substepped<..>>, ObsNormed<Substepped<..>>, ObsNormed<Lagged<Substepped<..>>>} that `v` names, and returns
+// f's status.  kMayObsNorm / kMaySubstep / Env::kMayLag = false prune the wrapper at compile time (a kernel family or an env
+// without those instantiations); a variant that asks for a pruned one is refused.
 template <typename Env, bool kMayObsNorm, bool kMaySubstep = Env::kMaySubstep, typename F>
 static inline int with_env_variant(const EnvVariant& v, F&& f) {
     auto normed = [&](auto tag, const auto& arg) -> int {
@@ -182,8 +230,16 @@ static inline int with_env_variant(const EnvVariant& v, F&& f) {
     auto substepped = [&](auto tag, const auto& arg) -> int {
         using E = typename decltype(tag)::type;
         if (!v.sub) return normed(tag, arg);
-        if constexpr (kMaySubstep) return normed(EnvTag<Substepped<E>>{}, SubstepArg<typename E::C>{arg, v.substeps});
-        else return set_error(TG_ERR_UNSUPPORTED, "substeps are not instantiated for this env");
+        if constexpr (kMaySubstep) {
+            const SubstepArg<typename E::C> sub{arg, v.substeps};
+            if (v.d_motor == nullptr) return normed(EnvTag<Substepped<E>>{}, sub);
+            if constexpr (Env::kMayLag)
+                return normed(EnvTag<Lagged<Substepped<E>>>{},
+                              LagArg<SubstepArg<typename E::C>>{sub, v.d_motor, lag_alpha(v.p->p[kLagSlot], v.p->timestep)});
+            else return set_error(TG_ERR_UNSUPPORTED, "the actuator lag is not instantiated for this env");
+        } else {
+            return set_error(TG_ERR_UNSUPPORTED, "substeps are not instantiated for this env");
+        }
     };
     if (v.d_ptab != nullptr) return substepped(EnvTag<PerEnv<Env>>{}, per_env_table(v.p, v.d_ptab));
     return substepped(EnvTag<Env>{}, Env::C::make(*v.p));
@@ -225,6 +281,45 @@ __device__ static inline StepOut substep_loop(const R (&s)[Env::S], const float 
     return out;
 }
 
+// One control step of a kLag kernel: substep_loop with the rotor lag in front of every call.  `m` (normalised action units, 0 = hover
+// thrust) is the motor state at the start of the control step and, on return, after the executed calls:
+//   m[k] <- m[k] + alpha * (clip1(a[k]) - m[k])        (three float32 operations, each rounded on its own)
+// then Env::step(o, m, ...), the env's own step (m lies in [-1, 1]: its clip1 is the identity).  A lane that has stopped filters no
+// more; with alive == false `m` comes back as it went in.  Everything else is substep_loop's rule, word for word.
+template <typename Env, typename R, typename C>
+__device__ static inline StepOut lagged_substep_loop(const R (&s)[Env::S], const float (&a)[Env::A], const C& c, int t, int k, bool alive,
+                                                     float alpha, float (&m)[Env::A], R (&o)[Env::S], R& reward, int& count) {
+#pragma clang fp contract(off)
+    constexpr int S = Env::S, A = Env::A;
+#pragma unroll
+    for (int i = 0; i < S; ++i) o[i] = s[i];
+    StepOut out;
+    out.truncated = false; out.balanced = false;
+    R sum = (R)0;
+    int cnt = t * k;
+    bool running = alive;
+#pragma clang loop unroll(disable)
+    for (int j = 0; j < k; ++j) {
+        if (__ballot(running) == 0ull) break;
+        // (in place, and the clip recomputed from `a`, which the caller keeps anyway: nothing but m and alpha lives across the step)
+#pragma unroll
+        for (int i = 0; i < A; ++i) m[i] = running ? rn_add(m[i], rn_mul(alpha, rn_sub(clip1(a[i]), m[i]))) : m[i];
+        R nx[S], r;
+        const StepOut so = Env::step(o, m, c, t * k + j + 1, nx, r);
+        if (running) {
+            out = so;
+            sum = (j == 0) ? r : sum + r;
+            cnt = t * k + j + 1;
+#pragma unroll
+            for (int i = 0; i < S; ++i) o[i] = nx[i];
+        }
+        running = running && !so.truncated;
+    }
+    reward = sum;
+    count = cnt;
+    return out;
+}
+
 // ---------------------------------------------------------------------------
 // CartPole swing-up.  cartpole_env.py:48-49, 51-92, 138-182.
 // ---------------------------------------------------------------------------
@@ -232,6 +327,7 @@ template <typename R> struct CartPoleEnv {
     static constexpr int S = 5, A = 1;
     static constexpr bool kBalanceTerminates = false;
     static constexpr bool kMaySubstep = true;
+    static constexpr bool kMayLag = false;
     struct C {
         R mc, mp, l, g, dt;
         int max_steps, time_trunc_step;
@@ -302,6 +398,7 @@ template <typename R> struct QuadPole2DEnv {
     static constexpr int S = 10, A = 2;
     static constexpr bool kBalanceTerminates = false;
     static constexpr bool kMaySubstep = true;
+    static constexpr bool kMayLag = true;    // (rotor thrust: the one actuator the lag models)
     struct C {
         R mq_Lp, mpLp, M, g, dt, bound, balance_radius;
         float hover32, Lq_over_I32, dt32;
@@ -400,6 +497,7 @@ template <typename R> struct QuadPoleEnv {
     static constexpr int S = 20, A = 4;
     static constexpr bool kBalanceTerminates = false;
     static constexpr bool kMaySubstep = true;
+    static constexpr bool kMayLag = true;
     struct C {
         R m0, m_p, g, L, Ixx, Iyy, Izz, arm, dt, bound, tension_k, m0L, inv_m0, s22, mpL2;
         float hover32, tc32;
@@ -580,6 +678,7 @@ template <typename R> struct QuadPoleEnv {
 template <typename R> struct PendulumEnv {
     static constexpr int S = 3, A = 1;
     static constexpr bool kBalanceTerminates = true;
+    static constexpr bool kMayLag = false;
     static constexpr bool kMaySubstep = false;   // (substeps_check: the balance count kept in len counts single steps)
     struct C {
         R mgl, inv_ml2, dt;
@@ -642,3 +741,5 @@ template <typename R> struct PendulumEnv {
 };
 
 }  // namespace tg
+
+#include "lag_occupancy.hpp"

@@ -123,6 +123,13 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c_arg
     constexpr bool kPerEnv = EnvTraits<Env>::kPerEnv;        // (domain randomisation: Env = PerEnv<...>, c_arg = the parameter table)
     typename EnvTraits<Env>::Consts own;
     if constexpr (kPerEnv && kSpec) own = env_constants<Env>(env_arg(c_arg), n, ic);
+    constexpr bool kLag = EnvTraits<Env>::kLag;              // (actuator lag: slot t of the motor record in, slot t + 1 out)
+    float m[A], alpha = 0.0f;
+    if constexpr (kLag && kSpec) {
+        alpha = lag_alpha_of<Env>(c_arg, n, ic);
+#pragma unroll
+        for (int k = 0; k < A; ++k) m[k] = lag_of(c_arg).motor[(k * T1 + t) * n + ic];
+    }
     if constexpr (kSpec) {
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = obs[(k * T1 + t) * n + ic];
@@ -141,6 +148,11 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c_arg
     if (__ballot(alive) == 0ull) return;
     if constexpr (kPerEnv && !kSpec) own = env_constants<Env>(env_arg(c_arg), n, ic);
     const auto& c = pick_constants(env_arg(c_arg), own);
+    if constexpr (kLag && !kSpec) {
+        alpha = lag_alpha_of<Env>(c_arg, n, ic);
+#pragma unroll
+        for (int k = 0; k < A; ++k) m[k] = alive ? lag_of(c_arg).motor[(k * T1 + t) * n + ic] : 0.0f;
+    }
     if constexpr (!kSpec) {
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = alive ? obs[(k * T1 + t) * n + ic] : (R)0;
@@ -173,7 +185,10 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c_arg
 
     R r;
     StepOut out;
-    if constexpr (EnvTraits<Env>::kSubsteps) {               // (control decimation: up to k calls of Env::step, rewards summed)
+    if constexpr (kLag) {                                    // (the rotor lag in front of every physics step)
+        int count;
+        out = lagged_substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, alpha, m, o, r, count);
+    } else if constexpr (EnvTraits<Env>::kSubsteps) {        // (control decimation: up to k calls of Env::step, rewards summed)
         int count;
         out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
     } else {
@@ -199,6 +214,10 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(typename Env::C c_arg
         mask[(int64_t)t * n + i] = alive ? 1 : 0;
 #pragma unroll
         for (int k = 0; k < S; ++k) obs[(k * T1 + t + 1) * n + i] = carry ? o[k] : (R)0;
+        if constexpr (kLag) {
+#pragma unroll
+            for (int k = 0; k < A; ++k) lag_of(c_arg).motor[(k * T1 + t + 1) * n + i] = carry ? m[k] : 0.0f;
+        }
         if (alive && done) len[i] = t + 1;
         else if (Env::kBalanceTerminates && alive) len[i] = -balanced_steps;
     }
@@ -238,6 +257,16 @@ __global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c_ar
         const R v = obs[(k * T1 + t_begin) * n + ic];
         s[k] = alive ? v : (R)0;
     }
+    constexpr bool kLag = EnvTraits<Env>::kLag;              // (actuator lag: the motor state stays in registers across the range)
+    float m[A], alpha = 0.0f;
+    if constexpr (kLag) {
+        alpha = lag_alpha_of<Env>(c_arg, n, ic);
+#pragma unroll
+        for (int k = 0; k < A; ++k) {
+            const float v = lag_of(c_arg).motor[(k * T1 + t_begin) * n + ic];
+            m[k] = alive ? v : 0.0f;
+        }
+    }
     float ab[kForcedAhead][A];
     auto load_actions = [&](int t, float (&dst)[A]) {
         const int tc = t < T ? t : T - 1;
@@ -257,7 +286,10 @@ __global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c_ar
             load_actions(t + kForcedAhead, ab[q]);
             R o[S], r;
             StepOut out;
-            if constexpr (EnvTraits<Env>::kSubsteps) {
+            if constexpr (kLag) {
+                int count;
+                out = lagged_substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, alpha, m, o, r, count);
+            } else if constexpr (EnvTraits<Env>::kSubsteps) {
                 int count;
                 out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
             } else {
@@ -276,11 +308,19 @@ __global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c_ar
                 mask[(int64_t)t * n + i] = alive ? 1 : 0;
 #pragma unroll
                 for (int k = 0; k < S; ++k) obs[(k * T1 + t + 1) * n + i] = carry ? o[k] : (R)0;
+                if constexpr (kLag) {
+#pragma unroll
+                    for (int k = 0; k < A; ++k) lag_of(c_arg).motor[(k * T1 + t + 1) * n + i] = carry ? m[k] : 0.0f;
+                }
             }
             if (alive && done) my_len = t + 1;
             else if (Env::kBalanceTerminates && alive) my_len = -balanced_steps;
 #pragma unroll
             for (int k = 0; k < S; ++k) s[k] = carry ? o[k] : (R)0;
+            if constexpr (kLag) {
+#pragma unroll
+                for (int k = 0; k < A; ++k) m[k] = carry ? m[k] : 0.0f;
+            }
             alive = carry;
         }
     }
@@ -295,8 +335,10 @@ __global__ __launch_bounds__(64) void rollout_forced_kernel(typename Env::C c_ar
 // the same bits as step_kernel gives for that input -- and writes it as an f32 row, with the time-limit flag
 // !failed(s_final) && (time_rule(L) || L == T).  A slot without a finished episode (len outside [1, T]) reads step 0 (a valid
 // address) and writes zeros / 0.
+// (lag_min_waves: the occupancy hint of the Lagged instantiations that need one, lag_occupancy.hpp; no attribute for the others)
 template <typename Env, typename R>
-__global__ __launch_bounds__(256) void final_state_kernel(typename Env::C c_arg, const R* __restrict__ obs, const float* __restrict__ act,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lag_min_waves<kLagFamFinal, Env, R>())))
+void final_state_kernel(typename Env::C c_arg, const R* __restrict__ obs, const float* __restrict__ act,
                                                           const int32_t* __restrict__ len, int64_t n, int32_t T,
                                                           float* __restrict__ s_final, uint8_t* __restrict__ timeout) {
     constexpr int S = Env::S, A = Env::A;
@@ -318,7 +360,12 @@ __global__ __launch_bounds__(256) void final_state_kernel(typename Env::C c_arg,
     for (int k = 0; k < A; ++k) a[k] = act[((int64_t)k * T + t) * n + i];
     R r;
     int count = L;                                            // the clock the time rule reads: physics steps under kSubsteps
-    if constexpr (EnvTraits<Env>::kSubsteps) (void)substep_loop<Env>(s, a, c, t, substeps_of(c_arg), true, o, r, count);
+    if constexpr (EnvTraits<Env>::kLag) {                     // (the motor state the last control step started from: slot L - 1)
+        float m[A];
+#pragma unroll
+        for (int k = 0; k < A; ++k) m[k] = lag_of(c_arg).motor[(k * T1 + t) * n + i];
+        (void)lagged_substep_loop<Env>(s, a, c, t, substeps_of(c_arg), true, lag_alpha_of<Env>(c_arg, n, i), m, o, r, count);
+    } else if constexpr (EnvTraits<Env>::kSubsteps) (void)substep_loop<Env>(s, a, c, t, substeps_of(c_arg), true, o, r, count);
     else (void)Env::step(s, a, c, t + 1, o, r);
 #pragma unroll
     for (int k = 0; k < S; ++k) s_final[i * S + k] = ended ? (float)o[k] : 0.0f;
@@ -747,6 +794,9 @@ static EnvVariant plain_variant(const tg_env_params* p, const double* d_ptab) { 
 static EnvVariant sub_variant(const tg_env_params* p, const double* d_ptab, int32_t substeps) {
     return EnvVariant{p, d_ptab, nullptr, 0.0f, substeps, true};
 }
+static EnvVariant lag_variant(const tg_env_params* p, const double* d_ptab, int32_t substeps, float* d_motor) {
+    return EnvVariant{p, d_ptab, nullptr, 0.0f, substeps, true, d_motor};
+}
 
 static int rollout_step_impl(const char* who, const EnvVariant& v, const tg_traj* tr, int32_t t, const float* d_mean,
                              int64_t mean_row_stride, const float* sigma, const uint64_t* d_rng, int64_t env_offset, void* stream) {
@@ -786,6 +836,15 @@ int tg_rollout_step_sub(const tg_env_params* p, const double* d_ptab, const tg_t
                              stream);
 }
 
+// The `_lag` entries: the `_sub` sibling plus the motor record (lag_check first: a refused lag launches nothing).
+int tg_rollout_step_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t, const float* d_mean, int64_t mean_row_stride,
+                        const float* sigma, const uint64_t* d_rng, int64_t env_offset, int32_t substeps, float* d_motor, void* stream) {
+    TG_REQUIRE(p != nullptr, "tg_rollout_step_lag: null pointer");
+    if (int rc = lag_check("tg_rollout_step_lag", p, d_ptab, d_motor)) return rc;
+    return rollout_step_impl("tg_rollout_step_lag", lag_variant(p, d_ptab, substeps, d_motor), tr, t, d_mean, mean_row_stride, sigma, d_rng,
+                             env_offset, stream);
+}
+
 static int rollout_forced_impl(const char* who, const EnvVariant& v, const tg_traj* tr, int32_t t_begin, int32_t t_end, void* stream) {
     const tg_env_params* p = v.p;
     TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_rew && tr->d_mask && tr->d_len, "%s: null pointer", who);
@@ -816,6 +875,13 @@ int tg_rollout_forced_sub(const tg_env_params* p, const double* d_ptab, const tg
     return rollout_forced_impl("tg_rollout_forced_sub", sub_variant(p, d_ptab, substeps), tr, t_begin, t_end, stream);
 }
 
+int tg_rollout_forced_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, int32_t t_begin, int32_t t_end, int32_t substeps,
+                          float* d_motor, void* stream) {
+    TG_REQUIRE(p != nullptr, "tg_rollout_forced_lag: null pointer");
+    if (int rc = lag_check("tg_rollout_forced_lag", p, d_ptab, d_motor)) return rc;
+    return rollout_forced_impl("tg_rollout_forced_lag", lag_variant(p, d_ptab, substeps, d_motor), tr, t_begin, t_end, stream);
+}
+
 static int final_state_impl(const char* who, const EnvVariant& v, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout, void* stream) {
     const tg_env_params* p = v.p;
     TG_REQUIRE(p && tr && tr->d_obs && tr->d_act && tr->d_len && d_s_final && d_timeout, "%s: null pointer", who);
@@ -844,6 +910,14 @@ int tg_rollout_final_state_dr(const tg_env_params* p, const double* d_ptab, cons
 int tg_rollout_final_state_sub(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
                                int32_t substeps, void* stream) {
     return final_state_impl("tg_rollout_final_state_sub", sub_variant(p, d_ptab, substeps), tr, d_s_final, d_timeout, stream);
+}
+
+int tg_rollout_final_state_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, float* d_s_final, uint8_t* d_timeout,
+                               int32_t substeps, const float* d_motor, void* stream) {
+    TG_REQUIRE(p != nullptr, "tg_rollout_final_state_lag: null pointer");
+    if (int rc = lag_check("tg_rollout_final_state_lag", p, d_ptab, d_motor)) return rc;
+    return final_state_impl("tg_rollout_final_state_lag", lag_variant(p, d_ptab, substeps, const_cast<float*>(d_motor)), tr, d_s_final, d_timeout,
+                            stream);
 }
 
 int tg_rollout_finish(const tg_traj* tr, void* stream) {

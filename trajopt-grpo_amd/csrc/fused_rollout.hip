@@ -74,9 +74,11 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
     constexpr int D = (NT == 1 && WPW == 4) ? 3 : 4, P = D - 1;   // ring slots, blocks in flight (LDS is shared by 2 workgroups at 4 x NT=1)
     static_assert(KS % WPW == 0, "every wave moves the same number of 1-KiB pieces per block");
     static_assert(S <= 32 && A <= 4, "state must fit one padded 32-feature tile; actions the first 4 head rows");
-    // the compaction staging ([32 * WPW][S + 1] floats) aliases xs (WPW * 64 * 32 bf16 = 4096 * WPW bytes);
-    // per wave: 32 records of S + 1 floats in 64 * 32 bf16; compaction only runs with NT == 1
-    static_assert(NT != 1 || 32 * (S + 1) * 4 <= 64 * 32 * 2, "compaction records must fit the input staging area they alias");
+    // the compaction staging ([32 * WPW][REC] floats, REC = S + 1, + A motor states under kLag) aliases xs (WPW * 64 * 32 bf16 =
+    // 4096 * WPW bytes); per wave: 32 records of REC floats in 64 * 32 bf16; compaction only runs with NT == 1
+    constexpr bool kLag = EnvTraits<Env>::kLag;
+    constexpr int REC = S + 1 + (kLag ? A : 0);
+    static_assert(NT != 1 || 32 * REC * 4 <= 64 * 32 * 2, "compaction records must fit the input staging area they alias");
     extern __shared__ uint4 lds[];
     uint4* ring = lds;                                                  // D * KS * 64 uint4
     float* bias_s = reinterpret_cast<float*>(lds + D * KS * 64);        // (n_hh + 2) * H floats
@@ -111,6 +113,17 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
     const int32_t len0 = len[ic];
     bool alive = in_range && (Env::kBalanceTerminates ? len0 <= 0 : len0 == 0);
     int balanced_steps = Env::kBalanceTerminates ? -len0 : 0;
+    // kLag: the motor state of the lane's env, from slot t0 (split launches compose), in registers from here on; its gain is the
+    // lane's own where the constants are
+    float m[A], alpha = 0.0f;
+    if constexpr (kLag) {
+        alpha = lag_alpha_of<Env>(c_arg, n, ic);
+#pragma unroll
+        for (int k = 0; k < A; ++k) {
+            const float v = lag_of(c_arg).motor[(k * T1 + t0) * n + ic];
+            m[k] = alive ? v : 0.0f;
+        }
+    }
     unsigned short* my_x = xs + (wave * 64 + lane) * 32;
     // zero the padding features once (columns S..31 never change)
 #pragma unroll
@@ -146,19 +159,23 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
                 total += cw;
             }
             if (total == 0) break;                            // every env of this workgroup has ended
-            float* stage = reinterpret_cast<float*>(xs);      // [32*WPW][S+1] floats; xs is rewritten every step anyway
+            float* stage = reinterpret_cast<float*>(xs);      // [32*WPW][REC] floats; xs is rewritten every step anyway
             if (own) {
-                float* d = stage + (offset + rank) * (S + 1);
+                float* d = stage + (offset + rank) * REC;
 #pragma unroll
                 for (int k = 0; k < S; ++k) d[k] = s[k];
                 d[S] = __int_as_float((int)(i - wg_base));
+                if constexpr (kLag) {
+#pragma unroll
+                    for (int k = 0; k < A; ++k) d[S + 1 + k] = m[k];
+                }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             const int slot = wave * 32 + col;
             if (slot < total) {
-                const float* d = stage + slot * (S + 1);
+                const float* d = stage + slot * REC;
 #pragma unroll
                 for (int k = 0; k < S; ++k) s[k] = d[k];
                 i = wg_base + __float_as_int(d[S]);
@@ -166,6 +183,11 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
                 in_range = (h == 0);
                 ic = i;
                 if constexpr (kPerEnv) own_c = env_constants<Env>(e_arg, n, ic);   // the vehicle follows the env, like the Philox key
+                if constexpr (kLag) {                                              // ... and so do its motor state and its gain
+#pragma unroll
+                    for (int k = 0; k < A; ++k) m[k] = d[S + 1 + k];
+                    if constexpr (kPerEnv) alpha = lag_alpha_of<Env>(c_arg, n, ic);
+                }
             } else {
                 alive = false;
                 in_range = false;                             // an empty slot records nothing
@@ -320,7 +342,10 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
         }
         float o[S], r;
         StepOut out;
-        if constexpr (EnvTraits<Env>::kSubsteps) {           // (control decimation: up to k calls of Env::step, rewards summed)
+        if constexpr (kLag) {                                // (the rotor lag in front of every physics step)
+            int count;
+            out = lagged_substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, alpha, m, o, r, count);
+        } else if constexpr (EnvTraits<Env>::kSubsteps) {    // (control decimation: up to k calls of Env::step, rewards summed)
             int count;
             out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
         } else {
@@ -340,10 +365,18 @@ __global__ __launch_bounds__(64 * WPW, (NT == 2) ? 1 : 2) void fused_rollout_ker
             mask[(int64_t)t * n + i] = alive ? 1 : 0;
 #pragma unroll
             for (int k = 0; k < S; ++k) obs[(k * T1 + t + 1) * n + i] = carry ? o[k] : 0.0f;
+            if constexpr (kLag) {
+#pragma unroll
+                for (int k = 0; k < A; ++k) lag_of(c_arg).motor[(k * T1 + t + 1) * n + i] = carry ? m[k] : 0.0f;
+            }
             if (alive && done) len[i] = t + 1;
         }
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = carry ? o[k] : 0.0f;
+        if constexpr (kLag) {
+#pragma unroll
+            for (int k = 0; k < A; ++k) m[k] = carry ? m[k] : 0.0f;
+        }
         alive = carry;
     }
     if (Env::kBalanceTerminates && in_range && alive) len[i] = -balanced_steps;   // a later segment [t1, ..) picks the count up
@@ -458,6 +491,16 @@ int tg_fused_rollout_sub(const tg_env_params* p, const double* d_ptab, const tg_
                          int32_t t_begin, int32_t t_end, const float* d_obs_norm, float clip, int32_t substeps, void* stream) {
     return fused_rollout_impl("tg_fused_rollout_sub", "tg_fused_rollout_sub", EnvVariant{p, d_ptab, d_obs_norm, clip, substeps, true}, tr, d_wfrag,
                               d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
+}
+
+// The `_sub` entry plus the motor record (lag_check first: a refused lag launches nothing).
+int tg_fused_rollout_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const void* d_wfrag, const float* d_bias,
+                         int32_t hidden, int32_t n_hidden_layers, const float* sigma, const uint64_t* d_rng, int64_t env_offset,
+                         int32_t t_begin, int32_t t_end, const float* d_obs_norm, float clip, int32_t substeps, float* d_motor, void* stream) {
+    TG_REQUIRE(p != nullptr, "tg_fused_rollout_lag: null pointer");
+    if (int rc = lag_check("tg_fused_rollout_lag", p, d_ptab, d_motor)) return rc;
+    return fused_rollout_impl("tg_fused_rollout_lag", "tg_fused_rollout_lag", EnvVariant{p, d_ptab, d_obs_norm, clip, substeps, true, d_motor}, tr,
+                              d_wfrag, d_bias, hidden, n_hidden_layers, sigma, d_rng, env_offset, t_begin, t_end, stream);
 }
 
 }  // extern "C"

@@ -55,7 +55,8 @@ __device__ static inline void lds_barrier() {
 // Tables: `wstream` f32 [H/32 waves][K1/2 + NHH*H/2 registers][64 lanes]; `tab` f32 [(NHH+1)*H biases][4*H head
 // weights, rows >= A zero][4 head biases].
 template <typename Env, int H, int NHH, int kAct>
-__global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
+__global__ __launch_bounds__(64 * (H / 32)) __attribute__((amdgpu_waves_per_eu(lag_min_waves<kLagFamF32, Env, float, H, NHH, kAct>())))
+void fused_rollout_f32_kernel(
     typename Env::C c_arg, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew, uint8_t* __restrict__ mask,
     int32_t* __restrict__ len, int64_t n, int32_t T, int32_t t0, int32_t t1, const float* __restrict__ wstream,
     const float* __restrict__ tab, SigmaF32 sigma, const uint64_t* __restrict__ rng, int64_t env_offset, int32_t agents) {
@@ -100,6 +101,16 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
     const int32_t len0 = len[ic];
     bool alive = (i < n) && (Env::kBalanceTerminates ? len0 <= 0 : len0 == 0);
     int balanced_steps = Env::kBalanceTerminates ? -len0 : 0;
+    constexpr bool kLag = EnvTraits<Env>::kLag;              // kLag: the motor state from slot t0 (split launches compose), in registers
+    float m[A], alpha = 0.0f;
+    if constexpr (kLag) {
+        alpha = lag_alpha_of<Env>(c_arg, n, ic);
+#pragma unroll
+        for (int k = 0; k < A; ++k) {
+            const float v = lag_of(c_arg).motor[(k * T1 + t0) * n + ic];
+            m[k] = alive ? v : 0.0f;
+        }
+    }
     __syncthreads();
     int par = 0, rpar = 0;
 
@@ -191,7 +202,10 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
         }
         float o[S], r;
         StepOut out;
-        if constexpr (EnvTraits<Env>::kSubsteps) {           // (control decimation: up to k calls of Env::step, rewards summed)
+        if constexpr (kLag) {                                // (the rotor lag in front of every physics step)
+            int count;
+            out = lagged_substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, alpha, m, o, r, count);
+        } else if constexpr (EnvTraits<Env>::kSubsteps) {    // (control decimation: up to k calls of Env::step, rewards summed)
             int count;
             out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
         } else {
@@ -211,10 +225,18 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
             mask[(int64_t)t * n + i] = alive ? 1 : 0;
 #pragma unroll
             for (int k = 0; k < S; ++k) obs[(k * T1 + t + 1) * n + i] = carry ? o[k] : 0.0f;
+            if constexpr (kLag) {
+#pragma unroll
+                for (int k = 0; k < A; ++k) lag_of(c_arg).motor[(k * T1 + t + 1) * n + i] = carry ? m[k] : 0.0f;
+            }
             if (alive && done) len[i] = t + 1;
         }
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = carry ? o[k] : 0.0f;
+        if constexpr (kLag) {
+#pragma unroll
+            for (int k = 0; k < A; ++k) m[k] = carry ? m[k] : 0.0f;
+        }
         alive = carry;
     }
     if (Env::kBalanceTerminates && in_range && alive) len[i] = -balanced_steps;   // a later segment [t1, ..) picks the count up
@@ -233,7 +255,8 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32_kernel(
 typedef float f32x4r __attribute__((ext_vector_type(4)));
 
 template <typename Env, int H, int NHH, int kAct>
-__global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
+__global__ __launch_bounds__(64 * (H / 32)) __attribute__((amdgpu_waves_per_eu(lag_min_waves<kLagFamF32x16, Env, float, H, NHH, kAct>())))
+void fused_rollout_f32x16_kernel(
     typename Env::C c_arg, float* __restrict__ obs, float* __restrict__ act, float* __restrict__ rew, uint8_t* __restrict__ mask,
     int32_t* __restrict__ len, int64_t n, int32_t T, int32_t t0, int32_t t1, const float* __restrict__ wstream,
     const float* __restrict__ tab, SigmaF32 sigma, const uint64_t* __restrict__ rng, int64_t env_offset, int32_t agents) {
@@ -282,6 +305,16 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
     const int32_t len0 = len[ic];
     bool alive = (i < n) && (Env::kBalanceTerminates ? len0 <= 0 : len0 == 0);
     int balanced_steps = Env::kBalanceTerminates ? -len0 : 0;
+    constexpr bool kLag = EnvTraits<Env>::kLag;              // kLag: the motor state from slot t0 (split launches compose), in registers
+    float m[A], alpha = 0.0f;
+    if constexpr (kLag) {
+        alpha = lag_alpha_of<Env>(c_arg, n, ic);
+#pragma unroll
+        for (int k = 0; k < A; ++k) {
+            const float v = lag_of(c_arg).motor[(k * T1 + t0) * n + ic];
+            m[k] = alive ? v : 0.0f;
+        }
+    }
     __syncthreads();
     int par = 0, rpar = 0;
     auto bias4 = [&](const float* b) { const float4 v = *reinterpret_cast<const float4*>(b); return f32x4r{v.x, v.y, v.z, v.w}; };
@@ -399,7 +432,10 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
         for (int k = 0; k < A; ++k) a[k] = rn_add(mu[k], rn_mul(sigma.v[k], eps[k]));
         float o[S], r;
         StepOut out;
-        if constexpr (EnvTraits<Env>::kSubsteps) {           // (control decimation: up to k calls of Env::step, rewards summed)
+        if constexpr (kLag) {                                // (the rotor lag in front of every physics step)
+            int count;
+            out = lagged_substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, alpha, m, o, r, count);
+        } else if constexpr (EnvTraits<Env>::kSubsteps) {    // (control decimation: up to k calls of Env::step, rewards summed)
             int count;
             out = substep_loop<Env>(s, a, c, t, substeps_of(c_arg), alive, o, r, count);
         } else {
@@ -419,10 +455,18 @@ __global__ __launch_bounds__(64 * (H / 32)) void fused_rollout_f32x16_kernel(
             mask[(int64_t)t * n + i] = alive ? 1 : 0;
 #pragma unroll
             for (int k = 0; k < S; ++k) obs[(k * T1 + t + 1) * n + i] = carry ? o[k] : 0.0f;
+            if constexpr (kLag) {
+#pragma unroll
+                for (int k = 0; k < A; ++k) lag_of(c_arg).motor[(k * T1 + t + 1) * n + i] = carry ? m[k] : 0.0f;
+            }
             if (alive && done) len[i] = t + 1;
         }
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = carry ? o[k] : 0.0f;
+        if constexpr (kLag) {
+#pragma unroll
+            for (int k = 0; k < A; ++k) m[k] = carry ? m[k] : 0.0f;
+        }
         alive = carry;
     }
     if (Env::kBalanceTerminates && in_range && alive) len[i] = -balanced_steps;   // a later segment [t1, ..) picks the count up
@@ -570,6 +614,17 @@ int tg_fused_rollout_f32_sub(const tg_env_params* p, const double* d_ptab, const
                              int32_t substeps, void* stream) {
     return fused_rollout_f32("tg_fused_rollout_f32_sub", EnvVariant{p, d_ptab, d_obs_norm, clip, substeps, true}, tr, d_wstream, d_tab, hidden,
                              n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end, activation, stream);
+}
+
+// The `_sub` entry plus the motor record (lag_check first: a refused lag launches nothing).
+int tg_fused_rollout_f32_lag(const tg_env_params* p, const double* d_ptab, const tg_traj* tr, const float* d_wstream, const float* d_tab,
+                             int32_t hidden, int32_t n_hidden_layers, int32_t block_envs, const float* sigma, const uint64_t* d_rng,
+                             int64_t env_offset, int32_t t_begin, int32_t t_end, int32_t activation, const float* d_obs_norm, float clip,
+                             int32_t substeps, float* d_motor, void* stream) {
+    TG_REQUIRE(p != nullptr, "tg_fused_rollout_f32_lag: null pointer");
+    if (int rc = lag_check("tg_fused_rollout_f32_lag", p, d_ptab, d_motor)) return rc;
+    return fused_rollout_f32("tg_fused_rollout_f32_lag", EnvVariant{p, d_ptab, d_obs_norm, clip, substeps, true, d_motor}, tr, d_wstream, d_tab,
+                             hidden, n_hidden_layers, block_envs, sigma, d_rng, env_offset, t_begin, t_end, activation, stream);
 }
 
 }  // extern "C"

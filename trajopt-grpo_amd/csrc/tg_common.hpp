@@ -151,6 +151,21 @@ static inline int substeps_check(const char* who, const tg_env_params* p, const 
                          who, tr->horizon, substeps, p->max_steps);
     return TG_OK;
 }
+// The actuator lag of a `_lag` entry point (checked before substeps_check): 0 = accepted, < 0 = refused (nothing is launched).
+// The time constant is p->p[10]: the one vehicle's without a parameter table (it must then be > 0: the feature is on), the nominal
+// value that row 10 of the table scales with one.
+static inline int lag_check(const char* who, const tg_env_params* p, const double* d_ptab, const float* d_motor) {
+    if (p->env_id != TG_ENV_QUADPOLE2D && p->env_id != TG_ENV_QUADPOLE)
+        return set_error(TG_ERR_UNSUPPORTED, "%s: env %d has no rotors to lag (QuadPole2D and QuadPole only)", who, p->env_id);
+    if (p->agents > 1)
+        return set_error(TG_ERR_UNSUPPORTED, "%s: swarm envs (agents=%d) are not supported", who, p->agents);
+    if (d_motor == nullptr) return set_error(TG_ERR_ARG, "%s: null motor record", who);
+    const double tau = p->p[10];
+    if (!(tau == tau) || tau - tau != 0.0) return set_error(TG_ERR_ARG, "%s: the motor time constant p[10] is not finite", who);
+    if (tau < 0.0 || (d_ptab == nullptr && tau <= 0.0))
+        return set_error(TG_ERR_ARG, "%s: the motor time constant p[10] = %g must be > 0 (0 is off: the `_sub` entry)", who, tau);
+    return TG_OK;
+}
 struct LdsOptIn { size_t bytes[kMaxDevices] = {}; };
 static inline int reserve_dynamic_lds(const void* kernel, size_t bytes, LdsOptIn& cache, const char* what) {
     if (bytes > 160 * 1024) return set_error(TG_ERR_ARG, "%s: %zu B of LDS needed (> 160 KiB)", what, bytes);

@@ -72,6 +72,7 @@ class Env:
         p = N.default_params(self.ENV_ID, self.max_steps)
         p.timestep = float(self.timestep)
         self._fill_params(p)
+        p.p[self.MOTOR_SLOT] = self._motor_tau
         N.check(N.load().tg_env_finalize_params(C.byref(p)), "tg_env_finalize_params")
         return p
 
@@ -116,8 +117,50 @@ class Env:
         p = N.default_params(self.ENV_ID, int(self.max_steps) * self._substeps)
         p.timestep = float(self.timestep)
         self._fill_params(p)
+        p.p[self.MOTOR_SLOT] = self._motor_tau
         N.check(N.load().tg_env_finalize_params(C.byref(p)), "tg_env_finalize_params")
         return p
+
+    # -- actuator lag ---------------------------------------------------------
+    MOTOR_SLOT = 10         # the p[] slot of the motor time constant (read by no env's own constants)
+    _motor_tau = 0.0
+    _motor = None           # the scalar API's motor state, float32 (A,), while the lag is on
+
+    @property
+    def motor_time_constant(self) -> float:
+        """Time constant `tau` of a first-order rotor lag, in seconds (default 0.0: off).  With tau > 0 every env carries a motor state
+        m (float32, normalised action units, 0 = hover thrust, 0 at the reset); in front of EVERY physics step
+        `m += alpha * (clip(a, -1, 1) - m)` with `alpha = float32(timestep / (tau + timestep))`, and the env's own step receives m
+        in place of the action.  The trajectory still records the commanded action; `DeviceTrajectory.motor` records m
+        ("Actuator lag").  A finite float >= 0; QuadPole2D and QuadPole only (no swarm): ValueError."""
+        return self._motor_tau
+
+    @motor_time_constant.setter
+    def motor_time_constant(self, tau):
+        if isinstance(tau, bool) or not isinstance(tau, (int, float, np.integer, np.floating)):
+            raise ValueError(f"motor_time_constant must be a finite float >= 0, got {tau!r}")
+        tau = float(tau)
+        if not (np.isfinite(tau) and tau >= 0.0):
+            raise ValueError(f"motor_time_constant must be a finite float >= 0, got {tau}")
+        if tau != 0.0 and self.ENV_ID not in (N.TG_ENV_QUADPOLE2D, N.TG_ENV_QUADPOLE):
+            raise ValueError(f"motor_time_constant: {type(self).__name__} has no rotors to lag (QuadPole2D and QuadPole only)")
+        if tau != 0.0 and int(getattr(self, "n_agents", 1)) > 1:
+            raise ValueError("motor_time_constant: swarm envs (n_agents > 1) are not supported")
+        self._motor_tau = tau
+        self._motor = None
+
+    def motor_alpha(self) -> np.float32:
+        """The filter gain float32(timestep / (tau + timestep)): one double add and divide, rounded to float32 once."""
+        dt = float(self.timestep)
+        return np.float32(dt / (self._motor_tau + dt))
+
+    def parameter_slots(self):
+        """name -> p[] slot of everything randomize(), a privileged critic and an Evaluator sweep may name: `RANDOMIZABLE`, plus
+        "motor_time_constant" while the lag is on."""
+        slots = dict(self.RANDOMIZABLE)
+        if self._motor_tau > 0.0:
+            slots["motor_time_constant"] = self.MOTOR_SLOT
+        return slots
 
     # -- per-env domain randomisation (device rollouts) --------------------
     def randomize(self, ranges=None, *, seed: int = 0):
@@ -137,10 +180,11 @@ class Env:
         if not 0 <= seed < 2 ** 64:
             raise ValueError(f"randomize(): seed {seed} is not an unsigned 64-bit integer")
         checked = {}
+        slots = self.parameter_slots()
         for name, rng in ranges.items():
-            if name not in self.RANDOMIZABLE:
+            if name not in slots:
                 raise ValueError(f"randomize(): {name!r} is not a randomisable parameter of {type(self).__name__} "
-                                 f"(randomisable: {', '.join(self.RANDOMIZABLE)})")
+                                 f"(randomisable: {', '.join(slots)})")
             try:
                 lo, hi = (float(v) for v in rng)
             except (TypeError, ValueError):
@@ -167,10 +211,15 @@ class Env:
         if not self._randomize:
             return None
         spec = N.RandomizeSpec()
-        items = sorted(self._randomize.items(), key=lambda kv: self.RANDOMIZABLE[kv[0]])
+        slots = self.parameter_slots()
+        gone = [name for name in self._randomize if name not in slots]
+        if gone:
+            raise ValueError(f"randomize(): {gone[0]!r} is no longer a randomisable parameter of {type(self).__name__} "
+                             f"(randomisable: {', '.join(slots)})")
+        items = sorted(self._randomize.items(), key=lambda kv: slots[kv[0]])
         spec.count, spec.seed = len(items), self._randomize_seed
         for k, (name, (lo, hi)) in enumerate(items):
-            spec.index[k], spec.lo[k], spec.hi[k] = self.RANDOMIZABLE[name], lo, hi
+            spec.index[k], spec.lo[k], spec.hi[k] = slots[name], lo, hi
         return spec
 
     @property
@@ -283,6 +332,7 @@ class Env:
         self._initial = self._state.clone()
         self._steps_t.zero_()
         self._tb_t.zero_()
+        self._motor = None
         self._steps, self._time, self._time_balanced = 0, 0, 0
         self._sync_state_dict()
         self._initial_state = {k: v.copy() for k, v in self.state_dict.items()}
@@ -295,6 +345,7 @@ class Env:
         self._initial = self._state.clone()
         self._steps_t.zero_()
         self._tb_t.zero_()
+        self._motor = None
         self._steps, self._time, self._time_balanced = 0, 0, 0
         self._sync_state_dict()
         self._initial_state = {k: v.copy() for k, v in self.state_dict.items()}
@@ -306,6 +357,7 @@ class Env:
         self._state.copy_(self._initial)
         self._steps_t.zero_()
         self._tb_t.zero_()
+        self._motor = None
         self._steps, self._time, self._time_balanced = 0, 0, 0
         self._sync_state_dict()
         return self._obs_np(), self._get_info()
@@ -319,7 +371,7 @@ class Env:
         """Advance the scalar env by one tg_env_step; returns (reward, truncated) and updates the bookkeeping."""
         if self._state is None:
             raise RuntimeError("step() before reset()")
-        if self._substeps != 1:
+        if self._substeps != 1 or self._motor_tau > 0.0:
             return self._native_substeps(action)
         p = self.native_params()
         a = torch.as_tensor(np.asarray(action, dtype=np.float32).reshape(self.act_dim, 1), device=self._device)
@@ -337,12 +389,25 @@ class Env:
 
     def _native_substeps(self, action):
         """One policy step of an env with substeps = k: up to k tg_env_step launches on the physics clock (the device step counter
-        counts physics steps), stopping after the first that truncates; the rewards are summed left to right in the env's dtype."""
+        counts physics steps), stopping after the first that truncates; the rewards are summed left to right in the env's dtype.
+        With an actuator lag (motor_time_constant > 0, also at k = 1) the host-side motor state is filtered towards the clipped action
+        in front of every launch -- NumPy float32, one rounding per operation -- and the launch receives it in place of the action."""
         p = self.physics_params()
         a = torch.as_tensor(np.asarray(action, dtype=np.float32).reshape(self.act_dim, 1), device=self._device)
         self._act_t.copy_(a)
+        lag = self._motor_tau > 0.0
+        if lag:
+            alpha = self.motor_alpha()
+            cmd = np.clip(np.asarray(action, dtype=np.float32).reshape(self.act_dim), np.float32(-1), np.float32(1))
+            if self._motor is None:
+                self._motor = np.zeros(self.act_dim, dtype=np.float32)
         total, truncated = None, False
         for _ in range(self._substeps):
+            if lag:
+                d = cmd - self._motor
+                e = alpha * d
+                self._motor = self._motor + e
+                self._act_t.copy_(torch.as_tensor(self._motor.reshape(self.act_dim, 1)))
             with torch.cuda.device(self._device):
                 N.check(N.load().tg_env_step(C.byref(p), N.dtype_code(self._dtype), self._state.data_ptr(), 1,
                                              self._act_t.data_ptr(), 1, self._state.data_ptr(), 1, self._steps_t.data_ptr(),

@@ -43,10 +43,11 @@ def check_sweep(env, sweep):
     if len(sweep) > 12:
         raise ValueError(f"Evaluator: sweep over {len(sweep)} parameters, an env has at most 12")
     out = []
+    slots = env.parameter_slots()                      # (RANDOMIZABLE, plus the motor time constant while the lag is on)
     for name, factors in sweep.items():
-        if name not in env.RANDOMIZABLE:
+        if name not in slots:
             raise ValueError(f"Evaluator: {name!r} is not a sweepable parameter of {type(env).__name__} "
-                             f"(sweepable: {', '.join(env.RANDOMIZABLE)})")
+                             f"(sweepable: {', '.join(slots)})")
         try:
             if isinstance(factors, (str, bytes)):
                 raise TypeError
@@ -57,7 +58,7 @@ def check_sweep(env, sweep):
             raise ValueError(f"Evaluator: the factor list of {name!r} is empty")
         if not all(math.isfinite(v) and v > 0.0 for v in vals):
             raise ValueError(f"Evaluator: the factors of {name!r} must be finite and > 0, got {vals}")
-        out.append((name, env.RANDOMIZABLE[name], vals))
+        out.append((name, slots[name], vals))
     out.sort(key=lambda item: item[1])
     return out
 
@@ -195,6 +196,7 @@ class Evaluator:
             eng.rng[1].zero_()
             traj = eng.run(deterministic=self.deterministic)
             self._s_final, self._timeout = K.rollout_final_state(eng.params, traj, self._s_final, self._timeout, env_params=eng.env_params,
-                                                                 **({"substeps": eng.substeps} if eng.substeps != 1 else {}))
+                                                                 **({"substeps": eng.substeps} if eng.substeps != 1 else {}),
+                                                                 **({"motor": traj.motor} if traj.motor is not None else {}))
             returns, cells = K.eval_cells(traj, self._timeout, self.episodes)
         return EvalResult(cells, returns, self._sweep, self.episodes, self.early_name)

@@ -285,14 +285,16 @@ def ppo_returns(rew, values, mask, gamma: float, lam: float, monte_carlo: bool, 
 
 
 def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: torch.Tensor = None, env_params: torch.Tensor = None,
-                        substeps: int = 1):
+                        substeps: int = 1, motor: torch.Tensor = None):
     """tg_rollout_final_state on a DeviceTrajectory: (s_final f32 [n][S], timeout u8 [n]) -- the state each episode's last step
     produced (Env.step on obs[:, len-1], act[:, len-1]: tg_env_step's bits) and whether the clock, not a failure, ended the episode.
     params: the env's tg_env_params (DeviceRollout.params / Env.native_params()).  A swarm env is refused: ValueError.
     env_params: the per-env parameter table of a randomised rollout (DeviceRollout.env_params, f64 [12][n]): every slot is re-stepped
     with its own vehicle (tg_rollout_final_state_dr).
     substeps != 1 (DeviceRollout.substeps; params are then those of the physics clock): the last CONTROL step is re-run, up to
-    `substeps` calls that stop at the first truncation (tg_rollout_final_state_sub, which takes the table or NULL)."""
+    `substeps` calls that stop at the first truncation (tg_rollout_final_state_sub, which takes the table or NULL).
+    motor: the motor record of a rollout with an actuator lag (DeviceTrajectory.motor, f32 [A][T+1][n]; params then carry the time
+    constant in p[10]): the re-step filters the last commanded action from slot len-1 (tg_rollout_final_state_lag)."""
     N.require_cuda(traj.obs, traj.act, traj.len, s_final, timeout)
     assert traj.obs.is_contiguous() and traj.act.is_contiguous() and traj.len.is_contiguous() and traj.len.dtype == torch.int32
     dev = traj.obs.device
@@ -307,7 +309,11 @@ def rollout_final_state(params, traj, s_final: torch.Tensor = None, timeout: tor
         N.require_cuda(env_params)
         assert env_params.dtype == torch.float64 and env_params.is_contiguous() and tuple(env_params.shape) == (12, traj.n)
     ptab = None if env_params is None else env_params.data_ptr()
-    if substeps != 1:
+    if motor is not None:
+        N.require_cuda(motor)
+        assert motor.dtype == torch.float32 and motor.is_contiguous() and tuple(motor.shape) == (traj.A, traj.T + 1, traj.n)
+        name, table, tail = "tg_rollout_final_state_lag", (ptab,), (int(substeps), motor.data_ptr())
+    elif substeps != 1:
         name, table, tail = "tg_rollout_final_state_sub", (ptab,), (int(substeps),)
     else:
         name, table = suffixed("tg_rollout_final_state", "_dr", None if ptab is None else (ptab,))

@@ -105,6 +105,8 @@ class Pipeline:
             meta["randomize"] = rand
         if int(getattr(self.env, "substeps", 1)) != 1:   # only when control decimation is on: `env.substeps = meta["substeps"]` restores it
             meta["substeps"] = int(self.env.substeps)
+        if float(getattr(self.env, "motor_time_constant", 0.0)) != 0.0:   # only when the actuator lag is on: the setter restores it
+            meta["motor_time_constant"] = float(self.env.motor_time_constant)
         return meta
 
     def load_metadata(self, path: str) -> Dict[str, Any]:

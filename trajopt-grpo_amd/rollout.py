@@ -10,6 +10,7 @@ legacy caller asks for it (`rollout()` / buffer attributes).
 
 Device layout (env index fastest, see include/trajopt_grpo_hip.h):
     obs [S][T+1][N]   act [A][T][N] f32   rew [T][N]   mask [T][N] u8   len [N] i32
+    motor [A][T+1][N] f32 (only with Env.motor_time_constant > 0: the rotor state at the start of every control step)
 Flat env index n = g*E + e (buffers/rollout_buffer.py:85-89).
 """
 from __future__ import annotations
@@ -42,6 +43,9 @@ class DeviceTrajectory:
         # {sum of rewards, n, valid env-steps} of the last rollout (tg_rollout_finish_stats) and its scratch
         self.stats = torch.zeros(3, dtype=torch.float64, device=device)
         self._stats_work = torch.empty(256, dtype=torch.float64, device=device)
+        # the motor state at the start of every control step, f32 [A][T+1][n] with obs's conventions (slot 0 and the slots behind an
+        # episode's end are zeros), while the env has an actuator lag (Env.motor_time_constant > 0); None otherwise
+        self.motor = None
         self.stats_fresh = False             # `stats` belongs to the rollout these tensors hold (a caller that edits them says so by clearing it)
         self.host_valid_rows = None          # callable -> this rollout's valid rows, already on the host (Rollout_Buffer.sample)
 
@@ -87,13 +91,16 @@ class DeviceTrajectory:
         return obs, act, rew, ln, mask
 
 
-def fused_entry(f32: bool, act: int, ptab, obs_norm, substeps: int = 1):
+def fused_entry(f32: bool, act: int, ptab, obs_norm, substeps: int = 1, motor=None):
     """(entry name, arguments after the env parameters, tail arguments) of the persistent rollout launch.  f32: the fp32 kernel
     (its entries beyond the plain one take the hidden activation `act`, TG_ACT_*); ptab: the per-env parameter table's address or
     None; obs_norm: (table address, clip value) or None.  `_on` takes the table, NULL when the rollout is not randomised.
-    substeps != 1: the `_sub` entry, which takes the table, the obs-norm pair (either may be NULL) and `substeps`."""
+    substeps != 1: the `_sub` entry, which takes the table, the obs-norm pair (either may be NULL) and `substeps`.
+    motor (the motor record's address; an actuator lag): the `_lag` entry, `_sub`'s arguments -- at substeps == 1 too -- and `motor`."""
     base = "tg_fused_rollout_f32" if f32 else "tg_fused_rollout"
     act_arg = (act,) if f32 else ()
+    if motor is not None:
+        return base + "_lag", (ptab,), act_arg + (tuple(obs_norm) if obs_norm is not None else (None, 0.0)) + (int(substeps), motor)
     if substeps != 1:
         return base + "_sub", (ptab,), act_arg + (tuple(obs_norm) if obs_norm is not None else (None, 0.0)) + (int(substeps),)
     if obs_norm is not None:
@@ -105,18 +112,23 @@ def fused_entry(f32: bool, act: int, ptab, obs_norm, substeps: int = 1):
     return base, (), ()
 
 
-def step_entry(forced: bool, ptab, substeps: int = 1):
+def step_entry(forced: bool, ptab, substeps: int = 1, motor=None):
     """(entry name, arguments after the env parameters) of a per-step launch (tg_rollout_step) or of the one-launch teacher-forced
     replay (tg_rollout_forced): `_dr` with the per-env parameter table of a randomised rollout.  substeps != 1: the `_sub` entry,
-    which takes the table (or NULL) there and `substeps` as its last argument before the stream (sub_tail)."""
+    which takes the table (or NULL) there and `substeps` as its last argument before the stream (sub_tail).  motor (the motor
+    record's address; an actuator lag): the `_lag` entry, which takes `substeps` (1 included) and `motor` there."""
     base = "tg_rollout_forced" if forced else "tg_rollout_step"
+    if motor is not None:
+        return K.suffixed(base, "_lag", (ptab,))
     if substeps != 1:
         return K.suffixed(base, "_sub", (ptab,))
     return K.suffixed(base, "_dr", None if ptab is None else (ptab,))
 
 
-def sub_tail(substeps: int):
-    """What a per-step `_sub` entry takes in front of the stream: () for the entries of substeps == 1."""
+def sub_tail(substeps: int, motor=None):
+    """What a per-step `_sub` / `_lag` entry takes in front of the stream: () for the entries of substeps == 1 without a lag."""
+    if motor is not None:
+        return (int(substeps), motor)
     return () if substeps == 1 else (int(substeps),)
 
 
@@ -216,6 +228,17 @@ class DeviceRollout:
         steps of env.timestep) and k, which every launch below passes to its `_sub` entry point."""
         self.substeps = int(getattr(self.env, "substeps", 1))
         self.params = self.env.native_params() if self.substeps == 1 else self.env.physics_params()
+        # an actuator lag (env.motor_time_constant > 0, in p[10] of the params): every launch below goes to its `_lag` entry point
+        # with the trajectory's motor record, allocated here and zero-filled by every rollout's prologue
+        self.lag = float(getattr(self.env, "motor_time_constant", 0.0)) > 0.0
+        if not self.lag:
+            self.traj.motor = None
+        elif self.traj.motor is None:
+            self.traj.motor = torch.zeros(self.A, self.T + 1, self.n, dtype=torch.float32, device=self.device)
+
+    def _motor_kw(self):
+        """The `motor` argument of fused_entry / step_entry / sub_tail: absent while the lag is off (the calls are the parent's)."""
+        return {"motor": self.traj.motor.data_ptr()} if self.lag else {}
 
     # ---- policy mean for time step t -------------------------------------------------
     def _refresh_weights(self, entry: bool = False):
@@ -322,6 +345,8 @@ class DeviceRollout:
     def _enqueue_prepare(self, initial_states):
         lib, tr, st = self.lib, self.traj.native(), N.stream_ptr(self.device)
         N.check(lib.tg_rollout_begin(C.byref(tr), self.S, self.A, st), "tg_rollout_begin")
+        if self.lag:
+            self.traj.motor.zero_()
         if initial_states is None:
             self._reset(tr, st)
         else:
@@ -354,7 +379,7 @@ class DeviceRollout:
         n_hidden = len(self._linears) - 1
         on = getattr(self.policy, "obs_norm", None)
         name, table, tail = fused_entry(self._fused_f32, self._f32_act, None if self.env_params is None else self.env_params.data_ptr(),
-                                        None if on is None else (on.table.data_ptr(), on.clip_value), self.substeps)
+                                        None if on is None else (on.table.data_ptr(), on.clip_value), self.substeps, **self._motor_kw())
         # (the fp32 kernel reads biases and head from a table and takes its envs per workgroup; the bf16 kernel reads a bias stream)
         weights = ((self._frag.table.data_ptr(), self._fused_H, n_hidden, self._f32_block_envs) if self._fused_f32 else
                    (self._frag.bias.data_ptr(), self._fused_H, n_hidden))
@@ -378,12 +403,13 @@ class DeviceRollout:
     def _launch_step(self, t, tr, st, *args):
         """One tg_rollout_step launch for time step t -- t None: the whole teacher-forced replay in one tg_rollout_forced launch --
         (`_dr`: a randomised rollout), bracketed by timing events when step_events is a list."""
-        name, table = step_entry(t is None, None if self.env_params is None else self.env_params.data_ptr(), self.substeps)
+        name, table = step_entry(t is None, None if self.env_params is None else self.env_params.data_ptr(), self.substeps,
+                                 **self._motor_kw())
         ev = None
         if self.step_events is not None:
             ev = N.event_pair()
             ev[0].record()
-        N.check(getattr(self.lib, name)(C.byref(self.params), *table, C.byref(tr), *args, *sub_tail(self.substeps), st), name)
+        N.check(getattr(self.lib, name)(C.byref(self.params), *table, C.byref(tr), *args, *sub_tail(self.substeps, **self._motor_kw()), st), name)
         if ev is not None:
             ev[1].record()
             self.step_events.append((t, ev[0], ev[1]))
@@ -413,11 +439,13 @@ class DeviceRollout:
             # the reset draw depends on the host-side stream id, so it stays outside the graph
             lib, tr, st = self.lib, self.traj.native(), N.stream_ptr(self.device)
             N.check(lib.tg_rollout_begin(C.byref(tr), self.S, self.A, st), "tg_rollout_begin")
+            if self.lag:
+                self.traj.motor.zero_()
             self._reset(tr, st)
             # tg_rollout_step takes sigma (and the env parameters) BY VALUE in its kernel arguments: a captured graph replays the
             # values of its capture.  A covariance annealed or restored since then (the learner reads policy.var afresh in every
             # learn(), actor_critic.py:131-136 reads self.cov in every forward) means a new capture.
-            baked = (tuple(self._sigma), bytes(self.params), self.substeps)
+            baked = (tuple(self._sigma), bytes(self.params), self.substeps, self._motor_kw().get("motor"))
             if self._graph is not None and baked != self._graph_baked:
                 self._graph = None
             if self._graph is None:
