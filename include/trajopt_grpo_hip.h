@@ -89,6 +89,11 @@ typedef struct tg_traj {
 
 const char* tg_last_error(void);
 int  tg_abi_version(void);
+/* Process-wide switch of the depth-specialised bf16 chain kernel: tg_mlp_backward_chain_ex with the first-layer gradient inside
+ * (d_x non-NULL), panel order, H = 256 and 5 hidden layers runs an instantiation with the depth as a compile-time constant -- the same
+ * arithmetic and memory operations, bit-identical results, fewer instructions.  on = 0: every launch takes the run-time-depth kernel.
+ * Default 1.  Returns the previous value. */
+int  tg_chain_depth_kernels(int on);
 
 int  tg_env_dims(int env_id, int* obs_dim, int* act_dim);
 int  tg_env_default_params(int env_id, int max_steps, tg_env_params* out);

@@ -147,6 +147,7 @@ _P, _I32, _I64, _U64, _F, _VP = C.POINTER, C.c_int32, C.c_int64, C.c_uint64, C.c
 SIGNATURES = {
     "tg_last_error": (C.c_char_p, []),
     "tg_abi_version": (C.c_int, []),
+    "tg_chain_depth_kernels": (C.c_int, [C.c_int]),
     "tg_env_dims": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int)]),
     "tg_env_default_params": (C.c_int, [C.c_int, C.c_int, _P(EnvParams)]),
     "tg_env_finalize_params": (C.c_int, [_P(EnvParams)]),
@@ -382,6 +383,12 @@ ALWAYS_REBUILD = os.environ.get("TG_ALWAYS_REBUILD", "0") == "1"    # 1: derived
 # whatever the keys say (one gather launch when the optimizer step is the fused one); between the updates of a learn(), where every
 # write is the build's own, the keys decide.  1: trust the keys at the entries too (saves the two launches per iteration).
 TRUST_KEYS = os.environ.get("TG_TRUST_VERSION_KEYS", "0") == "1"
+
+
+def chain_depth_kernels_default():
+    """TG_CHAIN_DEPTH_KERNELS (default 1): may the bf16 backward chain run its depth-specialised kernel (tg_chain_depth_kernels)?
+    Read when a GemmMLP is built; GemmMLP.depth_kernels carries it to every launch."""
+    return os.environ.get("TG_CHAIN_DEPTH_KERNELS", "1") != "0"
 
 
 def event_pair():

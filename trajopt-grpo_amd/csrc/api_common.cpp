@@ -1,5 +1,6 @@
 // Error reporting shared by every translation unit of libtrajopt_grpo_hip.so.
 #include "tg_common.hpp"
+#include <atomic>
 
 namespace tg {
 
@@ -13,11 +14,16 @@ int set_error(int code, const char* fmt, ...) {
     return code;
 }
 
+// tg_chain_depth_kernels: may the bf16 chain launchers pick a depth-specialised instantiation?  (process-wide)
+static std::atomic<int> g_chain_depth_kernels{1};
+bool chain_depth_kernels() { return g_chain_depth_kernels.load(std::memory_order_relaxed) != 0; }
+
 }  // namespace tg
 
 extern "C" {
 const char* tg_last_error(void) { return tg::g_err; }
 int tg_abi_version(void) { return TG_ABI_VERSION; }
+int tg_chain_depth_kernels(int on) { return tg::g_chain_depth_kernels.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed); }
 
 int tg_clock_probe_attach(int32_t family, void* d_probe) {
     switch (family) {

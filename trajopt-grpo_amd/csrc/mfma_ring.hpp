@@ -113,16 +113,47 @@ __device__ static inline void ring_dma_block(const uint4* __restrict__ gblock, u
 }
 
 // Consume the next block.  Expects in scope: wfrag, ring, n_blocks, wave, lane, the ring state (pre_pos, pre_slot,
-// cur_slot) and the constants KS, WPW, D; declares `cur` (the block's fragments).  WAITN: see above.
+// cur_slot) and the constants KS, WPW, D; declares `cur` (the block's fragments; TG_RING_NEXT_INTO: the caller declared it).
+// WAITN: see above.
 #define TG_RING_WAIT(WAITN) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAITN) : "memory");
-#define TG_RING_NEXT                                                                                       \
+#define TG_RING_NEXT_INTO(CUR)                                                                             \
     __builtin_amdgcn_s_barrier();                                                                          \
     asm volatile("" ::: "memory");                                                                         \
     ring_dma_block<KS, WPW>(wfrag + (int64_t)pre_pos * KS * 64, ring + pre_slot * KS * 64, wave, lane);    \
     pre_pos = (pre_pos + 1 == n_blocks) ? 0 : pre_pos + 1;                                                 \
     pre_slot = (pre_slot + 1 == D) ? 0 : pre_slot + 1;                                                     \
-    const uint4* cur = ring + cur_slot * KS * 64;                                                          \
+    CUR = ring + cur_slot * KS * 64;                                                                       \
     cur_slot = (cur_slot + 1 == D) ? 0 : cur_slot + 1;
+#define TG_RING_NEXT    \
+    const uint4* cur;   \
+    TG_RING_NEXT_INTO(cur)
 #define TG_RING_ADVANCE(WAITN) TG_RING_WAIT(WAITN) TG_RING_NEXT
+
+// Depth-specialised kernel (mlp_bwd_chain.hip: the network depth is a template argument, the block loops are fully unrolled): block
+// `c` of a round of NB blocks sits at a stream position and in ring slots that are constants of the unrolled code, so the ring
+// keeps no state -- provided D divides NB (the backward chain at 5 hidden layers: 33 blocks, 3 slots), so that the ring is back
+// where it was after every round.  Block c is read from slot c % D and the DMA behind its barrier fetches block (c + P) % NB into
+// slot (c + P) % D.  The same barrier, the same DMAs in the same order as TG_RING_NEXT: the counted waits in front of it stay what
+// they are.
+// `wave` must be a scalar (readfirstlane): the DMA's LDS destination is then a scalar constant (M0) and its source a scalar base
+// (stream + block position + the wave's piece) plus the lane's 32-bit offset `voff` (= 16 lane).  `voff` passes through an empty
+// asm statement at every block, and so does the stream pointer: left visible, every block's address is loop-invariant, hipcc
+// keeps all of them in registers across the round loop and spills (a vector spill's reload is a vector-memory operation: it
+// would drain the ring; 2 NB scalar pairs spill to lanes).  Per block: two scalar adds per piece.
+template <int KS, int WPW, int D, int NB>
+__device__ static inline const uint4* ring_next_at(const uint4*& wfrag, uint4* ring, int c, int wave, uint32_t& voff) {
+    static_assert(NB % D == 0, "the ring must be back at slot 0 after every round");
+    constexpr int P = D - 1;
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" : "+v"(voff), "+s"(wfrag) : : "memory");
+    const char* gblock = reinterpret_cast<const char*>(wfrag) + ((c + P) % NB) * (KS * 1024);
+    uint4* slot = ring + ((c + P) % D) * (KS * 64);
+#pragma unroll
+    for (int q = 0; q < KS / WPW; ++q) {
+        const int piece = q * WPW + wave;
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(gblock + piece * 1024 + voff), (lds_void*)(slot + piece * 64), 16, 0, 0);
+    }
+    return ring + (c % D) * (KS * 64);
+}
 
 }  // namespace tg

@@ -83,9 +83,16 @@ __device__ static inline uint4 lds_read_b128_opaque(const uint4* p) {
 }
 
 // kPanel: the dZ are stored in panel order (mfma_ring.hpp PanelOrder) instead of row-major.
-template <int H, int WPW, bool kFuse0, bool kPanel = false>
+// NL: the number of hidden layers as a compile-time constant (0: the run-time argument).  With it the layer loop is unrolled in
+// full: the activation tile needs no copy at a layer boundary (xin / xout are renamed, not moved), `fused_layer` and the wait
+// site of every block are constants, and so are a block's stream position and ring slots (ring_next_at: (NL - 1) MT + 1 blocks a
+// round must be a multiple of the ring's 3 slots).  It is the same kernel otherwise: the same vector-memory operations in the
+// same order and number per block, every TG_RING_WAIT argument and every barrier where the run-time form has them, the same
+// arithmetic on the same values -- bit-identical results (tests/test_chain_depth_gpu.py).
+template <int H, int WPW, bool kFuse0, bool kPanel = false, int NL = 0>
 __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4* __restrict__ dzh, const uint4* __restrict__ wfrag,
-                                                                    int32_t n_layers, int64_t rows, BwdChainPtrs ptrs) {
+                                                                    int32_t n_layers_arg, int64_t rows, BwdChainPtrs ptrs) {
+    const int n_layers = NL ? NL : n_layers_arg;
     constexpr int MT = H / 32, KS = H / 16, K8 = H / 32;
     // ring of 3 slots, 2 blocks in flight (4 / 3 measured the same; the LDS goes to the store staging instead).  Behind
     // the block a wait is for: the DMA of the one later block and the stores of the last two blocks, one of them odd
@@ -109,11 +116,23 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
     char* tiles = reinterpret_cast<char*>(mks + WPW * 3 * 64);
     char* xtiles = tiles + 2 * WPW * 2048;
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int wave = NL ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);   // (NL: a scalar, see ring_next_at)
     const int grp = lane >> 4, col = lane & 15, nib = 4 * (grp & 1);
     const bool store_top = ptrs.dz[0] != nullptr;                      // null: tg_mlp_weight_grad (kind RH) rebuilds the top layer's dZ
     const int64_t n_rounds = (rows + 32 * WPW - 1) / (32 * WPW);
     const int n_blocks = (n_layers - 1) * MT + 1;
+    [[maybe_unused]] const uint4* ring_src = wfrag;                     // (NL: the stream, see ring_next_at)
+    [[maybe_unused]] uint32_t ring_voff = 16u * (uint32_t)lane;         // (NL: the lane's offset into a 1-KiB piece)
+    constexpr int NB = NL ? (NL - 1) * MT + 1 : D;                      // (NL: blocks per round)
+    // the next block's barrier, DMA and fragments: TG_RING_NEXT, or with NL block C of the round at its constant position
+#define TG_BWD_RING_NEXT(C)                                                                       \
+    const uint4* cur;                                                                             \
+    if constexpr (NL != 0) {                                                                      \
+        cur = ring_next_at<KS, WPW, D, NB>(ring_src, ring, (C), wave, ring_voff);                 \
+    } else {                                                                                      \
+        TG_RING_NEXT_INTO(cur)                                                                    \
+    }
     constexpr int WPL = MT / 2;                                         // mask words per half-row and layer
 
     uint4* my_dzs = dzs + wave * 64;
@@ -228,7 +247,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
         {
             // (kFuse0: the last layer of the previous round stored nothing: only the one later DMA lies behind this block)
             if constexpr (kFuse0) { TG_RING_WAIT((P - 1) * (KS / WPW)) } else { TG_RING_WAIT(kWaitN) }
-            TG_RING_NEXT
+            TG_BWD_RING_NEXT(0)
             if constexpr (kFuse0) {
                 if (round != (int64_t)blockIdx.x) dma_x0(round, 0);   // everyone is past the previous round's last tile reads (the barrier above)
             }
@@ -269,72 +288,15 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
             ++mseq;
         }
         // ---- hidden layers, top down: dZ_below^T = W^T . dZ^T, one block per 32 output features ----
-        for (int j = 1; j < n_layers; ++j) {
+        if constexpr (NL != 0) {                     // unrolled in full: every `j` in the layer is a constant
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                // (without the head block's stores nothing but the one later DMA lies behind the second block of the first layer;
-                // kFuse0: nor behind its first block -- the previous round ended without stores -- nor from the third block of the
-                // last layer on, which writes LDS tiles instead of dZ)
-                const bool fused_layer = kFuse0 && j == n_layers - 1;
-                if constexpr (kFuse0) {
-                    if (fused_layer) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's tile writes are done
-                }
-                if ((mt == 1 && j == 1 && !store_top) || ((kFuse0 || kPanel) && mt == 0 && j == 1 && !store_top) ||
-                    (fused_layer && mt >= (kPanel ? 1 : 2))) {
-                    TG_RING_WAIT((P - 1) * (KS / WPW))
-                } else {
-                    TG_RING_WAIT(kWaitN)
-                }
-                TG_RING_NEXT
-
-                if (mt == 0) {
-                    prefetch_mask(round, j);
-                    mask_words(mw);
-                }
-                f32x4 acc[2][2] = {};
-                // scheduling fences around the block's products: left alone, hipcc threads the pack / mask arithmetic of the
-                // neighbouring blocks through the MFMA sequence (s_nop-padded); kept apart the kernel is 2.4 % faster (same-box A/B)
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int ks = 0; ks < K8; ++ks)
-#pragma unroll
-                    for (int f = 0; f < 2; ++f) {
-                        const bf16x8 a = __builtin_bit_cast(bf16x8, cur[(ks * 2 + f) * 64 + lane]);
-#pragma unroll
-                        for (int c = 0; c < 2; ++c) acc[f][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, xin[c][ks], acc[f][c], 0, 0, 0);
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (kFuse0) {
-                    // the tiles of block mt - 1 are complete behind this block's barrier; their products go behind this block's own
-                    // (in front of them the fragment reads' latency is exposed: same-box A/B 2522 -> 2513 us per 2^22 rows)
-                    if (fused_layer && mt >= 1) owner_work(mt - 1);
-                }
-#pragma unroll
-                for (int c = 0; c < 2; ++c) xout[c][mt] = masked_pack(acc[0][c], acc[1][c], mw[c][mt >> 1], mt);
-                if (kFuse0 && fused_layer) {
-                    // the block's 32 rows x 32 features into T[mt & 1][wave]; rows past the end (clamped duplicates of the last row)
-                    // as zeros: they must not be counted twice in the contraction
-                    char* tw = tiles + ((mt & 1) * WPW + wave) * 2048;
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        const int row = 16 * c + col;
-                        uint4 o = __builtin_bit_cast(uint4, xout[c][mt]);
-                        if (row0 + row >= rows) o = uint4{0u, 0u, 0u, 0u};
-                        lds_store16(tw + (row >> 2) * 256 + (row & 3) * 64 + ((grp ^ ((row >> 2) & 3)) * 16), o);
-                    }
-                } else if constexpr (kPanel) {
-                    const bf16x8 pv[2] = {xout[0][mt], xout[1][mt]};
-                    store_panel<H>(ptrs.dz[j], poff, mt, pv);
-                } else if (mt & 1) {
-                    const bf16x8 pa[2] = {xout[0][mt - 1], xout[1][mt - 1]}, pb[2] = {xout[0][mt], xout[1][mt]};
-                    store_pair(stage, ptrs.dz[j] + 32 * (mt - 1), row0, rows, H, lane, pa, pb);
-                }
+            for (int j = 1; j < NL; ++j) {
+#include "mlp_bwd_chain_layer.inc"
             }
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int ks = 0; ks < K8; ++ks) xin[c][ks] = xout[c][ks];
-            ++mseq;
+        } else {
+            for (int j = 1; j < n_layers; ++j) {
+#include "mlp_bwd_chain_layer.inc"
+            }
         }
         if constexpr (kFuse0) {                      // the last block's tiles: one plain barrier, then their products
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -354,6 +316,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_bwd_chain_kernel(const uint4*
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup's LDS allocation
     TG_CLOCK_PROBE_END(g_probe_bwd_chain)
+#undef TG_BWD_RING_NEXT
 }
 
 // Per-workgroup column sums of a dZ matrix (the bias gradient), for callers of tg_mlp_backward_chain that pass d_partial:
@@ -428,9 +391,17 @@ static int launch_bwd_chain(const void* d_dout8, const void* d_wfrag, int32_t n_
             return (int)TG_OK;
         };
         static LdsOptIn opt_in_w0, opt_in_plain;
-        const int rc = d_x ? launch(mlp_bwd_chain_kernel<H, WPW, true, true>, opt_in_w0)
-                           : launch(mlp_bwd_chain_kernel<H, WPW, false, true>, opt_in_plain);
-        if (rc != TG_OK) return rc;
+        auto pick = [&]() {
+            if constexpr (H == 256) {    // the learner's shape at 5 hidden layers: the depth-specialised instantiation (NL)
+                if (d_x && n_hidden_layers == 5 && chain_depth_kernels()) {
+                    static LdsOptIn opt_in_w0_nl5;
+                    return launch(mlp_bwd_chain_kernel<H, WPW, true, true, 5>, opt_in_w0_nl5);
+                }
+            }
+            return d_x ? launch(mlp_bwd_chain_kernel<H, WPW, true, true>, opt_in_w0)
+                       : launch(mlp_bwd_chain_kernel<H, WPW, false, true>, opt_in_plain);
+        };
+        if (const int rc = pick()) return rc;
     } else if (d_x) {
         auto kern = mlp_bwd_chain_kernel<H, WPW, true>;
         static LdsOptIn opt_in;

@@ -302,6 +302,10 @@ class GemmMLP:
         # ... the dZ only where the activations are (the plain loss head): a weight-gradient job with ONE operand in panel order ran
         # 6 % slower than with both or neither (profiles/r06_panel_order_ab.md).  True: the dZ regardless (tools/panel_order_probe.py)
         self.panel_mixed = False
+        # the bf16 backward chain may take its depth-specialised kernel (H = 256, 5 hidden layers: the same results bit for bit from
+        # fewer instructions, profiles/r19_chain_depth_ab.md); False: the run-time-depth kernel.  The native switch is process-wide
+        # (tg_chain_depth_kernels), so it is set in front of the launch it governs.
+        self.depth_kernels = N.chain_depth_kernels_default()
         if self.act == "Tanh":
             # (the resident 16-row kernel and the H = 256 kernel are ReLU-only: a Tanh net of the resident shape runs the chain kernel;
             # nothing is rebuilt from mask bits, so every activation and dZ is stored)
@@ -641,6 +645,12 @@ class GemmMLP:
         self._dz_head = dz_head
         return None if sums_out is not None else work[:grid * 4].view(grid, 4).sum(0)
 
+    def _set_depth_kernels(self, lib):
+        """Carries GemmMLP.depth_kernels to the native switch in front of a chain launch; -> the value set."""
+        on = bool(self.depth_kernels)
+        lib.tg_chain_depth_kernels(int(on))
+        return on
+
     def _flush_riders(self):
         """The partial gradients / loss sums a forward_loss() left for backward_fused()'s reduction launch, added here by torch instead
         (same sums, torch's order): only when that backward_fused() never came."""
@@ -881,6 +891,7 @@ class GemmMLP:
             dz_ptrs = (N.C.c_void_p * nh)(*[N.ptr(t) for t in dzs])
             if self._w0_slabs is None:
                 self._w0_slabs = torch.empty(2 * lib.tg_mlp_backward_chain_blocks() * H * 32, dtype=torch.float32, device=device)
+        depth = self._set_depth_kernels(lib) and dz_panel and fuse0 and H == 256 and nh == 5      # (what the launcher picks: the events' label)
         ev = None
         if self.dx_events is not None:
             ev = N.event_pair()
@@ -902,7 +913,7 @@ class GemmMLP:
             ev[1].record()
             n_stored = nh - 1 - (1 if fuse0 else 0)
             self.dx_events.append((ev[0], ev[1], rows, 16 + nh * (H // 8) + n_stored * 2 * H + (64 if fuse0 else 0),
-                                   f"tg::mlp_bwd_chain_kernel<{H},8,{'true' if fuse0 else 'false'}{',true' if dz_panel else ''}>"))
+                                   f"tg::mlp_bwd_chain_kernel<{H},8,{'true' if fuse0 else 'false'}{',true' if dz_panel else ''}{',5' if depth else ''}>"))
         riders, loss_rider = getattr(self, "_riders", None) or ([], None)
         self._riders = None
         if fuse0 and rows > 0:
