@@ -1124,6 +1124,61 @@ int  tg_eval_tile_states(const tg_traj* tr, int32_t S, int64_t episodes_per_cell
 int  tg_eval_cells(const tg_traj* tr, const uint8_t* d_timeout, int64_t episodes_per_cell, double* d_returns, double* d_cells,
                    void* stream);
 
+/* ---- Vector env: n auto-resetting env slots behind one launch per step (DeviceVecEnv; additions to ABI 13) ----
+ * The gymnasium VectorEnv contract in its SAME_STEP autoreset mode: a step takes actions f32 [n][A] (row-major, as every RL library
+ * hands them over), returns observations f32 [n][S], rewards and the terminated / truncated flags, and a slot whose episode ended
+ * comes back already reset.  The slots sit at DIFFERENT positions of their episodes; what persists between steps lives in device
+ * arrays the caller owns (struct of arrays, env fastest) and nothing a launch takes by value changes from step to step -- a step is
+ * one launch: no allocation, no host read, no synchronisation.
+ *   d_state     real [S][n]   the current state, in the arithmetic type `dtype`
+ *   d_steps     i32  [n]      control steps taken in the slot's current episode
+ *   d_balanced  i32  [n]      Pendulum: consecutive balanced steps so far (the other envs neither read nor write it)
+ *   d_ep_return f64  [n]      the current episode's rewards, each converted to f64 and added in step order
+ *   d_episode   u32  [n]      ordinal of the slot's current episode: the stream id of its reset draw
+ * The motor state f32 [A][n] of an actuator lag is the d_motor argument of the two entries (NULL: no lag), not a field.
+ * horizon = T, the control steps of an episode (env.max_steps); `p` describes the PHYSICS clock as for the `_sub` entries:
+ * p->max_steps = horizon * substeps.  Slot i is global env env_offset + i: shards with consecutive offsets are, bit for bit, the slots
+ * of one object (sharding over GPUs).
+ *
+ * tg_vec_env_step, per slot i with t = d_steps[i]:
+ *   1. one control step from d_state[:, i] under d_actions[i][:], exactly as tg_rollout_step's kernel takes it for a running episode:
+ *      the env's own step (the plain instantiation when d_ptab == NULL, substeps == 1 and d_motor == NULL), or up to `substeps`
+ *      calls of it with steps_after = t substeps + j + 1 (`_sub`), behind the rotor lag with d_motor non-NULL (`_lag`), with the
+ *      constants of column i of d_ptab f64 [12][n] when it is non-NULL (`_dr`; the table is the caller's: tg_env_randomize);
+ *   2. ended = the step's `truncated` || (Pendulum: the balanced count reached its limit) || t + 1 >= T;
+ *      timeout = !failed(new state) && (time_rule(the physics count the step stopped at) || t + 1 == T), tg_rollout_final_state's
+ *      rule; d_truncated[i] = ended && timeout (the clock), d_terminated[i] = ended && !timeout (a failure, or Pendulum's balance
+ *      terminal); their OR is the reference's "episode over";
+ *   3. d_reward[i] = (float)r; d_ep_return[i] += (double)r; where ended: d_final_return[i] = (float)d_ep_return[i],
+ *      d_final_length[i] = t + 1 (entries of slots that did not end keep what they held);
+ *   4. where ended, in the same launch: d_episode[i] += 1, the new state is tg_env_reset's for (seed, stream_id = d_episode[i],
+ *      key_offset = env_offset + i, key_div = 1), and steps, balanced, motor and ep_return go to 0; else steps (and balanced) count on;
+ *   5. d_obs f32 [n][S], row i = the next state -- the fresh initial state where the slot was reset -- an f64 state rounded once, on
+ *      the store; d_final_obs f32 [n][S], row i = the state the step produced BEFORE the reset.  A wavefront writes its 64 rows of
+ *      d_final_obs only when one of its slots ended: rows are defined only where terminated | truncated.
+ * tg_vec_env_reset_all: every slot starts a new episode in one launch -- d_episode[i] = 0 when restart != 0, else d_episode[i] + 1;
+ *   state and d_obs from that reset draw; steps, balanced, motor (when given) and ep_return zeroed.
+ * Refused before any launch: a null pointer other than d_ptab / d_motor, n <= 0, horizon <= 0, env_offset < 0, substeps outside
+ * [1, 64], p->max_steps != horizon * substeps, d_obs / d_final_obs not 16-byte aligned, d_actions not aligned to a row of 4 A bytes (TG_ERR_ARG); swarm envs
+ * (agents > 1), substeps != 1 on Pendulum, a motor state on an env without rotors, an unknown env or dtype (TG_ERR_UNSUPPORTED);
+ * with d_motor, tg_rollout_step_lag's conditions on p->p[10]. */
+typedef struct tg_vec_env {
+    void*     d_state;
+    int32_t*  d_steps;
+    int32_t*  d_balanced;
+    double*   d_ep_return;
+    uint32_t* d_episode;
+    int64_t   n;
+    int64_t   env_offset;
+    uint64_t  seed;
+    int32_t   horizon;
+    int32_t   dtype;         /* TG_F32 | TG_F64 */
+} tg_vec_env;
+int  tg_vec_env_step(const tg_env_params* p, const double* d_ptab, int32_t substeps, float* d_motor, const tg_vec_env* v,
+                     const float* d_actions, float* d_obs, float* d_reward, uint8_t* d_terminated, uint8_t* d_truncated,
+                     float* d_final_obs, float* d_final_return, int32_t* d_final_length, void* stream);
+int  tg_vec_env_reset_all(const tg_env_params* p, float* d_motor, const tg_vec_env* v, int32_t restart, float* d_obs, void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

@@ -142,6 +142,13 @@ class CompactArgs(C.Structure):
                 ("rows_cap", C.c_int64)]
 
 
+class VecEnv(C.Structure):
+    """tg_vec_env (include/trajopt_grpo_hip.h): the per-slot arrays of a vector env and what is fixed per object."""
+    _fields_ = [("d_state", C.c_void_p), ("d_steps", C.c_void_p), ("d_balanced", C.c_void_p), ("d_ep_return", C.c_void_p),
+                ("d_episode", C.c_void_p), ("n", C.c_int64), ("env_offset", C.c_int64), ("seed", C.c_uint64), ("horizon", C.c_int32),
+                ("dtype", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/trajopt_grpo_hip.h declares
 _P, _I32, _I64, _U64, _F, _VP = C.POINTER, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -319,6 +326,8 @@ SIGNATURES = {
     "tg_env_param_grid": (C.c_int, [_P(EnvParams), _P(ParamGrid), _VP, _I64, _I64, _VP]),
     "tg_eval_tile_states": (C.c_int, [_P(Traj), _I32, _I64, _VP]),
     "tg_eval_cells": (C.c_int, [_P(Traj), _VP, _I64, _VP, _VP, _VP]),
+    "tg_vec_env_step": (C.c_int, [_P(EnvParams), _VP, _I32, _VP, _P(VecEnv), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tg_vec_env_reset_all": (C.c_int, [_P(EnvParams), _VP, _P(VecEnv), _I32, _VP, _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),

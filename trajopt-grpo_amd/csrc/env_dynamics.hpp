@@ -740,6 +740,29 @@ template <typename R> struct PendulumEnv {
     }
 };
 
+// ---------------------------------------------------------------------------
+// host dispatch shared by the translation units that launch one lane per env slot (env_kernels.hip, vec_env.hip)
+// ---------------------------------------------------------------------------
+static inline dim3 env_grid(int64_t n, int& block) {
+    // small launches are latency-bound: one wave per workgroup spreads them over all CUs
+    block = (n <= (int64_t)1 << 18) ? 64 : 256;
+    return dim3((unsigned)ceil_div(n, block));
+}
+
+// (a Pendulum through a `_sub` entry never gets here: substeps_check refuses it, and Pendulum's kMaySubstep = false instantiates nothing)
+#define TG_ENV_SWITCH(env_id, dtype, CALL)                                                     \
+    switch ((env_id) * 2 + (dtype)) {                                                          \
+        case TG_ENV_CARTPOLE * 2 + TG_F32: return CALL(CartPoleEnv, float);                    \
+        case TG_ENV_CARTPOLE * 2 + TG_F64: return CALL(CartPoleEnv, double);                   \
+        case TG_ENV_QUADPOLE2D * 2 + TG_F32: return CALL(QuadPole2DEnv, float);                \
+        case TG_ENV_QUADPOLE2D * 2 + TG_F64: return CALL(QuadPole2DEnv, double);               \
+        case TG_ENV_QUADPOLE * 2 + TG_F32: return CALL(QuadPoleEnv, float);                    \
+        case TG_ENV_QUADPOLE * 2 + TG_F64: return CALL(QuadPoleEnv, double);                   \
+        case TG_ENV_PENDULUM * 2 + TG_F32: return CALL(PendulumEnv, float);                    \
+        case TG_ENV_PENDULUM * 2 + TG_F64: return CALL(PendulumEnv, double);                   \
+        default: return set_error(TG_ERR_UNSUPPORTED, "unsupported env_id %d / dtype %d", (int)(env_id), (int)(dtype)); \
+    }
+
 }  // namespace tg
 
 #include "lag_occupancy.hpp"

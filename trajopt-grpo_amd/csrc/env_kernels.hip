@@ -507,12 +507,6 @@ __global__ __launch_bounds__(256) void quadrotor12_kernel(const R* __restrict__ 
 // ---------------------------------------------------------------------------
 // host dispatch
 // ---------------------------------------------------------------------------
-static inline dim3 env_grid(int64_t n, int& block) {
-    // small launches are latency-bound: one wave per workgroup spreads them over all CUs
-    block = (n <= (int64_t)1 << 18) ? 64 : 256;
-    return dim3((unsigned)ceil_div(n, block));
-}
-
 template <template <typename> class EnvT, typename R>
 static int reset_dispatch(const tg_env_params* p, void* state, int64_t ld, int64_t n, uint64_t seed, uint64_t stream_id,
                           int64_t key_offset, int64_t key_div, hipStream_t st) {
@@ -592,20 +586,6 @@ static int final_state_dispatch(const char* who, const EnvVariant& v, const tg_t
         return TG_OK;
     });
 }
-
-// (a Pendulum through a `_sub` entry never gets here: substeps_check refuses it, and Pendulum's kMaySubstep = false instantiates nothing)
-#define TG_ENV_SWITCH(env_id, dtype, CALL)                                                     \
-    switch ((env_id) * 2 + (dtype)) {                                                          \
-        case TG_ENV_CARTPOLE * 2 + TG_F32: return CALL(CartPoleEnv, float);                    \
-        case TG_ENV_CARTPOLE * 2 + TG_F64: return CALL(CartPoleEnv, double);                   \
-        case TG_ENV_QUADPOLE2D * 2 + TG_F32: return CALL(QuadPole2DEnv, float);                \
-        case TG_ENV_QUADPOLE2D * 2 + TG_F64: return CALL(QuadPole2DEnv, double);               \
-        case TG_ENV_QUADPOLE * 2 + TG_F32: return CALL(QuadPoleEnv, float);                    \
-        case TG_ENV_QUADPOLE * 2 + TG_F64: return CALL(QuadPoleEnv, double);                   \
-        case TG_ENV_PENDULUM * 2 + TG_F32: return CALL(PendulumEnv, float);                    \
-        case TG_ENV_PENDULUM * 2 + TG_F64: return CALL(PendulumEnv, double);                   \
-        default: return set_error(TG_ERR_UNSUPPORTED, "unsupported env_id %d / dtype %d", (int)(env_id), (int)(dtype)); \
-    }
 
 static int cartpole_time_trunc_step(int max_steps, double timestep) {
     // cartpole_env.py:27,151,168: `_time += timestep` accumulated in fp64 vs max_steps*timestep
