@@ -1179,6 +1179,60 @@ int  tg_vec_env_step(const tg_env_params* p, const double* d_ptab, int32_t subst
                      float* d_final_obs, float* d_final_return, int32_t* d_final_length, void* stream);
 int  tg_vec_env_reset_all(const tg_env_params* p, float* d_motor, const tg_vec_env* v, int32_t restart, float* d_obs, void* stream);
 
+/* ---- Replay buffer: n-step transitions of a vector env for off-policy loops (DeviceReplayBuffer; additions to ABI 13) ----
+ * A ring of K = capacity_steps time slots of n env slots each, float32, row-major, row = slot * n + i: one time slot is one
+ * contiguous [n][.] block of every array.
+ *   d_obs f32 [K n][S], d_act f32 [K n][A], d_next_obs f32 [K n][S], d_rew f32 [K n], d_disc f32 [K n], d_nstep u8 [K n]
+ *   d_last_obs f32 [n][S]   the observation each slot's next action is applied to
+ *   d_cursor i32 [n]        the time slot the next push writes (equal across slots; a push block reads that of its first slot)
+ *   d_filled i32 [n]        time slots written so far, at most K (equal across slots; the sample reads entry 0)
+ *   d_open   i32 [n]        stored rows of slot i that the next push still extends, in [0, n_step - 1]
+ *   discount[j] = (float)(gamma^j), j = 0 .. n_step.
+ * Everything that changes from push to push lives in these device arrays: the arguments of a push are the same every time, so a
+ * vector-env step and a push can be captured into one hipGraph.
+ *
+ * tg_replay_start: d_last_obs = d_obs_in [n][S], d_open = 0; stored rows, d_cursor and d_filled stay.
+ * tg_replay_push, one launch; per env slot i with c = d_cursor, o = d_open[i], done = terminated[i] | truncated[i],
+ *   nx = done ? d_final_obs[i] : d_obs_in[i]:
+ *   row c n + i:                          obs = d_last_obs[i], act = d_actions[i], rew = d_reward[i], next_obs = nx,
+ *                                         disc = terminated[i] ? 0 : discount[1], nstep = 1;
+ *   rows ((c - j) mod K) n + i, j = 1..o: rew = fadd(rew, fmul(discount[j], d_reward[i])) (two float32 roundings), next_obs = nx,
+ *                                         disc = terminated[i] ? 0 : discount[j + 1], nstep = j + 1;
+ *   then d_open[i] = done ? 0 : min(o + 1, n_step - 1), d_cursor[i] = (c + 1) mod K, d_filled[i] = min(d_filled[i] + 1, K),
+ *   d_last_obs[i] = d_obs_in[i].
+ *   Every stored row is therefore at all times a consistent nstep-step transition with the target rew + disc * Q(next_obs): it never
+ *   spans an episode boundary, bootstraps through a truncation from final_obs and not at all through a termination.
+ * tg_replay_sample, one launch: R = d_filled[0] n; element b takes row d_indices[b], or with d_indices == NULL row
+ *   ((uint64)w R) >> 32 for w = word 0 of the Philox draw (seed, idx = b, sub = ordinal >> 32, stream = ordinal & 0xffffffff);
+ *   o_obs [B][S], o_act [B][A], o_rew [B], o_next_obs [B][S], o_disc [B] = that row, o_idx i64 [B] = its index.  A row outside
+ *   [0, R) is not read: its outputs are NaN.
+ * Refused before any launch: a null pointer (d_indices may be NULL), n <= 0, batch <= 0, capacity_steps <= 0, n_step outside
+ * [1, 16], capacity_steps < n_step, capacity_steps n >= 2^31, a storage array, d_last_obs or a sample output that is not 16-byte
+ * aligned (TG_ERR_ARG); obs_dim outside [1, 32] or act_dim outside [1, 8] (TG_ERR_UNSUPPORTED). */
+typedef struct tg_replay {
+    float*    d_obs;
+    float*    d_act;
+    float*    d_next_obs;
+    float*    d_rew;
+    float*    d_disc;
+    uint8_t*  d_nstep;
+    float*    d_last_obs;
+    int32_t*  d_cursor;
+    int32_t*  d_filled;
+    int32_t*  d_open;
+    int64_t   n;
+    int32_t   capacity_steps;
+    int32_t   obs_dim;
+    int32_t   act_dim;
+    int32_t   n_step;
+    float     discount[17];
+} tg_replay;
+int  tg_replay_start(const tg_replay* r, const float* d_obs_in, void* stream);
+int  tg_replay_push(const tg_replay* r, const float* d_actions, const float* d_obs_in, const float* d_reward, const uint8_t* d_terminated,
+                    const uint8_t* d_truncated, const float* d_final_obs, void* stream);
+int  tg_replay_sample(const tg_replay* r, int64_t batch, const int64_t* d_indices, uint64_t seed, uint64_t ordinal, float* o_obs,
+                      float* o_act, float* o_rew, float* o_next_obs, float* o_disc, int64_t* o_idx, void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

@@ -16,6 +16,7 @@ from .rollout import DeviceRollout, DeviceTrajectory, RolloutManager, RolloutWor
 from .buffers import Buffer, Rollout_Buffer
 from .evaluation import Evaluator, EvalResult
 from .vector import DeviceVecEnv
+from .replay import DeviceReplayBuffer
 from .algorithms import Algorithm, GRPO, PPO
 from .pipelines import (Pipeline, create_cartpole_pipeline_grpo, create_cartpole_pipeline_ppo,
                         create_quadpole_pipeline_ppo, create_quadpole2d_pipeline_ppo)
@@ -25,6 +26,6 @@ __all__ = [
     "Box", "Env", "CartPole", "Pendulum", "QuadPole", "QuadPole2D", "QuadPoleSwarm", "Quadrotor", "QuadrotorSwarm",
     "NeuralNetwork", "ActorCritic", "GaussianActor_NeuralNetwork", "GaussianActorCritic_NeuralNetwork",
     "DeviceRollout", "DeviceTrajectory", "RolloutManager", "RolloutWorker", "Buffer", "Rollout_Buffer",
-    "Algorithm", "GRPO", "PPO", "Evaluator", "EvalResult", "DeviceVecEnv", "Pipeline", "create_cartpole_pipeline_grpo", "create_cartpole_pipeline_ppo",
+    "Algorithm", "GRPO", "PPO", "Evaluator", "EvalResult", "DeviceVecEnv", "DeviceReplayBuffer", "Pipeline", "create_cartpole_pipeline_grpo", "create_cartpole_pipeline_ppo",
     "create_quadpole_pipeline_ppo", "create_quadpole2d_pipeline_ppo", "distributed", "hip_ops",
 ]

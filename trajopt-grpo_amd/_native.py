@@ -149,6 +149,14 @@ class VecEnv(C.Structure):
                 ("dtype", C.c_int32)]
 
 
+class Replay(C.Structure):
+    """tg_replay (include/trajopt_grpo_hip.h): the storage and per-slot arrays of a replay buffer and what is fixed per object."""
+    _fields_ = [("d_obs", C.c_void_p), ("d_act", C.c_void_p), ("d_next_obs", C.c_void_p), ("d_rew", C.c_void_p), ("d_disc", C.c_void_p),
+                ("d_nstep", C.c_void_p), ("d_last_obs", C.c_void_p), ("d_cursor", C.c_void_p), ("d_filled", C.c_void_p),
+                ("d_open", C.c_void_p), ("n", C.c_int64), ("capacity_steps", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32),
+                ("n_step", C.c_int32), ("discount", C.c_float * 17)]
+
+
 # name -> (restype, argtypes); every symbol include/trajopt_grpo_hip.h declares
 _P, _I32, _I64, _U64, _F, _VP = C.POINTER, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -328,6 +336,9 @@ SIGNATURES = {
     "tg_eval_cells": (C.c_int, [_P(Traj), _VP, _I64, _VP, _VP, _VP]),
     "tg_vec_env_step": (C.c_int, [_P(EnvParams), _VP, _I32, _VP, _P(VecEnv), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tg_vec_env_reset_all": (C.c_int, [_P(EnvParams), _VP, _P(VecEnv), _I32, _VP, _VP]),
+    "tg_replay_start": (C.c_int, [_P(Replay), _VP, _VP]),
+    "tg_replay_push": (C.c_int, [_P(Replay), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tg_replay_sample": (C.c_int, [_P(Replay), _I64, _VP, _U64, _U64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),
