@@ -94,6 +94,12 @@ int  tg_abi_version(void);
  * arithmetic and memory operations, bit-identical results, fewer instructions.  on = 0: every launch takes the run-time-depth kernel.
  * Default 1.  Returns the previous value. */
 int  tg_chain_depth_kernels(int on);
+/* Process-wide switch of the block-structured bf16 forward chain: tg_mlp_forward_chain_loss_ex with the plain head, panel order and
+ * H = 256 (any depth it takes) runs an instantiation whose first and top H x H layer are peeled off the layer loop and whose ring
+ * slots, wait counts and per-layer pointers are no per-block run-time work -- the same arithmetic and memory operations,
+ * bit-identical results, fewer instructions.  on = 0: every launch takes the run-time kernel.  Default 1.  Returns the previous value.
+ * Independent of tg_chain_depth_kernels. */
+int  tg_chain_fwd_kernels(int on);
 
 int  tg_env_dims(int env_id, int* obs_dim, int* act_dim);
 int  tg_env_default_params(int env_id, int max_steps, tg_env_params* out);

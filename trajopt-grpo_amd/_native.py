@@ -163,6 +163,7 @@ SIGNATURES = {
     "tg_last_error": (C.c_char_p, []),
     "tg_abi_version": (C.c_int, []),
     "tg_chain_depth_kernels": (C.c_int, [C.c_int]),
+    "tg_chain_fwd_kernels": (C.c_int, [C.c_int]),
     "tg_env_dims": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int)]),
     "tg_env_default_params": (C.c_int, [C.c_int, C.c_int, _P(EnvParams)]),
     "tg_env_finalize_params": (C.c_int, [_P(EnvParams)]),
@@ -409,6 +410,12 @@ def chain_depth_kernels_default():
     """TG_CHAIN_DEPTH_KERNELS (default 1): may the bf16 backward chain run its depth-specialised kernel (tg_chain_depth_kernels)?
     Read when a GemmMLP is built; GemmMLP.depth_kernels carries it to every launch."""
     return os.environ.get("TG_CHAIN_DEPTH_KERNELS", "1") != "0"
+
+
+def chain_fwd_kernels_default():
+    """TG_CHAIN_FWD_KERNELS (default 1): may the bf16 forward chain's training pass run its block-structured kernel
+    (tg_chain_fwd_kernels)?  Read when a GemmMLP is built; GemmMLP.fwd_depth_kernels carries it to every launch."""
+    return os.environ.get("TG_CHAIN_FWD_KERNELS", "1") != "0"
 
 
 def event_pair():

@@ -17,6 +17,9 @@ int set_error(int code, const char* fmt, ...) {
 // tg_chain_depth_kernels: may the bf16 chain launchers pick a depth-specialised instantiation?  (process-wide)
 static std::atomic<int> g_chain_depth_kernels{1};
 bool chain_depth_kernels() { return g_chain_depth_kernels.load(std::memory_order_relaxed) != 0; }
+// tg_chain_fwd_kernels: may the bf16 forward chain's training pass run its block-structured instantiation?  (process-wide)
+static std::atomic<int> g_chain_fwd_kernels{1};
+bool chain_fwd_kernels() { return g_chain_fwd_kernels.load(std::memory_order_relaxed) != 0; }
 
 }  // namespace tg
 
@@ -24,6 +27,7 @@ extern "C" {
 const char* tg_last_error(void) { return tg::g_err; }
 int tg_abi_version(void) { return TG_ABI_VERSION; }
 int tg_chain_depth_kernels(int on) { return tg::g_chain_depth_kernels.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed); }
+int tg_chain_fwd_kernels(int on) { return tg::g_chain_fwd_kernels.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed); }
 
 int tg_clock_probe_attach(int32_t family, void* d_probe) {
     switch (family) {

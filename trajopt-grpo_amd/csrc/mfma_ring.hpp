@@ -156,4 +156,31 @@ __device__ static inline const uint4* ring_next_at(const uint4*& wfrag, uint4* r
     return ring + (c % D) * (KS * 64);
 }
 
+// Block-structured forward chain (mlp_fwd_chain.hip, kBlk): a round of 8 n + 2 blocks on a ring of 4 slots turns the ring by HALF a
+// ring, whatever the depth n, so the ring keeps two per-round bases that swap at the round's end instead of per-block state.  Block
+// c of the round sits in slot (s + c) % 4, s = 0 or 2 the slot of the round's first block: relative slots j = c % 4 = 0, 1 hang off
+// the base of slot s, j = 2, 3 off the base of slot s ^ 2, at compile-time offsets.  `rd` are the lane's read pointers into those two
+// slots (fragment reads: one register plus an immediate), `m0b` the LDS byte addresses of the wave's first piece in them (scalars:
+// `wave` went through readfirstlane, M0 is one scalar add).  The DMA behind the barrier of a block in relative slot j refills
+// relative slot j + 3 (the block before it, which every wave has finished reading) from `src + off`: a scalar base (the stream, or
+// a layer's first block in it) plus a compile-time offset plus the lane's 32-bit offset `voff` (= 16 threadIdx.x: the wave's piece
+// and the lane's 16 bytes in it).  Base and lane offset pass through an empty asm statement, as in ring_next_at.  The same barrier
+// and the same DMAs in the same order as TG_RING_NEXT.
+template <int KS, int WPW>
+__device__ static inline const uint4* ring_next_rel(const char*& src, int off, const uint4* const (&rd)[2], const uint32_t (&m0b)[2], int j,
+                                                    uint32_t& voff) {
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" : "+v"(voff), "+s"(src) : : "memory");
+    const int jd = (j + 3) & 3;
+    const uint32_t dst = m0b[jd >> 1] + (jd & 1) * (KS * 1024);
+#pragma unroll
+    for (int q = 0; q < KS / WPW; ++q) {
+        // (the piece's scalar base is pinned too: folded with the lane offset, hipcc adds 64-bit constants on the vector unit)
+        const char* piece = src + off + q * (WPW * 1024);
+        asm volatile("" : "+s"(piece));
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(piece + voff), (lds_void*)(uintptr_t)(dst + q * (WPW * 1024)), 16, 0, 0);
+    }
+    return rd[(j & 3) >> 1] + (j & 1) * (KS * 64);
+}
+
 }  // namespace tg

@@ -184,6 +184,46 @@ __device__ static inline void chain_block(const uint4* __restrict__ cur, const f
                                 acc[1][c][3]);
 }
 
+// The same block for the block-structured kernel (kBlk, H = 256), with the fragment reads of a k-step as ONE opaque statement: both
+// halves' fragments, then the wait, then the step's four products -- the schedule hipcc gives chain_block above in the run-time
+// kernels.  In the block-structured kernel its scheduler finds the register pressure high, takes the reads apart and leaves every
+// pair of products waiting for an LDS read of its own (profiles/r19_chain_depth_ab.md, section 4: +2 % on the pass).  `base`: the
+// LDS byte address of the lane's 16 bytes in the first of a pair of ring slots, `second`: the block sits in the pair's second slot
+// (a constant of the unrolled caller).  The same products in the same order per accumulator: the same bits.
+#define TG_FRAG_PAIR(A0, A1, BASE, OFF)                                                                              \
+    asm volatile("ds_read_b128 %0, %2 offset:" #OFF "\n\tds_read_b128 %1, %2 offset:" #OFF "+1024\n\ts_waitcnt lgkmcnt(0)" \
+                 : "=&v"(A0), "=&v"(A1)                                                                               \
+                 : "v"(BASE)                                                                                         \
+                 : "memory");
+#define TG_PAIR_KSTEP(KS)                                                                                            \
+    {                                                                                                                \
+        uint4 a0, a1;                                                                                                \
+        if (second) { TG_FRAG_PAIR(a0, a1, base, 16384+KS*2048) } else { TG_FRAG_PAIR(a0, a1, base, KS*2048) }       \
+        _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                                \
+            acc[0][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a0), xin[c][KS], acc[0][c], 0, 0, 0); \
+        _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                                \
+            acc[1][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a1), xin[c][KS], acc[1][c], 0, 0, 0); \
+    }
+__device__ static inline void chain_block_pairs(uint32_t base, bool second, const float* __restrict__ b8, const bf16x8 (&xin)[2][8],
+                                                bf16x8 (&out)[2]) {
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+        const float4 b4 = lds_float4(b8 + 4 * f);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) acc[f][c] = f32x4{b4.x, b4.y, b4.z, b4.w};
+    }
+    __builtin_amdgcn_s_setprio(1);
+    TG_PAIR_KSTEP(0) TG_PAIR_KSTEP(1) TG_PAIR_KSTEP(2) TG_PAIR_KSTEP(3) TG_PAIR_KSTEP(4) TG_PAIR_KSTEP(5) TG_PAIR_KSTEP(6) TG_PAIR_KSTEP(7)
+    __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+        out[c] = relu_pack_bf16(acc[0][c][0], acc[0][c][1], acc[0][c][2], acc[0][c][3], acc[1][c][0], acc[1][c][1], acc[1][c][2],
+                                acc[1][c][3]);
+}
+#undef TG_PAIR_KSTEP
+#undef TG_FRAG_PAIR
+
 __device__ static inline int wave_of(unsigned tid) { return (int)(tid >> 6); }
 
 #define TG_CHAIN_ADVANCE(WAITN) TG_RING_ADVANCE(WAITN)
@@ -199,7 +239,14 @@ __device__ static inline int wave_of(unsigned tid) { return (int)(tid >> 6); }
 // kStd (with kHead): the policy's learned log-std (tg_mlp_forward_chain_loss_std): the Gaussian's constants come from the device, and
 // each valid actor row stores dlp (dmu_k^2 inv_var_k - 1), its contribution to d loss / d log_std (one more 16-B store per row).
 // kPanel (with kStore): the activations are stored in panel order (mfma_ring.hpp PanelOrder) instead of row-major.
-template <int H, int WPW, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false, bool kPanel = false>
+// kBlk (H = 256, kHead, kPanel, plain head): the learner's training pass with what a block can know at compile time taken off its
+// path.  The depth stays a run-time argument; the first and the top H x H layer are peeled off the layer loop (mlp_fwd_chain_layer.inc,
+// included three times), so every wait count and whether a block stores are constants; the ring keeps no per-block state
+// (ring_next_rel); acts.p / acts.m are read once per layer into scalars; the activation stores take a scalar base and the lane's
+// 32-bit offset.  Barriers, DMAs, stores and counted waits are the run-time form's, in the same order and number
+// (profiles/r22_fwd_chain_block_ab.md).  The other instantiations compile from the text they always had.
+template <int H, int WPW, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false, bool kPanel = false,
+          bool kBlk = false>
 __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16_t* __restrict__ x, const uint4* __restrict__ wfrag,
                                                                     const float* __restrict__ bias, int32_t n_hh, int64_t rows,
                                                                     ChainActs acts, float* __restrict__ out, int32_t out_cols,
@@ -208,6 +255,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     static_assert(!kRef || kHead, "the reference penalty is a term of the fused head");
     static_assert(!kStd || kHead, "the learned log-std is a term of the fused head");
     static_assert(!kPanel || (kStore && D == 4), "panel order is a layout of the stored activations; its wait counts are for P = 3");
+    static_assert(!kBlk || (H == 256 && WPW == 8 && kHead && kPanel && !kRef && !kStd), "the block-structured pass is the learner's plain head");
     // (written into the by-value argument as norm8's values are below: the compiler's resource report shows 0 B of scratch and no
     // vector-register spill for every instantiation of this kernel, the kStd ones included -- the fields stay scalar registers)
     if constexpr (kHead) loss_from_device<kStd>(L);
@@ -255,7 +303,8 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     [[maybe_unused]] float* sums_f = reinterpret_cast<float*>(dtiles + 2 * WPW * 1024 + WPW * 16 * 32) + (wave_of(threadIdx.x) * 16 + (threadIdx.x & 15)) * 4; \
     [[maybe_unused]] float* hacc = reinterpret_cast<float*>(dtiles + 2 * WPW * 1024 + WPW * 16 * 48) + (wave_of(threadIdx.x) * MT * 16 + (threadIdx.x & 15)) * 4;
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int wave = kBlk ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);   // (kBlk: a scalar, see ring_next_rel)
     const int grp = lane >> 4, col = lane & 15;
     const int64_t n_rounds = (rows + 32 * WPW - 1) / (32 * WPW);
     const int n_blocks = n_hh * MT + 2;
@@ -320,6 +369,22 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     // the counted wait assumes the stores of three earlier blocks behind the block it waits for; before the first
     // block there are none, so the prologue is drained once
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // kBlk: the ring's two per-round bases (the first round starts in slot 0), the stream and the lane's offset into a block
+    [[maybe_unused]] const uint4* rd[2] = {ring + lane, ring + 2 * KS * 64 + lane};
+    [[maybe_unused]] uint32_t m0b[2] = {(uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4*)ring + 1024u * (uint32_t)wave, 0u};
+    m0b[1] = m0b[0] + 2u * KS * 1024u;
+    [[maybe_unused]] const char* wsrc = reinterpret_cast<const char*>(wfrag);
+    [[maybe_unused]] uint32_t voff = 16u * threadIdx.x;
+    const int rl = kBlk ? 0 : lane;                  // (kBlk: `cur` is the lane's own pointer)
+    // the next block's barrier, DMA and fragments: TG_RING_NEXT, or with kBlk the block in relative slot J, whose DMA fetches stream
+    // block POS
+#define TG_FWD_RING_NEXT(J, POS)                                                          \
+    const uint4* cur;                                                                     \
+    if constexpr (kBlk) {                                                                 \
+        cur = ring_next_rel<KS, WPW>(wsrc, (POS) * (KS * 1024), rd, m0b, (J), voff);      \
+    } else {                                                                              \
+        TG_RING_NEXT_INTO(cur)                                                            \
+    }
 
     for (int64_t round = blockIdx.x; round < n_rounds; round += gridDim.x) {
         const int64_t row0 = round * (32 * WPW) + wave * 32;
@@ -335,12 +400,20 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
 #pragma unroll
             for (int c = 0; c < 2; ++c) poff[c] = PanelOrder<H>::chunk_off(PanelOrder<H>::store_row(row0 + 16 * c + col, rows), grp);
         }
+        // kBlk: the same offsets from the round's first tile, a scalar.  Every store row lies in the round's own 8 tiles (a round
+        // that runs holds a valid row, so the fall-back row `rows - 1` does too): 32 bits, and never negative.
+        [[maybe_unused]] const int64_t round_off = round * (WPW * (int64_t)PanelOrder<H>::PANEL);
+        [[maybe_unused]] uint32_t poff32[2];
+        if constexpr (kBlk) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) poff32[c] = (uint32_t)(poff[c] - round_off);
+        }
 
         // ---- layer 0: [H x 32] . [32 x 32 rows]; one block holds all MT output blocks (one k-step, 2 halves each) ----
         {
             // (kHead: the top layer of the previous round stored nothing: count the DMAs alone)
             if constexpr (kHead) { TG_RING_WAIT(kWaitMin) } else { TG_RING_WAIT(kWaitOdd) }
-            TG_RING_NEXT
+            TG_FWD_RING_NEXT(0, 3)
             // the x tile was issued a full round ago (or in the prologue): it is older than everything the wait let pass
             bf16x8 x0[2];
 #pragma unroll
@@ -352,7 +425,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
 #pragma unroll
                 for (int f = 0; f < 2; ++f) {
                     const float4 b4 = lds_float4(bias_s + 32 * mt + 8 * grp + 4 * f);
-                    const bf16x8 a = __builtin_bit_cast(bf16x8, cur[(mt * 2 + f) * 64 + lane]);
+                    const bf16x8 a = __builtin_bit_cast(bf16x8, cur[(mt * 2 + f) * 64 + rl]);
 #pragma unroll
                     for (int c = 0; c < 2; ++c)
                         acc[f][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, x0[c], f32x4{b4.x, b4.y, b4.z, b4.w}, 0, 0, 0);
@@ -377,7 +450,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                 for (int ks = 0; ks < K8; ++ks) xin[c][ks] = xout[c][ks];
         }
         // ---- hidden H x H layers: one block per 32 output features ----
-        for (int l = 0; l < n_hh; ++l) {
+        for (int l = 0; l < (kBlk ? 0 : n_hh); ++l) {      // (kBlk: the peeled form below)
             const float* bl = bias_s + (l + 1) * H + 8 * grp;
             uint32_t mw[2][MT / 2];
 #pragma unroll
@@ -429,10 +502,30 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
 #pragma unroll
                 for (int ks = 0; ks < K8; ++ks) xin[c][ks] = xout[c][ks];
         }
+        if constexpr (kBlk) {
+            // block 1 + MT l + mt of the round sits in relative slot (1 + mt) % 4 and fetches block 4 + MT l + mt: `lay` is the stream at
+            // the layer's first block; the top layer's last two blocks (and the head) fetch the next round's first three
+            const char* lay = wsrc + KS * 1024;
+            {
+                constexpr bool kFirst = true, kTop = false;
+                constexpr int l = 0;
+#include "mlp_fwd_chain_layer.inc"
+            }
+#pragma unroll 1
+            for (int l = 1; l < n_hh - 1; ++l) {
+                constexpr bool kFirst = false, kTop = false;
+#include "mlp_fwd_chain_layer.inc"
+            }
+            {
+                constexpr bool kFirst = false, kTop = true;
+                const int l = n_hh - 1;
+#include "mlp_fwd_chain_layer.inc"
+            }
+        }
         // ---- head: <= 16 outputs in half 0 of the block, natural order: register r of lane group g is output 4 g + r ----
         {
             if constexpr (kHead) { TG_RING_WAIT(kWaitMin) } else if constexpr (kPanel) { TG_PANEL_WAIT(3) } else { TG_RING_WAIT(kWaitEven) }
-            TG_RING_NEXT
+            TG_FWD_RING_NEXT(1, 2)
             if (kStore && acts.m[n_hh]) {                       // the last hidden activation's mask bits
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
@@ -446,7 +539,7 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
             f32x4 acc[2] = {f32x4{b4.x, b4.y, b4.z, b4.w}, f32x4{b4.x, b4.y, b4.z, b4.w}};
 #pragma unroll
             for (int ks = 0; ks < K8; ++ks) {
-                const bf16x8 a = __builtin_bit_cast(bf16x8, cur[(ks * 2) * 64 + lane]);
+                const bf16x8 a = __builtin_bit_cast(bf16x8, cur[(ks * 2) * 64 + rl]);
 #pragma unroll
                 for (int c = 0; c < 2; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, xin[c][ks], acc[c], 0, 0, 0);
             }
@@ -561,7 +654,16 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
                 dma_loss_inputs(round + gridDim.x);
             }
         }
+        if constexpr (kBlk) {                         // 8 n + 2 blocks on 4 slots: the next round starts two slots on
+            const uint4* r0 = rd[0];
+            rd[0] = rd[1];
+            rd[1] = r0;
+            const uint32_t m0 = m0b[0];
+            m0b[0] = m0b[1];
+            m0b[1] = m0;
+        }
     }
+#undef TG_FWD_RING_NEXT
     if constexpr (kHead) {
         TG_HEAD_LDS
         // partial head weight gradient: slab [workgroup][K quarter][16 outputs][H]; outputs 4 g + r (only < 8 are ever non-zero)
@@ -596,14 +698,15 @@ __global__ __launch_bounds__(64 * WPW, 2) void mlp_fwd_chain_kernel(const uint16
     if constexpr (kHead) { TG_CLOCK_PROBE_END(g_probe_fwd_chain) } else { TG_CLOCK_PROBE_END(g_probe_fwd_chain_plain) }
 }
 
-template <int H, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false, bool kPanel = false>
+template <int H, bool kStore, int D, bool kA0, bool kHead = false, bool kRef = false, bool kStd = false, bool kPanel = false,
+          bool kBlk = false>
 static int chain_launch(const void* x, const void* wfrag, const float* bias, int n_hh, int64_t rows, const ChainActs& acts, float* out,
                         int out_cols, hipStream_t st, const ChainLoss& loss = ChainLoss{}) {
     constexpr int WPW = 8, KS = H / 16;
     // (the store staging area: row-major stores transpose through it, the head phase keeps its shared tiles there)
     const size_t shmem = (size_t)D * KS * 1024 + (size_t)(n_hh + 2) * H * sizeof(float) + (size_t)WPW * 2048 +
                          (kPanel && !kHead ? 0 : (size_t)WPW * 32 * 128) + (kHead ? (size_t)2 * WPW * 1024 + (size_t)WPW * 16 * 48 + (size_t)WPW * (H / 32) * 16 * 16 : 0);
-    auto kern = mlp_fwd_chain_kernel<H, WPW, kStore, D, kA0, kHead, kRef, kStd, kPanel>;
+    auto kern = mlp_fwd_chain_kernel<H, WPW, kStore, D, kA0, kHead, kRef, kStd, kPanel, kBlk>;
     static LdsOptIn opt_in;
     if (int rc = reserve_dynamic_lds((const void*)kern, shmem, opt_in, "tg_mlp_forward_chain")) return rc;
     const int cus = device_cus();
@@ -714,6 +817,9 @@ static int forward_chain_loss(const void* d_x, const void* d_wfrag, const float*
     const int n_hh = n_hidden_layers - 1;
     if (layout == TG_LAYOUT_PANEL) {                    // (separate instantiations again)
         TG_REQUIRE(!use_std && !use_ref, "tg_mlp_forward_chain_loss_ex: panel order is built for the plain head only");
+        // the learner's shape: the block-structured instantiation (kBlk; any depth this entry point takes), unless switched off
+        if (hidden == 256 && chain_fwd_kernels())
+            return chain_launch<256, true, 4, false, true, false, false, true, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L);
         return hidden == 256 ? chain_launch<256, true, 4, false, true, false, false, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L)
                              : chain_launch<128, true, 4, false, true, false, false, true>(d_x, d_wfrag, d_bias, n_hh, rows, acts, nullptr, 8, st, L);
     }

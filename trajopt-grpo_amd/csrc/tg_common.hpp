@@ -11,6 +11,7 @@ namespace tg {
 
 int set_error(int code, const char* fmt, ...);
 bool chain_depth_kernels();                 // the switch of tg_chain_depth_kernels (api_common.cpp)
+bool chain_fwd_kernels();                   // the switch of tg_chain_fwd_kernels (api_common.cpp)
 
 #define TG_REQUIRE(cond, ...)                                   \
     do {                                                        \

@@ -306,6 +306,9 @@ class GemmMLP:
         # fewer instructions, profiles/r19_chain_depth_ab.md); False: the run-time-depth kernel.  The native switch is process-wide
         # (tg_chain_depth_kernels), so it is set in front of the launch it governs.
         self.depth_kernels = N.chain_depth_kernels_default()
+        # ... and the forward chain's training pass its block-structured kernel (H = 256, plain head, panel order, any depth: bit for
+        # bit the same again, profiles/r22_fwd_chain_block_ab.md); a switch of its own (tg_chain_fwd_kernels), set the same way
+        self.fwd_depth_kernels = N.chain_fwd_kernels_default()
         if self.act == "Tanh":
             # (the resident 16-row kernel and the H = 256 kernel are ReLU-only: a Tanh net of the resident shape runs the chain kernel;
             # nothing is rebuilt from mask bits, so every activation and dZ is stored)
@@ -618,6 +621,8 @@ class GemmMLP:
         name, tail, targs = loss_entry("bf16", N.TG_ACT_RELU, ref, std)
         if panel:
             name, tail, targs = "tg_mlp_forward_chain_loss_ex", (None, None, N.TG_LAYOUT_PANEL), ",false,false,true"
+            if self._set_fwd_depth_kernels(lib) and H == 256:             # (what the launcher picks: the events' label)
+                targs += ",true"
         ev = None
         if self.fwd_events is not None:
             ev = N.event_pair()
@@ -649,6 +654,12 @@ class GemmMLP:
         """Carries GemmMLP.depth_kernels to the native switch in front of a chain launch; -> the value set."""
         on = bool(self.depth_kernels)
         lib.tg_chain_depth_kernels(int(on))
+        return on
+
+    def _set_fwd_depth_kernels(self, lib):
+        """Carries GemmMLP.fwd_depth_kernels to the native switch in front of the forward chain's training launch; -> the value set."""
+        on = bool(self.fwd_depth_kernels)
+        lib.tg_chain_fwd_kernels(int(on))
         return on
 
     def _flush_riders(self):
