@@ -1239,6 +1239,50 @@ int  tg_replay_push(const tg_replay* r, const float* d_actions, const float* d_o
 int  tg_replay_sample(const tg_replay* r, int64_t batch, const int64_t* d_indices, uint64_t seed, uint64_t ordinal, float* o_obs,
                       float* o_act, float* o_rew, float* o_next_obs, float* o_disc, int64_t* o_idx, void* stream);
 
+/* ---- Prioritised replay: proportional priorities in a sum tree of fan-out 64 (csrc/replay_prio.hip; additions to ABI 13) ----
+ * The struct below is passed beside a tg_replay, 152 bytes.  Level 0 is one float32 leaf per storage row (leaf index = row index, R_cap =
+ * capacity_steps n of them), level l + 1 has size[l + 1] = ceil(size[l] / 64) nodes, up to the root (a level of one node; there is
+ * always at least one level above the leaves, at most 6 for R_cap < 2^31).  Level l starts at d_tree + offset[l]; every level is padded
+ * with zeros to a multiple of 64 floats, so a node's 64 children are 256 contiguous bytes.  tg_replay_prio_levels (host only) fills
+ * levels / size / offset for `rows` leaves and returns the floats of the allocation (TG_ERR_ARG for rows outside [1, 2^31)).
+ * A node is the float32 sum of its 64 children in one fixed order -- s[i] += s[i + 32], then strides 16, 8, 4, 2, 1, not contracted --
+ * and is always recomputed from its children, so a tree kept up to date by push / update equals tg_replay_prio_rebuild's bit for bit.
+ * d_max: the running maximum priority as float32 bits (leaves are >= 0, so bits order as unsigned integers), kept with integer
+ * atomicMax; the owner initialises it to 1.0f.  No float atomic anywhere.
+ *
+ * tg_replay_prio_push (behind tg_replay_push on the same stream): the n leaves of time slot (d_cursor[0] - 1) mod K = *d_max, and every
+ *   node above them is recomputed.  Other leaves stay.
+ * tg_replay_prio_update: with R = d_filled[0] n, for every b with 0 <= d_idx[b] < R and finite d_td[b], leaf d_idx[b] =
+ *   (float)pow((double)|d_td[b]| + (double)eps, (double)alpha), at most FLT_MAX; where d_idx repeats, the largest wins (one launch
+ *   stores 0 to every named leaf, the next integer-atomicMaxes the new bits into leaf and *d_max); then the nodes above.
+ * tg_replay_prio_sample, two launches: element b takes row d_indices[b], or with d_indices == NULL the leaf the descent reaches from
+ *   the root for t = (b + u01d(w0, w1)) / batch * (double)root in float64, (w0, w1) from the Philox draw of tg_replay_sample: at each
+ *   level the 64 children's inclusive float32 prefix by the Kogge-Stone scan (d = 1, 2, .., 32: x[i] += x[i - d] for i >= d), the child
+ *   is the first with child > 0 and (double)prefix > t, else the last with child > 0, and t -= (double)(prefix before it).  Outputs as
+ *   tg_replay_sample's plus o_raw [B] = (float)pow((double)R leaf / (double)root, -(double)beta) and o_weight [B] = o_raw / max_b o_raw
+ *   (float32 division; NaNs are not candidates for the maximum).  A row outside [0, R), a zero leaf or a zero root: NaN outputs
+ *   (o_idx = the index given, or -1).
+ * tg_replay_prio_rebuild: every level above the leaves from the leaves.
+ * Refused before any launch, beside what tg_replay's entries refuse: null pointers, levels / size / offset that are not
+ * tg_replay_prio_levels' for capacity_steps n rows, d_tree or an output not 16-byte aligned, batch outside [1, 2^31), alpha / eps /
+ * beta negative or not finite. */
+typedef struct tg_replay_prio {
+    float*    d_tree;
+    uint32_t* d_max;
+    int64_t   offset[8];
+    int64_t   size[8];
+    int32_t   levels;
+    int32_t   reserved;
+} tg_replay_prio;
+int64_t tg_replay_prio_levels(int64_t rows, tg_replay_prio* p);
+int  tg_replay_prio_push(const tg_replay* r, const tg_replay_prio* p, void* stream);
+int  tg_replay_prio_update(const tg_replay* r, const tg_replay_prio* p, int64_t batch, const int64_t* d_idx, const float* d_td,
+                           float alpha, float eps, void* stream);
+int  tg_replay_prio_sample(const tg_replay* r, const tg_replay_prio* p, int64_t batch, const int64_t* d_indices, uint64_t seed,
+                           uint64_t ordinal, float beta, float* o_obs, float* o_act, float* o_rew, float* o_next_obs, float* o_disc,
+                           int64_t* o_idx, float* o_raw, float* o_weight, void* stream);
+int  tg_replay_prio_rebuild(const tg_replay_prio* p, void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

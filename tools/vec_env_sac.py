@@ -9,6 +9,9 @@ learned temperature.  The buffer hands over consistent n-step rows, so the targe
 with disc = gamma^k where the window was closed by the clock or is still open, and 0 behind a termination.  It is not a benchmark.
 
     python tools/vec_env_sac.py --env CartPole --seeds 0 1 2 --n-step 3 --out profiles/curve.txt
+
+--per samples by proportional priority instead (DeviceReplayBuffer(prioritized=True)): the critic loss is weighted by the importance
+weights and every sampled row's priority becomes the mean |TD error| of the two critics.
 """
 import argparse
 import math
@@ -55,7 +58,8 @@ def train(seed, args, dev):
     torch.manual_seed(seed)
     env = tg.environments.ENV_CLASSES[args.env](max_steps=args.max_steps)
     venv = tg.DeviceVecEnv(env, args.envs, seed=seed, device=dev)
-    buf = tg.DeviceReplayBuffer.for_env(venv, args.capacity_steps, n_step=args.n_step, gamma=args.gamma, seed=seed)
+    buf = tg.DeviceReplayBuffer.for_env(venv, args.capacity_steps, n_step=args.n_step, gamma=args.gamma, seed=seed,
+                                        prioritized=args.per, alpha=args.per_alpha, beta=args.per_beta)
     S, A = venv.S, venv.A
     actor, critic, target = Actor(S, A, args.hidden).to(dev), TwinQ(S, A, args.hidden).to(dev), TwinQ(S, A, args.hidden).to(dev)
     target.load_state_dict(critic.state_dict())
@@ -76,13 +80,17 @@ def train(seed, args, dev):
         ret_cnt += done.sum()
         if it >= args.random_iters:
             for _ in range(args.updates):
-                b_obs, b_act, b_rew, b_next, b_disc, _ = buf.sample(args.batch)
+                b_obs, b_act, b_rew, b_next, b_disc, b_idx, *b_w = buf.sample(args.batch)
                 with torch.no_grad():
                     alpha = log_alpha.exp()
                     a2, logp2 = actor(b_next)
                     y = b_rew + b_disc * (torch.min(*target(b_next, a2)) - alpha * logp2)
                 q1, q2 = critic(b_obs, b_act)
-                q_loss = (q1 - y).pow(2).mean() + (q2 - y).pow(2).mean()
+                if args.per:                                             # importance-weighted, and the rows' new priorities
+                    q_loss = (b_w[0] * ((q1 - y).pow(2) + (q2 - y).pow(2))).mean()
+                    buf.update_priorities(b_idx, (0.5 * ((q1 - y).abs() + (q2 - y).abs())).detach())
+                else:
+                    q_loss = (q1 - y).pow(2).mean() + (q2 - y).pow(2).mean()
                 opt_q.zero_grad(set_to_none=True)
                 q_loss.backward()
                 opt_q.step()
@@ -129,6 +137,9 @@ def main():
     ap.add_argument("--tau", type=float, default=0.005)
     ap.add_argument("--eval-every", type=int, default=50, help="env steps of every slot per evaluation point")
     ap.add_argument("--log-every", type=int, default=10, help="print every this many evaluation points")
+    ap.add_argument("--per", action="store_true", help="proportional prioritised replay (importance-weighted critic loss)")
+    ap.add_argument("--per-alpha", type=float, default=0.6)
+    ap.add_argument("--per-beta", type=float, default=0.4)
     ap.add_argument("--out", default=None, help="write the curves here: one line per seed and evaluation point")
     args = ap.parse_args()
     if not torch.cuda.is_available():

@@ -157,6 +157,12 @@ class Replay(C.Structure):
                 ("n_step", C.c_int32), ("discount", C.c_float * 17)]
 
 
+class ReplayPrio(C.Structure):
+    """tg_replay_prio (include/trajopt_grpo_hip.h): the sum tree of a prioritised replay buffer, 152 bytes."""
+    _fields_ = [("d_tree", C.c_void_p), ("d_max", C.c_void_p), ("offset", C.c_int64 * 8), ("size", C.c_int64 * 8), ("levels", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/trajopt_grpo_hip.h declares
 _P, _I32, _I64, _U64, _F, _VP = C.POINTER, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -340,6 +346,11 @@ SIGNATURES = {
     "tg_replay_start": (C.c_int, [_P(Replay), _VP, _VP]),
     "tg_replay_push": (C.c_int, [_P(Replay), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tg_replay_sample": (C.c_int, [_P(Replay), _I64, _VP, _U64, _U64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tg_replay_prio_levels": (C.c_int64, [_I64, _P(ReplayPrio)]),
+    "tg_replay_prio_push": (C.c_int, [_P(Replay), _P(ReplayPrio), _VP]),
+    "tg_replay_prio_update": (C.c_int, [_P(Replay), _P(ReplayPrio), _I64, _VP, _VP, _F, _F, _VP]),
+    "tg_replay_prio_sample": (C.c_int, [_P(Replay), _P(ReplayPrio), _I64, _VP, _U64, _U64, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tg_replay_prio_rebuild": (C.c_int, [_P(ReplayPrio), _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),

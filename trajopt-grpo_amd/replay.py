@@ -11,6 +11,11 @@ transition for its own k = nstep <= n_step, with the target
 
 so no row is ever "not ready" and sampling needs no exclusion window.  INTEGRATION.md, "Replay buffer", states the rule;
 tests/replay_ref.py restates it in NumPy, bit for bit.  tools/vec_env_sac.py is a complete example.
+
+`prioritized=True` adds proportional prioritised replay (Schaul et al. 2016) on a sum tree of fan-out 64 in device memory
+(csrc/replay_prio.hip): a new row enters with the running maximum priority, sample() descends the tree with stratified draws and
+returns importance weights, update_priorities() writes (|td| + eps) ** alpha.  INTEGRATION.md, "Prioritised replay";
+tests/replay_prio_ref.py restates the tree and the descent bit for bit.
 """
 from __future__ import annotations
 
@@ -35,13 +40,16 @@ class DeviceReplayBuffer:
     capacity_steps  K: time slots of the ring; the buffer holds up to K * num_envs transitions (K >= n_step, K * num_envs < 2^31)
     n_step          longest return a row accumulates, in [1, 16]; gamma in (0, 1]
     seed            of sample()'s draws (unsigned 64-bit)
+    prioritized     True: proportional prioritised sampling with exponent `alpha`, importance exponent `beta` (sample()'s default) and
+                    `priority_eps` added to |td| (all three >= 0, held as float32); False: uniform sampling, nothing else is built
 
     Storage is float32, row-major, row = slot * num_envs + i: `obs`, `act`, `next_obs`, `rew`, `disc`, `nstep` (uint8).
 
     The tensors sample() returns are the object's own buffers, overwritten by the next sample(): clone what you keep."""
 
     def __init__(self, obs_dim: int, act_dim: int, num_envs: int, capacity_steps: int, *, n_step: int = 1, gamma: float = 0.99,
-                 seed: int = 0, device=None):
+                 seed: int = 0, device=None, prioritized: bool = False, alpha: float = 0.6, beta: float = 0.4,
+                 priority_eps: float = 1e-6):
         S, A, n, K, n_step, gamma = int(obs_dim), int(act_dim), int(num_envs), int(capacity_steps), int(n_step), float(gamma)
         if not 1 <= S <= MAX_OBS_DIM or not 1 <= A <= MAX_ACT_DIM:
             raise ValueError(f"DeviceReplayBuffer: obs_dim={S} must be in [1, {MAX_OBS_DIM}] and act_dim={A} in [1, {MAX_ACT_DIM}]")
@@ -55,6 +63,9 @@ class DeviceReplayBuffer:
             raise ValueError(f"DeviceReplayBuffer: capacity_steps {K} x num_envs {n} = {K * n} rows >= 2^31")
         if not 0.0 < gamma <= 1.0:
             raise ValueError(f"DeviceReplayBuffer: gamma={gamma} not in (0, 1]")
+        self.prioritized = bool(prioritized)
+        self.alpha, self.beta, self.priority_eps = (self._exponent(v, name) for v, name in
+                                                    ((alpha, "alpha"), (beta, "beta"), (priority_eps, "priority_eps")))
         self.seed = self._checked_seed(seed)
         self.device = torch.device(device) if device is not None else torch.device("cuda", 0)
         if self.device.type != "cuda":
@@ -86,6 +97,25 @@ class DeviceReplayBuffer:
         self._ordinal = 0                # sample() calls so far: the stream of the next call's draws
         self._started = False
         self._out, self._out_rows = None, 0
+        if self.prioritized:
+            p = N.ReplayPrio()
+            floats = int(self.lib.tg_replay_prio_levels(rows, C.byref(p)))
+            if floats <= 0:
+                N.check(floats, "tg_replay_prio_levels")
+            # every level of the tree in one allocation, zero-padded to multiples of 64; the leaves are its first `rows` floats
+            self._tree = torch.zeros(floats, dtype=torch.float32, device=dev)
+            self._max_priority = torch.ones(1, dtype=torch.float32, device=dev)       # read and written as its bits
+            self.priorities = self._tree[:rows]
+            self.tree_levels = [(int(p.offset[l]), int(p.size[l])) for l in range(p.levels)]
+            p.d_tree, p.d_max = self._tree.data_ptr(), self._max_priority.data_ptr()
+            self._prio = p
+
+    @staticmethod
+    def _exponent(value, name) -> float:
+        value = float(np.float32(value))
+        if not 0.0 <= value < float("inf"):
+            raise ValueError(f"DeviceReplayBuffer: {name}={value} must be finite and >= 0")
+        return value
 
     @classmethod
     def for_env(cls, venv, capacity_steps: int, **kwargs):
@@ -141,6 +171,9 @@ class DeviceReplayBuffer:
     def clear(self):
         """Drop every stored row: cursor, filled and open go to 0.  Call start() again before the next add()."""
         self._slots.zero_()
+        if self.prioritized:
+            self._tree.zero_()
+            self._max_priority.fill_(1.0)
         self._pushes = 0
         self._started = False
 
@@ -163,6 +196,9 @@ class DeviceReplayBuffer:
             N.check(self.lib.tg_replay_push(C.byref(self._native), actions.data_ptr(), obs.data_ptr(), reward.data_ptr(),
                                             terminated.data_ptr(), truncated.data_ptr(), final_obs.data_ptr(),
                                             N.stream_ptr(self.device)), "tg_replay_push")
+            if self.prioritized:         # the new time slot's leaves take the running maximum priority
+                N.check(self.lib.tg_replay_prio_push(C.byref(self._native), C.byref(self._prio), N.stream_ptr(self.device)),
+                        "tg_replay_prio_push")
         self._pushes += 1
 
     # ---- reading -----------------------------------------------------------------------------------------------------------------
@@ -175,10 +211,12 @@ class DeviceReplayBuffer:
                          torch.empty(batch, self.obs_dim, dtype=torch.float32, device=dev),
                          torch.empty(batch, dtype=torch.float32, device=dev),
                          torch.empty(batch, dtype=torch.int64, device=dev))
+            if self.prioritized:         # the raw importance weights (kept: `raw_weight`) and the normalised ones
+                self._out += (torch.empty(batch, dtype=torch.float32, device=dev), torch.empty(batch, dtype=torch.float32, device=dev))
             self._out_rows = batch
         return tuple(t[:batch] for t in self._out)
 
-    def sample(self, batch=None, indices=None):
+    def sample(self, batch=None, indices=None, beta=None):
         """-> (obs [B][S], act [B][A], rew [B], next_obs [B][S], disc [B], idx int64 [B]) in one launch; the TD target of row b is
         rew[b] + disc[b] * Q(next_obs[b]).
 
@@ -188,7 +226,16 @@ class DeviceReplayBuffer:
         tensor you refill in place).  With `indices` (int64 device tensor [B]) those rows are gathered; an index outside [0, R) is
         not read and gives a row of NaNs.
 
-        The six tensors are this object's buffers, reallocated only when B grows: the next sample() overwrites them."""
+        The six tensors are this object's buffers, reallocated only when B grows: the next sample() overwrites them.
+
+        prioritized=True: a seven-tuple, the six above and `weight` float32 [B], in two launches (tg_replay_prio_sample).  Element b
+        descends the sum tree for the stratified target (b + u) / B * root, u the 53-bit uniform of the same Philox draw's first two
+        words, so a row is drawn in proportion to its priority and a row of priority 0 or an unfilled one never.  weight[b] =
+        raw[b] / max(raw), raw = (R * priority / root) ** -beta (`beta=`: this call's exponent instead of the object's), also kept
+        in `raw_weight`.  With `indices`, the weights are those rows'.  `beta` and the ordinal are passed by value: a captured
+        graph repeats its draws."""
+        if beta is not None and not self.prioritized:
+            raise ValueError("DeviceReplayBuffer: beta= needs prioritized=True")
         if indices is not None:
             if (not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64 or indices.dim() != 1 or indices.numel() == 0
                     or (batch is not None and int(batch) != indices.numel())):
@@ -203,11 +250,45 @@ class DeviceReplayBuffer:
         if self._pushes == 0:
             raise RuntimeError("DeviceReplayBuffer: sample() on an empty buffer (no add() yet)")
         out = self._outputs(batch)
+        if self.prioritized:
+            beta = self.beta if beta is None else self._exponent(beta, "beta")
+            with torch.cuda.device(self.device):
+                N.check(self.lib.tg_replay_prio_sample(C.byref(self._native), C.byref(self._prio), batch, N.ptr(indices), self.seed,
+                                                       self._ordinal, beta, *(t.data_ptr() for t in out), N.stream_ptr(self.device)),
+                        "tg_replay_prio_sample")
+            self._ordinal += 1
+            self.raw_weight = out[6]
+            return out[:6] + out[7:]
         with torch.cuda.device(self.device):
             N.check(self.lib.tg_replay_sample(C.byref(self._native), batch, N.ptr(indices), self.seed, self._ordinal,
                                               *(t.data_ptr() for t in out), N.stream_ptr(self.device)), "tg_replay_sample")
         self._ordinal += 1
         return out
+
+    def update_priorities(self, idx, td_error):
+        """Row idx[b]'s priority becomes (|td_error[b]| + priority_eps) ** alpha (formed in float64, rounded once), and the running
+        maximum that new rows enter with follows.  idx int64 [B] (sample()'s sixth tensor as it is), td_error float32 [B],
+        both on the device; nothing is read on the host.  An index outside the stored rows and a non-finite error are ignored; where
+        idx repeats, the largest new priority wins.  An idx sampled before the ring took its row back names the new row."""
+        if not self.prioritized:
+            raise RuntimeError("DeviceReplayBuffer: update_priorities() needs prioritized=True")
+        for t, name, dtype in ((idx, "idx", torch.int64), (td_error, "td_error", torch.float32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or t.numel() == 0 or not t.is_cuda:
+                raise ValueError(f"DeviceReplayBuffer: {name} must be a non-empty {dtype} CUDA tensor [B]")
+        if idx.numel() != td_error.numel():
+            raise ValueError(f"DeviceReplayBuffer: idx has {idx.numel()} elements, td_error {td_error.numel()}")
+        idx, td_error = idx.contiguous(), td_error.detach().contiguous()
+        with torch.cuda.device(self.device):
+            N.check(self.lib.tg_replay_prio_update(C.byref(self._native), C.byref(self._prio), idx.numel(), idx.data_ptr(),
+                                                   td_error.data_ptr(), self.alpha, self.priority_eps, N.stream_ptr(self.device)),
+                    "tg_replay_prio_update")
+
+    def rebuild_tree(self):
+        """Every level above the leaves from `priorities` (tg_replay_prio_rebuild): after writing the leaves by hand."""
+        if not self.prioritized:
+            raise RuntimeError("DeviceReplayBuffer: rebuild_tree() needs prioritized=True")
+        with torch.cuda.device(self.device):
+            N.check(self.lib.tg_replay_prio_rebuild(C.byref(self._prio), N.stream_ptr(self.device)), "tg_replay_prio_rebuild")
 
     # ---- checkpointing -----------------------------------------------------------------------------------------------------------
     _TENSORS = ("obs", "act", "next_obs", "rew", "disc", "nstep", "_last_obs", "_slots")
@@ -218,6 +299,9 @@ class DeviceReplayBuffer:
         sd.update(obs_dim=self.obs_dim, act_dim=self.act_dim, num_envs=self.num_envs, capacity_steps=self.capacity_steps,
                   n_step=self._n_step, gamma=self._gamma, seed=self.seed, ordinal=self._ordinal, pushes=self._pushes,
                   started=self._started)
+        if self.prioritized:             # the leaves and the running maximum; the levels above are rebuilt on load
+            sd.update(priorities=self.priorities.clone(), max_priority=self._max_priority.clone(), alpha=self.alpha, beta=self.beta,
+                      priority_eps=self.priority_eps)
         return sd
 
     def load_state_dict(self, sd):
@@ -239,6 +323,12 @@ class DeviceReplayBuffer:
             if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
                 raise ValueError(f"DeviceReplayBuffer: state_dict's {name.lstrip('_')} is {src.dtype} {list(src.shape)}, "
                                  f"expected {dst.dtype} {list(dst.shape)}")
+        if self.prioritized:
+            if "priorities" not in sd or tuple(sd["priorities"].shape) != tuple(self.priorities.shape):
+                raise ValueError("DeviceReplayBuffer: state_dict has no priorities of this shape (was it saved with prioritized=True?)")
+            self.priorities.copy_(sd["priorities"])
+            self._max_priority.copy_(sd["max_priority"])
+            self.rebuild_tree()
         for name in self._TENSORS:
             getattr(self, name).copy_(sd[name.lstrip("_")])
         self.seed, self._ordinal = self._checked_seed(sd["seed"]), int(sd["ordinal"])
