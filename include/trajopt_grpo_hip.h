@@ -1283,6 +1283,75 @@ int  tg_replay_prio_sample(const tg_replay* r, const tg_replay_prio* p, int64_t 
                            int64_t* o_idx, float* o_raw, float* o_weight, void* stream);
 int  tg_replay_prio_rebuild(const tg_replay_prio* p, void* stream);
 
+/* ---- Rollout storage: fixed-length segments of a vector env for on-policy loops (DeviceRolloutStorage, csrc/segment.hip;
+ * additions to ABI 13) ----
+ * A segment is L = steps time rows of n env slots each, float32, [L][n]-major, row = t n + i: one time row is one contiguous [n][.]
+ * block of every array.  The slots sit anywhere in their episodes: an episode may end and restart in the middle of a column.
+ *   d_obs f32 [(L + 1) n][S]  row t: the observation the action of step t was applied to; row L: the one behind the last step
+ *   d_act f32 [L n][A], d_logp f32 [L n], d_val f32 [L n]   what the policy and the critic gave at step t
+ *   d_rew f32 [L n]           the effective reward (below);  d_flags u8 [L n]: bit 0 terminated, bit 1 truncated; done = flags != 0
+ *   d_adv f32 [L n], d_ret f32 [L n]   tg_segment_gae's results;  d_idx i64 [L n]: tg_segment_permute's permutation
+ *   d_step i32 [n]            the time row the next push writes (equal across slots; a push workgroup reads that of its first slot)
+ *   d_shuffles u64 [ceil(L n / TG_SEGMENT_PERMUTE_BLOCK)]   permutations drawn so far, one copy per workgroup of the permutation launch
+ *   d_first_obs f32 [n][S]    the observation step 0 of the segment was applied to: row 0 of d_obs as it was at the push of step 0.
+ *                             (The segment's own last push overwrites row 0 with the next segment's; the gather reads step 0 here.)
+ *   gamma = (float)gamma, gamma_lam = (float)(gamma * lam) with the product formed in double.
+ * Everything that changes from call to call lives in these device arrays: a vector-env step and a push, or a shuffle, can be
+ * captured into one hipGraph, and every replay stores the next row / draws the next permutation.
+ *
+ * tg_segment_push, one launch; with t = d_step, per slot i, row = t n + i:
+ *   when t = 0 first d_first_obs[i] = d_obs row i; then
+ *   d_obs row (t + 1) n + i = d_obs_in[i] (and, when t = L - 1, row i as well: the next segment's row 0), d_act = d_actions[i],
+ *   d_logp = d_logp_in[i], d_val = d_value[i], d_flags = terminated[i] | truncated[i] << 1,
+ *   d_rew = truncated[i] && !terminated[i] ? fadd(d_reward[i], fmul(gamma, d_final_value[i])) : d_reward[i]  (two float32 roundings;
+ *   a select: d_final_value[i] is read nowhere else and may be anything there), then d_step[i] = (t + 1) mod L.
+ * tg_segment_gae, one launch; per slot i, t = L - 1 .. 0, every operation float32 and rounded on its own, with adv[L] = 0:
+ *   live = flags[t] ? 0 : 1,  nxt = t == L - 1 ? d_last_value[i] : val[t + 1],
+ *   delta = (rew[t] + (gamma nxt) live) - val[t],  adv[t] = delta + ((gamma_lam live) adv[t + 1]),  ret[t] = adv[t] + val[t].
+ *   A terminated step bootstraps from nothing, a truncated one from the critic's value of the state the clock cut off (inside rew),
+ *   and neither passes anything on from the episode behind it.  The operands of the next TG_SEGMENT_GAE_PREFETCH steps are in
+ *   registers ahead of the recurrence.
+ * tg_segment_permute, one launch: d_idx = a bijection of [0, L n), a new one at every call.  With b even, >= 2, the smallest with
+ *   2^b >= L n, h = b / 2 and x = (l << h) | r:  four rounds (l, r) <- (r, l ^ (w & (2^h - 1))), w = word 0 of the Philox4x32-10 draw
+ *   with key `seed` and counter (r, round, d_shuffles lo, d_shuffles hi); d_idx[i] = the first of P(i), P(P(i)), .. below L n.
+ *   Then d_shuffles += 1.
+ * tg_segment_gather, one launch: o_*[b] = row d_idx[first + b] of d_obs [B][S] (a row below n: of d_first_obs), d_act [B][A], d_logp,
+ *   d_adv, d_ret, d_val, b in [0, count).  An index outside [0, L n) is not read: its outputs are NaN.
+ * Refused before any launch: a null pointer, n <= 0, steps <= 0, (steps + 1) n >= 2^31, gamma or gamma_lam outside (0, 1], d_obs,
+ *   d_act, d_first_obs, d_actions, d_obs_in, o_obs or o_act not 16-byte aligned, [first, first + count) not inside [0, L n) or empty (TG_ERR_ARG);
+ *   obs_dim outside [1, 32] or act_dim outside [1, 8] (TG_ERR_UNSUPPORTED). */
+#define TG_SEGMENT_SLOTS 64            /* slots of a push / GAE workgroup, rows of a gather workgroup: one wave */
+#define TG_SEGMENT_GAE_PREFETCH 8      /* time steps whose operands tg_segment_gae holds in registers ahead of the recurrence */
+#define TG_SEGMENT_PERMUTE_BLOCK 256   /* rows of a permutation workgroup: one d_shuffles entry each */
+typedef struct tg_segment {
+    float*    d_obs;
+    float*    d_act;
+    float*    d_logp;
+    float*    d_val;
+    float*    d_rew;
+    uint8_t*  d_flags;
+    float*    d_adv;
+    float*    d_ret;
+    int64_t*  d_idx;
+    int32_t*  d_step;
+    uint64_t* d_shuffles;
+    float*    d_first_obs;
+    int64_t   n;
+    uint64_t  seed;
+    int32_t   steps;
+    int32_t   obs_dim;
+    int32_t   act_dim;
+    float     gamma;
+    float     gamma_lam;
+} tg_segment;
+int  tg_segment_push(const tg_segment* s, const float* d_actions, const float* d_logp_in, const float* d_value, const float* d_obs_in,
+                     const float* d_reward, const uint8_t* d_terminated, const uint8_t* d_truncated, const float* d_final_value,
+                     void* stream);
+int  tg_segment_gae(const tg_segment* s, const float* d_last_value, void* stream);
+int  tg_segment_permute(const tg_segment* s, void* stream);
+int  tg_segment_gather(const tg_segment* s, int64_t first, int64_t count, float* o_obs, float* o_act, float* o_logp, float* o_adv,
+                       float* o_ret, float* o_val, void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

@@ -81,6 +81,56 @@ def train(seed, args, dev):
     return curve
 
 
+def train_storage(seed, args, dev):
+    """train() with tg.DeviceRolloutStorage in the place of the torch buffers, the GAE loop, randperm and the index_selects: one launch
+    per stored step, one for the returns, one per shuffle and one per minibatch.  The nets, the losses and the optimizer are the same."""
+    torch.manual_seed(seed)
+    venv = tg.DeviceVecEnv(tg.CartPole(max_steps=args.max_steps), args.envs, seed=seed, device=dev)
+    n, S, A, L = venv.num_envs, venv.S, venv.A, args.rollout
+    actor, critic = mlp(S, A).to(dev), mlp(S, 1).to(dev)
+    log_std = nn.Parameter(torch.full((A,), -0.5, device=dev))
+    params = list(actor.parameters()) + list(critic.parameters()) + [log_std]
+    opt = torch.optim.Adam(params, lr=args.lr)
+    st = tg.DeviceRolloutStorage.for_env(venv, L, gamma=args.gamma, lam=args.lam, seed=seed)
+    st.start(venv.reset(seed=seed)[0])
+    curve = []
+    for it in range(args.iters):
+        ret_sum = torch.zeros((), device=dev)
+        ret_cnt = torch.zeros((), device=dev)
+        with torch.no_grad():
+            for t in range(L):
+                dist = torch.distributions.Normal(actor(st.obs[t]), log_std.exp())
+                act = dist.sample()
+                value = critic(st.obs[t]).squeeze(-1)
+                obs, rew, terminated, truncated, info = venv.step(act)
+                # (the rows of final_obs are defined where the slot ended; add() reads the value only where the clock ended it)
+                st.add(act, dist.log_prob(act).sum(-1), value, obs, rew, terminated, truncated, critic(info["final_obs"]).squeeze(-1))
+                done = terminated | truncated
+                ret_sum += torch.where(done, info["episode_return"], 0.0).sum()
+                ret_cnt += done.sum()
+            st.compute_returns(critic(st.obs[L]).squeeze(-1))
+        for _ in range(args.epochs):
+            st.shuffle()
+            for k in range(args.minibatches):
+                b_obs, b_act, b_logp, a, b_ret, _ = st.minibatch(k, args.minibatches)
+                dist = torch.distributions.Normal(actor(b_obs), log_std.exp())
+                ratio = (dist.log_prob(b_act).sum(-1) - b_logp).exp()
+                a = (a - a.mean()) / (a.std() + 1e-8)
+                pi_loss = -torch.min(ratio * a, ratio.clamp(1 - args.clip, 1 + args.clip) * a).mean()
+                v_loss = 0.5 * (critic(b_obs).squeeze(-1) - b_ret).pow(2).mean()
+                opt.zero_grad(set_to_none=True)
+                (pi_loss + args.vf_coef * v_loss).backward()
+                nn.utils.clip_grad_norm_(params, 0.5)
+                opt.step()
+        episodes = int(ret_cnt.item())
+        mean_ret = float(ret_sum.item()) / max(episodes, 1)
+        curve.append(((it + 1) * L * n, episodes, mean_ret))
+        if it % args.log_every == 0 or it == args.iters - 1:
+            print(f"seed {seed} iter {it + 1:3d} env-steps {curve[-1][0]:8d} episodes {episodes:5d} mean episode return {mean_ret:9.3f}", flush=True)
+    venv.close()
+    return curve
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--seeds", type=int, nargs="+", default=[0])
@@ -97,13 +147,14 @@ def main():
     ap.add_argument("--vf-coef", type=float, default=0.5)
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--out", default=None, help="write the curves here: one line per seed and iteration")
+    ap.add_argument("--storage", action="store_true", help="the same PPO on tg.DeviceRolloutStorage: storing, GAE and minibatches on the device")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("vec_env_ppo.py needs an MI355X: DeviceVecEnv has no CPU fallback")
     dev = torch.device("cuda", 0)
     lines = ["# seed env_steps episodes mean_episode_return"]
     for seed in args.seeds:
-        for steps, episodes, mean_ret in train(seed, args, dev):
+        for steps, episodes, mean_ret in (train_storage if args.storage else train)(seed, args, dev):
             lines.append(f"{seed} {steps} {episodes} {mean_ret:.4f}")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

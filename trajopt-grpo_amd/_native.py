@@ -163,6 +163,14 @@ class ReplayPrio(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class Segment(C.Structure):
+    """tg_segment (include/trajopt_grpo_hip.h): the storage, results and counters of a rollout segment and what is fixed per object."""
+    _fields_ = [("d_obs", C.c_void_p), ("d_act", C.c_void_p), ("d_logp", C.c_void_p), ("d_val", C.c_void_p), ("d_rew", C.c_void_p),
+                ("d_flags", C.c_void_p), ("d_adv", C.c_void_p), ("d_ret", C.c_void_p), ("d_idx", C.c_void_p), ("d_step", C.c_void_p),
+                ("d_shuffles", C.c_void_p), ("d_first_obs", C.c_void_p), ("n", C.c_int64), ("seed", C.c_uint64), ("steps", C.c_int32), ("obs_dim", C.c_int32),
+                ("act_dim", C.c_int32), ("gamma", C.c_float), ("gamma_lam", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/trajopt_grpo_hip.h declares
 _P, _I32, _I64, _U64, _F, _VP = C.POINTER, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -351,6 +359,10 @@ SIGNATURES = {
     "tg_replay_prio_update": (C.c_int, [_P(Replay), _P(ReplayPrio), _I64, _VP, _VP, _F, _F, _VP]),
     "tg_replay_prio_sample": (C.c_int, [_P(Replay), _P(ReplayPrio), _I64, _VP, _U64, _U64, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tg_replay_prio_rebuild": (C.c_int, [_P(ReplayPrio), _VP]),
+    "tg_segment_push": (C.c_int, [_P(Segment), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tg_segment_gae": (C.c_int, [_P(Segment), _VP, _VP]),
+    "tg_segment_permute": (C.c_int, [_P(Segment), _VP]),
+    "tg_segment_gather": (C.c_int, [_P(Segment), _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),
