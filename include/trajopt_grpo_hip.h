@@ -1352,6 +1352,67 @@ int  tg_segment_permute(const tg_segment* s, void* stream);
 int  tg_segment_gather(const tg_segment* s, int64_t first, int64_t count, float* o_obs, float* o_act, float* o_logp, float* o_adv,
                        float* o_ret, float* o_val, void* stream);
 
+/* ---- Policy step: actor forward, sampling head, log-density and the critic's value in one launch (DeviceActor, csrc/policy_step.hip;
+ * additions to ABI 13) ----
+ * A net is Linear(S <= 32, H) act [Linear(H, H) act]{0..4} Linear(H, O), H in {64, 128, 256}, act ReLU or Tanh, float32.  tg_policy_net
+ * holds, per Linear layer, the device pointers of torch's own row-major weight [out][in] and bias [out] and the two widths: the
+ * kernel reads the parameters where torch keeps them, at every call; no derived layout exists.  The weights of the H x H layers must
+ * be 16-byte aligned.  The actor and the critic of one launch may differ in width, depth and activation; they read the same rows.
+ *
+ * tg_policy_step, one launch: per row i of d_obs [n][S] (unpadded), out = actor(obs_i), and with
+ *   eps_k = the rollout kernels' float32 Box-Muller of Philox4x32-10(key = seed, counter = (env_offset + i, d_calls[i], TG_POLICY_STEP_STREAM)),
+ *   or 0 for every k with `deterministic`:
+ *   TG_POLICY_HEAD_GAUSSIAN (O = A): mu = out, ls = d_log_std [A];  a = mu + exp(ls) eps;  mean = mu
+ *   TG_POLICY_HEAD_SQUASHED (O = 2 A): mu = out[0..A), ls = clamp(out[A..2A), log_std_lo, log_std_hi);  u = mu + exp(ls) eps,
+ *                            a = tanh(u);  mean = tanh(mu)
+ *   logp = sum_k(-0.5 eps_k^2 - ls_k - 0.5 log 2 pi), the squashed head's minus sum_k log(1 - a_k^2 + 1e-6)
+ *   d_action [n][A] = a, d_mean [n][A] = mean, d_logp [n] = logp, d_value [n] = critic(obs_i) (critic may be NULL: d_value is then
+ *   not written), and d_calls[i] += 1 unless `deterministic`.
+ *   The draw of slot i at its k-th call depends on neither n, the grid nor how the slots are sharded over objects.  Nothing that changes
+ *   from call to call is passed by value: a captured launch draws the next numbers at every replay.
+ * tg_policy_values, one launch: d_value [m] = critic(d_x [m][S]) on any rows.
+ * grid_limit: 0, or a cap on the workgroups per net (the default is two per CU).
+ * Counter words of the Philox draws, for reference: sampling in a rollout (idx = env, sub = t, stream = the rollout's stream id); a
+ *   reset (sub = 0xFFFFFFFF, stream = the stream id / the slot's episode ordinal); parameter draws (sub counted down from 0xFFFFFFFE);
+ *   replay sampling (idx = b, sub / stream = the ordinal's halves); the policy step (idx = env, sub = the slot's call count, stream =
+ *   TG_POLICY_STEP_STREAM).
+ * Refused (TG_ERR_ARG) before any launch: a NULL where a tensor is needed; a shape outside the set above; head outputs that do not match
+ *   the head and act_dim (1..4); a critic with another input width or more than one output; a misaligned weight or bias pointer; n or
+ *   m outside [1, 2^31). */
+#define TG_POLICY_MAX_LAYERS 6                 /* Linear layers of a net: up to 5 hidden layers and the head */
+#define TG_POLICY_STEP_STREAM 0x70737465u      /* "pste" */
+#define TG_POLICY_HEAD_GAUSSIAN 0
+#define TG_POLICY_HEAD_SQUASHED 1
+typedef struct tg_policy_net {
+    const float* w[TG_POLICY_MAX_LAYERS];
+    const float* b[TG_POLICY_MAX_LAYERS];
+    int32_t      in_dim[TG_POLICY_MAX_LAYERS];
+    int32_t      out_dim[TG_POLICY_MAX_LAYERS];
+    int32_t      n_layers;
+    int32_t      activation;
+} tg_policy_net;
+typedef struct tg_policy_step_args {
+    const float* d_obs;
+    const float* d_log_std;
+    uint32_t*    d_calls;
+    float*       d_action;
+    float*       d_logp;
+    float*       d_mean;
+    float*       d_value;
+    int64_t      n;
+    int64_t      env_offset;
+    uint64_t     seed;
+    int32_t      head;
+    int32_t      act_dim;
+    int32_t      deterministic;
+    int32_t      grid_limit;
+    float        log_std_lo;
+    float        log_std_hi;
+} tg_policy_step_args;
+int  tg_policy_step_limits(int32_t* max_obs_dim, int32_t* max_hidden_layers, int32_t* max_act_dim);
+int  tg_policy_step(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_step_args* s, void* stream);
+int  tg_policy_values(const tg_policy_net* critic, const float* d_x, int64_t m, float* d_value, int32_t grid_limit, void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

@@ -32,6 +32,9 @@ def train(seed, args, dev):
     buf = {"obs": torch.empty(L, n, S, device=dev), "act": torch.empty(L, n, A, device=dev), "logp": torch.empty(L, n, device=dev),
            "val": torch.empty(L, n, device=dev), "rew": torch.empty(L, n, device=dev), "done": torch.empty(L, n, device=dev)}
     obs, _ = venv.reset(seed=seed)
+    # --device-actor: sampling, log-density and both value calls of the collection are tg.DeviceActor launches on the same nets
+    da = tg.DeviceActor.for_env(venv, actor, critic, log_std=log_std) if args.device_actor else None
+    value_of = da.values if da else (lambda x: critic(x).squeeze(-1))
     curve = []
     for it in range(args.iters):
         ret_sum = torch.zeros((), device=dev)
@@ -39,19 +42,23 @@ def train(seed, args, dev):
         with torch.no_grad():
             for t in range(L):
                 buf["obs"][t].copy_(obs)                              # (obs is the env's own buffer: the next step overwrites it)
-                dist = torch.distributions.Normal(actor(buf["obs"][t]), log_std.exp())
-                act = dist.sample()
-                buf["act"][t], buf["logp"][t], buf["val"][t] = act, dist.log_prob(act).sum(-1), critic(buf["obs"][t]).squeeze(-1)
+                if da:
+                    act, buf["logp"][t], buf["val"][t] = da.act(buf["obs"][t])
+                    buf["act"][t] = act
+                else:
+                    dist = torch.distributions.Normal(actor(buf["obs"][t]), log_std.exp())
+                    act = dist.sample()
+                    buf["act"][t], buf["logp"][t], buf["val"][t] = act, dist.log_prob(act).sum(-1), critic(buf["obs"][t]).squeeze(-1)
                 obs, rew, terminated, truncated, info = venv.step(act)
                 # the clock is no part of the task: where it ended the episode, the value of the state it cut off stands in for the rest
-                boot = torch.where(truncated, critic(info["final_obs"]).squeeze(-1), 0.0)   # (rows are defined where the slot ended)
+                boot = torch.where(truncated, value_of(info["final_obs"]), 0.0)   # (rows are defined where the slot ended)
                 buf["rew"][t] = rew + args.gamma * boot
                 done = terminated | truncated
                 buf["done"][t] = done
                 ret_sum += torch.where(done, info["episode_return"], 0.0).sum()
                 ret_cnt += done.sum()
             adv = torch.empty(L, n, device=dev)
-            last, nxt = torch.zeros(n, device=dev), critic(obs).squeeze(-1)
+            last, nxt = torch.zeros(n, device=dev), value_of(obs)
             for t in reversed(range(L)):
                 live = 1.0 - buf["done"][t]
                 delta = buf["rew"][t] + args.gamma * nxt * live - buf["val"][t]
@@ -93,22 +100,28 @@ def train_storage(seed, args, dev):
     opt = torch.optim.Adam(params, lr=args.lr)
     st = tg.DeviceRolloutStorage.for_env(venv, L, gamma=args.gamma, lam=args.lam, seed=seed)
     st.start(venv.reset(seed=seed)[0])
+    # --device-actor: one collection step is act, venv.step, add -- three launches (and one for the value of final_obs)
+    da = tg.DeviceActor.for_env(venv, actor, critic, log_std=log_std) if args.device_actor else None
+    value_of = da.values if da else (lambda x: critic(x).squeeze(-1))
     curve = []
     for it in range(args.iters):
         ret_sum = torch.zeros((), device=dev)
         ret_cnt = torch.zeros((), device=dev)
         with torch.no_grad():
             for t in range(L):
-                dist = torch.distributions.Normal(actor(st.obs[t]), log_std.exp())
-                act = dist.sample()
-                value = critic(st.obs[t]).squeeze(-1)
+                if da:
+                    act, logp, value = da.act(st.obs[t])
+                else:
+                    dist = torch.distributions.Normal(actor(st.obs[t]), log_std.exp())
+                    act = dist.sample()
+                    logp, value = dist.log_prob(act).sum(-1), critic(st.obs[t]).squeeze(-1)
                 obs, rew, terminated, truncated, info = venv.step(act)
                 # (the rows of final_obs are defined where the slot ended; add() reads the value only where the clock ended it)
-                st.add(act, dist.log_prob(act).sum(-1), value, obs, rew, terminated, truncated, critic(info["final_obs"]).squeeze(-1))
+                st.add(act, logp, value, obs, rew, terminated, truncated, value_of(info["final_obs"]))
                 done = terminated | truncated
                 ret_sum += torch.where(done, info["episode_return"], 0.0).sum()
                 ret_cnt += done.sum()
-            st.compute_returns(critic(st.obs[L]).squeeze(-1))
+            st.compute_returns(value_of(st.obs[L]))
         for _ in range(args.epochs):
             st.shuffle()
             for k in range(args.minibatches):
@@ -148,6 +161,7 @@ def main():
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--out", default=None, help="write the curves here: one line per seed and iteration")
     ap.add_argument("--storage", action="store_true", help="the same PPO on tg.DeviceRolloutStorage: storing, GAE and minibatches on the device")
+    ap.add_argument("--device-actor", action="store_true", help="collect with tg.DeviceActor: sampling, log-density and values in one launch")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("vec_env_ppo.py needs an MI355X: DeviceVecEnv has no CPU fallback")

@@ -66,13 +66,17 @@ def train(seed, args, dev):
     log_alpha = nn.Parameter(torch.zeros((), device=dev))
     opt_pi, opt_q = torch.optim.Adam(actor.parameters(), lr=args.lr), torch.optim.Adam(critic.parameters(), lr=args.lr)
     opt_alpha = torch.optim.Adam([log_alpha], lr=args.lr)
+    # --device-actor: the two no-grad actor calls (collection, and a' of the target) are tg.DeviceActor launches on actor.net; the
+    # actor(b_obs) call that needs gradients stays torch
+    da = tg.DeviceActor.for_env(venv, actor.net, head="squashed") if args.device_actor else None
+    da_batch = tg.DeviceActor(actor.net, num_envs=args.batch, head="squashed", seed=seed + 1, device=dev) if args.device_actor else None
     obs, _ = venv.reset(seed=seed)
     buf.start(obs)
     ret_sum, ret_cnt = torch.zeros((), device=dev), torch.zeros((), device=dev)
     curve = []
     for it in range(args.iters):
         with torch.no_grad():
-            act = torch.rand(args.envs, A, device=dev) * 2 - 1 if it < args.random_iters else actor(obs)[0]
+            act = torch.rand(args.envs, A, device=dev) * 2 - 1 if it < args.random_iters else (da.act(obs) if da else actor(obs))[0]
         obs, rew, terminated, truncated, info = venv.step(act)
         buf.add(act, obs, rew, terminated, truncated, info)              # the env's own buffers as they are: one launch, no clone
         done = terminated | truncated
@@ -83,7 +87,7 @@ def train(seed, args, dev):
                 b_obs, b_act, b_rew, b_next, b_disc, b_idx, *b_w = buf.sample(args.batch)
                 with torch.no_grad():
                     alpha = log_alpha.exp()
-                    a2, logp2 = actor(b_next)
+                    a2, logp2 = da_batch.act(b_next)[:2] if da_batch else actor(b_next)
                     y = b_rew + b_disc * (torch.min(*target(b_next, a2)) - alpha * logp2)
                 q1, q2 = critic(b_obs, b_act)
                 if args.per:                                             # importance-weighted, and the rows' new priorities
@@ -141,6 +145,7 @@ def main():
     ap.add_argument("--per-alpha", type=float, default=0.6)
     ap.add_argument("--per-beta", type=float, default=0.4)
     ap.add_argument("--out", default=None, help="write the curves here: one line per seed and evaluation point")
+    ap.add_argument("--device-actor", action="store_true", help="the no-grad actor calls (collection, target) on tg.DeviceActor")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("vec_env_sac.py needs an MI355X: DeviceVecEnv and DeviceReplayBuffer have no CPU fallback")

@@ -18,6 +18,7 @@ from .evaluation import Evaluator, EvalResult
 from .vector import DeviceVecEnv
 from .replay import DeviceReplayBuffer
 from .storage import DeviceRolloutStorage
+from .policy_step import DeviceActor
 from .algorithms import Algorithm, GRPO, PPO
 from .pipelines import (Pipeline, create_cartpole_pipeline_grpo, create_cartpole_pipeline_ppo,
                         create_quadpole_pipeline_ppo, create_quadpole2d_pipeline_ppo)
@@ -27,6 +28,6 @@ __all__ = [
     "Box", "Env", "CartPole", "Pendulum", "QuadPole", "QuadPole2D", "QuadPoleSwarm", "Quadrotor", "QuadrotorSwarm",
     "NeuralNetwork", "ActorCritic", "GaussianActor_NeuralNetwork", "GaussianActorCritic_NeuralNetwork",
     "DeviceRollout", "DeviceTrajectory", "RolloutManager", "RolloutWorker", "Buffer", "Rollout_Buffer",
-    "Algorithm", "GRPO", "PPO", "Evaluator", "EvalResult", "DeviceVecEnv", "DeviceReplayBuffer", "DeviceRolloutStorage", "Pipeline", "create_cartpole_pipeline_grpo", "create_cartpole_pipeline_ppo",
+    "Algorithm", "GRPO", "PPO", "Evaluator", "EvalResult", "DeviceVecEnv", "DeviceReplayBuffer", "DeviceRolloutStorage", "DeviceActor", "Pipeline", "create_cartpole_pipeline_grpo", "create_cartpole_pipeline_ppo",
     "create_quadpole_pipeline_ppo", "create_quadpole2d_pipeline_ppo", "distributed", "hip_ops",
 ]

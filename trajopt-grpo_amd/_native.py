@@ -171,6 +171,26 @@ class Segment(C.Structure):
                 ("act_dim", C.c_int32), ("gamma", C.c_float), ("gamma_lam", C.c_float)]
 
 
+TG_POLICY_MAX_LAYERS = 6
+TG_POLICY_STEP_STREAM = 0x70737465
+TG_POLICY_HEAD_GAUSSIAN, TG_POLICY_HEAD_SQUASHED = 0, 1
+
+
+class PolicyNet(C.Structure):
+    """tg_policy_net (include/trajopt_grpo_hip.h): per Linear layer, torch's own weight and bias pointers and the two widths."""
+    _fields_ = [("w", C.c_void_p * TG_POLICY_MAX_LAYERS), ("b", C.c_void_p * TG_POLICY_MAX_LAYERS),
+                ("in_dim", C.c_int32 * TG_POLICY_MAX_LAYERS), ("out_dim", C.c_int32 * TG_POLICY_MAX_LAYERS), ("n_layers", C.c_int32),
+                ("activation", C.c_int32)]
+
+
+class PolicyStepArgs(C.Structure):
+    """tg_policy_step_args (include/trajopt_grpo_hip.h)."""
+    _fields_ = [("d_obs", C.c_void_p), ("d_log_std", C.c_void_p), ("d_calls", C.c_void_p), ("d_action", C.c_void_p),
+                ("d_logp", C.c_void_p), ("d_mean", C.c_void_p), ("d_value", C.c_void_p), ("n", C.c_int64), ("env_offset", C.c_int64),
+                ("seed", C.c_uint64), ("head", C.c_int32), ("act_dim", C.c_int32), ("deterministic", C.c_int32),
+                ("grid_limit", C.c_int32), ("log_std_lo", C.c_float), ("log_std_hi", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/trajopt_grpo_hip.h declares
 _P, _I32, _I64, _U64, _F, _VP = C.POINTER, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -363,6 +383,9 @@ SIGNATURES = {
     "tg_segment_gae": (C.c_int, [_P(Segment), _VP, _VP]),
     "tg_segment_permute": (C.c_int, [_P(Segment), _VP]),
     "tg_segment_gather": (C.c_int, [_P(Segment), _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tg_policy_step_limits": (C.c_int, [_P(_I32), _P(_I32), _P(_I32)]),
+    "tg_policy_step": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyStepArgs), _VP]),
+    "tg_policy_values": (C.c_int, [_P(PolicyNet), _VP, _I64, _VP, _I32, _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),

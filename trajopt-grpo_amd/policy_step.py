@@ -1,0 +1,245 @@
+"""DeviceActor: the policy step of an RL loop on DeviceVecEnv as ONE kernel launch.
+
+`act(obs)` runs the actor net, draws the action, computes its log-density and -- with a critic -- the value of the same rows in one
+launch (tg_policy_step, csrc/policy_step.hip); `values(x)` is the critic alone on any rows (tg_policy_values), for
+`V(info["final_obs"])` and the last value of a segment.  One collection step is then `act`, `venv.step`, `add`: three launches, all
+of them capturable into one hipGraph.
+
+The nets stay plain `torch.nn` modules that the caller trains with `torch.optim`: the kernel reads `nn.Linear.weight` / `.bias` where
+torch keeps them, and the pointer tables are filled from `param.data_ptr()` at every call.  An in-place optimizer step or a
+`param.data.copy_()` is therefore seen by the next call, outside a captured graph and inside one.  A parameter REBOUND to new storage
+(`param.data = other`, `load_state_dict(assign=True)`) is seen by the next eager call but not by a graph captured before it.
+
+Not built: gradients through act() (the learner's re-evaluation stays torch autograd), bf16, more than 4 actions, LayerNorm or mixed
+activations, a trunk shared by actor and critic.  There is no silent torch fallback: a net outside the kernel's set raises
+ValueError with supports()'s reason, and the caller's own torch code is the fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import types
+
+import torch
+
+from . import _native as N
+from . import mlp as M
+
+MAX_OBS_DIM, MAX_HIDDEN_LAYERS, MAX_ACT_DIM = 32, 5, 4          # tg_policy_step_limits
+WIDTHS = (64, 128, 256)
+HEADS = {"gaussian": N.TG_POLICY_HEAD_GAUSSIAN, "squashed": N.TG_POLICY_HEAD_SQUASHED}
+_ACT = {"ReLU": N.TG_ACT_RELU, "Tanh": N.TG_ACT_TANH}
+
+
+def _modules(net):
+    if isinstance(net, torch.nn.Sequential):
+        return list(net)
+    inner = getattr(net, "network", None)
+    return list(inner) if inner is not None else None
+
+
+def _shape(net, head):
+    """-> ((S, H, hidden layers, O, activation), None) of a net the kernel takes under `head` ("gaussian", "squashed" or "value"),
+    or (None, the reason)."""
+    mods = _modules(net)
+    if mods is None:
+        return None, f"{type(net).__name__} is neither an nn.Sequential nor a module with a `.network` Sequential"
+    if len(mods) < 3 or len(mods) % 2 == 0 or any(not isinstance(m, torch.nn.Linear) for m in mods[0::2]):
+        return None, "the net is not Linear [activation Linear]+"
+    act = M.hidden_activation(types.SimpleNamespace(network=mods))
+    if act is None:
+        kinds = sorted({type(m).__name__ for m in mods[1::2]})
+        return None, (f"mixed hidden activations {kinds}: one of ReLU / Tanh after every hidden layer" if len(kinds) > 1 else
+                      f"hidden activation {kinds[0]}: only ReLU and Tanh are built")
+    lin = mods[0::2]
+    S, H, nh, O = lin[0].in_features, lin[0].out_features, len(lin) - 1, lin[-1].out_features
+    if any(l.out_features != H for l in lin[:-1]) or any(l.in_features != H for l in lin[1:]):
+        return None, "the hidden layers differ in width"
+    if H not in WIDTHS:
+        return None, f"hidden width {H}: only {WIDTHS} are built"
+    if nh > MAX_HIDDEN_LAYERS:
+        return None, f"{nh} hidden layers: at most {MAX_HIDDEN_LAYERS}"
+    if not 1 <= S <= MAX_OBS_DIM:
+        return None, f"input width {S} outside [1, {MAX_OBS_DIM}]"
+    if any(l.bias is None for l in lin):
+        return None, "a Linear layer without a bias"
+    if head == "gaussian" and not 1 <= O <= MAX_ACT_DIM:
+        return None, f"{O} outputs under the gaussian head: 1..{MAX_ACT_DIM} actions"
+    if head == "squashed" and (O % 2 or not 2 <= O <= 2 * MAX_ACT_DIM):
+        return None, f"{O} outputs under the squashed head: (mean, log-std) pairs of 1..{MAX_ACT_DIM} actions, so an even count <= {2 * MAX_ACT_DIM}"
+    if head == "value" and O != 1:
+        return None, f"{O} outputs of a critic: 1"
+    if head not in ("gaussian", "squashed", "value"):
+        return None, f"unknown head {head!r}"
+    return (S, H, nh, O, act), None
+
+
+class DeviceActor:
+    """The policy step for `num_envs` slots on one GPU.
+
+    actor_net, critic_net   Linear(S <= 32, H) act [Linear(H, H) act]{0..4} Linear(H, O), H in {64, 128, 256}, act ReLU or Tanh, float32:
+                            an nn.Sequential or a module with such a `.network`.  The two may differ in width, depth and activation.
+    head        "gaussian": O = A, a = mu + exp(log_std) eps with the state-independent `log_std` [A] (a device tensor or Parameter,
+                read at every call); "squashed": O = 2 A, (mu, ls) = split(out), ls clamped to `log_std_bounds`, a = tanh(mu + exp(ls) eps)
+                and the squash correction - sum log(1 - a^2 + 1e-6) in the log-density.
+    seed, env_offset        eps of slot i at its k-th sampled call is the Box-Muller of Philox(seed, env_offset + i, k, the policy step's
+                stream constant): objects with consecutive offsets are, bit for bit, the slots of one larger object.
+
+    `action` [n][A], `logp` [n], `value` [n] and `mean` [n][A] are this object's own buffers, the same at every call and overwritten by
+    the next act() (DeviceVecEnv's rule): clone what you keep.  `mean` is the deterministic action of the last act(): mu, or tanh(mu)
+    under the squashed head.  values() has a buffer of its own per row count."""
+
+    def __init__(self, actor_net, critic_net=None, *, num_envs: int, log_std=None, head: str = "gaussian",
+                 log_std_bounds=(-5.0, 2.0), seed: int = 0, env_offset: int = 0, device=None):
+        if head not in HEADS:
+            raise ValueError(f"DeviceActor: head {head!r} is not one of {sorted(HEADS)}")
+        shape, why = _shape(actor_net, head)
+        if shape is None:
+            raise ValueError(f"DeviceActor: the actor is not supported: {why}")
+        self.S, self.H, self.hidden_layers, O, self.activation = shape
+        self.A = O // 2 if head == "squashed" else O
+        self.head, self.actor_net, self.critic_net = head, actor_net, critic_net
+        if critic_net is not None:
+            cshape, why = _shape(critic_net, "value")
+            if cshape is None:
+                raise ValueError(f"DeviceActor: the critic is not supported: {why}")
+            if cshape[0] != self.S:
+                raise ValueError(f"DeviceActor: the critic reads {cshape[0]} inputs, the actor {self.S}")
+        if int(num_envs) <= 0 or int(env_offset) < 0:
+            raise ValueError(f"DeviceActor: num_envs={num_envs} must be positive and env_offset={env_offset} non-negative")
+        self.num_envs, self.env_offset = int(num_envs), int(env_offset)
+        self.seed = self._checked_seed(seed)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", 0)
+        if self.device.type != "cuda":
+            raise N.NativeLibraryError("DeviceActor needs an MI355X (cuda) device; there is no CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        lo, hi = (float(v) for v in log_std_bounds)
+        if not lo <= hi:
+            raise ValueError(f"DeviceActor: log_std_bounds {log_std_bounds} are empty")
+        self.log_std_bounds = (lo, hi)
+        if head == "gaussian":
+            if not isinstance(log_std, torch.Tensor):
+                raise ValueError("DeviceActor: the gaussian head needs `log_std`, a float32 device tensor [A]")
+            if tuple(log_std.shape) != (self.A,):
+                raise ValueError(f"DeviceActor: log_std must be [{self.A}], got {list(log_std.shape)}")
+        elif log_std is not None:
+            raise ValueError("DeviceActor: the squashed head takes its log-std from the net; `log_std` must be None")
+        self.log_std = log_std
+        self.lib = N.load()
+        n, A, dev, f32 = self.num_envs, self.A, self.device, torch.float32
+        self.action = torch.zeros(n, A, dtype=f32, device=dev)
+        self.mean = torch.zeros(n, A, dtype=f32, device=dev)
+        self.logp = torch.zeros(n, dtype=f32, device=dev)
+        self.value = torch.zeros(n, dtype=f32, device=dev) if critic_net is not None else None
+        self._calls = torch.zeros(n, dtype=torch.int32, device=dev)            # (the bits of a u32)
+        self._values_out = {}
+        self._grid_limit = 0             # 0: two workgroups per CU; a test sets it to force further trips of a workgroup's row loop
+        s = N.PolicyStepArgs()
+        s.d_calls, s.d_action, s.d_logp, s.d_mean = (t.data_ptr() for t in (self._calls, self.action, self.logp, self.mean))
+        s.d_value = N.ptr(self.value)
+        s.n, s.env_offset, s.seed, s.head, s.act_dim = n, self.env_offset, self.seed, HEADS[head], A
+        s.log_std_lo, s.log_std_hi = lo, hi
+        self._native = s
+
+    @classmethod
+    def for_env(cls, venv, actor_net, critic_net=None, log_std=None, head: str = "gaussian", log_std_bounds=(-5.0, 2.0), seed=None):
+        """The actor that fits a DeviceVecEnv: its slot count, widths, device and env_offset, and (unless given) its seed."""
+        self = cls(actor_net, critic_net, num_envs=venv.num_envs, log_std=log_std, head=head, log_std_bounds=log_std_bounds,
+                   seed=venv.seed if seed is None else seed, env_offset=venv.env_offset, device=venv.device)
+        if self.S != venv.S or self.A != venv.A:
+            raise ValueError(f"DeviceActor: the actor maps {self.S} inputs to {self.A} actions under the {head} head, the env has "
+                             f"{venv.S} observations and {venv.A} actions")
+        return self
+
+    @staticmethod
+    def supports(net, head: str = "gaussian"):
+        """None if the kernel takes `net` under `head` ("gaussian", "squashed", or "value" for a critic), else the reason as a string."""
+        return _shape(net, head)[1]
+
+    @staticmethod
+    def _checked_seed(seed) -> int:
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"DeviceActor: seed {seed} is not an unsigned 64-bit integer")
+        return seed
+
+    # ---- the tables: filled from the parameters' CURRENT storage at every call -----------------------------------------------------
+    def _table(self, net, name):
+        lin = _modules(net)[0::2]
+        t = N.PolicyNet()
+        t.n_layers = len(lin)
+        t.activation = _ACT[M.hidden_activation(types.SimpleNamespace(network=_modules(net)))]
+        for l, m in enumerate(lin):
+            for p, what in ((m.weight, "weight"), (m.bias, "bias")):
+                if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
+                    raise ValueError(f"DeviceActor: {name} layer {l} {what} must be a contiguous float32 tensor on {self.device}, got "
+                                     f"{p.dtype} on {p.device}{'' if p.is_contiguous() else ', not contiguous'}")
+            if 0 < l < len(lin) - 1 and m.weight.data_ptr() % 16:
+                raise ValueError(f"DeviceActor: {name} layer {l} weight is not 16-byte aligned")
+            t.w[l], t.b[l], t.in_dim[l], t.out_dim[l] = m.weight.data_ptr(), m.bias.data_ptr(), m.in_features, m.out_features
+        return t
+
+    def _rows(self, x, name, rows):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.S or \
+                (rows is not None and x.shape[0] != rows) or x.shape[0] == 0:
+            got = f"{x.dtype} {list(x.shape)}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"DeviceActor: {name} must be float32 [{'m' if rows is None else rows}][{self.S}], got {got}")
+        if x.device != self.device:
+            raise ValueError(f"DeviceActor: {name} is on {x.device}, the actor on {self.device} (there is no CPU fallback)")
+        x = x.detach()
+        return x if x.is_contiguous() else x.contiguous()
+
+    # ---- the two launches ----------------------------------------------------------------------------------------------------------
+    def act(self, obs, deterministic: bool = False):
+        """-> (action [n][A], logp [n], value [n] or None) of `obs` [n][S] in one launch.  With `deterministic` the action is the
+        mean (tanh(mu) under the squashed head), logp the log-density there, and the draw counters do not advance."""
+        obs = self._rows(obs, "obs", self.num_envs)
+        s = self._native
+        s.d_obs, s.deterministic, s.grid_limit = obs.data_ptr(), int(bool(deterministic)), self._grid_limit
+        if self.head == "gaussian":
+            ls = self.log_std
+            if ls.dtype != torch.float32 or not ls.is_contiguous() or ls.device != self.device:
+                raise ValueError(f"DeviceActor: log_std must be a contiguous float32 tensor on {self.device}")
+            s.d_log_std = ls.data_ptr()
+        actor = self._table(self.actor_net, "the actor")
+        critic = self._table(self.critic_net, "the critic") if self.critic_net is not None else None
+        with torch.cuda.device(self.device):
+            N.check(self.lib.tg_policy_step(C.byref(actor), C.byref(critic) if critic is not None else None, C.byref(s),
+                                            N.stream_ptr(self.device)), "tg_policy_step")
+        return self.action, self.logp, self.value
+
+    def values(self, x):
+        """-> value [m] of any rows `x` [m][S], the critic alone, in one launch.  The result is this object's buffer for m rows,
+        overwritten by the next values() of the same row count."""
+        if self.critic_net is None:
+            raise ValueError("DeviceActor: values() needs a critic")
+        x = self._rows(x, "x", None)
+        m = x.shape[0]
+        out = self._values_out.get(m)
+        if out is None:
+            out = self._values_out[m] = torch.zeros(m, dtype=torch.float32, device=self.device)
+        critic = self._table(self.critic_net, "the critic")
+        with torch.cuda.device(self.device):
+            N.check(self.lib.tg_policy_values(C.byref(critic), x.data_ptr(), m, out.data_ptr(), self._grid_limit,
+                                              N.stream_ptr(self.device)), "tg_policy_values")
+        return out
+
+    @property
+    def calls(self) -> torch.Tensor:
+        """A copy of every slot's count of sampled act() calls, int64 [n]."""
+        return self._calls.long() & 0xFFFFFFFF
+
+    # ---- checkpointing -------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """The draw counters and what keys the draws (the nets are the caller's)."""
+        return {"calls": self._calls.clone(), "seed": self.seed, "env_offset": self.env_offset, "num_envs": self.num_envs}
+
+    def load_state_dict(self, sd):
+        """Take over a state_dict() of an object over the same slots: later draws agree bit for bit with the original's."""
+        if int(sd["num_envs"]) != self.num_envs or int(sd["env_offset"]) != self.env_offset:
+            raise ValueError(f"DeviceActor: state_dict is of {sd['num_envs']} slots at offset {sd['env_offset']}, this object of "
+                             f"{self.num_envs} at {self.env_offset}")
+        if tuple(sd["calls"].shape) != (self.num_envs,) or sd["calls"].dtype != torch.int32:
+            raise ValueError("DeviceActor: state_dict's calls is not int32 [num_envs]")
+        self._calls.copy_(sd["calls"])
+        self.seed = self._native.seed = self._checked_seed(sd["seed"])
