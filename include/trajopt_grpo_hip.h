@@ -1253,8 +1253,12 @@ int  tg_replay_sample(const tg_replay* r, int64_t batch, const int64_t* d_indice
  * tg_replay_prio_push (behind tg_replay_push on the same stream): the n leaves of time slot (d_cursor[0] - 1) mod K = *d_max, and every
  *   node above them is recomputed.  Other leaves stay.
  * tg_replay_prio_update: with R = d_filled[0] n, for every b with 0 <= d_idx[b] < R and finite d_td[b], leaf d_idx[b] =
- *   (float)pow((double)|d_td[b]| + (double)eps, (double)alpha), at most FLT_MAX; where d_idx repeats, the largest wins (one launch
+ *   (float)pow((double)|d_td[b]| + (double)eps, (double)alpha), at most 2^96; where d_idx repeats, the largest wins (one launch
  *   stores 0 to every named leaf, the next integer-atomicMaxes the new bits into leaf and *d_max); then the nodes above.
+ *   The cap is the overflow rule: *d_max starts at 1 and only update raises it, so every leaf that push and update write is at most
+ *   2^96, fewer than 2^31 of them sum to less than 2^127, and no node, prefix or root leaves float32.  Leaves written by the owner
+ *   (then tg_replay_prio_rebuild) are the owner's to keep finite in sum: with root = +inf every element's t is +inf, the descent falls
+ *   to the last child > 0 at every level, and o_raw and o_weight are NaN.
  * tg_replay_prio_sample, two launches: element b takes row d_indices[b], or with d_indices == NULL the leaf the descent reaches from
  *   the root for t = (b + u01d(w0, w1)) / batch * (double)root in float64, (w0, w1) from the Philox draw of tg_replay_sample: at each
  *   level the 64 children's inclusive float32 prefix by the Kogge-Stone scan (d = 1, 2, .., 32: x[i] += x[i - d] for i >= d), the child

@@ -31,6 +31,8 @@ constexpr int kPrioBlock = 256, kPrioWaves = kPrioBlock / kWave;
 constexpr int kPrioCrownBlock = 1024;
 constexpr int kPrioMaxLevels = 7;                                          // the leaves and at most 6 levels above them
 constexpr int kPrioMaxObs = 32, kPrioMaxAct = 8, kPrioMaxNStep = 16;
+// the cap of a new priority: fewer than 2^31 leaves of at most 2^96 sum to less than 2^127, so no node, prefix or root leaves float32
+constexpr float kPrioMaxPriority = 0x1p96f;
 
 // the sum of a node's 64 children, one per lane, in the fixed butterfly order; lane 0 holds it (the other lanes hold partial sums)
 __device__ static inline float node_sum(float x) {
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(kPrioCrownBlock) void prio_crown_kernel(tg_replay_p
 __device__ static inline float new_priority(float td, float alpha, float eps) {
     if (!(__builtin_fabsf(td) <= 3.4028235e38f)) return -1.0f;              // NaN or infinite
     const double v = pow((double)__builtin_fabsf(td) + (double)eps, (double)alpha);
-    return v < 3.4028235e38 ? (float)v : 3.4028235e38f;
+    return v < (double)kPrioMaxPriority ? (float)v : kPrioMaxPriority;
 }
 __global__ __launch_bounds__(kPrioBlock) void prio_zero_kernel(tg_replay r, tg_replay_prio p, int64_t batch,
                                                                 const int64_t* __restrict__ idx, const float* __restrict__ td) {

@@ -269,7 +269,11 @@ class DeviceReplayBuffer:
         """Row idx[b]'s priority becomes (|td_error[b]| + priority_eps) ** alpha (formed in float64, rounded once), and the running
         maximum that new rows enter with follows.  idx int64 [B] (sample()'s sixth tensor as it is), td_error float32 [B],
         both on the device; nothing is read on the host.  An index outside the stored rows and a non-finite error are ignored; where
-        idx repeats, the largest new priority wins.  An idx sampled before the ring took its row back names the new row."""
+        idx repeats, the largest new priority wins.  An idx sampled before the ring took its row back names the new row.
+
+        A new priority is capped at 2^96 (about 7.9e28): fewer than 2^31 such leaves sum to less than 2^127, so the tree's float32
+        sums, sample()'s root and its weights stay finite whatever errors arrive.  `priorities` written by hand (then rebuild_tree())
+        are the caller's to keep finite in sum: an infinite root draws the last row of positive priority every time, with NaN weights."""
         if not self.prioritized:
             raise RuntimeError("DeviceReplayBuffer: update_priorities() needs prioritized=True")
         for t, name, dtype in ((idx, "idx", torch.int64), (td_error, "td_error", torch.float32)):
