@@ -1417,6 +1417,48 @@ int  tg_policy_step_limits(int32_t* max_obs_dim, int32_t* max_hidden_layers, int
 int  tg_policy_step(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_step_args* s, void* stream);
 int  tg_policy_values(const tg_policy_net* critic, const float* d_x, int64_t m, float* d_value, int32_t grid_limit, void* stream);
 
+/* ---- Q critics on [obs, action] rows and the SAC target in one launch (DeviceActor.q_values / .sac_target, csrc/policy_q.hip;
+ * additions to ABI 13) ----
+ * A Q net is a tg_policy_net with obs_dim + act_dim <= 32 inputs and one output; its input row is d_obs[i][0..obs_dim) followed by the
+ * act_dim <= 4 action values.  All nets of a launch share the hidden width and the activation; depths are free.
+ * tg_policy_q_values, one launch: d_q1 [n] = Q1(d_obs_i, d_act_i); with q2 non-NULL also d_q2 [n] and d_qmin [n] = min(q1, q2).  The
+ *   fields behind d_act in the struct that are not named here are not read.
+ * tg_policy_sac_target, one launch, per row i: (a', logp) = tg_policy_step's TG_POLICY_HEAD_SQUASHED head of actor(d_obs_i) with the
+ *   draw at d_calls[i], which advances by one (same key, same TG_POLICY_STEP_STREAM: bit for bit what tg_policy_step gives on these
+ *   rows and counters); q1 = Q1(d_obs_i, a'), q2 = Q2(d_obs_i, a') (bit for bit tg_policy_q_values on d_action);
+ *   d_y[i] = d_reward[i] + d_discount[i] * (min(q1, q2) - d_alpha[0] * logp), every operation rounded to float32 on its own.
+ *   d_action [n][act_dim], d_logp, d_q1, d_q2, d_qmin, d_y [n] are written; d_act is not read; d_alpha is a device scalar.
+ * tg_policy_q_fits: TG_OK if a launch with these nets is taken (actor NULL: the q_values form; q2 NULL: one critic), else TG_ERR_ARG
+ *   with the reason -- a shape outside the set, nets that differ in width or activation, a critic whose input width is not
+ *   obs_dim + act_dim, or resident tables and weight ring beyond 160 KiB of LDS.  Only the widths of the tables are read. */
+typedef struct tg_policy_q_args {
+    const float* d_obs;
+    const float* d_act;
+    const float* d_reward;
+    const float* d_discount;
+    const float* d_alpha;
+    uint32_t*    d_calls;
+    float*       d_action;
+    float*       d_logp;
+    float*       d_q1;
+    float*       d_q2;
+    float*       d_qmin;
+    float*       d_y;
+    int64_t      n;
+    int64_t      env_offset;
+    uint64_t     seed;
+    int32_t      obs_dim;
+    int32_t      act_dim;
+    int32_t      grid_limit;
+    int32_t      reserved;
+    float        log_std_lo;
+    float        log_std_hi;
+} tg_policy_q_args;
+int  tg_policy_q_fits(const tg_policy_net* actor, const tg_policy_net* q1, const tg_policy_net* q2, int32_t act_dim);
+int  tg_policy_q_values(const tg_policy_net* q1, const tg_policy_net* q2, const tg_policy_q_args* s, void* stream);
+int  tg_policy_sac_target(const tg_policy_net* actor, const tg_policy_net* q1, const tg_policy_net* q2, const tg_policy_q_args* s,
+                          void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

@@ -69,7 +69,9 @@ def train(seed, args, dev):
     # --device-actor: the two no-grad actor calls (collection, and a' of the target) are tg.DeviceActor launches on actor.net; the
     # actor(b_obs) call that needs gradients stays torch
     da = tg.DeviceActor.for_env(venv, actor.net, head="squashed") if args.device_actor else None
-    da_batch = tg.DeviceActor(actor.net, num_envs=args.batch, head="squashed", seed=seed + 1, device=dev) if args.device_actor else None
+    # ... and the whole target (a', both target critics, min, y) is ONE sac_target launch on the target nets where they are
+    da_batch = tg.DeviceActor(actor.net, q_nets=(target.q1, target.q2), num_envs=args.batch, head="squashed", seed=seed + 1,
+                              device=dev) if args.device_actor else None
     obs, _ = venv.reset(seed=seed)
     buf.start(obs)
     ret_sum, ret_cnt = torch.zeros((), device=dev), torch.zeros((), device=dev)
@@ -87,8 +89,11 @@ def train(seed, args, dev):
                 b_obs, b_act, b_rew, b_next, b_disc, b_idx, *b_w = buf.sample(args.batch)
                 with torch.no_grad():
                     alpha = log_alpha.exp()
-                    a2, logp2 = da_batch.act(b_next)[:2] if da_batch else actor(b_next)
-                    y = b_rew + b_disc * (torch.min(*target(b_next, a2)) - alpha * logp2)
+                    if da_batch:
+                        y = da_batch.sac_target(b_next, b_rew, b_disc, alpha)
+                    else:
+                        a2, logp2 = actor(b_next)
+                        y = b_rew + b_disc * (torch.min(*target(b_next, a2)) - alpha * logp2)
                 q1, q2 = critic(b_obs, b_act)
                 if args.per:                                             # importance-weighted, and the rows' new priorities
                     q_loss = (b_w[0] * ((q1 - y).pow(2) + (q2 - y).pow(2))).mean()

@@ -191,6 +191,15 @@ class PolicyStepArgs(C.Structure):
                 ("grid_limit", C.c_int32), ("log_std_lo", C.c_float), ("log_std_hi", C.c_float)]
 
 
+class PolicyQArgs(C.Structure):
+    """tg_policy_q_args (include/trajopt_grpo_hip.h)."""
+    _fields_ = [("d_obs", C.c_void_p), ("d_act", C.c_void_p), ("d_reward", C.c_void_p), ("d_discount", C.c_void_p),
+                ("d_alpha", C.c_void_p), ("d_calls", C.c_void_p), ("d_action", C.c_void_p), ("d_logp", C.c_void_p), ("d_q1", C.c_void_p),
+                ("d_q2", C.c_void_p), ("d_qmin", C.c_void_p), ("d_y", C.c_void_p), ("n", C.c_int64), ("env_offset", C.c_int64),
+                ("seed", C.c_uint64), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("grid_limit", C.c_int32), ("reserved", C.c_int32),
+                ("log_std_lo", C.c_float), ("log_std_hi", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/trajopt_grpo_hip.h declares
 _P, _I32, _I64, _U64, _F, _VP = C.POINTER, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -386,6 +395,9 @@ SIGNATURES = {
     "tg_policy_step_limits": (C.c_int, [_P(_I32), _P(_I32), _P(_I32)]),
     "tg_policy_step": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyStepArgs), _VP]),
     "tg_policy_values": (C.c_int, [_P(PolicyNet), _VP, _I64, _VP, _I32, _VP]),
+    "tg_policy_q_fits": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyNet), _I32]),
+    "tg_policy_q_values": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyQArgs), _VP]),
+    "tg_policy_sac_target": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyNet), _P(PolicyQArgs), _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),

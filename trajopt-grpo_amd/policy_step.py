@@ -10,9 +10,15 @@ torch keeps them, and the pointer tables are filled from `param.data_ptr()` at e
 `param.data.copy_()` is therefore seen by the next call, outside a captured graph and inside one.  A parameter REBOUND to new storage
 (`param.data = other`, `load_state_dict(assign=True)`) is seen by the next eager call but not by a graph captured before it.
 
-Not built: gradients through act() (the learner's re-evaluation stays torch autograd), bf16, more than 4 actions, LayerNorm or mixed
-activations, a trunk shared by actor and critic.  There is no silent torch fallback: a net outside the kernel's set raises
-ValueError with supports()'s reason, and the caller's own torch code is the fallback.
+With `q_nets` (one Q critic on [obs, action] rows, or SAC's twin pair) two more launches exist (csrc/policy_q.hip): `q_values(obs, act)`
+gives q1, q2 and min(q1, q2) of any rows, and `sac_target(next_obs, reward, discount, alpha)` is the whole off-policy target
+y = reward + discount * (min(Q1', Q2')(s', a') - alpha * logp(a'|s')) with a' drawn by the actor, in ONE launch: a wave runs the
+actor and then both critics on its 16 rows and hands a' over in registers.
+
+Not built: gradients through act(), q_values() or sac_target() (the learner's re-evaluation and the critic / actor updates stay torch
+autograd), bf16, more than 4 actions, LayerNorm or mixed activations, a trunk shared by actor and critic, Q nets whose width or
+activation differs from the actor's, more than two critics, a target for TD3 / DDPG heads.  There is no silent torch fallback: a net
+outside the kernel's set raises ValueError with supports()'s reason, and the caller's own torch code is the fallback.
 """
 from __future__ import annotations
 
@@ -68,9 +74,52 @@ def _shape(net, head):
         return None, f"{O} outputs under the squashed head: (mean, log-std) pairs of 1..{MAX_ACT_DIM} actions, so an even count <= {2 * MAX_ACT_DIM}"
     if head == "value" and O != 1:
         return None, f"{O} outputs of a critic: 1"
-    if head not in ("gaussian", "squashed", "value"):
+    if head == "q" and O != 1:
+        return None, f"{O} outputs of a Q critic: 1"
+    if head == "q" and S < 2:
+        return None, f"input width {S} of a Q critic: at least one observation and one action"
+    if head not in ("gaussian", "squashed", "value", "q"):
         return None, f"unknown head {head!r}"
     return (S, H, nh, O, act), None
+
+
+def _widths(net):
+    """tg_policy_net of `net` with the widths alone (no pointers)."""
+    lin = _modules(net)[0::2]
+    t = N.PolicyNet()
+    t.n_layers = len(lin)
+    t.activation = _ACT[M.hidden_activation(types.SimpleNamespace(network=_modules(net)))]
+    for l, m in enumerate(lin):
+        t.in_dim[l], t.out_dim[l] = m.in_features, m.out_features
+    return t
+
+
+def _q_refusal(actor_net, actor_shape, head, q_nets):
+    """None if q_values() and (with a pair) sac_target() take `q_nets` beside the actor, else the reason.  What the nets must share is
+    compared here; whether their tables and the weight ring fit in LDS is the library's verdict (tg_policy_q_fits)."""
+    S, H, _, O, act = actor_shape
+    A = O // 2
+    if head != "squashed":
+        return f"q_nets go with the squashed head (SAC's actor), not {head!r}"
+    if not 1 <= len(q_nets) <= 2:
+        return f"{len(q_nets)} Q nets: one, or a twin pair"
+    for k, q in enumerate(q_nets, 1):
+        shape, why = _shape(q, "q")
+        if shape is None:
+            return f"Q{k} is not supported: {why}"
+        if shape[1] != H or shape[4] != act:
+            return f"Q{k} is {shape[1]} wide with {shape[4]}, the actor {H} wide with {act}: one kernel body runs all three nets"
+        if shape[0] != S + A:
+            return f"Q{k} reads {shape[0]} inputs, the actor gives {S} observations + {A} actions"
+    lib = N.load()
+    tables = [_widths(q) for q in q_nets]
+    forms = [(None, *tables, *([None] * (2 - len(tables))))]
+    if len(tables) == 2:
+        forms.append((_widths(actor_net), *tables))
+    for actor, q1, q2 in forms:
+        if lib.tg_policy_q_fits(C.byref(actor) if actor is not None else None, C.byref(q1), C.byref(q2) if q2 is not None else None, A):
+            return lib.tg_last_error().decode("utf-8", "replace")
+    return None
 
 
 class DeviceActor:
@@ -81,6 +130,8 @@ class DeviceActor:
     head        "gaussian": O = A, a = mu + exp(log_std) eps with the state-independent `log_std` [A] (a device tensor or Parameter,
                 read at every call); "squashed": O = 2 A, (mu, ls) = split(out), ls clamped to `log_std_bounds`, a = tanh(mu + exp(ls) eps)
                 and the squash correction - sum log(1 - a^2 + 1e-6) in the log-density.
+    q_nets      None, one Q net or a pair: Linear(S + A <= 32, H) act [Linear(H, H) act]{0..4} Linear(H, 1) with the ACTOR's H and
+                activation (depths are free), under the squashed head: q_values() and, with a pair, sac_target().
     seed, env_offset        eps of slot i at its k-th sampled call is the Box-Muller of Philox(seed, env_offset + i, k, the policy step's
                 stream constant): objects with consecutive offsets are, bit for bit, the slots of one larger object.
 
@@ -88,7 +139,7 @@ class DeviceActor:
     the next act() (DeviceVecEnv's rule): clone what you keep.  `mean` is the deterministic action of the last act(): mu, or tanh(mu)
     under the squashed head.  values() has a buffer of its own per row count."""
 
-    def __init__(self, actor_net, critic_net=None, *, num_envs: int, log_std=None, head: str = "gaussian",
+    def __init__(self, actor_net, critic_net=None, *, q_nets=None, num_envs: int, log_std=None, head: str = "gaussian",
                  log_std_bounds=(-5.0, 2.0), seed: int = 0, env_offset: int = 0, device=None):
         if head not in HEADS:
             raise ValueError(f"DeviceActor: head {head!r} is not one of {sorted(HEADS)}")
@@ -104,6 +155,11 @@ class DeviceActor:
                 raise ValueError(f"DeviceActor: the critic is not supported: {why}")
             if cshape[0] != self.S:
                 raise ValueError(f"DeviceActor: the critic reads {cshape[0]} inputs, the actor {self.S}")
+        self.q_nets = () if q_nets is None else ((q_nets,) if isinstance(q_nets, torch.nn.Module) else tuple(q_nets))
+        if q_nets is not None:
+            why = _q_refusal(actor_net, shape, head, self.q_nets)
+            if why is not None:
+                raise ValueError(f"DeviceActor: the Q nets are not supported: {why}")
         if int(num_envs) <= 0 or int(env_offset) < 0:
             raise ValueError(f"DeviceActor: num_envs={num_envs} must be positive and env_offset={env_offset} non-negative")
         self.num_envs, self.env_offset = int(num_envs), int(env_offset)
@@ -133,7 +189,10 @@ class DeviceActor:
         self.value = torch.zeros(n, dtype=f32, device=dev) if critic_net is not None else None
         self._calls = torch.zeros(n, dtype=torch.int32, device=dev)            # (the bits of a u32)
         self._values_out = {}
-        self._grid_limit = 0             # 0: two workgroups per CU; a test sets it to force further trips of a workgroup's row loop
+        self._q_out = {}
+        if len(self.q_nets) == 2:                                              # sac_target's by-products and its owned alpha
+            self.q1, self.q2, self.qmin, self.y, self._alpha = (torch.zeros(k, dtype=f32, device=dev) for k in (n, n, n, n, 1))
+        self._grid_limit = 0           # 0: two workgroups per CU; a test sets it to force further trips of a workgroup's row loop
         s = N.PolicyStepArgs()
         s.d_calls, s.d_action, s.d_logp, s.d_mean = (t.data_ptr() for t in (self._calls, self.action, self.logp, self.mean))
         s.d_value = N.ptr(self.value)
@@ -153,7 +212,8 @@ class DeviceActor:
 
     @staticmethod
     def supports(net, head: str = "gaussian"):
-        """None if the kernel takes `net` under `head` ("gaussian", "squashed", or "value" for a critic), else the reason as a string."""
+        """None if the kernel takes `net` under `head` ("gaussian", "squashed", "value" for a critic, "q" for a Q critic on [obs, action]
+        rows), else the reason as a string.  What the Q nets must share with the actor is checked by the constructor."""
         return _shape(net, head)[1]
 
     @staticmethod
@@ -166,9 +226,7 @@ class DeviceActor:
     # ---- the tables: filled from the parameters' CURRENT storage at every call -----------------------------------------------------
     def _table(self, net, name):
         lin = _modules(net)[0::2]
-        t = N.PolicyNet()
-        t.n_layers = len(lin)
-        t.activation = _ACT[M.hidden_activation(types.SimpleNamespace(network=_modules(net)))]
+        t = _widths(net)
         for l, m in enumerate(lin):
             for p, what in ((m.weight, "weight"), (m.bias, "bias")):
                 if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.device:
@@ -176,14 +234,17 @@ class DeviceActor:
                                      f"{p.dtype} on {p.device}{'' if p.is_contiguous() else ', not contiguous'}")
             if 0 < l < len(lin) - 1 and m.weight.data_ptr() % 16:
                 raise ValueError(f"DeviceActor: {name} layer {l} weight is not 16-byte aligned")
-            t.w[l], t.b[l], t.in_dim[l], t.out_dim[l] = m.weight.data_ptr(), m.bias.data_ptr(), m.in_features, m.out_features
+            t.w[l], t.b[l] = m.weight.data_ptr(), m.bias.data_ptr()
         return t
 
-    def _rows(self, x, name, rows):
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.S or \
+    def _rows(self, x, name, rows, width=None):
+        """`x` as a contiguous float32 [rows][width] (the observation width by default; 0: a vector [rows]) on this device."""
+        width = self.S if width is None else width
+        shape = ("m" if rows is None else rows,) + ((width,) if width else ())
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != len(shape) or (width and x.shape[1] != width) or \
                 (rows is not None and x.shape[0] != rows) or x.shape[0] == 0:
             got = f"{x.dtype} {list(x.shape)}" if isinstance(x, torch.Tensor) else type(x).__name__
-            raise ValueError(f"DeviceActor: {name} must be float32 [{'m' if rows is None else rows}][{self.S}], got {got}")
+            raise ValueError(f"DeviceActor: {name} must be float32 {''.join(f'[{d}]' for d in shape)}, got {got}")
         if x.device != self.device:
             raise ValueError(f"DeviceActor: {name} is on {x.device}, the actor on {self.device} (there is no CPU fallback)")
         x = x.detach()
@@ -223,6 +284,59 @@ class DeviceActor:
             N.check(self.lib.tg_policy_values(C.byref(critic), x.data_ptr(), m, out.data_ptr(), self._grid_limit,
                                               N.stream_ptr(self.device)), "tg_policy_values")
         return out
+
+    def q_values(self, obs, act):
+        """-> (q1 [m], q2 [m] or None, min(q1, q2) [m] or None) of any rows `obs` [m][S], `act` [m][A]: the Q nets on the rows
+        [obs, act] in one launch.  The results are this object's buffers for m rows, overwritten by the next q_values() of that
+        row count."""
+        if not self.q_nets:
+            raise ValueError("DeviceActor: q_values() needs q_nets")
+        obs = self._rows(obs, "obs", None)
+        act = self._rows(act, "act", obs.shape[0], self.A)
+        m, twin = obs.shape[0], len(self.q_nets) == 2
+        out = self._q_out.get(m)
+        if out is None:
+            out = self._q_out[m] = tuple(torch.zeros(m, dtype=torch.float32, device=self.device) if k == 0 or twin else None
+                                         for k in range(3))
+        s = N.PolicyQArgs()
+        s.d_obs, s.d_act, s.n, s.obs_dim, s.act_dim, s.grid_limit = obs.data_ptr(), act.data_ptr(), m, self.S, self.A, self._grid_limit
+        s.d_q1, s.d_q2, s.d_qmin = (N.ptr(t) for t in out)
+        q = [self._table(net, f"Q{k + 1}") for k, net in enumerate(self.q_nets)]
+        with torch.cuda.device(self.device):
+            N.check(self.lib.tg_policy_q_values(C.byref(q[0]), C.byref(q[1]) if twin else None, C.byref(s), N.stream_ptr(self.device)),
+                    "tg_policy_q_values")
+        return out
+
+    def sac_target(self, next_obs, reward, discount, alpha):
+        """-> y [n] = reward + discount * (min(Q1, Q2)(next_obs, a') - alpha * logp(a' | next_obs)) in one launch, every operation
+        rounded to float32 on its own; a' is the actor's next draw on these slots (what act(next_obs) would have given: the same
+        counters, which advance).  `q_nets` are the TARGET critics.  `alpha` is a 0-dim float32 device tensor, read by the kernel at
+        every call (and at every replay of a captured one), or a float.  `self.action`, `self.logp`, `self.q1`, `self.q2` hold a',
+        its log-density and the two critics' values; like y (`self.y`) they are overwritten by the next call."""
+        if len(self.q_nets) != 2:
+            raise ValueError("DeviceActor: sac_target() needs a pair of q_nets")
+        n = self.num_envs
+        obs = self._rows(next_obs, "next_obs", n)
+        reward, discount = self._rows(reward, "reward", n, 0), self._rows(discount, "discount", n, 0)
+        if isinstance(alpha, torch.Tensor):
+            if alpha.dtype != torch.float32 or alpha.dim() != 0 or alpha.device != self.device:
+                raise ValueError(f"DeviceActor: alpha must be a 0-dim float32 tensor on {self.device} or a float")
+            alpha = alpha.detach()
+        else:
+            alpha = self._alpha.fill_(float(alpha))
+        a = self._native
+        s = N.PolicyQArgs()
+        s.d_obs, s.d_reward, s.d_discount, s.d_alpha = obs.data_ptr(), reward.data_ptr(), discount.data_ptr(), alpha.data_ptr()
+        s.d_calls, s.d_action, s.d_logp = a.d_calls, a.d_action, a.d_logp
+        s.d_q1, s.d_q2, s.d_qmin, s.d_y = (t.data_ptr() for t in (self.q1, self.q2, self.qmin, self.y))
+        s.n, s.env_offset, s.seed, s.obs_dim, s.act_dim, s.grid_limit = n, self.env_offset, self.seed, self.S, self.A, self._grid_limit
+        s.log_std_lo, s.log_std_hi = self.log_std_bounds
+        actor = self._table(self.actor_net, "the actor")
+        q = [self._table(net, f"Q{k + 1}") for k, net in enumerate(self.q_nets)]
+        with torch.cuda.device(self.device):
+            N.check(self.lib.tg_policy_sac_target(C.byref(actor), C.byref(q[0]), C.byref(q[1]), C.byref(s), N.stream_ptr(self.device)),
+                    "tg_policy_sac_target")
+        return self.y
 
     @property
     def calls(self) -> torch.Tensor:
