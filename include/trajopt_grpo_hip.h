@@ -1459,6 +1459,52 @@ int  tg_policy_q_values(const tg_policy_net* q1, const tg_policy_net* q2, const 
 int  tg_policy_sac_target(const tg_policy_net* actor, const tg_policy_net* q1, const tg_policy_net* q2, const tg_policy_q_args* s,
                           void* stream);
 
+/* ---- Policy re-evaluation with gradients (DeviceActor.evaluate, csrc/policy_grad.hip; additions to ABI 13) ----
+ * The learner side of the policy step under TG_POLICY_HEAD_GAUSSIAN: m stored rows (d_obs [m][S], d_act [m][A]) through the actor and,
+ * if given, the critic (tg_policy_net as above, read where torch keeps them), forward and backward, float32.
+ * tg_policy_eval_forward, one launch: mu = actor(obs_i) -> d_mu [m][A]; eps_k = (a_k - mu_k) / exp(ls_k);
+ *   d_logp [m] = sum_k(-0.5 eps_k^2 - ls_k - 0.5 log 2 pi) (tg_policy_step's expression), d_entropy [m] = sum_k(ls_k + 0.5 + 0.5 log 2 pi),
+ *   d_value [m] = critic(obs_i); every hidden layer's post-activation goes to d_acts_* [hidden layers][m][H].  No draw, no counter.
+ * tg_policy_eval_backward, one launch: from d_g_logp, d_g_entropy, d_g_value [m] (the loss's gradients with respect to the three
+ *   outputs), d_mu and d_acts_*: the head gradients d_dout_* [m][4] (actor: g_logp (a - mu) exp(-2 ls); critic: g_value; zero-padded),
+ *   d_std_rows [m][4] = g_logp (eps^2 - 1) + g_entropy (tg_log_std_grad's input), and dZ of every hidden layer, d_dz_* [hidden layers][m][H].
+ * tg_policy_eval_weight_grad, two launches: dW_l = dZ_l^T A_{l-1}, db_l = the column sums of dZ_l, for every layer of both nets, added
+ *   over row slabs in a fixed order (d_partials; no atomics: the same bits at every call), written to d_grad_* in torch's layout: per
+ *   Linear layer in order, weight [out][in] then bias [out], back to back.
+ * tg_policy_eval_workspace: the sizes, in floats, for (nets, m): act_floats [2] (d_acts_* = d_dz_* of the actor and the critic),
+ *   grad_floats [2] (d_grad_*), partial_floats (d_partials).  critic may be NULL (its sizes are 0).  Only widths are read.
+ * Refused (TG_ERR_ARG) before any launch: what tg_policy_step refuses, a net beyond 160 KiB of LDS, misaligned workspaces. */
+typedef struct tg_policy_eval_args {
+    const float* d_obs;
+    const float* d_act;
+    const float* d_log_std;
+    float*       d_mu;
+    float*       d_logp;
+    float*       d_entropy;
+    float*       d_value;
+    float*       d_acts_actor;
+    float*       d_acts_critic;
+    const float* d_g_logp;
+    const float* d_g_entropy;
+    const float* d_g_value;
+    float*       d_dz_actor;
+    float*       d_dz_critic;
+    float*       d_dout_actor;
+    float*       d_dout_critic;
+    float*       d_std_rows;
+    float*       d_grad_actor;
+    float*       d_grad_critic;
+    float*       d_partials;
+    int64_t      m;
+    int32_t      act_dim;
+    int32_t      grid_limit;
+} tg_policy_eval_args;
+int  tg_policy_eval_workspace(const tg_policy_net* actor, const tg_policy_net* critic, int64_t m, int64_t* act_floats, int64_t* grad_floats,
+                              int64_t* partial_floats);
+int  tg_policy_eval_forward(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, void* stream);
+int  tg_policy_eval_backward(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, void* stream);
+int  tg_policy_eval_weight_grad(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

@@ -21,6 +21,16 @@ def mlp(n_in, n_out, hidden=64):
     return nn.Sequential(nn.Linear(n_in, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh(), nn.Linear(hidden, n_out))
 
 
+def evaluate(da, args, actor, critic, log_std, obs, act):
+    """-> (log-density of the stored actions, value) of a minibatch, with gradients: --device-evaluate takes them from
+    tg.DeviceActor.evaluate (HIP forward and backward behind one autograd node), else the torch forward."""
+    if args.device_evaluate:
+        logp, _, value = da.evaluate(obs, act)
+        return logp, value
+    dist = torch.distributions.Normal(actor(obs), log_std.exp())
+    return dist.log_prob(act).sum(-1), critic(obs).squeeze(-1)
+
+
 def train(seed, args, dev):
     torch.manual_seed(seed)
     venv = tg.DeviceVecEnv(tg.CartPole(max_steps=args.max_steps), args.envs, seed=seed, device=dev)
@@ -69,12 +79,12 @@ def train(seed, args, dev):
         f_adv, f_ret = adv.reshape(-1), ret.reshape(-1)
         for _ in range(args.epochs):
             for idx in torch.randperm(L * n, device=dev).chunk(args.minibatches):
-                dist = torch.distributions.Normal(actor(flat["obs"][idx]), log_std.exp())
-                ratio = (dist.log_prob(flat["act"][idx]).sum(-1) - flat["logp"][idx]).exp()
+                logp, value = evaluate(da, args, actor, critic, log_std, flat["obs"][idx], flat["act"][idx])
+                ratio = (logp - flat["logp"][idx]).exp()
                 a = f_adv[idx]
                 a = (a - a.mean()) / (a.std() + 1e-8)
                 pi_loss = -torch.min(ratio * a, ratio.clamp(1 - args.clip, 1 + args.clip) * a).mean()
-                v_loss = 0.5 * (critic(flat["obs"][idx]).squeeze(-1) - f_ret[idx]).pow(2).mean()
+                v_loss = 0.5 * (value - f_ret[idx]).pow(2).mean()
                 opt.zero_grad(set_to_none=True)
                 (pi_loss + args.vf_coef * v_loss).backward()
                 nn.utils.clip_grad_norm_(params, 0.5)
@@ -126,11 +136,11 @@ def train_storage(seed, args, dev):
             st.shuffle()
             for k in range(args.minibatches):
                 b_obs, b_act, b_logp, a, b_ret, _ = st.minibatch(k, args.minibatches)
-                dist = torch.distributions.Normal(actor(b_obs), log_std.exp())
-                ratio = (dist.log_prob(b_act).sum(-1) - b_logp).exp()
+                logp, value = evaluate(da, args, actor, critic, log_std, b_obs, b_act)
+                ratio = (logp - b_logp).exp()
                 a = (a - a.mean()) / (a.std() + 1e-8)
                 pi_loss = -torch.min(ratio * a, ratio.clamp(1 - args.clip, 1 + args.clip) * a).mean()
-                v_loss = 0.5 * (critic(b_obs).squeeze(-1) - b_ret).pow(2).mean()
+                v_loss = 0.5 * (value - b_ret).pow(2).mean()
                 opt.zero_grad(set_to_none=True)
                 (pi_loss + args.vf_coef * v_loss).backward()
                 nn.utils.clip_grad_norm_(params, 0.5)
@@ -162,7 +172,11 @@ def main():
     ap.add_argument("--out", default=None, help="write the curves here: one line per seed and iteration")
     ap.add_argument("--storage", action="store_true", help="the same PPO on tg.DeviceRolloutStorage: storing, GAE and minibatches on the device")
     ap.add_argument("--device-actor", action="store_true", help="collect with tg.DeviceActor: sampling, log-density and values in one launch")
+    ap.add_argument("--device-evaluate", action="store_true", help="with --device-actor: the update's log-density and value, forward and "
+                    "backward, from tg.DeviceActor.evaluate instead of the torch forward")
     args = ap.parse_args()
+    if args.device_evaluate and not args.device_actor:
+        ap.error("--device-evaluate needs --device-actor")
     if not torch.cuda.is_available():
         sys.exit("vec_env_ppo.py needs an MI355X: DeviceVecEnv has no CPU fallback")
     dev = torch.device("cuda", 0)

@@ -200,6 +200,14 @@ class PolicyQArgs(C.Structure):
                 ("log_std_lo", C.c_float), ("log_std_hi", C.c_float)]
 
 
+class PolicyEvalArgs(C.Structure):
+    """tg_policy_eval_args (include/trajopt_grpo_hip.h)."""
+    _fields_ = [(name, C.c_void_p) for name in (
+        "d_obs", "d_act", "d_log_std", "d_mu", "d_logp", "d_entropy", "d_value", "d_acts_actor", "d_acts_critic", "d_g_logp", "d_g_entropy",
+        "d_g_value", "d_dz_actor", "d_dz_critic", "d_dout_actor", "d_dout_critic", "d_std_rows", "d_grad_actor", "d_grad_critic",
+        "d_partials")] + [("m", C.c_int64), ("act_dim", C.c_int32), ("grid_limit", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/trajopt_grpo_hip.h declares
 _P, _I32, _I64, _U64, _F, _VP = C.POINTER, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -398,6 +406,10 @@ SIGNATURES = {
     "tg_policy_q_fits": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyNet), _I32]),
     "tg_policy_q_values": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyQArgs), _VP]),
     "tg_policy_sac_target": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyNet), _P(PolicyQArgs), _VP]),
+    "tg_policy_eval_workspace": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _I64, _P(_I64), _P(_I64), _P(_I64)]),
+    "tg_policy_eval_forward": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyEvalArgs), _VP]),
+    "tg_policy_eval_backward": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyEvalArgs), _VP]),
+    "tg_policy_eval_weight_grad": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyEvalArgs), _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),

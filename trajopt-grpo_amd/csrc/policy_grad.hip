@@ -1,0 +1,736 @@
+// The learner side of DeviceActor (DeviceActor.evaluate, trajopt-grpo_amd/policy_step.py): stored (obs, action) rows re-evaluated
+// forward and backward in float32 on v_mfma_f32_16x16x4_f32, against torch's own row-major `nn.Linear` storage -- weights are READ
+// where torch keeps them and gradients are WRITTEN in torch's [out][in] / [out] layout.  Three launches:
+//
+//   tg_policy_eval_forward      policy_step.hip's machine (a wave owns 16 rows, 4 waves per workgroup, the net as grid dimension y, a
+//                               3-slot LDS-DMA ring of 16-output-row weight blocks) with two differences: every hidden layer's 16 x H
+//                               post-activation tile goes to acts[l][m][H] (lane (j, g)'s registers r = 0..3 of tile t are features
+//                               16 t + 4 g + r of row j: one 16-byte store), and the epilogue takes the action from memory.  No Philox.
+//   tg_policy_eval_backward     backward data on the same split.  Head gradient and dA_top = d_out . W_head on the vector unit, then per
+//                               H x H layer from the top: dZ_l = dA_l * act'(acts[l]) (stored [m][H]), dA_{l-1} = dZ_l . W_l on MFMAs.
+//   tg_policy_eval_weight_grad  dW_l = dZ_l^T A_{l-1}, db_l = column sums of dZ_l, for every layer of both nets in one launch, and a
+//                               fixed-order finishing pass.
+//
+// Backward data, the form chosen: the operand of step (t, r) is W_l[16 t + 4 g + r][16 ti + ii] -- a COLUMN piece of W_l.  The ring
+// runs over the same contiguous 16-output-row regions of W_l as the forward (block t = rows 16 t .. 16 t + 15, 16 H floats in one
+// run, so the DMA is a linear copy: lane `lane` of piece p moves bytes 1024 p + 16 lane), landed plain row-major in LDS, and all
+// H / 16 input-feature accumulator tiles of the wave's 16 rows stay live (64 registers at H = 256) while the block is consumed:
+// lane (ii, g) reads the 4 bytes at row 4 g + r, column 16 ti + ii, and each such read feeds one MFMA.  The four lane groups read
+// four different 4-row groups, so every 4-row group (H / 64 DMA pieces) is followed by 16 floats of padding: the groups' reads fall
+// into four different quarters of the banks.  Why not the transposing 16 x 16 sub-block read: it keeps one accumulator tile live
+// instead of H / 16, but needs H / 16 passes over the ring per layer (each block re-fetched per input tile) or a transposed copy
+// of W_l in LDS (64 KiB+ at H = 256 beside the ring); the accumulators fit (128 VGPRs with the dZ operands at H = 256, the
+// forward's count), so the single pass wins on bytes moved.
+//
+// Weight gradient: a workgroup owns a 64 x 64 output tile of one layer and a slab of rows; per 64 rows it stages the dZ columns and
+// the A columns of its tile through LDS (row stride 80 floats: the four lane groups' rows land in different bank quarters), wave w
+// owns output rows 16 w .. 16 w + 15 against the four 16-column tiles (one A read per four B reads).  Both operands are row-major
+// over rows, which is what the 16x16x4 fragments want: lane (i, g) reads element [4 s + g][i].  The head (O <= 4 rows of dW) and
+// the first layer (K = S <= 32 columns) run as zero-PADDED TILES of the same body, not on the vector unit: operand columns past
+// the width are staged as zeros and never stored.  Bias sums: the workgroups of column tile 0 add their staged dZ columns on the
+// vector unit.  Partials [tile][slab][64 x 64 + 64] are added over the slabs in index order by the finishing pass: no atomics, the
+// same bits at every call.  The slab count depends on m alone (<= 32 slabs of whole 64-row chunks).
+#include <stdlib.h>
+
+#include "tg_common.hpp"
+#include "mfma_ring.hpp"
+#include "act_f32.hpp"
+
+namespace tg {
+
+constexpr int kPgLinear = TG_POLICY_MAX_LAYERS;
+constexpr int kPgWaves = 4;
+constexpr int kPgD = 3, kPgP = kPgD - 1;                // ring slots, blocks in flight
+constexpr int kPgMaxOut = 4;                            // gaussian head: <= 4 means; a critic: 1
+constexpr int kPgMaxIn = 32;
+constexpr int kPgMaxSlabs = 32;
+constexpr int kPgTile = 64, kPgLd = 80;                 // weight gradient: tile edge, LDS row stride (floats)
+constexpr int kPgPartial = kPgTile * kPgTile + kPgTile; // floats of one partial: the tile and its bias sums
+constexpr int kPgJobs = 2 * kPgLinear;
+
+struct PgNet {
+    const float* w[kPgLinear];
+    const float* b[kPgLinear];
+    int32_t S, H, nh, O, act;                           // input width, hidden width, hidden layers, head outputs, TG_ACT_*
+};
+
+struct PgArgs {
+    PgNet net[2];                   // [0] the actor, [1] the critic
+    int32_t act_dim;
+    const float* x;                 // [rows][S], unpadded
+    const float* action;            // [rows][A]
+    int64_t rows;
+    const float* log_std;           // [A]
+    float* mu; float* logp; float* entropy; float* value;
+    float* acts[2];                 // [nh][rows][H] per net
+    const float* g_logp; const float* g_entropy; const float* g_value;
+    float* dz[2];                   // [nh][rows][H] per net
+    float* dout[2];                 // [rows][4] per net, zero-padded
+    float* std_rows;                // [rows][4], zero-padded
+};
+
+__device__ static inline uint4 pg_lds_u4(const uint4* __restrict__ p) { return *p; }
+__device__ static inline float4 pg_lds_f4(const float* __restrict__ p) { return *reinterpret_cast<const float4*>(p); }
+__device__ static inline float pg_lds_f(const float* __restrict__ p) { return *p; }
+
+static size_t pg_fwd_lds_bytes(const PgNet& n) {
+    const int NT = n.H / 16, K4 = (n.S + 3) / 4;
+    return (size_t)kPgD * NT * 1024 + (size_t)NT * K4 * 256 + (size_t)(n.nh + n.O) * n.H * 4 + 8 * 4;
+}
+static size_t pg_bwd_lds_bytes(const PgNet& n) {
+    return (size_t)kPgD * (16 * n.H + 64) * 4 + (size_t)n.O * n.H * 4;
+}
+
+// (uniform selects over the kernel arguments: a run-time index into a local copy of the tables would put it into scratch)
+__device__ static inline const float* pg_weight(const PgArgs& a, bool critic, int l) {
+    const float* r = critic ? a.net[1].w[0] : a.net[0].w[0];
+#pragma unroll
+    for (int q = 1; q < kPgLinear; ++q) r = l == q ? (critic ? a.net[1].w[q] : a.net[0].w[q]) : r;
+    return r;
+}
+__device__ static inline const float* pg_bias(const PgArgs& a, bool critic, int l) {
+    const float* r = critic ? a.net[1].b[0] : a.net[0].b[0];
+#pragma unroll
+    for (int q = 1; q < kPgLinear; ++q) r = l == q ? (critic ? a.net[1].b[q] : a.net[0].b[q]) : r;
+    return r;
+}
+
+// ---- 1. forward: ps_forward (policy_step.hip) + the activation stores + the epilogue on a given action ------------------------------
+template <int H, int kAct>
+__device__ __attribute__((always_inline)) static inline void pg_forward(const PgArgs& a, const int S, const int nh, const int O,
+                                                                        const int role, uint4* lds) {
+    constexpr int NT = H / 16, KS = NT, WPW = kPgWaves, D = kPgD, P = kPgP, SLOT = KS * 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 15, g = lane >> 4;
+    const int n_hh = nh - 1, K4 = (S + 3) >> 2;
+    const bool critic = role == 1;
+    uint4* ring = lds;
+    float* w0_s = reinterpret_cast<float*>(ring + D * SLOT);          // [NT][K4][64 lanes]
+    float* bias_s = w0_s + NT * K4 * 64;                              // [nh][H]
+    float* wh_s = bias_s + nh * H;                                    // [O][H]
+    float* bh_s = wh_s + O * H;                                       // [8]
+    const int64_t rows = a.rows;
+    const int64_t n_rounds = (rows + 63) / 64;
+    float* acts = critic ? a.acts[1] : a.acts[0];
+
+    int pre_l = 1, pre_mo = 0, pre_slot = 0, cur_slot = 0;
+    auto dma_next = [&]() {
+        const float* src = pg_weight(a, critic, pre_l) + ((16 * pre_mo + j) * H + 4 * g);
+        uint4* slot = ring + pre_slot * SLOT;
+#pragma unroll
+        for (int q = 0; q < KS / WPW; ++q) {
+            const int piece = q * WPW + wave;
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(src + 16 * piece), (lds_void*)(slot + piece * 64), 16, 0, 0);
+        }
+        pre_mo = (pre_mo + 1 == NT) ? 0 : pre_mo + 1;
+        pre_l = pre_mo != 0 ? pre_l : (pre_l == n_hh ? 1 : pre_l + 1);
+        pre_slot = (pre_slot + 1 == D) ? 0 : pre_slot + 1;
+    };
+    if (n_hh > 0) {
+#pragma unroll
+        for (int b = 0; b < P; ++b) dma_next();
+    }
+    const float* w0 = pg_weight(a, critic, 0);
+    for (int q = tid; q < NT * K4 * 64; q += 64 * WPW) {
+        const int ln = q & 63, ps = q >> 6, mo = ps / K4, s = ps - mo * K4;
+        const int k = 4 * s + (ln >> 4);
+        const bool in = k < S;
+        const float v = w0[(16 * mo + (ln & 15)) * S + (in ? k : 0)];
+        w0_s[q] = in ? v : 0.f;
+    }
+    for (int l = 0; l < nh; ++l) {
+        const float* bl = pg_bias(a, critic, l);
+        for (int q = tid; q < H; q += 64 * WPW) bias_s[l * H + q] = bl[q];
+    }
+    {
+        const float* Wh = pg_weight(a, critic, nh);
+        const float* Bh = pg_bias(a, critic, nh);
+        for (int q = tid; q < O * H; q += 64 * WPW) wh_s[q] = Wh[q];
+        const float bv = Bh[tid < O ? tid : 0];
+        if (tid < 8) bh_s[tid] = tid < O ? bv : 0.f;
+    }
+    __syncthreads();
+    // (the activation stores of a round are issued behind the block a wait names and are not counted: stricter, never weaker)
+    constexpr int kWait = (P - 1) * (KS / WPW);
+
+    auto act4 = [&](f32x4& v) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = act_f32<kAct>(v[r]);
+    };
+    auto tile_products = [&](const uint4* __restrict__ cur, const f32x4 (&xin)[NT], f32x4 acc) {
+        const uint4* __restrict__ p = cur + lane;
+        f32x4 acc1 = {0.f, 0.f, 0.f, 0.f};
+        uint4 wa = pg_lds_u4(p), wb = pg_lds_u4(p + 64);
+        dma_next();
+#pragma unroll
+        for (int t = 0; t < NT; t += 2) {
+            uint4 na = wa, nb = wb;
+            if (t + 2 < NT) { na = pg_lds_u4(p + (t + 2) * 64); nb = pg_lds_u4(p + (t + 3) * 64); }
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.x), xin[t][0], acc, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.x), xin[t + 1][0], acc1, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.y), xin[t][1], acc, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.y), xin[t + 1][1], acc1, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.z), xin[t][2], acc, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.z), xin[t + 1][2], acc1, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.w), xin[t][3], acc, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.w), xin[t + 1][3], acc1, 0, 0, 0);
+            wa = na; wb = nb;
+        }
+        return acc + acc1;
+    };
+
+    for (int64_t round = blockIdx.x; round < n_rounds; round += gridDim.x) {
+        const int64_t row = round * 64 + wave * 16 + j;
+        const bool valid = row < rows;
+        const int64_t rowc = valid ? row : rows - 1;
+        f32x4 xin[NT], xout[NT];
+        // the lane's 16 bytes of layer l's tile mo: features 16 mo + 4 g .. + 3 of its row
+        auto store_act = [&](int l, int mo, const f32x4& v) {
+            if (valid) *reinterpret_cast<float4*>(acts + ((int64_t)l * rows + row) * H + 16 * mo + 4 * g) = float4{v[0], v[1], v[2], v[3]};
+        };
+
+        float xr[kPgMaxIn / 4];
+#pragma unroll
+        for (int s = 0; s < kPgMaxIn / 4; ++s) {
+            const int k = 4 * s + g;
+            const bool in = k < S;
+            const float v = a.x[rowc * S + (in ? k : 0)];
+            xr[s] = in ? v : 0.f;
+        }
+#pragma unroll
+        for (int mo = 0; mo < NT; ++mo) {
+            const float4 b4 = pg_lds_f4(bias_s + 16 * mo + 4 * g);
+            f32x4 acc = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+            for (int s = 0; s < kPgMaxIn / 4; ++s)
+                if (s < K4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pg_lds_f(w0_s + (mo * K4 + s) * 64 + lane), xr[s], acc, 0, 0, 0);
+            act4(acc);
+            xin[mo] = acc;
+            store_act(0, mo, acc);
+        }
+        for (int l = 1; l <= n_hh; ++l) {
+            const float* bias_l = bias_s + l * H + 4 * g;
+#pragma unroll
+            for (int mo = 0; mo < NT; ++mo) {
+                TG_RING_WAIT(kWait)
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                const uint4* cur = ring + cur_slot * SLOT;
+                cur_slot = (cur_slot + 1 == D) ? 0 : cur_slot + 1;
+                const float4 b4 = pg_lds_f4(bias_l + 16 * mo);
+                f32x4 acc = tile_products(cur, xin, f32x4{b4.x, b4.y, b4.z, b4.w});
+                act4(acc);
+                xout[mo] = acc;
+                store_act(l, mo, acc);
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t) xin[t] = xout[t];
+        }
+        auto head_out = [&](int k) {
+            float s = 0.f;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const float4 w = pg_lds_f4(wh_s + k * H + 16 * t + 4 * g);
+                s = fmaf(xin[t][0], w.x, s);
+                s = fmaf(xin[t][1], w.y, s);
+                s = fmaf(xin[t][2], w.z, s);
+                s = fmaf(xin[t][3], w.w, s);
+            }
+            const float p1 = __shfl_xor(s, 16, 64);
+            const float pair = (g & 1) ? p1 + s : s + p1;
+            const float p2 = __shfl_xor(pair, 32, 64);
+            return ((g & 2) ? p2 + pair : pair + p2) + pg_lds_f(bh_s + k);
+        };
+        const int A = critic ? 1 : a.act_dim;
+        float mu_k[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < A) mu_k[k] = head_out(k);
+        const bool store = valid && g == 0;
+        if (critic) {
+            if (store) a.value[row] = mu_k[0];
+            continue;
+        }
+        // ---- the actor's epilogue on the GIVEN action: eps = (a - mu) / exp(log_std), then act()'s expression term by term ----
+        float logp = 0.f, ent = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < A) {
+                const float ls = a.log_std[k];
+                const float av = a.action[rowc * A + k];
+                const float e = rn_div(rn_sub(av, mu_k[k]), expf(ls));
+                const float lp = rn_sub(rn_sub(rn_mul(-0.5f, rn_mul(e, e)), ls), 0.91893853320467274f);
+                logp = rn_add(logp, lp);
+                ent = rn_add(ent, rn_add(ls, 1.4189385332046727f));
+                if (store) a.mu[row * A + k] = mu_k[k];
+            }
+        }
+        if (store) {
+            a.logp[row] = logp;
+            a.entropy[row] = ent;
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// ---- 2. backward data ----------------------------------------------------------------------------------------------------------------
+template <int H, int kAct>
+__device__ __attribute__((always_inline)) static inline void pg_backward(const PgArgs& a, const int nh, const int O, const int role,
+                                                                         uint4* lds) {
+    // a 16-output-row block of W_l: four 4-row groups of 4 H floats (H / 64 DMA pieces each), 16 floats of padding behind each
+    constexpr int NT = H / 16, WPW = kPgWaves, D = kPgD, P = kPgP, PPG = H / 64, GROUP = 4 * H + 16, SLOT = 4 * GROUP;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 15, g = lane >> 4;
+    const int n_hh = nh - 1;
+    const bool critic = role == 1;
+    float* ring = reinterpret_cast<float*>(lds);
+    float* wh_s = ring + D * SLOT;                                    // [O][H]
+    const int64_t rows = a.rows;
+    const int64_t n_rounds = (rows + 63) / 64;
+    const float* acts = critic ? a.acts[1] : a.acts[0];
+    float* dzb = critic ? a.dz[1] : a.dz[0];
+    float* doutb = critic ? a.dout[1] : a.dout[0];
+
+    // ---- the ring: block (l, t) = rows 16 t .. + 15 of W_l, l from the top H x H layer down to layer 1 ----
+    int pre_l = n_hh, pre_t = 0, pre_slot = 0, cur_slot = 0;
+    auto dma_next = [&]() {
+        const float* src = pg_weight(a, critic, pre_l) + (16 * pre_t * H + 4 * lane);
+        float* slot = ring + pre_slot * SLOT;
+#pragma unroll
+        for (int q = 0; q < NT / WPW; ++q) {
+            const int piece = q * WPW + wave;
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(src + 256 * piece),
+                                             (lds_void*)(slot + (piece / PPG) * GROUP + (piece % PPG) * 256), 16, 0, 0);
+        }
+        pre_t = (pre_t + 1 == NT) ? 0 : pre_t + 1;
+        pre_l = pre_t != 0 ? pre_l : (pre_l == 1 ? n_hh : pre_l - 1);
+        pre_slot = (pre_slot + 1 == D) ? 0 : pre_slot + 1;
+    };
+    if (n_hh > 0) {
+#pragma unroll
+        for (int b = 0; b < P; ++b) dma_next();
+    }
+    {
+        const float* Wh = pg_weight(a, critic, nh);
+        for (int q = tid; q < O * H; q += 64 * WPW) wh_s[q] = Wh[q];
+    }
+    __syncthreads();                                                  // (the head; drains the prologue's DMA too: once)
+    constexpr int kWait = (P - 1) * (NT / WPW);
+
+    for (int64_t round = blockIdx.x; round < n_rounds; round += gridDim.x) {
+        const int64_t row = round * 64 + wave * 16 + j;
+        const bool valid = row < rows;
+        const int64_t rowc = valid ? row : rows - 1;
+        // ---- the head's gradient, per row (every lane group holds the same bits, lane group 0 stores) ----
+        float d_out[4] = {0.f, 0.f, 0.f, 0.f}, d_std[4] = {0.f, 0.f, 0.f, 0.f};
+        if (critic) {
+            d_out[0] = a.g_value[rowc];
+        } else {
+            const float gl = a.g_logp[rowc], ge = a.g_entropy[rowc];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (k < a.act_dim) {
+                    const float inv = expf(-a.log_std[k]);
+                    const float e = (a.action[rowc * a.act_dim + k] - a.mu[rowc * a.act_dim + k]) * inv;
+                    d_out[k] = gl * e * inv;
+                    d_std[k] = fmaf(gl, fmaf(e, e, -1.0f), ge);
+                }
+            }
+        }
+        if (valid && g == 0) {
+            *reinterpret_cast<float4*>(doutb + row * 4) = float4{d_out[0], d_out[1], d_out[2], d_out[3]};
+            if (!critic) *reinterpret_cast<float4*>(a.std_rows + row * 4) = float4{d_std[0], d_std[1], d_std[2], d_std[3]};
+        }
+        // dZ_l = dA * act'(acts[l]) from the stored activation, kept as the next product's B operand and stored [m][H]
+        f32x4 dz[NT];
+        auto mask_store = [&](int l, const f32x4 (&dA)[NT]) {
+            const int64_t at = ((int64_t)l * rows + rowc) * H + 4 * g;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const float4 av = *reinterpret_cast<const float4*>(acts + at + 16 * t);
+                const float h[4] = {av.x, av.y, av.z, av.w};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if constexpr (kAct == TG_ACT_TANH) dz[t][r] = dA[t][r] * fmaf(-h[r], h[r], 1.0f);
+                    else dz[t][r] = h[r] > 0.f ? dA[t][r] : 0.f;
+                }
+                if (valid) *reinterpret_cast<float4*>(dzb + at + 16 * t) = float4{dz[t][0], dz[t][1], dz[t][2], dz[t][3]};
+            }
+        };
+        // ---- dA_top = d_out . W_head on the vector unit ----
+        f32x4 acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < kPgMaxOut; ++k) {
+                if (k < O) {
+                    const float4 w = pg_lds_f4(wh_s + k * H + 16 * t + 4 * g);
+                    acc[t][0] = fmaf(d_out[k], w.x, acc[t][0]);
+                    acc[t][1] = fmaf(d_out[k], w.y, acc[t][1]);
+                    acc[t][2] = fmaf(d_out[k], w.z, acc[t][2]);
+                    acc[t][3] = fmaf(d_out[k], w.w, acc[t][3]);
+                }
+            }
+        }
+        mask_store(n_hh, acc);
+        // ---- H x H layers from the top down: dA_{l-1}[row][16 ti + ii] = sum_o dZ_l[row][o] W_l[o][16 ti + ii] ----
+        for (int l = n_hh; l >= 1; --l) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                TG_RING_WAIT(kWait)
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                const float* __restrict__ p = ring + cur_slot * SLOT + g * GROUP + j;
+                cur_slot = (cur_slot + 1 == D) ? 0 : cur_slot + 1;
+                dma_next();                                           // (refills the slot of the block before this one)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+#pragma unroll
+                    for (int ti = 0; ti < NT; ++ti)
+                        acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(pg_lds_f(p + r * H + 16 * ti), dz[t][r], acc[ti], 0, 0, 0);
+                }
+            }
+            mask_store(l - 1, acc);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+__global__ __launch_bounds__(64 * kPgWaves, 2) void policy_eval_forward_kernel(PgArgs a) {
+    extern __shared__ uint4 lds[];
+    const int role = __builtin_amdgcn_readfirstlane((int)blockIdx.y);
+    const bool critic = role == 1;
+    const int S = critic ? a.net[1].S : a.net[0].S, H = critic ? a.net[1].H : a.net[0].H, nh = critic ? a.net[1].nh : a.net[0].nh;
+    const int O = critic ? a.net[1].O : a.net[0].O, act = critic ? a.net[1].act : a.net[0].act;
+    const bool tanh_net = act == TG_ACT_TANH;
+    if (H == 64) {
+        if (tanh_net) pg_forward<64, TG_ACT_TANH>(a, S, nh, O, role, lds); else pg_forward<64, TG_ACT_RELU>(a, S, nh, O, role, lds);
+    } else if (H == 128) {
+        if (tanh_net) pg_forward<128, TG_ACT_TANH>(a, S, nh, O, role, lds); else pg_forward<128, TG_ACT_RELU>(a, S, nh, O, role, lds);
+    } else {
+        if (tanh_net) pg_forward<256, TG_ACT_TANH>(a, S, nh, O, role, lds); else pg_forward<256, TG_ACT_RELU>(a, S, nh, O, role, lds);
+    }
+}
+
+__global__ __launch_bounds__(64 * kPgWaves, 2) void policy_eval_backward_kernel(PgArgs a) {
+    extern __shared__ uint4 lds[];
+    const int role = __builtin_amdgcn_readfirstlane((int)blockIdx.y);
+    const bool critic = role == 1;
+    const int H = critic ? a.net[1].H : a.net[0].H, nh = critic ? a.net[1].nh : a.net[0].nh;
+    const int O = critic ? a.net[1].O : a.net[0].O, act = critic ? a.net[1].act : a.net[0].act;
+    const bool tanh_net = act == TG_ACT_TANH;
+    if (H == 64) {
+        if (tanh_net) pg_backward<64, TG_ACT_TANH>(a, nh, O, role, lds); else pg_backward<64, TG_ACT_RELU>(a, nh, O, role, lds);
+    } else if (H == 128) {
+        if (tanh_net) pg_backward<128, TG_ACT_TANH>(a, nh, O, role, lds); else pg_backward<128, TG_ACT_RELU>(a, nh, O, role, lds);
+    } else {
+        if (tanh_net) pg_backward<256, TG_ACT_TANH>(a, nh, O, role, lds); else pg_backward<256, TG_ACT_RELU>(a, nh, O, role, lds);
+    }
+}
+
+// ---- 3. weight gradient --------------------------------------------------------------------------------------------------------------
+// One Linear layer of one net: dW [No][Ni] = dz^T a over the rows, db [No] = column sums of dz.  `w_dz` / `w_a`: the operands' stored
+// widths (the head's d_out rows are zero-padded to 4); `vec_*`: 16-byte loads (an aligned base, a leading dimension and a width that
+// are multiples of 4), else floats one by one (the observations).
+struct PgJob {
+    const float* dz; const float* a;
+    float* gw; float* gb;
+    int32_t ld_dz, w_dz, ld_a, w_a, No, Ni, tiles_i, tile_base, vec_dz, vec_a;
+};
+struct PgDwArgs {
+    PgJob job[kPgJobs];
+    int32_t n_jobs, n_slabs;
+    int64_t rows, slab_rows;
+    float* partials;                // [tiles][n_slabs][kPgPartial]
+};
+
+__device__ static inline int pg_job_of(const PgDwArgs& a, int tile) {
+    int jb = 0;
+    for (int q = 1; q < kPgJobs; ++q) jb = (q < a.n_jobs && tile >= a.job[q].tile_base) ? q : jb;
+    return jb;
+}
+
+// 64 rows x 64 columns of a row-major operand into LDS (row stride kPgLd), zeros past the rows and past the width
+__device__ static inline void pg_stage(float* __restrict__ dst, const float* __restrict__ src, int64_t ld, int width, bool vec, int64_t r0,
+                                       int64_t r_end, int col0, int tid) {
+#pragma unroll
+    for (int q = tid; q < kPgTile * kPgTile / 4; q += 64 * kPgWaves) {
+        const int rr = q >> 4, c = col0 + 4 * (q & 15);
+        const int64_t row = r0 + rr;
+        float4 v = {0.f, 0.f, 0.f, 0.f};
+        if (vec) {
+            const bool ok = row < r_end && c < width;
+            const float4 t = *reinterpret_cast<const float4*>(src + (ok ? row * ld + c : 0));
+            v = float4{ok ? t.x : 0.f, ok ? t.y : 0.f, ok ? t.z : 0.f, ok ? t.w : 0.f};
+        } else {
+            auto one = [&](int k) {                                   // (clamped address, selected value: no load under a branch)
+                const bool ok = row < r_end && c + k < width;
+                const float t = src[ok ? row * ld + c + k : 0];
+                return ok ? t : 0.f;
+            };
+            v = float4{one(0), one(1), one(2), one(3)};
+        }
+        *reinterpret_cast<float4*>(dst + rr * kPgLd + 4 * (q & 15)) = v;
+    }
+}
+
+__global__ __launch_bounds__(64 * kPgWaves) void policy_eval_weight_grad_kernel(PgDwArgs a) {
+    __shared__ float dz_s[kPgTile * kPgLd];
+    __shared__ float a_s[kPgTile * kPgLd];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 15, g = lane >> 4;
+    const int tile = blockIdx.x, slab = blockIdx.y;
+    const PgJob& jb = a.job[pg_job_of(a, tile)];
+    const int local = tile - jb.tile_base, to = local / jb.tiles_i, ti0 = local - to * jb.tiles_i;
+    const int64_t r_begin = (int64_t)slab * a.slab_rows;
+    const int64_t r_end = r_begin + a.slab_rows < a.rows ? r_begin + a.slab_rows : a.rows;
+    const bool with_bias = ti0 == 0;
+
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum = 0.f;                                                 // column tid & 63 of dz over rows 16 (tid >> 6) .. + 15 of every chunk
+    for (int64_t r0 = r_begin; r0 < r_end; r0 += kPgTile) {
+        __syncthreads();                                              // (everyone has finished with the chunk before)
+        pg_stage(dz_s, jb.dz, jb.ld_dz, jb.w_dz, jb.vec_dz != 0, r0, r_end, kPgTile * to, tid);
+        pg_stage(a_s, jb.a, jb.ld_a, jb.w_a, jb.vec_a != 0, r0, r_end, kPgTile * ti0, tid);
+        __syncthreads();
+        // lane (i, g) of step s: dz[4 s + g][16 wave + i] and a[4 s + g][16 t + i]
+        const float* __restrict__ pa = dz_s + g * kPgLd + 16 * wave + i;
+        const float* __restrict__ pb = a_s + g * kPgLd + i;
+#pragma unroll
+        for (int s = 0; s < kPgTile / 4; ++s) {
+            const float av = pa[4 * s * kPgLd];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, pb[4 * s * kPgLd + 16 * t], acc[t], 0, 0, 0);
+        }
+        if (with_bias) {
+            const float* __restrict__ pc = dz_s + 16 * (tid >> 6) * kPgLd + (tid & 63);
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) bsum += pc[rr * kPgLd];
+        }
+    }
+    // the partial: lane (i, g) register r of tile t is dW[16 wave + 4 g + r][16 t + i] of the 64 x 64 tile
+    float* part = a.partials + ((int64_t)tile * a.n_slabs + slab) * kPgPartial;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[(16 * wave + 4 * g + r) * kPgTile + 16 * t + i] = acc[t][r];
+    }
+    if (with_bias) {
+        __syncthreads();
+        dz_s[tid] = bsum;
+        __syncthreads();
+        if (tid < kPgTile) part[kPgTile * kPgTile + tid] = (dz_s[tid] + dz_s[64 + tid]) + (dz_s[128 + tid] + dz_s[192 + tid]);
+    }
+}
+
+// the slabs of a tile added in index order, written where torch keeps the gradient
+__global__ __launch_bounds__(256) void policy_eval_weight_grad_finish_kernel(PgDwArgs a) {
+    const int tile = blockIdx.x;
+    const PgJob& jb = a.job[pg_job_of(a, tile)];
+    const int local = tile - jb.tile_base, to = local / jb.tiles_i, ti0 = local - to * jb.tiles_i;
+    const float* part = a.partials + (int64_t)tile * a.n_slabs * kPgPartial;
+    for (int e = threadIdx.x; e < kPgPartial; e += 256) {
+        if (e >= kPgTile * kPgTile && ti0 != 0) break;
+        float s = 0.f;
+        for (int q = 0; q < a.n_slabs; ++q) s += part[(int64_t)q * kPgPartial + e];
+        if (e < kPgTile * kPgTile) {
+            const int o = kPgTile * to + e / kPgTile, c = kPgTile * ti0 + e % kPgTile;
+            if (o < jb.No && c < jb.Ni) jb.gw[(int64_t)o * jb.Ni + c] = s;
+        } else {
+            const int o = kPgTile * to + e - kPgTile * kPgTile;
+            if (o < jb.No) jb.gb[o] = s;
+        }
+    }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------------
+// what the entries refuse about a net; `outs`: the head outputs expected; `pointers`: the launches (the workspace entry reads widths)
+static int pg_fill_net(const char* who, const char* name, const tg_policy_net* n, int outs, bool pointers, PgNet& out) {
+    TG_REQUIRE(n != nullptr, "%s: the %s table is null", who, name);
+    TG_REQUIRE(n->n_layers >= 2 && n->n_layers <= kPgLinear, "%s: %s has %d Linear layers, outside 2..%d (1..%d hidden layers)", who, name,
+               n->n_layers, kPgLinear, kPgLinear - 1);
+    TG_REQUIRE(n->activation == TG_ACT_RELU || n->activation == TG_ACT_TANH, "%s: %s has an unknown hidden activation %d", who, name,
+               n->activation);
+    const int L = n->n_layers, S = n->in_dim[0], H = n->out_dim[0], O = n->out_dim[L - 1];
+    TG_REQUIRE(S >= 1 && S <= kPgMaxIn, "%s: %s has input width %d outside [1, %d]", who, name, S, kPgMaxIn);
+    TG_REQUIRE(H == 64 || H == 128 || H == 256, "%s: %s has hidden width %d (64, 128 or 256)", who, name, H);
+    for (int l = 0; l < L; ++l) {
+        TG_REQUIRE((l == 0 || n->in_dim[l] == H) && (l == L - 1 || n->out_dim[l] == H), "%s: %s layer %d is %d -> %d, hidden width %d", who,
+                   name, l, n->in_dim[l], n->out_dim[l], H);
+        if (pointers) {
+            TG_REQUIRE(n->w[l] && n->b[l], "%s: %s layer %d has a null weight or bias", who, name, l);
+            const uintptr_t mask = (l > 0 && l < L - 1) ? 15 : 3;     // (the H x H layers are read 16 bytes at a time)
+            TG_REQUIRE(((uintptr_t)n->w[l] & mask) == 0 && ((uintptr_t)n->b[l] & 3) == 0,
+                       "%s: %s layer %d has a misaligned weight or bias pointer", who, name, l);
+        }
+        out.w[l] = n->w[l];
+        out.b[l] = n->b[l];
+    }
+    for (int l = L; l < kPgLinear; ++l) { out.w[l] = n->w[0]; out.b[l] = n->b[0]; }
+    TG_REQUIRE(O == outs, "%s: %s has %d head outputs, %d expected", who, name, O, outs);
+    out.S = S; out.H = H; out.nh = L - 1; out.O = O; out.act = n->activation;
+    const size_t fwd = pg_fwd_lds_bytes(out), bwd = pg_bwd_lds_bytes(out);
+    TG_REQUIRE(fwd <= 160 * 1024 && bwd <= 160 * 1024, "%s: %s needs %zu B (forward) / %zu B (backward) of LDS (> 160 KiB)", who, name, fwd, bwd);
+    return TG_OK;
+}
+
+static int64_t pg_grad_floats(const PgNet& n) {
+    return (int64_t)n.H * (n.S + 1) + (int64_t)(n.nh - 1) * n.H * (n.H + 1) + (int64_t)n.O * (n.H + 1);
+}
+static int64_t pg_tiles(const PgNet& n) {
+    const int64_t th = n.H / kPgTile;
+    return th + (n.nh - 1) * th * th + th;                           // first layer (S <= 32: one column tile), H x H layers, head
+}
+static void pg_slabs(int64_t m, int64_t& slab_rows, int32_t& n_slabs) {
+    const int64_t chunks = ceil_div(m, kPgTile), per = ceil_div(chunks, kPgMaxSlabs);
+    slab_rows = per * kPgTile;
+    n_slabs = (int32_t)ceil_div(chunks, per);
+}
+
+// the nets and the tensors every launch needs; `forward`: the three results too
+static int pg_plan(const char* who, const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, bool forward,
+                   PgArgs& args) {
+    TG_REQUIRE(s != nullptr, "%s: null arguments", who);
+    TG_REQUIRE(s->act_dim >= 1 && s->act_dim <= 4, "%s: act_dim=%d outside [1, 4]", who, s->act_dim);
+    TG_REQUIRE(s->m > 0 && s->m < ((int64_t)1 << 31), "%s: m=%lld outside [1, 2^31)", who, (long long)s->m);
+    if (int rc = pg_fill_net(who, "the actor", actor, s->act_dim, true, args.net[0])) return rc;
+    if (critic != nullptr) {
+        if (int rc = pg_fill_net(who, "the critic", critic, 1, true, args.net[1])) return rc;
+        TG_REQUIRE(args.net[1].S == args.net[0].S, "%s: the critic reads %d inputs, the actor %d", who, args.net[1].S, args.net[0].S);
+        TG_REQUIRE((s->d_value || !forward) && s->d_acts_critic, "%s: d_value / d_acts_critic is null with a critic", who);
+    } else {
+        args.net[1] = args.net[0];
+    }
+    TG_REQUIRE(s->d_obs && s->d_act && s->d_log_std && s->d_mu && s->d_acts_actor, "%s: null pointer", who);
+    TG_REQUIRE(!forward || (s->d_logp && s->d_entropy), "%s: d_logp / d_entropy is null", who);
+    TG_REQUIRE((((uintptr_t)s->d_acts_actor | (uintptr_t)s->d_acts_critic) & 15) == 0, "%s: the activations are not 16-B aligned", who);
+    args.act_dim = s->act_dim; args.x = s->d_obs; args.action = s->d_act; args.rows = s->m; args.log_std = s->d_log_std;
+    args.mu = s->d_mu; args.logp = s->d_logp; args.entropy = s->d_entropy; args.value = s->d_value;
+    args.acts[0] = s->d_acts_actor; args.acts[1] = s->d_acts_critic;
+    return TG_OK;
+}
+
+static int pg_plan_backward(const char* who, const tg_policy_net* critic, const tg_policy_eval_args* s, PgArgs& args) {
+    TG_REQUIRE(s->d_g_logp && s->d_g_entropy && s->d_dz_actor && s->d_dout_actor && s->d_std_rows, "%s: null pointer", who);
+    TG_REQUIRE(critic == nullptr || (s->d_g_value && s->d_dz_critic && s->d_dout_critic), "%s: null pointer with a critic", who);
+    TG_REQUIRE((((uintptr_t)s->d_dz_actor | (uintptr_t)s->d_dz_critic | (uintptr_t)s->d_dout_actor | (uintptr_t)s->d_dout_critic |
+                 (uintptr_t)s->d_std_rows) & 15) == 0, "%s: dZ / d_out / the log-std rows are not 16-B aligned", who);
+    args.g_logp = s->d_g_logp; args.g_entropy = s->d_g_entropy; args.g_value = s->d_g_value;
+    args.dz[0] = s->d_dz_actor; args.dz[1] = s->d_dz_critic;
+    args.dout[0] = s->d_dout_actor; args.dout[1] = s->d_dout_critic;
+    args.std_rows = s->d_std_rows;
+    return TG_OK;
+}
+
+template <typename K>
+static int pg_launch(const char* who, K kernel, LdsOptIn& opt_in, const PgArgs& args, int nets, bool backward, int32_t grid_limit,
+                     hipStream_t st) {
+    size_t shmem = 0;
+    for (int r = 0; r < nets; ++r) {
+        const size_t b = backward ? pg_bwd_lds_bytes(args.net[r]) : pg_fwd_lds_bytes(args.net[r]);
+        shmem = b > shmem ? b : shmem;
+    }
+    if (int rc = reserve_dynamic_lds((const void*)kernel, shmem, opt_in, who)) return rc;
+    const int64_t tiles = ceil_div(args.rows, 64);
+    const int64_t cap = grid_limit > 0 ? grid_limit : 2 * device_cus();
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles < cap ? tiles : cap), (unsigned)nets), dim3(64 * kPgWaves), shmem, st, args);
+    TG_LAUNCH_CHECK(who);
+    return TG_OK;
+}
+
+}  // namespace tg
+
+using namespace tg;
+
+extern "C" {
+
+int tg_policy_eval_workspace(const tg_policy_net* actor, const tg_policy_net* critic, int64_t m, int64_t* act_floats, int64_t* grad_floats,
+                             int64_t* partial_floats) {
+    const char* who = "tg_policy_eval_workspace";
+    TG_REQUIRE(actor && act_floats && grad_floats && partial_floats, "%s: null pointer", who);
+    TG_REQUIRE(m > 0 && m < ((int64_t)1 << 31), "%s: m=%lld outside [1, 2^31)", who, (long long)m);
+    const tg_policy_net* nets[2] = {actor, critic};
+    int64_t slab_rows, tiles = 0;
+    int32_t n_slabs;
+    pg_slabs(m, slab_rows, n_slabs);
+    for (int r = 0; r < 2; ++r) {
+        act_floats[r] = grad_floats[r] = 0;
+        if (nets[r] == nullptr) continue;
+        PgNet n = {};
+        const int L = nets[r]->n_layers;                             // (the head's own width here; its range is checked below)
+        const int outs = L >= 1 && L <= kPgLinear ? nets[r]->out_dim[L - 1] : 0;
+        if (int rc = pg_fill_net(who, r ? "the critic" : "the actor", nets[r], outs, false, n)) return rc;
+        TG_REQUIRE(n.O >= 1 && n.O <= (r ? 1 : kPgMaxOut), "%s: %s has %d head outputs (the gaussian head: 1..%d, a critic: 1)", who,
+                   r ? "the critic" : "the actor", n.O, kPgMaxOut);
+        act_floats[r] = (int64_t)n.nh * m * n.H;
+        grad_floats[r] = pg_grad_floats(n);
+        tiles += pg_tiles(n);
+    }
+    *partial_floats = tiles * n_slabs * kPgPartial;
+    return TG_OK;
+}
+
+int tg_policy_eval_forward(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, void* stream) {
+    const char* who = "tg_policy_eval_forward";
+    PgArgs args = {};
+    if (int rc = pg_plan(who, actor, critic, s, true, args)) return rc;
+    static LdsOptIn opt_in;
+    return pg_launch(who, policy_eval_forward_kernel, opt_in, args, critic ? 2 : 1, false, s->grid_limit, (hipStream_t)stream);
+}
+
+int tg_policy_eval_backward(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, void* stream) {
+    const char* who = "tg_policy_eval_backward";
+    PgArgs args = {};
+    if (int rc = pg_plan(who, actor, critic, s, false, args)) return rc;
+    if (int rc = pg_plan_backward(who, critic, s, args)) return rc;
+    static LdsOptIn opt_in;
+    return pg_launch(who, policy_eval_backward_kernel, opt_in, args, critic ? 2 : 1, true, s->grid_limit, (hipStream_t)stream);
+}
+
+int tg_policy_eval_weight_grad(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, void* stream) {
+    const char* who = "tg_policy_eval_weight_grad";
+    PgArgs args = {};
+    if (int rc = pg_plan(who, actor, critic, s, false, args)) return rc;
+    if (int rc = pg_plan_backward(who, critic, s, args)) return rc;
+    TG_REQUIRE(s->d_grad_actor && s->d_partials && (critic == nullptr || s->d_grad_critic), "%s: null gradient or partials pointer", who);
+    PgDwArgs d = {};
+    float* grads[2] = {s->d_grad_actor, s->d_grad_critic};
+    const int64_t m = s->m;
+    int tiles = 0;
+    for (int r = 0; r < (critic ? 2 : 1); ++r) {
+        const PgNet& n = args.net[r];
+        float* gp = grads[r];
+        for (int l = 0; l <= n.nh; ++l) {
+            PgJob& jb = d.job[d.n_jobs++];
+            const bool first = l == 0, head = l == n.nh;
+            jb.dz = head ? args.dout[r] : args.dz[r] + (int64_t)l * m * n.H;
+            jb.ld_dz = jb.w_dz = head ? 4 : n.H;
+            jb.No = head ? n.O : n.H;
+            jb.a = first ? args.x : args.acts[r] + (int64_t)(l - 1) * m * n.H;
+            jb.ld_a = jb.w_a = jb.Ni = first ? n.S : n.H;
+            jb.vec_dz = 1;
+            jb.vec_a = !first || (n.S % 4 == 0 && ((uintptr_t)args.x & 15) == 0);
+            jb.gw = gp; jb.gb = gp + (int64_t)jb.No * jb.Ni;
+            gp = jb.gb + jb.No;
+            jb.tiles_i = (int32_t)ceil_div(jb.Ni, kPgTile);
+            jb.tile_base = tiles;
+            tiles += (int)ceil_div(jb.No, kPgTile) * jb.tiles_i;
+        }
+    }
+    d.rows = m;
+    pg_slabs(m, d.slab_rows, d.n_slabs);
+    d.partials = s->d_partials;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(policy_eval_weight_grad_kernel, dim3((unsigned)tiles, (unsigned)d.n_slabs), dim3(64 * kPgWaves), 0, st, d);
+    TG_LAUNCH_CHECK(who);
+    hipLaunchKernelGGL(policy_eval_weight_grad_finish_kernel, dim3((unsigned)tiles), dim3(256), 0, st, d);
+    TG_LAUNCH_CHECK("tg_policy_eval_weight_grad(finish)");
+    return TG_OK;
+}
+
+}  // extern "C"

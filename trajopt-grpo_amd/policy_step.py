@@ -15,8 +15,12 @@ gives q1, q2 and min(q1, q2) of any rows, and `sac_target(next_obs, reward, disc
 y = reward + discount * (min(Q1', Q2')(s', a') - alpha * logp(a'|s')) with a' drawn by the actor, in ONE launch: a wave runs the
 actor and then both critics on its 16 rows and hands a' over in registers.
 
-Not built: gradients through act(), q_values() or sac_target() (the learner's re-evaluation and the critic / actor updates stay torch
-autograd), bf16, more than 4 actions, LayerNorm or mixed activations, a trunk shared by actor and critic, Q nets whose width or
+`evaluate(obs, action)` is the learner's side under the gaussian head (csrc/policy_grad.hip): log-density, entropy and value of stored
+rows as ONE autograd node over log_std and the nets' own parameters, forward and backward in HIP, so any torch loss of the three
+fills `.grad` and any torch.optim steps the nets.
+
+Not built: gradients to observations or actions, through the squashed head, q_values() or sac_target() (SAC's critic / actor updates
+stay torch autograd), graph capture of evaluate()'s backward, bf16, more than 4 actions, LayerNorm or mixed activations, a trunk shared by actor and critic, Q nets whose width or
 activation differs from the actor's, more than two critics, a target for TD3 / DDPG heads.  There is no silent torch fallback: a net
 outside the kernel's set raises ValueError with supports()'s reason, and the caller's own torch code is the fallback.
 """
@@ -122,6 +126,61 @@ def _q_refusal(actor_net, actor_shape, head, q_nets):
     return None
 
 
+class _Evaluate(torch.autograd.Function):
+    """DeviceActor.evaluate as ONE autograd node over log_std and every weight / bias of both nets (csrc/policy_grad.hip): forward
+    is tg_policy_eval_forward; backward is tg_policy_eval_backward, tg_policy_eval_weight_grad and tg_log_std_grad, and returns the
+    gradients in torch's own shapes (views of one fresh buffer per net), so .grad accumulation, zero_grad, clip_grad_norm_ and any
+    torch.optim work unchanged.  The parameters are saved tensors: torch itself refuses a backward() after an in-place step."""
+
+    @staticmethod
+    def forward(ctx, da, obs, action, log_std, *params):
+        if log_std.dtype != torch.float32 or not log_std.is_contiguous() or log_std.device != da.device:
+            raise ValueError(f"DeviceActor: log_std must be a contiguous float32 tensor on {da.device}")
+        m = obs.shape[0]
+        ws = da._eval_workspace(m)
+        out = [torch.empty(m, dtype=torch.float32, device=da.device) for _ in range(3 if da.critic_net is not None else 2)]
+        s = da._eval_args(ws, obs, action, log_std.detach(), out[0], out[1], out[2] if len(out) == 3 else None)
+        actor, critic, _keep = da._eval_tables()
+        with torch.cuda.device(da.device):
+            N.check(da.lib.tg_policy_eval_forward(actor, critic, C.byref(s), N.stream_ptr(da.device)), "tg_policy_eval_forward")
+        if any(ctx.needs_input_grad):
+            ctx.da, ctx.ws = da, ws
+            ctx.save_for_backward(obs, action, log_std, *params)
+        else:
+            da._eval_pool[m].append(ws)                                        # (no backward will come for it)
+        return tuple(out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *g):
+        from . import hip_ops as K
+        da, ws = ctx.da, ctx.ws
+        if ws is None:
+            raise RuntimeError("DeviceActor: this evaluate() was already backpropagated (its activations are gone)")
+        obs, action, log_std, *params = ctx.saved_tensors
+        m, dev = ws.m, da.device
+        g = [torch.zeros(m, dtype=torch.float32, device=dev) if t is None else t.contiguous() for t in g]
+        s = da._eval_args(ws, obs, action, log_std.detach(), None, None, None)
+        s.d_g_logp, s.d_g_entropy, s.d_g_value = g[0].data_ptr(), g[1].data_ptr(), (g[2].data_ptr() if len(g) == 3 else 0)
+        flat = [torch.empty(k, dtype=torch.float32, device=dev) if k else None for k in ws.grad_floats]
+        s.d_grad_actor, s.d_grad_critic = (N.ptr(t) for t in flat)
+        actor, critic, _keep = da._eval_tables()
+        g_std = torch.zeros(da.A, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            N.check(da.lib.tg_policy_eval_backward(actor, critic, C.byref(s), N.stream_ptr(dev)), "tg_policy_eval_backward")
+            N.check(da.lib.tg_policy_eval_weight_grad(actor, critic, C.byref(s), N.stream_ptr(dev)), "tg_policy_eval_weight_grad")
+            K.log_std_grad(ws.std_rows, da.A, g_std)
+        ctx.ws = None
+        da._eval_pool[m].append(ws)
+        grads, at, net = [], 0, 0
+        for k, p in enumerate(params):                                         # per net: weight [out][in], bias [out], layer by layer
+            if at == flat[net].numel():
+                at, net = 0, net + 1
+            grads.append(flat[net][at:at + p.numel()].view(p.shape))
+            at += p.numel()
+        return (None, None, None, g_std, *grads)
+
+
 class DeviceActor:
     """The policy step for `num_envs` slots on one GPU.
 
@@ -190,7 +249,8 @@ class DeviceActor:
         self._calls = torch.zeros(n, dtype=torch.int32, device=dev)            # (the bits of a u32)
         self._values_out = {}
         self._q_out = {}
-        if len(self.q_nets) == 2:                                              # sac_target's by-products and its owned alpha
+        self._eval_pool = {}                                                   # row count -> free evaluate() workspaces
+        if len(self.q_nets) == 2:                                             # sac_target's by-products and its owned alpha
             self.q1, self.q2, self.qmin, self.y, self._alpha = (torch.zeros(k, dtype=f32, device=dev) for k in (n, n, n, n, 1))
         self._grid_limit = 0           # 0: two workgroups per CU; a test sets it to force further trips of a workgroup's row loop
         s = N.PolicyStepArgs()
@@ -337,6 +397,56 @@ class DeviceActor:
             N.check(self.lib.tg_policy_sac_target(C.byref(actor), C.byref(q[0]), C.byref(q[1]), C.byref(s), N.stream_ptr(self.device)),
                     "tg_policy_sac_target")
         return self.y
+
+    # ---- the learner's re-evaluation: forward and backward in HIP, an ordinary autograd node ----------------------------------------
+    def evaluate(self, obs, action):
+        """-> (logp [m], entropy [m], value [m] or None) of stored rows `obs` [m][S], `action` [m][A] (any m >= 1), each with a grad_fn:
+        any torch loss of the three fills `.grad` of actor_net's, critic_net's parameters and of `log_std` on backward().  logp is
+        act()'s float32 expression with eps = (a - mu) / exp(log_std); entropy = sum_k(log_std_k + 0.5 + 0.5 log 2 pi) for every row
+        (a gradient to log_std alone).  Gradients to obs / action are not built (ValueError if either requires one).  Fresh result
+        tensors at every call.  The stored activations live in a workspace per row count m that this call's backward() consumes
+        and hands back; a second evaluate() of the same m before that backward() owns a fresh workspace (both graphs stay valid)."""
+        if self.head != "gaussian":
+            raise ValueError(f"DeviceActor: the head is {self.head!r}; evaluate() is built for the gaussian head")
+        for t, name in ((obs, "obs"), (action, "action")):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise ValueError(f"DeviceActor: evaluate() builds no gradient to {name} (it requires one)")
+        obs = self._rows(obs, "obs", None)
+        action = self._rows(action, "action", obs.shape[0], self.A)
+        nets = [self.actor_net] + ([self.critic_net] if self.critic_net is not None else [])
+        params = [p for net in nets for m in _modules(net)[0::2] for p in (m.weight, m.bias)]
+        out = _Evaluate.apply(self, obs, action, self.log_std, *params)
+        return (out[0], out[1], out[2] if self.critic_net is not None else None)
+
+    def _eval_workspace(self, m):
+        """A free workspace for m rows (activations, dZ, head gradients, weight-gradient partials) and the gradient sizes."""
+        pool = self._eval_pool.setdefault(m, [])
+        if pool:
+            return pool.pop()
+        acts, grads, partial = (C.c_int64 * 2)(), (C.c_int64 * 2)(), C.c_int64()
+        critic = _widths(self.critic_net) if self.critic_net is not None else None
+        if self.lib.tg_policy_eval_workspace(C.byref(_widths(self.actor_net)), C.byref(critic) if critic is not None else None, m, acts,
+                                             grads, C.byref(partial)):
+            raise ValueError("DeviceActor: evaluate() does not take these nets: " + self.lib.tg_last_error().decode("utf-8", "replace"))
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        ws = types.SimpleNamespace(m=m, grad_floats=tuple(grads), mu=new(m, self.A), std_rows=new(m, 4), partials=new(partial.value),
+                                   acts=[new(k) if k else None for k in acts], dz=[new(k) if k else None for k in acts],
+                                   dout=[new(m, 4) if k else None for k in acts])
+        return ws
+
+    def _eval_args(self, ws, obs, action, log_std, logp, entropy, value):
+        s = N.PolicyEvalArgs()
+        s.d_obs, s.d_act, s.d_log_std, s.m, s.act_dim, s.grid_limit = obs.data_ptr(), action.data_ptr(), log_std.data_ptr(), ws.m, self.A, self._grid_limit
+        s.d_mu, s.d_logp, s.d_entropy, s.d_value, s.d_std_rows, s.d_partials = (N.ptr(t) for t in (ws.mu, logp, entropy, value, ws.std_rows, ws.partials))
+        s.d_acts_actor, s.d_acts_critic = (N.ptr(t) for t in ws.acts)
+        s.d_dz_actor, s.d_dz_critic = (N.ptr(t) for t in ws.dz)
+        s.d_dout_actor, s.d_dout_critic = (N.ptr(t) for t in ws.dout)
+        return s
+
+    def _eval_tables(self):
+        actor = self._table(self.actor_net, "the actor")
+        critic = self._table(self.critic_net, "the critic") if self.critic_net is not None else None
+        return C.byref(actor), (C.byref(critic) if critic is not None else None), (actor, critic)
 
     @property
     def calls(self) -> torch.Tensor:
