@@ -121,6 +121,20 @@ def test_forward_and_gradients_against_fp64(tg, case, m):
     assert_grads(f"{case} m={m}", [p.grad for p in params], gref64, gref32)
 
 
+@pytest.mark.parametrize("m", [70, 130])
+@pytest.mark.parametrize("case", CASES[:2], ids=lambda c: "-".join(map(str, c)))
+def test_mean_and_value_are_the_policy_steps_bit_for_bit(tg, case, m):
+    """The three entries run one definition of the tile forward (csrc/policy_tile.hpp): evaluate()'s mu is the mean of a
+    deterministic act() on the same rows and its value is values()', bit for bit.  (logp divides by exp(log_std): no identity.)"""
+    actor, critic, log_std, obs, action, _, _ = on_device(case, m)
+    da = tg.DeviceActor(actor, critic, num_envs=m, log_std=log_std, device=DEV)
+    da._grid_limit = 2 if m == 130 else 0
+    da.act(obs, deterministic=True)
+    logp, _, value = da.evaluate(obs, action)
+    assert torch.equal(logp.grad_fn.ws.mu, da.mean)                   # (the node's workspace holds mu for its backward)
+    assert torch.equal(value.detach(), da.values(obs))
+
+
 def test_two_rounds_are_bit_identical_and_a_second_backward_accumulates(tg):
     case, m = CASES[1], 130
     rounds = []

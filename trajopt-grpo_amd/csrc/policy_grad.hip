@@ -2,10 +2,10 @@
 // forward and backward in float32 on v_mfma_f32_16x16x4_f32, against torch's own row-major `nn.Linear` storage -- weights are READ
 // where torch keeps them and gradients are WRITTEN in torch's [out][in] / [out] layout.  Three launches:
 //
-//   tg_policy_eval_forward      policy_step.hip's machine (a wave owns 16 rows, 4 waves per workgroup, the net as grid dimension y, a
-//                               3-slot LDS-DMA ring of 16-output-row weight blocks) with two differences: every hidden layer's 16 x H
-//                               post-activation tile goes to acts[l][m][H] (lane (j, g)'s registers r = 0..3 of tile t are features
-//                               16 t + 4 g + r of row j: one 16-byte store), and the epilogue takes the action from memory.  No Philox.
+//   tg_policy_eval_forward      policy_tile.hpp's forward as policy_step.hip runs it (a wave owns 16 rows, 4 waves per workgroup, the
+//                               net as grid dimension y) with two differences: every hidden layer's 16 x H post-activation tile goes
+//                               to acts[l][m][H] (lane (j, g)'s registers r = 0..3 of tile t are features 16 t + 4 g + r of row j:
+//                               one 16-byte store), and the epilogue takes the action from memory.  No Philox.
 //   tg_policy_eval_backward     backward data on the same split.  Head gradient and dA_top = d_out . W_head on the vector unit, then per
 //                               H x H layer from the top: dZ_l = dA_l * act'(acts[l]) (stored [m][H]), dA_{l-1} = dZ_l . W_l on MFMAs.
 //   tg_policy_eval_weight_grad  dW_l = dZ_l^T A_{l-1}, db_l = column sums of dZ_l, for every layer of both nets in one launch, and a
@@ -33,29 +33,18 @@
 #include <stdlib.h>
 
 #include "tg_common.hpp"
-#include "mfma_ring.hpp"
-#include "act_f32.hpp"
+#include "policy_tile.hpp"
 
 namespace tg {
 
-constexpr int kPgLinear = TG_POLICY_MAX_LAYERS;
-constexpr int kPgWaves = 4;
-constexpr int kPgD = 3, kPgP = kPgD - 1;                // ring slots, blocks in flight
 constexpr int kPgMaxOut = 4;                            // gaussian head: <= 4 means; a critic: 1
-constexpr int kPgMaxIn = 32;
 constexpr int kPgMaxSlabs = 32;
 constexpr int kPgTile = 64, kPgLd = 80;                 // weight gradient: tile edge, LDS row stride (floats)
 constexpr int kPgPartial = kPgTile * kPgTile + kPgTile; // floats of one partial: the tile and its bias sums
-constexpr int kPgJobs = 2 * kPgLinear;
-
-struct PgNet {
-    const float* w[kPgLinear];
-    const float* b[kPgLinear];
-    int32_t S, H, nh, O, act;                           // input width, hidden width, hidden layers, head outputs, TG_ACT_*
-};
+constexpr int kPgJobs = 2 * kPolicyLinear;
 
 struct PgArgs {
-    PgNet net[2];                   // [0] the actor, [1] the critic
+    PolicyNet net[2];               // [0] the actor, [1] the critic
     int32_t act_dim;
     const float* x;                 // [rows][S], unpadded
     const float* action;            // [rows][A]
@@ -69,59 +58,28 @@ struct PgArgs {
     float* std_rows;                // [rows][4], zero-padded
 };
 
-__device__ static inline uint4 pg_lds_u4(const uint4* __restrict__ p) { return *p; }
-__device__ static inline float4 pg_lds_f4(const float* __restrict__ p) { return *reinterpret_cast<const float4*>(p); }
-__device__ static inline float pg_lds_f(const float* __restrict__ p) { return *p; }
-
-static size_t pg_fwd_lds_bytes(const PgNet& n) {
-    const int NT = n.H / 16, K4 = (n.S + 3) / 4;
-    return (size_t)kPgD * NT * 1024 + (size_t)NT * K4 * 256 + (size_t)(n.nh + n.O) * n.H * 4 + 8 * 4;
-}
-static size_t pg_bwd_lds_bytes(const PgNet& n) {
-    return (size_t)kPgD * (16 * n.H + 64) * 4 + (size_t)n.O * n.H * 4;
+static size_t pg_bwd_lds_bytes(const PolicyNet& n) {
+    return (size_t)kTileD * (16 * n.H + 64) * 4 + (size_t)n.O * n.H * 4;
 }
 
-// (uniform selects over the kernel arguments: a run-time index into a local copy of the tables would put it into scratch)
-__device__ static inline const float* pg_weight(const PgArgs& a, bool critic, int l) {
-    const float* r = critic ? a.net[1].w[0] : a.net[0].w[0];
-#pragma unroll
-    for (int q = 1; q < kPgLinear; ++q) r = l == q ? (critic ? a.net[1].w[q] : a.net[0].w[q]) : r;
-    return r;
-}
-__device__ static inline const float* pg_bias(const PgArgs& a, bool critic, int l) {
-    const float* r = critic ? a.net[1].b[0] : a.net[0].b[0];
-#pragma unroll
-    for (int q = 1; q < kPgLinear; ++q) r = l == q ? (critic ? a.net[1].b[q] : a.net[0].b[q]) : r;
-    return r;
-}
-
-// ---- 1. forward: ps_forward (policy_step.hip) + the activation stores + the epilogue on a given action ------------------------------
+// ---- 1. forward: the shared tile forward, the activation stores as its on_tile, the epilogue on a given action ------------------------
 template <int H, int kAct>
 __device__ __attribute__((always_inline)) static inline void pg_forward(const PgArgs& a, const int S, const int nh, const int O,
                                                                         const int role, uint4* lds) {
-    constexpr int NT = H / 16, KS = NT, WPW = kPgWaves, D = kPgD, P = kPgP, SLOT = KS * 64;
+    constexpr int NT = H / 16, D = kTileD, P = kTileP, SLOT = NT * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, g = lane >> 4;
     const int n_hh = nh - 1, K4 = (S + 3) >> 2;
     const bool critic = role == 1;
     uint4* ring = lds;
-    float* w0_s = reinterpret_cast<float*>(ring + D * SLOT);          // [NT][K4][64 lanes]
-    float* bias_s = w0_s + NT * K4 * 64;                              // [nh][H]
-    float* wh_s = bias_s + nh * H;                                    // [O][H]
-    float* bh_s = wh_s + O * H;                                       // [8]
+    const NetTables<H> tb(reinterpret_cast<float*>(ring + D * SLOT), K4, nh, O);
     const int64_t rows = a.rows;
     const int64_t n_rounds = (rows + 63) / 64;
     float* acts = critic ? a.acts[1] : a.acts[0];
 
     int pre_l = 1, pre_mo = 0, pre_slot = 0, cur_slot = 0;
     auto dma_next = [&]() {
-        const float* src = pg_weight(a, critic, pre_l) + ((16 * pre_mo + j) * H + 4 * g);
-        uint4* slot = ring + pre_slot * SLOT;
-#pragma unroll
-        for (int q = 0; q < KS / WPW; ++q) {
-            const int piece = q * WPW + wave;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(src + 16 * piece), (lds_void*)(slot + piece * 64), 16, 0, 0);
-        }
+        ring_dma_rows<NT>(net_weight(a, critic, pre_l) + ((16 * pre_mo + j) * H + 4 * g), ring + pre_slot * SLOT, wave);
         pre_mo = (pre_mo + 1 == NT) ? 0 : pre_mo + 1;
         pre_l = pre_mo != 0 ? pre_l : (pre_l == n_hh ? 1 : pre_l + 1);
         pre_slot = (pre_slot + 1 == D) ? 0 : pre_slot + 1;
@@ -130,122 +88,35 @@ __device__ __attribute__((always_inline)) static inline void pg_forward(const Pg
 #pragma unroll
         for (int b = 0; b < P; ++b) dma_next();
     }
-    const float* w0 = pg_weight(a, critic, 0);
-    for (int q = tid; q < NT * K4 * 64; q += 64 * WPW) {
-        const int ln = q & 63, ps = q >> 6, mo = ps / K4, s = ps - mo * K4;
-        const int k = 4 * s + (ln >> 4);
-        const bool in = k < S;
-        const float v = w0[(16 * mo + (ln & 15)) * S + (in ? k : 0)];
-        w0_s[q] = in ? v : 0.f;
-    }
-    for (int l = 0; l < nh; ++l) {
-        const float* bl = pg_bias(a, critic, l);
-        for (int q = tid; q < H; q += 64 * WPW) bias_s[l * H + q] = bl[q];
-    }
-    {
-        const float* Wh = pg_weight(a, critic, nh);
-        const float* Bh = pg_bias(a, critic, nh);
-        for (int q = tid; q < O * H; q += 64 * WPW) wh_s[q] = Wh[q];
-        const float bv = Bh[tid < O ? tid : 0];
-        if (tid < 8) bh_s[tid] = tid < O ? bv : 0.f;
-    }
+    stage_net_tables<H>(net_weight(a, critic, 0), S, nh, O, [&](int l) { return net_bias(a, critic, l); }, net_weight(a, critic, nh),
+                        net_bias(a, critic, nh), tb.w0, tid);
     __syncthreads();
-    // (the activation stores of a round are issued behind the block a wait names and are not counted: stricter, never weaker)
-    constexpr int kWait = (P - 1) * (KS / WPW);
-
-    auto act4 = [&](f32x4& v) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = act_f32<kAct>(v[r]);
-    };
-    auto tile_products = [&](const uint4* __restrict__ cur, const f32x4 (&xin)[NT], f32x4 acc) {
-        const uint4* __restrict__ p = cur + lane;
-        f32x4 acc1 = {0.f, 0.f, 0.f, 0.f};
-        uint4 wa = pg_lds_u4(p), wb = pg_lds_u4(p + 64);
-        dma_next();
-#pragma unroll
-        for (int t = 0; t < NT; t += 2) {
-            uint4 na = wa, nb = wb;
-            if (t + 2 < NT) { na = pg_lds_u4(p + (t + 2) * 64); nb = pg_lds_u4(p + (t + 3) * 64); }
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.x), xin[t][0], acc, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.x), xin[t + 1][0], acc1, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.y), xin[t][1], acc, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.y), xin[t + 1][1], acc1, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.z), xin[t][2], acc, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.z), xin[t + 1][2], acc1, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.w), xin[t][3], acc, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.w), xin[t + 1][3], acc1, 0, 0, 0);
-            wa = na; wb = nb;
-        }
-        return acc + acc1;
-    };
 
     for (int64_t round = blockIdx.x; round < n_rounds; round += gridDim.x) {
         const int64_t row = round * 64 + wave * 16 + j;
         const bool valid = row < rows;
         const int64_t rowc = valid ? row : rows - 1;
-        f32x4 xin[NT], xout[NT];
+        f32x4 xin[NT];
         // the lane's 16 bytes of layer l's tile mo: features 16 mo + 4 g .. + 3 of its row
         auto store_act = [&](int l, int mo, const f32x4& v) {
             if (valid) *reinterpret_cast<float4*>(acts + ((int64_t)l * rows + row) * H + 16 * mo + 4 * g) = float4{v[0], v[1], v[2], v[3]};
         };
 
-        float xr[kPgMaxIn / 4];
+        float xr[kTileMaxIn / 4];
 #pragma unroll
-        for (int s = 0; s < kPgMaxIn / 4; ++s) {
+        for (int s = 0; s < kTileMaxIn / 4; ++s) {
             const int k = 4 * s + g;
             const bool in = k < S;
             const float v = a.x[rowc * S + (in ? k : 0)];
             xr[s] = in ? v : 0.f;
         }
-#pragma unroll
-        for (int mo = 0; mo < NT; ++mo) {
-            const float4 b4 = pg_lds_f4(bias_s + 16 * mo + 4 * g);
-            f32x4 acc = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-            for (int s = 0; s < kPgMaxIn / 4; ++s)
-                if (s < K4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pg_lds_f(w0_s + (mo * K4 + s) * 64 + lane), xr[s], acc, 0, 0, 0);
-            act4(acc);
-            xin[mo] = acc;
-            store_act(0, mo, acc);
-        }
-        for (int l = 1; l <= n_hh; ++l) {
-            const float* bias_l = bias_s + l * H + 4 * g;
-#pragma unroll
-            for (int mo = 0; mo < NT; ++mo) {
-                TG_RING_WAIT(kWait)
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                const uint4* cur = ring + cur_slot * SLOT;
-                cur_slot = (cur_slot + 1 == D) ? 0 : cur_slot + 1;
-                const float4 b4 = pg_lds_f4(bias_l + 16 * mo);
-                f32x4 acc = tile_products(cur, xin, f32x4{b4.x, b4.y, b4.z, b4.w});
-                act4(acc);
-                xout[mo] = acc;
-                store_act(l, mo, acc);
-            }
-#pragma unroll
-            for (int t = 0; t < NT; ++t) xin[t] = xout[t];
-        }
-        auto head_out = [&](int k) {
-            float s = 0.f;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float4 w = pg_lds_f4(wh_s + k * H + 16 * t + 4 * g);
-                s = fmaf(xin[t][0], w.x, s);
-                s = fmaf(xin[t][1], w.y, s);
-                s = fmaf(xin[t][2], w.z, s);
-                s = fmaf(xin[t][3], w.w, s);
-            }
-            const float p1 = __shfl_xor(s, 16, 64);
-            const float pair = (g & 1) ? p1 + s : s + p1;
-            const float p2 = __shfl_xor(pair, 32, 64);
-            return ((g & 2) ? p2 + pair : pair + p2) + pg_lds_f(bh_s + k);
-        };
+        first_layer<H, kAct>(tb.w0, tb.bias, K4, lane, xr, xin, store_act);
+        hidden_layers<H, kAct>(ring, cur_slot, tb.bias, n_hh, lane, xin, dma_next, store_act);
         const int A = critic ? 1 : a.act_dim;
         float mu_k[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (k < A) mu_k[k] = head_out(k);
+            if (k < A) mu_k[k] = head_out<NT>(tb.wh, tb.bh, xin, k, g);
         const bool store = valid && g == 0;
         if (critic) {
             if (store) a.value[row] = mu_k[0];
@@ -259,8 +130,7 @@ __device__ __attribute__((always_inline)) static inline void pg_forward(const Pg
                 const float ls = a.log_std[k];
                 const float av = a.action[rowc * A + k];
                 const float e = rn_div(rn_sub(av, mu_k[k]), expf(ls));
-                const float lp = rn_sub(rn_sub(rn_mul(-0.5f, rn_mul(e, e)), ls), 0.91893853320467274f);
-                logp = rn_add(logp, lp);
+                logp = rn_add(logp, gaussian_logp_term(e, ls));
                 ent = rn_add(ent, rn_add(ls, 1.4189385332046727f));
                 if (store) a.mu[row * A + k] = mu_k[k];
             }
@@ -278,7 +148,7 @@ template <int H, int kAct>
 __device__ __attribute__((always_inline)) static inline void pg_backward(const PgArgs& a, const int nh, const int O, const int role,
                                                                          uint4* lds) {
     // a 16-output-row block of W_l: four 4-row groups of 4 H floats (H / 64 DMA pieces each), 16 floats of padding behind each
-    constexpr int NT = H / 16, WPW = kPgWaves, D = kPgD, P = kPgP, PPG = H / 64, GROUP = 4 * H + 16, SLOT = 4 * GROUP;
+    constexpr int NT = H / 16, WPW = kTileWaves, D = kTileD, P = kTileP, PPG = H / 64, GROUP = 4 * H + 16, SLOT = 4 * GROUP;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, g = lane >> 4;
     const int n_hh = nh - 1;
@@ -294,7 +164,7 @@ __device__ __attribute__((always_inline)) static inline void pg_backward(const P
     // ---- the ring: block (l, t) = rows 16 t .. + 15 of W_l, l from the top H x H layer down to layer 1 ----
     int pre_l = n_hh, pre_t = 0, pre_slot = 0, cur_slot = 0;
     auto dma_next = [&]() {
-        const float* src = pg_weight(a, critic, pre_l) + (16 * pre_t * H + 4 * lane);
+        const float* src = net_weight(a, critic, pre_l) + (16 * pre_t * H + 4 * lane);
         float* slot = ring + pre_slot * SLOT;
 #pragma unroll
         for (int q = 0; q < NT / WPW; ++q) {
@@ -311,7 +181,7 @@ __device__ __attribute__((always_inline)) static inline void pg_backward(const P
         for (int b = 0; b < P; ++b) dma_next();
     }
     {
-        const float* Wh = pg_weight(a, critic, nh);
+        const float* Wh = net_weight(a, critic, nh);
         for (int q = tid; q < O * H; q += 64 * WPW) wh_s[q] = Wh[q];
     }
     __syncthreads();                                                  // (the head; drains the prologue's DMA too: once)
@@ -365,7 +235,7 @@ __device__ __attribute__((always_inline)) static inline void pg_backward(const P
 #pragma unroll
             for (int k = 0; k < kPgMaxOut; ++k) {
                 if (k < O) {
-                    const float4 w = pg_lds_f4(wh_s + k * H + 16 * t + 4 * g);
+                    const float4 w = lds_f4(wh_s + k * H + 16 * t + 4 * g);
                     acc[t][0] = fmaf(d_out[k], w.x, acc[t][0]);
                     acc[t][1] = fmaf(d_out[k], w.y, acc[t][1]);
                     acc[t][2] = fmaf(d_out[k], w.z, acc[t][2]);
@@ -390,7 +260,7 @@ __device__ __attribute__((always_inline)) static inline void pg_backward(const P
                 for (int r = 0; r < 4; ++r) {
 #pragma unroll
                     for (int ti = 0; ti < NT; ++ti)
-                        acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(pg_lds_f(p + r * H + 16 * ti), dz[t][r], acc[ti], 0, 0, 0);
+                        acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(lds_f(p + r * H + 16 * ti), dz[t][r], acc[ti], 0, 0, 0);
                 }
             }
             mask_store(l - 1, acc);
@@ -399,36 +269,26 @@ __device__ __attribute__((always_inline)) static inline void pg_backward(const P
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-__global__ __launch_bounds__(64 * kPgWaves, 2) void policy_eval_forward_kernel(PgArgs a) {
+__global__ __launch_bounds__(64 * kTileWaves, 2) void policy_eval_forward_kernel(PgArgs a) {
     extern __shared__ uint4 lds[];
     const int role = __builtin_amdgcn_readfirstlane((int)blockIdx.y);
     const bool critic = role == 1;
     const int S = critic ? a.net[1].S : a.net[0].S, H = critic ? a.net[1].H : a.net[0].H, nh = critic ? a.net[1].nh : a.net[0].nh;
     const int O = critic ? a.net[1].O : a.net[0].O, act = critic ? a.net[1].act : a.net[0].act;
-    const bool tanh_net = act == TG_ACT_TANH;
-    if (H == 64) {
-        if (tanh_net) pg_forward<64, TG_ACT_TANH>(a, S, nh, O, role, lds); else pg_forward<64, TG_ACT_RELU>(a, S, nh, O, role, lds);
-    } else if (H == 128) {
-        if (tanh_net) pg_forward<128, TG_ACT_TANH>(a, S, nh, O, role, lds); else pg_forward<128, TG_ACT_RELU>(a, S, nh, O, role, lds);
-    } else {
-        if (tanh_net) pg_forward<256, TG_ACT_TANH>(a, S, nh, O, role, lds); else pg_forward<256, TG_ACT_RELU>(a, S, nh, O, role, lds);
-    }
+    dispatch_width_act(H, act, [&](auto h, auto k) __attribute__((always_inline)) {
+        pg_forward<decltype(h)::value, decltype(k)::value>(a, S, nh, O, role, lds);
+    });
 }
 
-__global__ __launch_bounds__(64 * kPgWaves, 2) void policy_eval_backward_kernel(PgArgs a) {
+__global__ __launch_bounds__(64 * kTileWaves, 2) void policy_eval_backward_kernel(PgArgs a) {
     extern __shared__ uint4 lds[];
     const int role = __builtin_amdgcn_readfirstlane((int)blockIdx.y);
     const bool critic = role == 1;
     const int H = critic ? a.net[1].H : a.net[0].H, nh = critic ? a.net[1].nh : a.net[0].nh;
     const int O = critic ? a.net[1].O : a.net[0].O, act = critic ? a.net[1].act : a.net[0].act;
-    const bool tanh_net = act == TG_ACT_TANH;
-    if (H == 64) {
-        if (tanh_net) pg_backward<64, TG_ACT_TANH>(a, nh, O, role, lds); else pg_backward<64, TG_ACT_RELU>(a, nh, O, role, lds);
-    } else if (H == 128) {
-        if (tanh_net) pg_backward<128, TG_ACT_TANH>(a, nh, O, role, lds); else pg_backward<128, TG_ACT_RELU>(a, nh, O, role, lds);
-    } else {
-        if (tanh_net) pg_backward<256, TG_ACT_TANH>(a, nh, O, role, lds); else pg_backward<256, TG_ACT_RELU>(a, nh, O, role, lds);
-    }
+    dispatch_width_act(H, act, [&](auto h, auto k) __attribute__((always_inline)) {
+        pg_backward<decltype(h)::value, decltype(k)::value>(a, nh, O, role, lds);
+    });
 }
 
 // ---- 3. weight gradient --------------------------------------------------------------------------------------------------------------
@@ -457,7 +317,7 @@ __device__ static inline int pg_job_of(const PgDwArgs& a, int tile) {
 __device__ static inline void pg_stage(float* __restrict__ dst, const float* __restrict__ src, int64_t ld, int width, bool vec, int64_t r0,
                                        int64_t r_end, int col0, int tid) {
 #pragma unroll
-    for (int q = tid; q < kPgTile * kPgTile / 4; q += 64 * kPgWaves) {
+    for (int q = tid; q < kPgTile * kPgTile / 4; q += 64 * kTileWaves) {
         const int rr = q >> 4, c = col0 + 4 * (q & 15);
         const int64_t row = r0 + rr;
         float4 v = {0.f, 0.f, 0.f, 0.f};
@@ -477,7 +337,7 @@ __device__ static inline void pg_stage(float* __restrict__ dst, const float* __r
     }
 }
 
-__global__ __launch_bounds__(64 * kPgWaves) void policy_eval_weight_grad_kernel(PgDwArgs a) {
+__global__ __launch_bounds__(64 * kTileWaves) void policy_eval_weight_grad_kernel(PgDwArgs a) {
     __shared__ float dz_s[kPgTile * kPgLd];
     __shared__ float a_s[kPgTile * kPgLd];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -549,40 +409,18 @@ __global__ __launch_bounds__(256) void policy_eval_weight_grad_finish_kernel(PgD
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-// what the entries refuse about a net; `outs`: the head outputs expected; `pointers`: the launches (the workspace entry reads widths)
-static int pg_fill_net(const char* who, const char* name, const tg_policy_net* n, int outs, bool pointers, PgNet& out) {
-    TG_REQUIRE(n != nullptr, "%s: the %s table is null", who, name);
-    TG_REQUIRE(n->n_layers >= 2 && n->n_layers <= kPgLinear, "%s: %s has %d Linear layers, outside 2..%d (1..%d hidden layers)", who, name,
-               n->n_layers, kPgLinear, kPgLinear - 1);
-    TG_REQUIRE(n->activation == TG_ACT_RELU || n->activation == TG_ACT_TANH, "%s: %s has an unknown hidden activation %d", who, name,
-               n->activation);
-    const int L = n->n_layers, S = n->in_dim[0], H = n->out_dim[0], O = n->out_dim[L - 1];
-    TG_REQUIRE(S >= 1 && S <= kPgMaxIn, "%s: %s has input width %d outside [1, %d]", who, name, S, kPgMaxIn);
-    TG_REQUIRE(H == 64 || H == 128 || H == 256, "%s: %s has hidden width %d (64, 128 or 256)", who, name, H);
-    for (int l = 0; l < L; ++l) {
-        TG_REQUIRE((l == 0 || n->in_dim[l] == H) && (l == L - 1 || n->out_dim[l] == H), "%s: %s layer %d is %d -> %d, hidden width %d", who,
-                   name, l, n->in_dim[l], n->out_dim[l], H);
-        if (pointers) {
-            TG_REQUIRE(n->w[l] && n->b[l], "%s: %s layer %d has a null weight or bias", who, name, l);
-            const uintptr_t mask = (l > 0 && l < L - 1) ? 15 : 3;     // (the H x H layers are read 16 bytes at a time)
-            TG_REQUIRE(((uintptr_t)n->w[l] & mask) == 0 && ((uintptr_t)n->b[l] & 3) == 0,
-                       "%s: %s layer %d has a misaligned weight or bias pointer", who, name, l);
-        }
-        out.w[l] = n->w[l];
-        out.b[l] = n->b[l];
-    }
-    for (int l = L; l < kPgLinear; ++l) { out.w[l] = n->w[0]; out.b[l] = n->b[0]; }
-    TG_REQUIRE(O == outs, "%s: %s has %d head outputs, %d expected", who, name, O, outs);
-    out.S = S; out.H = H; out.nh = L - 1; out.O = O; out.act = n->activation;
-    const size_t fwd = pg_fwd_lds_bytes(out), bwd = pg_bwd_lds_bytes(out);
+// the shared verdict on a net, and whether both passes fit; `pointers`: the launches (the workspace entry reads widths)
+static int pg_fill_net(const char* who, const char* name, const tg_policy_net* n, int outs, bool pointers, PolicyNet& out) {
+    if (int rc = policy_net_check(who, name, n, outs, pointers, out)) return rc;
+    const size_t fwd = ring_tables_lds_bytes(out), bwd = pg_bwd_lds_bytes(out);
     TG_REQUIRE(fwd <= 160 * 1024 && bwd <= 160 * 1024, "%s: %s needs %zu B (forward) / %zu B (backward) of LDS (> 160 KiB)", who, name, fwd, bwd);
     return TG_OK;
 }
 
-static int64_t pg_grad_floats(const PgNet& n) {
+static int64_t pg_grad_floats(const PolicyNet& n) {
     return (int64_t)n.H * (n.S + 1) + (int64_t)(n.nh - 1) * n.H * (n.H + 1) + (int64_t)n.O * (n.H + 1);
 }
-static int64_t pg_tiles(const PgNet& n) {
+static int64_t pg_tiles(const PolicyNet& n) {
     const int64_t th = n.H / kPgTile;
     return th + (n.nh - 1) * th * th + th;                           // first layer (S <= 32: one column tile), H x H layers, head
 }
@@ -632,15 +470,10 @@ static int pg_launch(const char* who, K kernel, LdsOptIn& opt_in, const PgArgs& 
                      hipStream_t st) {
     size_t shmem = 0;
     for (int r = 0; r < nets; ++r) {
-        const size_t b = backward ? pg_bwd_lds_bytes(args.net[r]) : pg_fwd_lds_bytes(args.net[r]);
+        const size_t b = backward ? pg_bwd_lds_bytes(args.net[r]) : ring_tables_lds_bytes(args.net[r]);
         shmem = b > shmem ? b : shmem;
     }
-    if (int rc = reserve_dynamic_lds((const void*)kernel, shmem, opt_in, who)) return rc;
-    const int64_t tiles = ceil_div(args.rows, 64);
-    const int64_t cap = grid_limit > 0 ? grid_limit : 2 * device_cus();
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles < cap ? tiles : cap), (unsigned)nets), dim3(64 * kPgWaves), shmem, st, args);
-    TG_LAUNCH_CHECK(who);
-    return TG_OK;
+    return launch_row_tiles(who, kernel, opt_in, args, nets, shmem, grid_limit, 2, st);
 }
 
 }  // namespace tg
@@ -661,9 +494,9 @@ int tg_policy_eval_workspace(const tg_policy_net* actor, const tg_policy_net* cr
     for (int r = 0; r < 2; ++r) {
         act_floats[r] = grad_floats[r] = 0;
         if (nets[r] == nullptr) continue;
-        PgNet n = {};
+        PolicyNet n = {};
         const int L = nets[r]->n_layers;                             // (the head's own width here; its range is checked below)
-        const int outs = L >= 1 && L <= kPgLinear ? nets[r]->out_dim[L - 1] : 0;
+        const int outs = L >= 1 && L <= kPolicyLinear ? nets[r]->out_dim[L - 1] : 0;
         if (int rc = pg_fill_net(who, r ? "the critic" : "the actor", nets[r], outs, false, n)) return rc;
         TG_REQUIRE(n.O >= 1 && n.O <= (r ? 1 : kPgMaxOut), "%s: %s has %d head outputs (the gaussian head: 1..%d, a critic: 1)", who,
                    r ? "the critic" : "the actor", n.O, kPgMaxOut);
@@ -703,7 +536,7 @@ int tg_policy_eval_weight_grad(const tg_policy_net* actor, const tg_policy_net* 
     const int64_t m = s->m;
     int tiles = 0;
     for (int r = 0; r < (critic ? 2 : 1); ++r) {
-        const PgNet& n = args.net[r];
+        const PolicyNet& n = args.net[r];
         float* gp = grads[r];
         for (int l = 0; l <= n.nh; ++l) {
             PgJob& jb = d.job[d.n_jobs++];
@@ -726,7 +559,7 @@ int tg_policy_eval_weight_grad(const tg_policy_net* actor, const tg_policy_net* 
     pg_slabs(m, d.slab_rows, d.n_slabs);
     d.partials = s->d_partials;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(policy_eval_weight_grad_kernel, dim3((unsigned)tiles, (unsigned)d.n_slabs), dim3(64 * kPgWaves), 0, st, d);
+    hipLaunchKernelGGL(policy_eval_weight_grad_kernel, dim3((unsigned)tiles, (unsigned)d.n_slabs), dim3(64 * kTileWaves), 0, st, d);
     TG_LAUNCH_CHECK(who);
     hipLaunchKernelGGL(policy_eval_weight_grad_finish_kernel, dim3((unsigned)tiles), dim3(256), 0, st, d);
     TG_LAUNCH_CHECK("tg_policy_eval_weight_grad(finish)");

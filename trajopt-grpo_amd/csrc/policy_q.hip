@@ -7,12 +7,12 @@
 //                y = rn_add(r, rn_mul(d, rn_sub(min(q1, q2), rn_mul(alpha, logp)))): one float32 rounding per operation (this file
 //                is built without packed fp32 instructions, as segment.hip is), alpha read from a device scalar at every call
 //
-// The machine is policy_step.hip's: a wave owns 16 rows; lane (j = lane & 15, g = lane >> 4) of accumulator tile t holds features
-// 16 t + 4 g + r of row j, register r of the four lane groups is the B operand of MFMA step (t, r) of the next layer, and the A
-// operands are 16-byte pieces of torch's own row-major nn.Linear.weight, moved by LDS-DMA into a ring of 3 slots of one 16-feature
-// block, two blocks in flight, a counted vmcnt wait and one raw s_barrier per block.  The tile routines are copies of
-// policy_step.hip's (copied, not shared through a header: that file and its kernel stay as they are), so the actor's bits are
-// tg_policy_step's.
+// The machine is policy_tile.hpp's 16-row tile (lane layout, operand order, ring and tables: there), the one policy_step.hip runs.
+// Constants, LDS reads, the net refusals and the launch are that header's.  The tile routines and the sampling head in pq_forward
+// are this file's OWN TEXT of the header's (tests/test_sac_target_gpu.py holds the actor's bits to tg_policy_step's): at B = 256 a
+// launch is one round of four workgroups, 21.7 us from a graph, and every form of this body built on the header's routines -- one at
+// a time or all together -- moved that by + 0.07 to + 0.4 us (and the 128-wide kernel by - 0.3 to + 0.3 us), reproducibly to
+// 0.02 us.  Whoever changes a routine there changes its twin here.
 //
 // What is new: ONE wave runs up to three nets back to back on its 16 rows -- the actor, Q1, Q2 -- and keeps what passes from one
 // to the next in registers.  A critic's input row is obs[row][0..S) followed by the A <= 4 action values, zero-padded to a multiple
@@ -42,21 +42,15 @@
 #include <stdlib.h>
 
 #include "tg_common.hpp"
-#include "mfma_ring.hpp"
-#include "act_f32.hpp"
+#include "policy_tile.hpp"
 
 namespace tg {
 
-constexpr int kPqLinear = TG_POLICY_MAX_LAYERS;         // Linear layers of a net: up to 5 hidden layers and the head
-constexpr int kPqWaves = 4;
-constexpr int kPqD = 3, kPqP = kPqD - 1;                // ring slots, blocks in flight
-constexpr int kPqMaxOut = 8;
-constexpr int kPqMaxIn = 32;
 constexpr int kPqNets = 3;                              // [0] the actor, [1] Q1, [2] Q2
 
 struct PqNet {
-    const float* w[kPqLinear];
-    const float* b[kPqLinear];
+    const float* w[kPolicyLinear];
+    const float* b[kPolicyLinear];
     int32_t K, nh, O;                                   // input width (the actor: S, a critic: S + A), hidden layers, head outputs
     int32_t tab;                                        // where the net's tables start behind the ring, in floats
 };
@@ -78,10 +72,6 @@ struct PqArgs {
     float* q1; float* q2; float* qmin;
 };
 
-__device__ static inline uint4 pq_lds_u4(const uint4* __restrict__ p) { return *p; }
-__device__ static inline float4 pq_lds_f4(const float* __restrict__ p) { return *reinterpret_cast<const float4*>(p); }
-__device__ static inline float pq_lds_f(const float* __restrict__ p) { return *p; }
-
 // A field of net n / layer l's pointers of net n.  A run-time index into a local copy of the tables puts it into scratch, and
 // uniform selects over the 36 pointer arguments keep all of them in scalar registers: the tables are read where the launch put
 // them, in the kernel-argument segment, by scalar loads at a workgroup-uniform index (n and l are workgroup-uniform).
@@ -94,7 +84,7 @@ __device__ static inline const float* pq_bias(const PqArgs& a, int n, int l) { r
 
 template <int H, int kAct>
 __device__ __attribute__((always_inline)) static inline void pq_forward(const PqArgs& a, uint4* lds) {
-    constexpr int NT = H / 16, KS = NT, WPW = kPqWaves, D = kPqD, P = kPqP, SLOT = KS * 64;
+    constexpr int NT = H / 16, KS = NT, WPW = kTileWaves, D = kTileD, P = kTileP, SLOT = KS * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, g = lane >> 4;
     const int first = a.first, last = a.last, S = a.S, A = a.A;
@@ -157,7 +147,7 @@ __device__ __attribute__((always_inline)) static inline void pq_forward(const Pq
         const float* Bh = pq_bias(a, n, nh);
         for (int q = tid; q < O * H; q += 64 * WPW) wh_s[q] = Wh[q];
         const float bv = Bh[tid < O ? tid : 0];
-        if (tid < kPqMaxOut) bh_s[tid] = tid < O ? bv : 0.f;
+        if (tid < kTileHeadBias) bh_s[tid] = tid < O ? bv : 0.f;
     }
     __syncthreads();                                                  // (the tables; drains the prologue's DMA too: once)
     // counted wait for the block about to be consumed: behind its DMA there are always the pieces of the P - 1 later blocks.  The
@@ -168,16 +158,16 @@ __device__ __attribute__((always_inline)) static inline void pq_forward(const Pq
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = act_f32<kAct>(v[r]);
     };
-    // one 16-feature output tile against a whole H-wide operand (policy_step.hip's tile_products, instruction for instruction)
+    // one 16-feature output tile against a whole H-wide operand (policy_tile.hpp's tile_products)
     auto tile_products = [&](const uint4* __restrict__ cur, const f32x4 (&xin)[NT], f32x4 acc) {
         const uint4* __restrict__ p = cur + lane;
         f32x4 acc1 = {0.f, 0.f, 0.f, 0.f};
-        uint4 wa = pq_lds_u4(p), wb = pq_lds_u4(p + 64);
+        uint4 wa = lds_u4(p), wb = lds_u4(p + 64);
         dma_next();
 #pragma unroll
         for (int t = 0; t < NT; t += 2) {
             uint4 na = wa, nb = wb;
-            if (t + 2 < NT) { na = pq_lds_u4(p + (t + 2) * 64); nb = pq_lds_u4(p + (t + 3) * 64); }
+            if (t + 2 < NT) { na = lds_u4(p + (t + 2) * 64); nb = lds_u4(p + (t + 3) * 64); }
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.x), xin[t][0], acc, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wb.x), xin[t + 1][0], acc1, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa.y), xin[t][1], acc, 0, 0, 0);
@@ -199,9 +189,9 @@ __device__ __attribute__((always_inline)) static inline void pq_forward(const Pq
 
         // ---- the observation part of every net's input row: lane group g holds obs[4 s + g] for the steps s (no load under a
         //      divergent branch); the action part: four registers, a' of the actor's epilogue below or the caller's rows ----
-        float xo[kPqMaxIn / 4];
+        float xo[kTileMaxIn / 4];
 #pragma unroll
-        for (int s = 0; s < kPqMaxIn / 4; ++s) {
+        for (int s = 0; s < kTileMaxIn / 4; ++s) {
             const int k = 4 * s + g;
             const bool in = k < S;
             const float v = a.obs[rowc * S + (in ? k : 0)];
@@ -228,20 +218,20 @@ __device__ __attribute__((always_inline)) static inline void pq_forward(const Pq
             f32x4 xin[NT], xout[NT];
 
             // ---- layer 0: input k = 4 s + g is obs[k] below S and action k - S behind it (zero while the actor runs, and past A) ----
-            float xr[kPqMaxIn / 4];
+            float xr[kTileMaxIn / 4];
 #pragma unroll
-            for (int s = 0; s < kPqMaxIn / 4; ++s) {
+            for (int s = 0; s < kTileMaxIn / 4; ++s) {
                 const int ka = 4 * s + g - S;
                 const float av = ka == 0 ? ak[0] : (ka == 1 ? ak[1] : (ka == 2 ? ak[2] : (ka == 3 ? ak[3] : 0.f)));
                 xr[s] = ka < 0 ? xo[s] : av;
             }
 #pragma unroll
             for (int mo = 0; mo < NT; ++mo) {
-                const float4 b4 = pq_lds_f4(bias_s + 16 * mo + 4 * g);
+                const float4 b4 = lds_f4(bias_s + 16 * mo + 4 * g);
                 f32x4 acc = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-                for (int s = 0; s < kPqMaxIn / 4; ++s)
-                    if (s < K4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pq_lds_f(w0_s + (mo * K4 + s) * 64 + lane), xr[s], acc, 0, 0, 0);
+                for (int s = 0; s < kTileMaxIn / 4; ++s)
+                    if (s < K4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(lds_f(w0_s + (mo * K4 + s) * 64 + lane), xr[s], acc, 0, 0, 0);
                 act4(acc);
                 xin[mo] = acc;
             }
@@ -255,7 +245,7 @@ __device__ __attribute__((always_inline)) static inline void pq_forward(const Pq
                     asm volatile("" ::: "memory");
                     const uint4* cur = ring + cur_slot * SLOT;
                     cur_slot = (cur_slot + 1 == D) ? 0 : cur_slot + 1;
-                    const float4 b4 = pq_lds_f4(bias_l + 16 * mo);
+                    const float4 b4 = lds_f4(bias_l + 16 * mo);
                     f32x4 acc = tile_products(cur, xin, f32x4{b4.x, b4.y, b4.z, b4.w});
                     act4(acc);
                     xout[mo] = acc;
@@ -268,7 +258,7 @@ __device__ __attribute__((always_inline)) static inline void pq_forward(const Pq
                 float s = 0.f;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
-                    const float4 w = pq_lds_f4(wh_s + k * H + 16 * t + 4 * g);
+                    const float4 w = lds_f4(wh_s + k * H + 16 * t + 4 * g);
                     s = fmaf(xin[t][0], w.x, s);
                     s = fmaf(xin[t][1], w.y, s);
                     s = fmaf(xin[t][2], w.z, s);
@@ -278,7 +268,7 @@ __device__ __attribute__((always_inline)) static inline void pq_forward(const Pq
                 const float p1 = __shfl_xor(s, 16, 64);
                 const float pair = (g & 1) ? p1 + s : s + p1;
                 const float p2 = __shfl_xor(pair, 32, 64);
-                return ((g & 2) ? p2 + pair : pair + p2) + pq_lds_f(bh_s + k);
+                return ((g & 2) ? p2 + pair : pair + p2) + lds_f(bh_s + k);
             };
             if (n != 0) {
                 const float qv = head_out(0);
@@ -350,39 +340,18 @@ __device__ __attribute__((always_inline)) static inline void pq_forward(const Pq
 // two 64-register activation sets and what passes between the nets: it is given the register file of one wave per SIMD, which is
 // all its LDS leaves room for at QuadPole's shapes anyway; the narrower bodies keep two workgroups per CU.
 template <int H>
-__global__ __launch_bounds__(64 * kPqWaves, H == 256 ? 1 : 2) void policy_q_kernel(PqArgs a) {
+__global__ __launch_bounds__(64 * kTileWaves, H == 256 ? 1 : 2) void policy_q_kernel(PqArgs a) {
     extern __shared__ uint4 lds[];
     if (a.act == TG_ACT_TANH) pq_forward<H, TG_ACT_TANH>(a, lds); else pq_forward<H, TG_ACT_RELU>(a, lds);
 }
 
-// what the entries refuse about one net; `outs`: the head outputs the caller expects; `pointers`: the launches (tg_policy_q_fits
-// reads the widths alone)
+// the shared verdict on one net, in this file's table form; `pointers`: the launches (tg_policy_q_fits reads the widths alone)
 static int pq_fill_net(const char* who, const char* name, const tg_policy_net* n, int outs, bool pointers, PqNet& out, int& H_out, int& act_out) {
-    TG_REQUIRE(n != nullptr, "%s: the %s table is null", who, name);
-    TG_REQUIRE(n->n_layers >= 2 && n->n_layers <= kPqLinear, "%s: %s has %d Linear layers, outside 2..%d (1..%d hidden layers)", who, name,
-               n->n_layers, kPqLinear, kPqLinear - 1);
-    TG_REQUIRE(n->activation == TG_ACT_RELU || n->activation == TG_ACT_TANH, "%s: %s has an unknown hidden activation %d", who, name,
-               n->activation);
-    const int L = n->n_layers, K = n->in_dim[0], H = n->out_dim[0], O = n->out_dim[L - 1];
-    TG_REQUIRE(K >= 1 && K <= kPqMaxIn, "%s: %s has input width %d outside [1, %d]", who, name, K, kPqMaxIn);
-    TG_REQUIRE(H == 64 || H == 128 || H == 256, "%s: %s has hidden width %d (64, 128 or 256)", who, name, H);
-    for (int l = 0; l < L; ++l) {
-        TG_REQUIRE((l == 0 || n->in_dim[l] == H) && (l == L - 1 || n->out_dim[l] == H), "%s: %s layer %d is %d -> %d, hidden width %d", who,
-                   name, l, n->in_dim[l], n->out_dim[l], H);
-        if (pointers) {
-            TG_REQUIRE(n->w[l] && n->b[l], "%s: %s layer %d has a null weight or bias", who, name, l);
-            // the H x H layers are read 16 bytes at a time, everything else as floats
-            const uintptr_t mask = (l > 0 && l < L - 1) ? 15 : 3;
-            TG_REQUIRE(((uintptr_t)n->w[l] & mask) == 0 && ((uintptr_t)n->b[l] & 3) == 0,
-                       "%s: %s layer %d has a misaligned weight or bias pointer", who, name, l);
-        }
-        out.w[l] = n->w[l];
-        out.b[l] = n->b[l];
-    }
-    for (int l = L; l < kPqLinear; ++l) { out.w[l] = n->w[0]; out.b[l] = n->b[0]; }
-    TG_REQUIRE(O == outs, "%s: %s has %d head outputs, %d expected", who, name, O, outs);
-    out.K = K; out.nh = L - 1; out.O = O;
-    H_out = H; act_out = n->activation;
+    PolicyNet c = {};
+    if (int rc = policy_net_check(who, name, n, outs, pointers, c)) return rc;
+    for (int l = 0; l < kPolicyLinear; ++l) { out.w[l] = c.w[l]; out.b[l] = c.b[l]; }
+    out.K = c.S; out.nh = c.nh; out.O = c.O;
+    H_out = c.H; act_out = c.act;
     return TG_OK;
 }
 
@@ -404,8 +373,8 @@ static int pq_plan(const char* who, const tg_policy_net* actor, const tg_policy_
         TG_REQUIRE(H[n] == H[f] && act[n] == act[f], "%s: %s is %d wide with activation %d, %s %d wide with %d: one kernel body runs "
                    "all nets of a launch", who, names[n], H[n], act[n], names[f], H[f], act[f]);
     if (actor) obs_dim = args.net[0].K;
-    TG_REQUIRE(obs_dim >= 1 && obs_dim + act_dim <= kPqMaxIn, "%s: %d observations + %d actions outside [2, %d]", who, obs_dim, act_dim,
-               kPqMaxIn);
+    TG_REQUIRE(obs_dim >= 1 && obs_dim + act_dim <= kTileMaxIn, "%s: %d observations + %d actions outside [2, %d]", who, obs_dim, act_dim,
+               kTileMaxIn);
     for (int n = 1; n <= args.last; ++n)
         TG_REQUIRE(args.net[n].K == obs_dim + act_dim, "%s: %s reads %d inputs, not %d observations + %d actions", who, names[n],
                    args.net[n].K, obs_dim, act_dim);
@@ -419,11 +388,11 @@ static int pq_plan(const char* who, const tg_policy_net* actor, const tg_policy_
             continue;
         }
         args.net[n].tab = (int32_t)floats;
-        floats += (size_t)NT * ((args.net[n].K + 3) / 4) * 64 + (size_t)(args.net[n].nh + args.net[n].O) * args.H + kPqMaxOut;
+        floats += (size_t)NT * ((args.net[n].K + 3) / 4) * 64 + (size_t)(args.net[n].nh + args.net[n].O) * args.H + kTileHeadBias;
     }
-    shmem = (size_t)kPqD * NT * 1024 + floats * 4;
+    shmem = (size_t)kTileD * NT * 1024 + floats * 4;
     TG_REQUIRE(shmem <= 160 * 1024, "%s: the ring (%d B) and the resident tables of %d nets (%zu B) need %zu B of LDS (> 160 KiB): "
-               "fewer hidden layers or inputs, or a narrower width", who, kPqD * NT * 1024, args.last - args.first + 1, floats * 4, shmem);
+               "fewer hidden layers or inputs, or a narrower width", who, kTileD * NT * 1024, args.last - args.first + 1, floats * 4, shmem);
     return TG_OK;
 }
 
@@ -431,12 +400,7 @@ static int pq_launch(const char* who, PqArgs& args, size_t shmem, int32_t grid_l
     static LdsOptIn opt_in[3];
     void (*const kernels[3])(PqArgs) = {policy_q_kernel<64>, policy_q_kernel<128>, policy_q_kernel<256>};
     const int v = args.H == 64 ? 0 : (args.H == 128 ? 1 : 2);
-    if (int rc = reserve_dynamic_lds((const void*)kernels[v], shmem, opt_in[v], who)) return rc;
-    const int64_t tiles = ceil_div(args.rows, 64);
-    const int64_t cap = grid_limit > 0 ? grid_limit : ((v == 2 || shmem > 80 * 1024) ? 1 : 2) * device_cus();
-    hipLaunchKernelGGL(kernels[v], dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(64 * kPqWaves), shmem, st, args);
-    TG_LAUNCH_CHECK(who);
-    return TG_OK;
+    return launch_row_tiles(who, kernels[v], opt_in[v], args, 1, shmem, grid_limit, (v == 2 || shmem > 80 * 1024) ? 1 : 2, st);
 }
 
 }  // namespace tg

@@ -144,7 +144,7 @@ class _Evaluate(torch.autograd.Function):
         with torch.cuda.device(da.device):
             N.check(da.lib.tg_policy_eval_forward(actor, critic, C.byref(s), N.stream_ptr(da.device)), "tg_policy_eval_forward")
         if any(ctx.needs_input_grad):
-            ctx.da, ctx.ws = da, ws
+            ctx.da, ctx.ws = da, ws                                            # (tests/test_policy_grad_gpu.py reads ws.mu off the node)
             ctx.save_for_backward(obs, action, log_std, *params)
         else:
             da._eval_pool[m].append(ws)                                        # (no backward will come for it)
