@@ -1505,6 +1505,74 @@ int  tg_policy_eval_forward(const tg_policy_net* actor, const tg_policy_net* cri
 int  tg_policy_eval_backward(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, void* stream);
 int  tg_policy_eval_weight_grad(const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, void* stream);
 
+/* ---- SAC's gradient steps: the reparameterised squashed-head draw and the Q critics, forward and backward (DeviceActor.rsample /
+ * .q_evaluate, csrc/policy_sac_grad.hip; additions to ABI 13) ----
+ * Nets are tg_policy_net as above, read where torch keeps them; a Q net reads obs_dim + act_dim <= 32 inputs.  One args struct serves
+ * all entries; an entry reads the fields its paragraph names.
+ * tg_policy_rsample_forward, one launch, per row i of d_obs [m][obs_dim]: tg_policy_step's TG_POLICY_HEAD_SQUASHED head of actor(obs_i)
+ *   at the draw d_calls[i] (which advances by one): d_action [m][act_dim] and d_logp [m] are tg_policy_step's bits; d_eps [m][act_dim] is
+ *   the draw; d_acts1 [hidden layers][m][H] the post-activations; d_head_rows [m][8] = {inside_k ? exp(ls_k) eps_k : 0} x 4,
+ *   {inside_k} x 4, with inside_k = 1 where the pre-clamp log-std lies in [log_std_lo, log_std_hi] and 0 elsewhere.
+ * tg_policy_rsample_backward, one launch: from d_g_action [m][act_dim], d_g_logp [m], d_action, d_head_rows and d_acts1, with
+ *   s = 1 - a^2: d_mu_k = g_a_k s + g_logp 2 a s / (s + 1e-6), d_ls_k = inside_k (d_mu_k exp(ls_k) eps_k - g_logp) (eps held constant),
+ *   as d_dout1 [m][8] = (d_mu.., d_ls.., zeros), and dZ of every hidden layer, d_dz1 [hidden layers][m][H].
+ * tg_policy_q_eval_forward, one launch: d_q1 [m] = Q1(d_obs_i, d_act_i) and with q2 d_q2 [m], bit for bit tg_policy_q_values';
+ *   d_acts1 / d_acts2 the critics' post-activations; d_xcat [m][obs_dim + act_dim] the rows [obs_i, act_i].
+ * tg_policy_q_eval_backward, one launch: from d_g_q1 / d_g_q2 [m] and the activations: d_dout1 / d_dout2 [m][4] (g_q, zero-padded),
+ *   d_dz1 / d_dz2, and -- unless d_g_act is NULL -- the critics' action gradients d_g_act [2][m][4] (zero-padded; without q2 the
+ *   second half is not written): d_g_act[c][i][k] = sum_o dZ_0[i][o] W_0[o][obs_dim + k] of critic c.
+ * tg_policy_sac_weight_grad, four launches, over the actor's layers (actor non-NULL, q1 and q2 NULL: d_obs, d_acts1, d_dz1, d_dout1 ->
+ *   d_grad1) or the critics' (actor NULL: d_xcat, d_acts*, d_dz*, d_dout* -> d_grad1, d_grad2), through d_partials (16-B aligned);
+ *   gradients in torch's layout as there.  First and hidden layers: tg_policy_eval_weight_grad's kernels.  Head layers (<= 8 outputs,
+ *   sums of cancelling terms over all rows): added in float64 on the vector unit over the same row slabs, in index order, rounded to
+ *   float32 once; their partials lie where the workspace entry counts the heads' tiles.  The same bits at every call.
+ * tg_policy_sac_grad_workspace: the sizes, in floats, for (nets, m): act_floats [3] and grad_floats [3] of the actor, Q1, Q2 (0 for a
+ *   NULL net), partial_floats [2] (d_partials of the actor's launch, of the critics').  Only widths are read.
+ * Refused (TG_ERR_ARG) before any launch: what tg_policy_step refuses, a net beyond 160 KiB of LDS, misaligned workspaces. */
+typedef struct tg_policy_sac_grad_args {
+    const float* d_obs;
+    const float* d_act;
+    float*       d_xcat;
+    float*       d_q1;
+    float*       d_q2;
+    float*       d_acts1;
+    float*       d_acts2;
+    float*       d_dz1;
+    float*       d_dz2;
+    float*       d_dout1;
+    float*       d_dout2;
+    const float* d_g_q1;
+    const float* d_g_q2;
+    float*       d_g_act;
+    uint32_t*    d_calls;
+    float*       d_action;
+    float*       d_logp;
+    float*       d_eps;
+    float*       d_head_rows;
+    const float* d_g_action;
+    const float* d_g_logp;
+    float*       d_grad1;
+    float*       d_grad2;
+    float*       d_partials;
+    int64_t      m;
+    int64_t      env_offset;
+    uint64_t     seed;
+    int32_t      obs_dim;
+    int32_t      act_dim;
+    int32_t      grid_limit;
+    int32_t      reserved;
+    float        log_std_lo;
+    float        log_std_hi;
+} tg_policy_sac_grad_args;
+int  tg_policy_sac_grad_workspace(const tg_policy_net* actor, const tg_policy_net* q1, const tg_policy_net* q2, int32_t act_dim, int64_t m,
+                                  int64_t* act_floats, int64_t* grad_floats, int64_t* partial_floats);
+int  tg_policy_rsample_forward(const tg_policy_net* actor, const tg_policy_sac_grad_args* s, void* stream);
+int  tg_policy_rsample_backward(const tg_policy_net* actor, const tg_policy_sac_grad_args* s, void* stream);
+int  tg_policy_q_eval_forward(const tg_policy_net* q1, const tg_policy_net* q2, const tg_policy_sac_grad_args* s, void* stream);
+int  tg_policy_q_eval_backward(const tg_policy_net* q1, const tg_policy_net* q2, const tg_policy_sac_grad_args* s, void* stream);
+int  tg_policy_sac_weight_grad(const tg_policy_net* actor, const tg_policy_net* q1, const tg_policy_net* q2,
+                               const tg_policy_sac_grad_args* s, void* stream);
+
 /* ---- Measurement instruments (bench.py's roofline object; nothing on the product path calls them) ----
  * tg_clock_probe_attach: the update's persistent kernels are bound by the package power limit, i.e. by the shader clock the chip
  *   can hold while they run -- a clock neither rocm-smi's sclk nor a kernel duration shows.  With a probe attached, thread 0 of

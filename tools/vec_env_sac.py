@@ -12,6 +12,10 @@ with disc = gamma^k where the window was closed by the clock or is still open, a
 
 --per samples by proportional priority instead (DeviceReplayBuffer(prioritized=True)): the critic loss is weighted by the importance
 weights and every sampled row's priority becomes the mean |TD error| of the two critics.
+
+--device-update (implies --device-actor) runs both gradient steps' nets in HIP too: a batch-sized tg.DeviceActor over the ONLINE
+critics gives the critic update's q1, q2 through q_evaluate(b_obs, b_act) and the actor update's through rsample(b_obs) and
+q_evaluate(b_obs, a_new, detach_params=True); torch.min, the losses, the alpha update, Adam and the Polyak step stay torch.
 """
 import argparse
 import math
@@ -72,6 +76,9 @@ def train(seed, args, dev):
     # ... and the whole target (a', both target critics, min, y) is ONE sac_target launch on the target nets where they are
     da_batch = tg.DeviceActor(actor.net, q_nets=(target.q1, target.q2), num_envs=args.batch, head="squashed", seed=seed + 1,
                               device=dev) if args.device_actor else None
+    # --device-update: the nets of both gradient steps as autograd nodes of a second batch-sized object over the ONLINE critics
+    da_upd = tg.DeviceActor(actor.net, q_nets=(critic.q1, critic.q2), num_envs=args.batch, head="squashed", seed=seed + 2,
+                            device=dev) if args.device_update else None
     obs, _ = venv.reset(seed=seed)
     buf.start(obs)
     ret_sum, ret_cnt = torch.zeros((), device=dev), torch.zeros((), device=dev)
@@ -94,7 +101,7 @@ def train(seed, args, dev):
                     else:
                         a2, logp2 = actor(b_next)
                         y = b_rew + b_disc * (torch.min(*target(b_next, a2)) - alpha * logp2)
-                q1, q2 = critic(b_obs, b_act)
+                q1, q2 = da_upd.q_evaluate(b_obs, b_act) if da_upd else critic(b_obs, b_act)
                 if args.per:                                             # importance-weighted, and the rows' new priorities
                     q_loss = (b_w[0] * ((q1 - y).pow(2) + (q2 - y).pow(2))).mean()
                     buf.update_priorities(b_idx, (0.5 * ((q1 - y).abs() + (q2 - y).abs())).detach())
@@ -103,8 +110,13 @@ def train(seed, args, dev):
                 opt_q.zero_grad(set_to_none=True)
                 q_loss.backward()
                 opt_q.step()
-                a_new, logp = actor(b_obs)
-                pi_loss = (alpha * logp - torch.min(*critic(b_obs, a_new))).mean()
+                if da_upd:
+                    a_new, logp = da_upd.rsample(b_obs)
+                    q_new = da_upd.q_evaluate(b_obs, a_new, detach_params=True)
+                else:
+                    a_new, logp = actor(b_obs)
+                    q_new = critic(b_obs, a_new)
+                pi_loss = (alpha * logp - torch.min(*q_new)).mean()
                 opt_pi.zero_grad(set_to_none=True)
                 pi_loss.backward()
                 opt_pi.step()
@@ -151,7 +163,9 @@ def main():
     ap.add_argument("--per-beta", type=float, default=0.4)
     ap.add_argument("--out", default=None, help="write the curves here: one line per seed and evaluation point")
     ap.add_argument("--device-actor", action="store_true", help="the no-grad actor calls (collection, target) on tg.DeviceActor")
+    ap.add_argument("--device-update", action="store_true", help="both gradient steps' nets on tg.DeviceActor.rsample / .q_evaluate too")
     args = ap.parse_args()
+    args.device_actor = args.device_actor or args.device_update
     if not torch.cuda.is_available():
         sys.exit("vec_env_sac.py needs an MI355X: DeviceVecEnv and DeviceReplayBuffer have no CPU fallback")
     dev = torch.device("cuda", 0)

@@ -208,6 +208,16 @@ class PolicyEvalArgs(C.Structure):
         "d_partials")] + [("m", C.c_int64), ("act_dim", C.c_int32), ("grid_limit", C.c_int32)]
 
 
+class PolicySacGradArgs(C.Structure):
+    """tg_policy_sac_grad_args (include/trajopt_grpo_hip.h)."""
+    _fields_ = [(name, C.c_void_p) for name in (
+        "d_obs", "d_act", "d_xcat", "d_q1", "d_q2", "d_acts1", "d_acts2", "d_dz1", "d_dz2", "d_dout1", "d_dout2", "d_g_q1", "d_g_q2",
+        "d_g_act", "d_calls", "d_action", "d_logp", "d_eps", "d_head_rows", "d_g_action", "d_g_logp", "d_grad1", "d_grad2",
+        "d_partials")] + [("m", C.c_int64), ("env_offset", C.c_int64), ("seed", C.c_uint64), ("obs_dim", C.c_int32),
+                          ("act_dim", C.c_int32), ("grid_limit", C.c_int32), ("reserved", C.c_int32), ("log_std_lo", C.c_float),
+                          ("log_std_hi", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/trajopt_grpo_hip.h declares
 _P, _I32, _I64, _U64, _F, _VP = C.POINTER, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -410,6 +420,12 @@ SIGNATURES = {
     "tg_policy_eval_forward": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyEvalArgs), _VP]),
     "tg_policy_eval_backward": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyEvalArgs), _VP]),
     "tg_policy_eval_weight_grad": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyEvalArgs), _VP]),
+    "tg_policy_sac_grad_workspace": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyNet), _I32, _I64, _P(_I64), _P(_I64), _P(_I64)]),
+    "tg_policy_rsample_forward": (C.c_int, [_P(PolicyNet), _P(PolicySacGradArgs), _VP]),
+    "tg_policy_rsample_backward": (C.c_int, [_P(PolicyNet), _P(PolicySacGradArgs), _VP]),
+    "tg_policy_q_eval_forward": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicySacGradArgs), _VP]),
+    "tg_policy_q_eval_backward": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicySacGradArgs), _VP]),
+    "tg_policy_sac_weight_grad": (C.c_int, [_P(PolicyNet), _P(PolicyNet), _P(PolicyNet), _P(PolicySacGradArgs), _VP]),
     "tg_clock_probe_attach": (C.c_int, [_I32, _VP]),
     "tg_mfma_sustained_probe_blocks": (C.c_int, []),
     "tg_mfma_sustained_probe_flops": (C.c_double, [_I32, _I32]),

@@ -11,6 +11,9 @@
 //   tg_policy_eval_weight_grad  dW_l = dZ_l^T A_{l-1}, db_l = column sums of dZ_l, for every layer of both nets in one launch, and a
 //                               fixed-order finishing pass.
 //
+// The backward-data body and the weight-gradient argument tables are policy_bwd.hpp's, shared with policy_sac_grad.hip (rsample,
+// q_evaluate), which reaches the weight-gradient kernels of this file through policy_weight_grad_launch.
+//
 // Backward data, the form chosen: the operand of step (t, r) is W_l[16 t + 4 g + r][16 ti + ii] -- a COLUMN piece of W_l.  The ring
 // runs over the same contiguous 16-output-row regions of W_l as the forward (block t = rows 16 t .. 16 t + 15, 16 H floats in one
 // run, so the DMA is a linear copy: lane `lane` of piece p moves bytes 1024 p + 16 lane), landed plain row-major in LDS, and all
@@ -34,14 +37,11 @@
 
 #include "tg_common.hpp"
 #include "policy_tile.hpp"
+#include "policy_bwd.hpp"
 
 namespace tg {
 
 constexpr int kPgMaxOut = 4;                            // gaussian head: <= 4 means; a critic: 1
-constexpr int kPgMaxSlabs = 32;
-constexpr int kPgTile = 64, kPgLd = 80;                 // weight gradient: tile edge, LDS row stride (floats)
-constexpr int kPgPartial = kPgTile * kPgTile + kPgTile; // floats of one partial: the tile and its bias sums
-constexpr int kPgJobs = 2 * kPolicyLinear;
 
 struct PgArgs {
     PolicyNet net[2];               // [0] the actor, [1] the critic
@@ -58,9 +58,7 @@ struct PgArgs {
     float* std_rows;                // [rows][4], zero-padded
 };
 
-static size_t pg_bwd_lds_bytes(const PolicyNet& n) {
-    return (size_t)kTileD * (16 * n.H + 64) * 4 + (size_t)n.O * n.H * 4;
-}
+static size_t pg_bwd_lds_bytes(const PolicyNet& n) { return bwd_lds_bytes(n); }
 
 // ---- 1. forward: the shared tile forward, the activation stores as its on_tile, the epilogue on a given action ------------------------
 template <int H, int kAct>
@@ -143,56 +141,16 @@ __device__ __attribute__((always_inline)) static inline void pg_forward(const Pg
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// ---- 2. backward data ----------------------------------------------------------------------------------------------------------------
+// ---- 2. backward data: policy_bwd.hpp's body under the gaussian head's / the critic's head gradient -----------------------------------
 template <int H, int kAct>
 __device__ __attribute__((always_inline)) static inline void pg_backward(const PgArgs& a, const int nh, const int O, const int role,
                                                                          uint4* lds) {
-    // a 16-output-row block of W_l: four 4-row groups of 4 H floats (H / 64 DMA pieces each), 16 floats of padding behind each
-    constexpr int NT = H / 16, WPW = kTileWaves, D = kTileD, P = kTileP, PPG = H / 64, GROUP = 4 * H + 16, SLOT = 4 * GROUP;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 15, g = lane >> 4;
-    const int n_hh = nh - 1;
     const bool critic = role == 1;
-    float* ring = reinterpret_cast<float*>(lds);
-    float* wh_s = ring + D * SLOT;                                    // [O][H]
-    const int64_t rows = a.rows;
-    const int64_t n_rounds = (rows + 63) / 64;
-    const float* acts = critic ? a.acts[1] : a.acts[0];
-    float* dzb = critic ? a.dz[1] : a.dz[0];
     float* doutb = critic ? a.dout[1] : a.dout[0];
-
-    // ---- the ring: block (l, t) = rows 16 t .. + 15 of W_l, l from the top H x H layer down to layer 1 ----
-    int pre_l = n_hh, pre_t = 0, pre_slot = 0, cur_slot = 0;
-    auto dma_next = [&]() {
-        const float* src = net_weight(a, critic, pre_l) + (16 * pre_t * H + 4 * lane);
-        float* slot = ring + pre_slot * SLOT;
+    auto head_grad = [&](int64_t row, int64_t rowc, bool store, float (&d_out)[kPgMaxOut]) {
+        float d_std[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int q = 0; q < NT / WPW; ++q) {
-            const int piece = q * WPW + wave;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(src + 256 * piece),
-                                             (lds_void*)(slot + (piece / PPG) * GROUP + (piece % PPG) * 256), 16, 0, 0);
-        }
-        pre_t = (pre_t + 1 == NT) ? 0 : pre_t + 1;
-        pre_l = pre_t != 0 ? pre_l : (pre_l == 1 ? n_hh : pre_l - 1);
-        pre_slot = (pre_slot + 1 == D) ? 0 : pre_slot + 1;
-    };
-    if (n_hh > 0) {
-#pragma unroll
-        for (int b = 0; b < P; ++b) dma_next();
-    }
-    {
-        const float* Wh = net_weight(a, critic, nh);
-        for (int q = tid; q < O * H; q += 64 * WPW) wh_s[q] = Wh[q];
-    }
-    __syncthreads();                                                  // (the head; drains the prologue's DMA too: once)
-    constexpr int kWait = (P - 1) * (NT / WPW);
-
-    for (int64_t round = blockIdx.x; round < n_rounds; round += gridDim.x) {
-        const int64_t row = round * 64 + wave * 16 + j;
-        const bool valid = row < rows;
-        const int64_t rowc = valid ? row : rows - 1;
-        // ---- the head's gradient, per row (every lane group holds the same bits, lane group 0 stores) ----
-        float d_out[4] = {0.f, 0.f, 0.f, 0.f}, d_std[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < kPgMaxOut; ++k) d_out[k] = 0.f;
         if (critic) {
             d_out[0] = a.g_value[rowc];
         } else {
@@ -207,66 +165,13 @@ __device__ __attribute__((always_inline)) static inline void pg_backward(const P
                 }
             }
         }
-        if (valid && g == 0) {
+        if (store) {
             *reinterpret_cast<float4*>(doutb + row * 4) = float4{d_out[0], d_out[1], d_out[2], d_out[3]};
             if (!critic) *reinterpret_cast<float4*>(a.std_rows + row * 4) = float4{d_std[0], d_std[1], d_std[2], d_std[3]};
         }
-        // dZ_l = dA * act'(acts[l]) from the stored activation, kept as the next product's B operand and stored [m][H]
-        f32x4 dz[NT];
-        auto mask_store = [&](int l, const f32x4 (&dA)[NT]) {
-            const int64_t at = ((int64_t)l * rows + rowc) * H + 4 * g;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float4 av = *reinterpret_cast<const float4*>(acts + at + 16 * t);
-                const float h[4] = {av.x, av.y, av.z, av.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if constexpr (kAct == TG_ACT_TANH) dz[t][r] = dA[t][r] * fmaf(-h[r], h[r], 1.0f);
-                    else dz[t][r] = h[r] > 0.f ? dA[t][r] : 0.f;
-                }
-                if (valid) *reinterpret_cast<float4*>(dzb + at + 16 * t) = float4{dz[t][0], dz[t][1], dz[t][2], dz[t][3]};
-            }
-        };
-        // ---- dA_top = d_out . W_head on the vector unit ----
-        f32x4 acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < kPgMaxOut; ++k) {
-                if (k < O) {
-                    const float4 w = lds_f4(wh_s + k * H + 16 * t + 4 * g);
-                    acc[t][0] = fmaf(d_out[k], w.x, acc[t][0]);
-                    acc[t][1] = fmaf(d_out[k], w.y, acc[t][1]);
-                    acc[t][2] = fmaf(d_out[k], w.z, acc[t][2]);
-                    acc[t][3] = fmaf(d_out[k], w.w, acc[t][3]);
-                }
-            }
-        }
-        mask_store(n_hh, acc);
-        // ---- H x H layers from the top down: dA_{l-1}[row][16 ti + ii] = sum_o dZ_l[row][o] W_l[o][16 ti + ii] ----
-        for (int l = n_hh; l >= 1; --l) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                TG_RING_WAIT(kWait)
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                const float* __restrict__ p = ring + cur_slot * SLOT + g * GROUP + j;
-                cur_slot = (cur_slot + 1 == D) ? 0 : cur_slot + 1;
-                dma_next();                                           // (refills the slot of the block before this one)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                    for (int ti = 0; ti < NT; ++ti)
-                        acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(lds_f(p + r * H + 16 * ti), dz[t][r], acc[ti], 0, 0, 0);
-                }
-            }
-            mask_store(l - 1, acc);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    backward_tiles<H, kAct, kPgMaxOut>(a, critic, nh, O, critic ? a.acts[1] : a.acts[0], critic ? a.dz[1] : a.dz[0], lds, head_grad,
+                                       [](const f32x4 (&)[H / 16], int64_t, bool) {});
 }
 
 __global__ __launch_bounds__(64 * kTileWaves, 2) void policy_eval_forward_kernel(PgArgs a) {
@@ -292,21 +197,7 @@ __global__ __launch_bounds__(64 * kTileWaves, 2) void policy_eval_backward_kerne
 }
 
 // ---- 3. weight gradient --------------------------------------------------------------------------------------------------------------
-// One Linear layer of one net: dW [No][Ni] = dz^T a over the rows, db [No] = column sums of dz.  `w_dz` / `w_a`: the operands' stored
-// widths (the head's d_out rows are zero-padded to 4); `vec_*`: 16-byte loads (an aligned base, a leading dimension and a width that
-// are multiples of 4), else floats one by one (the observations).
-struct PgJob {
-    const float* dz; const float* a;
-    float* gw; float* gb;
-    int32_t ld_dz, w_dz, ld_a, w_a, No, Ni, tiles_i, tile_base, vec_dz, vec_a;
-};
-struct PgDwArgs {
-    PgJob job[kPgJobs];
-    int32_t n_jobs, n_slabs;
-    int64_t rows, slab_rows;
-    float* partials;                // [tiles][n_slabs][kPgPartial]
-};
-
+// (PgJob / PgDwArgs: policy_bwd.hpp)
 __device__ static inline int pg_job_of(const PgDwArgs& a, int tile) {
     int jb = 0;
     for (int q = 1; q < kPgJobs; ++q) jb = (q < a.n_jobs && tile >= a.job[q].tile_base) ? q : jb;
@@ -417,19 +308,6 @@ static int pg_fill_net(const char* who, const char* name, const tg_policy_net* n
     return TG_OK;
 }
 
-static int64_t pg_grad_floats(const PolicyNet& n) {
-    return (int64_t)n.H * (n.S + 1) + (int64_t)(n.nh - 1) * n.H * (n.H + 1) + (int64_t)n.O * (n.H + 1);
-}
-static int64_t pg_tiles(const PolicyNet& n) {
-    const int64_t th = n.H / kPgTile;
-    return th + (n.nh - 1) * th * th + th;                           // first layer (S <= 32: one column tile), H x H layers, head
-}
-static void pg_slabs(int64_t m, int64_t& slab_rows, int32_t& n_slabs) {
-    const int64_t chunks = ceil_div(m, kPgTile), per = ceil_div(chunks, kPgMaxSlabs);
-    slab_rows = per * kPgTile;
-    n_slabs = (int32_t)ceil_div(chunks, per);
-}
-
 // the nets and the tensors every launch needs; `forward`: the three results too
 static int pg_plan(const char* who, const tg_policy_net* actor, const tg_policy_net* critic, const tg_policy_eval_args* s, bool forward,
                    PgArgs& args) {
@@ -474,6 +352,18 @@ static int pg_launch(const char* who, K kernel, LdsOptIn& opt_in, const PgArgs& 
         shmem = b > shmem ? b : shmem;
     }
     return launch_row_tiles(who, kernel, opt_in, args, nets, shmem, grid_limit, 2, st);
+}
+
+int policy_weight_grad_launch(const char* who, PgDwArgs& d, int tiles, int64_t m, float* partials, hipStream_t st) {
+    d.rows = m;
+    pg_slabs(m, d.slab_rows, d.n_slabs);
+    d.partials = partials;
+    hipLaunchKernelGGL(policy_eval_weight_grad_kernel, dim3((unsigned)tiles, (unsigned)d.n_slabs), dim3(64 * kTileWaves), 0, st, d);
+    TG_LAUNCH_CHECK(who);
+    hipLaunchKernelGGL(policy_eval_weight_grad_finish_kernel, dim3((unsigned)tiles), dim3(256), 0, st, d);
+    hipError_t e = hipGetLastError();                                 // (told apart from a failure of the launch before it)
+    if (e != hipSuccess) return set_error(TG_ERR_HIP, "%s(finish): %s", who, hipGetErrorString(e));
+    return TG_OK;
 }
 
 }  // namespace tg
@@ -533,37 +423,10 @@ int tg_policy_eval_weight_grad(const tg_policy_net* actor, const tg_policy_net* 
     TG_REQUIRE(s->d_grad_actor && s->d_partials && (critic == nullptr || s->d_grad_critic), "%s: null gradient or partials pointer", who);
     PgDwArgs d = {};
     float* grads[2] = {s->d_grad_actor, s->d_grad_critic};
-    const int64_t m = s->m;
     int tiles = 0;
-    for (int r = 0; r < (critic ? 2 : 1); ++r) {
-        const PolicyNet& n = args.net[r];
-        float* gp = grads[r];
-        for (int l = 0; l <= n.nh; ++l) {
-            PgJob& jb = d.job[d.n_jobs++];
-            const bool first = l == 0, head = l == n.nh;
-            jb.dz = head ? args.dout[r] : args.dz[r] + (int64_t)l * m * n.H;
-            jb.ld_dz = jb.w_dz = head ? 4 : n.H;
-            jb.No = head ? n.O : n.H;
-            jb.a = first ? args.x : args.acts[r] + (int64_t)(l - 1) * m * n.H;
-            jb.ld_a = jb.w_a = jb.Ni = first ? n.S : n.H;
-            jb.vec_dz = 1;
-            jb.vec_a = !first || (n.S % 4 == 0 && ((uintptr_t)args.x & 15) == 0);
-            jb.gw = gp; jb.gb = gp + (int64_t)jb.No * jb.Ni;
-            gp = jb.gb + jb.No;
-            jb.tiles_i = (int32_t)ceil_div(jb.Ni, kPgTile);
-            jb.tile_base = tiles;
-            tiles += (int)ceil_div(jb.No, kPgTile) * jb.tiles_i;
-        }
-    }
-    d.rows = m;
-    pg_slabs(m, d.slab_rows, d.n_slabs);
-    d.partials = s->d_partials;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(policy_eval_weight_grad_kernel, dim3((unsigned)tiles, (unsigned)d.n_slabs), dim3(64 * kTileWaves), 0, st, d);
-    TG_LAUNCH_CHECK(who);
-    hipLaunchKernelGGL(policy_eval_weight_grad_finish_kernel, dim3((unsigned)tiles), dim3(256), 0, st, d);
-    TG_LAUNCH_CHECK("tg_policy_eval_weight_grad(finish)");
-    return TG_OK;
+    for (int r = 0; r < (critic ? 2 : 1); ++r)
+        pg_add_net_jobs(d, tiles, args.net[r], s->m, args.x, args.acts[r], args.dz[r], args.dout[r], 4, grads[r]);
+    return policy_weight_grad_launch(who, d, tiles, s->m, s->d_partials, (hipStream_t)stream);
 }
 
 }  // extern "C"

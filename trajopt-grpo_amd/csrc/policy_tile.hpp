@@ -228,6 +228,56 @@ __device__ __attribute__((always_inline)) static inline float head_out(const flo
     return ((g & 2) ? p2 + pair : pair + p2) + lds_f(bh_s + k);
 }
 
+// The whole forward of a workgroup on one net of `a` (`second`: a.net[1]) with K inputs: the ring's prefetch cursor, the resident
+// tables, and per round of 64 rows
+//   inputs(row, rowc, valid, xr)          fills the lane's first-layer operands: xr[s] = input 4 s + g of its row, zero past K
+//   on_tile(row, valid, l, mo, acc)       sees every finished hidden tile (the activation stores)
+//   epilogue(row, rowc, valid, xin, tb)   the head and what follows it, on the top hidden layer's tiles
+// rowc is the row clamped into the batch (no load under a branch), valid says whether the lane's row exists.
+template <int H, int kAct, typename Args, typename Inputs, typename OnTile, typename Epilogue>
+__device__ __attribute__((always_inline)) static inline void forward_tiles(const Args& a, const bool second, const int K, const int nh,
+                                                                           const int O, uint4* lds, Inputs&& inputs, OnTile&& on_tile,
+                                                                           Epilogue&& epilogue) {
+    constexpr int NT = H / 16, D = kTileD, P = kTileP, SLOT = NT * 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 15, g = lane >> 4;
+    const int n_hh = nh - 1, K4 = (K + 3) >> 2;
+    uint4* ring = lds;
+    const NetTables<H> tb(reinterpret_cast<float*>(ring + D * SLOT), K4, nh, O);
+    const int64_t rows = a.rows;
+    const int64_t n_rounds = (rows + 63) / 64;
+
+    int pre_l = 1, pre_mo = 0, pre_slot = 0, cur_slot = 0;
+    auto dma_next = [&]() {
+        ring_dma_rows<NT>(net_weight(a, second, pre_l) + ((16 * pre_mo + j) * H + 4 * g), ring + pre_slot * SLOT, wave);
+        pre_mo = (pre_mo + 1 == NT) ? 0 : pre_mo + 1;
+        pre_l = pre_mo != 0 ? pre_l : (pre_l == n_hh ? 1 : pre_l + 1);
+        pre_slot = (pre_slot + 1 == D) ? 0 : pre_slot + 1;
+    };
+    if (n_hh > 0) {
+#pragma unroll
+        for (int b = 0; b < P; ++b) dma_next();
+    }
+    stage_net_tables<H>(net_weight(a, second, 0), K, nh, O, [&](int l) { return net_bias(a, second, l); }, net_weight(a, second, nh),
+                        net_bias(a, second, nh), tb.w0, tid);
+    __syncthreads();                                                  // (the tables; drains the prologue's DMA too: once)
+
+    for (int64_t round = blockIdx.x; round < n_rounds; round += gridDim.x) {
+        const int64_t row = round * 64 + wave * 16 + j;
+        const bool valid = row < rows;
+        const int64_t rowc = valid ? row : rows - 1;
+        f32x4 xin[NT];
+        float xr[kTileMaxIn / 4];
+        inputs(row, rowc, valid, xr);
+        auto tile = [&](int l, int mo, const f32x4& v) { on_tile(row, valid, l, mo, v); };
+        first_layer<H, kAct>(tb.w0, tb.bias, K4, lane, xr, xin, tile);
+        hidden_layers<H, kAct>(ring, cur_slot, tb.bias, n_hh, lane, xin, dma_next, tile);
+        epilogue(row, rowc, valid, xin, tb);
+    }
+    // the ring's prefetches of a round that never came: let them land before the workgroup's LDS goes away
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 // ---- sampling and density: the rollout kernels' float32 Box-Muller (fused_rollout_f32.hip) on one Philox draw, and the terms of
 //      logp, one float32 rounding per operation -----------------------------------------------------------------------------------
 __device__ static inline void box_muller_eps(const uint32_t (&rnd)[4], const int A, float (&eps)[4]) {

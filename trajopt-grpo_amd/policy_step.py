@@ -19,8 +19,13 @@ actor and then both critics on its 16 rows and hands a' over in registers.
 rows as ONE autograd node over log_std and the nets' own parameters, forward and backward in HIP, so any torch loss of the three
 fills `.grad` and any torch.optim steps the nets.
 
-Not built: gradients to observations or actions, through the squashed head, q_values() or sac_target() (SAC's critic / actor updates
-stay torch autograd), graph capture of evaluate()'s backward, bf16, more than 4 actions, LayerNorm or mixed activations, a trunk shared by actor and critic, Q nets whose width or
+`rsample(obs)` and `q_evaluate(obs, act)` are SAC's two gradient steps (csrc/policy_sac_grad.hip): act()'s squashed-head draw as an
+autograd node over the actor's parameters (the reparameterised path, eps held constant), and q_values() as a node over the Q nets'
+parameters and the action.  The critic update is q_evaluate(b_obs, b_act); the actor update is a, logp = rsample(b_obs) followed by
+q_evaluate(b_obs, a, detach_params=True); torch.min, the losses and torch.optim stay the caller's.
+
+Not built: gradients to observations, through evaluate()'s action, sac_target() or the gaussian head's draw, graph capture of a
+backward, bf16, more than 4 actions, LayerNorm or mixed activations, a trunk shared by actor and critic, Q nets whose width or
 activation differs from the actor's, more than two critics, a target for TD3 / DDPG heads.  There is no silent torch fallback: a net
 outside the kernel's set raises ValueError with supports()'s reason, and the caller's own torch code is the fallback.
 """
@@ -126,6 +131,17 @@ def _q_refusal(actor_net, actor_shape, head, q_nets):
     return None
 
 
+def _grad_views(flat, params):
+    """The parameters' gradients as views of `flat` (one buffer per net: weight [out][in], bias [out], layer by layer)."""
+    grads, at, net = [], 0, 0
+    for p in params:
+        if at == flat[net].numel():
+            at, net = 0, net + 1
+        grads.append(flat[net][at:at + p.numel()].view(p.shape))
+        at += p.numel()
+    return grads
+
+
 class _Evaluate(torch.autograd.Function):
     """DeviceActor.evaluate as ONE autograd node over log_std and every weight / bias of both nets (csrc/policy_grad.hip): forward
     is tg_policy_eval_forward; backward is tg_policy_eval_backward, tg_policy_eval_weight_grad and tg_log_std_grad, and returns the
@@ -172,13 +188,104 @@ class _Evaluate(torch.autograd.Function):
             K.log_std_grad(ws.std_rows, da.A, g_std)
         ctx.ws = None
         da._eval_pool[m].append(ws)
-        grads, at, net = [], 0, 0
-        for k, p in enumerate(params):                                         # per net: weight [out][in], bias [out], layer by layer
-            if at == flat[net].numel():
-                at, net = 0, net + 1
-            grads.append(flat[net][at:at + p.numel()].view(p.shape))
-            at += p.numel()
-        return (None, None, None, g_std, *grads)
+        return (None, None, None, g_std, *_grad_views(flat, params))
+
+
+def _consumed(ctx, what):
+    if ctx.ws is None:
+        raise RuntimeError(f"DeviceActor: this {what}() was already backpropagated (its activations are gone)")
+    return ctx.da, ctx.ws
+
+
+class _RSample(torch.autograd.Function):
+    """DeviceActor.rsample as ONE autograd node over the actor's weights and biases (csrc/policy_sac_grad.hip): forward is
+    tg_policy_rsample_forward; backward is tg_policy_rsample_backward and the actor's tg_policy_sac_weight_grad."""
+
+    @staticmethod
+    def forward(ctx, da, grad_mode, obs, *params):
+        n, dev = da.num_envs, da.device
+        ws = da._sac_workspace("actor", n)
+        action, logp = torch.empty(n, da.A, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+        s = da._sac_args(ws, obs)
+        s.d_action, s.d_logp, s.d_eps, s.d_calls = action.data_ptr(), logp.data_ptr(), da.eps.data_ptr(), da._calls.data_ptr()
+        actor = da._table(da.actor_net, "the actor")
+        with torch.cuda.device(dev):
+            N.check(da.lib.tg_policy_rsample_forward(C.byref(actor), C.byref(s), N.stream_ptr(dev)), "tg_policy_rsample_forward")
+        if grad_mode and any(ctx.needs_input_grad):                            # (needs_input_grad alone ignores torch.no_grad())
+            ctx.da, ctx.ws = da, ws
+            ctx.save_for_backward(obs, action, *params)
+        else:
+            da._sac_pool[("actor", n)].append(ws)                              # (no backward will come for it)
+        return action, logp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_action, g_logp):
+        da, ws = _consumed(ctx, "rsample")
+        obs, action, *params = ctx.saved_tensors
+        n, dev = ws.m, da.device
+        g_action = torch.zeros(n, da.A, dtype=torch.float32, device=dev) if g_action is None else g_action.contiguous()
+        g_logp = torch.zeros(n, dtype=torch.float32, device=dev) if g_logp is None else g_logp.contiguous()
+        flat = [torch.empty(ws.grad_floats[0], dtype=torch.float32, device=dev)]
+        s = da._sac_args(ws, obs)
+        s.d_action, s.d_g_action, s.d_g_logp, s.d_grad1 = action.data_ptr(), g_action.data_ptr(), g_logp.data_ptr(), flat[0].data_ptr()
+        actor = da._table(da.actor_net, "the actor")
+        with torch.cuda.device(dev):
+            N.check(da.lib.tg_policy_rsample_backward(C.byref(actor), C.byref(s), N.stream_ptr(dev)), "tg_policy_rsample_backward")
+            N.check(da.lib.tg_policy_sac_weight_grad(C.byref(actor), None, None, C.byref(s), N.stream_ptr(dev)), "tg_policy_sac_weight_grad")
+        ctx.ws = None
+        da._sac_pool[("actor", n)].append(ws)
+        return (None, None, None, *_grad_views(flat, params))
+
+
+class _QEvaluate(torch.autograd.Function):
+    """DeviceActor.q_evaluate as ONE autograd node over the action and every weight / bias of the Q nets (csrc/policy_sac_grad.hip):
+    forward is tg_policy_q_eval_forward; backward is tg_policy_q_eval_backward -- with the action gradient only if the action needs
+    one -- and, only if a Q parameter needs one, the critics' tg_policy_sac_weight_grad."""
+
+    @staticmethod
+    def forward(ctx, da, grad_mode, obs, act, *params):
+        m, dev, twin = obs.shape[0], da.device, len(da.q_nets) == 2
+        ws = da._sac_workspace("q", m)
+        out = [torch.empty(m, dtype=torch.float32, device=dev) for _ in da.q_nets]
+        s = da._sac_args(ws, obs)
+        s.d_act, s.d_q1, s.d_q2 = act.data_ptr(), out[0].data_ptr(), (out[1].data_ptr() if twin else 0)
+        q = [da._table(net, f"Q{k + 1}") for k, net in enumerate(da.q_nets)]
+        with torch.cuda.device(dev):
+            N.check(da.lib.tg_policy_q_eval_forward(C.byref(q[0]), C.byref(q[1]) if twin else None, C.byref(s), N.stream_ptr(dev)),
+                    "tg_policy_q_eval_forward")
+        if grad_mode and any(ctx.needs_input_grad):                            # (needs_input_grad alone ignores torch.no_grad())
+            ctx.da, ctx.ws = da, ws
+            ctx.save_for_backward(obs, *params)
+        else:
+            da._sac_pool[("q", m)].append(ws)                                  # (no backward will come for it)
+        return tuple(out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *g):
+        da, ws = _consumed(ctx, "q_evaluate")
+        obs, *params = ctx.saved_tensors
+        m, dev, twin = ws.m, da.device, len(da.q_nets) == 2
+        need_act, need_params = ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
+        g = [torch.zeros(m, dtype=torch.float32, device=dev) if t is None else t.contiguous() for t in g]
+        g_act = torch.empty(2, m, 4, dtype=torch.float32, device=dev) if need_act else None
+        s = da._sac_args(ws, obs)
+        s.d_g_q1, s.d_g_q2, s.d_g_act = g[0].data_ptr(), (g[1].data_ptr() if twin else 0), N.ptr(g_act)
+        q = [da._table(net, f"Q{k + 1}") for k, net in enumerate(da.q_nets)]
+        q1, q2 = C.byref(q[0]), (C.byref(q[1]) if twin else None)
+        flat = None
+        with torch.cuda.device(dev):
+            N.check(da.lib.tg_policy_q_eval_backward(q1, q2, C.byref(s), N.stream_ptr(dev)), "tg_policy_q_eval_backward")
+            if need_params:
+                flat = [torch.empty(k, dtype=torch.float32, device=dev) for k in ws.grad_floats[1:1 + len(q)]]
+                s.d_grad1, s.d_grad2 = flat[0].data_ptr(), (flat[1].data_ptr() if twin else 0)
+                N.check(da.lib.tg_policy_sac_weight_grad(None, q1, q2, C.byref(s), N.stream_ptr(dev)), "tg_policy_sac_weight_grad")
+        ctx.ws = None
+        da._sac_pool[("q", m)].append(ws)
+        if need_act:                                                           # the two critics' buffers added: one torch add
+            g_act = (g_act[0] + g_act[1] if twin else g_act[0])[:, :da.A]
+        return (None, None, None, g_act, *(_grad_views(flat, params) if need_params else [None] * len(params)))
 
 
 class DeviceActor:
@@ -250,6 +357,9 @@ class DeviceActor:
         self._values_out = {}
         self._q_out = {}
         self._eval_pool = {}                                                   # row count -> free evaluate() workspaces
+        self._sac_pool = {}                                                    # ("actor" | "q", row count) -> free rsample() / q_evaluate() workspaces
+        if head == "squashed":
+            self.eps = torch.zeros(n, A, dtype=f32, device=dev)                # the draw of the last rsample()
         if len(self.q_nets) == 2:                                             # sac_target's by-products and its owned alpha
             self.q1, self.q2, self.qmin, self.y, self._alpha = (torch.zeros(k, dtype=f32, device=dev) for k in (n, n, n, n, 1))
         self._grid_limit = 0           # 0: two workgroups per CU; a test sets it to force further trips of a workgroup's row loop
@@ -447,6 +557,67 @@ class DeviceActor:
         actor = self._table(self.actor_net, "the actor")
         critic = self._table(self.critic_net, "the critic") if self.critic_net is not None else None
         return C.byref(actor), (C.byref(critic) if critic is not None else None), (actor, critic)
+
+    # ---- SAC's gradient steps: the reparameterised draw and the Q critics as autograd nodes ------------------------------------------
+    def rsample(self, obs):
+        """-> (action [n][A], logp [n]) of `obs` [n][S], each with a grad_fn: the slot's next draw under the squashed head (with or
+        without `q_nets`: the node reads the actor alone) -- what
+        act(obs) would have given, bit for bit, from the same counters, which advance -- as ONE autograd node over the actor's
+        parameters along a = tanh(mu + exp(ls) eps), eps held constant, through the log-std clamp (derivative 1 on the closed interval
+        `log_std_bounds`, 0 outside) and the squash correction.  `self.eps` [n][A] holds the draw (overwritten by the next rsample()).
+        Fresh result tensors at every call; the workspace rules are evaluate()'s.  No gradient to obs (ValueError if it requires one)."""
+        if self.head != "squashed":
+            raise ValueError(f"DeviceActor: the head is {self.head!r}; rsample() is built for the squashed head")
+        if isinstance(obs, torch.Tensor) and obs.requires_grad:
+            raise ValueError("DeviceActor: rsample() builds no gradient to obs (it requires one)")
+        obs = self._rows(obs, "obs", self.num_envs)
+        params = [p for m in _modules(self.actor_net)[0::2] for p in (m.weight, m.bias)]
+        return _RSample.apply(self, torch.is_grad_enabled(), obs, *params)
+
+    def q_evaluate(self, obs, act, detach_params: bool = False):
+        """-> (q1 [m], q2 [m] or None) of any rows `obs` [m][S], `act` [m][A], each with a grad_fn: q_values()' bits as ONE autograd node
+        over every weight and bias of the Q nets and -- if `act` requires a gradient (rsample()'s action) -- over `act`.  With
+        `detach_params` the Q parameters stay out of the node (SAC's actor update: no weight gradient is launched for the critics);
+        the same launch is skipped whenever no Q parameter needs a gradient, and the action gradient whenever `act` needs none.
+        No gradient to obs (ValueError if it requires one)."""
+        if not self.q_nets:
+            raise ValueError("DeviceActor: q_evaluate() needs q_nets")
+        if isinstance(obs, torch.Tensor) and obs.requires_grad:
+            raise ValueError("DeviceActor: q_evaluate() builds no gradient to obs (it requires one)")
+        obs = self._rows(obs, "obs", None)
+        self._rows(act, "act", obs.shape[0], self.A)
+        params = [] if detach_params else [p for net in self.q_nets for m in _modules(net)[0::2] for p in (m.weight, m.bias)]
+        out = _QEvaluate.apply(self, torch.is_grad_enabled(), obs, act if act.is_contiguous() else act.contiguous(), *params)
+        return (out[0], out[1] if len(self.q_nets) == 2 else None)
+
+    def _sac_workspace(self, kind, m):
+        """A free workspace of rsample() (`kind` "actor") or q_evaluate() ("q") for m rows: activations, dZ, head gradients, the
+        weight-gradient partials, and the gradient sizes (actor, Q1, Q2)."""
+        pool = self._sac_pool.setdefault((kind, m), [])
+        if pool:
+            return pool.pop()
+        acts, grads, partial = (C.c_int64 * 3)(), (C.c_int64 * 3)(), (C.c_int64 * 2)()
+        nets = [self.actor_net] if kind == "actor" else [None, *self.q_nets]
+        tables = [_widths(net) if net is not None else None for net in nets] + [None] * (3 - len(nets))
+        if self.lib.tg_policy_sac_grad_workspace(*(C.byref(t) if t is not None else None for t in tables), self.A, m, acts, grads, partial):
+            raise ValueError("DeviceActor: rsample() / q_evaluate() do not take these nets: " + self.lib.tg_last_error().decode("utf-8", "replace"))
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        own = [0] if kind == "actor" else [1, 2][:len(self.q_nets)]
+        ws = types.SimpleNamespace(m=m, kind=kind, grad_floats=tuple(grads), partials=new(partial[kind == "q"]),
+                                   acts=[new(acts[k]) for k in own], dz=[new(acts[k]) for k in own],
+                                   dout=[new(m, 8 if kind == "actor" else 4) for _ in own],
+                                   head_rows=new(m, 8) if kind == "actor" else None, xcat=new(m, self.S + self.A) if kind == "q" else None)
+        return ws
+
+    def _sac_args(self, ws, obs):
+        s = N.PolicySacGradArgs()
+        s.d_obs, s.m, s.obs_dim, s.act_dim, s.grid_limit = obs.data_ptr(), ws.m, self.S, self.A, self._grid_limit
+        s.env_offset, s.seed = self.env_offset, self.seed
+        s.log_std_lo, s.log_std_hi = self.log_std_bounds
+        two = lambda ts: (N.ptr(ts[0]), N.ptr(ts[1]) if len(ts) == 2 else None)
+        (s.d_acts1, s.d_acts2), (s.d_dz1, s.d_dz2), (s.d_dout1, s.d_dout2) = two(ws.acts), two(ws.dz), two(ws.dout)
+        s.d_xcat, s.d_head_rows, s.d_partials = N.ptr(ws.xcat), N.ptr(ws.head_rows), N.ptr(ws.partials)
+        return s
 
     @property
     def calls(self) -> torch.Tensor:
